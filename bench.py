@@ -17,6 +17,7 @@ import argparse
 import json
 import math
 import os
+import subprocess
 import sys
 import time
 
@@ -81,6 +82,9 @@ def parse():
                     help="steps of the run that times every step on its own (step_ms_spread): at least --steps; 0 = --steps (the profiling passes)")
     ap.add_argument("--path-only", action="store_true",
                     help="only the timed hot path and its roofline (no ICP / tracking / host-buffer legs): what the profiling passes run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the vertex and normal maps "
+                         "(no-hit NaNs as 0, with a per-pixel validity mask each), and (one volume) a fixed seeded sample of the volume's distances and weights")
     a = ap.parse_args()
     if a.grid is None:
         a.grid = 1024 if a.workload == "config4" else 512
@@ -120,12 +124,13 @@ def main():
             s_.bind(("127.0.0.1", 0))
             port = s_.getsockname()[1]
         os.dup2(json_fd, 1)
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         if os.environ.get("BENCH_LAUNCH_DRYRUN") == "1":     # (tests/test_bench_launcher.py: the command, not the run)
-            print(json.dumps([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
+            print(json.dumps(cmd))
             return
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        # a child process, not an exec: this process has loaded the HIP runtime with torch, and is never replaced
+        raise SystemExit(subprocess.call(cmd))
     if world != args.gpus:
         raise SystemExit("bench.py --gpus %d inside a world of %d ranks" % (args.gpus, world))
     # Debug aid for a 1-GPU box: TSDF_BENCH_SHARE_GPU=1 puts every rank on device 0 and uses gloo for the
@@ -391,6 +396,8 @@ def main():
     checksum = float(torch.nan_to_num(vert_dev.double(), nan=0.0).sum().item())   # the picture of the last timed frame
     last_vertices = vert_dev.clone()
     bits_v, bits_n = run_bits[-1]
+    if args.dump_outputs and rank == 0:      # (before the legs below reuse the maps and the volume)
+        dump_outputs(args.dump_outputs, vert_dev, norm_dev, None if sharded else vol)
 
     trace("timed region done")
     # ---- untimed replays of the SAME K frames: (1) every stage and every launch of the dominant kernels bracketed with HIP
@@ -701,6 +708,30 @@ def main():
         if exch is not None:
             exch.close()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 21      # voxels of the volume sample --dump-outputs writes (8 MB per array)
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(d, vert_dev, norm_dev, vol):
+    """--dump-outputs: the last timed step's vertex and normal maps and, for one volume, its distances and weights at a fixed
+    seeded sample of voxels (the same voxels for the same grid) -- 26 MB in all at 512^3.  Every value written is finite: a map's
+    NaNs (no hit, no normal) become 0 and its pixels are told apart by <map>_valid (1 = all three components finite, 0 = not)."""
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for name, valid_name, m in (("vertices", "vertex_valid", vert_dev), ("normals", "normal_valid", norm_dev)):
+        a = m.cpu().numpy()
+        ok = np.isfinite(a)
+        out[name] = np.where(ok, a, np.float32(0.0))
+        out[valid_name] = ok.all(axis=1)
+    if vol is not None:
+        n = vol.resident_voxels()
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+        out["distance_sample"] = vol.get_distance_data()[pick]
+        out["weight_sample"] = vol.get_weight_data()[pick]
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def host_api_time(vol, bil, frames, cams, last):

@@ -65,6 +65,32 @@ def test_few_steps_and_no_sampled_events_still_give_strict_json():
     assert d["steps"] == 3 and d["value"] > 0 and len(d["ms_per_step_runs"]) == 1
 
 
+def test_dumped_outputs_are_the_last_timed_step_and_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs DIR: what the timed path computed in its last step -- the vertex and normal maps with a validity mask each (a
+    pixel without a hit or a normal is 0 in the map and 0 in the mask), and a fixed seeded sample of the volume's distances and
+    weights -- as float32 .npy files of finite values, at most 64 MB in all; a second run with the same arguments writes the same bits."""
+    import numpy as np
+    args = ("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-parity", "--path-only", "--repeats", "1", "--spread-steps", "0")
+    runs = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        d = run_bench(*args, "--dump-outputs", str(out))
+        runs.append((d, {f[:-len(".npy")]: np.load(str(out / f)) for f in os.listdir(out)}))
+    d, a = runs[0]
+    assert sorted(a) == ["distance_sample", "normal_valid", "normals", "vertex_valid", "vertices", "weight_sample"]
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["vertices"].shape == a["normals"].shape == (640 * 480, 3) and a["distance_sample"].shape == a["weight_sample"].shape
+    vv, nv = a["vertex_valid"], a["normal_valid"]
+    assert vv.shape == nv.shape == (640 * 480,) and set(np.unique(vv)) <= {0.0, 1.0} and set(np.unique(nv)) <= {0.0, 1.0}
+    assert vv.sum() > 1000 and nv.sum() > 1000
+    assert not a["vertices"][vv == 0].any() and not a["normals"][nv == 0].any()
+    # the maps are the line's picture: the sum of its finite vertex coordinates
+    assert math.isclose(float(a["vertices"].astype(np.float64).sum()), d["last_frame_vertex_checksum"], rel_tol=1e-9)
+    assert (a["weight_sample"] > 0).any()
+    for name, x in runs[1][1].items():
+        assert np.array_equal(x.view(np.uint32), a[name].view(np.uint32)), name
+
+
 def test_more_ranks_than_gpus_is_refused_with_a_reason():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None); env.pop("TSDF_BENCH_SHARE_GPU", None)

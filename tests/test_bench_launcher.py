@@ -1,5 +1,5 @@
 """bench.py --gpus N started plainly (no torchrun, WORLD_SIZE unset) becomes its own launcher (round 4).
-CPU check of the command it would exec; the run itself is covered on the GPU box by tests/test_bench_contract.py."""
+CPU check of the command it would start as its child; the run itself is covered on the GPU box by tests/test_bench_contract.py."""
 import json
 import os
 import subprocess

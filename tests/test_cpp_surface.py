@@ -3,8 +3,8 @@ TUMDataLoader / extract_surface ...) on the GPU.
 
   * build/test_surface (tests/cpp/test_surface.cpp) drives the classes the way the reference's kinfu.cpp does and
     dumps raw results; they must be bit-identical to what the oracle computes from the same inputs.
-  * where $TSDF_REF_BUILD/linkcheck/bin/kinfu exists (the REFERENCE's unchanged src/Tools/kinfu.cpp compiled against this
-    repo's headers by tools/linkcheck.sh -- outside the tree, so only on a machine that has both the reference and a GPU), it is
+  * where oracle/_ref/linkcheck/kinfu exists (the REFERENCE's unchanged src/Tools/kinfu.cpp compiled against this repo's
+    headers by oracle/linkcheck.sh, where the reference is present; it travels with the tree like the rest of oracle/_ref), it is
     run end to end on a synthetic TUM-layout directory.
 """
 import os
@@ -18,8 +18,8 @@ from tsdf_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "build", "test_surface")
-REF_BUILD = os.environ.get("TSDF_REF_BUILD") or "/tmp/tsdf_ref_build"
-KINFU = os.path.join(REF_BUILD, "linkcheck", "bin", "kinfu")
+LINKCHECK = os.path.join(ROOT, "oracle", "_ref", "linkcheck")
+KINFU = os.path.join(LINKCHECK, "kinfu")
 
 
 def test_headers_of_the_class_surface_compile_standalone():
@@ -146,7 +146,7 @@ def test_cpp_surface_matches_the_oracle(tmp_path, oracle):
 @pytest.mark.gpu
 def test_reference_kinfu_runs_end_to_end_against_this_library(tmp_path):
     if not os.path.exists(KINFU):
-        pytest.skip("linkcheck/bin/kinfu not present (compiled reference code stays in the build container)")
+        pytest.skip("oracle/_ref/linkcheck/kinfu not present (built where the reference is present)")
     d = tmp_path / "tum"
     synth.write_tum_directory(str(d), 3, seed=0x5EED0002)
     r = subprocess.run([KINFU, "-m", "3", "-d", str(d)], capture_output=True, text=True, timeout=300)
@@ -162,11 +162,11 @@ def test_reference_kinfu_runs_end_to_end_against_this_library(tmp_path):
 
 @pytest.mark.gpu
 def test_reference_tsdf_icp_runs_against_this_library(tmp_path):
-    """src/Tools/tsdf_icp.cpp of the reference, compiled unchanged (tools/linkcheck.sh): loads a .tsdf volume and a depth
+    """src/Tools/tsdf_icp.cpp of the reference, compiled unchanged (oracle/linkcheck.sh): loads a .tsdf volume and a depth
     PNG, renders the volume from the pose stored in it and runs ICPOdometry between the two images."""
-    tool = os.path.join(REF_BUILD, "linkcheck", "bin", "tsdf_icp")
+    tool = os.path.join(LINKCHECK, "tsdf_icp")
     if not os.path.exists(tool) or not os.path.exists(BIN):
-        pytest.skip("linkcheck/bin/tsdf_icp not present (compiled reference code stays in the build container)")
+        pytest.skip("oracle/_ref/linkcheck/tsdf_icp not present (built where the reference is present)")
     # a volume file written by the class surface (test_surface saves <out>/volume.tsdf) ...
     depth, cam = synth.depth_frame(2, 30, seed=0x5EED0001)
     depth.tofile(str(tmp_path / "depth.u16"))
