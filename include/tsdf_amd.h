@@ -210,9 +210,11 @@ int tsdf_volume_set_timing(tsdf_volume *volume, int enabled);
 int tsdf_volume_kernel_time(tsdf_volume *volume, int which, uint32_t *launches, float *average_ms);
 
 /* Diagnostics: when enabled, integrate also counts the voxels whose weight changed (U in the
- * roofline model).  Costs one atomic per wave; leave off when timing. */
+ * roofline model) and the distances it stored -- fewer: a distance whose bits the blend leaves as
+ * they are is not written back.  Costs two atomics per wave; leave off when timing. */
 int tsdf_volume_set_counting(tsdf_volume *volume, int enabled);
 int tsdf_volume_last_updated_voxels(const tsdf_volume *volume, uint64_t *count);
+int tsdf_volume_last_distance_stores(const tsdf_volume *volume, uint64_t *count);
 
 /* ---- raycast ---------------------------------------------------------------------------- */
 /* Replaces GPURaycaster::raycast = get_vertices/process_ray + compute_normals

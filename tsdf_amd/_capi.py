@@ -100,6 +100,7 @@ _SIGS = {
     "tsdf_volume_kernel_time": (_i, [_vp, _i, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "tsdf_volume_set_counting": (_i, [_vp, _i]),
     "tsdf_volume_last_updated_voxels": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_volume_last_distance_stores": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_raycast": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_raycast_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_normals_device": (_i, [_u32, _u32, _vp, _vp, _vp]),

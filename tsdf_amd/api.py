@@ -266,6 +266,12 @@ class TSDFVolume:
         check(lib.tsdf_volume_last_updated_voxels(self._h, C.byref(c)))
         return int(c.value)
 
+    def last_distance_stores(self):
+        """Distances the last integrate with counting on wrote (<= last_updated_voxels(): unchanged bits are not stored)."""
+        c = C.c_uint64()
+        check(lib.tsdf_volume_last_distance_stores(self._h, C.byref(c)))
+        return int(c.value)
+
     # ---- raycast (TSDFVolume.hpp:260): forwards to GPURaycaster like TSDFVolume.cu:1054-1058
     def raycast(self, width, height, camera):
         return GPURaycaster(width, height).raycast(self, camera)

@@ -196,6 +196,8 @@ constexpr int kBrickGrow = 2;
 constexpr int kReachLevels = 5;     // largest block: 2^(5-1) = 16 bricks = 64 voxels per side
 constexpr int kSlabSkip = 32;       // voxels: granularity at which a slab passes regions it cannot own
 constexpr int kSlabSkipShift = 5;
+constexpr int kCounterSlots = 5;    // tsdf_volume::counter_dev
+constexpr int kCounterStores = 4;   // its slot for the distances a counted integrate stored
 struct OccGrid {
     uint8_t *fine;
     uint8_t *cell;
@@ -355,8 +357,9 @@ struct tsdf_volume {
     int reach_dirty; // 1 = `fine` changed since `reach` was computed
     uint16_t *occ_bits;              // 16 summary bits per brick, kept between rebuilds (volume.hip)
     uint8_t *occ_rim_bits;           // 8 more: which 2^3-voxel octants hold a voxel that is not flat (read for boundary bricks only)
-    // A rebuild reads only the distances integrate may have written since the previous one: integrate_kernel marks its brick
-    // in `touched` (one byte per integrate brick, index order), the scan skips the others and their summary bits stand.
+    // A rebuild reads only the distances integrate has written since the previous one: integrate_kernel marks its brick in
+    // `touched` (one byte per integrate brick, index order) when it stored a distance there -- a store that would write back
+    // the same bits is skipped -- the scan skips the others and their summary bits stand.
     // occ_scan_all = 1: the next rebuild reads everything (first rebuild, clear, set_distance_data, mark_dirty, new truncation).
     uint8_t *touched;
     uint32_t touched_nx, touched_ny, touched_nz;
@@ -386,7 +389,7 @@ struct tsdf_volume {
     std::vector<hipEvent_t> *tev[3];  // [0] integrate_kernel, [1] process_ray_kernel, [2] process_ray_tail_kernel: start/stop pairs
     // diagnostics
     int counting;
-    unsigned long long *counter_dev;  // [0] = updated voxels, [1] = samples, [2] = hits
+    unsigned long long *counter_dev;  // [0] = updated voxels, [1] = samples, [2] = hits, [kCounterStores] = distances stored
     uint64_t last_updated;
     size_t resident_voxels() const { return (size_t)g.X * g.Y * (g.z_store_end - g.z_store_begin); }
 };

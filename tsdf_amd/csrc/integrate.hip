@@ -336,13 +336,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
     const float fwidth = (float)width, fheight = (float)height;
     // see round_quotients: thr = 4e-7 * (max(width, height) + 2); the float just below 1/2 - thr
     const float round_near_half = __uint_as_float(__float_as_uint(0.5f - 4.0e-7f * ((float)max(width, height) + 2.0f)) - 1u);   // (positive: one ulp down)
-    uint32_t updated = 0;
+    uint32_t updated = 0, stores = 0;   // (COUNT: voxels updated, distances stored)
 
     for (uint32_t i = blockIdx.x; i < n_active; i += gridDim.x) {
         const unsigned long long dbg_t0 = (!COUNT && counter) ? wall_clock64() : 0ull;   // (diagnostics, TSDF_DEBUG_BRICKS=3: per-brick clocks)
         const uint32_t b = DEFORM ? i : list[i];
         const uint32_t bx = b % bg.nx, by = (b / bg.nx) % bg.ny, bz = b / (bg.nx * bg.ny);
-        if (tid == 0) touched[b] = 1;   // for the next occupancy rebuild: this brick's distances may change (volume.hip)
         const uint32_t vx = bx * kTileX + threadIdx.x;
         const uint32_t vy = by * kTileY + threadIdx.y;
         const uint32_t z0 = g.z_store_begin + bz * kChunkZ;
@@ -418,6 +417,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
         float r1 = 0.f, r2 = 0.f, r3 = 0.f, r4 = 0.f;
         float r4_[kBatchZ] = {};
         uint32_t low_lo = 0, low_hi = 0;   // bit o: my voxel of plane z0 + o got a distance that is not safely positive
+        bool wrote = false;                 // my lane stored a distance of this brick
         // Voxels a brick at the grid boundary depends on are held to the stricter test of those bricks (flat, not just positive:
         // OccGrid).  Both tests are "not (d > lo) or d > hi" with per-lane bounds: (tau, +inf) inside, (the float below flat_lo,
         // flat_hi) for lanes in the x / y part of the rim zone; the planes of the z part are picked per batch of planes below.
@@ -541,7 +541,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
                     const float new_distance = ((pd_[j] * pw_[j]) + (tsdf_[j] * 1.0f)) / new_weight;
                     const size_t pb = brick_base + plane * (size_t)(zb - z0 + j);
                     (weight + pb)[lane_off] = new_weight;
-                    (dist + pb)[lane_off] = new_distance;
+                    // only a distance whose bits change is stored (integrate_packed.hip: free space keeps +trunc at most counts)
+                    if (__float_as_uint(new_distance) != __float_as_uint(pd_[j])) {
+                        (dist + pb)[lane_off] = new_distance;
+                        wrote = true;
+                        if (COUNT) stores++;
+                    }
                     if (!(new_distance > lo) || new_distance > hi) {   // not safely positive (rim zone: not flat): remember the plane, the bricks are marked when this one is done
                         const uint32_t o_ = zb + j - z0;
                         if (o_ < 32u) low_lo |= 1u << o_; else low_hi |= 1u << (o_ - 32u);
@@ -567,12 +572,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
         }
         if (__any((low_lo | low_hi) != 0u))
             mark_low_voxels(occ, low_lo, low_hi, (bx * kTileX) >> kBrickShift, __builtin_amdgcn_readfirstlane(vy), z0, z0, z1 - 1u, threadIdx.x);
+        // for the next occupancy rebuild (volume.hip): this brick's distances have changed (a brick with every store skipped is not)
+        if (__any(wrote) && threadIdx.x == 0) touched[b] = 1;
         if (!COUNT && counter && tid == 0) { counter[2 * i] = dbg_t0; counter[2 * i + 1] = wall_clock64(); }
     }
     if (COUNT) {
         // wave reduction then one atomic per wave
         for (int o = 32; o > 0; o >>= 1) updated += __shfl_down(updated, o);
+        for (int o = 32; o > 0; o >>= 1) stores += __shfl_down(stores, o);
         if ((threadIdx.x & 63u) == 0 && updated) atomicAdd(counter, (unsigned long long)updated);
+        if ((threadIdx.x & 63u) == 0 && stores) atomicAdd(counter + kCounterStores, (unsigned long long)stores);
     }
 }
 
@@ -668,7 +677,10 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     if (!v->plane_const) TSDF_HIP(hipMalloc((void **)&v->plane_const, n_plane_const * 4 * sizeof(float)), "plane constants alloc");
     float4 *plane_const = reinterpret_cast<float4 *>(v->plane_const);
 
-    if (v->counting && phase == kIntBoth) TSDF_HIP(hipMemsetAsync(v->counter_dev, 0, sizeof(unsigned long long), v->stream), "reset counter");
+    if (v->counting && phase == kIntBoth) {
+        TSDF_HIP(hipMemsetAsync(v->counter_dev, 0, sizeof(unsigned long long), v->stream), "reset counter");
+        TSDF_HIP(hipMemsetAsync(v->counter_dev + kCounterStores, 0, sizeof(unsigned long long), v->stream), "reset counter");
+    }
     if (prepared) {
         v->brick_count_side = 1u - v->brick_count_side;
     } else if (!v->nodes) {

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
     // see round_quotients (integrate.hip): thr = 4e-7 * (max(width, height) + 2); the float just below 1/2 - thr
     const float round_near_half = __uint_as_float(__float_as_uint(0.5f - 4.0e-7f * ((float)max(width, height) + 2.0f)) - 1u);
     const uint32_t planes_resident = g.z_store_end - g.z_store_begin;
-    uint32_t updated = 0;
+    uint32_t updated = 0, stores = 0;   // (COUNT: voxels updated, distances stored)
 
     // One brick per workgroup (launch_integrate sizes the grid to the whole brick grid; workgroups beyond the list leave at once).  No loop
     // over bricks: what the prologue needs of the kernel's arguments is dead once the planes are walked, which the scalar register
@@ -117,7 +117,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
 #else
         const uint32_t bx = co.x & 0xffffu, by = co.x >> 16, bz = co.y;
 #endif
-        if (tid == 0) touched[b] = 1;   // for the next occupancy rebuild: this brick's distances may change (volume.hip)
         const uint32_t vx = bx * kTileX + threadIdx.x;
         const uint32_t vy = by * kTileY + threadIdx.y;
         const uint32_t z0 = g.z_store_begin + bz * kChunkZ;
@@ -214,6 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
         float r3 = ip.m31 * cx + ip.m32 * cy;
         if (vx >= g.X) r3 = NAN;   // lanes past the grid's x edge stay in (the marks at the end are made by the wave's first lanes): NaN depth, no update
         uint32_t low_lo = 0, low_hi = 0;   // bit o: my voxel of plane z0 + o got a distance that is not safely positive
+        bool wrote = false;                 // my lane stored a distance (a lane mask: scalar registers)
         // (see integrate_kernel: voxels a boundary brick depends on are held to the stricter "flat" test)
         const bool rim_xy = occ.in_rim_zone(vx, occ.nbx) || occ.in_rim_zone(vy, occ.nby);
         const float flat_lo_open = __uint_as_float(__float_as_uint(occ.flat_lo) - 1u);
@@ -324,7 +324,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
                     const float new_weight = prior_weight + 1.0f;                                                   // :375-376
                     const float new_distance = div_by_count((pd_[j] * prior_weight) + (tsdf_[j] * 1.0f), new_weight);   // :381
                     nw_[w] += 1u << s;   // (the caller has made room: weights.hip, weights_make_room)
-                    if (true DIAG_NOSTORE_D) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, new_distance), drsrc, lane_off4, dsoff(o + j), 0);
+                    // The distance is stored only when its bits change: a voxel that has only seen free space holds +trunc, and the
+                    // blend (D w + trunc) / (w + 1) gives +trunc back bit for bit at most counts (it moves at 6, 7, 9, 12, 22, 25, ...),
+                    // so most stores in front of the surface would write what memory holds.  Bits, not floats: -0 / +0 and NaN
+                    // payloads stay as the blend leaves them.
+                    if (__float_as_uint(new_distance) != __float_as_uint(pd_[j]) DIAG_NOSTORE_D) {
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(new_distance), drsrc, lane_off4, dsoff(o + j), 0);
+                        wrote = true;
+                        if (COUNT) stores++;
+                    }
                     if (!(new_distance > lo) || new_distance > hi) {   // not safely positive (rim zone: not flat): remember the plane
                         const uint32_t o_ = o + j;
                         if (o_ < 32u) low_lo |= 1u << o_; else low_hi |= 1u << (o_ - 32u);
@@ -367,10 +375,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
         if (staged) walk(std::true_type{}); else walk(std::false_type{});
         if (__any((low_lo | low_hi) != 0u))
             mark_low_voxels(occ, low_lo, low_hi, (bx * kTileX) >> kBrickShift, __builtin_amdgcn_readfirstlane(vy), z0, z0, z1 - 1u, threadIdx.x);
+        // for the next occupancy rebuild (volume.hip): this brick's distances have changed.  A brick whose every store was skipped
+        // holds the bits it held, so the summary bits of its last scan still describe it and it is left unmarked.
+        if (__any(wrote) && threadIdx.x == 0) touched[b] = 1;
     }
     if (COUNT) {   // (waves that left early counted nothing)
         for (int o = 32; o > 0; o >>= 1) updated += __shfl_down(updated, o);
+        for (int o = 32; o > 0; o >>= 1) stores += __shfl_down(stores, o);
         if ((threadIdx.x & 63u) == 0 && updated) atomicAdd(counter, (unsigned long long)updated);
+        if ((threadIdx.x & 63u) == 0 && stores) atomicAdd(counter + kCounterStores, (unsigned long long)stores);
     }
 }
 

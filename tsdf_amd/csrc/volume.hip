@@ -882,8 +882,8 @@ int tsdf_volume_create_slab(uint32_t sx, uint32_t sy, uint32_t sz, float px, flo
     if (e == hipSuccess) e = hipMalloc((void **)&v->occ.reach, v->occ.fine_count());
     size_t bytes = v->resident_voxels() * sizeof(float);
     if (e == hipSuccess) e = hipMalloc((void **)&v->dist, bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&v->counter_dev, 4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(v->counter_dev, 0, 4 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&v->counter_dev, kCounterSlots * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(v->counter_dev, 0, kCounterSlots * sizeof(unsigned long long));
     if (e != hipSuccess) {
         int rc = hip_fail(e, "Couldn't allocate space for TSDF data");
         tsdf_volume_destroy(v);
@@ -1381,6 +1381,15 @@ int tsdf_volume_last_updated_voxels(const tsdf_volume *v, uint64_t *count) {
     TSDF_REQUIRE(v && count, "null argument");
     unsigned long long c = 0;
     TSDF_HIP(hipMemcpyAsync(&c, v->counter_dev, sizeof(c), hipMemcpyDeviceToHost, v->stream), "read counter");
+    TSDF_HIP(hipStreamSynchronize(v->stream), "read counter");
+    *count = c;
+    return TSDF_OK;
+}
+
+int tsdf_volume_last_distance_stores(const tsdf_volume *v, uint64_t *count) {
+    TSDF_REQUIRE(v && count, "null argument");
+    unsigned long long c = 0;
+    TSDF_HIP(hipMemcpyAsync(&c, v->counter_dev + tsdf::kCounterStores, sizeof(c), hipMemcpyDeviceToHost, v->stream), "read counter");
     TSDF_HIP(hipStreamSynchronize(v->stream), "read counter");
     *count = c;
     return TSDF_OK;
