@@ -216,6 +216,48 @@ int tsdf_volume_set_counting(tsdf_volume *volume, int enabled);
 int tsdf_volume_last_updated_voxels(const tsdf_volume *volume, uint64_t *count);
 int tsdf_volume_last_distance_stores(const tsdf_volume *volume, uint64_t *count);
 
+/* ---- colour fusion (no reference counterpart: the reference allocates a uchar3 colour per voxel, src/include/TSDFVolume.hpp:290-293,
+ * that none of its kernels writes) --------------------------------------------------------------------------------------------- */
+/* Opt-in per volume.  A volume that never enables colour behaves exactly as without this group: no allocation, no launch.
+ *   Storage: one dword per voxel {r, g, b, n} -- r in bits 0-7, g 8-15, b 16-23, n = colour observations (saturating at 255) in
+ *     bits 24-31 -- x fastest like the distances; allocated and zeroed by tsdf_volume_enable_colour(v, 1) (4 bytes a voxel: 512 MiB
+ *     at 512^3), freed by (v, 0), zeroed by tsdf_volume_clear.
+ *   Integrate: tsdf_integrate_colour updates distances, weights, occupancy and counters with exactly the bits of tsdf_integrate for
+ *     the same depth and camera, then updates the colour of every voxel that update touched (in the frustum, depth > 0,
+ *     sdf >= -trunc: src/TSDF/TSDFVolume.cu:337-366) whose sdf is also <= +trunc, from the pixel (u, v) whose depth it used.  rgb
+ *     is 8-bit interleaved RGB, width x height x 3, REGISTERED to the depth image (same camera, same size: TUM's depth frames are
+ *     registered to its RGB frames).  Per channel, with c the pixel's value, in uint32 arithmetic:
+ *         new = (old * n + c + ((n + 1) >> 1)) / (n + 1);     n' = min(n + 1, 255)
+ *     (with n capped, later observations blend at 1/256).  Voxels with sdf > trunc (free space) keep their colour.
+ *   Sampling: a world point p (mm) takes voxel i = (int)floorf(((p - offset) - offset_at_clear) / voxel_size) per axis, in fp32 in
+ *     that order -- the cell whose centre as integrate forms it is nearest -- and reads that voxel's {r, g, b}; (0, 0, 0) for a NaN
+ *     coordinate, an index outside the grid, or a voxel with n == 0.
+ *   Refused (TSDF_ERR_INVALID, with a message): enabling colour on a Z-slab volume (tsdf_volume_create_slab); colour integrate on a
+ *     volume whose deformation nodes are explicit (tsdf_volume_deformation / tsdf_volume_set_deformation); colour integrate,
+ *     sampling or data access on a volume without colour enabled.
+ *   Out of scope: colour in tsdf_pipeline_step, the tracker and kinfu_stream; slab (multi-GPU) colour; trilinear colour
+ *     interpolation; colour with explicit deformation nodes; RGB cameras with intrinsics or extrinsics of their own. */
+int tsdf_volume_enable_colour(tsdf_volume *volume, int enabled);   /* 1: allocate zeroed (kept if already enabled), 0: free */
+int tsdf_volume_colour_enabled(const tsdf_volume *volume, int *enabled);
+int tsdf_volume_colours(const tsdf_volume *volume, uint32_t **device_ptr);   /* the device array, one dword per resident voxel */
+/* Blocking copies of every resident voxel's dword. */
+int tsdf_volume_get_colour_data(const tsdf_volume *volume, uint32_t *host);
+int tsdf_volume_set_colour_data(tsdf_volume *volume, const uint32_t *host);
+/* tsdf_integrate / tsdf_integrate_device with the colour pass behind the integrate kernel (same stream, same brick list). */
+int tsdf_integrate_colour(tsdf_volume *volume, const uint16_t *host_depth, const uint8_t *host_rgb, uint32_t width, uint32_t height,
+                          const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]);
+int tsdf_integrate_colour_device(tsdf_volume *volume, const uint16_t *device_depth, const uint8_t *device_rgb, uint32_t width,
+                                 uint32_t height, const float pose[16], const float inv_pose[16], const float k[9],
+                                 const float kinv[9]);
+/* n points (3 floats each, device) -> 3 bytes each (device), one thread per point, on hip_stream (NULL = the default stream). */
+int tsdf_volume_sample_colours_device(const tsdf_volume *volume, uint64_t n, const float *device_points, uint8_t *device_rgb,
+                                      void *hip_stream);
+/* tsdf_raycast / tsdf_raycast_device, then the sampling of every vertex (misses are NaN: 0, 0, 0); 3 * width * height bytes. */
+int tsdf_raycast_colour(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16], const float kinv[9],
+                        float *host_vertices, float *host_normals, uint8_t *host_rgb);
+int tsdf_raycast_colour_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
+                               const float kinv[9], float *device_vertices, float *device_normals, uint8_t *device_rgb);
+
 /* ---- raycast ---------------------------------------------------------------------------- */
 /* Replaces GPURaycaster::raycast = get_vertices/process_ray + compute_normals
  * (src/RayCaster/GPURaycaster.cu:519-547, 432-486, 265-377, 393-427, 496-510).

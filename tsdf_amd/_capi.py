@@ -101,6 +101,16 @@ _SIGS = {
     "tsdf_volume_set_counting": (_i, [_vp, _i]),
     "tsdf_volume_last_updated_voxels": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_last_distance_stores": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_volume_enable_colour": (_i, [_vp, _i]),
+    "tsdf_volume_colour_enabled": (_i, [_vp, C.POINTER(_i)]),
+    "tsdf_volume_colours": (_i, [_vp, C.POINTER(_vp)]),
+    "tsdf_volume_get_colour_data": (_i, [_vp, _vp]),
+    "tsdf_volume_set_colour_data": (_i, [_vp, _vp]),
+    "tsdf_integrate_colour": (_i, [_vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_integrate_colour_device": (_i, [_vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_volume_sample_colours_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    "tsdf_raycast_colour": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
+    "tsdf_raycast_colour_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_raycast": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_raycast_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_normals_device": (_i, [_u32, _u32, _vp, _vp, _vp]),
@@ -208,8 +218,10 @@ _HOST_SIGS = {
     "tsdf_host_tum_open": (_vp, [C.c_char_p]),
     "tsdf_host_tum_next": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_uint), _fp]),
     "tsdf_host_tum_close": (None, [_vp]),
+    "tsdf_host_tum_next_rgb": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_uint), _fp, _vp, C.c_size_t]),
     "tsdf_host_block_loader_parse": (_i, [C.c_char_p, _vp, _vp, _vp, _vp, C.c_size_t]),
     "tsdf_host_write_ply": (None, [C.c_char_p, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "tsdf_host_write_ply_coloured": (_i, [C.c_char_p, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "tsdf_host_read_nyu_depth_map": (C.c_size_t, [C.c_char_p, C.POINTER(C.c_uint), _vp, C.c_size_t]),
     "tsdf_host_match_file_name": (_i, [C.c_char_p, _i, C.c_char_p, C.c_char_p, C.c_char_p]),
     "tsdf_host_process_file_by_lines": (C.c_size_t, [C.c_char_p, C.POINTER(_i), C.c_char_p, C.c_size_t]),

@@ -233,6 +233,84 @@ class TSDFVolume:
         check(lib.tsdf_integrate_prepare_device_tiles(self._h, C.c_void_p(int(depth_ptr)), width, height, _fp(pose), _fp(ipose),
                                                       _fp(k), _fp(kinv), C.c_void_p(int(tile_max_ptr)), C.c_void_p(int(stream))))
 
+    # ---- colour fusion (include/tsdf_amd.h, "colour fusion"; not in the reference's class)
+    def enable_colour(self, enabled=True):
+        """Allocate the {r, g, b, n} dword per voxel, zeroed (False: free it).  Refused on a Z-slab."""
+        check(lib.tsdf_volume_enable_colour(self._h, 1 if enabled else 0))
+        self.synchronize()
+
+    def colour_enabled(self):
+        e = C.c_int()
+        check(lib.tsdf_volume_colour_enabled(self._h, C.byref(e)))
+        return bool(e.value)
+
+    def colour_data(self):
+        """Device pointer to the colour dwords."""
+        p = C.c_void_p()
+        check(lib.tsdf_volume_colours(self._h, C.byref(p)))
+        return p.value
+
+    def get_colour_data(self):
+        """uint32 per resident voxel: r | g << 8 | b << 16 | n << 24."""
+        a = np.empty(self.resident_voxels(), np.uint32)
+        check(lib.tsdf_volume_get_colour_data(self._h, a.ctypes.data))
+        return a
+
+    def set_colour_data(self, colour_data):
+        a = np.ascontiguousarray(colour_data, dtype=np.uint32).reshape(-1)
+        if a.size != self.resident_voxels():
+            raise ValueError("expected %d colour words, got %d" % (self.resident_voxels(), a.size))
+        check(lib.tsdf_volume_set_colour_data(self._h, a.ctypes.data))
+
+    def integrate_colour(self, depth_map, rgb, width, height, camera):
+        """integrate() plus the colour of rgb (uint8, width*height*3 interleaved RGB, registered to the depth map); blocking."""
+        d = np.ascontiguousarray(depth_map, dtype=np.uint16).reshape(-1)
+        c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1)
+        if d.size != width * height or c.size != 3 * width * height:
+            raise ValueError("expected %d depth pixels and %d colour bytes, got %d and %d" % (width * height, 3 * width * height, d.size, c.size))
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_integrate_colour(self._h, d.ctypes.data, c.ctypes.data, width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
+    def integrate_colour_device(self, depth_ptr, rgb_ptr, width, height, camera):
+        """Asynchronous on the volume's stream; device pointers to width*height uint16 and width*height*3 uint8."""
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_integrate_colour_device(self._h, C.c_void_p(int(depth_ptr)), C.c_void_p(int(rgb_ptr)), width, height, _fp(pose),
+                                               _fp(ipose), _fp(k), _fp(kinv)))
+
+    def sample_colours_device(self, n, points_ptr, rgb_ptr, stream=None):
+        """n points (3 float32 each) -> 3 uint8 each, device pointers; on `stream` (default: the volume's)."""
+        s = self.stream_ptr() if stream is None else stream
+        check(lib.tsdf_volume_sample_colours_device(self._h, int(n), C.c_void_p(int(points_ptr)), C.c_void_p(int(rgb_ptr)),
+                                                    C.c_void_p(int(s) if s else 0)))
+
+    def sample_colours(self, points):
+        """(n, 3) float32 world points (mm) -> (n, 3) uint8: the colour of the voxel each lies in, (0, 0, 0) for NaN, off-grid
+        and unobserved voxels."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), 3), np.uint8)
+        if not len(p):
+            if not self.colour_enabled():
+                raise ValueError("sample_colours: colour is not enabled on this volume")
+            return out
+        dp, dc = C.c_void_p(), C.c_void_p()
+        check(lib.tsdf_device_alloc(p.nbytes, C.byref(dp)))
+        try:
+            check(lib.tsdf_device_alloc(out.nbytes, C.byref(dc)))
+            check(lib.tsdf_device_upload(dp, p.ctypes.data, p.nbytes))
+            self.sample_colours_device(len(p), dp.value, dc.value)
+            self.synchronize()
+            check(lib.tsdf_device_download(out.ctypes.data, dc, out.nbytes))
+        finally:
+            lib.tsdf_device_free(dp)
+            if dc.value:
+                lib.tsdf_device_free(dc)
+        return out
+
+    def extract_coloured_surface(self):
+        """extract_surface() and the colour of every vertex (sample_colours): (vertices (3T, 3) float32, colours (3T, 3) uint8)."""
+        V = self.extract_surface()
+        return V, self.sample_colours(V)
+
     def occupancy(self):
         """(occupied, total) bricks of the ray caster's empty-space summary."""
         o, t = C.c_uint64(), C.c_uint64()
@@ -293,6 +371,23 @@ class GPURaycaster:
         check(lib.tsdf_raycast(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), V.ctypes.data,
                                N.ctypes.data))
         return V, N
+
+    def raycast_colour(self, volume, camera):
+        """raycast() plus the colour of the voxel every vertex lies in: (vertices, normals, rgb (width*height, 3) uint8); misses
+        and unobserved voxels are (0, 0, 0).  The volume must have colour enabled."""
+        pose, _, _, kinv = _camera_matrices(camera)
+        n = self.m_width * self.m_height
+        V = np.empty((n, 3), np.float32)
+        N = np.empty((n, 3), np.float32)
+        rgb = np.empty((n, 3), np.uint8)
+        check(lib.tsdf_raycast_colour(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), V.ctypes.data, N.ctypes.data,
+                                      rgb.ctypes.data))
+        return V, N, rgb
+
+    def raycast_colour_device(self, volume, camera, vertices_ptr, normals_ptr, rgb_ptr):
+        pose, _, _, kinv = _camera_matrices(camera)
+        check(lib.tsdf_raycast_colour_device(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), C.c_void_p(int(vertices_ptr)),
+                                             C.c_void_p(int(normals_ptr)) if normals_ptr else None, C.c_void_p(int(rgb_ptr))))
 
     def get_vertices(self, volume, camera):
         pose, _, _, kinv = _camera_matrices(camera)

@@ -391,6 +391,12 @@ struct tsdf_volume {
     int counting;
     unsigned long long *counter_dev;  // [0] = updated voxels, [1] = samples, [2] = hits, [kCounterStores] = distances stored
     uint64_t last_updated;
+    // colour fusion (colour.hip): one dword {r, g, b, n} per resident voxel while enabled (tsdf_volume_enable_colour), else null;
+    // rgb_buf caches the host variant's upload of the colour frame
+    uint32_t *colour;
+    uint8_t *rgb_buf;
+    size_t rgb_cap;
+    int slab;                 // made by tsdf_volume_create_slab (colour is refused there)
     size_t resident_voxels() const { return (size_t)g.X * g.Y * (g.z_store_end - g.z_store_begin); }
 };
 

@@ -93,6 +93,10 @@ int launch_integrate_packed_kernel(tsdf_volume *v, dim3 grid, const BrickGrid &b
                                    uint32_t height, const uint16_t *d_depth, unsigned long long *counter_arg, const uint4 *boxes,
                                    const uint2 *coords, const uint32_t *count, const float4 *plane_const);
 
+// colour.hip
+int launch_colour_integrate(tsdf_volume *v, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, const Mat33 &mkinv, bool std_camera,
+                            uint32_t width, uint32_t height, const uint16_t *d_depth, const uint8_t *d_rgb, const uint32_t *count);
+
 constexpr int kDepthTile = TSDF_DEPTH_TILE;  // pixels per side of a depth tile (16)
 constexpr int kCullTilesLds = 4096;  // tile maxima brick_cull_kernel keeps in LDS (1200 at 640x480)
 
@@ -280,34 +284,7 @@ __global__ __launch_bounds__(256) void brick_cull_kernel(const Geom g, const Bri
 // image.z == cam.z, surface z == depth, w == 1 (adding -0 is the identity, adding +0 only turns a -0 into +0, and
 // a zero's sign reaches neither the rounded pixel nor the sdf).  The kernel then skips those multiplications and
 // the divisions by 1.
-// rx = roundf(a1 / b), ry = roundf(a2 / b) exactly as the reference's IEEE divisions + round() give them
-// (src/Utilities/cuda_coordinate_transforms.cu:25-26), at a fraction of the cost.  The quotients are first formed with
-// the hardware reciprocal (relative error < 2.4e-7 against the correctly rounded quotient) and rounded to the nearest
-// integer r (v_rndne; round 1 used floor(q + 1/2), the same number wherever the fast path is kept);
-// h = 1/2 - |q - r| is the distance of q to the nearest rounding boundary (x.5).
-//   * |q| <= L = max(width, height) + 2 and h > thr = 4e-7 * L: the IEEE quotient lies on the same side of the same
-//     boundaries, and away from a boundary floor(q + 1/2) == roundf(q) for either sign (the addition q + 1/2 is exact
-//     or errs by less than thr), so the result is the reference's;
-//   * |q| > L: the IEEE quotient is beyond the image as well (> max(width, height) + 1 in magnitude), whatever the
-//     two round to fails the reference's frustum test alike;
-//   * otherwise (also NaN / infinite quotients, zero or denormal divisors: h is NaN or <= thr) the lane redoes the IEEE
-//     division and roundf, and maps NaN to 0 as the target's float -> int conversion does.
-__device__ inline void round_quotients(float a1, float a2, float b, float near_half, float &rx, float &ry) {
-    const float rc = __builtin_amdgcn_rcpf(b);
-    const float q1 = a1 * rc, q2 = a2 * rc;
-    // nearest integer (ties to even): equals floor(q + 1/2) wherever the test below lets the fast path stand -- the two differ
-    // only on ties and where q + 1/2 itself rounds across an integer, and both leave |q - r| within thr of 1/2
-    rx = __builtin_rintf(q1);
-    ry = __builtin_rintf(q2);
-    // h > thr  <=>  |q - r| < 1/2 - thr; near_half is the float just BELOW fl(1/2 - thr) (host), so the comparison can only
-    // send more lanes to the exact path than the bound in the comment above asks for.  NaN compares false -> exact path.
-    if (!(fabsf(q1 - rx) < near_half) || !(fabsf(q2 - ry) < near_half)) {
-        rx = roundf(a1 / b);
-        ry = roundf(a2 / b);
-        if (rx != rx) rx = 0.0f;
-        if (ry != ry) ry = 0.0f;
-    }
-}
+// round_quotients (integrate_grid.hpp): the pixel of a voxel, as the reference rounds it
 
 // Per z plane, the terms of the projection that depend on z only (the same fp32 products the reference forms per voxel):
 // {cz, inv_pose.m13 * cz, inv_pose.m23 * cz, inv_pose.m33 * cz}, cz = the voxel-centre z of the plane (:343, :783-785).
@@ -592,7 +569,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 enum IntegratePhase { kIntBoth = 0, kIntPrepare = 1 };
 static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t width, uint32_t height,
                             const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *caller_tile_max = nullptr,
-                            IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr) {
+                            IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr, const uint8_t *d_rgb = nullptr) {
     Mat44 ip;
     Mat33 mk, mkinv;
     memcpy(&ip, inv_pose, sizeof(ip));
@@ -771,6 +748,10 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     }
 #undef LAUNCH
     TSDF_HIP(hipGetLastError(), "Integrate kernel failed");
+    if (d_rgb) {   // tsdf_integrate_colour: the colour pass over the same brick list, right behind the integrate kernel
+        const int rcc = launch_colour_integrate(v, bg, ip, mk, mkinv, std_camera, width, height, d_depth, d_rgb, count);
+        if (rcc != TSDF_OK) return rcc;
+    }
 #ifdef TSDF_DIAGNOSTICS
     diag_brick_report(v, bg, n_bricks, count, boxes, brick_log);   // TSDF_DEBUG_BRICKS: survivors, list order, per-brick clocks
 #endif
@@ -787,6 +768,12 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
                     v->integrations_total >= 2)))
         v->occ_tighten_due = 1;
     return TSDF_OK;
+}
+
+// tsdf_integrate_colour_device (colour.hip): integrate with the colour pass behind it
+int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
+                          const float inv_pose[16], const float k[9], const float kinv[9]) {
+    return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, d_rgb);
 }
 
 }  // namespace tsdf

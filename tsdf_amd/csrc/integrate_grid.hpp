@@ -81,6 +81,35 @@ __device__ inline int cvt_i32_sat(float f) {
     return i;
 }
 
+// rx = roundf(a1 / b), ry = roundf(a2 / b) exactly as the reference's IEEE divisions + round() give them
+// (src/Utilities/cuda_coordinate_transforms.cu:25-26), at a fraction of the cost.  The quotients are first formed with
+// the hardware reciprocal (relative error < 2.4e-7 against the correctly rounded quotient) and rounded to the nearest
+// integer r (v_rndne; round 1 used floor(q + 1/2), the same number wherever the fast path is kept);
+// h = 1/2 - |q - r| is the distance of q to the nearest rounding boundary (x.5).
+//   * |q| <= L = max(width, height) + 2 and h > thr = 4e-7 * L: the IEEE quotient lies on the same side of the same
+//     boundaries, and away from a boundary floor(q + 1/2) == roundf(q) for either sign (the addition q + 1/2 is exact
+//     or errs by less than thr), so the result is the reference's;
+//   * |q| > L: the IEEE quotient is beyond the image as well (> max(width, height) + 1 in magnitude), whatever the
+//     two round to fails the reference's frustum test alike;
+//   * otherwise (also NaN / infinite quotients, zero or denormal divisors: h is NaN or <= thr) the lane redoes the IEEE
+//     division and roundf, and maps NaN to 0 as the target's float -> int conversion does.
+__device__ inline void round_quotients(float a1, float a2, float b, float near_half, float &rx, float &ry) {
+    const float rc = __builtin_amdgcn_rcpf(b);
+    const float q1 = a1 * rc, q2 = a2 * rc;
+    // nearest integer (ties to even): equals floor(q + 1/2) wherever the test below lets the fast path stand -- the two differ
+    // only on ties and where q + 1/2 itself rounds across an integer, and both leave |q - r| within thr of 1/2
+    rx = __builtin_rintf(q1);
+    ry = __builtin_rintf(q2);
+    // h > thr  <=>  |q - r| < 1/2 - thr; near_half is the float just BELOW fl(1/2 - thr) (host), so the comparison can only
+    // send more lanes to the exact path than the bound in the comment above asks for.  NaN compares false -> exact path.
+    if (!(fabsf(q1 - rx) < near_half) || !(fabsf(q2 - ry) < near_half)) {
+        rx = roundf(a1 / b);
+        ry = roundf(a2 / b);
+        if (rx != rx) rx = 0.0f;
+        if (ry != ry) ry = 0.0f;
+    }
+}
+
 #endif  // __HIPCC__
 
 #ifdef TSDF_DIAGNOSTICS

@@ -850,6 +850,7 @@ int tsdf_volume_create_slab(uint32_t sx, uint32_t sy, uint32_t sz, float px, flo
     }
     std::memset(v, 0, sizeof(*v));
     v->occ_scan_all = 1;
+    v->slab = 1;   // (tsdf_volume_create clears it)
     Geom &g = v->g;
     g.X = sx; g.Y = sy; g.Z = sz;
     g.phys = {px, py, pz};
@@ -904,7 +905,9 @@ int tsdf_volume_create_slab(uint32_t sx, uint32_t sy, uint32_t sz, float px, flo
 
 int tsdf_volume_create(uint32_t sx, uint32_t sy, uint32_t sz, float px, float py, float pz, tsdf_volume **out) {
     TSDF_REQUIRE(sz > 0, "Attempt to construct TSDFVolume with zero or negative size");
-    return tsdf_volume_create_slab(sx, sy, sz, px, py, pz, 0, sz, out);
+    const int rc = tsdf_volume_create_slab(sx, sy, sz, px, py, pz, 0, sz, out);
+    if (rc == TSDF_OK) (*out)->slab = 0;
+    return rc;
 }
 
 int tsdf_volume_destroy(tsdf_volume *v) {
@@ -947,6 +950,8 @@ int tsdf_volume_destroy(tsdf_volume *v) {
     if (v->brick_list) (void)hipFree(v->brick_list);
     if (v->brick_boxes) (void)hipFree(v->brick_boxes);
     if (v->tile_max) (void)hipFree(v->tile_max);
+    if (v->colour) (void)hipFree(v->colour);
+    if (v->rgb_buf) (void)hipFree(v->rgb_buf);
     delete v;
     return TSDF_OK;
 }
@@ -982,6 +987,7 @@ int tsdf_volume_clear(tsdf_volume *v) {
     }
     hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, v->stream, v->dist, n, v->g.trunc);
     TSDF_HIP(hipGetLastError(), "Couldn't clear TSDF data");
+    if (v->colour) TSDF_HIP(hipMemsetAsync(v->colour, 0, n * sizeof(uint32_t), v->stream), "Couldn't clear colour data");
     // every distance is +trunc again: only the permanent boundary marks remain
     int rc0 = occupancy_reset(v);
     if (rc0 != TSDF_OK) return rc0;

@@ -4,6 +4,7 @@
 #define TSDF_AMD_HOST_GPU_RAYCASTER_INCLUDED
 
 #include <Eigen/Core>
+#include <vector>
 
 #include "DepthImage.hpp"
 #include "Raycaster.hpp"
@@ -16,6 +17,11 @@ public:
     virtual void raycast(const TSDFVolume &volume, const Camera &camera,
                          Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
                          Eigen::Matrix<float, 3, Eigen::Dynamic> &normals) const;
+
+    // the same plus the colour of the voxel each vertex lies in ((0, 0, 0) for misses and unobserved voxels); the volume must
+    // have colour enabled (not in the reference's class)
+    void raycast(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
+                 Eigen::Matrix<float, 3, Eigen::Dynamic> &normals, std::vector<uchar3> &colours) const;
 
     // ray cast, then camera-space z of every vertex rounded to uint16 mm; caller deletes the image
     DepthImage *render_to_depth_image(const TSDFVolume &volume, const Camera &camera) const;

@@ -10,6 +10,10 @@
 #include "TSDFVolume.hpp"
 
 void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles);
+// the same with the colour of the voxel each vertex lies in (tsdf_volume_sample_colours_device); the volume must have colour
+// enabled (not in the reference)
+void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                     std::vector<uchar3> &colours);
 
 // The same marching cubes over a host distance array (x fastest, voxel centres at (i + 0.5) * voxel_size + offset):
 // appends three vertices per triangle.  extract_surface is this on the volume's distances.

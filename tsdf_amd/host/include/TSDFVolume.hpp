@@ -94,6 +94,15 @@ public:
     // fuse one depth frame (uint16 mm, 0 = invalid) seen from `camera`
     void integrate(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera);
 
+    // Colour fusion (include/tsdf_amd.h, "colour fusion"; not in the reference's class): one {r, g, b, n} dword per voxel while
+    // enabled.  enable_colour(true) allocates it zeroed (throws std::invalid_argument on a Z-slab), false frees it.
+    void enable_colour(bool enabled);
+    bool colour_enabled() const;
+    // DEVICE pointer to the colour dwords (x fastest); throws std::invalid_argument while colour is off
+    const uint32_t *colour_data() const;
+    // integrate() plus the colour of `rgb` (8-bit interleaved RGB, width * height * 3, registered to the depth map); needs colour on
+    void integrate(const uint16_t *depth_map, const uint8_t *rgb, uint32_t width, uint32_t height, const Camera &camera);
+
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);
 

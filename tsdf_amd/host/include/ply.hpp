@@ -9,4 +9,11 @@
 void write_to_ply(const std::string &file_name,
                   const std::vector<float3> &vertices,
                   const std::vector<int3> &triangles);
+
+// the same with a colour per vertex: "property uchar red / green / blue" after "property float z", and " r g b" ending each
+// vertex line (colours.size() == vertices.size())
+void write_to_ply(const std::string &file_name,
+                  const std::vector<float3> &vertices,
+                  const std::vector<int3> &triangles,
+                  const std::vector<uchar3> &colours);
 #endif

@@ -21,6 +21,18 @@ void GPURaycaster::raycast(const TSDFVolume &volume, const Camera &camera,
           "process_ray failed ");
 }
 
+void GPURaycaster::raycast(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
+                           Eigen::Matrix<float, 3, Eigen::Dynamic> &normals, std::vector<uchar3> &colours) const {
+    static_assert(sizeof(uchar3) == 3, "uchar3 must be 3 packed bytes");
+    vertices.resize(3, m_width * m_height);
+    normals.resize(3, m_width * m_height);
+    colours.resize((size_t)m_width * m_height);
+    const Eigen::Matrix3f kinv = camera.kinv();
+    check(tsdf_raycast_colour(volume.handle(), m_width, m_height, camera.pose().data(), kinv.data(), vertices.data(), normals.data(),
+                              reinterpret_cast<uint8_t *>(colours.data())),
+          "process_ray failed ");
+}
+
 // reference: src/RayCaster/GPURaycaster.cu:555-606 (without its debug PNG dump to a hard-coded path)
 DepthImage *GPURaycaster::render_to_depth_image(const TSDFVolume &volume, const Camera &camera) const {
     if (tsdf_host::verbose()) std::cout << "Rendering depth map" << std::endl;

@@ -189,3 +189,31 @@ void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, st
     // triangles are implicit, three consecutive vertices each, wired (i, i+2, i+1) like the reference (:549)
     for (size_t i = 0; i + 2 < vertices.size(); i += 3) triangles.push_back(int3{(int)i, (int)i + 2, (int)i + 1});
 }
+
+void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                     std::vector<uchar3> &colours) {
+    static_assert(sizeof(uchar3) == 3, "uchar3 must be 3 packed bytes");
+    extract_surface(volume, vertices, triangles);
+    colours.assign(vertices.size(), uchar3{0, 0, 0});
+    if (vertices.empty()) {
+        int enabled = 0;
+        tsdf_host::check(tsdf_volume_colour_enabled(volume->handle(), &enabled), "Couldn't query colour");
+        if (!enabled) throw std::invalid_argument("extract_surface: colour is not enabled on this volume");
+        return;
+    }
+    // the vertices to the device, one colour sample per vertex on the volume's stream, the colours back
+    const size_t n = vertices.size();
+    void *d_points = nullptr, *d_rgb = nullptr, *stream = nullptr;
+    tsdf_host::check(tsdf_volume_stream(volume->handle(), &stream), "Couldn't colour the surface");
+    tsdf_host::check(tsdf_device_alloc(n * sizeof(float3), &d_points), "Couldn't colour the surface");
+    int rc = tsdf_device_alloc(n * 3, &d_rgb);
+    if (rc == TSDF_OK) rc = tsdf_device_upload(d_points, vertices.data(), n * sizeof(float3));
+    if (rc == TSDF_OK)
+        rc = tsdf_volume_sample_colours_device(volume->handle(), n, static_cast<const float *>(d_points), static_cast<uint8_t *>(d_rgb),
+                                               stream);
+    if (rc == TSDF_OK) rc = tsdf_stream_synchronize(stream);
+    if (rc == TSDF_OK) rc = tsdf_device_download(colours.data(), d_rgb, n * 3);
+    (void)tsdf_device_free(d_points);
+    if (d_rgb) (void)tsdf_device_free(d_rgb);
+    tsdf_host::check(rc, "Couldn't colour the surface");
+}

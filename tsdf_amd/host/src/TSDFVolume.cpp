@@ -3,6 +3,7 @@
 #include "TSDFVolume.hpp"
 
 #include <cassert>
+#include <algorithm>
 #include <cmath>
 #include <fstream>
 #include <stdexcept>
@@ -139,6 +140,32 @@ void TSDFVolume::integrate(const uint16_t *depth_map, uint32_t width, uint32_t h
     if (tsdf_host::verbose()) std::cout << "Integration finished" << std::endl;
 }
 
+// ---- colour fusion (no reference counterpart)
+void TSDFVolume::enable_colour(bool enabled) {
+    check(tsdf_volume_enable_colour(m_handle, enabled ? 1 : 0), "Couldn't enable colour");
+    check(tsdf_volume_synchronize(m_handle), "Couldn't enable colour");
+}
+
+bool TSDFVolume::colour_enabled() const {
+    int enabled = 0;
+    check(tsdf_volume_colour_enabled(m_handle, &enabled), "Couldn't query colour");
+    return enabled != 0;
+}
+
+const uint32_t *TSDFVolume::colour_data() const {
+    uint32_t *p = nullptr;
+    check(tsdf_volume_colours(m_handle, &p), "Couldn't get colour data");
+    return p;
+}
+
+void TSDFVolume::integrate(const uint16_t *depth_map, const uint8_t *rgb, uint32_t width, uint32_t height, const Camera &camera) {
+    assert(depth_map && rgb);
+    const Eigen::Matrix3f k = camera.k(), kinv = camera.kinv();
+    check(tsdf_integrate_colour(m_handle, depth_map, rgb, width, height, camera.pose().data(), camera.inverse_pose().data(), k.data(),
+                                kinv.data()),
+          "Integrate kernel failed");
+}
+
 // reference: src/TSDF/TSDFVolume.cu:1054-1058
 void TSDFVolume::raycast(uint16_t width, uint16_t height, const Camera &camera,
                          Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
@@ -155,7 +182,8 @@ void TSDFVolume::deform_mesh(const int num_points, float3 *points) const {
 // ---- file format (reference: src/TSDF/TSDFVolume.cu:911-1027 writer, :463-664 reader):
 // 68-byte header {dim3 size, float3 physical, float3 offset, float trunc, float max_weight,
 // float3 global_translation, float3 global_rotation} then float dist[N], float weight[N],
-// uchar3 colour[N], DeformationNode[N]; little-endian, no padding.
+// uchar3 colour[N], DeformationNode[N]; little-endian, no padding.  The colour block holds each voxel's r, g, b when colour is
+// enabled, zeros otherwise (the reference writes its never-written array).
 bool TSDFVolume::save_to_file(const std::string &file_name) const {
     const size_t n = (size_t)m_size.x * m_size.y * m_size.z;
     std::vector<float> dist(n), weight(n);
@@ -178,8 +206,21 @@ bool TSDFVolume::save_to_file(const std::string &file_name) const {
     ofs.write((const char *)&m_global_rotation, sizeof(m_global_rotation));
     ofs.write((const char *)dist.data(), n * sizeof(float));
     ofs.write((const char *)weight.data(), n * sizeof(float));
-    // colours: never written by any kernel of the path -> all zero, streamed plane by plane
-    {
+    // colours: r, g, b of the colour dwords when colour is enabled; otherwise all zero, streamed plane by plane
+    if (colour_enabled()) {
+        std::vector<uint32_t> colour(n);
+        if (tsdf_volume_get_colour_data(m_handle, colour.data()) != TSDF_OK) {
+            std::cout << "Failed to copy colour data from device memory [" << tsdf_last_error() << "] " << std::endl;
+            return false;
+        }
+        std::vector<unsigned char> rgb(n * 3);
+        for (size_t i = 0; i < n; i++) {
+            rgb[3 * i + 0] = (unsigned char)colour[i];
+            rgb[3 * i + 1] = (unsigned char)(colour[i] >> 8);
+            rgb[3 * i + 2] = (unsigned char)(colour[i] >> 16);
+        }
+        ofs.write((const char *)rgb.data(), rgb.size());
+    } else {
         std::vector<unsigned char> zeros((size_t)m_size.x * m_size.y * 3, 0);
         for (unsigned z = 0; z < m_size.z; z++) ofs.write((const char *)zeros.data(), zeros.size());
     }
@@ -233,8 +274,23 @@ TSDFVolume::TSDFVolume(const std::string &file_name) : m_handle{nullptr}, m_offs
             else if (tsdf_volume_set_weight_data(m_handle, buf.data()) != TSDF_OK) why = "Failed to copy weight data to device";
         }
         if (why.empty()) {
-            ifs.seekg((std::streamoff)(n * 3), std::ios::cur);  // colours: unused by the path
-            if (!ifs.good()) why = "Failed to read colour data";
+            // colours: a block with a nonzero byte enables colour fusion (files of volumes without colour load as before).  The
+            // observation count is not in the file: n = min(max((int)weight, 1), 255) for a voxel whose colour is not (0, 0, 0),
+            // n = 0 otherwise -- so a voxel observed as pure black reads back as unobserved.
+            std::vector<unsigned char> rgb(n * 3);
+            if (!ifs.read((char *)rgb.data(), rgb.size())) why = "Failed to read colour data";
+            bool any = false;
+            for (size_t i = 0; i < rgb.size() && why.empty() && !any; i++) any = rgb[i] != 0;
+            if (any) {
+                std::vector<uint32_t> colour(n);
+                for (size_t i = 0; i < n; i++) {
+                    const uint32_t c = rgb[3 * i] | ((uint32_t)rgb[3 * i + 1] << 8) | ((uint32_t)rgb[3 * i + 2] << 16);
+                    const int w = (int)buf[i];   // (buf holds the weights just read)
+                    colour[i] = c ? c | ((uint32_t)std::min(std::max(w, 1), 255) << 24) : 0u;
+                }
+                if (tsdf_volume_enable_colour(m_handle, 1) != TSDF_OK || tsdf_volume_set_colour_data(m_handle, colour.data()) != TSDF_OK)
+                    why = std::string("Failed to copy colour data to device: ") + tsdf_last_error();
+            }
         }
         if (why.empty()) {
             // deformation nodes: keep the grid implicit when the file holds the regular grid

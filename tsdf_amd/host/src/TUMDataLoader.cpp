@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "FileUtilities.hpp"
+#include "PngUtilities.hpp"
 
 namespace {
 bool is_plain_file(const std::string &path) {
@@ -36,6 +37,7 @@ TUMDataLoader::TUMDataLoader(const std::string &directory) : m_next{0}, m_root{d
         fields >> stem;
         for (float &value : f.tq) fields >> value;
         f.png = m_root + "/depth/" + stem + ".png";
+        f.rgb = m_root + "/rgb/" + stem + ".png";
         m_frames.push_back(f);
     }
 }
@@ -74,5 +76,27 @@ DepthImage *TUMDataLoader::next(Eigen::Matrix4f &pose) {
     DepthImage *image = new DepthImage(f.png);
     image->scale_depth(0.2f);
     pose = pose_of(f);
+    return image;
+}
+
+DepthImage *TUMDataLoader::next(Eigen::Matrix4f &pose, std::vector<uint8_t> &rgb) {
+    if (m_next >= m_frames.size()) return nullptr;
+    const std::string rgb_file = m_frames[m_next].rgb;
+    Eigen::Matrix4f p;
+    DepthImage *image = next(p);
+    if (!image) return nullptr;
+    uint32_t w = 0, h = 0;
+    uint8_t *pixels = nullptr;
+    if (is_plain_file(rgb_file)) pixels = load_colour_png_from_file(rgb_file, w, h);
+    else std::cerr << "Couldn't find file " << rgb_file << std::endl;
+    if (!pixels || w != image->width() || h != image->height()) {
+        if (pixels && (w != image->width() || h != image->height())) std::cerr << "Colour frame " << rgb_file << " is not the depth frame's size" << std::endl;
+        delete[] pixels;
+        delete image;
+        return nullptr;
+    }
+    rgb.assign(pixels, pixels + (size_t)w * h * 3);
+    delete[] pixels;
+    pose = p;
     return image;
 }

@@ -129,6 +129,32 @@ int tsdf_host_tum_next(tsdf_tum_loader *l, uint16_t *depth, size_t capacity, uns
     return 1;
 }
 void tsdf_host_tum_close(tsdf_tum_loader *l) { delete reinterpret_cast<TUMDataLoader *>(l); }
+// tsdf_host_tum_next with the record's colour frame (TUMDataLoader::next(pose, rgb)): rgb receives width * height * 3 bytes when
+// rgb_capacity suffices.  1: a frame; 0: exhausted; -1: the record was consumed but its depth or colour frame is missing, unreadable
+// or (colour) of another size.
+int tsdf_host_tum_next_rgb(tsdf_tum_loader *l, uint16_t *depth, size_t capacity, unsigned size[2], float pose[16], uint8_t *rgb,
+                           size_t rgb_capacity) {
+    if (!l || !size || !pose) return -1;
+    TUMDataLoader *loader = reinterpret_cast<TUMDataLoader *>(l);
+    if (loader->records_left() == 0) return 0;
+    Eigen::Matrix4f p;
+    std::vector<uint8_t> colour;
+    DepthImage *image = nullptr;
+    try {
+        image = loader->next(p, colour);
+    } catch (const std::exception &) {
+        return -1;
+    }
+    if (!image) return -1;
+    size[0] = image->width();
+    size[1] = image->height();
+    const size_t n = (size_t)image->width() * image->height();
+    if (depth && capacity >= n) memcpy(depth, image->data(), n * sizeof(uint16_t));
+    if (rgb && rgb_capacity >= colour.size()) memcpy(rgb, colour.data(), colour.size());
+    memcpy(pose, p.data(), 16 * sizeof(float));
+    delete image;
+    return 1;
+}
 
 static const char *or_empty(const char *s) { return s ? s : ""; }   // (a null string from a binding reads as the empty one)
 
@@ -139,6 +165,26 @@ void tsdf_host_write_ply(const char *file_name, const float *vertices, size_t n_
     for (size_t i = 0; i < n_vertices; i++) v[i] = float3{vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]};
     for (size_t i = 0; i < n_triangles; i++) t[i] = int3{triangles[3 * i], triangles[3 * i + 1], triangles[3 * i + 2]};
     write_to_ply(or_empty(file_name), v, t);
+}
+
+// write_to_ply with a colour per vertex (3 bytes a vertex); 0 = written, -1 = a null array or an exception
+int tsdf_host_write_ply_coloured(const char *file_name, const float *vertices, size_t n_vertices, const int *triangles, size_t n_triangles,
+                                 const uint8_t *colours) {
+    if ((n_vertices && (!vertices || !colours)) || (n_triangles && !triangles)) return -1;
+    try {
+        std::vector<float3> v(n_vertices);
+        std::vector<int3> t(n_triangles);
+        std::vector<uchar3> c(n_vertices);
+        for (size_t i = 0; i < n_vertices; i++) {
+            v[i] = float3{vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]};
+            c[i] = uchar3{colours[3 * i], colours[3 * i + 1], colours[3 * i + 2]};
+        }
+        for (size_t i = 0; i < n_triangles; i++) t[i] = int3{triangles[3 * i], triangles[3 * i + 1], triangles[3 * i + 2]};
+        write_to_ply(or_empty(file_name), v, t, c);
+    } catch (const std::exception &) {
+        return -1;
+    }
+    return 0;
 }
 
 // read_nyu_depth_map (DepthMapUtilities.cpp): returns width * height (0: the file did not parse) and copies the samples when

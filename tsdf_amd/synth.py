@@ -56,8 +56,17 @@ def camera_for_frame(i, n, camera=None, inside=False):
     return cam
 
 
+# per-object blue of the colour texture (trace_colour); 0 = nothing hit
+WALL_B, SPHERE_B, BOX_B = 64, 160, 240
+
+
 def trace_depth(camera, width=WIDTH, height=HEIGHT):
     """Exact camera-z depth (float64 mm, inf = nothing hit) of the analytic scene."""
+    return _trace(camera, width, height)[0]
+
+
+def _trace(camera, width, height):
+    """-> (camera-z depth, blue of the object hit (0: none), camera origin, world ray directions with camera z == 1)."""
     kinv = camera.kinv().astype(np.float64).reshape(3, 3).T
     pose = camera.pose().astype(np.float64).reshape(4, 4).T
     R, o = pose[:3, :3], pose[:3, 3]
@@ -66,11 +75,13 @@ def trace_depth(camera, width=WIDTH, height=HEIGHT):
     d_cam = pix @ kinv.T                                              # camera-space ray, z == 1
     d = d_cam @ R.T                                                   # world-space, t == camera z
     best = np.full(xs.shape, np.inf)
+    obj = np.zeros(xs.shape, np.uint8)
 
     # wall z = WALL_Z
     with np.errstate(divide="ignore", invalid="ignore"):
         t = (WALL_Z - o[2]) / d[..., 2]
     ok = (t > 0) & np.isfinite(t)
+    obj = np.where(ok & (t < best), WALL_B, obj)
     best = np.where(ok & (t < best), t, best)
 
     # sphere
@@ -82,6 +93,7 @@ def trace_depth(camera, width=WIDTH, height=HEIGHT):
     with np.errstate(invalid="ignore"):
         t = (-b - np.sqrt(disc)) / (2.0 * a)
     ok = (disc >= 0) & (t > 0)
+    obj = np.where(ok & (t < best), SPHERE_B, obj)
     best = np.where(ok & (t < best), t, best)
 
     # box (slab method)
@@ -91,8 +103,35 @@ def trace_depth(camera, width=WIDTH, height=HEIGHT):
     tn = np.max(np.minimum(t0, t1), axis=-1)
     tf = np.min(np.maximum(t0, t1), axis=-1)
     ok = (tn <= tf) & (tn > 0)
+    obj = np.where(ok & (tn < best), BOX_B, obj)
     best = np.where(ok & (tn < best), tn, best)
-    return best
+    return best, obj, o, d
+
+
+def texture(points, blue):
+    """The scene's colour at world points (..., 3) mm: r = 255 x / 3000, g = 255 y / 3000 (rounded, clamped), b = the object's
+    constant blue (WALL_B / SPHERE_B / BOX_B); uint8 (..., 3)."""
+    p = np.asarray(points, np.float64)
+    r = np.clip(np.rint(255.0 * p[..., 0] / 3000.0), 0, 255)
+    g = np.clip(np.rint(255.0 * p[..., 1] / 3000.0), 0, 255)
+    return np.stack([r, g, np.asarray(blue, np.float64) + 0 * r], axis=-1).astype(np.uint8)
+
+
+def trace_colour(camera, width=WIDTH, height=HEIGHT):
+    """Per-pixel RGB (uint8 (H*W, 3)) of the analytic scene at the traced hit point (texture()); (0, 0, 0) where nothing is hit."""
+    z, obj, o, d = _trace(camera, width, height)
+    hit = np.isfinite(z)
+    p = o + d * np.where(hit, z, 0.0)[..., None]          # (camera z == ray parameter: d has camera z 1)
+    rgb = np.where(hit[..., None], texture(p, obj), 0)
+    return rgb.astype(np.uint8).reshape(-1, 3)
+
+
+def colour_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, inside=False):
+    """-> (rgb uint8 (H*W, 3), camera): the colour frame registered to depth_frame(i, n, seed, ...) -- same camera, same pixels (a
+    depth dropout keeps its colour).  Noise-free: `seed` is accepted for symmetry with depth_frame."""
+    del seed
+    cam = camera_for_frame(i, n, camera, inside)
+    return trace_colour(cam, width, height), cam
 
 
 def depth_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, noise=True, inside=False):
@@ -148,12 +187,32 @@ def _write_png16(path, image):
         f.write(chunk(b"IEND", b""))
 
 
-def write_tum_directory(directory, n_frames, seed, stream_frames=None, width=WIDTH, height=HEIGHT):
+def _write_png_rgb(path, image):
+    """8-bit RGB PNG (filter 0): the colour frames of a TUM-style directory."""
+    import struct
+    import zlib
+    h, w, _ = image.shape
+    raw = b"".join(b"\x00" + image[y].astype(np.uint8).tobytes() for y in range(h))
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(raw, 6)))
+        f.write(chunk(b"IEND", b""))
+
+
+def write_tum_directory(directory, n_frames, seed, stream_frames=None, width=WIDTH, height=HEIGHT, colour=False):
     """Writes the layout the reference's TUMDataLoader expects (src/DataLoader/TUMDataLoader.cpp:20,111-128):
     <dir>/depth/<stem>.png (uint16, 5 units per mm) and <dir>/ground_truth.txt with lines
-    '<stem> tx ty tz qx qy qz qw' (metres, TUM quaternion order).  Returns the per-frame (depth_mm, pose16)."""
+    '<stem> tx ty tz qx qy qz qw' (metres, TUM quaternion order).  Returns the per-frame (depth_mm, pose16).
+    colour=True also writes <dir>/rgb/<stem>.png (8-bit RGB, colour_frame) for TUMDataLoader::next(pose, rgb)."""
     import os
     os.makedirs(os.path.join(directory, "depth"), exist_ok=True)
+    if colour:
+        os.makedirs(os.path.join(directory, "rgb"), exist_ok=True)
     frames = []
     lines = ["# synthetic TUM surrogate (tsdf_amd.synth), seed 0x%X" % seed]
     total = stream_frames or n_frames
@@ -162,6 +221,8 @@ def write_tum_directory(directory, n_frames, seed, stream_frames=None, width=WID
         stem = "%010.6f" % (1305031102.0 + i / 30.0)
         _write_png16(os.path.join(directory, "depth", stem + ".png"), (depth.astype(np.uint32) * 5).clip(0, 65535)
                      .astype(np.uint16).reshape(height, width))
+        if colour:
+            _write_png_rgb(os.path.join(directory, "rgb", stem + ".png"), trace_colour(cam, width, height).reshape(height, width, 3))
         P = cam.pose().astype(np.float64).reshape(4, 4).T
         R, t = P[:3, :3], P[:3, 3] / 1000.0
         # rotation -> quaternion (w largest-branch free form is enough for these small rotations)
