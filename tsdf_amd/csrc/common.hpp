@@ -57,20 +57,12 @@ struct Tuning {
     int ray_cells_look;      // TSDF_RAY_CELLS_LOOK     1 (default): every flagged brick is projected when the list is built -- unseen ones dropped, large ones listed in parts; 0: never
     int ray_cells_grid;      // TSDF_RAY_CELLS_GRID     workgroups of cast_cells_kernel (2048: two or three bricks a wave at 20 000 listed bricks; see raycast_cells.hpp)
     int ray_cells_sort;      // TSDF_RAY_CELLS_SORT     the cell-parallel cast's list front to back: 0 never, 1 for views from inside the volume, 2 always
-    int ray_chooser;         // TSDF_RAY_CHOOSER        0 (default): TSDF_RAY_CELLS=1 goes by the static rules alone; 1: the cast is chosen from measured times (choose_cast); 2: a trial of the other cast every few casts (test aid)
     int ray_entry_bound;     // TSDF_RAY_ENTRY_BOUND    0: no per-tile entry bound (default 1: rays start at the nearest flagged block their 16 x 16 tile can see)
-    int icp_persistent;      // TSDF_ICP_PERSISTENT     default 0: one launch per ICP iteration (the chain); 1 / 2: all 19 in one launch with a grid barrier (slower, kept for study)
     int occ_rebuild_period;  // TSDF_OCC_REBUILD_PERIOD integrations between tightenings of the ray caster's flags (16; 0: never)
     int occ_scan_all;        // TSDF_OCC_SCAN_ALL       1: every tightening reads the whole distance array
     int reach_lds;           // TSDF_REACH_LDS          1: the workgroup variant of the reach summary on every grid
     int int_grid_per_cu;     // TSDF_INT_GRID_PER_CU    integrate: n > 0 = a resident grid of n workgroups per CU walking the brick list
     int weight_pack;         // TSDF_WEIGHT_PACK        how a volume's weights are stored to begin with (weights.hip): 8 (default) / 16-bit counts, 0 = the reference's fp32 array
-    int pipe_release;        // TSDF_PIPE_RELEASE       when tsdf_pipeline_step lets the next frame's filter + culling start on the side stream: 0 after
-                             //                          this frame's integrate (beside the bulk ray kernel), 1 after the bulk ray kernel (beside the tail kernel), 2 the filter already after the previous step (beside integrate); both measured slower
-    int pipe_word_release;   // TSDF_PIPE_WORD_RELEASE  0 (default): the pipeline's second stream is released by an event; 1: by a word the cast's first kernel stores (no packet in the step's stream, but the runtime's wait is a spinning kernel: 0.2167 -> 0.2149 ms, kept as the measured alternative)
-    int pipe_host_wait;      // TSDF_PIPE_HOST_WAIT     1: tsdf_pipeline_step waits on the HOST for the frame filtered ahead instead of putting a wait packet into the step's stream
-    int event_scope;         // TSDF_EVENT_SCOPE        the events that order the library's own streams: 0 HIP's default (a system-scope fence when the event completes: cache
-                             //                          write-back + invalidate for the host's and other devices' sake), 1 hipEventReleaseToDevice, 2 (default) hipEventDisableSystemFence
     int timing_bracket;      // TSDF_TIMING_BRACKET     1: tsdf_volume_set_timing brackets launches with hipEventRecord
     int verbose;             // TSDF_VERBOSE            the reference's chatter
     int debug_rays;          // TSDF_DEBUG_RAYS         how many pieces went through the tail queue (synchronises)
@@ -80,10 +72,7 @@ const Tuning &tuning();
 // it (the kernels either side of it release / acquire at device scope at their own boundaries, as consecutive kernels of one stream
 // do), so the system-scope fence HIP attaches to an event by default is dropped: 4-6 us of every 270 us step (profiles/r04zz_event_scope_ab.txt).
 // The events of the multi-GPU exchange (pipeline.hip: cast, merged) keep HIP's default.
-inline unsigned stream_order_event_flags() {
-    const int scope = tuning().event_scope;
-    return hipEventDisableTiming | (scope == 1 ? hipEventReleaseToDevice : scope == 2 ? hipEventDisableSystemFence : 0u);
-}
+inline unsigned stream_order_event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
 int occupancy_rebuild(struct ::tsdf_volume *v);  // volume.hip
 int occupancy_join(struct ::tsdf_volume *v);     // volume.hip: the volume's stream waits for a tightening enqueued elsewhere
 int occupancy_tighten_on(struct ::tsdf_volume *v, hipStream_t stream);  // volume.hip: the periodic rebuild on another stream
@@ -91,7 +80,6 @@ struct EntryParams;
 // volume.hip: bring fine + reach up to date; with `entry` (a whole-volume ray cast whose camera allows it) the same launch also leaves
 // the per-tile entry bound of that view (EntryParams)
 int occupancy_refresh(struct ::tsdf_volume *v, const EntryParams *entry = nullptr);
-bool raycast_takes_cells(const struct ::tsdf_volume *v, uint32_t width, uint32_t height, const float pose[16], const float kinv[9]);   // raycast.hip: would tsdf_raycast_device take the cell-parallel cast now?
 int occupancy_flags_refresh(struct ::tsdf_volume *v);   // volume.hip: the flags only (fine, cell), not the reach summary: what the cell-parallel cast reads
 int build_t_table(struct ::tsdf_volume *v);      // volume.hip
 // timing helpers (volume.hip).  When timing is on, a launch of kernel `which` carries a start and a stop event that take the
@@ -254,21 +242,6 @@ __host__ __device__ inline int f2i_sat(float f) {
 // ---- object state ------------------------------------------------------------------------
 }  // namespace tsdf
 
-namespace tsdf {
-// which cast a volume's casts take, from measured times (raycast.hip: choose_cast)
-struct CastChooser {
-    float ms[2];                  // whole cast, smoothed: [0] the march, [1] the cell-parallel cast
-    uint32_t seen[2];             // casts measured
-    uint64_t measured_at[2];      // ... the last one at this cast
-    uint64_t casts, next_trial;   // whole-volume casts so far; when the cast not taken is tried next
-    uint32_t gap;                 // casts between trials (64 ... 4096)
-    bool pending, pending_trial, blocked;
-    int pending_kind, last_kind, trial_kind, trial_left;   // trial_left > 0: casts of the running trial still to come (the last one is measured)
-    hipEvent_t ev[2];             // around the sampled cast on the volume's stream
-    float trial_origin[3], trial_axis[3];   // the view of the last trial (a trial lost by 3 x waits for another view)
-};
-}  // namespace tsdf
-
 struct tsdf_volume {
     tsdf::Geom g;
     uint32_t z_begin, z_end;  // owned planes
@@ -297,9 +270,6 @@ struct tsdf_volume {
     size_t ray_cap;
     // per pixel: {the smallest sample index found <= 0 so far by the ray march, that sample's value} in one 64-bit word (all ones
     // = none); every kernel of the march lowers it with atomicMin, resolve_hits_kernel turns it into the vertex and resets it (raycast.hip)
-    uint32_t *release_word;  // when set: the cell-parallel cast's first kernel stores release_value there as it starts (tsdf_pipeline_step, scheduling)
-    uint32_t release_value;
-    hipEvent_t after_bulk;   // when set: recorded on the volume's stream right behind the bulk ray kernel's launch (tsdf_pipeline_step, scheduling)
     uint64_t *ray_best;      // two copies of ray_best_cap words, used alternately (ray_best_side)
     size_t ray_best_cap;
     int ray_best_side;
@@ -315,7 +285,6 @@ struct tsdf_volume {
     size_t cell_rays_cap;
     uint32_t *cell_bricks;
     uint32_t *cell_count_scratch;   // two words for count_cell_bricks_kernel (raycast.hip)
-    tsdf::CastChooser chooser;
     int cell_recount_wait;          // casts that kept the march because the list was over the limit, since the last recount
     size_t cell_bricks_cap;
     uint32_t *cell_cast_host;

@@ -110,9 +110,6 @@ struct tsdf_pipeline {
     // events are made once and recorded again every other frame (creating one per frame makes the runtime grow its pool of
     // signals now and then: a stall of tens of milliseconds in the middle of a stream)
     hipEvent_t done[2], ready[2];   // [b]: the integrate that read buffer b has finished; buffer b has been filtered (and culled) ahead
-    hipEvent_t bulk;                // the bulk ray kernel of this frame's cast has ended (TSDF_PIPE_RELEASE=1)
-    uint32_t *release_word;         // signal memory: the cell-parallel cast's first kernel stores release_seq there (see tsdf_pipeline_step); may be null
-    uint32_t release_seq;
     hipEvent_t cast, merged;        // third-stream exchange: the slab cast has left its records; the merge has consumed them
     bool merged_pending;
     const uint16_t *ahead_depth;    // the frame filtered ahead into buffer ahead_buf (nullptr: none)
@@ -435,12 +432,10 @@ int tsdf_pipeline_destroy(tsdf_pipeline *p) {
         if (p->done[b]) (void)hipEventDestroy(p->done[b]);
         if (p->ready[b]) (void)hipEventDestroy(p->ready[b]);
     }
-    if (p->bulk) (void)hipEventDestroy(p->bulk);
     if (p->cast) (void)hipEventDestroy(p->cast);
     if (p->merged) (void)hipEventDestroy(p->merged);
     if (p->hits_mine) (void)hipFree(p->hits_mine);
     if (p->hits_all) (void)hipFree(p->hits_all);
-    if (p->release_word) (void)hipFree(p->release_word);
     if (p->side) (void)hipStreamDestroy(p->side);
     if (p->xstream) (void)hipStreamDestroy(p->xstream);
     if (p->main) (void)hipStreamDestroy(p->main);
@@ -490,17 +485,6 @@ int tsdf_pipeline_create(tsdf_volume *volume, const tsdf_bilateral *filter, uint
         if (e == hipSuccess) e = hipEventCreateWithFlags(&p->done[b], stream_order_event_flags());
         if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ready[b], stream_order_event_flags());
     }
-    if (e == hipSuccess && overlap) e = hipEventCreateWithFlags(&p->bulk, stream_order_event_flags());
-    if (e == hipSuccess && overlap && !exchange && tuning().pipe_word_release) {
-        // (a word the second stream can wait for without an event in the step's stream; where the runtime has no such memory the events do it)
-        if (hipExtMallocWithFlags((void **)&p->release_word, 2 * sizeof(uint32_t), hipMallocSignalMemory) != hipSuccess) {
-            (void)hipGetLastError();
-            p->release_word = nullptr;
-        } else if (hipMemset(p->release_word, 0, 2 * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipFree(p->release_word);
-            p->release_word = nullptr;
-        }
-    }
     if (e == hipSuccess && p->xstream) e = hipEventCreateWithFlags(&p->cast, hipEventDisableTiming);
     if (e == hipSuccess && p->xstream) e = hipEventCreateWithFlags(&p->merged, hipEventDisableTiming);
     if (e == hipSuccess && exchange) {
@@ -540,24 +524,12 @@ int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsd
     const uint32_t W = p->width, H = p->height;
     const int b = (int)(p->frames & 1u);
     int rc;
-    // TSDF_PIPE_RELEASE=2 (experiment): the next frame's FILTER is released by the end of the previous step already and runs beside
-    // this frame's integrate (its buffers were last read by the integrate before that); its culling still waits for this integrate.
-    const bool early_filter = p->side && next_device_depth && !p->exchange && tuning().pipe_release == 2;
-    if (early_filter) {
-        TSDF_HIP(hipEventRecord(p->bulk, p->main), "pipeline: previous step done");
-        TSDF_HIP(hipStreamWaitEvent(p->side, p->bulk, 0), "pipeline: release the next frame's filter");
-        rc = run_filter(p, next_device_depth, 1 - b, p->side);
-        if (rc != TSDF_OK) return rc;
-    }
     if (p->ahead_depth && p->ahead_depth == device_depth && p->ahead_buf == b) {
         // The frame filtered (and culled) ahead on the side stream.  A wait packet in the step's stream costs it 6-12 us even when the
         // event completed long ago (the packet breaks the back-to-back dispatch of resolve -> integrate); when the event is already
-        // complete at this call no packet is needed, and with TSDF_PIPE_HOST_WAIT=1 the host waits for it here instead (it completes while
-        // the previous frame's tail kernel runs: the host then enqueues this step beside the rest of the previous one).
-        if (hipEventQuery(p->ready[b]) != hipSuccess) {
-            if (tuning().pipe_host_wait) TSDF_HIP(hipEventSynchronize(p->ready[b]), "pipeline: wait for the frame filtered ahead");
-            else TSDF_HIP(hipStreamWaitEvent(p->main, p->ready[b], 0), "pipeline: wait for the frame filtered ahead");
-        }
+        // complete at this call no packet is needed.
+        if (hipEventQuery(p->ready[b]) != hipSuccess)
+            TSDF_HIP(hipStreamWaitEvent(p->main, p->ready[b], 0), "pipeline: wait for the frame filtered ahead");
     } else {
         if (p->ahead_depth) {
             // Another frame than the one announced: the side stream may still be writing a filtered buffer, its tile maxima and
@@ -571,57 +543,10 @@ int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsd
     p->ahead_depth = nullptr;
     rc = tsdf_integrate_device_tiles(p->volume, p->filtered[b], W, H, cam->pose, cam->inv_pose, cam->k, cam->kinv, p->tile_max[b]);
     if (rc != TSDF_OK) return rc;
-    bool late_release = false;
-    bool by_word = false;   // the second stream waits for a word the cast's first kernel stores, not for an event of the step's stream
-    // The word's promise, kept on every way out: once the side stream has been told to wait for this step's sequence number, a step
-    // that returns early -- the filter ahead failed, the cast failed or took the march -- stores the number itself (behind whatever the
-    // step's stream holds) and takes the pointer back from the volume: otherwise the side stream waits for ever (synchronize and
-    // destroy with it) and a later cell-parallel cast would store through a pointer whose memory the pipeline has freed.
-    struct WordGuard {
-        tsdf_pipeline *p = nullptr;
-        ~WordGuard() {
-            if (!p || !p->volume->release_word) return;   // (taken: the cast's first kernel stores it)
-            p->volume->release_word = nullptr;
-            if (hipStreamWriteValue32(p->main, p->release_word, p->release_seq, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("tsdf_pipeline_step: the release word could not be stored; the side stream is left waiting (destroy the pipeline)");
-            }
-        }
-    } word_guard;
-    auto filter_ahead = [&](hipEvent_t release) -> int {
-        if (by_word) TSDF_HIP(hipStreamWaitValue32(p->side, p->release_word, p->release_seq, hipStreamWaitValueGte, 0xffffffffu), "pipeline: release the next frame's filter");
-        else TSDF_HIP(hipStreamWaitEvent(p->side, release, 0), "pipeline: release the next frame's filter");
-        int rc_ = early_filter ? TSDF_OK : run_filter(p, next_device_depth, 1 - b, p->side);
-        if (rc_ != TSDF_OK) return rc_;
-        if (next_cam) {
-            rc_ = tsdf_integrate_prepare_device_tiles(p->volume, p->filtered[1 - b], W, H, next_cam->pose, next_cam->inv_pose, next_cam->k,
-                                                      next_cam->kinv, p->tile_max[1 - b], p->side);
-            if (rc_ != TSDF_OK) return rc_;
-        }
-        TSDF_HIP(hipEventRecord(p->ready[1 - b], p->side), "pipeline: next frame ready");
-        p->ahead_depth = next_device_depth;
-        p->ahead_buf = 1 - b;
-        return TSDF_OK;
-    };
     if (p->side) {
-        // An event recorded behind integrate costs the step's stream 5-6 us (a packet between two kernels that would otherwise run back
-        // to back; profiles/r05y_sync_ubench.txt).  When the cast that follows is the cell-parallel one its first kernel -- in front of
-        // which on this stream lies exactly what the second stream has to wait for -- stores a sequence number into a word of signal
-        // memory as it starts, and the second stream waits for that value: the wait's cost lands where there is slack.  Measured
-        // (TSDF_PIPE_WORD_RELEASE=1, profiles/r05y_word_release_ab.txt): the gap behind integrate goes (5.6 -> 0 us), but the runtime's
-        // wait is a kernel that spins on the word for the 100-150 us until it comes, and the cast's first kernel beside it takes 14 us
-        // instead of 11.8: 0.2167 -> 0.2149 ms per step over three runs each.  Off by default.
-        const bool tighten_ahead = p->volume->occ_tighten_due && !p->volume->occ_dirty && !(p->flags & TSDF_PIPELINE_NO_TIGHTEN_AHEAD);
-        by_word = p->release_word && next_device_depth && !p->exchange && !tighten_ahead && tuning().pipe_release == 0 &&
-                  raycast_takes_cells(p->volume, W, H, cam->pose, cam->kinv);
-        if (by_word) {
-            p->release_seq++;
-            p->volume->release_word = p->release_word;
-            p->volume->release_value = p->release_seq;
-            word_guard.p = p;   // (from here on every way out of the step leaves the word stored: the side stream waits for it)
-        } else {
-            TSDF_HIP(hipEventRecord(p->done[b], p->main), "pipeline: integrate done");
-        }
+        // (An event recorded behind integrate costs the step's stream 5-6 us: a packet between two kernels that would otherwise run back
+        // to back; profiles/r05y_sync_ubench.txt.)
+        TSDF_HIP(hipEventRecord(p->done[b], p->main), "pipeline: integrate done");
         if (p->volume->occ_tighten_due && !p->volume->occ_dirty && !(p->flags & TSDF_PIPELINE_NO_TIGHTEN_AHEAD)) {
             // the periodic tightening of the ray caster's flags (every 16th frame: a scan of what integrate has written since the last
             // one, 60-125 us) goes beside this frame's ray cast instead of in front of it: the flags as they are still cover the
@@ -633,27 +558,26 @@ int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsd
             rc = occupancy_tighten_on(p->volume, p->side);
             if (rc != TSDF_OK) return rc;
         }
-        // The next frame's filter + culling on the side stream: released by THIS frame's integrate (never beside integrate_kernel; the
+        // The next frame's filter + culling on the side stream, released by THIS frame's integrate (never beside integrate_kernel; the
         // other buffer was last read by the previous frame's integrate, which lies before it on the step's stream; the brick list, the
-        // boxes and the plane constants are free once this frame's integrate_kernel is done) -- or, TSDF_PIPE_RELEASE=1, only by the end
-        // of this frame's bulk ray kernel, so that it runs beside the tail kernel instead (whole-volume casts).
-        late_release = next_device_depth && !p->exchange && tuning().pipe_release == 1;
-        if (next_device_depth && !late_release) {
-            rc = filter_ahead(p->done[b]);
+        // boxes and the plane constants are free once this frame's integrate_kernel is done).
+        if (next_device_depth) {
+            TSDF_HIP(hipStreamWaitEvent(p->side, p->done[b], 0), "pipeline: release the next frame's filter");
+            rc = run_filter(p, next_device_depth, 1 - b, p->side);
             if (rc != TSDF_OK) return rc;
+            if (next_cam) {
+                rc = tsdf_integrate_prepare_device_tiles(p->volume, p->filtered[1 - b], W, H, next_cam->pose, next_cam->inv_pose, next_cam->k,
+                                                         next_cam->kinv, p->tile_max[1 - b], p->side);
+                if (rc != TSDF_OK) return rc;
+            }
+            TSDF_HIP(hipEventRecord(p->ready[1 - b], p->side), "pipeline: next frame ready");
+            p->ahead_depth = next_device_depth;
+            p->ahead_buf = 1 - b;
         }
     }
     if (!p->exchange) {
-        p->volume->after_bulk = late_release ? p->bulk : nullptr;
         rc = tsdf_raycast_device(p->volume, W, H, cam->pose, cam->kinv, device_vertices, device_normals);
-        p->volume->after_bulk = nullptr;
-        // (a cast that did not take the kernel that stores the word -- the list's count arrived between the two looks at it, or the
-        // cast failed: word_guard stores it from the step's stream, behind whatever was launched)
         if (rc != TSDF_OK) return rc;
-        if (late_release) {
-            rc = filter_ahead(p->bulk);
-            if (rc != TSDF_OK) return rc;
-        }
     } else {
         if (p->xstream && p->merged_pending)   // the previous frame's merge still reads hits_all / the collective hits_mine
             TSDF_HIP(hipStreamWaitEvent(p->main, p->merged, 0), "pipeline: wait for the previous exchange");

@@ -1007,12 +1007,9 @@ static int count_after_bulk_change(tsdf_volume *v) {
     return TSDF_OK;
 }
 
-// (can: the view allows the cell-parallel cast at all -- a projection, sizes within the formats; returns whether the STATIC rules
-// prefer it: the choice where nothing has been measured, and the bound on what a trial may cost, choose_cast)
-static bool choose_cell_cast(const tsdf_volume *v, const RayParams &rp, EntryParams &ep, bool *can = nullptr, bool *trial_ok = nullptr) {
+// -> true: the cell-parallel cast (ep filled), by the static rules below
+static bool choose_cell_cast(const tsdf_volume *v, const RayParams &rp, EntryParams &ep) {
     const int mode = tuning().ray_cells;
-    if (can) *can = false;
-    if (trial_ok) *trial_ok = false;
     // (a list entry: 10 bits of each brick coordinate; a record of the cast: 13 bits of sample index;
     // ... and a brick's pairs are counted in 31 bits: 64 cells that each ask every pixel)
     if (mode == 0 || v->occ.fine_count() >= ((size_t)1 << 30) || v->occ.nbx > 1024u || v->occ.nby > 1024u || v->occ.nbz > 1024u ||
@@ -1058,7 +1055,6 @@ static bool choose_cell_cast(const tsdf_volume *v, const RayParams &rp, EntryPar
     // pixels a cell -- one wave's work for milliseconds without the parts.  (Its cost hides behind the ray records since the list's
     // workgroups start first: 11.0 -> 11.3 us; TSDF_RAY_CELLS_LOOK=0 switches it off for study.)
     ep.cell_pairs = tuning().ray_cells_look ? (uint32_t)tuning().ray_cells_pairs : 0u;
-    if (can) *can = true;
     if (mode == 2) return true;
     // What the cast costs is the number of (mixed cell, pixel) pairs: a voxel that covers several pixels makes every cell a dozen pairs
     // or more.  Measured over grid sizes on one scene (640x480, the camera 2 m from the centre of 3 m of volume; cast stage, march /
@@ -1068,13 +1064,8 @@ static bool choose_cell_cast(const tsdf_volume *v, const RayParams &rp, EntryPar
     // cell-parallel cast's list length (arbitrary fields: every brick flagged).  From inside the volume the view holds surface after
     // surface behind the first -- every mixed cell is looked at, hidden or not: 4.2 M pairs at 1024^3 against 2.0 M for the view from
     // outside, 0.29 ms against the march's 0.215 -- and the march kernels keep it (TSDF_RAY_CELLS=2 takes the cell-parallel cast there too).
-    const uint32_t listed_ = v->cell_cast_host ? *v->cell_cast_host : 0u;
-    // (a trial of the cast where these rules keep the march: its cost must be bounded -- the list within the limit, and from outside a
-    // voxel of at most 64 pixels at the nearest depth a sample can have; from inside the volume the list with its parts is the bound)
     // (never from inside the volume: nothing bounds how close a surface is, and on the stream of BASELINE configs[3] single frames next to
     // a wall took the cells 10 ms -- 0.278 ms a cast over the stream against the march's 0.207, profiles/r06_cells_front_to_back.txt)
-    if (trial_ok) *trial_ok = listed_ <= (uint32_t)tuning().ray_cells_limit && ep.z_clip > 0.0f &&
-                              vs_max * std::max(std::fabs(ep.k[0][0]), std::fabs(ep.k[1][1])) <= 64.0f * (2.0f * ep.z_clip);
     if (ep.z_clip == 0.0f) return false;
     if (!(footprint <= tuning().ray_cells_footprint)) return false;
     // ... and a camera that could have a surface right in front of it: a wall six voxels behind the face it looks through, the camera
@@ -1095,126 +1086,6 @@ static bool choose_cell_cast(const tsdf_volume *v, const RayParams &rp, EntryPar
     }
     return false;
 }
-
-// Which cast a volume's stream of casts takes, from MEASURED times (round 6; TSDF_RAY_CELLS=1 with TSDF_RAY_CHOOSER=1 -- built, measured,
-// OFF by default: see the end of this comment).  The static rules of
-// choose_cell_cast have cliffs on both sides -- a flat wall in front of the camera is 0.094 ms marched and 0.122 with the cells, the
-// bench's room 0.149 and 0.100; a view from inside a 1024^3 volume 0.197 and 0.175 now that the list is sorted front to back, a
-// close-up of a wall 0.08 and 2.0 -- and no rule on footprints tells these apart.  So: one cast in sixteen is bracketed with two events
-// on the volume's stream, from in front of its flag refresh to behind its resolve kernel (5-6 us each: 0.7 us a cast on average; read
-// when a later cast finds them complete, nothing waits), the cast not taken is tried once every `gap` casts where the static rules
-// bound what the trial can cost, and the faster of the two runs.  (The brackets, not the dominant launches' own timestamps: those
-// miss what differs between the casts around them -- the march's reach summary is rebuilt whenever integrate has set a flag -- and in
-// the pipelined step they called the march, 0.135 ms of its two kernels, equal to the cells' 0.115 + list + resolve while every step
-// with it was 8 % slower.  Where the host enqueues slower than the GPU runs the brackets hold the host's gaps, the same for both casts.)  A trial that loses doubles the gap (64 ... 4096 casts), one that loses by 3 x is not repeated before the camera has moved
-// a tenth of the volume or turned by 10 degrees.  Scheduling only: both casts give the same bits (tests/test_parity_raycast.py).
-// Why it is off by default (profiles/r06_cast_chooser.txt): a trial has to be SHORT to be cheap and LONG to be fair.  The march reaches its
-// steady state over several casts -- the reach summary, the entry bound it leaves for the next cast, the dispatch order it learns: on the
-// wall scene 0.183 ms in a trial's first cast, 0.112 in the second, 0.121 / 0.111 in the third / fourth, 0.096 in a stream of its own -- so
-// trials of up to four casts call the march lost or even where it wins by a fifth, while on the bench scene each trial is three or four steps
-// at 1.5 x the median.  The static rules stay the default; the chooser is there for streams that sit in one of their cliffs.
-constexpr int kTrialCasts = 4;
-static void chooser_poll(tsdf_volume *v) {
-    CastChooser &c = v->chooser;
-    if (!c.pending || hipEventQuery(c.ev[1]) != hipSuccess) { (void)hipGetLastError(); return; }
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c.ev[0], c.ev[1]) == hipSuccess && ms > 0.0f) {
-        const int k = c.pending_kind;
-        if (tuning().debug_rays) fprintf(stderr, "tsdf: chooser: cast %llu measured %s %.4f ms%s (march %.4f, cells %.4f so far)\n", (unsigned long long)c.casts, k ? "cells" : "march", ms, c.pending_trial ? " [trial]" : "", c.ms[0], c.ms[1]);
-        // (the first casts of a kind run cold -- flags just rebuilt, nothing in the caches: 0.34 ms for a cast that takes 0.10 -- so the
-        // smaller of the first three counts, the mean of old and new after that)
-        c.ms[k] = c.seen[k] == 0 ? ms : (c.seen[k] < 3 ? std::min(c.ms[k], ms) : 0.5f * (c.ms[k] + ms));
-        c.seen[k]++;
-        c.measured_at[k] = c.casts;
-        if (c.pending_trial) {
-            const int other = 1 - k;
-            const bool lost = c.seen[other] && ms > 1.05f * c.ms[other];
-            c.gap = tuning().ray_chooser == 2 ? 3u : (lost ? std::min(c.gap * 2u, 4096u) : 64u);
-            c.blocked = lost && ms > 3.0f * c.ms[other] && tuning().ray_chooser != 2;   // (until the view has changed: chooser_view_moved)
-            c.next_trial = c.casts + c.gap;
-        }
-    } else {
-        (void)hipGetLastError();
-    }
-    c.pending = false;
-}
-static bool chooser_view_moved(const tsdf_volume *v, const RayParams &rp) {
-    const CastChooser &c = v->chooser;
-    const float dx = rp.origin.x - c.trial_origin[0], dy = rp.origin.y - c.trial_origin[1], dz = rp.origin.z - c.trial_origin[2];
-    const float reach = 0.1f * std::max(v->g.phys.x, std::max(v->g.phys.y, v->g.phys.z));
-    const float dot = rp.rot.m13 * c.trial_axis[0] + rp.rot.m23 * c.trial_axis[1] + rp.rot.m33 * c.trial_axis[2];
-    const float n2 = rp.rot.m13 * rp.rot.m13 + rp.rot.m23 * rp.rot.m23 + rp.rot.m33 * rp.rot.m33;
-    const float m2 = c.trial_axis[0] * c.trial_axis[0] + c.trial_axis[1] * c.trial_axis[1] + c.trial_axis[2] * c.trial_axis[2];
-    return !(dx * dx + dy * dy + dz * dz <= reach * reach) || !(dot >= 0.985f * std::sqrt(n2 * m2));
-}
-// -> true: the cell-parallel cast (ep filled); *sample: bracket this cast with the chooser's events
-static bool choose_cast(tsdf_volume *v, const RayParams &rp, EntryParams &ep, bool *sample) {
-    *sample = false;
-    bool can = false, trial_ok = false;
-    const bool by_rules = choose_cell_cast(v, rp, ep, &can, &trial_ok);
-    if (tuning().ray_cells != 1 || !tuning().ray_chooser) return by_rules;
-    CastChooser &c = v->chooser;
-    if (c.gap == 0u) {   // (a new volume, or one that was cleared: the first trial after 64 casts)
-        c.gap = 64u;
-        c.next_trial = c.casts + (tuning().ray_chooser == 2 ? 3u : 64u);   // (2: a test aid -- a trial every few casts, whatever the times say)
-    }
-    chooser_poll(v);
-    c.casts++;
-    if (!can) return false;
-    int kind = by_rules ? 1 : 0;
-    // both measured, and not long ago: the faster one (5 % of hysteresis towards the one that ran last)
-    const bool fresh[2] = {c.seen[0] && c.casts - c.measured_at[0] <= 8192u, c.seen[1] && c.casts - c.measured_at[1] <= 8192u};
-    if (fresh[0] && fresh[1]) {
-        const float bias0 = c.last_kind == 0 ? 0.95f : 1.0f, bias1 = c.last_kind == 1 ? 0.95f : 1.0f;
-        kind = c.ms[1] * bias1 <= c.ms[0] * bias0 ? 1 : 0;
-    }
-    bool trial = false;
-    if (c.trial_left > 0) {
-        // A trial is kTrialCasts casts of the other kind, the LAST of them measured: the first march after a run of cell casts rebuilds
-        // the reach summary and has no dispatch order learnt, the first cell cast its list's length unknown -- 0.18 ms for a march that
-        // takes 0.09 from its fourth cast on -- the entry bound it leaves for the next cast, the order it learns (the wall scene: trials of one, two and three casts called it lost: 0.183, 0.112, 0.121 ms).
-        kind = c.trial_kind;
-        if (kind == 1 && !can) { c.trial_left = 0; kind = 0; }
-        else if (c.trial_left > 1) c.trial_left--;
-        else if (!c.pending) { trial = true; c.trial_left = 0; }   // (its measured cast; waits a cast while an earlier sample is still out)
-    } else if (!c.pending && c.casts >= c.next_trial && (!c.blocked || chooser_view_moved(v, rp))) {
-        const int other = 1 - kind;
-        // A trial is a slow step when it loses (the march on the bench scene: + 0.06 ms), so none is made that cannot win: the cast that
-        // runs is measured anyway, and the other one's best case is known -- the march 0.092 ms for 640 x 480 rays on a wall in front of
-        // the camera, the cells 0.098 on the bench's room (whole casts, per pixel; profiles/r06_cast_chooser.txt) -- a cast already within 15 % of
-        // that stays.
-        const float mpix = (float)rp.width * (float)rp.height * 1.0e-6f, best_other = (other == 0 ? 0.30f : 0.32f) * mpix;
-        const bool could_win = !c.seen[kind] || c.ms[kind] > 1.15f * best_other || tuning().ray_chooser == 2;
-        if (!could_win) {
-            c.next_trial = c.casts + c.gap;
-        } else if (other == 0 || trial_ok) {   // (the march is always affordable; the cells where the static bound says so)
-            kind = other;
-            c.trial_kind = other;
-            c.trial_left = kTrialCasts - 1;   // (this cast is the first of them)
-            c.next_trial = c.casts + c.gap;   // (replaced when the trial's measurement arrives)
-            c.blocked = false;
-            c.trial_origin[0] = rp.origin.x; c.trial_origin[1] = rp.origin.y; c.trial_origin[2] = rp.origin.z;
-            c.trial_axis[0] = rp.rot.m13; c.trial_axis[1] = rp.rot.m23; c.trial_axis[2] = rp.rot.m33;
-        } else {
-            c.next_trial = c.casts + c.gap;
-        }
-    }
-    if (kind == 1 && (v->cell_cast_host ? *v->cell_cast_host : 0u) > (uint32_t)tuning().ray_cells_limit) kind = 0;   // (never past the list's limit)
-    if (!c.pending && c.casts > 1u && (trial || (c.trial_left == 0 && (c.seen[kind] < 3u || (c.casts & 15u) == 0u)))) {
-        if (!c.ev[0]) {
-            if (hipEventCreate(&c.ev[0]) != hipSuccess || hipEventCreate(&c.ev[1]) != hipSuccess) { (void)hipGetLastError(); c.ev[0] = nullptr; }
-        }
-        if (c.ev[0]) {
-            *sample = true;
-            c.pending_kind = kind;
-            c.pending_trial = trial;
-        }
-    }
-    c.last_kind = kind;
-    return kind == 1;
-}
-// a whole-volume cast of the kind chosen, bracketed for the chooser when it asks
-static int cast_whole(tsdf_volume *v, RayParams &rp, float *out, float *normals, const float *depth_inv_pose, uint16_t *depth_out);
 
 // The production march: process_ray_kernel over the sample ranges of every ray with a pass budget, process_ray_tail_kernel
 // for the stretches it handed over, resolve_hits_kernel for the vertices (packed float3, or {k, t} records for a slab).
@@ -1325,8 +1196,7 @@ static int march_and_resolve(tsdf_volume *v, RayParams &rp, float *out, float *n
         }
         CellCast cc = {reinterpret_cast<RayRecord *>(v->cell_rays), reinterpret_cast<uint2 *>(v->cell_bricks), v->tail_count + 3, v->cell_cast_host, cells->cell_pairs,
                        sort_list ? v->tail_count + 4 : nullptr, reinterpret_cast<uint2 *>(v->cell_bricks) + v->cell_bricks_cap, depth0, depth_scale,
-                       v->dist, tail.best, v->release_word, v->release_value};
-        v->release_word = nullptr;   // (taken)
+                       v->dist, tail.best};
         const size_t table_lds = ((size_t)kMaxSamples + 1) * sizeof(float);
         const uint32_t n_ray_blocks = (uint32_t)((n_pix + 255) / 256);
         const uint32_t n_list_blocks = (uint32_t)std::min<size_t>((v->occ.fine_count() / 4 + 255) / 256 + 1, 2048);
@@ -1367,7 +1237,6 @@ static int march_and_resolve(tsdf_volume *v, RayParams &rp, float *out, float *n
                 TSDF_LAUNCH_TIMED(v, 2, (cast_cells_kernel<SLAB, false>), cgrid, dim3(256), v->dist, v->g, rp, *cells, v->occ, v->t_table, cc, tail.best);
         }
         TSDF_HIP(hipGetLastError(), "cell-parallel cast failed");
-        if (v->after_bulk) TSDF_HIP(hipEventRecord(v->after_bulk, v->stream), "process_ray: bulk kernel event");
     } else {
     rp.seg_len = (kMaxSamples + n_segments - 1) / n_segments;
     rp.slab_ranges = SLAB ? (uint32_t)n_segments : 0u;
@@ -1382,7 +1251,6 @@ static int march_and_resolve(tsdf_volume *v, RayParams &rp, float *out, float *n
         TSDF_LAUNCH_TIMED_LDS(v, 1, (process_ray_kernel<SLAB, false, true, false, true, true>), grid, dim3(256), table_lds, v->dist, v->g, rp,
                               (float *)nullptr, (unsigned long long *)nullptr, (unsigned int *)nullptr, v->occ, v->t_table, tail);
     TSDF_HIP(hipGetLastError(), "process_ray failed");
-    if (v->after_bulk) TSDF_HIP(hipEventRecord(v->after_bulk, v->stream), "process_ray: bulk kernel event");
     // persistent workgroups: groups of 16 lanes, fetching queue entries until none is left
     // (the default group width is compiled in; another one, a tuning aid, takes the variant that reads it at run time)
     const bool fixed_lanes = tail_lanes() == kTailLanesDefault;
@@ -1426,26 +1294,10 @@ static int cast_whole(tsdf_volume *v, RayParams &rp, float *out, float *normals,
     int rc = count_after_bulk_change(v);
     if (rc != TSDF_OK) return rc;
     EntryParams view;
-    bool sample = false;
-    const bool cells = choose_cast(v, rp, view, &sample);
-    CastChooser &c = v->chooser;
-    if (sample && hipEventRecord(c.ev[0], v->stream) != hipSuccess) { (void)hipGetLastError(); sample = false; }
+    const bool cells = choose_cell_cast(v, rp, view);
     if (cells) rc = occupancy_flags_refresh(v); else rc = refresh_for_cast(v, rp);
     if (rc != TSDF_OK) return rc;
-    rc = cells ? march_and_resolve<false>(v, rp, out, normals, depth_inv_pose, depth_out, &view) : march_and_resolve<false>(v, rp, out, normals, depth_inv_pose, depth_out);
-    if (sample && rc == TSDF_OK) {
-        if (hipEventRecord(c.ev[1], v->stream) == hipSuccess) c.pending = true; else (void)hipGetLastError();
-    }
-    return rc;
-}
-
-// Would tsdf_raycast_device take the cell-parallel cast for this view now?  (tsdf_pipeline_step: how to release its second stream.)
-bool raycast_takes_cells(const tsdf_volume *v, uint32_t width, uint32_t height, const float pose[16], const float kinv[9]) {
-    if (!v || v->z_begin != 0 || v->z_end != v->g.Z || check_ray_args(v, width, height, pose, kinv) != TSDF_OK) return false;
-    if (count_after_bulk_change(const_cast<tsdf_volume *>(v)) != TSDF_OK) return false;
-    RayParams rp = make_params(v, width, height, pose, kinv);
-    EntryParams view;
-    return choose_cell_cast(v, rp, view);
+    return cells ? march_and_resolve<false>(v, rp, out, normals, depth_inv_pose, depth_out, &view) : march_and_resolve<false>(v, rp, out, normals, depth_inv_pose, depth_out);
 }
 
 }  // namespace tsdf

@@ -36,7 +36,6 @@ const Tuning &tuning() {
         u.ray_cells_limit = std::max(num("TSDF_RAY_CELLS_LIMIT", 131072), 0);
         u.ray_cells_grid = clamp(num("TSDF_RAY_CELLS_GRID", 2048), 1, 65535);
         u.ray_cells_sort = clamp(num("TSDF_RAY_CELLS_SORT", 1), 0, 2);
-        u.ray_chooser = clamp(num("TSDF_RAY_CHOOSER", 0), 0, 2);
         u.ray_cells_pairs = clamp(num("TSDF_RAY_CELLS_PAIRS", 1024), 0, 1 << 24);
         u.ray_cells_look = clamp(num("TSDF_RAY_CELLS_LOOK", 1), 0, 1);
         { const char *fp = getenv("TSDF_RAY_CELLS_FOOTPRINT"); u.ray_cells_footprint = fp ? (float)atof(fp) : 10.0f; }
@@ -50,17 +49,12 @@ const Tuning &tuning() {
         u.ray_learned_order = num("TSDF_RAY_LEARNED_ORDER", 1) != 0;
         u.ray_heavy_passes = std::max(num("TSDF_RAY_HEAVY_PASSES", 0), 0);
         u.ray_entry_bound = num("TSDF_RAY_ENTRY_BOUND", 1) != 0;
-        u.icp_persistent = num("TSDF_ICP_PERSISTENT", 0);
         u.occ_rebuild_period = std::max(num("TSDF_OCC_REBUILD_PERIOD", 16), 0);
         u.occ_scan_all = num("TSDF_OCC_SCAN_ALL", 0) != 0;
         u.reach_lds = num("TSDF_REACH_LDS", 0) != 0;
         u.int_grid_per_cu = num("TSDF_INT_GRID_PER_CU", 0);
         u.weight_pack = num("TSDF_WEIGHT_PACK", 8);
         if (u.weight_pack != 0 && u.weight_pack != 16) u.weight_pack = 8;
-        u.pipe_release = clamp(num("TSDF_PIPE_RELEASE", 0), 0, 2);
-        u.pipe_host_wait = num("TSDF_PIPE_HOST_WAIT", 0) != 0;
-        u.pipe_word_release = num("TSDF_PIPE_WORD_RELEASE", 0) != 0;
-        u.event_scope = clamp(num("TSDF_EVENT_SCOPE", 2), 0, 2);
         u.timing_bracket = num("TSDF_TIMING_BRACKET", 0) != 0;
         u.verbose = getenv("TSDF_VERBOSE") != nullptr;
         u.debug_rays = getenv("TSDF_DEBUG_RAYS") != nullptr;
@@ -934,8 +928,6 @@ int tsdf_volume_destroy(tsdf_volume *v) {
     if (v->cell_rays) (void)hipFree(v->cell_rays);
     if (v->cell_bricks) (void)hipFree(v->cell_bricks);
     if (v->cell_count_scratch) (void)hipFree(v->cell_count_scratch);
-    for (int i = 0; i < 2; i++)
-        if (v->chooser.ev[i]) (void)hipEventDestroy(v->chooser.ev[i]);
     if (v->cell_cast_host) (void)hipHostFree(v->cell_cast_host);
     if (v->ray_heavy) (void)hipFree(v->ray_heavy);
     if (v->ray_order) (void)hipFree(v->ray_order);
@@ -995,10 +987,6 @@ int tsdf_volume_clear(tsdf_volume *v) {
     v->occ_dirty = 0;
     v->occ_tighten_due = 0;
     if (v->cell_cast_host) *v->cell_cast_host = 0;   // (the cell-parallel cast's list of an empty volume; a cast in flight may still write the old count: it only costs a march)
-    v->chooser.seen[0] = v->chooser.seen[1] = 0;   // (what was measured on the old contents says nothing about the new: choose_cast starts over)
-    v->chooser.gap = 0;
-    v->chooser.blocked = false;
-    v->chooser.trial_left = 0;
     v->prepared_valid = 0;   // (a brick list prepared ahead bakes in the offset at clear time)
     v->integrations_since_rebuild = v->integrations_total = 0;
     // initialise_deformation bakes the CURRENT offset into the node translations (Q1)
