@@ -223,19 +223,25 @@ int tsdf_volume_last_distance_stores(const tsdf_volume *volume, uint64_t *count)
  *     bits 24-31 -- x fastest like the distances; allocated and zeroed by tsdf_volume_enable_colour(v, 1) (4 bytes a voxel: 512 MiB
  *     at 512^3), freed by (v, 0), zeroed by tsdf_volume_clear.
  *   Integrate: tsdf_integrate_colour updates distances, weights, occupancy and counters with exactly the bits of tsdf_integrate for
- *     the same depth and camera, then updates the colour of every voxel that update touched (in the frustum, depth > 0,
+ *     the same depth and camera, and updates the colour of every voxel that update touched (in the frustum, depth > 0,
  *     sdf >= -trunc: src/TSDF/TSDFVolume.cu:337-366) whose sdf is also <= +trunc, from the pixel (u, v) whose depth it used.  rgb
  *     is 8-bit interleaved RGB, width x height x 3, REGISTERED to the depth image (same camera, same size: TUM's depth frames are
  *     registered to its RGB frames).  Per channel, with c the pixel's value, in uint32 arithmetic:
  *         new = (old * n + c + ((n + 1) >> 1)) / (n + 1);     n' = min(n + 1, 255)
- *     (with n capped, later observations blend at 1/256).  Voxels with sdf > trunc (free space) keep their colour.
+ *     (with n capped, later observations blend at 1/256).  Voxels with sdf > trunc (free space) keep their colour.  Where the
+ *     volume's weights are packed counts and the camera standard, the packed integrate kernel makes the colour update itself
+ *     (integrate_packed_colour_kernel); otherwise a colour pass follows the integrate kernel on the same stream and brick list.  The
+ *     words are the same either way.
+ *   Per frame: tsdf_pipeline_step_colour and tsdf_tracker_integrate_colour (below) are tsdf_pipeline_step and
+ *     tsdf_tracker_integrate with a colour integrate of the filtered frame; tsdf_pipeline_step and tsdf_tracker_integrate leave the
+ *     colours of a colour-enabled volume alone.
  *   Sampling: a world point p (mm) takes voxel i = (int)floorf(((p - offset) - offset_at_clear) / voxel_size) per axis, in fp32 in
  *     that order -- the cell whose centre as integrate forms it is nearest -- and reads that voxel's {r, g, b}; (0, 0, 0) for a NaN
  *     coordinate, an index outside the grid, or a voxel with n == 0.
  *   Refused (TSDF_ERR_INVALID, with a message): enabling colour on a Z-slab volume (tsdf_volume_create_slab); colour integrate on a
  *     volume whose deformation nodes are explicit (tsdf_volume_deformation / tsdf_volume_set_deformation); colour integrate,
  *     sampling or data access on a volume without colour enabled.
- *   Out of scope: colour in tsdf_pipeline_step, the tracker and kinfu_stream; slab (multi-GPU) colour; trilinear colour
+ *   Out of scope: slab (multi-GPU) colour, in a volume or a sharded pipeline; colour sampled inside the cast kernels; trilinear colour
  *     interpolation; colour with explicit deformation nodes; RGB cameras with intrinsics or extrinsics of their own. */
 int tsdf_volume_enable_colour(tsdf_volume *volume, int enabled);   /* 1: allocate zeroed (kept if already enabled), 0: free */
 int tsdf_volume_colour_enabled(const tsdf_volume *volume, int *enabled);
@@ -243,7 +249,7 @@ int tsdf_volume_colours(const tsdf_volume *volume, uint32_t **device_ptr);   /* 
 /* Blocking copies of every resident voxel's dword. */
 int tsdf_volume_get_colour_data(const tsdf_volume *volume, uint32_t *host);
 int tsdf_volume_set_colour_data(tsdf_volume *volume, const uint32_t *host);
-/* tsdf_integrate / tsdf_integrate_device with the colour pass behind the integrate kernel (same stream, same brick list). */
+/* tsdf_integrate / tsdf_integrate_device with the colour update of the same frame (same stream, same brick list). */
 int tsdf_integrate_colour(tsdf_volume *volume, const uint16_t *host_depth, const uint8_t *host_rgb, uint32_t width, uint32_t height,
                           const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]);
 int tsdf_integrate_colour_device(tsdf_volume *volume, const uint16_t *device_depth, const uint8_t *device_rgb, uint32_t width,
@@ -405,6 +411,15 @@ int tsdf_pipeline_create(tsdf_volume *volume, const tsdf_bilateral *filter, uint
 int tsdf_pipeline_step(tsdf_pipeline *pipeline, const uint16_t *device_depth, const tsdf_camera_matrices *camera,
                        float *device_vertices, float *device_normals, const uint16_t *next_device_depth /* or NULL */,
                        const tsdf_camera_matrices *next_camera /* or NULL */);
+/* tsdf_pipeline_step with a colour integrate of the FILTERED frame and device_rgb (3 * width * height bytes, registered to the depth
+ * image; it must stay valid until this step's integrate has run on the step's stream: nothing of it is read ahead).  device_colours
+ * (3 * width * height bytes, or NULL): the colour of the voxel every vertex of the ray cast lies in, sampled on the step's stream as
+ * tsdf_raycast_colour_device samples it.  Distances, weights, vertices and normals are those of tsdf_pipeline_step.  Refused
+ * (TSDF_ERR_INVALID, with a message): a volume without colour enabled, a sharded pipeline, a NULL rgb frame. */
+int tsdf_pipeline_step_colour(tsdf_pipeline *pipeline, const uint16_t *device_depth, const uint8_t *device_rgb,
+                              const tsdf_camera_matrices *camera, float *device_vertices, float *device_normals,
+                              uint8_t *device_colours /* or NULL */, const uint16_t *next_device_depth /* or NULL */,
+                              const tsdf_camera_matrices *next_camera /* or NULL */);
 int tsdf_pipeline_synchronize(tsdf_pipeline *pipeline);
 /* The pipeline's hipStream_t handles (side_stream is NULL without TSDF_PIPELINE_OVERLAP), e.g. to order the caller's own work. */
 int tsdf_pipeline_streams(const tsdf_pipeline *pipeline, void **main_stream, void **side_stream);
@@ -430,6 +445,9 @@ int tsdf_tracker_filter(tsdf_tracker *tracker, const uint16_t *device_depth);
 int tsdf_tracker_align(tsdf_tracker *tracker, const tsdf_camera_matrices *previous, double T_prev_curr[16] /* in: start, out */,
                        float *last_error, float *last_inliers);
 int tsdf_tracker_integrate(tsdf_tracker *tracker, const tsdf_camera_matrices *camera);
+/* tsdf_tracker_integrate plus the colour of device_rgb (as tsdf_pipeline_step_colour: the filtered frame, rgb valid until the
+ * integrate has run on the tracker's stream; refused without colour enabled or with a NULL rgb frame). */
+int tsdf_tracker_integrate_colour(tsdf_tracker *tracker, const tsdf_camera_matrices *camera, const uint8_t *device_rgb);
 int tsdf_tracker_synchronize(tsdf_tracker *tracker);
 int tsdf_tracker_streams(const tsdf_tracker *tracker, void **main_stream, void **side_stream);
 /* The ICP inputs of the last aligned frame: the rendered model depth and the filtered frame (width * height uint16, device). */

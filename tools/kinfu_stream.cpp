@@ -8,7 +8,13 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour]
+//   --colour: colour fusion as well -- every frame's <dir>/rgb/<stem>.png read with TUMDataLoader::next(pose, rgb) and kept in HBM
+//           beside its depth frame, colour enabled on the volume, tsdf_pipeline_step_colour (with --track tsdf_tracker_integrate_colour)
+//           for every step; the line gains "colour": true and the last picture's colour checksum, --dump colours.u8 (the last picture's
+//           colours) and colour.u32 (the volume's colour words).  A missing colour image, or one not the depth frame's size, ends the
+//           run (exit 1); single-volume only.  With --track there is no picture: the line gains "colour": true alone and --dump
+//           writes colour.u32.
 //   --planes Z: a grid of n x n x Z voxels over the same physical cube (flat voxels along z): many planes to shard at a small cost
 //   --validate-merge (with --ranks): SURVEY.md 8e mode B after the timed steps -- every rank all-gathers the distance slabs, casts the
 //           whole volume the single-volume way and compares its bits with the merged picture (tsdf_slab_validate_merge)
@@ -106,7 +112,7 @@ int main(int argc, char **argv) {
     unsigned n = 512;
     float physical = 3000.0f;
     int K = 20, Wu = 5;
-    bool overlap = true, cull_ahead = true, track = false, validate_merge = false;
+    bool overlap = true, cull_ahead = true, track = false, validate_merge = false, colour = false;
     unsigned planes = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -130,8 +136,9 @@ int main(int argc, char **argv) {
         else if (a == "--share-gpu") share_gpu = true;
         else if (a == "--planes") planes = (unsigned)std::atoi(value());
         else if (a == "--validate-merge") validate_merge = true;
+        else if (a == "--colour") colour = true;
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour]\n");
             return 2;
         }
     }
@@ -140,18 +147,31 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "kinfu_stream: -d <tum dir>, -k >= 1, -w >= 0, -n >= 1, 1 <= --ranks <= min(%d, grid), --track is single-volume\n", kMaxRanks);
         return 2;
     }
+    if (colour && ranks > 1) {
+        std::fprintf(stderr, "kinfu_stream: --colour is single-volume (colour is not supported on Z-slabs): drop --ranks\n");
+        return 2;
+    }
 
     // ---- the stream: every frame of the directory, in millimetres, with its ground-truth pose (kinfu.cpp:32-51) ----------
     std::vector<std::vector<uint16_t>> frames;
+    std::vector<std::vector<uint8_t>> rgb_frames;   // (--colour)
     std::vector<tsdf_camera_matrices> cams;
     std::vector<Eigen::Matrix4f> truth;
     uint32_t W = 0, H = 0;
     try {
         TUMDataLoader loader(dir);
+        std::unique_ptr<TUMDataLoader> colour_loader(colour ? new TUMDataLoader(dir) : nullptr);   // (--colour: the same records, in step)
         std::unique_ptr<Camera> camera(Camera::default_depth_camera());
-        Eigen::Matrix4f pose;
+        Eigen::Matrix4f pose, colour_pose;
+        std::vector<uint8_t> rgb;
         while (DepthImage *di = loader.next(pose)) {
             std::unique_ptr<DepthImage> image(di);
+            if (colour) {
+                // the depth frame is there, so a record without a frame here has no usable colour image (the loader has named the
+                // file on stderr): fusing black instead is not an option
+                std::unique_ptr<DepthImage> again(colour_loader->next(colour_pose, rgb));
+                if (!again) throw std::invalid_argument("frame " + std::to_string(frames.size()) + ": its colour image (rgb/) is missing, unreadable or not the depth frame's size");
+            }
             if (frames.empty()) {
                 W = image->width();
                 H = image->height();
@@ -159,6 +179,7 @@ int main(int argc, char **argv) {
                 throw std::invalid_argument("depth images of different sizes");
             }
             frames.emplace_back(image->data(), image->data() + (size_t)W * H);
+            if (colour) rgb_frames.push_back(rgb);
             camera->set_pose(pose);
             cams.push_back(matrices_of(*camera));
             truth.push_back(pose);
@@ -229,9 +250,15 @@ int main(int argc, char **argv) {
 
     // ---- everything resident in HBM before the clock starts ---------------------------------------------------------------
     uint16_t *depth_dev = nullptr;
+    uint8_t *rgb_dev = nullptr, *colours_dev = nullptr;
     float *vert_dev = nullptr, *norm_dev = nullptr;
     ok(tsdf_device_alloc(F * n_pix * sizeof(uint16_t), (void **)&depth_dev), "frames");
     for (size_t i = 0; i < F; i++) ok(tsdf_device_upload(depth_dev + i * n_pix, frames[i].data(), n_pix * sizeof(uint16_t)), "frames");
+    if (colour) {
+        ok(tsdf_device_alloc(F * n_pix * 3, (void **)&rgb_dev), "colour frames");
+        for (size_t i = 0; i < F; i++) ok(tsdf_device_upload(rgb_dev + i * n_pix * 3, rgb_frames[i].data(), n_pix * 3), "colour frames");
+        ok(tsdf_device_alloc(n_pix * 3, (void **)&colours_dev), "colour map");
+    }
     ok(tsdf_device_alloc(n_pix * 3 * sizeof(float), (void **)&vert_dev), "vertex map");
     ok(tsdf_device_alloc(n_pix * 3 * sizeof(float), (void **)&norm_dev), "normal map");
     tsdf_volume *vol = nullptr;
@@ -242,6 +269,7 @@ int main(int argc, char **argv) {
     const uint32_t z_begin = (uint32_t)((uint64_t)planes * rank / ranks), z_end = (uint32_t)((uint64_t)planes * (rank + 1) / ranks);   // equal plane counts
     if (ranks == 1) {
         ok(tsdf_volume_create(n, n, planes, physical, physical, physical, &vol), "volume");
+        if (colour) ok(tsdf_volume_enable_colour(vol, 1), "colour");
     } else {
         ok(tsdf_volume_create_slab(n, n, planes, physical, physical, physical, z_begin, z_end, &vol), "slab volume");
         if (use_rccl) {
@@ -290,7 +318,8 @@ int main(int argc, char **argv) {
                 camera->set_pose(next);
             }
             const tsdf_camera_matrices now = matrices_of(*camera);
-            ok(tsdf_tracker_integrate(trk, &now), "integrate");
+            if (colour) ok(tsdf_tracker_integrate_colour(trk, &now, rgb_dev + i * n_pix * 3), "integrate");
+            else ok(tsdf_tracker_integrate(trk, &now), "integrate");
             tracked.insert(tracked.end(), now.pose, now.pose + 16);
         }
         ok(tsdf_tracker_synchronize(trk), "synchronize");
@@ -299,14 +328,20 @@ int main(int argc, char **argv) {
         double dt2 = 0.0;
         for (int r = 0; r < 3; r++) dt2 += ((double)last(r, 3) - want(r, 3)) * ((double)last(r, 3) - want(r, 3));
         std::printf("{\"driver\": \"tools/kinfu_stream.cpp --track (C++, tsdf_tracker_*)\", \"grid\": %u, \"image\": [%u, %u], \"frames\": %zu, \"overlap\": %s, "
-                    "\"ms_per_frame\": %.4f, \"last_pose_translation_error_mm\": %.4f, \"last_icp_inliers\": %.0f, \"last_icp_error\": %.6g}\n",
+                    "\"ms_per_frame\": %.4f, \"last_pose_translation_error_mm\": %.4f, \"last_icp_inliers\": %.0f, \"last_icp_error\": %.6g",
                     n, W, H, n_track, overlap ? "true" : "false", n_track > first_timed ? elapsed * 1e3 / (double)(n_track - first_timed) : 0.0, std::sqrt(dt2),
                     inliers, error);
+        std::printf(colour ? ", \"colour\": true}\n" : "}\n");
         if (!dump_dir.empty()) {
             dump(dump_dir + "/poses.f32", tracked.data(), tracked.size() * sizeof(float));
             std::vector<float> a((size_t)n * n * planes);
             ok(tsdf_volume_get_distance_data(vol, a.data()), "distances");
             dump(dump_dir + "/distances.f32", a.data(), a.size() * sizeof(float));
+            if (colour) {
+                std::vector<uint32_t> c((size_t)n * n * planes);
+                ok(tsdf_volume_get_colour_data(vol, c.data()), "colour words");
+                dump(dump_dir + "/colour.u32", c.data(), c.size() * sizeof(uint32_t));
+            }
         }
         ok(tsdf_tracker_destroy(trk), "tracker");
         tsdf_icp_destroy(icp);
@@ -315,6 +350,8 @@ int main(int argc, char **argv) {
         (void)tsdf_device_free(depth_dev);
         (void)tsdf_device_free(vert_dev);
         (void)tsdf_device_free(norm_dev);
+        if (rgb_dev) (void)tsdf_device_free(rgb_dev);
+        if (colours_dev) (void)tsdf_device_free(colours_dev);
         return 0;
     }
     ok(tsdf_pipeline_create(vol, bil, W, H, overlap ? TSDF_PIPELINE_OVERLAP : 0, exch, &pipe), "pipeline");
@@ -322,7 +359,11 @@ int main(int argc, char **argv) {
     auto step = [&](int i) {
         const size_t f = (size_t)i % F, g = (size_t)(i + 1) % F;
         // (every step announces its successor, the last timed one too -- as bench.py does)
-        ok(tsdf_pipeline_step(pipe, depth_dev + f * n_pix, &cams[f], vert_dev, norm_dev, depth_dev + g * n_pix, cull_ahead ? &cams[g] : nullptr), "step");
+        if (colour)
+            ok(tsdf_pipeline_step_colour(pipe, depth_dev + f * n_pix, rgb_dev + f * n_pix * 3, &cams[f], vert_dev, norm_dev, colours_dev,
+                                         depth_dev + g * n_pix, cull_ahead ? &cams[g] : nullptr), "step");
+        else
+            ok(tsdf_pipeline_step(pipe, depth_dev + f * n_pix, &cams[f], vert_dev, norm_dev, depth_dev + g * n_pix, cull_ahead ? &cams[g] : nullptr), "step");
     };
     for (int i = 0; i < Wu; i++) step(i);
     ok(tsdf_pipeline_synchronize(pipe), "synchronize");
@@ -346,6 +387,13 @@ int main(int argc, char **argv) {
         bits_n += w;
     }
     for (size_t i = 0; i < n_pix; i++) hits += !std::isnan(V[3 * i]);
+    std::vector<uint8_t> colours;
+    long long bits_c = 0;   // (--colour) the sum of the last picture's colour bytes
+    if (colour) {
+        colours.resize(n_pix * 3);
+        ok(tsdf_device_download(colours.data(), colours_dev, colours.size()), "colour map");
+        for (uint8_t c : colours) bits_c += c;
+    }
     bool ranks_agree = true;
     if (shared) {   // the step is as long as its slowest rank; every rank holds the merged picture: the checksums must agree
         shared->elapsed[rank] = elapsed;
@@ -384,8 +432,10 @@ int main(int argc, char **argv) {
             std::printf("{\"driver\": \"tools/kinfu_stream.cpp (C++, tsdf_pipeline_step)\", ");
         std::printf("\"grid\": %u, \"planes\": %u, \"image\": [%u, %u], \"frames_in_directory\": %zu, "
                     "\"steps\": %d, \"warmup\": %d, \"overlap\": %s, \"cull_ahead\": %s, \"ms_per_step\": %.4f, \"value\": %.3f, \"unit\": \"Mvoxels/s\", "
-                    "\"last_frame_vertex_bits\": %lld, \"last_frame_normal_bits\": %lld, \"last_frame_hits\": %lld}\n",
+                    "\"last_frame_vertex_bits\": %lld, \"last_frame_normal_bits\": %lld, \"last_frame_hits\": %lld",
                     n, planes, W, H, F, K, Wu, overlap ? "true" : "false", cull_ahead ? "true" : "false", ms, voxels * K / elapsed / 1e6, bits_v, bits_n, hits);
+        if (colour) std::printf(", \"colour\": true, \"last_frame_colour_bits\": %lld", bits_c);
+        std::printf("}\n");
     }
 
     if (!dump_dir.empty() && ranks > 1) {   // the merged picture (rank 0) and every rank's slab of the volume (its own planes, without the halo)
@@ -409,6 +459,12 @@ int main(int argc, char **argv) {
         std::vector<float> poses;
         for (const tsdf_camera_matrices &m : cams) poses.insert(poses.end(), m.pose, m.pose + 16);
         dump(dump_dir + "/poses.f32", poses.data(), poses.size() * sizeof(float));
+        if (colour) {
+            dump(dump_dir + "/colours.u8", colours.data(), colours.size());
+            std::vector<uint32_t> c((size_t)n * n * planes);
+            ok(tsdf_volume_get_colour_data(vol, c.data()), "colour words");
+            dump(dump_dir + "/colour.u32", c.data(), c.size() * sizeof(uint32_t));
+        }
     }
 
     ok(tsdf_pipeline_destroy(pipe), "pipeline");
@@ -418,6 +474,8 @@ int main(int argc, char **argv) {
     (void)tsdf_device_free(depth_dev);
     (void)tsdf_device_free(vert_dev);
     (void)tsdf_device_free(norm_dev);
+    if (rgb_dev) (void)tsdf_device_free(rgb_dev);
+    if (colours_dev) (void)tsdf_device_free(colours_dev);
     std::fflush(stdout);
     return (shared && !ranks_agree) ? 1 : 0;
 }

@@ -138,6 +138,7 @@ _SIGS = {
     "tsdf_slab_exchange_destroy": (_i, [_vp]),
     "tsdf_pipeline_create": (_i, [_vp, _vp, _u32, _u32, _i, _vp, C.POINTER(_vp)]),
     "tsdf_pipeline_step": (_i, [_vp, _vp, C.POINTER(CameraMatrices), _vp, _vp, _vp, C.POINTER(CameraMatrices)]),
+    "tsdf_pipeline_step_colour": (_i, [_vp, _vp, _vp, C.POINTER(CameraMatrices), _vp, _vp, _vp, _vp, C.POINTER(CameraMatrices)]),
     "tsdf_pipeline_synchronize": (_i, [_vp]),
     "tsdf_pipeline_streams": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_pipeline_hit_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -146,6 +147,7 @@ _SIGS = {
     "tsdf_tracker_filter": (_i, [_vp, _vp]),
     "tsdf_tracker_align": (_i, [_vp, C.POINTER(CameraMatrices), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tsdf_tracker_integrate": (_i, [_vp, C.POINTER(CameraMatrices)]),
+    "tsdf_tracker_integrate_colour": (_i, [_vp, C.POINTER(CameraMatrices), _vp]),
     "tsdf_tracker_synchronize": (_i, [_vp]),
     "tsdf_tracker_streams": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_tracker_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

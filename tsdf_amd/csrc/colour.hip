@@ -124,7 +124,7 @@ int launch_colour_integrate(tsdf_volume *v, const BrickGrid &bg, const Mat44 &ip
 }
 
 int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
-                          const float inv_pose[16], const float k[9], const float kinv[9]);   // integrate.hip
+                          const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max);   // integrate.hip
 
 static int sample_colours(const tsdf_volume *v, uint64_t n, const float *d_points, uint8_t *d_rgb, hipStream_t stream) {
     if (n == 0) return TSDF_OK;
@@ -213,7 +213,7 @@ int tsdf_integrate_colour_device(tsdf_volume *v, const uint16_t *device_depth, c
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate_colour: empty depth map");
     TSDF_REQUIRE(!v->nodes, "tsdf_integrate_colour: not supported once the deformation nodes are explicit (deformation() / set_deformation())");
     (void)pose;   // (as tsdf_integrate: the reference never reads it)
-    return integrate_with_colour(v, device_depth, device_rgb, width, height, inv_pose, k, kinv);
+    return integrate_with_colour(v, device_depth, device_rgb, width, height, inv_pose, k, kinv, nullptr);
 }
 
 int tsdf_integrate_colour(tsdf_volume *v, const uint16_t *host_depth, const uint8_t *host_rgb, uint32_t width, uint32_t height,

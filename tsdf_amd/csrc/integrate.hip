@@ -91,7 +91,7 @@ __device__ inline void mark_occupied(const OccGrid &occ, uint32_t vx, uint32_t v
 // integrate_packed.hip
 int launch_integrate_packed_kernel(tsdf_volume *v, dim3 grid, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, uint32_t width,
                                    uint32_t height, const uint16_t *d_depth, unsigned long long *counter_arg, const uint4 *boxes,
-                                   const uint2 *coords, const uint32_t *count, const float4 *plane_const);
+                                   const uint2 *coords, const uint32_t *count, const float4 *plane_const, const uint8_t *d_rgb);
 
 // colour.hip
 int launch_colour_integrate(tsdf_volume *v, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, const Mat33 &mkinv, bool std_camera,
@@ -734,9 +734,13 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
 #define LAUNCH(DEF, CNT, STDC)                                                                                       \
     TSDF_LAUNCH_TIMED(v, 0, (integrate_kernel<DEF, CNT, STDC>), grid, block, v->dist, v->weight, v->nodes,          \
                       g, bg, ip, mk, mkinv, width, height, d_depth, counter_arg, v->occ, v->brick_list, boxes, count, plane_const, v->touched)
+    // tsdf_integrate_colour: integrate_packed_kernel's colour variant makes the colour update itself (its rgb look-ups are 32-bit byte
+    // offsets); every other kernel is followed by the separate colour pass below
+    const bool fused_colour = d_rgb && v->wmode != 0 && (size_t)width * height * 3u <= 0x7fffffffu;
     if (v->wmode != 0) {
         const int rcp = launch_integrate_packed_kernel(v, dim3((unsigned)n_bricks), bg,   // (one brick per workgroup, always)
-                                                        ip, mk, width, height, d_depth, counter_arg, boxes, coords, count, plane_const);
+                                                        ip, mk, width, height, d_depth, counter_arg, boxes, coords, count, plane_const,
+                                                        fused_colour ? d_rgb : nullptr);
         if (rcp != TSDF_OK) return rcp;
         v->weight_bound++;
     } else if (v->nodes) {
@@ -748,7 +752,7 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     }
 #undef LAUNCH
     TSDF_HIP(hipGetLastError(), "Integrate kernel failed");
-    if (d_rgb) {   // tsdf_integrate_colour: the colour pass over the same brick list, right behind the integrate kernel
+    if (d_rgb && !fused_colour) {   // tsdf_integrate_colour: the colour pass over the same brick list, right behind the integrate kernel
         const int rcc = launch_colour_integrate(v, bg, ip, mk, mkinv, std_camera, width, height, d_depth, d_rgb, count);
         if (rcc != TSDF_OK) return rcc;
     }
@@ -770,10 +774,11 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     return TSDF_OK;
 }
 
-// tsdf_integrate_colour_device (colour.hip): integrate with the colour pass behind it
+// tsdf_integrate_colour_device (colour.hip) and the pipeline's / tracker's coloured steps (pipeline.hip, with the filter's tile
+// maxima): integrate and the colour update, in the packed kernel or as the colour pass behind the integrate kernel
 int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
-                          const float inv_pose[16], const float k[9], const float kinv[9]) {
-    return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, d_rgb);
+                          const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max) {
+    return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, tile_max, kIntBoth, nullptr, d_rgb);
 }
 
 }  // namespace tsdf

@@ -145,6 +145,11 @@ struct tsdf_tracker {
 
 using namespace tsdf;
 
+namespace tsdf {
+int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
+                          const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max);   // integrate.hip
+}
+
 static int run_filter(tsdf_pipeline *p, const uint16_t *depth, int b, hipStream_t s) {
     return tsdf_bilateral_filter_u16_device_tiles(p->filter, depth, p->filtered[b], (int)p->width, (int)p->height, p->tile_max[b], s);
 }
@@ -518,9 +523,10 @@ int tsdf_pipeline_hit_buffers(const tsdf_pipeline *p, tsdf_hit_record **device_m
     return TSDF_OK;
 }
 
-int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsdf_camera_matrices *cam, float *device_vertices,
-                       float *device_normals, const uint16_t *next_device_depth, const tsdf_camera_matrices *next_cam) {
-    TSDF_REQUIRE(p && device_depth && cam && device_vertices, "tsdf_pipeline_step: null argument");
+// tsdf_pipeline_step (rgb == nullptr) and tsdf_pipeline_step_colour
+static int pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const uint8_t *rgb, const tsdf_camera_matrices *cam,
+                         float *device_vertices, float *device_normals, uint8_t *device_colours, const uint16_t *next_device_depth,
+                         const tsdf_camera_matrices *next_cam) {
     const uint32_t W = p->width, H = p->height;
     const int b = (int)(p->frames & 1u);
     int rc;
@@ -541,7 +547,11 @@ int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsd
         if (rc != TSDF_OK) return rc;
     }
     p->ahead_depth = nullptr;
-    rc = tsdf_integrate_device_tiles(p->volume, p->filtered[b], W, H, cam->pose, cam->inv_pose, cam->k, cam->kinv, p->tile_max[b]);
+    if (rgb)   // (the colour update reads the brick list the next frame's culling rewrites: when it is a pass of its own it is
+               // enqueued in there too, so the `done` event below comes after it)
+        rc = integrate_with_colour(p->volume, p->filtered[b], rgb, W, H, cam->inv_pose, cam->k, cam->kinv, p->tile_max[b]);
+    else
+        rc = tsdf_integrate_device_tiles(p->volume, p->filtered[b], W, H, cam->pose, cam->inv_pose, cam->k, cam->kinv, p->tile_max[b]);
     if (rc != TSDF_OK) return rc;
     if (p->side) {
         // (An event recorded behind integrate costs the step's stream 5-6 us: a packet between two kernels that would otherwise run back
@@ -578,6 +588,10 @@ int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsd
     if (!p->exchange) {
         rc = tsdf_raycast_device(p->volume, W, H, cam->pose, cam->kinv, device_vertices, device_normals);
         if (rc != TSDF_OK) return rc;
+        if (device_colours) {
+            rc = tsdf_volume_sample_colours_device(p->volume, (uint64_t)W * H, device_vertices, device_colours, p->main);
+            if (rc != TSDF_OK) return rc;
+        }
     } else {
         if (p->xstream && p->merged_pending)   // the previous frame's merge still reads hits_all / the collective hits_mine
             TSDF_HIP(hipStreamWaitEvent(p->main, p->merged, 0), "pipeline: wait for the previous exchange");
@@ -605,6 +619,23 @@ int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsd
     }
     p->frames++;
     return TSDF_OK;
+}
+
+int tsdf_pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const tsdf_camera_matrices *cam, float *device_vertices,
+                       float *device_normals, const uint16_t *next_device_depth, const tsdf_camera_matrices *next_cam) {
+    TSDF_REQUIRE(p && device_depth && cam && device_vertices, "tsdf_pipeline_step: null argument");
+    return pipeline_step(p, device_depth, nullptr, cam, device_vertices, device_normals, nullptr, next_device_depth, next_cam);
+}
+
+int tsdf_pipeline_step_colour(tsdf_pipeline *p, const uint16_t *device_depth, const uint8_t *device_rgb, const tsdf_camera_matrices *cam,
+                              float *device_vertices, float *device_normals, uint8_t *device_colours, const uint16_t *next_device_depth,
+                              const tsdf_camera_matrices *next_cam) {
+    TSDF_REQUIRE(p && device_depth && cam && device_vertices, "tsdf_pipeline_step_colour: null argument");
+    TSDF_REQUIRE(device_rgb, "tsdf_pipeline_step_colour: null rgb frame");
+    TSDF_REQUIRE(!p->exchange, "tsdf_pipeline_step_colour: colour is not supported on a sharded pipeline (slab exchange)");
+    TSDF_REQUIRE(p->volume->colour, "tsdf_pipeline_step_colour: colour is not enabled on this volume (tsdf_volume_enable_colour)");
+    TSDF_REQUIRE(!p->volume->nodes, "tsdf_pipeline_step_colour: not supported once the deformation nodes are explicit (deformation() / set_deformation())");
+    return pipeline_step(p, device_depth, device_rgb, cam, device_vertices, device_normals, device_colours, next_device_depth, next_cam);
 }
 
 int tsdf_pipeline_synchronize(tsdf_pipeline *p) {
@@ -750,19 +781,35 @@ int tsdf_tracker_align(tsdf_tracker *t, const tsdf_camera_matrices *previous, do
     return tsdf_icp_get_incremental_transformation(t->icp, T_prev_curr, last_error, last_inliers);
 }
 
-int tsdf_tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera) {
-    TSDF_REQUIRE(t && camera, "tsdf_tracker_integrate: null argument");
+// tsdf_tracker_integrate (rgb == nullptr) and tsdf_tracker_integrate_colour
+static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera, const uint8_t *rgb) {
     TSDF_REQUIRE(t->have_frame, "tsdf_tracker_integrate: no frame filtered");
     int rc = tracker_join(t);
     if (rc != TSDF_OK) return rc;
     const int b = t->cur;
-    rc = tsdf_integrate_device_tiles(t->volume, t->filtered[b], t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
-                                     t->tile_max[b]);
+    if (rgb)
+        rc = integrate_with_colour(t->volume, t->filtered[b], rgb, t->width, t->height, camera->inv_pose, camera->k, camera->kinv, t->tile_max[b]);
+    else
+        rc = tsdf_integrate_device_tiles(t->volume, t->filtered[b], t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
+                                         t->tile_max[b]);
     if (rc != TSDF_OK) return rc;
     if (t->side) TSDF_HIP(hipEventRecord(t->integrated[b], t->main), "tracker: integrate done");
     t->have_frame = false;
     t->frames++;
     return TSDF_OK;
+}
+
+int tsdf_tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera) {
+    TSDF_REQUIRE(t && camera, "tsdf_tracker_integrate: null argument");
+    return tracker_integrate(t, camera, nullptr);
+}
+
+int tsdf_tracker_integrate_colour(tsdf_tracker *t, const tsdf_camera_matrices *camera, const uint8_t *device_rgb) {
+    TSDF_REQUIRE(t && camera, "tsdf_tracker_integrate_colour: null argument");
+    TSDF_REQUIRE(device_rgb, "tsdf_tracker_integrate_colour: null rgb frame");
+    TSDF_REQUIRE(t->volume->colour, "tsdf_tracker_integrate_colour: colour is not enabled on this volume (tsdf_volume_enable_colour)");
+    TSDF_REQUIRE(!t->volume->nodes, "tsdf_tracker_integrate_colour: not supported once the deformation nodes are explicit (deformation() / set_deformation())");
+    return tracker_integrate(t, camera, device_rgb);
 }
 
 int tsdf_tracker_synchronize(tsdf_tracker *t) {

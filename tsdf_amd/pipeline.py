@@ -67,6 +67,18 @@ class FusionPipeline:
                                      C.c_void_p(int(next_depth_ptr)) if next_depth_ptr else None,
                                      C.byref(nxt) if nxt is not None else None))
 
+    def step_colour(self, depth_ptr, rgb_ptr, camera, vertices_ptr, normals_ptr=None, colours_ptr=None, next_depth_ptr=None, next_camera=None):
+        """step() with a colour integrate of the filtered frame and `rgb_ptr` (device, 3 * width * height uint8, registered to the
+        depth image; valid until this step's integrate has run on the pipeline's stream).  `colours_ptr` (device, 3 * width * height
+        uint8, or None): the colour of the voxel every vertex lies in.  The volume must have colour enabled."""
+        cam = _matrices(camera)
+        nxt = _matrices(next_camera) if (next_camera is not None and next_depth_ptr is not None) else None
+        check(lib.tsdf_pipeline_step_colour(self._h, C.c_void_p(int(depth_ptr)), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, C.byref(cam),
+                                            C.c_void_p(int(vertices_ptr)), C.c_void_p(int(normals_ptr)) if normals_ptr else None,
+                                            C.c_void_p(int(colours_ptr)) if colours_ptr else None,
+                                            C.c_void_p(int(next_depth_ptr)) if next_depth_ptr else None,
+                                            C.byref(nxt) if nxt is not None else None))
+
     def synchronize(self):
         check(lib.tsdf_pipeline_synchronize(self._h))
 

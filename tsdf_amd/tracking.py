@@ -57,10 +57,12 @@ class FrameToModelTracker:
         """Current camera pose, 4x4 float64 (camera -> world, millimetres)."""
         return self.camera.pose().astype(np.float64).reshape(4, 4).T.copy()
 
-    def process_device(self, depth_ptr, initial_pose=None):
+    def process_device(self, depth_ptr, initial_pose=None, rgb_ptr=None):
         """One frame (uint16 millimetres on the device; it must stay valid until the call returns ... and until the frame has been
         filtered: synchronize() or the next call).  The first frame is placed at `initial_pose` (4x4, camera -> world, mm; default:
-        the camera's current pose) and only integrated.  Returns the pose used for the frame."""
+        the camera's current pose) and only integrated.  `rgb_ptr` (device, 3 * width * height uint8 registered to the depth
+        image, valid until the frame has been integrated): the frame is integrated with its colour (the volume must have colour
+        enabled).  Returns the pose used for the frame."""
         check(lib.tsdf_tracker_filter(self._h, C.c_void_p(int(depth_ptr))))
         if self.frames == 0:
             if initial_pose is not None:
@@ -77,7 +79,10 @@ class FrameToModelTracker:
             self.icp.last_error, self.icp.last_inliers = self.last_error, self.last_inliers
             self.camera.set_pose_rows(self.pose() @ T)
         cam = _matrices(self.camera)
-        check(lib.tsdf_tracker_integrate(self._h, C.byref(cam)))
+        if rgb_ptr is None:
+            check(lib.tsdf_tracker_integrate(self._h, C.byref(cam)))
+        else:
+            check(lib.tsdf_tracker_integrate_colour(self._h, C.byref(cam), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None))
         self.frames += 1
         return self.pose()
 
@@ -98,10 +103,16 @@ class FrameToModelTracker:
             out.append(a)
         return tuple(out)
 
-    def process(self, depth, initial_pose=None):
-        """Host depth image (uint16 mm)."""
+    def process(self, depth, initial_pose=None, rgb=None):
+        """Host depth image (uint16 mm); `rgb`: its host colour image (uint8, width * height * 3), or None."""
         d = self.torch.from_numpy(np.ascontiguousarray(depth, dtype=np.uint16).reshape(-1).view(np.int16)).cuda()
+        c = None
+        if rgb is not None:
+            c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1)
+            if c.size != 3 * self.width * self.height:
+                raise ValueError("expected %d colour bytes, got %d" % (3 * self.width * self.height, c.size))
+            c = self.torch.from_numpy(c).cuda()
         self.torch.cuda.current_stream().synchronize()
-        pose = self.process_device(d.data_ptr(), initial_pose)
+        pose = self.process_device(d.data_ptr(), initial_pose, rgb_ptr=c.data_ptr() if c is not None else None)
         self.synchronize()           # (the temporary upload is released on return)
         return pose
