@@ -10,8 +10,11 @@ RCCL); every rank integrates its slab (+1 halo plane), ray casts the samples it 
 8-byte hit records {k, t} per pixel is merged by a min-k select.  Total work is fixed => "strong".
 
 Rank 0 prints ONE JSON line.  `value` = voxels of the grid pushed through the whole step per second (whole
-job); per-stage figures (integrate Mvoxels/s, raycast Mrays/s), the roofline of the dominant kernel and the
-CPU baseline (the oracle, timed here on the host cores on a bounded sample) ride along in the same object.
+job).  A plain run does only what that figure needs: set up, warm up, time the K steps (R times, `--repeats`),
+write `--dump-outputs`, print the line.  `--full` then goes on with everything else the benchmark measures and
+checks, in the same object: per-stage figures (integrate Mvoxels/s, raycast Mrays/s) from untimed replays, the
+per-step spread, the roofline of the dominant kernel, the host-buffer / ICP / tracking legs, the parity gate
+against the oracle and the CPU baseline (the oracle, timed here on the host cores on a bounded sample).
 """
 import argparse
 import json
@@ -43,8 +46,13 @@ def parse():
     ap.add_argument("--grid", type=int, default=None, help="voxels per side (default 512, or 1024 for --workload config4)")
     ap.add_argument("--physical", type=float, default=3000.0)
     ap.add_argument("--stream-frames", type=int, default=None, help="length of the synthetic trajectory (default 200; 100 for config4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures and checks: untimed replays for the stage and kernel "
+                         "times, the per-step spread, the weight-storage legs, the roofline, the host-buffer / ICP / tracking legs, the parity "
+                         "gate, the CPU baseline (N > 1: every rank's times, the single-volume parity replay).  The options below marked "
+                         "(--full) only trim or steer that part")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full)")
+    ap.add_argument("--no-parity", action="store_true", help="(--full)")
     ap.add_argument("--event-period", type=int, default=0,
                     help="per-stage HIP events inside the TIMED region on every n-th step (0 = none: each record costs a few "
                          "microseconds of stream time).  Stage and kernel times always come from an untimed replay of the same frames "
@@ -56,8 +64,8 @@ def parse():
                          "work estimate of a small planner volume, or equal plane counts")
     ap.add_argument("--plan-rounds", type=int, default=3, help="--slab-plan measured: rebalancing rounds (each costs a few frames)")
     ap.add_argument("--validate-merge", action="store_true",
-                    help="N > 1: SURVEY.md 8e mode B after the measurements -- every rank all-gathers the distance slabs, casts the whole "
-                         "volume the single-volume way and compares its bits with the merged picture (tsdf_slab_validate_merge)")
+                    help="(--full) N > 1: SURVEY.md 8e mode B after the measurements -- every rank all-gathers the distance slabs, casts the "
+                         "whole volume the single-volume way and compares its bits with the merged picture (tsdf_slab_validate_merge)")
     ap.add_argument("--one-rank-slab-path", action="store_true",
                     help="--gpus 1 only: run the N > 1 code path (slab volume, slab ray cast, all-gather of the hit records over the "
                          "nccl = RCCL backend, merge) with a world of one rank -- the collective degenerates but RCCL initialises, "
@@ -71,21 +79,24 @@ def parse():
     ap.add_argument("--tum-dir", default=None,
                     help="take the stream from a TUM-layout directory (depth/*.png + ground_truth.txt) through the host library's "
                          "TUMDataLoader instead of synthesising it: the frames tools/kinfu_stream.cpp sees (tools/compare_drivers.sh)")
-    ap.add_argument("--cpu-budget-s", type=float, default=20.0)
+    ap.add_argument("--cpu-budget-s", type=float, default=20.0, help="(--full)")
     ap.add_argument("--repeats", type=int, default=5,
                     help="the K-step timed region (barrier + synchronise on both sides, MAX over ranks) is run this many times, each on a freshly "
                          "cleared volume fed the same warm-up and the same K frames; ms_per_step / value are the MEDIAN region, every region is "
                          "listed in ms_per_step_runs")
     ap.add_argument("--parity-grid", type=int, default=None,
-                    help="grid of the parity gate (default: the benchmarked grid, first and last timed frame against the oracle)")
+                    help="(--full) grid of the parity gate (default: the benchmarked grid, first and last timed frame against the oracle)")
     ap.add_argument("--spread-steps", type=int, default=100,
-                    help="steps of the run that times every step on its own (step_ms_spread): at least --steps; 0 = --steps (the profiling passes)")
+                    help="(--full) steps of the run that times every step on its own (step_ms_spread): at least --steps; 0 = --steps (the "
+                         "profiling passes)")
     ap.add_argument("--path-only", action="store_true",
-                    help="only the timed hot path and its roofline (no ICP / tracking / host-buffer legs): what the profiling passes run")
+                    help="(--full) only the timed hot path and its roofline (no ICP / tracking / host-buffer legs): what the profiling passes run")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the vertex and normal maps "
                          "(no-hit NaNs as 0, with a per-pixel validity mask each), and (one volume) a fixed seeded sample of the volume's distances and weights")
     a = ap.parse_args()
+    if a.validate_merge and not a.full:
+        ap.error("--validate-merge is a check of the --full run")
     if a.grid is None:
         a.grid = 1024 if a.workload == "config4" else 512
     if a.stream_frames is None:
@@ -163,8 +174,8 @@ def main():
     n = args.grid
     N_vox = n * n * n
     K, Wu = args.steps, args.warmup
-    S_spread = K if args.spread_steps <= 0 else max(K, args.spread_steps)   # steps of the per-step timing run
-    n_frames = max(K, S_spread) + Wu + 1
+    S_spread = K if args.spread_steps <= 0 else max(K, args.spread_steps)   # steps of the per-step timing run (--full)
+    n_frames = (S_spread if args.full else K) + Wu + 1       # (+ 1: the last step announces the next frame)
     inside = args.workload == "config4"
     seed = 0x5EED0004 if inside else SEED
 
@@ -178,10 +189,17 @@ def main():
         for i in range(n_frames):
             frames.append(loaded[i % len(loaded)][0])
             cams.append(loaded[i % len(loaded)][1])
-    for i in range(0 if args.tum_dir else n_frames):
-        d, cam = synth.depth_frame(i % args.stream_frames, args.stream_frames, seed=seed, inside=inside)
-        frames.append(d)
-        cams.append(cam)
+    if not args.tum_dir:
+        # each distinct frame of the trajectory is made once, on a few host threads (numpy leaves the GIL in its array loops; a frame
+        # depends on its index alone, so the bits are those of one thread)
+        from concurrent.futures import ThreadPoolExecutor
+        distinct = sorted({i % args.stream_frames for i in range(n_frames)})
+        with ThreadPoolExecutor(max_workers=min(8, len(distinct))) as pool_:
+            made = dict(zip(distinct, pool_.map(lambda j: synth.depth_frame(j, args.stream_frames, seed=seed, inside=inside), distinct)))
+        for i in range(n_frames):
+            d, cam = made[i % args.stream_frames]
+            frames.append(d)
+            cams.append(cam)
     depth_dev = torch.from_numpy(np.stack(frames).view(np.int16)).cuda()           # (F, H*W) uint16 bits
     filt_dev = torch.empty((H * W,), dtype=torch.int16, device="cuda")
     # the bilateral filter leaves the 16 x 16 tile maxima of its output for integrate's brick culling (one launch fewer per frame;
@@ -398,8 +416,51 @@ def main():
     bits_v, bits_n = run_bits[-1]
     if args.dump_outputs and rank == 0:      # (before the legs below reuse the maps and the volume)
         dump_outputs(args.dump_outputs, vert_dev, norm_dev, None if sharded else vol)
+    ms_per_step = elapsed * 1e3 / K
+    value = N_vox * K / elapsed / 1e6
+
+    out = {
+        "metric": "Mvoxels/s integrate + Mrays/s raycast, 512^3 grid, 640x480 depth; 1/2/4/8 GPU",
+        "value": round(value, 3),
+        "unit": "Mvoxels/s",
+        "value_definition": "grid voxels pushed through the whole step (bilateral+integrate+raycast+normals) per second",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": Wu,
+        "event_period": period,     # HIP events inside the timed region on every n-th step (0 = none)
+        "ms_per_step": round(ms_per_step, 4),
+        "ms_per_step_is": "median of %d timed regions of %d steps, each on a freshly cleared volume fed the same %d warm-up + %d timed frames" % (R, K, Wu, K),
+        "ms_per_step_runs": [round(r_ * 1e3 / K, 4) for r_ in runs],
+        "picture_bits_equal_across_runs": bool(all(b_ == run_bits[0] for b_ in run_bits)),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "configs[%d]: %d^3 TSDF over %.0f mm, synthetic TUM-surrogate stream (%d-frame "
+                               "trajectory%s, seed 0x%X), 640x480 uint16 depth, bilateral(30,4.5) + integrate + "
+                               "raycast + normals per frame" % (3 if inside else 2, n, args.physical, args.stream_frames,
+                                                                " inside the volume" if inside else "", seed),
+                   "grid": [n, n, n], "image": [W, H], "parallelism": "zslab%d" % world,
+                   "overlap": ("bilateral + brick culling of frame i+1 on a lower-priority stream during the ray cast of frame i (tsdf_pipeline_step, C++)"
+                               if pipe.overlap else "none"),
+                   "depth_tile_maxima": "integrate's own launch" if args.separate_tile_max else "left by the bilateral filter's launch",
+                   "collective_backend": (dist.get_backend() if sharded else None), "ranks": (dist.get_world_size() if sharded else 1),
+                   "collective": (exch_note if sharded else None)},
+        # sum of the finite vertex coordinates of the last frame's picture: equal between runs that differ only in schedule
+        "last_frame_vertex_checksum": checksum,
+        "last_frame_vertex_bits": bits_v, "last_frame_normal_bits": bits_n,
+        "stream": ("TUM directory %s through TUMDataLoader" % args.tum_dir) if args.tum_dir else "synthesised in memory (tsdf_amd/synth.py)",
+        "full": args.full,          # false: the headline alone; --full adds the replays, the roofline, the legs and the checks below
+    }
+    if sharded and rank == 0:
+        out["slabs"] = [list(r_) for r_ in slab_plan]
+        out["slab_plan"] = {"method": args.slab_plan, "rounds": plan_log}
 
     trace("timed region done")
+    if not args.full:
+        finish(out, rank, sharded, pipe, exch if sharded else None, json_fd)
+        return
     # ---- untimed replays of the SAME K frames: (1) every stage and every launch of the dominant kernels bracketed with HIP
     # events on the launch stream (K launches timed, none of their cost inside `value`); (2) the voxels each frame updates,
     # counted by the kernel (which voxels a frame updates does not depend on the volume's state: depth > 0 and sdf >= -trunc,
@@ -508,50 +569,16 @@ def main():
         for i in range(Wu + K):
             step(i, False)
         torch.cuda.synchronize()
-    ms_per_step = elapsed * 1e3 / K
-    value = N_vox * K / elapsed / 1e6
-
-    out = {
-        "metric": "Mvoxels/s integrate + Mrays/s raycast, 512^3 grid, 640x480 depth; 1/2/4/8 GPU",
-        "value": round(value, 3),
-        "unit": "Mvoxels/s",
-        "value_definition": "grid voxels pushed through the whole step (bilateral+integrate+raycast+normals) per second",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": Wu,
-        "event_period": period,     # HIP events inside the timed region on every n-th step (0 = none)
+    out.update({
         "stage_and_kernel_times_from": "untimed replay of the %d timed frames from the same volume state (cleared + the warm-up frames), one stage "
                                        "after the other (no overlap), every launch bracketed with HIP events on the launch stream" % K,
-        "ms_per_step": round(ms_per_step, 4),
-        "ms_per_step_is": "median of %d timed regions of %d steps, each on a freshly cleared volume fed the same %d warm-up + %d timed frames" % (R, K, Wu, K),
-        "ms_per_step_runs": [round(r_ * 1e3 / K, 4) for r_ in runs],
         "ms_per_step_max": step_spread["max"], "ms_per_step_p95": step_spread["p95"], "step_ms_spread": step_spread,
         "integrate_ms_by_weight_storage": int_by_storage or None,
-        "picture_bits_equal_across_runs": bool(all(b_ == run_bits[0] for b_ in run_bits)),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "configs[%d]: %d^3 TSDF over %.0f mm, synthetic TUM-surrogate stream (%d-frame "
-                               "trajectory%s, seed 0x%X), 640x480 uint16 depth, bilateral(30,4.5) + integrate + "
-                               "raycast + normals per frame" % (3 if inside else 2, n, args.physical, args.stream_frames,
-                                                                " inside the volume" if inside else "", seed),
-                   "grid": [n, n, n], "image": [W, H], "parallelism": "zslab%d" % world,
-                   "overlap": ("bilateral + brick culling of frame i+1 on a lower-priority stream during the ray cast of frame i (tsdf_pipeline_step, C++)"
-                               if pipe.overlap else "none"),
-                   "depth_tile_maxima": "integrate's own launch" if args.separate_tile_max else "left by the bilateral filter's launch",
-                   "collective_backend": (dist.get_backend() if sharded else None), "ranks": (dist.get_world_size() if sharded else 1),
-                   "collective": (exch_note if sharded else None)},
         "integrate_mvoxels_per_s": round(N_vox / (stage_ms["integrate"] * 1e-3) / 1e6, 1),
         "raycast_mrays_per_s": round(W * H / ((stage_ms["raycast"] + stage_ms["exchange"] + stage_ms["normals"]) * 1e-3) / 1e6, 2),
         "stage_ms": {s: (round(v, 4) if v is not None else None) for s, v in stage_ms.items()},
         "stage_outliers_dropped": stage_outliers,
-        # sum of the finite vertex coordinates of the last frame's picture: equal between runs that differ only in schedule
-        "last_frame_vertex_checksum": checksum,
-        "last_frame_vertex_bits": bits_v, "last_frame_normal_bits": bits_n,
-        "stream": ("TUM directory %s through TUMDataLoader" % args.tum_dir) if args.tum_dir else "synthesised in memory (tsdf_amd/synth.py)",
-    }
+    })
 
     trace("replays done")
     # ---- roofline of the dominant kernel (by time): HIP-event durations of the replay, bytes of the same launches ----------
@@ -657,8 +684,6 @@ def main():
         if rank == 0:
             names = stage_names + ["integrate_kernel", "process_ray_kernel", "process_ray_tail_kernel", "U_voxels_updated"]
             out["per_rank_ms"] = {nm: [round(float(v), 4) for v in allr[:, j].tolist()] for j, nm in enumerate(names)}
-            out["slabs"] = [list(r_) for r_ in slab_plan]
-            out["slab_plan"] = {"method": args.slab_plan, "rounds": plan_log}
             out["roofline"] = roof_int
             out["roofline"]["note"] = "rank 0's slab"
             if not args.no_parity:
@@ -692,6 +717,11 @@ def main():
         if rank == 0:
             out["collective"] = coll
     trace("parity replay done")
+    finish(out, rank, sharded, pipe, exch if sharded else None, json_fd)
+
+
+def finish(out, rank, sharded, pipe, exch, json_fd):
+    """Rank 0 prints the line on the saved stdout; N > 1: every rank leaves the process group together."""
     if rank == 0:
         def finite(o):      # strict JSON: a non-finite number (an unsampled average, an empty ratio) becomes null
             if isinstance(o, float):
@@ -703,6 +733,7 @@ def main():
             return o
         os.write(json_fd, (json.dumps(finite(out), allow_nan=False) + "\n").encode())
     if sharded:
+        import torch.distributed as dist
         dist.barrier()
         pipe.close()
         if exch is not None:

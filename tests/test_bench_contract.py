@@ -23,7 +23,7 @@ def run_bench(*args):
 
 
 def test_default_shaped_run_prints_the_contract_line():
-    d = run_bench("--gpus", "1", "--steps", "20", "--warmup", "2", "--cpu-budget-s", "3")
+    d = run_bench("--gpus", "1", "--steps", "20", "--warmup", "2", "--full", "--cpu-budget-s", "3")
     for key, kind in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                       ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                       ("config", dict), ("roofline", dict), ("cpu_baseline", dict)):
@@ -60,8 +60,29 @@ def test_default_shaped_run_prints_the_contract_line():
     assert t["mesh"]["same_as_host"] is True and t["mesh"]["triangles"] > 500_000
 
 
+def test_plain_run_is_the_headline_alone_on_the_frames_the_full_run_times():
+    """Without --full: the same timed region and the same line fields, nothing after it (no replays, legs or checks); its last
+    timed picture is the full run's, bit for bit."""
+    args = ("--gpus", "1", "--steps", "20", "--warmup", "2")
+    d = run_bench(*args)
+    for key, kind in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                      ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str), ("config", dict)):
+        assert key in d and isinstance(d[key], kind), key
+    assert d["full"] is False and d["unit"] == "Mvoxels/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    n_vox = d["config"]["grid"][0] * d["config"]["grid"][1] * d["config"]["grid"][2]
+    assert math.isclose(d["value"], n_vox / (d["ms_per_step"] * 1e-3) / 1e6, rel_tol=2e-3)
+    runs = d["ms_per_step_runs"]
+    assert len(runs) == 5 and math.isclose(sorted(runs)[2], d["ms_per_step"], rel_tol=1e-3) and d["picture_bits_equal_across_runs"] is True
+    for key in ("stage_ms", "step_ms_spread", "roofline", "roofline_other", "parity", "cpu_baseline", "tracking", "icp", "host_buffer_api"):
+        assert key not in d, key
+    f = run_bench(*args, "--full", "--path-only", "--no-parity", "--no-cpu-baseline", "--repeats", "1", "--spread-steps", "0")
+    assert f["full"] is True and "stage_ms" in f and "roofline" in f
+    for key in ("last_frame_vertex_bits", "last_frame_normal_bits", "last_frame_vertex_checksum"):
+        assert d[key] == f[key], key
+
+
 def test_few_steps_and_no_sampled_events_still_give_strict_json():
-    d = run_bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-parity", "--event-period", "0", "--repeats", "1", "--spread-steps", "0")
+    d = run_bench("--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-parity", "--event-period", "0", "--repeats", "1", "--spread-steps", "0")
     assert d["steps"] == 3 and d["value"] > 0 and len(d["ms_per_step_runs"]) == 1
 
 
@@ -108,7 +129,8 @@ def test_two_ranks_on_one_gpu_walk_the_sharded_path_and_agree_with_one_volume():
     env = dict(os.environ, TSDF_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     # started plainly, the way the driver starts N = 1: bench.py becomes its own torch.distributed.run launcher (round 4)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--plan-rounds", "1", "--repeats", "3", "--spread-steps", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--plan-rounds", "1", "--repeats", "3",
+           "--spread-steps", "0"]
     p = subprocess.run(cmd, cwd=ROOT, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -126,7 +148,7 @@ def test_one_rank_walks_the_sharded_path_over_rccl():
     """What a one-GPU box can check of the multi-GPU path on the real backend: a world of ONE rank initialises nccl (= RCCL),
     builds a communicator on the box's GPU and pushes the hit records through all_gather_into_tensor on device memory, between the
     slab ray cast and the merge kernel of every step; the merged picture must equal a single-volume replay."""
-    d = run_bench("--gpus", "1", "--one-rank-slab-path", "--steps", "6", "--warmup", "2", "--plan-rounds", "1", "--no-cpu-baseline", "--validate-merge", "--spread-steps", "0")
+    d = run_bench("--gpus", "1", "--one-rank-slab-path", "--steps", "6", "--warmup", "2", "--full", "--plan-rounds", "1", "--no-cpu-baseline", "--validate-merge", "--spread-steps", "0")
     assert d["config"]["collective_backend"] == "nccl" and d["config"]["ranks"] == 1 and d["config"]["parallelism"] == "zslab1"
     # the line says how many ranks the communicator itself holds (ncclCommCount), and mode B -- the all-gathered distance slab cast
     # the single-volume way -- gives the merged picture bit for bit
@@ -137,7 +159,7 @@ def test_one_rank_walks_the_sharded_path_over_rccl():
     assert d["per_rank_ms"]["exchange"][0] > 0 and d["value"] > 0
     # the collective was RCCL's, called on the step's own stream (no fallback to torch's)
     assert d["config"]["collective"].startswith("ncclAllGather on the step's stream"), d["config"]["collective"]
-    t = run_bench("--gpus", "1", "--one-rank-slab-path", "--torch-collective", "--steps", "6", "--warmup", "2", "--plan-rounds", "0",
+    t = run_bench("--gpus", "1", "--one-rank-slab-path", "--torch-collective", "--steps", "6", "--warmup", "2", "--full", "--plan-rounds", "0",
                   "--no-cpu-baseline", "--spread-steps", "0")
     assert t["config"]["collective"].startswith("torch.distributed") and t["parity"]["pass"] is True
     assert t["last_frame_vertex_checksum"] == d["last_frame_vertex_checksum"]

@@ -4,7 +4,7 @@ out=${1:-gpurun_out/r05i}; mkdir -p $out
 for cfg in "256 1" "256 2" "256 4" "256 1" "256 4" "512 1" "512 2" "512 1"; do
   set -- $cfg
   echo -n "grid $1 split $2: "
-  TSDF_INT_SPLIT=$2 timeout 300 python bench.py --grid $1 --steps 20 --warmup 5 --path-only --no-parity --no-cpu-baseline 2>/dev/null | python -c "
+  TSDF_INT_SPLIT=$2 timeout 300 python bench.py --full --grid $1 --steps 20 --warmup 5 --path-only --no-parity --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline'] if d['roofline']['kernel'].startswith('integrate') else d['roofline_other']

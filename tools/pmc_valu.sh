@@ -1,7 +1,7 @@
 #!/bin/bash
 root=$(pwd); out=$root/gpurun_out; mkdir -p $out/profiles_valu
 cd /tmp && export TMPDIR=/tmp
-cmd="python $root/bench.py --no-cpu-baseline --no-parity --steps 40 --warmup 4"
+cmd="python $root/bench.py --full --no-cpu-baseline --no-parity --steps 40 --warmup 4"
 for c in SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES; do
   timeout 300 rocprofv3 --kernel-trace --pmc $c -d $out/prof_$c -o bench -- $cmd > $out/prof_$c.log 2>&1
   cd $root; python tools/rocprof_summary.py pmc $(find $out/prof_$c -name "*.db" | head -1) > $out/profiles_valu/r01o_pmc_$c.txt; cd /tmp

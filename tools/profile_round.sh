@@ -11,7 +11,7 @@ root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out/profiles_$tag
 cd /tmp && export TMPDIR=/tmp
-cmd="python $root/bench.py --no-cpu-baseline --no-parity --path-only --repeats 1 --spread-steps 0 --steps $steps --warmup $warmup $extra"
+cmd="python $root/bench.py --full --no-cpu-baseline --no-parity --path-only --repeats 1 --spread-steps 0 --steps $steps --warmup $warmup $extra"
 rm -rf $out/prof_stats $out/prof_fetch $out/prof_write $out/prof_activity
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/prof_stats -o bench -- $cmd > $out/prof_stats.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $out/prof_fetch -o bench -- $cmd > $out/prof_fetch.log 2>&1
@@ -27,7 +27,7 @@ python tools/rocprof_summary.py pmc $(f prof_activity) > $out/profiles_$tag/${ta
 python tools/rocprof_summary.py traffic+activity $(f prof_fetch) $(f prof_write) $(f prof_activity) $warmup $steps tag=$tag kernel_source_sha=$sha \
     "bench_args={\"steps\": $steps, \"warmup\": $warmup, \"grid\": $grid, \"gpus\": 1}" > $out/profiles_$tag/${tag}_traffic.json
 cp $out/profiles_$tag/${tag}_traffic.json profiles/traffic_${tag}.json   # (so that the bench line below carries `traffic`; commit it with the summaries)
-timeout 900 python bench.py --steps $steps --warmup $warmup $extra > $out/profiles_$tag/${tag}_bench.json 2> $out/bench.err
+timeout 900 python bench.py --full --steps $steps --warmup $warmup $extra > $out/profiles_$tag/${tag}_bench.json 2> $out/bench.err
 tail -c 600 $out/profiles_$tag/${tag}_kernel_stats.txt
 # the raw databases are scratch (gpurun copies back at most 64 MiB): keep only the summaries
 rm -rf $out/prof_stats $out/prof_fetch $out/prof_write $out/prof_activity

@@ -15,7 +15,7 @@ for wl in ${WORKLOADS:-config3 config4}; do
     if [ "$n" -gt "$have" ] && [ -z "$TSDF_BENCH_SHARE_GPU" ]; then echo "$wl N=$n skipped: $have GPU(s) visible"; continue; fi
     port=$((29500 + n)); f=$out/scale_${wl}_N$n
     # (bench.py --gpus N started plainly re-executes itself under torch.distributed.run, one rank per GPU, 127.0.0.1 rendezvous)
-    timeout 1200 python $root/bench.py --gpus $n --steps $steps --warmup $warmup --workload $wl "$@" > $f.json 2> $f.err
+    timeout 1200 python $root/bench.py --full --gpus $n --steps $steps --warmup $warmup --workload $wl "$@" > $f.json 2> $f.err
     echo "$wl N=$n rc=$? $(tail -c 300 $f.json | head -c 300)"
   done
 done
