@@ -59,7 +59,7 @@ oracle:
 	$(MAKE) -C oracle -s all
 
 # C++ test program of the class surface (run by tests/test_cpp_surface.py on the GPU box)
-cpptest: build/test_surface build/test_colour build/kinfu_stream
+cpptest: build/test_surface build/test_colour build/test_weight_cap build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
 build/kinfu_stream: tools/kinfu_stream.cpp $(LIBDIR)/libtsdf_host.so include/tsdf_amd.h
@@ -74,6 +74,11 @@ build/test_surface: tests/cpp/test_surface.cpp $(LIBDIR)/libtsdf_host.so
 build/test_colour: tests/cpp/test_colour.cpp $(LIBDIR)/libtsdf_host.so
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_colour.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
+
+# C++ check of the weight cap through the class surface (run by tests/test_cpp_weight_cap.py on the GPU box)
+build/test_weight_cap: tests/cpp/test_weight_cap.cpp $(LIBDIR)/libtsdf_host.so
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_weight_cap.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
 clean:
 	rm -f $(HIP_OBJS) $(HOST_OBJS) $(LIBDIR)/*.so

@@ -216,6 +216,36 @@ int tsdf_volume_set_counting(tsdf_volume *volume, int enabled);
 int tsdf_volume_last_updated_voxels(const tsdf_volume *volume, uint64_t *count);
 int tsdf_volume_last_distance_stores(const tsdf_volume *volume, uint64_t *count);
 
+/* ---- weight cap (what the reference's m_max_weight was for: src/include/TSDFVolume.hpp, src/TSDF/TSDFVolume.cu:375-381) ------------ */
+/* Opt-in per volume, off by default.  With cap == 0 nothing changes anywhere: the plain kernels, no allocation, no launch -- a volume
+ * averages every frame it has ever seen, as the reference's does.  With a cap c in 1 .. 65535, every voxel that the plain integrate
+ * updates (same frustum, depth and sdf >= -trunc tests, same voxels) gets
+ *       new_distance  = (prior_distance * prior_weight + tsdf * 1.0f) / (prior_weight + 1.0f)        (unchanged, :375-381)
+ *       stored_weight = (prior_weight + 1.0f > (float)c) ? (float)c : prior_weight + 1.0f
+ * The divisor is always prior_weight + 1; only the weight that is STORED is clamped.  (The reference's commented-out line, :378, clamps
+ * the divisor itself: a saturated voxel would then compute D + tsdf / c every frame and run away, which is presumably why it is
+ * commented out.)  So:
+ *   - the distance of a saturated voxel is an exponential average with factor c / (c + 1): a surface that moves shows after a few
+ *     times c frames instead of never;
+ *   - a weight found above the cap (uploaded, or integrated before the cap was set) is used as it is for that blend and comes out
+ *     as c; a NaN weight stays NaN (the comparison form above); voxels the frame does not update keep their weight;
+ *   - the cap is a run-time setting of the volume object: tsdf_volume_clear keeps it, it is not written to .tsdf files, and
+ *     tsdf_volume_info.max_weight stays the inert header field it is.  tsdf_volume_set_weight_cap(v, (uint32_t)info.max_weight) gives
+ *     what the reference's field was for.  cap > 65535 is TSDF_ERR_INVALID with a message;
+ *   - the cap may be changed between any two integrates; 0 returns to the plain kernels from the next integrate on.  A slab volume
+ *     carries its own cap: the caller gives all slabs of one grid the same one;
+ *   - storage (tsdf_volume_weight_storage): with 1 <= c <= 255 a volume with 8-bit counts keeps them for ever -- no look at the
+ *     counts, no host round trip inside integrate, no widening; with c >= 256 it may go to 16 bits by the usual rule and never
+ *     to fp32 for reasons of overflow.  Setting a cap never narrows: a volume at 16 or 32 bits stays there until clear().
+ *     tsdf_volume_set_weight_data with counts above the cap is accepted and stored as without one;
+ *   - colour is untouched: tsdf_integrate_colour with a cap gives the capped distances and weights and exactly the colour words
+ *     it gives without one (the colour count n has its own saturation);
+ *   - tsdf_volume_last_updated_voxels counts the voxels the frame updated, capped or not (the same number as without a cap);
+ *     tsdf_volume_last_distance_stores counts the distance stores made.
+ * Every integrate entry point honours it: tsdf_integrate*, tsdf_integrate_colour*, tsdf_pipeline_step*, tsdf_tracker_integrate*. */
+int tsdf_volume_set_weight_cap(tsdf_volume *volume, uint32_t cap);   /* 0 = off (default: the reference's behaviour), 1..65535 */
+int tsdf_volume_weight_cap(const tsdf_volume *volume, uint32_t *cap);
+
 /* ---- colour fusion (no reference counterpart: the reference allocates a uchar3 colour per voxel, src/include/TSDFVolume.hpp:290-293,
  * that none of its kernels writes) --------------------------------------------------------------------------------------------- */
 /* Opt-in per volume.  A volume that never enables colour behaves exactly as without this group: no allocation, no launch.

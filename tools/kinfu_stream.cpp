@@ -8,7 +8,10 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N]
+//   --weight-cap N: tsdf_volume_set_weight_cap(N) on the volume (with --ranks on every slab) before the first step -- a running average
+//           whose counts stay in 8 bits for N <= 255; 0 (the default) = off; valid with --track, --colour and --ranks; the line gains
+//           "weight_cap": N.
 //   --colour: colour fusion as well -- every frame's <dir>/rgb/<stem>.png read with TUMDataLoader::next(pose, rgb) and kept in HBM
 //           beside its depth frame, colour enabled on the volume, tsdf_pipeline_step_colour (with --track tsdf_tracker_integrate_colour)
 //           for every step; the line gains "colour": true and the last picture's colour checksum, --dump colours.u8 (the last picture's
@@ -114,6 +117,7 @@ int main(int argc, char **argv) {
     int K = 20, Wu = 5;
     bool overlap = true, cull_ahead = true, track = false, validate_merge = false, colour = false;
     unsigned planes = 0;
+    long weight_cap = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&]() -> const char * {
@@ -137,14 +141,19 @@ int main(int argc, char **argv) {
         else if (a == "--planes") planes = (unsigned)std::atoi(value());
         else if (a == "--validate-merge") validate_merge = true;
         else if (a == "--colour") colour = true;
+        else if (a == "--weight-cap") weight_cap = std::atol(value());
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N]\n");
             return 2;
         }
     }
     if (planes == 0) planes = n;
     if (dir.empty() || K < 1 || Wu < 0 || n < 1 || ranks < 1 || ranks > kMaxRanks || (unsigned)ranks > planes || (track && ranks > 1)) {
         std::fprintf(stderr, "kinfu_stream: -d <tum dir>, -k >= 1, -w >= 0, -n >= 1, 1 <= --ranks <= min(%d, grid), --track is single-volume\n", kMaxRanks);
+        return 2;
+    }
+    if (weight_cap < 0 || weight_cap > 65535) {
+        std::fprintf(stderr, "kinfu_stream: --weight-cap is 0 (off) or 1 .. 65535\n");
         return 2;
     }
     if (colour && ranks > 1) {
@@ -280,6 +289,7 @@ int main(int argc, char **argv) {
             ok(tsdf_slab_exchange_create_callback(rank, ranks, shm_all_gather, &shm_gather, &exch), "slab exchange (shared memory)");
         }
     }
+    if (weight_cap) ok(tsdf_volume_set_weight_cap(vol, (uint32_t)weight_cap), "weight cap");
     ok(tsdf_bilateral_create(30.0f, 4.5f, &bil), "bilateral filter");
 
     if (track) {
@@ -331,6 +341,7 @@ int main(int argc, char **argv) {
                     "\"ms_per_frame\": %.4f, \"last_pose_translation_error_mm\": %.4f, \"last_icp_inliers\": %.0f, \"last_icp_error\": %.6g",
                     n, W, H, n_track, overlap ? "true" : "false", n_track > first_timed ? elapsed * 1e3 / (double)(n_track - first_timed) : 0.0, std::sqrt(dt2),
                     inliers, error);
+        if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
         std::printf(colour ? ", \"colour\": true}\n" : "}\n");
         if (!dump_dir.empty()) {
             dump(dump_dir + "/poses.f32", tracked.data(), tracked.size() * sizeof(float));
@@ -435,6 +446,7 @@ int main(int argc, char **argv) {
                     "\"last_frame_vertex_bits\": %lld, \"last_frame_normal_bits\": %lld, \"last_frame_hits\": %lld",
                     n, planes, W, H, F, K, Wu, overlap ? "true" : "false", cull_ahead ? "true" : "false", ms, voxels * K / elapsed / 1e6, bits_v, bits_n, hits);
         if (colour) std::printf(", \"colour\": true, \"last_frame_colour_bits\": %lld", bits_c);
+        if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
         std::printf("}\n");
     }
 

@@ -153,6 +153,19 @@ class TSDFVolume:
         """Widen the weight storage now (8 -> 16 -> 32 bits, values unchanged) instead of when a count is about to overflow."""
         check(lib.tsdf_volume_set_weight_storage(self._h, int(bits)))
 
+    def set_weight_cap(self, cap):
+        """Cap the weight integrate stores at `cap` (1 .. 65535; 0 = off, the default): a running average that follows a scene that
+        changes, and -- up to 255 -- counts that stay in 8 bits for ever.  The blend's divisor is never clamped (include/tsdf_amd.h)."""
+        cap = int(cap)
+        if cap < 0 or cap > 0xFFFFFFFF:
+            raise ValueError("set_weight_cap: the cap is 0 (off) or 1 .. 65535")
+        check(lib.tsdf_volume_set_weight_cap(self._h, cap))
+
+    def weight_cap(self):
+        c = C.c_uint32()
+        check(lib.tsdf_volume_weight_cap(self._h, C.byref(c)))
+        return int(c.value)
+
     def deformation(self):
         p = C.c_void_p()
         check(lib.tsdf_volume_deformation(self._h, C.byref(p)))

@@ -261,6 +261,7 @@ struct tsdf_volume {
     int wmode;
     uint32_t weight_bound;   // packed modes: no count exceeds this (integrations since the weights were last known + their maximum then)
     int weight_pinned;       // the caller holds the fp32 device pointer (tsdf_volume_weights): the volume keeps the reference's layout
+    uint32_t weight_cap;     // tsdf_volume_set_weight_cap: 0 = off (the plain kernels), else the largest weight integrate stores
     tsdf_deformation_node *nodes;  // nullptr while implicit
     // cached per-call temporaries (the reference mallocs/frees these every call)
     uint16_t *depth_buf;

@@ -92,9 +92,10 @@ template <bool COUNT, int WBITS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED_WAVES, TSDF_PACKED_WAVES))) void integrate_packed_kernel(TSDF_PACKED_PARAMS) {
     __shared__ uint16_t tile[kTilePixels];                                   // the brick's pixel box inside a ring of zeros
     __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
-    constexpr bool COLOUR = false;
+    constexpr bool COLOUR = false, CAPPED = false;
     uint32_t *const colour = nullptr;
     const uint8_t *const rgb = nullptr;
+    const uint32_t cap = 0;
 #include "integrate_packed_body.hpp"
 }
 
@@ -108,7 +109,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
     TSDF_PACKED_PARAMS, uint32_t *__restrict__ colour, const uint8_t *__restrict__ rgb) {
     __shared__ uint16_t tile[kTilePixels];
     __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
-    constexpr bool COLOUR = true;
+    constexpr bool COLOUR = true, CAPPED = false;
+    const uint32_t cap = 0;
+#include "integrate_packed_body.hpp"
+}
+
+// The two kernels above with a weight cap (tsdf_volume_set_weight_cap; 1 <= cap <= the field's largest value -- launch_integrate's
+// weights_make_room sees to it): the blend divides by count + 1 as ever, the count it STORES is min(count + 1, cap), each field of the
+// packed word on its own -- a field at 255 (65535) takes no increment, so nothing carries into its neighbour -- and a word whose fields
+// all sit at the cap comes out as it went in and is not stored.  Kernels of their own names, compiled for the occupancy of their plain
+// counterparts: the plain kernels and their rocprof rows stay as they are.
+template <bool COUNT, int WBITS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED_WAVES, TSDF_PACKED_WAVES))) void integrate_packed_capped_kernel(
+    TSDF_PACKED_PARAMS, const uint32_t cap) {
+    __shared__ uint16_t tile[kTilePixels];
+    __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
+    constexpr bool COLOUR = false, CAPPED = true;
+    uint32_t *const colour = nullptr;
+    const uint8_t *const rgb = nullptr;
+#include "integrate_packed_body.hpp"
+}
+template <bool COUNT, int WBITS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED_COLOUR_WAVES, TSDF_PACKED_COLOUR_WAVES))) void integrate_packed_colour_capped_kernel(
+    TSDF_PACKED_PARAMS, uint32_t *__restrict__ colour, const uint8_t *__restrict__ rgb, const uint32_t cap) {
+    __shared__ uint16_t tile[kTilePixels];
+    __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
+    constexpr bool COLOUR = true, CAPPED = true;
 #include "integrate_packed_body.hpp"
 }
 #undef TSDF_PACKED_PARAMS
@@ -121,7 +147,14 @@ int launch_integrate_packed_kernel(tsdf_volume *v, dim3 grid, const BrickGrid &b
     const dim3 block(kTileX, kTileY, 1);
 #define LAUNCH(CNT, BITS)                                                                                                       \
     do {                                                                                                                        \
-        if (d_rgb)                                                                                                              \
+        if (v->weight_cap && d_rgb)                                                                                             \
+            TSDF_LAUNCH_TIMED(v, 0, (integrate_packed_colour_capped_kernel<CNT, BITS>), grid, block, v->dist, v->wpacked, v->g, bg, ip, mk, width, height, \
+                              d_depth, v->depth_pad, counter_arg, v->occ, v->brick_list, boxes, coords, count, plane_const, v->touched, v->colour, d_rgb, \
+                              v->weight_cap);                                                                                   \
+        else if (v->weight_cap)                                                                                                 \
+            TSDF_LAUNCH_TIMED(v, 0, (integrate_packed_capped_kernel<CNT, BITS>), grid, block, v->dist, v->wpacked, v->g, bg, ip, mk, width, height, d_depth, \
+                              v->depth_pad, counter_arg, v->occ, v->brick_list, boxes, coords, count, plane_const, v->touched, v->weight_cap);     \
+        else if (d_rgb)                                                                                                         \
             TSDF_LAUNCH_TIMED(v, 0, (integrate_packed_colour_kernel<CNT, BITS>), grid, block, v->dist, v->wpacked, v->g, bg, ip, mk, width, height, \
                               d_depth, v->depth_pad, counter_arg, v->occ, v->brick_list, boxes, coords, count, plane_const, v->touched, v->colour, d_rgb); \
         else                                                                                                                    \

@@ -1,5 +1,5 @@
 // The body of integrate_packed_kernel and integrate_packed_colour_kernel (integrate_packed.hip), included inside each of the two:
-// not a header.  The including kernel declares `tile`, `plane_lds`, `constexpr bool COLOUR`, `colour` and `rgb`.  (A body shared
+// not a header.  The including kernel declares `tile`, `plane_lds`, `constexpr bool COLOUR`, `colour`, `rgb`, `constexpr bool CAPPED`, `cap`.  (A body shared
 // through an inlined device function compiled to other instructions for the plain kernel than the body written inside it.)
     constexpr int kPlanesPerWord = 32 / WBITS, kWords = kBatchZ / kPlanesPerWord;
     static_assert(kBatchZ == 4 && (WBITS == 8 || WBITS == 16), "a batch is two pairs of planes");
@@ -269,6 +269,12 @@
                     asm("" : "+v"(prior_weight));   // (opaque: the compiler otherwise forms count + 1 in integers and converts a second time)
                     const float new_weight = prior_weight + 1.0f;                                                   // :375-376
                     const float new_distance = div_by_count((pd_[j] * prior_weight) + (tsdf_[j] * 1.0f), new_weight);   // :381
+                    if constexpr (CAPPED) {
+                        // the stored count is min(count + 1, cap) -- the divisor above stays count + 1 -- as a signed step of this field
+                        // alone: 0 at the cap, negative for a count found above it; every field stays inside its bits, so no carry or borrow
+                        const uint32_t c = (pw_[w] >> s) & kMask;
+                        nw_[w] += (min(c + 1u, cap) - c) << s;
+                    } else
                     nw_[w] += 1u << s;   // (the caller has made room: weights.hip, weights_make_room)
                     // The distance is stored only when its bits change: a voxel that has only seen free space holds +trunc, and the
                     // blend (D w + trunc) / (w + 1) gives +trunc back bit for bit at most counts (it moves at 6, 7, 9, 12, 22, 25, ...),

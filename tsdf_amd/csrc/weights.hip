@@ -220,7 +220,11 @@ static int widen_to_16(tsdf_volume *v) {
 // region seen 250 times that then leaves the view would leave the bound at 250 and the scan due every 5th frame for the rest of the
 // session.  So the mode is widened already when the largest count is in the top quarter of what it holds, and a scan that keeps the
 // mode buys at least 64 (16 384) integrations without another.
+// With a weight cap (tsdf_volume_set_weight_cap) the capped kernels store min(count + 1, cap): a cap that fits the mode's field -- at
+// most 255 in 8 bits, any cap in 16 -- keeps every count inside it for ever (a count found above the cap only comes down), so there is
+// nothing to look at and nothing to widen: no scan, no host round trip.  A cap above 255 in 8 bits goes by the rule above.
 int weights_make_room(tsdf_volume *v) {
+    if (v->weight_cap && (v->wmode == 16 || (v->wmode == 8 && v->weight_cap <= 255u))) return TSDF_OK;
     bool widen = false;
     if ((v->wmode == 8 && v->weight_bound >= 255u) || (v->wmode == 16 && v->weight_bound >= 65535u)) {
         const int rc = refresh_bound(v);
@@ -381,6 +385,19 @@ int tsdf_volume_set_weight_storage(tsdf_volume *v, int bits_per_weight) {
     if (now == 8 && bits_per_weight >= 16) rc = widen_to_16(v);
     if (rc == TSDF_OK && bits_per_weight == 32) rc = weights_require_f32(v);
     return rc;
+}
+
+int tsdf_volume_set_weight_cap(tsdf_volume *v, uint32_t cap) {
+    TSDF_REQUIRE(v, "null argument");
+    TSDF_REQUIRE(cap <= 65535u, "tsdf_volume_set_weight_cap: the cap is 0 (off) or 1 .. 65535");
+    v->weight_cap = cap;   // (read by the next integrate: launch_integrate, weights_make_room)
+    return TSDF_OK;
+}
+
+int tsdf_volume_weight_cap(const tsdf_volume *v, uint32_t *cap) {
+    TSDF_REQUIRE(v && cap, "null argument");
+    *cap = v->weight_cap;
+    return TSDF_OK;
 }
 
 int tsdf_volume_weight_storage(const tsdf_volume *v, int *bits_per_weight, int *pinned) {

@@ -140,6 +140,15 @@ void TSDFVolume::integrate(const uint16_t *depth_map, uint32_t width, uint32_t h
     if (tsdf_host::verbose()) std::cout << "Integration finished" << std::endl;
 }
 
+// ---- weight cap (what the reference's m_max_weight was for)
+void TSDFVolume::weight_cap(uint32_t cap) { check(tsdf_volume_set_weight_cap(m_handle, cap), "Couldn't set the weight cap"); }
+
+uint32_t TSDFVolume::weight_cap() const {
+    uint32_t cap = 0;
+    check(tsdf_volume_weight_cap(m_handle, &cap), "Couldn't query the weight cap");
+    return cap;
+}
+
 // ---- colour fusion (no reference counterpart)
 void TSDFVolume::enable_colour(bool enabled) {
     check(tsdf_volume_enable_colour(m_handle, enabled ? 1 : 0), "Couldn't enable colour");
