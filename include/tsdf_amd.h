@@ -246,6 +246,44 @@ int tsdf_volume_last_distance_stores(const tsdf_volume *volume, uint64_t *count)
 int tsdf_volume_set_weight_cap(tsdf_volume *volume, uint32_t cap);   /* 0 = off (default: the reference's behaviour), 1..65535 */
 int tsdf_volume_weight_cap(const tsdf_volume *volume, uint32_t *cap);
 
+/* ---- de-integration (no reference counterpart: the reference's volume can only accumulate) ------------------------------------------ */
+/* Takes a fused frame back out.  tsdf_deintegrate* takes the arguments of tsdf_integrate* and visits every voxel that tsdf_integrate
+ * visits for the same depth image and camera -- the same frustum, depth and sdf >= -trunc tests, the same tsdf value, the same handling
+ * of deformation nodes; that set depends on the image and the camera only, never on the volume's contents.  A volume on which it is
+ * never called launches and allocates nothing new.  With w = prior_weight and D = prior_distance, in fp32, every operation rounded on
+ * its own, in this order:
+ *       if (!(w >= 1.0f))          the voxel is left alone            (never fused, already removed, a NaN weight)
+ *       else  nw = w - 1.0f
+ *             if (nw > 0.0f)  new_distance = ((D * w) - (tsdf * 1.0f)) / nw ;  weight = nw
+ *             else            new_distance = truncation_distance ;             weight = 0     (what tsdf_volume_clear leaves)
+ * So:
+ *   - sequence property: after any sequence of integrates on a cleared, uncapped volume, de-integrating all of the same frames, in any
+ *     order, leaves every distance at truncation_distance and every weight at 0, bit for bit;
+ *   - one removal gives the other frames' average up to rounding.  With u = 2^-24 and T = truncation_distance: an integrate changes
+ *     the voxel's sum D * w by the frame's tsdf within (3 w - 1) u T (the product at most (w - 1) T, the sum at most w T, the quotient
+ *     at most T, each rounded once), a removal by -tsdf within 3 w u T.  Removing the frame integrated last therefore returns the
+ *     distance the voxel had before it within (5 w / (w - 1) + 1) u T <= 11 u T < 6 * 2^-23 * T for every prior weight w >= 2: the
+ *     bound does not grow with w.  Removing an earlier frame differs from the fp32 average of the remaining frames by the rounding
+ *     of both running means as well, 3 u T per operation in the worst case -- any two orders of averaging differ by that;
+ *   - weight cap: a volume with tsdf_volume_weight_cap != 0 is refused, TSDF_ERR_INVALID with a message: a saturated count is not a
+ *     frame count;
+ *   - colour words are never touched: the integer colour blend (rounded, saturating at 255) is not invertible.  There is no coloured
+ *     variant;
+ *   - storage: packed 8- and 16-bit counts go down in their own field (w >= 1: no borrow); the storage neither widens nor narrows,
+ *     the bound behind tsdf_volume_weight_storage stays an upper bound.  Volumes the packed kernel does not serve (explicit
+ *     deformation nodes, cameras not of the standard shape) take the fp32 layout as they do for tsdf_integrate;
+ *   - tsdf_volume_last_updated_voxels counts the voxels whose weight went down, tsdf_volume_last_distance_stores the distance stores
+ *     made (a distance whose bits stay is not written back);
+ *   - occupancy stays a conservative superset: a removal that pulls a distance down flags its bricks as an integrate does; a ray
+ *     cast after a removal gives exactly the picture it gives after a forced rebuild of the flags;
+ *   - Z-slab volumes take out their own planes; the caller de-integrates on every slab of a grid.
+ * Host variant: blocking, depth in host memory.  Device variant: depth in HBM, asynchronous on the volume's stream.  The frame must be
+ * given exactly as it was integrated (the filtered image where the filtered image was fused) and at the same camera. */
+int tsdf_deintegrate(tsdf_volume *volume, const uint16_t *host_depth, uint32_t width, uint32_t height,
+                     const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]);
+int tsdf_deintegrate_device(tsdf_volume *volume, const uint16_t *device_depth, uint32_t width, uint32_t height,
+                            const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]);
+
 /* ---- colour fusion (no reference counterpart: the reference allocates a uchar3 colour per voxel, src/include/TSDFVolume.hpp:290-293,
  * that none of its kernels writes) --------------------------------------------------------------------------------------------- */
 /* Opt-in per volume.  A volume that never enables colour behaves exactly as without this group: no allocation, no launch.
@@ -478,6 +516,15 @@ int tsdf_tracker_integrate(tsdf_tracker *tracker, const tsdf_camera_matrices *ca
 /* tsdf_tracker_integrate plus the colour of device_rgb (as tsdf_pipeline_step_colour: the filtered frame, rgb valid until the
  * integrate has run on the tracker's stream; refused without colour enabled or with a NULL rgb frame). */
 int tsdf_tracker_integrate_colour(tsdf_tracker *tracker, const tsdf_camera_matrices *camera, const uint8_t *device_rgb);
+/* Windowed tracking: n = 0 (the default) is off -- nothing is kept, nothing allocated.  n >= 1 makes the tracker keep device copies of
+ * the last n filtered frames it integrated with their camera matrices (n * width * height * 2 bytes); tsdf_tracker_integrate and
+ * tsdf_tracker_integrate_colour then integrate the new frame and, once n frames are kept, take the oldest back out on the same stream
+ * (tsdf_deintegrate_device; colour words stay): the volume holds exactly the last n frames.  Refused with a message when the volume has
+ * a weight cap (TSDF_ERR_INVALID), when the ring cannot be allocated (TSDF_ERR_NOMEM) and between tsdf_tracker_filter and the integrate
+ * of that frame (TSDF_ERR_INVALID).  Setting n again, to the same value too, resizes the ring and forgets the frames it held; the volume
+ * is left as it is. */
+int tsdf_tracker_set_window(tsdf_tracker *tracker, uint32_t n);
+int tsdf_tracker_window(const tsdf_tracker *tracker, uint32_t *n);
 int tsdf_tracker_synchronize(tsdf_tracker *tracker);
 int tsdf_tracker_streams(const tsdf_tracker *tracker, void **main_stream, void **side_stream);
 /* The ICP inputs of the last aligned frame: the rendered model depth and the filtered frame (width * height uint16, device). */

@@ -8,7 +8,10 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N]
+//   --window N (with --track): tsdf_tracker_set_window(N) -- the volume holds the last N tracked frames, each integrate past the N-th takes
+//           the oldest back out (tsdf_deintegrate); 0 (the default) = off; refused without --track, with --weight-cap and with --ranks; the
+//           line gains "window": N.
 //   --weight-cap N: tsdf_volume_set_weight_cap(N) on the volume (with --ranks on every slab) before the first step -- a running average
 //           whose counts stay in 8 bits for N <= 255; 0 (the default) = off; valid with --track, --colour and --ranks; the line gains
 //           "weight_cap": N.
@@ -118,6 +121,7 @@ int main(int argc, char **argv) {
     bool overlap = true, cull_ahead = true, track = false, validate_merge = false, colour = false;
     unsigned planes = 0;
     long weight_cap = 0;
+    long window = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&]() -> const char * {
@@ -142,8 +146,9 @@ int main(int argc, char **argv) {
         else if (a == "--validate-merge") validate_merge = true;
         else if (a == "--colour") colour = true;
         else if (a == "--weight-cap") weight_cap = std::atol(value());
+        else if (a == "--window") window = std::atol(value());
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N]\n");
             return 2;
         }
     }
@@ -154,6 +159,10 @@ int main(int argc, char **argv) {
     }
     if (weight_cap < 0 || weight_cap > 65535) {
         std::fprintf(stderr, "kinfu_stream: --weight-cap is 0 (off) or 1 .. 65535\n");
+        return 2;
+    }
+    if (window < 0 || window > 65535 || (window && (!track || weight_cap || ranks > 1))) {
+        std::fprintf(stderr, "kinfu_stream: --window is 0 (off) or 1 .. 65535 frames; it needs --track and goes with neither --weight-cap nor --ranks\n");
         return 2;
     }
     if (colour && ranks > 1) {
@@ -300,6 +309,7 @@ int main(int argc, char **argv) {
         tsdf_tracker *trk = nullptr;
         ok(tsdf_icp_create((int)W, (int)H, k(0, 2), k(1, 2), k(0, 0), k(1, 1), 0.10f, sinf(20.f * 3.14159254f / 180.f), &icp), "ICP");   // ICPOdometry.h:27
         ok(tsdf_tracker_create(vol, bil, icp, W, H, 20.0f, overlap ? TSDF_PIPELINE_OVERLAP : 0, &trk), "tracker");
+        if (window) ok(tsdf_tracker_set_window(trk, (uint32_t)window), "window");
         const size_t n_track = std::min(F, (size_t)K);
         std::vector<float> tracked;
         float error = 0.f, inliers = 0.f;
@@ -342,6 +352,7 @@ int main(int argc, char **argv) {
                     n, W, H, n_track, overlap ? "true" : "false", n_track > first_timed ? elapsed * 1e3 / (double)(n_track - first_timed) : 0.0, std::sqrt(dt2),
                     inliers, error);
         if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
+        if (window) std::printf(", \"window\": %ld", window);
         std::printf(colour ? ", \"colour\": true}\n" : "}\n");
         if (!dump_dir.empty()) {
             dump(dump_dir + "/poses.f32", tracked.data(), tracked.size() * sizeof(float));

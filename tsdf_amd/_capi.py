@@ -95,6 +95,8 @@ _SIGS = {
     "tsdf_volume_set_offset_at_clear": (_i, [_vp, _vp]),
     "tsdf_integrate": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
     "tsdf_integrate_device": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_deintegrate": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_deintegrate_device": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
     "tsdf_integrate_device_tiles": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _vp]),
     "tsdf_integrate_prepare_device_tiles": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _vp, _vp]),
     "tsdf_integrate_discard_prepared": (_i, [_vp]),
@@ -150,6 +152,8 @@ _SIGS = {
     "tsdf_tracker_align": (_i, [_vp, C.POINTER(CameraMatrices), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tsdf_tracker_integrate": (_i, [_vp, C.POINTER(CameraMatrices)]),
     "tsdf_tracker_integrate_colour": (_i, [_vp, C.POINTER(CameraMatrices), _vp]),
+    "tsdf_tracker_set_window": (_i, [_vp, _u32]),
+    "tsdf_tracker_window": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "tsdf_tracker_synchronize": (_i, [_vp]),
     "tsdf_tracker_streams": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_tracker_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -239,6 +239,22 @@ class TSDFVolume:
             check(lib.tsdf_integrate_device(self._h, C.c_void_p(int(depth_ptr)), width, height, _fp(pose), _fp(ipose),
                                             _fp(k), _fp(kinv)))
 
+    def deintegrate(self, depth_map, width, height, camera):
+        """Take a frame back out (include/tsdf_amd.h, "de-integration"): the depth map and camera of an earlier integrate().  Blocking.
+        Refused on a volume with a weight cap."""
+        if depth_map is None:
+            raise AssertionError("depth_map")
+        d = np.ascontiguousarray(depth_map, dtype=np.uint16).reshape(-1)
+        if d.size != width * height:
+            raise ValueError("depth map has %d pixels, expected %d" % (d.size, width * height))
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_deintegrate(self._h, d.ctypes.data, width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
+    def deintegrate_device(self, depth_ptr, width, height, camera):
+        """deintegrate() of a device image (width*height uint16), asynchronous on the volume's stream."""
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_deintegrate_device(self._h, C.c_void_p(int(depth_ptr)), width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
     def integrate_prepare_device(self, depth_ptr, width, height, camera, tile_max_ptr, stream):
         """The brick culling of integrate_device(depth_ptr, ..., tile_max_ptr=...) ahead of time, on `stream` (see
         tsdf_integrate_prepare_device_tiles); the matching integrate_device call then launches the integrate kernel alone."""

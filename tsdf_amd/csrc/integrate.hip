@@ -91,7 +91,7 @@ __device__ inline void mark_occupied(const OccGrid &occ, uint32_t vx, uint32_t v
 // integrate_packed.hip
 int launch_integrate_packed_kernel(tsdf_volume *v, dim3 grid, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, uint32_t width,
                                    uint32_t height, const uint16_t *d_depth, unsigned long long *counter_arg, const uint4 *boxes,
-                                   const uint2 *coords, const uint32_t *count, const float4 *plane_const, const uint8_t *d_rgb);
+                                   const uint2 *coords, const uint32_t *count, const float4 *plane_const, const uint8_t *d_rgb, bool remove);
 
 // colour.hip
 int launch_colour_integrate(tsdf_volume *v, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, const Mat33 &mkinv, bool std_camera,
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void brick_cull_kernel(const Geom g, const Bri
         const uint32_t *__restrict__ count, const float4 *__restrict__ plane_const, uint8_t *__restrict__ touched
 template <bool DEFORM, bool COUNT, bool STD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_kernel(TSDF_INTEGRATE_PARAMS) {
-    constexpr bool CAPPED = false;
+    constexpr bool CAPPED = false, REMOVE = false;
     const float capf = 0.0f;
 #include "integrate_body.hpp"
 }
@@ -305,7 +305,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // clamped to the cap.  A kernel of its own name: the plain kernels and their rocprof rows stay as they are.  capf = (float)cap, exact.
 template <bool DEFORM, bool COUNT, bool STD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_capped_kernel(TSDF_INTEGRATE_PARAMS, const float capf) {
-    constexpr bool CAPPED = true;
+    constexpr bool CAPPED = true, REMOVE = false;
+#include "integrate_body.hpp"
+}
+
+// De-integration (include/tsdf_amd.h, "de-integration") for every volume the packed kernel does not take -- fp32 weights (pinned,
+// uploaded, widened), general cameras, explicit nodes: the same walk, the blend inverted where the weight is at least 1.  A kernel of
+// its own name: the plain kernels and their rocprof rows stay as they are.
+template <bool DEFORM, bool COUNT, bool STD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_remove_kernel(TSDF_INTEGRATE_PARAMS) {
+    constexpr bool CAPPED = false, REMOVE = true;
+    const float capf = 0.0f;
 #include "integrate_body.hpp"
 }
 #undef TSDF_INTEGRATE_PARAMS
@@ -314,10 +324,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // (tsdf_integrate_prepare_device_tiles: the brick list of a frame built ahead, e.g. on a lower-priority stream while the
 // previous frame's ray cast runs -- the culling needs the depth image's tile maxima and the pose, not the volume); kIntBoth
 // then finds the list prepared (same image, pose, intrinsics, tile maxima) and launches integrate_kernel alone.
+// remove: tsdf_deintegrate* -- the same culling, list and counters, then the removal kernel of the volume's storage; the weights are
+// neither given room nor counted (weight_bound stays an upper bound), and the frame does not count as an integration.
 enum IntegratePhase { kIntBoth = 0, kIntPrepare = 1 };
 static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t width, uint32_t height,
                             const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *caller_tile_max = nullptr,
-                            IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr, const uint8_t *d_rgb = nullptr) {
+                            IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr, const uint8_t *d_rgb = nullptr,
+                            bool remove = false) {
     Mat44 ip;
     Mat33 mk, mkinv;
     memcpy(&ip, inv_pose, sizeof(ip));
@@ -476,13 +489,16 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     if (v->wmode != 0) {
         // (integrate_packed_kernel addresses a brick's planes with 32-bit byte offsets)
         const bool planes_fit = (size_t)g.X * g.Y * sizeof(float) * (kChunkZ + kBatchZ) < ((size_t)1 << 31);
-        int rcw = (v->nodes || !std_camera || brick_log || !planes_fit) ? weights_require_f32(v) : weights_make_room(v);
+        int rcw = (v->nodes || !std_camera || brick_log || !planes_fit) ? weights_require_f32(v) : (remove ? TSDF_OK : weights_make_room(v));
         if (rcw != TSDF_OK) return rcw;
     }
     const float capf = (float)v->weight_cap;   // (at most 65535: exact)
 #define LAUNCH(DEF, CNT, STDC)                                                                                       \
     do {                                                                                                             \
-        if (v->weight_cap)                                                                                           \
+        if (remove)                                                                                                  \
+            TSDF_LAUNCH_TIMED(v, 0, (integrate_remove_kernel<DEF, CNT, STDC>), grid, block, v->dist, v->weight, v->nodes, \
+                              g, bg, ip, mk, mkinv, width, height, d_depth, counter_arg, v->occ, v->brick_list, boxes, count, plane_const, v->touched); \
+        else if (v->weight_cap)                                                                                      \
             TSDF_LAUNCH_TIMED(v, 0, (integrate_capped_kernel<DEF, CNT, STDC>), grid, block, v->dist, v->weight, v->nodes, g, bg, ip, mk, mkinv, \
                               width, height, d_depth, counter_arg, v->occ, v->brick_list, boxes, count, plane_const, v->touched, capf);        \
         else                                                                                                         \
@@ -495,10 +511,10 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     if (v->wmode != 0) {
         const int rcp = launch_integrate_packed_kernel(v, dim3((unsigned)n_bricks), bg,   // (one brick per workgroup, always)
                                                         ip, mk, width, height, d_depth, counter_arg, boxes, coords, count, plane_const,
-                                                        fused_colour ? d_rgb : nullptr);
+                                                        fused_colour ? d_rgb : nullptr, remove);
         if (rcp != TSDF_OK) return rcp;
         // (with a cap a count at or above it never grows: uploaded counts above the cap keep the bound where it is)
-        if (!v->weight_cap || v->weight_bound < v->weight_cap) v->weight_bound++;
+        if (!remove && (!v->weight_cap || v->weight_bound < v->weight_cap)) v->weight_bound++;
     } else if (v->nodes) {
         if (v->counting) LAUNCH(true, true, false); else LAUNCH(true, false, false);
     } else if (std_camera) {
@@ -516,6 +532,7 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     diag_brick_report(v, bg, n_bricks, count, boxes, brick_log);   // TSDF_DEBUG_BRICKS: survivors, list order, per-brick clocks
 #endif
     v->reach_dirty = 1;  // bricks may have been flagged
+    if (remove) return TSDF_OK;   // (a removal only adds flags, like an integrate; it does not move the rebuild schedule)
     // The kernel only sets occupancy flags.  A voxel that was low when first seen (sensor dropouts smeared by the
     // bilateral filter put phantom surfaces into free space) and has since been averaged back up keeps its bricks
     // flagged, which fragments the empty regions the ray caster jumps over; so the flags are recomputed from the
@@ -549,6 +566,16 @@ int tsdf_integrate_device(tsdf_volume *v, const uint16_t *device_depth, uint32_t
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate: empty depth map");
     (void)pose;  // the reference passes pose to its kernel but never reads it (src/TSDF/TSDFVolume.cu:316)
     return launch_integrate(v, device_depth, width, height, inv_pose, k, kinv);
+}
+
+// de-integration (include/tsdf_amd.h): the frame's voxels are the ones tsdf_integrate_device visits; the blend is inverted
+int tsdf_deintegrate_device(tsdf_volume *v, const uint16_t *device_depth, uint32_t width, uint32_t height,
+                            const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]) {
+    TSDF_REQUIRE(v && device_depth && inv_pose && k && kinv, "tsdf_deintegrate: null argument");
+    TSDF_REQUIRE(width > 0 && height > 0, "tsdf_deintegrate: empty depth map");
+    TSDF_REQUIRE(v->weight_cap == 0, "tsdf_deintegrate: the volume has a weight cap (a saturated count is not a frame count: tsdf_volume_set_weight_cap(volume, 0) first)");
+    (void)pose;
+    return launch_integrate(v, device_depth, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, nullptr, true);
 }
 
 int tsdf_integrate_device_tiles(tsdf_volume *v, const uint16_t *device_depth, uint32_t width, uint32_t height,
@@ -592,6 +619,27 @@ int tsdf_integrate(tsdf_volume *v, const uint16_t *host_depth, uint32_t width, u
     int rc = tsdf_integrate_device(v, v->depth_buf, width, height, pose, inv_pose, k, kinv);
     if (rc != TSDF_OK) return rc;
     TSDF_HIP(hipStreamSynchronize(v->stream), "Integrate kernel failed");
+    return TSDF_OK;
+}
+
+int tsdf_deintegrate(tsdf_volume *v, const uint16_t *host_depth, uint32_t width, uint32_t height,
+                     const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]) {
+    TSDF_REQUIRE(v && host_depth && inv_pose && k && kinv, "tsdf_deintegrate: null argument");
+    TSDF_REQUIRE(width > 0 && height > 0, "tsdf_deintegrate: empty depth map");
+    TSDF_REQUIRE(v->weight_cap == 0, "tsdf_deintegrate: the volume has a weight cap (a saturated count is not a frame count: tsdf_volume_set_weight_cap(volume, 0) first)");
+    size_t bytes = (size_t)width * height * sizeof(uint16_t);
+    if (v->depth_cap < bytes) {
+        if (v->depth_buf) (void)hipFree(v->depth_buf);
+        v->depth_buf = nullptr;
+        v->depth_cap = 0;
+        TSDF_HIP(hipMalloc((void **)&v->depth_buf, bytes), "Couldn't allocate storage for depth map");
+        v->depth_cap = bytes;
+    }
+    TSDF_HIP(hipMemcpyAsync(v->depth_buf, host_depth, bytes, hipMemcpyHostToDevice, v->stream),
+             "Failed to copy depth map to GPU");
+    int rc = tsdf_deintegrate_device(v, v->depth_buf, width, height, pose, inv_pose, k, kinv);
+    if (rc != TSDF_OK) return rc;
+    TSDF_HIP(hipStreamSynchronize(v->stream), "De-integrate kernel failed");
     return TSDF_OK;
 }
 

@@ -1,5 +1,6 @@
 // The body of integrate_kernel and integrate_capped_kernel (integrate.hip), included inside each of the two: not a header (see
-// integrate_packed_body.hpp).  The including kernel declares `constexpr bool CAPPED` and `capf`, the weight cap as a float.
+// integrate_packed_body.hpp).  The including kernel declares `constexpr bool CAPPED`, `capf`, the weight cap as a float, and
+// `constexpr bool REMOVE` (integrate_remove_kernel: the frame is taken back out, include/tsdf_amd.h "de-integration").
     // Depth tile of the current brick: the pixel box the cull kernel derived for it, staged once per brick with
     // coalesced row loads; the per-voxel depth look-ups then read LDS instead of gathering from L2.
     __shared__ uint16_t tile[kTilePixels + 2];  // [kTilePixels] stays 0: where look-ups that miss the box are pointed
@@ -212,6 +213,26 @@
 #pragma unroll
             for (int j = 0; j < kBatchZ; j++) {
                 if (tsdf_[j] == tsdf_[j]) {
+                    if constexpr (REMOVE) {
+                        // de-integration: !(w >= 1) -- never fused, already taken out, a NaN -- is left alone; w - 1 > 0 inverts the blend,
+                        // otherwise (w == 1) the voxel returns to the cleared state
+                        if (pw_[j] >= 1.0f) {
+                            const float new_weight = pw_[j] - 1.0f;
+                            const float new_distance = new_weight > 0.0f ? ((pd_[j] * pw_[j]) - (tsdf_[j] * 1.0f)) / new_weight : g.trunc;
+                            const size_t pb = brick_base + plane * (size_t)(zb - z0 + j);
+                            (weight + pb)[lane_off] = new_weight;   // (+0 when it is not > 0)
+                            if (__float_as_uint(new_distance) != __float_as_uint(pd_[j])) {
+                                (dist + pb)[lane_off] = new_distance;
+                                wrote = true;
+                                if (COUNT) stores++;
+                            }
+                            if (!(new_distance > lo) || new_distance > hi) {
+                                const uint32_t o_ = zb + j - z0;
+                                if (o_ < 32u) low_lo |= 1u << o_; else low_hi |= 1u << (o_ - 32u);
+                            }
+                            if (COUNT) updated++;
+                        }
+                    } else {
                     const float new_weight = pw_[j] + 1.0f;
                     const float new_distance = ((pd_[j] * pw_[j]) + (tsdf_[j] * 1.0f)) / new_weight;
                     const size_t pb = brick_base + plane * (size_t)(zb - z0 + j);
@@ -233,6 +254,7 @@
                         if (o_ < 32u) low_lo |= 1u << o_; else low_hi |= 1u << (o_ - 32u);
                     }
                     if (COUNT) updated++;
+                    }
                 }
             }
         };

@@ -92,7 +92,7 @@ template <bool COUNT, int WBITS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED_WAVES, TSDF_PACKED_WAVES))) void integrate_packed_kernel(TSDF_PACKED_PARAMS) {
     __shared__ uint16_t tile[kTilePixels];                                   // the brick's pixel box inside a ring of zeros
     __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
-    constexpr bool COLOUR = false, CAPPED = false;
+    constexpr bool COLOUR = false, CAPPED = false, REMOVE = false;
     uint32_t *const colour = nullptr;
     const uint8_t *const rgb = nullptr;
     const uint32_t cap = 0;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
     TSDF_PACKED_PARAMS, uint32_t *__restrict__ colour, const uint8_t *__restrict__ rgb) {
     __shared__ uint16_t tile[kTilePixels];
     __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
-    constexpr bool COLOUR = true, CAPPED = false;
+    constexpr bool COLOUR = true, CAPPED = false, REMOVE = false;
     const uint32_t cap = 0;
 #include "integrate_packed_body.hpp"
 }
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
     TSDF_PACKED_PARAMS, const uint32_t cap) {
     __shared__ uint16_t tile[kTilePixels];
     __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
-    constexpr bool COLOUR = false, CAPPED = true;
+    constexpr bool COLOUR = false, CAPPED = true, REMOVE = false;
     uint32_t *const colour = nullptr;
     const uint8_t *const rgb = nullptr;
 #include "integrate_packed_body.hpp"
@@ -134,20 +134,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
     TSDF_PACKED_PARAMS, uint32_t *__restrict__ colour, const uint8_t *__restrict__ rgb, const uint32_t cap) {
     __shared__ uint16_t tile[kTilePixels];
     __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
-    constexpr bool COLOUR = true, CAPPED = true;
+    constexpr bool COLOUR = true, CAPPED = true, REMOVE = false;
+#include "integrate_packed_body.hpp"
+}
+
+// De-integration (include/tsdf_amd.h, "de-integration"): the same walk over the same voxels -- the set a frame updates depends on the
+// depth image and the camera only -- with the blend inverted: a count of at least 1 goes down by one in its own field (no borrow), the
+// distance becomes ((D w) - tsdf) / (w - 1), or +trunc with the last frame.  div_by_count's divisor w - 1 is 1 .. 65534.  A kernel of its
+// own name, compiled for the occupancy of the plain one: the plain kernels and their rocprof rows stay as they are.  No colour variant:
+// the integer colour blend cannot be inverted.
+template <bool COUNT, int WBITS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED_WAVES, TSDF_PACKED_WAVES))) void integrate_packed_remove_kernel(TSDF_PACKED_PARAMS) {
+    __shared__ uint16_t tile[kTilePixels];
+    __shared__ __align__(16) float plane_lds[(kChunkZ + kBatchZ) / 2 * kPairFloats];
+    constexpr bool COLOUR = false, CAPPED = false, REMOVE = true;
+    uint32_t *const colour = nullptr;
+    const uint8_t *const rgb = nullptr;
+    const uint32_t cap = 0;
 #include "integrate_packed_body.hpp"
 }
 #undef TSDF_PACKED_PARAMS
 
 // Launched by launch_integrate (integrate.hip) in place of integrate_kernel<false, *, true> when the volume's weights are packed.
 // d_rgb != nullptr: integrate_packed_colour_kernel, which also makes the frame's colour update (v->colour).
+// remove: integrate_packed_remove_kernel (tsdf_deintegrate*; no cap, no colour -- the callers see to it).
 int launch_integrate_packed_kernel(tsdf_volume *v, dim3 grid, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, uint32_t width,
                                    uint32_t height, const uint16_t *d_depth, unsigned long long *counter_arg, const uint4 *boxes,
-                                   const uint2 *coords, const uint32_t *count, const float4 *plane_const, const uint8_t *d_rgb) {
+                                   const uint2 *coords, const uint32_t *count, const float4 *plane_const, const uint8_t *d_rgb, bool remove) {
     const dim3 block(kTileX, kTileY, 1);
 #define LAUNCH(CNT, BITS)                                                                                                       \
     do {                                                                                                                        \
-        if (v->weight_cap && d_rgb)                                                                                             \
+        if (remove)                                                                                                             \
+            TSDF_LAUNCH_TIMED(v, 0, (integrate_packed_remove_kernel<CNT, BITS>), grid, block, v->dist, v->wpacked, v->g, bg, ip, mk, width, height, d_depth, \
+                              v->depth_pad, counter_arg, v->occ, v->brick_list, boxes, coords, count, plane_const, v->touched);                    \
+        else if (v->weight_cap && d_rgb)                                                                                        \
             TSDF_LAUNCH_TIMED(v, 0, (integrate_packed_colour_capped_kernel<CNT, BITS>), grid, block, v->dist, v->wpacked, v->g, bg, ip, mk, width, height, \
                               d_depth, v->depth_pad, counter_arg, v->occ, v->brick_list, boxes, coords, count, plane_const, v->touched, v->colour, d_rgb, \
                               v->weight_cap);                                                                                   \

@@ -1,5 +1,6 @@
 // The body of integrate_packed_kernel and integrate_packed_colour_kernel (integrate_packed.hip), included inside each of the two:
-// not a header.  The including kernel declares `tile`, `plane_lds`, `constexpr bool COLOUR`, `colour`, `rgb`, `constexpr bool CAPPED`, `cap`.  (A body shared
+// not a header.  The including kernel declares `tile`, `plane_lds`, `constexpr bool COLOUR`, `colour`, `rgb`, `constexpr bool CAPPED`, `cap`,
+// `constexpr bool REMOVE` (integrate_packed_remove_kernel: the frame is taken back out, include/tsdf_amd.h "de-integration").  (A body shared
 // through an inlined device function compiled to other instructions for the plain kernel than the body written inside it.)
     constexpr int kPlanesPerWord = 32 / WBITS, kWords = kBatchZ / kPlanesPerWord;
     static_assert(kBatchZ == 4 && (WBITS == 8 || WBITS == 16), "a batch is two pairs of planes");
@@ -265,6 +266,30 @@
                 if (upd_[j]) {
                     constexpr uint32_t kMask = WBITS == 8 ? 0xffu : 0xffffu;
                     const int w = j / kPlanesPerWord, s = (j % kPlanesPerWord) * WBITS;
+                    if constexpr (REMOVE) {
+                        // de-integration: a voxel whose count is 0 (never fused, or already taken out) is left alone; the others get
+                        // ((D w) - tsdf) / (w - 1), or the cleared state (+trunc, 0) when this was their only frame.  The count goes down
+                        // in its own field: it is at least 1, so nothing is borrowed from the neighbour.
+                        const uint32_t c = (pw_[w] >> s) & kMask;
+                        if (c >= 1u) {
+                            float prior_weight = (float)c;
+                            asm("" : "+v"(prior_weight));   // (opaque, as in the blend below)
+                            const float new_weight = prior_weight - 1.0f;
+                            float new_distance = g.trunc;
+                            if (new_weight > 0.0f) new_distance = div_by_count((pd_[j] * prior_weight) - (tsdf_[j] * 1.0f), new_weight);
+                            nw_[w] -= 1u << s;
+                            if (__float_as_uint(new_distance) != __float_as_uint(pd_[j])) {   // (only a distance whose bits change is stored)
+                                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(new_distance), drsrc, lane_off4, dsoff(o + j), 0);
+                                wrote = true;
+                                if (COUNT) stores++;
+                            }
+                            if (!(new_distance > lo) || new_distance > hi) {   // (the blend's test: a removal can pull a distance down)
+                                const uint32_t o_ = o + j;
+                                if (o_ < 32u) low_lo |= 1u << o_; else low_hi |= 1u << (o_ - 32u);
+                            }
+                            if (COUNT) updated++;
+                        }
+                    } else {
                     float prior_weight = (float)((pw_[w] >> s) & kMask);
                     asm("" : "+v"(prior_weight));   // (opaque: the compiler otherwise forms count + 1 in integers and converts a second time)
                     const float new_weight = prior_weight + 1.0f;                                                   // :375-376
@@ -290,6 +315,7 @@
                         if (o_ < 32u) low_lo |= 1u << o_; else low_hi |= 1u << (o_ - 32u);
                     }
                     if (COUNT) updated++;
+                    }
                 }
             }
 #pragma unroll

@@ -141,6 +141,10 @@ struct tsdf_tracker {
     int cur;
     bool have_frame;
     uint64_t frames;            // frames integrated
+    // tsdf_tracker_set_window: the last `window` frames as they were integrated (filtered image + camera), oldest at ring_head
+    uint32_t window, ring_count, ring_head;
+    uint16_t *ring;             // window * width * height pixels
+    tsdf_camera_matrices *ring_cam;
 };
 
 using namespace tsdf;
@@ -662,6 +666,8 @@ int tsdf_tracker_destroy(tsdf_tracker *t) {
     }
     if (t->ready) (void)hipEventDestroy(t->ready);
     if (t->model) (void)hipFree(t->model);
+    if (t->ring) (void)hipFree(t->ring);
+    delete[] t->ring_cam;
     if (t->side) (void)hipStreamDestroy(t->side);
     if (t->main) (void)hipStreamDestroy(t->main);
     delete t;
@@ -793,9 +799,56 @@ static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera
         rc = tsdf_integrate_device_tiles(t->volume, t->filtered[b], t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
                                          t->tile_max[b]);
     if (rc != TSDF_OK) return rc;
+    if (t->window) {
+        // the new frame is in; once the ring is full the oldest goes out (same stream), and the new one takes its slot
+        const size_t n = (size_t)t->width * t->height;
+        uint32_t slot = (t->ring_head + t->ring_count) % t->window;
+        if (t->ring_count == t->window) {
+            slot = t->ring_head;
+            const tsdf_camera_matrices &old = t->ring_cam[slot];
+            rc = tsdf_deintegrate_device(t->volume, t->ring + n * slot, t->width, t->height, old.pose, old.inv_pose, old.k, old.kinv);
+            if (rc != TSDF_OK) return rc;
+            t->ring_head = (t->ring_head + 1u) % t->window;
+        } else
+            t->ring_count++;
+        TSDF_HIP(hipMemcpyAsync(t->ring + n * slot, t->filtered[b], n * sizeof(uint16_t), hipMemcpyDeviceToDevice, t->main), "tracker: keep the frame");
+        t->ring_cam[slot] = *camera;
+    }
     if (t->side) TSDF_HIP(hipEventRecord(t->integrated[b], t->main), "tracker: integrate done");
     t->have_frame = false;
     t->frames++;
+    return TSDF_OK;
+}
+
+int tsdf_tracker_set_window(tsdf_tracker *t, uint32_t n) {
+    TSDF_REQUIRE(t, "tsdf_tracker_set_window: null tracker");
+    TSDF_REQUIRE(!t->have_frame, "tsdf_tracker_set_window: a frame has been filtered and not yet integrated (call it between frames)");
+    TSDF_REQUIRE(n == 0 || t->volume->weight_cap == 0, "tsdf_tracker_set_window: the volume has a weight cap (a window takes frames back out: tsdf_deintegrate)");
+    TSDF_HIP(hipStreamSynchronize(t->main), "tsdf_tracker_set_window");   // (a removal may still read the old ring)
+    if (t->ring) (void)hipFree(t->ring);
+    delete[] t->ring_cam;
+    t->ring = nullptr;
+    t->ring_cam = nullptr;
+    t->window = t->ring_count = t->ring_head = 0;
+    if (n == 0) return TSDF_OK;
+    const size_t bytes = (size_t)n * t->width * t->height * sizeof(uint16_t);
+    tsdf_camera_matrices *cams = new (std::nothrow) tsdf_camera_matrices[n];
+    uint16_t *ring = nullptr;
+    if (!cams || hipMalloc((void **)&ring, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        delete[] cams;
+        set_error("tsdf_tracker_set_window: cannot allocate the ring of %u frames (%zu bytes)", n, bytes);
+        return TSDF_ERR_NOMEM;
+    }
+    t->ring = ring;
+    t->ring_cam = cams;
+    t->window = n;
+    return TSDF_OK;
+}
+
+int tsdf_tracker_window(const tsdf_tracker *t, uint32_t *n) {
+    TSDF_REQUIRE(t && n, "tsdf_tracker_window: null argument");
+    *n = t->window;
     return TSDF_OK;
 }
 

@@ -103,6 +103,10 @@ public:
     // integrate() plus the colour of `rgb` (8-bit interleaved RGB, width * height * 3, registered to the depth map); needs colour on
     void integrate(const uint16_t *depth_map, const uint8_t *rgb, uint32_t width, uint32_t height, const Camera &camera);
 
+    // De-integration (include/tsdf_amd.h, "de-integration"; not in the reference's class): takes the frame of an earlier integrate() --
+    // the same depth map at the same camera -- back out.  Throws std::invalid_argument on a volume with a weight cap.
+    void deintegrate(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera);
+
     // Weight cap (include/tsdf_amd.h, "weight cap"; what the reference's m_max_weight was for): integrate stores min(weight + 1, cap),
     // the blend's divisor stays weight + 1.  0 = off (the default), 1 .. 65535; throws std::invalid_argument above that.
     void weight_cap(uint32_t cap);

@@ -141,6 +141,13 @@ void TSDFVolume::integrate(const uint16_t *depth_map, uint32_t width, uint32_t h
 }
 
 // ---- weight cap (what the reference's m_max_weight was for)
+void TSDFVolume::deintegrate(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera) {
+    assert(depth_map);
+    const Eigen::Matrix3f k = camera.k(), kinv = camera.kinv();
+    check(tsdf_deintegrate(m_handle, depth_map, width, height, camera.pose().data(), camera.inverse_pose().data(), k.data(), kinv.data()),
+          "De-integrate kernel failed");
+}
+
 void TSDFVolume::weight_cap(uint32_t cap) { check(tsdf_volume_set_weight_cap(m_handle, cap), "Couldn't set the weight cap"); }
 
 uint32_t TSDFVolume::weight_cap() const {

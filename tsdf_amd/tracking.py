@@ -22,7 +22,7 @@ from .pipeline import OVERLAP, _matrices
 
 
 class FrameToModelTracker:
-    def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True):
+    def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True, window=0):
         import torch
         self.torch = torch
         self.volume = volume
@@ -42,6 +42,8 @@ class FrameToModelTracker:
         m, s = C.c_void_p(), C.c_void_p()
         check(lib.tsdf_tracker_streams(self._h, C.byref(m), C.byref(s)))
         self.stream = torch.cuda.ExternalStream(m.value, device=torch.device("cuda", torch.cuda.current_device()))
+        if window:
+            self.set_window(window)
         self.frames = 0
         self.last_error, self.last_inliers = 0.0, 0.0
         self.last_T = None          # the last incremental transformation (4x4, metres) as ICPOdometry returned it
@@ -52,6 +54,19 @@ class FrameToModelTracker:
             self._h = C.c_void_p()
 
     __del__ = close
+
+    def set_window(self, n):
+        """Keep only the last `n` frames in the volume (0: every frame, the default): each integrate past the n-th takes the oldest
+        kept frame back out (tsdf_tracker_set_window).  Refused on a volume with a weight cap."""
+        n = int(n)
+        if n < 0 or n > 0xFFFFFFFF:
+            raise ValueError("set_window: the window is 0 (off) or a number of frames")
+        check(lib.tsdf_tracker_set_window(self._h, n))
+
+    def window(self):
+        n = C.c_uint32()
+        check(lib.tsdf_tracker_window(self._h, C.byref(n)))
+        return int(n.value)
 
     def pose(self):
         """Current camera pose, 4x4 float64 (camera -> world, millimetres)."""
