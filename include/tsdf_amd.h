@@ -332,6 +332,51 @@ int tsdf_raycast_colour(const tsdf_volume *volume, uint32_t width, uint32_t heig
 int tsdf_raycast_colour_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
                                const float kinv[9], float *device_vertices, float *device_normals, uint8_t *device_rgb);
 
+/* ---- field queries (no reference counterpart: the reference's volume can be fused into, rendered and meshed, not asked) ---------- */
+/* The trilinear distance, its gradient and the weight of the fused field at world points.  Opt-in by being called: a volume on which
+ * these are never called does exactly what it did.
+ *   Frame: for a world point p (mm), q = p - offset per axis in fp32, offset being the volume's CURRENT offset -- the space_min of the
+ *     ray cast and the frame tsdf_volume_marching_cubes emits vertices in, because the points one asks about are ray-cast and mesh
+ *     vertices.  This is deliberately NOT the frame of tsdf_volume_sample_colours_device, which also subtracts offset_at_clear.
+ *   S(q): the ray cast's trilinear sample (src/RayCaster/GPURaycaster.cu:53-124 as tsdf_raycast evaluates it), bit for bit: the same
+ *     voxel_for_point, the same lower-corner rule on the unclamped point, the same tap clamping at the far faces, the same eight-term
+ *     sum in the same order, every fp32 operation rounded on its own.
+ *   valid(q): every component is finite, >= 0 and < size[i] * voxel_size[i] (the fp32 product); -0.0 is valid.
+ *   distance: S(q) if valid(q), else NaN.
+ *   weight: the weight of the voxel (int)floorf(q[i] / voxel_size[i]) (IEEE division) as a float if valid(q), else 0.0f -- the same
+ *     value in all three storages (8-bit counts, 16-bit counts, fp32); uploaded non-integer or NaN fp32 weights come back as stored.
+ *     (A valid point within rounding of the upper bound can divide to size[i] itself: there is no such voxel, the weight is 0.0f and
+ *     the distance, as in the ray cast, NaN.)  The query never widens, pins or converts the storage: tsdf_volume_weight_storage
+ *     reports the same before and after.
+ *   gradient: with h = voxel_size, for each axis a, q+ = q with q[a] + h[a] and q- = q with q[a] - h[a] (one fp32 add each) and
+ *         grad[a] = (S(q+) - S(q-)) / (h[a] + h[a])
+ *     each S a full sample as above.  If q or any of the six shifted points is not valid, the whole gradient is (NaN, NaN, NaN): within
+ *     one voxel of a face the distance is a number and the gradient is not.  The TSDF is positive in front of a surface, so the
+ *     gradient points out of it.
+ *   TSDF_FIELD_UNIT_GRADIENT: len = sqrtf((gx * gx + gy * gy) + gz * gz), the output is grad / len per component; if len is not > 0
+ *     (zero, or NaN) the output is the NaN triple.  (Correctly rounded sqrtf and division.)
+ *   Explicit deformation nodes are ignored, as the ray cast ignores them.
+ *   Refused (TSDF_ERR_INVALID, with a message): a Z-slab volume (tsdf_volume_create_slab: the taps cross slab boundaries); all three
+ *     outputs NULL; NULL points with n > 0.  n == 0 is TSDF_OK and launches nothing.
+ *   Stream order: the query reads the distance array and the weight storage on the stream it is given (NULL = the default stream);
+ *     the caller orders that stream behind the integrates it wants to see (and in front of whatever replaces the weight storage:
+ *     an integrate that widens it, tsdf_volume_weights, clear).  It writes nothing that belongs to the volume: no occupancy flag, no
+ *     dirty mark, no counter.
+ *   Out of scope: slab volumes, queries in the deformed space, colour interpolation, use inside the tracker. */
+#define TSDF_FIELD_UNIT_GRADIENT 1
+/* n points (3 floats each, device) -> distance (n floats), gradient (3 n floats), weight (n floats): any of the three may be NULL and
+ * then costs nothing (a distance-only or weight-only query reads none of the gradient's taps). */
+int tsdf_volume_sample_field_device(const tsdf_volume *volume, uint64_t n, const float *device_points, float *device_distance,
+                                    float *device_gradient, float *device_weight, int flags, void *hip_stream);
+/* The same on host arrays, on the volume's stream; blocking. */
+int tsdf_volume_sample_field(const tsdf_volume *volume, uint64_t n, const float *host_points, float *host_distance,
+                             float *host_gradient, float *host_weight, int flags);
+/* tsdf_raycast_device, then the unit gradient at every vertex in place of compute_normals (whose cross products are NaN along every
+ * silhouette and beside every miss); a miss is the NaN triple.  The vertices are those of tsdf_raycast_device.  Asynchronous on the
+ * volume's stream. */
+int tsdf_raycast_gradient_normals_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
+                                         const float kinv[9], float *device_vertices, float *device_normals);
+
 /* ---- raycast ---------------------------------------------------------------------------- */
 /* Replaces GPURaycaster::raycast = get_vertices/process_ray + compute_normals
  * (src/RayCaster/GPURaycaster.cu:519-547, 432-486, 265-377, 393-427, 496-510).

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSDF_HIP_LIB") or os.path.join(_HERE, "lib", "libtsdf_hip.so")
 
 TSDF_OK, TSDF_ERR_INVALID, TSDF_ERR_DEVICE, TSDF_ERR_NOMEM = 0, 1, 2, 3
+TSDF_FIELD_UNIT_GRADIENT = 1
 
 
 class TsdfError(RuntimeError):
@@ -115,6 +116,9 @@ _SIGS = {
     "tsdf_volume_sample_colours_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp]),
     "tsdf_raycast_colour": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_raycast_colour_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
+    "tsdf_volume_sample_field_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _i, _vp]),
+    "tsdf_volume_sample_field": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _i]),
+    "tsdf_raycast_gradient_normals_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_raycast": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_raycast_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_normals_device": (_i, [_u32, _u32, _vp, _vp, _vp]),
@@ -230,6 +234,8 @@ _HOST_SIGS = {
     "tsdf_host_block_loader_parse": (_i, [C.c_char_p, _vp, _vp, _vp, _vp, C.c_size_t]),
     "tsdf_host_write_ply": (None, [C.c_char_p, _vp, C.c_size_t, _vp, C.c_size_t]),
     "tsdf_host_write_ply_coloured": (_i, [C.c_char_p, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "tsdf_host_write_ply_normals": (_i, [C.c_char_p, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "tsdf_host_write_ply_normals_coloured": (_i, [C.c_char_p, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     "tsdf_host_read_nyu_depth_map": (C.c_size_t, [C.c_char_p, C.POINTER(C.c_uint), _vp, C.c_size_t]),
     "tsdf_host_match_file_name": (_i, [C.c_char_p, _i, C.c_char_p, C.c_char_p, C.c_char_p]),
     "tsdf_host_process_file_by_lines": (C.c_size_t, [C.c_char_p, C.POINTER(_i), C.c_char_p, C.c_size_t]),

@@ -340,6 +340,39 @@ class TSDFVolume:
         V = self.extract_surface()
         return V, self.sample_colours(V)
 
+    # ---- field queries (include/tsdf_amd.h, "field queries"; not in the reference's class)
+    def sample_field_device(self, n, points_ptr, distance_ptr=None, gradient_ptr=None, weight_ptr=None, unit_gradient=False,
+                            stream=None):
+        """n points (3 float32 each, device) -> distance (n float32), gradient (3 n), weight (n): device pointers, any of the three
+        may be None; on `stream` (default: the volume's).  Points are in the frame of ray-cast and mesh vertices (the current
+        offset)."""
+        s = self.stream_ptr() if stream is None else stream
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_volume_sample_field_device(self._h, int(n), ptr(points_ptr), ptr(distance_ptr), ptr(gradient_ptr),
+                                                  ptr(weight_ptr), _capi.TSDF_FIELD_UNIT_GRADIENT if unit_gradient else 0,
+                                                  C.c_void_p(int(s) if s else 0)))
+
+    def sample_field(self, points, gradient=True, weight=True, unit_gradient=False):
+        """(n, 3) float32 world points (mm) -> (distance (n,), gradient (n, 3) or None, weight (n,) or None), float32: the trilinear
+        distance the ray cast samples (NaN outside the grid), its central-difference gradient (NaN triple within a voxel of a face;
+        unit_gradient: normalised -- it points out of the surface) and the weight of the voxel the point lies in (0 outside)."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        # (one row more than asked for: the pointer of an empty array may be null, which the C ABI reads as "not asked for")
+        d = np.empty(n + 1, np.float32)
+        g = np.empty((n + 1, 3), np.float32) if gradient else None
+        w = np.empty(n + 1, np.float32) if weight else None
+        check(lib.tsdf_volume_sample_field(self._h, n, p.ctypes.data if n else None, d.ctypes.data,
+                                           g.ctypes.data if gradient else None, w.ctypes.data if weight else None,
+                                           _capi.TSDF_FIELD_UNIT_GRADIENT if unit_gradient else 0))
+        return d[:n], g[:n] if gradient else None, w[:n] if weight else None
+
+    def extract_surface_with_normals(self):
+        """extract_surface() and the unit gradient of the field at every vertex (sample_field): (vertices (3T, 3), normals (3T, 3)),
+        float32; a normal is the NaN triple within a voxel of the grid's faces."""
+        V = self.extract_surface()
+        return V, self.sample_field(V, weight=False, unit_gradient=True)[1]
+
     def occupancy(self):
         """(occupied, total) bricks of the ray caster's empty-space summary."""
         o, t = C.c_uint64(), C.c_uint64()
@@ -417,6 +450,32 @@ class GPURaycaster:
         pose, _, _, kinv = _camera_matrices(camera)
         check(lib.tsdf_raycast_colour_device(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), C.c_void_p(int(vertices_ptr)),
                                              C.c_void_p(int(normals_ptr)) if normals_ptr else None, C.c_void_p(int(rgb_ptr))))
+
+    def raycast_gradient_normals(self, volume, camera):
+        """raycast() with the unit gradient of the fused field at every vertex in place of the cross-product normals (NaN along
+        every silhouette and beside every miss): -> (vertices, normals); the vertices are raycast()'s, a miss is a NaN row in both."""
+        n = self.m_width * self.m_height
+        V = np.empty((n, 3), np.float32)
+        N = np.empty((n, 3), np.float32)
+        if not n:
+            return V, N
+        dv = C.c_void_p()
+        check(lib.tsdf_device_alloc(2 * V.nbytes, C.byref(dv)))
+        try:
+            self.raycast_gradient_normals_device(volume, camera, dv.value, dv.value + V.nbytes)
+            volume.synchronize()
+            check(lib.tsdf_device_download(V.ctypes.data, dv, V.nbytes))
+            check(lib.tsdf_device_download(N.ctypes.data, C.c_void_p(dv.value + V.nbytes), N.nbytes))
+        finally:
+            volume.synchronize()
+            lib.tsdf_device_free(dv)
+        return V, N
+
+    def raycast_gradient_normals_device(self, volume, camera, vertices_ptr, normals_ptr):
+        """The same on device buffers (3 * width * height float32 each), asynchronous on the volume's stream."""
+        pose, _, _, kinv = _camera_matrices(camera)
+        check(lib.tsdf_raycast_gradient_normals_device(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv),
+                                                       C.c_void_p(int(vertices_ptr)), C.c_void_p(int(normals_ptr))))
 
     def get_vertices(self, volume, camera):
         pose, _, _, kinv = _camera_matrices(camera)

@@ -23,6 +23,12 @@ public:
     void raycast(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
                  Eigen::Matrix<float, 3, Eigen::Dynamic> &normals, std::vector<uchar3> &colours) const;
 
+    // raycast() with the unit gradient of the fused field at every vertex in place of the cross-product normals (which are NaN along
+    // every silhouette and beside every miss): tsdf_raycast_gradient_normals_device.  Same vertices; a miss is the NaN triple (not
+    // in the reference's class)
+    void raycast_gradient_normals(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
+                                  Eigen::Matrix<float, 3, Eigen::Dynamic> &normals) const;
+
     // ray cast, then camera-space z of every vertex rounded to uint16 mm; caller deletes the image
     DepthImage *render_to_depth_image(const TSDFVolume &volume, const Camera &camera) const;
 };

@@ -14,6 +14,13 @@ void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, st
 // enabled (not in the reference)
 void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
                      std::vector<uchar3> &colours);
+// with a normal per vertex: the unit gradient of the fused field there (tsdf_volume_sample_field, TSDF_FIELD_UNIT_GRADIENT), which
+// points out of the surface; the NaN triple within one voxel of the grid's faces and where the gradient vanishes.  Alone, or with
+// the colours as above (not in the reference)
+void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                     std::vector<float3> &normals);
+void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                     std::vector<float3> &normals, std::vector<uchar3> &colours);
 
 // The same marching cubes over a host distance array (x fastest, voxel centres at (i + 0.5) * voxel_size + offset):
 // appends three vertices per triangle.  extract_surface is this on the volume's distances.

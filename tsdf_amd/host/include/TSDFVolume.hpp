@@ -112,6 +112,14 @@ public:
     void weight_cap(uint32_t cap);
     uint32_t weight_cap() const;
 
+    // Field queries (include/tsdf_amd.h, "field queries"; not in the reference's class): the trilinear distance the ray cast samples, its
+    // central-difference gradient (unit_gradient: normalised; it points out of the surface) and the weight of the voxel each world
+    // point (mm, in the frame of ray-cast and mesh vertices: the current offset) lies in.  Any of the three outputs may be null; each
+    // one given is resized to points.size().  Outside the grid: NaN, the NaN triple, 0.  Throws std::invalid_argument on a Z-slab and
+    // when all three are null.
+    void sample_field(const std::vector<float3> &points, std::vector<float> *distances, std::vector<float3> *gradients,
+                      std::vector<float> *weights, bool unit_gradient = false) const;
+
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);
 

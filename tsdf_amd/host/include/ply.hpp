@@ -16,4 +16,17 @@ void write_to_ply(const std::string &file_name,
                   const std::vector<float3> &vertices,
                   const std::vector<int3> &triangles,
                   const std::vector<uchar3> &colours);
+
+// with a normal per vertex (extract_surface(volume, vertices, triangles, normals)): "property float nx / ny / nz" after
+// "property float z" and before the colour properties, " nx ny nz" after the coordinates of each vertex line, printed like them
+// (normals.size() == vertices.size(); a missing normal is written as 0 0 0)
+void write_to_ply(const std::string &file_name,
+                  const std::vector<float3> &vertices,
+                  const std::vector<int3> &triangles,
+                  const std::vector<float3> &normals);
+void write_to_ply(const std::string &file_name,
+                  const std::vector<float3> &vertices,
+                  const std::vector<int3> &triangles,
+                  const std::vector<float3> &normals,
+                  const std::vector<uchar3> &colours);
 #endif

@@ -33,6 +33,29 @@ void GPURaycaster::raycast(const TSDFVolume &volume, const Camera &camera, Eigen
           "process_ray failed ");
 }
 
+void GPURaycaster::raycast_gradient_normals(const TSDFVolume &volume, const Camera &camera,
+                                            Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
+                                            Eigen::Matrix<float, 3, Eigen::Dynamic> &normals) const {
+    const size_t n = (size_t)m_width * m_height, bytes = n * 3 * sizeof(float);
+    vertices.resize(3, n);
+    normals.resize(3, n);
+    if (n == 0) return;
+    const Eigen::Matrix3f kinv = camera.kinv();
+    // the entry point works on device buffers: both maps in one allocation, cast + gradients on the volume's stream, then back
+    void *d_maps = nullptr, *stream = nullptr;
+    check(tsdf_volume_stream(volume.handle(), &stream), "process_ray failed ");
+    check(tsdf_device_alloc(2 * bytes, &d_maps), "Vertices alloc failed");
+    float *d_vertices = static_cast<float *>(d_maps), *d_normals = d_vertices + 3 * n;
+    int rc = tsdf_raycast_gradient_normals_device(volume.handle(), m_width, m_height, camera.pose().data(), kinv.data(), d_vertices,
+                                                  d_normals);
+    const int rs = tsdf_stream_synchronize(stream);   // (before the buffer goes, whatever happened)
+    if (rc == TSDF_OK) rc = rs;
+    if (rc == TSDF_OK) rc = tsdf_device_download(vertices.data(), d_vertices, bytes);
+    if (rc == TSDF_OK) rc = tsdf_device_download(normals.data(), d_normals, bytes);
+    (void)tsdf_device_free(d_maps);
+    check(rc, "process_ray failed ");
+}
+
 // reference: src/RayCaster/GPURaycaster.cu:555-606 (without its debug PNG dump to a hard-coded path)
 DepthImage *GPURaycaster::render_to_depth_image(const TSDFVolume &volume, const Camera &camera) const {
     if (tsdf_host::verbose()) std::cout << "Rendering depth map" << std::endl;

@@ -217,3 +217,15 @@ void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, st
     if (d_rgb) (void)tsdf_device_free(d_rgb);
     tsdf_host::check(rc, "Couldn't colour the surface");
 }
+
+void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                     std::vector<float3> &normals) {
+    extract_surface(volume, vertices, triangles);
+    volume->sample_field(vertices, nullptr, &normals, nullptr, true);
+}
+
+void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                     std::vector<float3> &normals, std::vector<uchar3> &colours) {
+    extract_surface(volume, vertices, triangles, colours);
+    volume->sample_field(vertices, nullptr, &normals, nullptr, true);
+}

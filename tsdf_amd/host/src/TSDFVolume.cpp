@@ -148,6 +148,24 @@ void TSDFVolume::deintegrate(const uint16_t *depth_map, uint32_t width, uint32_t
           "De-integrate kernel failed");
 }
 
+void TSDFVolume::sample_field(const std::vector<float3> &points, std::vector<float> *distances, std::vector<float3> *gradients,
+                              std::vector<float> *weights, bool unit_gradient) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    if (!distances && !gradients && !weights) throw std::invalid_argument("sample_field: no output asked for");
+    const size_t n = points.size();
+    // (one element more than needed: data() of an empty vector may be null, which the C ABI reads as "not asked for")
+    if (distances) distances->assign(n + 1, 0.0f);
+    if (gradients) gradients->assign(n + 1, float3{0.0f, 0.0f, 0.0f});
+    if (weights) weights->assign(n + 1, 0.0f);
+    check(tsdf_volume_sample_field(m_handle, n, reinterpret_cast<const float *>(points.data()), distances ? distances->data() : nullptr,
+                                   gradients ? reinterpret_cast<float *>(gradients->data()) : nullptr,
+                                   weights ? weights->data() : nullptr, unit_gradient ? TSDF_FIELD_UNIT_GRADIENT : 0),
+          "Couldn't sample the field");
+    if (distances) distances->resize(n);
+    if (gradients) gradients->resize(n);
+    if (weights) weights->resize(n);
+}
+
 void TSDFVolume::weight_cap(uint32_t cap) { check(tsdf_volume_set_weight_cap(m_handle, cap), "Couldn't set the weight cap"); }
 
 uint32_t TSDFVolume::weight_cap() const {

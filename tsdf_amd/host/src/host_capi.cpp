@@ -187,6 +187,37 @@ int tsdf_host_write_ply_coloured(const char *file_name, const float *vertices, s
     return 0;
 }
 
+// write_to_ply with a normal per vertex (3 floats a vertex) and, when `colours` is not null, a colour per vertex; 0 = written, -1 = a
+// null array or an exception
+static int write_ply_normals(const char *file_name, const float *vertices, size_t n_vertices, const int *triangles, size_t n_triangles,
+                             const float *normals, const uint8_t *colours, bool coloured) {
+    if ((n_vertices && (!vertices || !normals || (coloured && !colours))) || (n_triangles && !triangles)) return -1;
+    try {
+        std::vector<float3> v(n_vertices), n(n_vertices);
+        std::vector<int3> t(n_triangles);
+        std::vector<uchar3> c(coloured ? n_vertices : 0);
+        for (size_t i = 0; i < n_vertices; i++) {
+            v[i] = float3{vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]};
+            n[i] = float3{normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+            if (coloured) c[i] = uchar3{colours[3 * i], colours[3 * i + 1], colours[3 * i + 2]};
+        }
+        for (size_t i = 0; i < n_triangles; i++) t[i] = int3{triangles[3 * i], triangles[3 * i + 1], triangles[3 * i + 2]};
+        if (coloured) write_to_ply(or_empty(file_name), v, t, n, c);
+        else write_to_ply(or_empty(file_name), v, t, n);
+    } catch (const std::exception &) {
+        return -1;
+    }
+    return 0;
+}
+int tsdf_host_write_ply_normals(const char *file_name, const float *vertices, size_t n_vertices, const int *triangles, size_t n_triangles,
+                                const float *normals) {
+    return write_ply_normals(file_name, vertices, n_vertices, triangles, n_triangles, normals, nullptr, false);
+}
+int tsdf_host_write_ply_normals_coloured(const char *file_name, const float *vertices, size_t n_vertices, const int *triangles,
+                                         size_t n_triangles, const float *normals, const uint8_t *colours) {
+    return write_ply_normals(file_name, vertices, n_vertices, triangles, n_triangles, normals, colours, true);
+}
+
 // read_nyu_depth_map (DepthMapUtilities.cpp): returns width * height (0: the file did not parse) and copies the samples when
 // `out` holds at least that many
 size_t tsdf_host_read_nyu_depth_map(const char *file_name, unsigned size[2], uint16_t *out, size_t capacity) {
