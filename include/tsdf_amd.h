@@ -377,6 +377,41 @@ int tsdf_volume_sample_field(const tsdf_volume *volume, uint64_t n, const float 
 int tsdf_raycast_gradient_normals_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
                                          const float kinv[9], float *device_vertices, float *device_normals);
 
+/* ---- volume fusion (no reference counterpart: the reference's volume is filled from depth frames only) ------------------------------ */
+/* Resamples the field of `src` onto the grid of `dst` through a rigid transform and blends it in: merging a second session's volume or
+ * a sub-map, re-posing a volume after a loop closure, moving a volume to a finer or coarser grid, re-centring the grid.  Opt-in by
+ * being called.  Grids, voxel sizes, offsets and truncation distances of the two volumes may all differ.
+ *   dst_to_src is column-major like a pose; only its top three rows are used.  fused_voxels may be NULL.
+ *   Every kernel goes on dst's stream after that stream has waited for src's.  With fused_voxels non-NULL the call synchronises and
+ *   stores the number of voxels it updated; otherwise it is asynchronous like tsdf_integrate_device.
+ * Everything below is separately rounded fp32 in exactly this order.  For every voxel (x, y, z) of dst:
+ *   1. centre: c.x = ((x + 0.5f) * voxel_size_dst.x) + offset_dst.x, likewise y and z -- dst's CURRENT offset, the frame of ray-cast and
+ *      mesh vertices, the one the field queries use;
+ *   2. transform: p.x = ((m[0] * c.x + m[4] * c.y) + m[8] * c.z) + m[12], likewise rows 1 and 2;
+ *   3. source point: q = p - offset_src; the voxel is skipped unless valid(q) in the sense of the field queries;
+ *   4. sample: s = S(q) of src, the ray cast's trilinear sample, bit for bit (see "field queries");
+ *   5. eight taps: the ones that sample reads -- the same lower-corner rule on the unclamped point, the same clamping of the +1 taps at
+ *      the far faces, so taps may coincide.  The voxel is skipped unless all eight tap weights are > 0: a tap that was never observed
+ *      holds the cleared distance and would otherwise bleed into the blend;
+ *   6. source weight: ws, the weight of the source voxel q lies in -- the one a field query reports, always one of the eight taps;
+ *   7. a NaN s skips the voxel; otherwise s = fminf(fmaxf(s, -trunc_dst), trunc_dst);
+ *   8. blend: d' = ((d * w) + (s * ws)) / (w + ws), w' = w + ws (IEEE division);
+ *   9. weight cap: with tsdf_volume_set_weight_cap on dst the stored weight is min(w + ws, cap), the divisor stays w + ws.
+ * Skipped voxels keep their distance and weight bit for bit.  src is never written and its weight storage is not converted.
+ *   Weight storage of dst: counts stay counts.  Before the launch dst is widened (8 -> 16 bits -> fp32) whenever its weight bound plus
+ *   the largest source weight could pass what its storage holds (the source's bound: its integration count in packed storage, a max
+ *   reduction over fp32 weights); a cap that fits the field needs no room.  If src holds fp32 weights that are not all non-negative
+ *   integers <= 65535, dst takes fp32 storage.  All nine combinations of {8, 16, 32}-bit storage on the two sides give the same bits.
+ *   The ray caster's summary of dst is handed over as tsdf_volume_mark_dirty does: the next cast rebuilds it from the distances.
+ *   Colour is out of scope: dst's colour array is left untouched.
+ * Refused (TSDF_ERR_INVALID, with a message, nothing written): null arguments; dst == src; volumes on different devices; a Z-slab on
+ * either side; a materialised deformation-node array on either side (voxel centres must be the implicit grid); a non-finite entry in
+ * the top three rows of the matrix. */
+int tsdf_volume_fuse(tsdf_volume *dst, const tsdf_volume *src, const float dst_to_src[16], uint64_t *fused_voxels);
+/* Diagnostics of the last tsdf_volume_fuse into dst: how many of its 64 x 4 x 32-voxel bricks the cull kept, and how many there are
+ * (both 0 before the first fuse).  Synchronises dst's stream. */
+int tsdf_volume_last_fuse_bricks(const tsdf_volume *dst, uint32_t *listed_bricks, uint32_t *total_bricks);
+
 /* ---- raycast ---------------------------------------------------------------------------- */
 /* Replaces GPURaycaster::raycast = get_vertices/process_ray + compute_normals
  * (src/RayCaster/GPURaycaster.cu:519-547, 432-486, 265-377, 393-427, 496-510).

@@ -373,6 +373,22 @@ class TSDFVolume:
         V = self.extract_surface()
         return V, self.sample_field(V, weight=False, unit_gradient=True)[1]
 
+    # ---- volume fusion (include/tsdf_amd.h, "volume fusion"; not in the reference's class)
+    def fuse(self, src, dst_to_src=None):
+        """Resample the field of `src` (another TSDFVolume) onto this volume's grid through the rigid transform dst_to_src (4 x 4,
+        column-major like a pose; default: identity) and blend it in, weights added.  -> the number of voxels updated.  Grids, voxel
+        sizes, offsets and truncation distances may differ; src is not changed.  Raises ValueError on the refusals."""
+        m = _mat(np.eye(4, dtype=np.float32) if dst_to_src is None else dst_to_src, 16)
+        n = C.c_uint64()
+        check(lib.tsdf_volume_fuse(self._h, src._h, _fp(m), C.byref(n)))
+        return int(n.value)
+
+    def last_fuse_bricks(self):
+        """(listed, total) 64 x 4 x 32-voxel bricks of the last fuse() into this volume: what its cull kept, and all of them."""
+        listed, total = C.c_uint32(), C.c_uint32()
+        check(lib.tsdf_volume_last_fuse_bricks(self._h, C.byref(listed), C.byref(total)))
+        return int(listed.value), int(total.value)
+
     def occupancy(self):
         """(occupied, total) bricks of the ray caster's empty-space summary."""
         o, t = C.c_uint64(), C.c_uint64()

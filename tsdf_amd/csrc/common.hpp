@@ -367,6 +367,10 @@ struct tsdf_volume {
     uint8_t *rgb_buf;
     size_t rgb_cap;
     int slab;                 // made by tsdf_volume_create_slab (colour is refused there)
+    // volume fusion (fuse.hip), as the destination: the fused-voxel counter, the list of destination bricks and the source's summary
+    void *fuse_scratch;
+    size_t fuse_scratch_cap;
+    uint32_t fuse_bricks_total;   // destination bricks of the last fuse (0: none yet)
     size_t resident_voxels() const { return (size_t)g.X * g.Y * (g.z_store_end - g.z_store_begin); }
 };
 

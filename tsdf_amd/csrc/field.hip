@@ -15,15 +15,9 @@
 // Nothing of the volume is written: no occupancy flag, no dirty mark, no counter.
 #include "common.hpp"
 #include "raycast_sample.hpp"
+#include "weight_view.hpp"
 
 namespace tsdf {
-
-// where the weights are, as the kernel needs it (weights.hip's three layouts)
-struct WeightView {
-    const float *f32;          // wmode 0
-    const uint32_t *packed;    // wmode 8 / 16
-    int mode;
-};
 
 // valid(q): finite, >= 0 and below the fp32 product the cast forms as max_x / y / z (false for NaN; -0.0 is valid)
 __device__ inline bool field_valid(float x, float y, float z, const TriConst &tc) {

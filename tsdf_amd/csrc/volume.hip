@@ -944,6 +944,7 @@ int tsdf_volume_destroy(tsdf_volume *v) {
     if (v->tile_max) (void)hipFree(v->tile_max);
     if (v->colour) (void)hipFree(v->colour);
     if (v->rgb_buf) (void)hipFree(v->rgb_buf);
+    if (v->fuse_scratch) (void)hipFree(v->fuse_scratch);
     delete v;
     return TSDF_OK;
 }

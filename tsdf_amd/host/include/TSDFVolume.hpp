@@ -120,6 +120,13 @@ public:
     void sample_field(const std::vector<float3> &points, std::vector<float> *distances, std::vector<float3> *gradients,
                       std::vector<float> *weights, bool unit_gradient = false) const;
 
+    // Volume fusion (include/tsdf_amd.h, "volume fusion"; not in the reference's class): resamples the field of `src` onto this volume's
+    // grid through the rigid transform dst_to_src (this volume's world frame -> src's) and blends it in, weights added; returns the
+    // number of voxels updated.  Grids, voxel sizes, offsets and truncation distances may differ; src is not changed.  Throws
+    // std::invalid_argument on the refusals (src == this, a Z-slab or materialised deformation nodes on either side, a non-finite
+    // matrix entry).
+    uint64_t fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_src);
+
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);
 

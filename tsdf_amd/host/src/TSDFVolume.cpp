@@ -166,6 +166,12 @@ void TSDFVolume::sample_field(const std::vector<float3> &points, std::vector<flo
     if (weights) weights->resize(n);
 }
 
+uint64_t TSDFVolume::fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_src) {
+    uint64_t fused = 0;
+    check(tsdf_volume_fuse(m_handle, src.m_handle, dst_to_src.data(), &fused), "Fuse kernel failed");
+    return fused;
+}
+
 void TSDFVolume::weight_cap(uint32_t cap) { check(tsdf_volume_set_weight_cap(m_handle, cap), "Couldn't set the weight cap"); }
 
 uint32_t TSDFVolume::weight_cap() const {
