@@ -342,6 +342,11 @@ float orc_trilinear(const float point[3], const uint32_t dims[3], const float vs
     return trilinear_core(point, dims, vs, dist, 0, NULL, 0, 0, 0, NULL);
 }
 
+/* orc_trilinear of n points (xyz interleaved), one call each in order: for references that sample a whole grid (tests/fuse_ref.py) */
+void orc_trilinear_n(size_t n, const float *points, const uint32_t dims[3], const float vs[3], const float *dist, float *out) {
+    for (size_t i = 0; i < n; i++) out[i] = orc_trilinear(points + 3 * i, dims, vs, dist);
+}
+
 /*
  * One ray.  ref: src/RayCaster/GPURaycaster.cu:265-377.
  * slab == 0: full semantics, writes vertex (NaN triple on miss), returns #samples.

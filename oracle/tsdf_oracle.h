@@ -114,6 +114,7 @@ void orc_normals(uint32_t width, uint32_t height, const float *vertices, float *
 int orc_ray_box(const float origin[3], const float dir[3], const float space_min[3],
                 const float space_max[3], float *near_t, float *far_t);
 float orc_trilinear(const float point[3], const uint32_t dims[3], const float vs[3], const float *dist);
+void orc_trilinear_n(size_t n, const float *points, const uint32_t dims[3], const float vs[3], const float *dist, float *out);
 void orc_ray_direction(uint16_t px, uint16_t py, const float rot[9], const float kinv[9], float dir[3]);
 void orc_world_to_pixel(const float p[3], const float inv_pose[16], const float k[9], int pix[2]);
 void orc_world_to_camera(const float p[3], const float inv_pose[16], float out[3]);

@@ -20,9 +20,11 @@ def rotation(axis, degrees, translation=(0.0, 0.0, 0.0)):
     return M.T.astype(F).reshape(-1).copy()   # (the transpose of the rows, flattened: column-major)
 
 
-def fuse(O, dst_geom, dst_trunc, dist, weight, src_geom, src_dist, src_weight, m=None, cap=0):
+def fuse(O, dst_geom, dst_trunc, dist, weight, src_geom, src_dist, src_weight, m=None, cap=0, detail=None):
     """-> (distances, weights, updated) of dst after the fuse: float32 copies of the whole grid (x fastest) and a bool mask.
-    dst_geom / src_geom = (dims, vs, offset) as geometry() gives them; m: 16 floats, column-major dst -> src (None: identity)."""
+    dst_geom / src_geom = (dims, vs, offset) as geometry() gives them; m: 16 floats, column-major dst -> src (None: identity).
+    detail: a dict that receives what the tests' preconditions count -- "q" (the three float32 arrays of step 3), "tapped" (the mask
+    after step 5) and "sample" (S at those voxels before step 7, NaN elsewhere)."""
     (X, Y, Z), dvs, doff = dst_geom
     sdims, svs, soff = src_geom
     dvs, doff, svs, soff = (np.asarray(a, F) for a in (dvs, doff, svs, soff))
@@ -65,8 +67,9 @@ def fuse(O, dst_geom, dst_trunc, dist, weight, src_geom, src_dist, src_weight, m
         ws = src_weight[at(v[0], v[1], v[2])]
         # 4. the sample, through the oracle, where it is needed
         s = np.full(X * Y * Z, np.nan, F)
-        for i in np.flatnonzero(ok):
-            s[i] = O.trilinear(np.array([q[0][i], q[1][i], q[2][i]], F), sdims, svs, src_dist)
+        s[ok] = O.trilinear_n(np.stack([a[ok] for a in q], axis=1), sdims, svs, src_dist)
+        if detail is not None:
+            detail.update(q=q, tapped=ok.copy(), sample=s.copy())
         # 7. NaN skips, then the clamp
         ok &= ~np.isnan(s)
         s = np.minimum(np.maximum(s, -trunc), trunc)
