@@ -412,6 +412,65 @@ int tsdf_volume_fuse(tsdf_volume *dst, const tsdf_volume *src, const float dst_t
  * (both 0 before the first fuse).  Synchronises dst's stream. */
 int tsdf_volume_last_fuse_bricks(const tsdf_volume *dst, uint32_t *listed_bricks, uint32_t *total_bricks);
 
+/* ---- field alignment (no reference counterpart: nothing in the reference produces a transform from the field itself) --------------- */
+/* The rigid pose that puts a point set on the zero level of the fused field: Gauss-Newton on sum S(T x)^2, which is point-to-plane ICP
+ * with the association replaced by a trilinear sample (the field is the model: distance 0 on the surface, the gradient its normal).
+ * No ray cast, no model maps, no projective association.  Opt-in by being called: a process that never calls these does what it did.
+ *   Pose: T is a column-major double[16] mapping the points' frame to the frame of the field queries -- the volume's CURRENT offset,
+ *     in volume units.  Only its top three rows are read; the bottom row comes back as (0, 0, 0, 1).
+ *   Pivot: the pose is kept about the centre of the volume's box, so that the rotation columns of the system are not inflated by the
+ *     distance to the world origin: h[a] = 0.5f * max[a] with max[a] the fp32 product size[a] * voxel_size[a], and
+ *     T_c = Tr(-(offset + h)) * T, formed in double on the host, which also converts back on the way out.
+ *   Per point x, every fp32 operation rounded on its own: R, t are T_c narrowed to fp32;
+ *         u[r] = ((R[r,0] * x0 + R[r,1] * x1) + R[r,2] * x2) + t[r]          (ICP's expression)
+ *         q = u + h per axis;  d = S(q), the sample of "field queries";
+ *         g = the raw central-difference gradient of "field queries" at q (six more samples at q -+ voxel_size e_a, each difference
+ *             divided by voxel_size[a] + voxel_size[a]).
+ *     The point is an inlier iff valid(q) and valid of all six shifted points ("field queries": NaN and infinite points fall out
+ *     here); the weight of the voxel q lies in is > 0 and so is the weight of the voxel each shifted point lies in (the field query's
+ *     weight, any storage: an unobserved neighbourhood holds the cleared distance, not a surface); d and all of g are finite;
+ *     fabsf(d) < gate; (gx * gx + gy * gy) + gz * gz > 0.
+ *     Row: (gx, gy, gz, u1 * gz - u2 * gy, u2 * gx - u0 * gz, u0 * gy - u1 * gx, -d).  An inlier adds the row's 28 upper-triangular
+ *     products (for o < 7, for i >= o: sum[s++] += row[o] * row[i]) and 1.0f to entry 28; entry 27 is the sum of d^2.
+ *   Order of the sums (part of the contract, as for ICP): B = min(256, ceil(n / 256)) workgroups of 256 threads; thread (b, t) takes
+ *     points i = 256 b + t, then i += 256 B, sequentially in fp32; then the wave64 shuffle-down tree (offsets 32 ... 1); then the four
+ *     waves as ((w0 + w1) + w2) + w3; the per-workgroup sums are then added as tsdf_icp_* adds them (8 groups of 32 workgroups in
+ *     double, narrowed to fp32), and the solve (6 x 6 LDL^T in double, zero pivots give zero components), the SE3 exponential and
+ *     T_c <- exp(x) * T_c are those of tsdf_icp_get_incremental_transformation.
+ *   Nothing of the volume is written; the calls read the distances and the weight storage on the aligner's stream, which the caller
+ *     orders behind the integrates it wants seen.
+ *   Refused (TSDF_ERR_INVALID, with a message, nothing written): null arguments; a Z-slab volume; a non-finite entry in T's top three
+ *     rows; gate not > 0; more than 8 stages; step == 0; volume and aligner on different devices.
+ *   Out of scope: robust weights, colour terms, slab volumes, the deformed space. */
+typedef struct tsdf_aligner tsdf_aligner;   /* opaque: partial sums, the double-buffered state, a pinned in/out block and a stream */
+int tsdf_aligner_create(tsdf_aligner **out);   /* on the current device */
+void tsdf_aligner_destroy(tsdf_aligner *aligner);
+int tsdf_aligner_set_stream(tsdf_aligner *aligner, void *hip_stream);
+int tsdf_aligner_stream(const tsdf_aligner *aligner, void **hip_stream);
+/* One step's sums at T without an update (the counterpart of tsdf_icp_estimate_step): the 6 x 6 normal matrix A, b, {sum of d^2,
+ * inliers}.  n points of 3 floats on the device.  device_rows (may be NULL): 7 n floats, the row of every point, the NaN row for an
+ * outlier.  n == 0 gives zeros and launches nothing.  Blocking. */
+int tsdf_aligner_step(tsdf_aligner *aligner, const tsdf_volume *volume, uint32_t n, const float *device_points, const double T[16],
+                      float gate, float A[36], float b[6], float residual_inliers[2], float *device_rows);
+typedef struct tsdf_align_stage {
+    const float *device_points;   /* n points of 3 floats */
+    uint32_t n;
+    uint32_t iterations;
+} tsdf_align_stage;
+/* Up to 8 stages queued back to back as one chain on the aligner's stream: each launch finishes the step before it, one finishing
+ * launch and one synchronise come at the end; the pose travels through pinned memory.  A stage with n == 0 or iterations == 0 is
+ * skipped.  A step with 0 inliers leaves the pose as it is; residual / inliers (either may be NULL) are the sum of d^2 and the inlier
+ * count of the last step, so inliers == 0 says the chain ended blind: the caller judges.  A chain that never moved the pose returns T
+ * as given, bit for bit. */
+int tsdf_aligner_run(tsdf_aligner *aligner, const tsdf_volume *volume, uint32_t n_stages, const tsdf_align_stage *stages, float gate,
+                     double T[16] /* in: start, out */, float *residual, float *inliers);
+/* Pixel (x * step, y * step) of a uint16 depth image (millimetres) -> the camera-frame point (kinv * (px, py, 1)) * (depth / z of
+ * that product), kinv column-major 3 x 3, each row summed as (k1 * px + k2 * py) + k3; the NaN triple for depth 0 or depth >
+ * depth_cutoff (millimetres; INFINITY: none).  ceil(width / step) x ceil(height / step) interleaved points, row-major.  Asynchronous
+ * on hip_stream. */
+int tsdf_depth_to_points_device(uint32_t width, uint32_t height, const uint16_t *device_depth, const float kinv[9], uint32_t step,
+                                float depth_cutoff, float *device_points, void *hip_stream);
+
 /* ---- raycast ---------------------------------------------------------------------------- */
 /* Replaces GPURaycaster::raycast = get_vertices/process_ray + compute_normals
  * (src/RayCaster/GPURaycaster.cu:519-547, 432-486, 265-377, 393-427, 496-510).
@@ -592,6 +651,16 @@ int tsdf_tracker_create(tsdf_volume *volume, const tsdf_bilateral *filter, tsdf_
 int tsdf_tracker_filter(tsdf_tracker *tracker, const uint16_t *device_depth);
 int tsdf_tracker_align(tsdf_tracker *tracker, const tsdf_camera_matrices *previous, double T_prev_curr[16] /* in: start, out */,
                        float *last_error, float *last_inliers);
+/* tsdf_tracker_align without the ray cast ("field alignment"): the filtered current frame becomes camera-frame points through
+ * tsdf_depth_to_points_device (kinv; the tracker's depth cutoff) at steps 4, 2 and 1, then tsdf_aligner_run with ICP's 4 / 5 / 10
+ * iterations, coarse to fine, on the tracker's main stream, the gate at the volume's truncation distance.  T_world_cam: camera ->
+ * world in volume units (what tsdf_camera_matrices::pose holds, as doubles), in: the prediction (e.g. the previous pose), out: the
+ * aligned pose; residual / inliers as tsdf_aligner_run.  Blocks for the result.  The aligner and the three point buffers are created
+ * on the first call: a tracker that never calls this allocates and launches nothing new.  tsdf_tracker_filter still runs ICP's
+ * initICP for the new frame whichever align follows (no existing behaviour changes; dropping it for field-only users is a later
+ * change). */
+int tsdf_tracker_align_field(tsdf_tracker *tracker, const float kinv[9], double T_world_cam[16] /* in: prediction, out */,
+                             float *residual, float *inliers);
 int tsdf_tracker_integrate(tsdf_tracker *tracker, const tsdf_camera_matrices *camera);
 /* tsdf_tracker_integrate plus the colour of device_rgb (as tsdf_pipeline_step_colour: the filtered frame, rgb valid until the
  * integrate has run on the tracker's stream; refused without colour enabled or with a NULL rgb frame). */

@@ -8,7 +8,10 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field]
+//   --field (with --track): every tracked frame is aligned to the volume's distance field (tsdf_tracker_align_field: the filtered frame's
+//           pixels as points, no model ray cast, no ICP) from the previous pose; refused without --track and with --ranks; the line
+//           gains "align": "field" and reports the last step's inliers and sum of squared distances in the ICP fields.
 //   --window N (with --track): tsdf_tracker_set_window(N) -- the volume holds the last N tracked frames, each integrate past the N-th takes
 //           the oldest back out (tsdf_deintegrate); 0 (the default) = off; refused without --track, with --weight-cap and with --ranks; the
 //           line gains "window": N.
@@ -118,7 +121,7 @@ int main(int argc, char **argv) {
     unsigned n = 512;
     float physical = 3000.0f;
     int K = 20, Wu = 5;
-    bool overlap = true, cull_ahead = true, track = false, validate_merge = false, colour = false;
+    bool overlap = true, cull_ahead = true, track = false, validate_merge = false, colour = false, field = false;
     unsigned planes = 0;
     long weight_cap = 0;
     long window = 0;
@@ -140,6 +143,7 @@ int main(int argc, char **argv) {
         else if (a == "--no-cull-ahead") cull_ahead = false;
         else if (a == "--dump") dump_dir = value();
         else if (a == "--track") track = true;
+        else if (a == "--field") field = true;
         else if (a == "--ranks") ranks = std::atoi(value());
         else if (a == "--share-gpu") share_gpu = true;
         else if (a == "--planes") planes = (unsigned)std::atoi(value());
@@ -148,7 +152,7 @@ int main(int argc, char **argv) {
         else if (a == "--weight-cap") weight_cap = std::atol(value());
         else if (a == "--window") window = std::atol(value());
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field]\n");
             return 2;
         }
     }
@@ -163,6 +167,10 @@ int main(int argc, char **argv) {
     }
     if (window < 0 || window > 65535 || (window && (!track || weight_cap || ranks > 1))) {
         std::fprintf(stderr, "kinfu_stream: --window is 0 (off) or 1 .. 65535 frames; it needs --track and goes with neither --weight-cap nor --ranks\n");
+        return 2;
+    }
+    if (field && (!track || ranks > 1)) {
+        std::fprintf(stderr, "kinfu_stream: --field needs --track and does not go with --ranks\n");
         return 2;
     }
     if (colour && ranks > 1) {
@@ -322,7 +330,16 @@ int main(int argc, char **argv) {
                 t0 = std::chrono::steady_clock::now();
             }
             ok(tsdf_tracker_filter(trk, depth_dev + i * n_pix), "filter");
-            if (i > 0) {
+            if (i > 0 && field) {
+                // the previous pose is the prediction; the aligned pose comes back in its place (camera -> world, millimetres)
+                const tsdf_camera_matrices prev = matrices_of(*camera);
+                double T[16];
+                for (int j = 0; j < 16; j++) T[j] = prev.pose[j];
+                ok(tsdf_tracker_align_field(trk, prev.kinv, T, &error, &inliers), "align to the field");
+                Eigen::Matrix4f next;
+                for (int j = 0; j < 16; j++) next.data()[j] = (float)T[j];
+                camera->set_pose(next);
+            } else if (i > 0) {
                 const tsdf_camera_matrices prev = matrices_of(*camera);
                 double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};     // column-major; current camera -> previous camera, metres
                 ok(tsdf_tracker_align(trk, &prev, T, &error, &inliers), "align");
@@ -353,6 +370,7 @@ int main(int argc, char **argv) {
                     inliers, error);
         if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
         if (window) std::printf(", \"window\": %ld", window);
+        if (field) std::printf(", \"align\": \"field\"");
         std::printf(colour ? ", \"colour\": true}\n" : "}\n");
         if (!dump_dir.empty()) {
             dump(dump_dir + "/poses.f32", tracked.data(), tracked.size() * sizeof(float));

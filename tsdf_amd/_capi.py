@@ -29,6 +29,11 @@ class VolumeInfo(C.Structure):
                 ("fast_division_verified", C.c_int32)]
 
 
+class AlignStage(C.Structure):
+    """struct tsdf_align_stage (include/tsdf_amd.h)."""
+    _fields_ = [("device_points", C.c_void_p), ("n", C.c_uint32), ("iterations", C.c_uint32)]
+
+
 class CameraMatrices(C.Structure):
     """struct tsdf_camera_matrices (include/tsdf_amd.h)."""
     _fields_ = [("pose", C.c_float * 16), ("inv_pose", C.c_float * 16), ("k", C.c_float * 9), ("kinv", C.c_float * 9)]
@@ -121,6 +126,13 @@ _SIGS = {
     "tsdf_raycast_gradient_normals_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_volume_fuse": (_i, [_vp, _vp, _fp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_last_fuse_bricks": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tsdf_aligner_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_aligner_destroy": (None, [_vp]),
+    "tsdf_aligner_set_stream": (_i, [_vp, _vp]),
+    "tsdf_aligner_stream": (_i, [_vp, C.POINTER(_vp)]),
+    "tsdf_aligner_step": (_i, [_vp, _vp, _u32, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "tsdf_aligner_run": (_i, [_vp, _vp, _u32, _vp, _f, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "tsdf_depth_to_points_device": (_i, [_u32, _u32, _vp, _vp, _u32, _f, _vp, _vp]),
     "tsdf_raycast": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_raycast_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_normals_device": (_i, [_u32, _u32, _vp, _vp, _vp]),
@@ -156,6 +168,7 @@ _SIGS = {
     "tsdf_tracker_create": (_i, [_vp, _vp, _vp, _u32, _u32, _f, _i, C.POINTER(_vp)]),
     "tsdf_tracker_filter": (_i, [_vp, _vp]),
     "tsdf_tracker_align": (_i, [_vp, C.POINTER(CameraMatrices), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "tsdf_tracker_align_field": (_i, [_vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tsdf_tracker_integrate": (_i, [_vp, C.POINTER(CameraMatrices)]),
     "tsdf_tracker_integrate_colour": (_i, [_vp, C.POINTER(CameraMatrices), _vp]),
     "tsdf_tracker_set_window": (_i, [_vp, _u32]),

@@ -373,6 +373,19 @@ class TSDFVolume:
         V = self.extract_surface()
         return V, self.sample_field(V, weight=False, unit_gradient=True)[1]
 
+    # ---- field alignment (include/tsdf_amd.h, "field alignment"; not in the reference's class)
+    def align_points(self, points, T0=None, iterations=10, gate=None):
+        """The rigid pose that puts (n, 3) float32 points on this volume's surface: `iterations` Gauss-Newton steps on the squared
+        field distance from T0 (4 x 4, points' frame -> the frame of mesh and ray-cast vertices; default identity), points further
+        than `gate` (default: the truncation distance) from the surface left out.  -> (T 4 x 4 float64, residual, inliers) of the
+        last step; inliers == 0 means the chain ended blind.  Raises ValueError on the refusals."""
+        return FieldAligner().run(self, [(points, int(iterations))], T0, gate)
+
+    def register(self, src, T0=None, iterations=10, gate=None):
+        """Volume-to-volume registration: align the mesh vertices of `src` (another TSDFVolume) to this volume's field from T0.
+        -> (T src -> this volume, residual, inliers); the inverse of T is the dst_to_src that fuse(src, ...) takes."""
+        return self.align_points(src.extract_surface(), T0, iterations, gate)
+
     # ---- volume fusion (include/tsdf_amd.h, "volume fusion"; not in the reference's class)
     def fuse(self, src, dst_to_src=None):
         """Resample the field of `src` (another TSDFVolume) onto this volume's grid through the rigid transform dst_to_src (4 x 4,
@@ -635,6 +648,126 @@ def marching_cubes_table():
     t = np.empty((256, 32), np.int8)
     _capi.host.tsdf_host_mc_table(t.ctypes.data)
     return t
+
+
+class _DeviceArray:
+    """A device copy of a host array for the length of a `with` block (tsdf_device_alloc / upload / free)."""
+
+    def __init__(self, host=None, nbytes=None):
+        self.host = host
+        self.nbytes = int(host.nbytes if host is not None else nbytes)
+        self.ptr = C.c_void_p()
+
+    def __enter__(self):
+        if self.nbytes:
+            check(lib.tsdf_device_alloc(self.nbytes, C.byref(self.ptr)))
+            if self.host is not None:
+                try:
+                    check(lib.tsdf_device_upload(self.ptr, self.host.ctypes.data, self.nbytes))
+                except Exception:
+                    lib.tsdf_device_free(self.ptr)
+                    raise
+        return self
+
+    def __exit__(self, *a):
+        if self.ptr.value:
+            lib.tsdf_device_free(self.ptr)
+            self.ptr = C.c_void_p()
+
+
+def _pose16(T):
+    """4 x 4 (normal indexing; None: identity) -> column-major float64[16]."""
+    T = np.eye(4) if T is None else np.asarray(T, np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("expected a 4 x 4 pose, got shape %s" % (T.shape,))
+    return np.ascontiguousarray(T.T.reshape(-1))
+
+
+class FieldAligner:
+    """tsdf_aligner (include/tsdf_amd.h, "field alignment"): Gauss-Newton alignment of point sets to a volume's field.  Every call
+    runs on the volume's stream."""
+
+    MAX_STAGES = 8
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        check(lib.tsdf_aligner_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:   # (lib is None during interpreter shutdown)
+            lib.tsdf_aligner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def _on(self, volume, gate):
+        s = volume.stream_ptr()
+        check(lib.tsdf_aligner_set_stream(self._h, C.c_void_p(int(s) if s else 0)))
+        return float(volume.truncation_distance() if gate is None else gate)
+
+    def step_device(self, volume, n, points_ptr, T=None, gate=None, rows_ptr=None):
+        """One step's sums at T over n device points: (A 6x6, b 6, residual, inliers), float32; rows_ptr: 7 n floats or None."""
+        gate = self._on(volume, gate)
+        Tc = _pose16(T)
+        A, b, ri = np.zeros(36, np.float32), np.zeros(6, np.float32), np.zeros(2, np.float32)
+        check(lib.tsdf_aligner_step(self._h, volume._h, int(n), C.c_void_p(int(points_ptr)) if points_ptr else None, Tc.ctypes.data, gate,
+                                    A.ctypes.data, b.ctypes.data, ri.ctypes.data, C.c_void_p(int(rows_ptr)) if rows_ptr else None))
+        return A.reshape(6, 6), b, float(ri[0]), float(ri[1])
+
+    def step(self, volume, points, T=None, gate=None, rows=False):
+        """(n, 3) float32 host points -> (A, b, residual, inliers) and, with rows=True, the (n, 7) rows (NaN rows for outliers)."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        out = np.empty((n, 7), np.float32)
+        with _DeviceArray(p) as dp, _DeviceArray(nbytes=out.nbytes if rows else 0) as dr:
+            res = self.step_device(volume, n, dp.ptr.value, T, gate, dr.ptr.value)
+            if rows and n:
+                check(lib.tsdf_device_download(out.ctypes.data, dr.ptr, out.nbytes))
+        return res + (out,) if rows else res
+
+    def run_device(self, volume, stages, T0=None, gate=None):
+        """stages: up to 8 (points_ptr, n, iterations) run as one chain -> (T 4x4 float64, residual, inliers) of the last step."""
+        gate = self._on(volume, gate)
+        st = (_capi.AlignStage * max(1, len(stages)))()
+        for i, (ptr, n, it) in enumerate(stages):
+            st[i].device_points, st[i].n, st[i].iterations = (int(ptr) if ptr else None), int(n), int(it)
+        Tc = _pose16(T0)
+        res, inl = C.c_float(), C.c_float()
+        check(lib.tsdf_aligner_run(self._h, volume._h, len(stages), st, gate, Tc.ctypes.data, C.byref(res), C.byref(inl)))
+        return Tc.reshape(4, 4).T.copy(), float(res.value), float(inl.value)
+
+    def run(self, volume, stages, T0=None, gate=None):
+        """stages: up to 8 ((n, 3) float32 host points, iterations)."""
+        import contextlib
+        hosts = [(np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3), int(it)) for p, it in stages]
+        with contextlib.ExitStack() as stack:
+            dev = [(stack.enter_context(_DeviceArray(p)).ptr.value, len(p), it) for p, it in hosts]
+            return self.run_device(volume, dev, T0, gate)
+
+
+def depth_to_points_device(width, height, depth_ptr, kinv, step, depth_cutoff, points_ptr, stream=0):
+    """tsdf_depth_to_points_device: every step-th pixel of a uint16 depth image (mm) -> ceil(width / step) * ceil(height / step)
+    camera-frame points on the device; asynchronous on `stream`."""
+    check(lib.tsdf_depth_to_points_device(int(width), int(height), C.c_void_p(int(depth_ptr)) if depth_ptr else None, _fp(_mat(kinv, 9)),
+                                          int(step), float(depth_cutoff), C.c_void_p(int(points_ptr)) if points_ptr else None,
+                                          C.c_void_p(int(stream) if stream else 0)))
+
+
+def depth_to_points(depth, width, height, kinv, step=1, depth_cutoff=float("inf")):
+    """Host uint16 depth image (mm) -> (ceil(height / step), ceil(width / step), 3) float32 camera-frame points of every step-th
+    pixel; the NaN triple for depth 0 or depth > depth_cutoff (mm)."""
+    d = np.ascontiguousarray(depth, dtype=np.uint16).reshape(-1)
+    width, height, step = int(width), int(height), int(step)
+    if d.size != width * height:
+        raise ValueError("depth has %d pixels, expected %d" % (d.size, width * height))
+    if step <= 0:
+        raise ValueError("depth_to_points: step is 0")
+    out = np.empty((-(-height // step), -(-width // step), 3), np.float32)
+    with _DeviceArray(d) as dd, _DeviceArray(nbytes=out.nbytes) as dp:
+        depth_to_points_device(width, height, dd.ptr.value, kinv, step, depth_cutoff, dp.ptr.value)
+        check(lib.tsdf_stream_synchronize(None))
+        check(lib.tsdf_device_download(out.ctypes.data, dp.ptr, out.nbytes))
+    return out
 
 
 class ICPOdometry:

@@ -1,0 +1,257 @@
+// The Gauss-Newton back end shared by icp.hip (frame-to-model ICP) and align.hip (field alignment): the second stage of the
+// 29-entry reduction, the 6 x 6 LDL^T solvers, the SE3 exponential and T <- exp(x) * T (icp_finish_step), with the constants of the
+// reduction's shape.  Moved here from icp.hip unchanged, so that both translation units finish a step with the very same expressions.
+#pragma once
+
+#include <cmath>
+
+#include "common.hpp"
+
+namespace tsdf {
+
+constexpr int kIcpBlocks = 256;   // one workgroup per CU (icp_finish_step adds them as 8 groups of 32)
+constexpr int kIcpThreads = 256;
+constexpr int kIcpStateDoubles = 64;
+
+// icp.hip: launches icp_finish_kernel (one workgroup: icp_finish_step of the sums in partial_prev, state_in -> state_out; `mirror`,
+// pinned host memory or null, also gets pose, residual and inliers) on `stream`
+void launch_gn_finish(hipStream_t stream, const double *state_in, double *state_out, const float *partial_prev, int n_blocks, int update,
+                      double *mirror);
+
+// x = A^-1 b, 6x6 symmetric positive (semi-)definite, LDL^T with diagonal pivoting in double -- the job of
+// `A_icp.cast<double>().ldlt().solve(b_icp.cast<double>())` (ICPOdometry.cpp:131).  Zero pivots give zero components.
+// One lane runs this, so latency is everything: all loops are fully unrolled and the pivot exchanges are predicated
+// swaps at compile-time indices, which keeps the matrices in registers instead of scratch memory.
+__device__ inline void swap_if(bool c, double &a, double &b) {
+    const double t = a;
+    a = c ? b : a;
+    b = c ? t : b;
+}
+// The same factorisation without pivoting: for the positive definite, reasonably conditioned normal matrix of a
+// healthy ICP step it needs no row exchanges; returns false (result unused) when a pivot is not safely positive, and the
+// pivoted version above/below takes over.  ~250 dependent flops instead of ~4000 predicated moves.
+__device__ inline bool ldlt_solve6_unpivoted(const float *A_in, const float *b_in, double *x) {
+    double A[6][6], L[6][6], D[6], Dinv[6], y[6];
+    double dmax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        y[i] = b_in[i];
+#pragma unroll
+        for (int j = 0; j < 6; j++) A[i][j] = A_in[i * 6 + j];
+        dmax = fmax(dmax, fabs(A[i][i]));
+    }
+    bool ok = dmax > 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        D[k] = A[k][k];
+        ok = ok && D[k] > 1.0e-9 * dmax;
+        const double inv = 1.0 / D[k];
+        Dinv[k] = inv;
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) L[i][k] = A[i][k] * inv;
+#pragma unroll
+        for (int i = k + 1; i < 6; i++)
+#pragma unroll
+            for (int j = k + 1; j <= i; j++) {
+                A[i][j] -= L[i][k] * D[k] * L[j][k];
+                A[j][i] = A[i][j];
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < i; j++) y[i] -= L[i][j] * y[j];
+#pragma unroll
+    for (int i = 0; i < 6; i++) y[i] = y[i] * Dinv[i];   // (the pivots' reciprocals again: six divisions fewer on the critical path)
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+#pragma unroll
+        for (int j = i + 1; j < 6; j++) y[i] -= L[j][i] * y[j];
+        x[i] = y[i];
+    }
+    return ok;
+}
+
+__device__ inline void ldlt_solve6(const float *A_in, const float *b_in, double *x) {
+    double A[6][6], L[6][6], D[6], y[6], z[6];
+    int perm[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        perm[i] = i;
+        y[i] = b_in[i];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            A[i][j] = A_in[i * 6 + j];
+            L[i][j] = 0.0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        // pivot: the largest remaining diagonal entry (first one on ties)
+        int p = k;
+        double best = fabs(A[k][k]);
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) {
+            const double v = fabs(A[i][i]);
+            if (v > best) {
+                best = v;
+                p = i;
+            }
+        }
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) {
+            const bool sw = (p == i);  // exchange rows / columns k and i of A, rows of L, the permutation, the rhs
+#pragma unroll
+            for (int j = 0; j < 6; j++) swap_if(sw, A[k][j], A[i][j]);
+#pragma unroll
+            for (int r = 0; r < 6; r++) swap_if(sw, A[r][k], A[r][i]);
+#pragma unroll
+            for (int j = 0; j < k; j++) swap_if(sw, L[k][j], L[i][j]);
+            const int tp = perm[k];
+            perm[k] = sw ? perm[i] : perm[k];
+            perm[i] = sw ? tp : perm[i];
+            swap_if(sw, y[k], y[i]);
+        }
+        D[k] = A[k][k];
+        L[k][k] = 1.0;
+        const bool nz = D[k] != 0.0;
+#pragma unroll
+        for (int i = k + 1; i < 6; i++) L[i][k] = nz ? A[i][k] / D[k] : 0.0;
+#pragma unroll
+        for (int i = k + 1; i < 6; i++)
+#pragma unroll
+            for (int j = k + 1; j < 6; j++) A[i][j] -= L[i][k] * D[k] * L[j][k];
+    }
+    // (y was permuted along with the rows: y = P b)
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < i; j++) y[i] -= L[i][j] * y[j];
+#pragma unroll
+    for (int i = 0; i < 6; i++) z[i] = (D[i] != 0.0) ? y[i] / D[i] : 0.0;
+#pragma unroll
+    for (int i = 5; i >= 0; i--)
+#pragma unroll
+        for (int j = i + 1; j < 6; j++) z[i] -= L[j][i] * z[j];
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++)
+            if (perm[i] == j) x[j] = z[i];
+}
+
+// Sophus::SE3d::exp(a) for a = (upsilon, omega): R = exp(hat(omega)), translation = V * upsilon; E column-major 4x4.
+__device__ inline void se3_exp(const double *a, double *E) {
+    const double wx = a[3], wy = a[4], wz = a[5];
+    const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
+    const double W[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
+    double W2[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            W2[i][j] = 0;
+            for (int k = 0; k < 3; k++) W2[i][j] += W[i][k] * W[k][j];
+        }
+    double A, B, C;  // sin th / th, (1 - cos th) / th^2, (th - sin th) / th^3
+    if (th2 < 0.0625) {
+        // |th| < 1/4 (every step of a converging ICP): the three entire functions by their power series in th^2, summed
+        // from the smallest term (Horner, constant reciprocals: a double division costs this lane ~25 dependent instructions);
+        // the first omitted terms are < 1e-19 relative.  One lane evaluates this on the
+        // critical path of every iteration, and the library's double sin / cos cost several microseconds there.
+        const double t = th2;
+        A = 1.0 - t * (1.0 / 6.0) * (1.0 - t * (1.0 / 20.0) * (1.0 - t * (1.0 / 42.0) * (1.0 - t * (1.0 / 72.0) * (1.0 - t * (1.0 / 110.0) * (1.0 - t * (1.0 / 156.0) * (1.0 - t * (1.0 / 210.0)))))));
+        B = 0.5 * (1.0 - t * (1.0 / 12.0) * (1.0 - t * (1.0 / 30.0) * (1.0 - t * (1.0 / 56.0) * (1.0 - t * (1.0 / 90.0) * (1.0 - t * (1.0 / 132.0) * (1.0 - t * (1.0 / 182.0) * (1.0 - t * (1.0 / 240.0))))))));
+        C = 1.0 / 6.0 * (1.0 - t * (1.0 / 20.0) * (1.0 - t * (1.0 / 42.0) * (1.0 - t * (1.0 / 72.0) * (1.0 - t * (1.0 / 110.0) * (1.0 - t * (1.0 / 156.0) * (1.0 - t * (1.0 / 210.0) * (1.0 - t * (1.0 / 272.0))))))));
+    } else {
+        A = sin(th) / th;
+        B = (1.0 - cos(th)) / th2;
+        C = (th - sin(th)) / (th2 * th);
+    }
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++) E[c * 4 + r] = (r == c) ? 1.0 : 0.0;
+    for (int i = 0; i < 3; i++) {
+        double ti = 0;
+        for (int j = 0; j < 3; j++) {
+            const double I = (i == j) ? 1.0 : 0.0;
+            E[j * 4 + i] = I + A * W[i][j] + B * W2[i][j];
+            ti += (I + B * W[i][j] + C * W2[i][j]) * a[j];
+        }
+        E[12 + i] = ti;
+    }
+}
+
+// Second stage of the reduction (reduceSum<29>, Cuda/estimate.cu:70-85) + the host part of estimateStep /
+// getIncrementalTransformation: A, b, residual, inliers; when `update` != 0 also x = A^-1 b and T <- exp(x) * T.
+// Run by all 256 threads of a workgroup; the pose after the step goes to pose_out (shared memory, for the caller's
+// __syncthreads), the whole state to state_out when that is not null.  The sums were written by the previous launch.
+__device__ __forceinline__ void icp_finish_step(const float *partial, int n_blocks, const double *state_in, int update, double *pose_out,
+                                       double *state_out) {
+    // 29 entries x 8 groups of blocks: thread (entry, group) adds its 32 blocks in order (loads issued together), then
+    // one thread per entry adds the 8 group sums in order -- a fixed tree, in double
+    __shared__ double group_sum[8][32];
+    __shared__ float total[32];
+    const int entry = threadIdx.x & 31, group = threadIdx.x >> 5;
+    // (the pose the sums were taken at: requested now, with the sums, not after them -- one memory round trip less on the
+    // path every iteration waits for)
+    double T[16];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) T[i] = state_in[i];
+    }
+    if (entry < 29) {
+        // (The loads are unconditional -- a block past n_blocks re-reads block 0 and its value is replaced by 0 afterwards: with the
+        // test in front of each load the compiler made 32 branches, each load waited for on its own: 32 dependent round trips, 8 of
+        // the 9.5 us this step took, profiles/r04zz_icp_finish_phases.txt.)
+        float v[32];
+#pragma unroll
+        for (int i = 0; i < 32; i++) {
+            const int b = group * 32 + i, bb = b < n_blocks ? b : 0;
+            v[i] = partial[bb * 32 + entry];
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 32; i++) s += (double)(group * 32 + i < n_blocks ? v[i] : 0.0f);
+        group_sum[group][entry] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 29) {
+        double s = 0.0;
+#pragma unroll
+        for (int g = 0; g < 8; g++) s += group_sum[g][threadIdx.x];
+        total[threadIdx.x] = (float)s;  // the reference hands fp32 sums to the host
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float A[36], b[6];
+    int shift = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 7; ++j) {
+            const float value = total[shift++];
+            if (j == 6) b[i] = value;
+            else A[j * 6 + i] = A[i * 6 + j] = value;
+        }
+    if (state_out) {
+        state_out[16] = total[27];
+        state_out[17] = total[28];
+        for (int i = 0; i < 36; i++) state_out[18 + i] = A[i];
+        for (int i = 0; i < 6; i++) state_out[54 + i] = b[i];
+    }
+    double out[16];
+    for (int i = 0; i < 16; i++) out[i] = T[i];
+    if (update) {
+        double x[6], E[16];
+        if (!ldlt_solve6_unpivoted(A, b, x)) ldlt_solve6(A, b, x);
+        se3_exp(x, E);
+        for (int c = 0; c < 4; c++)
+            for (int r = 0; r < 4; r++) {
+                double s = 0;
+                for (int k = 0; k < 4; k++) s += E[k * 4 + r] * T[c * 4 + k];
+                out[c * 4 + r] = s;
+            }
+    }
+    for (int i = 0; i < 16; i++) {
+        pose_out[i] = out[i];
+        if (state_out) state_out[i] = out[i];
+    }
+}
+
+}  // namespace tsdf

@@ -145,6 +145,9 @@ struct tsdf_tracker {
     uint32_t window, ring_count, ring_head;
     uint16_t *ring;             // window * width * height pixels
     tsdf_camera_matrices *ring_cam;
+    // tsdf_tracker_align_field: made on its first call (nullptr before)
+    tsdf_aligner *aligner;
+    float *align_points[3];     // the filtered frame as camera-frame points at steps 1, 2, 4
 };
 
 using namespace tsdf;
@@ -668,6 +671,9 @@ int tsdf_tracker_destroy(tsdf_tracker *t) {
     if (t->model) (void)hipFree(t->model);
     if (t->ring) (void)hipFree(t->ring);
     delete[] t->ring_cam;
+    if (t->aligner) tsdf_aligner_destroy(t->aligner);
+    for (int i = 0; i < 3; i++)
+        if (t->align_points[i]) (void)hipFree(t->align_points[i]);
     if (t->side) (void)hipStreamDestroy(t->side);
     if (t->main) (void)hipStreamDestroy(t->main);
     delete t;
@@ -785,6 +791,29 @@ int tsdf_tracker_align(tsdf_tracker *t, const tsdf_camera_matrices *previous, do
     rc = tsdf_icp_init_device(t->icp, 1, t->model, t->depth_cutoff);
     if (rc != TSDF_OK) return rc;
     return tsdf_icp_get_incremental_transformation(t->icp, T_prev_curr, last_error, last_inliers);
+}
+
+int tsdf_tracker_align_field(tsdf_tracker *t, const float kinv[9], double T_world_cam[16], float *residual, float *inliers) {
+    TSDF_REQUIRE(t && kinv && T_world_cam, "tsdf_tracker_align_field: null argument");
+    TSDF_REQUIRE(t->have_frame && t->frames > 0, "tsdf_tracker_align_field: no frame filtered, or nothing integrated to align it to");
+    const uint32_t steps[3] = {1, 2, 4};
+    uint32_t count[3];
+    for (int i = 0; i < 3; i++) count[i] = ((t->width + steps[i] - 1) / steps[i]) * ((t->height + steps[i] - 1) / steps[i]);
+    if (!t->aligner) {
+        int rc = tsdf_aligner_create(&t->aligner);
+        if (rc != TSDF_OK) return rc;
+        (void)tsdf_aligner_set_stream(t->aligner, t->main);
+    }
+    for (int i = 0; i < 3; i++)
+        if (!t->align_points[i]) TSDF_HIP(hipMalloc((void **)&t->align_points[i], (size_t)count[i] * 3 * sizeof(float)), "tsdf_tracker_align_field: point buffers");
+    int rc = tracker_join(t);
+    if (rc != TSDF_OK) return rc;
+    for (int i = 2; i >= 0; i--) {
+        rc = tsdf_depth_to_points_device(t->width, t->height, t->filtered[t->cur], kinv, steps[i], t->depth_cutoff * 1000.0f, t->align_points[i], t->main);
+        if (rc != TSDF_OK) return rc;
+    }
+    const tsdf_align_stage stages[3] = {{t->align_points[2], count[2], 4}, {t->align_points[1], count[1], 5}, {t->align_points[0], count[0], 10}};   // ICP's 4 / 5 / 10, coarse to fine
+    return tsdf_aligner_run(t->aligner, t->volume, 3, stages, t->volume->g.trunc, T_world_cam, residual, inliers);
 }
 
 // tsdf_tracker_integrate (rgb == nullptr) and tsdf_tracker_integrate_colour

@@ -127,6 +127,14 @@ public:
     // matrix entry).
     uint64_t fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_src);
 
+    // Field alignment (include/tsdf_amd.h, "field alignment"; not in the reference's class): the rigid pose that puts `points` on this
+    // volume's surface -- `iterations` Gauss-Newton steps on the squared field distance from T0 (points' frame -> the frame of ray-cast
+    // and mesh vertices), points further than `gate` (<= 0: the truncation distance) from the surface left out.  residual / inliers
+    // (may be null): the sum of squared distances and the inlier count of the last step; 0 inliers means the chain ended blind.
+    // Throws std::invalid_argument on the refusals (a Z-slab, a non-finite entry in T0's top three rows).
+    Eigen::Matrix4d align_points(const std::vector<float3> &points, const Eigen::Matrix4d &T0, uint32_t iterations = 10, float gate = 0.0f,
+                                 float *residual = nullptr, float *inliers = nullptr) const;
+
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);
 

@@ -166,6 +166,37 @@ void TSDFVolume::sample_field(const std::vector<float3> &points, std::vector<flo
     if (weights) weights->resize(n);
 }
 
+Eigen::Matrix4d TSDFVolume::align_points(const std::vector<float3> &points, const Eigen::Matrix4d &T0, uint32_t iterations, float gate,
+                                         float *residual, float *inliers) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    if (points.size() > 0xFFFFFFFFull) throw std::invalid_argument("align_points: too many points");
+    tsdf_volume_info info;
+    check(tsdf_volume_get_info(m_handle, &info), "Couldn't read the volume's geometry");
+    // one object owns the aligner and the device copy of the points, whatever is thrown
+    struct Scratch {
+        tsdf_aligner *aligner = nullptr;
+        void *points = nullptr;
+        ~Scratch() {
+            if (aligner) tsdf_aligner_destroy(aligner);
+            if (points) tsdf_device_free(points);
+        }
+    } s;
+    check(tsdf_aligner_create(&s.aligner), "Couldn't create the aligner");
+    void *stream = nullptr;
+    check(tsdf_volume_stream(m_handle, &stream), "Couldn't read the volume's stream");
+    check(tsdf_aligner_set_stream(s.aligner, stream), "Couldn't set the aligner's stream");
+    const size_t bytes = points.size() * sizeof(float3);
+    if (bytes) {
+        check(tsdf_device_alloc(bytes, &s.points), "Couldn't allocate the points");
+        check(tsdf_device_upload(s.points, points.data(), bytes), "Couldn't upload the points");
+    }
+    Eigen::Matrix4d T = T0;
+    const tsdf_align_stage stage = {static_cast<const float *>(s.points), (uint32_t)points.size(), iterations};
+    check(tsdf_aligner_run(s.aligner, m_handle, 1, &stage, gate <= 0.0f ? info.truncation_distance : gate, T.data(), residual, inliers),
+          "Align kernels failed");
+    return T;
+}
+
 uint64_t TSDFVolume::fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_src) {
     uint64_t fused = 0;
     check(tsdf_volume_fuse(m_handle, src.m_handle, dst_to_src.data(), &fused), "Fuse kernel failed");

@@ -10,6 +10,10 @@ ICPOdometry) -- the library composes them per frame, device resident (tsdf_amd/c
     pose[i]   = pose[i-1] * T                                      (translation back to millimetres; here, with the Camera class)
     volume.integrate(filtered, pose[i])
 
+With method="field" the model image, its maps and ICP are replaced by field alignment (include/tsdf_amd.h, "field alignment"): the
+filtered frame's pixels become camera-frame points and the pose is refined directly against the volume's distance field from the
+previous pose (tsdf_tracker_align_field); no ray cast.
+
 This class is the ctypes mirror of those entry points plus the pose composition; torch only wraps the tracker's streams.
 """
 import ctypes as C
@@ -22,8 +26,12 @@ from .pipeline import OVERLAP, _matrices
 
 
 class FrameToModelTracker:
-    def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True, window=0):
+    def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True, window=0,
+                 method="icp"):
         import torch
+        if method not in ("icp", "field"):
+            raise ValueError("method is 'icp' or 'field', got %r" % (method,))
+        self.method = method
         self.torch = torch
         self.volume = volume
         self.width, self.height = int(width), int(height)
@@ -82,6 +90,14 @@ class FrameToModelTracker:
         if self.frames == 0:
             if initial_pose is not None:
                 self.camera.set_pose_rows(np.asarray(initial_pose, np.float64))
+        elif self.method == "field":
+            Tc = np.ascontiguousarray(self.pose().T.reshape(-1))     # column-major double: the previous pose is the prediction
+            kinv = np.ascontiguousarray(self.camera.kinv(), np.float32).reshape(-1)
+            res, inl = C.c_float(), C.c_float()
+            check(lib.tsdf_tracker_align_field(self._h, kinv.ctypes.data, Tc.ctypes.data, C.byref(res), C.byref(inl)))
+            self.last_T = None
+            self.last_error, self.last_inliers = float(res.value), float(inl.value)   # sum of squared distances (mm^2), inliers
+            self.camera.set_pose_rows(Tc.reshape(4, 4).T.copy())
         else:
             prev = _matrices(self.camera)
             Tc = np.ascontiguousarray(np.eye(4).T.reshape(-1))      # column-major double, identity start
