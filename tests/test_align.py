@@ -11,6 +11,7 @@ import pytest
 import tsdf_amd
 from tests import align_ref as R
 from tests import field_ref
+from tests.field_cases import DIV_EDGES, division_case, division_volume
 from tests.helpers import assert_same_floats
 from tsdf_amd import _capi
 
@@ -122,6 +123,30 @@ def test_rows_match_the_reference_bit_for_bit(scene):
         A, b, res, count, rows = s.aligner.step(s.gv, s.row_points, T, s.gate, rows=True)
         assert_same_floats(rows, ref, "rows")
         assert count == inl.sum()
+
+
+@pytest.mark.parametrize("edge, proved", zip(DIV_EDGES, (0, 1)))
+def test_both_instances_of_the_division_give_the_reference_rows(oracle, edge, proved):
+    """The scene above has one geometry, so one of the kernel's two division instances; tests/test_field_query.py's two uploaded
+    volumes pick one each.  Their query points, through a pose 0.4 voxels and 1.5 degrees off, gate one voxel."""
+    c = division_case(oracle, edge)
+    T = R.perturbation(0.4 * edge, 1.5, R.pivot(c.geom)[1], 21)
+    gate = 1.0 * edge           # (inside the truncation of 1.9 voxels: the gate decides, not the clamp)
+    ref, inl = R.rows_at(oracle, c.geom, c.dist, c.weight, c.points, R.to_pivot(T, c.geom), gate)
+    assert inl.sum() >= 50 and (~inl).sum() >= 50
+    # outliers that pass the seven validity tests and leave later: at the weights (inliers once every voxel counts as observed), and
+    # -- every weight > 0 -- at the gate (inliers once it is infinite)
+    Tc = R.to_pivot(T, c.geom)
+    _, seen = R.rows_at(oracle, c.geom, c.dist, c.weight, c.points, Tc, np.inf)
+    _, anywhere = R.rows_at(oracle, c.geom, c.dist, np.ones_like(c.weight), c.points, Tc, np.inf)
+    assert (anywhere & ~seen).sum() >= 50 and (seen & ~inl).sum() >= 50
+    vol = division_volume(c, proved)
+    aligner = tsdf_amd.FieldAligner()
+    A, b, res, count, rows = aligner.step(vol, c.points, T, gate, rows=True)
+    assert_same_floats(rows, ref, "rows")
+    assert count == inl.sum()
+    aligner.close()
+    vol.close()
 
 
 def test_every_weight_storage_gives_the_same_rows(scene, oracle):

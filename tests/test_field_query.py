@@ -11,14 +11,14 @@ import pytest
 
 import tsdf_amd
 from tests import field_ref
+from tests.field_cases import DIV_EDGES, N_RANDOM, SEED, build_points, division_case, division_volume
 from tests.helpers import H, W, Cam, assert_same_floats, sphere_tsdf
 from tsdf_amd import _capi, synth
 
 F = np.float32
 SIZE, PHYS, OFFSET = (37, 34, 45), (2900.0, 3100.0, 3300.0), (-150.0, 40.0, 275.0)
-SEED, FRAMES, PERIOD = 0x5EEDF1E1, (0, 9, 18), 40
+FRAMES, PERIOD = (0, 9, 18), 40
 CAST_W, CAST_H = 80, 60
-N_RANDOM, N_LATTICE, N_FACE = 1200, 240, 30
 GUARD = 0x7FC0BEEF
 
 
@@ -30,62 +30,6 @@ def cast_camera(O, cam):
     """The frame's pose with the default intrinsics scaled to an 80 x 60 image."""
     k, kinv = O.camera_k(591.1 / 8, 590.1 / 8, 331.0 / 8, 234.6 / 8)
     return Cam(cam.pose(), cam.inverse_pose(), k, kinv)
-
-
-def world_for(q, offset):
-    """A float32 p with p - offset == q exactly (fp32), or None: the nearest float to q + offset or one of its neighbours."""
-    q, offset = F(q), F(offset)
-    p = F(q + offset)
-    for c in (p, np.nextafter(p, F(np.inf)), np.nextafter(p, F(-np.inf))):
-        if F(c - offset) == q:
-            return c
-    return None
-
-
-def build_points(geom, mesh, hits):
-    """-> (points (n, 3) float32, {name: slice}).  geom = (dims, vs, offset) as field_ref.geometry gives it."""
-    dims, vs, offset = geom
-    rng = np.random.RandomState(SEED & 0x7FFFFFFF)
-    mx = np.array(field_ref.bounds(dims, vs), F)
-    parts = {}
-    # uniform in the box enlarged by 10 %: some are outside
-    parts["random"] = (offset + (rng.uniform(-0.05, 1.05, (N_RANDOM, 3)) * mx)).astype(F)
-    parts["mesh"] = np.asarray(mesh, F).reshape(-1, 3)
-    parts["hits"] = np.asarray(hits, F).reshape(-1, 3)
-    # voxel centres and exact cell faces: q[a] = k * vs[a] or (k + 0.5) * vs[a] in fp32, k = 0 .. size (size itself: the upper bound)
-    lattice = np.empty((N_LATTICE, 3), F)
-    for i in range(N_LATTICE):
-        for a in range(3):
-            k = F(rng.randint(0, dims[a] + 1)) + (F(0.5) if rng.randint(2) else F(0))
-            q = F(k * vs[a])
-            p = world_for(q, offset[a])
-            lattice[i, a] = p if p is not None else F(q + offset[a])
-    parts["lattice"] = lattice
-    # within one voxel of each of the six faces, well inside along the other two axes: a distance, no gradient
-    face = []
-    for a in range(3):
-        for far in (False, True):
-            q = (vs * F(1.5) + rng.uniform(0, 1, (N_FACE, 3)) * (mx - vs * F(3))).astype(F)
-            t = rng.uniform(0.02, 0.98, N_FACE).astype(F) * vs[a]
-            q[:, a] = (mx[a] - vs[a]) + t if far else t
-            face.append((q + offset).astype(F))
-    parts["faces"] = np.concatenate(face)
-    # the exact upper bound per axis (invalid), NaN, both infinities, -0.0 as a coordinate
-    inside = (offset + mx * F(0.5)).astype(F)
-    special = []
-    for a in range(3):
-        p = world_for(mx[a], offset[a])
-        for v in (p if p is not None else F(mx[a] + offset[a]), F(np.nan), F(np.inf), F(-np.inf), F(-0.0)):
-            s = inside.copy()
-            s[a] = v
-            special.append(s)
-    parts["special"] = np.array(special, F)
-    out, where, at = [], {}, 0
-    for name, p in parts.items():
-        out.append(p)
-        where[name] = slice(at, at + len(p))
-        at += len(p)
-    return np.concatenate(out).astype(F), where
 
 
 class Scene:
@@ -182,6 +126,23 @@ def test_distance_gradient_and_weight_match_the_reference_bit_for_bit(scene):
     # no points: empty arrays, nothing launched
     e = s.gv.sample_field(np.empty((0, 3), F))
     assert [len(a) for a in e] == [0, 0, 0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("edge, proved", zip(DIV_EDGES, (0, 1)))
+def test_both_instances_of_the_division_match_the_reference(oracle, edge, proved):
+    c = division_case(oracle, edge)
+    vol = division_volume(c, proved)
+    d, g, w = vol.sample_field(c.points)
+    assert_same_floats(d, c.ref_d, "distance")
+    assert_same_floats(g, c.ref_g, "gradient")
+    assert_same_floats(w, c.ref_w, "weight")
+    _, u, _ = vol.sample_field(c.points, weight=False, unit_gradient=True)
+    assert_same_floats(u, c.ref_u, "unit gradient")
+    # the instances of one output each
+    for i, (ref, name) in enumerate(((c.ref_d, "distance"), (c.ref_u, "unit gradient"), (c.ref_w, "weight"))):
+        assert_same_floats(device_query(vol, c.points, *(j == i for j in range(3)), unit=True)[i], ref, "%s alone" % name)
+    vol.close()
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@
 // association replaced by a trilinear sample: no ray cast, no model maps, no projective association.  No reference counterpart.
 //
 //   * One hot kernel, align_reduce_kernel: per point the pose product (ICP's expression), the field query of field.hip (the ray cast's
-//     trilinear(), the central-difference gradient: seven samples), seven weight reads through weight_view.hpp, the row
+//     trilinear(), the central-difference gradient: seven samples), seven weight reads at the same points (field_sample.hpp), the row
 //     (g, u x g, -d) and its 28 products + the inlier count, summed in icp_accumulate's order: per-thread fp32 over a strided share
 //     of the points, the wave64 shuffle tree, the four waves in a fixed order.  B = min(256, ceil(n / 256)) workgroups.
 //   * The chain is ICP's: every launch first finishes the step before it in every workgroup (icp_finish_step of gn_solve.hpp: second
@@ -18,8 +18,7 @@
 
 #include "common.hpp"
 #include "gn_solve.hpp"
-#include "raycast_sample.hpp"
-#include "weight_view.hpp"
+#include "field_sample.hpp"
 
 struct tsdf_aligner {
     int device;
@@ -35,67 +34,33 @@ namespace tsdf {
 
 constexpr int kAlignMaxStages = 8;
 
-// what of the volume the kernel reads, and the pivot
+// the aligner's own constants of a call
 struct AlignField {
-    const float *dist;
-    WeightView wv;
-    Geom g;
-    F3 h;          // 0.5f * TriConst's max per axis
+    F3 h;          // the pivot: 0.5f * TriConst's max per axis
     float gate;
 };
 
-// field.hip's valid(q)
-__device__ inline bool align_valid(float x, float y, float z, const TriConst &tc) {
-    return x >= 0.0f && x < tc.max_x && y >= 0.0f && y < tc.max_y && z >= 0.0f && z < tc.max_z;
-}
-
-// the weight of the voxel a valid point lies in (the field query's rule: 0 where the quotient reaches `size` itself)
-template <bool FASTDIV>
-__device__ inline float align_weight(float x, float y, float z, const AlignField &f, const TriConst &tc) {
-    const int vx = f2i_sat(floorf(div_by<FASTDIV>(x, tc.dx)));
-    const int vy = f2i_sat(floorf(div_by<FASTDIV>(y, tc.dy)));
-    const int vz = f2i_sat(floorf(div_by<FASTDIV>(z, tc.dz)));
-    if (!((uint32_t)vx < f.g.X && (uint32_t)vy < f.g.Y && (uint32_t)vz < f.g.Z)) return 0.0f;
-    return weight_at(f.wv, (size_t)f.g.X * f.g.Y, (size_t)f.g.X * (uint32_t)vy + (uint32_t)vx, (uint32_t)vz);
-}
-
-template <bool FASTDIV>
-__device__ inline float align_sample(float x, float y, float z, const AlignField &f, const TriConst &tc, const RayParams &rp) {
-    bool owned;
-    return trilinear<false, false, FASTDIV>(x, y, z, f.dist, f.g, tc, rp, owned, nullptr);
-}
-
 // The row of one point at the pose (R, t about the pivot); false for an outlier (row then undefined).
 template <bool FASTDIV>
-__device__ inline bool align_row(const float *R, const float *t, float x0, float x1, float x2, const AlignField &f, const RayParams &rp,
+__device__ inline bool align_row(const float *R, const float *t, float x0, float x1, float x2, const FieldView &f, const AlignField &a,
                                  float *row) {
-    const TriConst &tc = rp.tc;
     const float u0 = ((R[0] * x0 + R[3] * x1) + R[6] * x2) + t[0];
     const float u1 = ((R[1] * x0 + R[4] * x1) + R[7] * x2) + t[1];
     const float u2 = ((R[2] * x0 + R[5] * x1) + R[8] * x2) + t[2];
-    const float qx = u0 + f.h.x, qy = u1 + f.h.y, qz = u2 + f.h.z;
-    const float xp = qx + f.g.vs.x, xm = qx - f.g.vs.x;
-    const float yp = qy + f.g.vs.y, ym = qy - f.g.vs.y;
-    const float zp = qz + f.g.vs.z, zm = qz - f.g.vs.z;
-    if (!(align_valid(qx, qy, qz, tc) && align_valid(xp, qy, qz, tc) && align_valid(xm, qy, qz, tc) && align_valid(qx, yp, qz, tc) &&
-          align_valid(qx, ym, qz, tc) && align_valid(qx, qy, zp, tc) && align_valid(qx, qy, zm, tc)))
-        return false;
+    const FieldStencil s = field_stencil(f, u0 + a.h.x, u1 + a.h.y, u2 + a.h.z);
+    if (!field_stencil_valid(f, s)) return false;
     // an unobserved neighbourhood holds the cleared distance, not a surface
-    const float w0 = align_weight<FASTDIV>(qx, qy, qz, f, tc);
-    const float w1 = align_weight<FASTDIV>(xp, qy, qz, f, tc), w2 = align_weight<FASTDIV>(xm, qy, qz, f, tc);
-    const float w3 = align_weight<FASTDIV>(qx, yp, qz, f, tc), w4 = align_weight<FASTDIV>(qx, ym, qz, f, tc);
-    const float w5 = align_weight<FASTDIV>(qx, qy, zp, f, tc), w6 = align_weight<FASTDIV>(qx, qy, zm, f, tc);
+    const float w0 = field_weight<FASTDIV>(f, s.x, s.y, s.z);
+    const float w1 = field_weight<FASTDIV>(f, s.xp, s.y, s.z), w2 = field_weight<FASTDIV>(f, s.xm, s.y, s.z);
+    const float w3 = field_weight<FASTDIV>(f, s.x, s.yp, s.z), w4 = field_weight<FASTDIV>(f, s.x, s.ym, s.z);
+    const float w5 = field_weight<FASTDIV>(f, s.x, s.y, s.zp), w6 = field_weight<FASTDIV>(f, s.x, s.y, s.zm);
     if (!(w0 > 0.0f && w1 > 0.0f && w2 > 0.0f && w3 > 0.0f && w4 > 0.0f && w5 > 0.0f && w6 > 0.0f)) return false;
-    const float d = align_sample<FASTDIV>(qx, qy, qz, f, tc, rp);
-    const float sxp = align_sample<FASTDIV>(xp, qy, qz, f, tc, rp), sxm = align_sample<FASTDIV>(xm, qy, qz, f, tc, rp);
-    const float syp = align_sample<FASTDIV>(qx, yp, qz, f, tc, rp), sym = align_sample<FASTDIV>(qx, ym, qz, f, tc, rp);
-    const float szp = align_sample<FASTDIV>(qx, qy, zp, f, tc, rp), szm = align_sample<FASTDIV>(qx, qy, zm, f, tc, rp);
-    const float gx = (sxp - sxm) / (f.g.vs.x + f.g.vs.x);
-    const float gy = (syp - sym) / (f.g.vs.y + f.g.vs.y);
-    const float gz = (szp - szm) / (f.g.vs.z + f.g.vs.z);
+    const float d = field_distance<FASTDIV>(f, s.x, s.y, s.z);
+    float gx, gy, gz;
+    field_gradient<FASTDIV>(f, s, gx, gy, gz);
     const float inf = INFINITY;
     if (!(fabsf(d) < inf && fabsf(gx) < inf && fabsf(gy) < inf && fabsf(gz) < inf)) return false;   // (false for NaN)
-    if (!(fabsf(d) < f.gate)) return false;
+    if (!(fabsf(d) < a.gate)) return false;
     if (!((gx * gx + gy * gy) + gz * gz > 0.0f)) return false;
     row[0] = gx;
     row[1] = gy;
@@ -114,7 +79,7 @@ __device__ inline bool align_row(const float *R, const float *t, float x0, float
 template <bool FASTDIV, bool ROWS>
 __global__ __launch_bounds__(kIcpThreads) void align_reduce_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
                                                                   const float *__restrict__ partial_prev, int pending, int prev_blocks,
-                                                                  const AlignField f, const RayParams rp, const uint32_t n,
+                                                                  const FieldView f, const AlignField a, const uint32_t n,
                                                                   const float *__restrict__ points, float *__restrict__ rows,
                                                                   float *__restrict__ partial) {
     __shared__ double pose[16];
@@ -139,7 +104,7 @@ __global__ __launch_bounds__(kIcpThreads) void align_reduce_kernel(const double 
     const uint32_t stride = (uint32_t)kIcpThreads * gridDim.x;   // <= 65536
     for (uint64_t i = (uint64_t)blockIdx.x * kIcpThreads + threadIdx.x; i < n; i += stride) {
         float row[7];
-        const bool in = align_row<FASTDIV>(R, t, points[3 * i + 0], points[3 * i + 1], points[3 * i + 2], f, rp, row);
+        const bool in = align_row<FASTDIV>(R, t, points[3 * i + 0], points[3 * i + 1], points[3 * i + 2], f, a, row);
         if (ROWS) {
 #pragma unroll
             for (int k = 0; k < 7; k++) rows[7 * i + k] = in ? row[k] : NAN;
@@ -209,30 +174,26 @@ static int align_blocks(uint32_t n) {
 
 // everything a launch needs of the volume, formed once per call
 struct AlignSetup {
-    AlignField f;
-    RayParams rp;
+    FieldView f;
+    AlignField a;
     double pivot[3];   // offset + h: subtracted from the caller's translation on the way in, added on the way out
     int fast_div;
 };
 
 static int align_setup(const tsdf_aligner *a, const tsdf_volume *v, const double *T, float gate, const char *what, AlignSetup &s) {
     TSDF_REQUIRE(a && v && T, "%s: null argument", what);
-    TSDF_REQUIRE(!v->slab && v->g.z_store_begin == 0 && v->g.z_store_end == v->g.Z,
-                 "%s: not supported on a Z-slab volume (tsdf_volume_create_slab): the taps of a sample cross slab boundaries", what);
+    const int rc = field_refuse_slab(v, what);
+    if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(v->device == a->device, "%s: the volume (device %d) and the aligner (device %d) are on different devices", what, v->device, a->device);
     for (int c = 0; c < 4; c++)
         for (int r = 0; r < 3; r++) TSDF_REQUIRE(std::isfinite(T[c * 4 + r]), "%s: T has a non-finite entry in its top three rows", what);
     TSDF_REQUIRE(gate > 0.0f, "%s: the gate must be > 0", what);   // (false for NaN)
-    std::memset(&s, 0, sizeof(s));
-    s.rp.tc = make_tri_const(v->g);
-    s.f.dist = v->dist;
-    s.f.wv = {v->weight, v->wpacked, v->wmode};
-    s.f.g = v->g;
-    s.f.h = {0.5f * s.rp.tc.max_x, 0.5f * s.rp.tc.max_y, 0.5f * s.rp.tc.max_z};
-    s.f.gate = gate;
-    s.pivot[0] = (double)v->g.offset.x + (double)s.f.h.x;
-    s.pivot[1] = (double)v->g.offset.y + (double)s.f.h.y;
-    s.pivot[2] = (double)v->g.offset.z + (double)s.f.h.z;
+    s.f = make_field_view(v);
+    s.a.h = {0.5f * s.f.tc.max_x, 0.5f * s.f.tc.max_y, 0.5f * s.f.tc.max_z};
+    s.a.gate = gate;
+    s.pivot[0] = (double)v->g.offset.x + (double)s.a.h.x;
+    s.pivot[1] = (double)v->g.offset.y + (double)s.a.h.y;
+    s.pivot[2] = (double)v->g.offset.z + (double)s.a.h.z;
     s.fast_div = v->fast_div;
     return TSDF_OK;
 }
@@ -257,7 +218,7 @@ static void launch_align_step(tsdf_aligner *a, const AlignSetup &s, uint32_t n, 
     float *partial = a->partial + (size_t)out * kIcpBlocks * 32;
     const dim3 grid((unsigned)align_blocks(n)), block(kIcpThreads);
 #define TSDF_ALIGN_LAUNCH(FD, RW) \
-    hipLaunchKernelGGL((align_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, state_out, partial_prev, pending, prev_blocks, s.f, s.rp, n, points, rows, partial)
+    hipLaunchKernelGGL((align_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, state_out, partial_prev, pending, prev_blocks, s.f, s.a, n, points, rows, partial)
     if (rows) {
         if (s.fast_div) TSDF_ALIGN_LAUNCH(true, true);
         else TSDF_ALIGN_LAUNCH(false, true);

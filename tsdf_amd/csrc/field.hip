@@ -4,8 +4,9 @@
 //
 // One kernel, one thread per point, a template on the outputs asked for:
 //   - q = p - offset per axis (the ray cast's space_min: ray-cast and mesh vertices are in this frame);
-//   - every sample S(.) is the ray cast's own trilinear() (raycast_sample.hpp): the same voxel_for_point, lower-corner rule on the
-//     unclamped point, tap clamping at the far faces and eight-term sum, so a query agrees bit for bit with what the cast saw;
+//   - every sample S(.) is the ray cast's own trilinear() (through field_sample.hpp, where the rules of reading the field at a point
+//     are): the same voxel_for_point, lower-corner rule on the unclamped point, tap clamping at the far faces and eight-term sum, so a
+//     query agrees bit for bit with what the cast saw;
 //   - the gradient is six more full samples at q -+ voxel_size along each axis.  Each sample derives its own cell -- the cells of the
 //     seven samples are not assumed to be neighbours: at a cell face rounding decides -- so the 56 taps are 56 loads of which 32
 //     are distinct voxels; the repeats hit in the vector L1 / L2 (LABNOTES.md, "field queries").  An instance asked for the distance
@@ -14,72 +15,30 @@
 //     dword, or fp32) and never converts it.
 // Nothing of the volume is written: no occupancy flag, no dirty mark, no counter.
 #include "common.hpp"
-#include "raycast_sample.hpp"
-#include "weight_view.hpp"
+#include "field_sample.hpp"
 
 namespace tsdf {
 
-// valid(q): finite, >= 0 and below the fp32 product the cast forms as max_x / y / z (false for NaN; -0.0 is valid)
-__device__ inline bool field_valid(float x, float y, float z, const TriConst &tc) {
-    return x >= 0.0f && x < tc.max_x && y >= 0.0f && y < tc.max_y && z >= 0.0f && z < tc.max_z;
-}
-
-template <bool FASTDIV>
-__device__ inline float field_sample(float x, float y, float z, const float *__restrict__ dist, const Geom &g, const TriConst &tc,
-                                     const RayParams &rp) {
-    bool owned;
-    return trilinear<false, false, FASTDIV>(x, y, z, dist, g, tc, rp, owned, nullptr);
-}
-
-// rp: only its type is needed (trilinear reads it for slabs alone); it travels as a kernel argument so that no lane forms one
 template <bool DIST, bool GRAD, bool WEIGHT, bool FASTDIV>
-__global__ __launch_bounds__(256) void field_sample_kernel(const float *__restrict__ dist, const WeightView wv, const Geom g,
-                                                           const RayParams rp, const uint64_t n_points,
-                                                           const float *__restrict__ points, float *__restrict__ out_distance,
-                                                           float *__restrict__ out_gradient, float *__restrict__ out_weight,
-                                                           const int unit) {
+__global__ __launch_bounds__(256) void field_sample_kernel(const FieldView f, const uint64_t n_points, const float *__restrict__ points,
+                                                           float *__restrict__ out_distance, float *__restrict__ out_gradient,
+                                                           float *__restrict__ out_weight, const int unit) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n_points) return;
-    const TriConst &tc = rp.tc;
-    const float qx = points[3 * i + 0] - g.offset.x;
-    const float qy = points[3 * i + 1] - g.offset.y;
-    const float qz = points[3 * i + 2] - g.offset.z;
-    const bool valid = field_valid(qx, qy, qz, tc);
+    const float qx = points[3 * i + 0] - f.g.offset.x;
+    const float qy = points[3 * i + 1] - f.g.offset.y;
+    const float qz = points[3 * i + 2] - f.g.offset.z;
+    const bool valid = field_valid(f, qx, qy, qz);
 
-    if (DIST) out_distance[i] = valid ? field_sample<FASTDIV>(qx, qy, qz, dist, g, tc, rp) : NAN;
+    if (DIST) out_distance[i] = valid ? field_distance<FASTDIV>(f, qx, qy, qz) : NAN;
 
-    if (WEIGHT) {
-        float w = 0.0f;
-        if (valid) {
-            // the voxel the point lies in: trilinear's voxel_for_point of a valid point (same quotient, FASTDIV or not)
-            const int vx = f2i_sat(floorf(div_by<FASTDIV>(qx, tc.dx)));
-            const int vy = f2i_sat(floorf(div_by<FASTDIV>(qy, tc.dy)));
-            const int vz = f2i_sat(floorf(div_by<FASTDIV>(qz, tc.dz)));
-            // (a point within rounding of the upper bound can divide to `size` itself: no such voxel, weight 0)
-            if ((uint32_t)vx < g.X && (uint32_t)vy < g.Y && (uint32_t)vz < g.Z) {
-                const size_t xy = (size_t)g.X * g.Y, in_plane = (size_t)g.X * (uint32_t)vy + (uint32_t)vx;
-                const uint32_t z = (uint32_t)vz;
-                if (wv.mode == 0) w = wv.f32[xy * z + in_plane];
-                else if (wv.mode == 8) w = (float)((wv.packed[xy * (z >> 2) + in_plane] >> (8u * (z & 3u))) & 0xffu);
-                else w = (float)((wv.packed[xy * (z >> 1) + in_plane] >> (16u * (z & 1u))) & 0xffffu);
-            }
-        }
-        out_weight[i] = w;
-    }
+    if (WEIGHT) out_weight[i] = valid ? field_weight<FASTDIV>(f, qx, qy, qz) : 0.0f;
 
     if (GRAD) {
-        const float xp = qx + g.vs.x, xm = qx - g.vs.x;
-        const float yp = qy + g.vs.y, ym = qy - g.vs.y;
-        const float zp = qz + g.vs.z, zm = qz - g.vs.z;
+        const FieldStencil s = field_stencil(f, qx, qy, qz);
         float gx = NAN, gy = NAN, gz = NAN;
-        if (valid && field_valid(xp, qy, qz, tc) && field_valid(xm, qy, qz, tc) && field_valid(qx, yp, qz, tc) &&
-            field_valid(qx, ym, qz, tc) && field_valid(qx, qy, zp, tc) && field_valid(qx, qy, zm, tc)) {
-            const float sxp = field_sample<FASTDIV>(xp, qy, qz, dist, g, tc, rp), sxm = field_sample<FASTDIV>(xm, qy, qz, dist, g, tc, rp);
-            const float syp = field_sample<FASTDIV>(qx, yp, qz, dist, g, tc, rp), sym = field_sample<FASTDIV>(qx, ym, qz, dist, g, tc, rp);
-            const float szp = field_sample<FASTDIV>(qx, qy, zp, dist, g, tc, rp), szm = field_sample<FASTDIV>(qx, qy, zm, dist, g, tc, rp);
-            gx = (sxp - sxm) / (g.vs.x + g.vs.x);
-            gy = (syp - sym) / (g.vs.y + g.vs.y);
-            gz = (szp - szm) / (g.vs.z + g.vs.z);
+        if (field_stencil_valid(f, s)) {
+            field_gradient<FASTDIV>(f, s, gx, gy, gz);
             if (unit) {
                 const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
                 if (len > 0.0f) {   // (false for NaN)
@@ -98,38 +57,34 @@ __global__ __launch_bounds__(256) void field_sample_kernel(const float *__restri
 }
 
 template <bool DIST, bool GRAD, bool WEIGHT>
-static void launch_field_instance(const tsdf_volume *v, const WeightView &wv, const RayParams &rp, uint64_t n, const float *points,
-                                  float *d, float *grad, float *w, int unit, hipStream_t stream) {
+static void launch_field_instance(const tsdf_volume *v, uint64_t n, const float *points, float *d, float *grad, float *w, int unit,
+                                  hipStream_t stream) {
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const FieldView f = make_field_view(v);
     if (v->fast_div)
-        hipLaunchKernelGGL((field_sample_kernel<DIST, GRAD, WEIGHT, true>), grid, block, 0, stream, v->dist, wv, v->g, rp, n, points, d, grad, w, unit);
+        hipLaunchKernelGGL((field_sample_kernel<DIST, GRAD, WEIGHT, true>), grid, block, 0, stream, f, n, points, d, grad, w, unit);
     else
-        hipLaunchKernelGGL((field_sample_kernel<DIST, GRAD, WEIGHT, false>), grid, block, 0, stream, v->dist, wv, v->g, rp, n, points, d, grad, w, unit);
+        hipLaunchKernelGGL((field_sample_kernel<DIST, GRAD, WEIGHT, false>), grid, block, 0, stream, f, n, points, d, grad, w, unit);
 }
 
 static int field_check(const tsdf_volume *v, const char *what) {
     TSDF_REQUIRE(v, "%s: null volume", what);
-    TSDF_REQUIRE(!v->slab && v->g.z_store_begin == 0 && v->g.z_store_end == v->g.Z,
-                 "%s: not supported on a Z-slab volume (tsdf_volume_create_slab): the taps of a sample cross slab boundaries", what);
-    return TSDF_OK;
+    return field_refuse_slab(v, what);
 }
 
 // the launch; v has passed field_check, at least one output is asked for, n > 0
 static int sample_field(const tsdf_volume *v, uint64_t n, const float *points, float *d, float *grad, float *w, int flags,
                         hipStream_t stream) {
     TSDF_REQUIRE((n + 255) / 256 <= 0x7FFFFFFFull, "tsdf_volume_sample_field: too many points");
-    RayParams rp = {};
-    rp.tc = make_tri_const(v->g);
-    const WeightView wv = {v->weight, v->wpacked, v->wmode};
     const int unit = (flags & TSDF_FIELD_UNIT_GRADIENT) ? 1 : 0;
     switch ((d ? 1 : 0) | (grad ? 2 : 0) | (w ? 4 : 0)) {
-        case 1: launch_field_instance<true, false, false>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
-        case 2: launch_field_instance<false, true, false>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
-        case 3: launch_field_instance<true, true, false>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
-        case 4: launch_field_instance<false, false, true>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
-        case 5: launch_field_instance<true, false, true>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
-        case 6: launch_field_instance<false, true, true>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
-        default: launch_field_instance<true, true, true>(v, wv, rp, n, points, d, grad, w, unit, stream); break;
+        case 1: launch_field_instance<true, false, false>(v, n, points, d, grad, w, unit, stream); break;
+        case 2: launch_field_instance<false, true, false>(v, n, points, d, grad, w, unit, stream); break;
+        case 3: launch_field_instance<true, true, false>(v, n, points, d, grad, w, unit, stream); break;
+        case 4: launch_field_instance<false, false, true>(v, n, points, d, grad, w, unit, stream); break;
+        case 5: launch_field_instance<true, false, true>(v, n, points, d, grad, w, unit, stream); break;
+        case 6: launch_field_instance<false, true, true>(v, n, points, d, grad, w, unit, stream); break;
+        default: launch_field_instance<true, true, true>(v, n, points, d, grad, w, unit, stream); break;
     }
     TSDF_HIP(hipGetLastError(), "Field sample kernel failed");
     return TSDF_OK;

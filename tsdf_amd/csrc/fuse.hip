@@ -12,12 +12,11 @@
 //   - fuse_kernel: one workgroup per listed brick, a lane per (x, y) walking the brick's z planes one packed weight dword (four, two or
 //     one plane) at a time, so that counts are stored as whole dwords the way integrate stores them.  Per voxel: centre, transform,
 //     the source's voxel and its weight (most lanes of a shell leave here), the eight tap weights, the ray cast's own trilinear()
-//     (raycast_sample.hpp), clamp, blend.  The division is the IEEE one in all three storages: the kernel waits on its gathers, not
+//     (field_sample.hpp), clamp, blend.  The division is the IEEE one in all three storages: the kernel waits on its gathers, not
 //     on its arithmetic (LABNOTES.md, "volume fusion").
 // The destination's occupancy summary is handed over the way tsdf_volume_mark_dirty does it (occ_dirty + occ_scan_all).
 #include "common.hpp"
-#include "raycast_sample.hpp"
-#include "weight_view.hpp"
+#include "field_sample.hpp"
 
 namespace tsdf {
 
@@ -27,11 +26,6 @@ constexpr uint32_t kCullBoxLimit = 4096;      // summary bytes a destination bri
 struct FuseMat {
     float m[16];   // column-major dst -> src, rows 0-2 used
 };
-
-// field_valid of field.hip: finite, >= 0 and below the fp32 product the cast forms as max_x / y / z (false for NaN; -0.0 is valid)
-__device__ inline bool fuse_valid(float x, float y, float z, const TriConst &tc) {
-    return x >= 0.0f && x < tc.max_x && y >= 0.0f && y < tc.max_y && z >= 0.0f && z < tc.max_z;
-}
 
 // ---- source summary ------------------------------------------------------------------------------------------------------------
 // one thread per weight dword (packed: PER planes of one (x, y)) or per weight (fp32): a byte store where something is > 0.  Several
@@ -138,17 +132,14 @@ __global__ __launch_bounds__(256) void fuse_cull_kernel(const Geom dg, const Geo
 // ---- the main kernel ---------------------------------------------------------------------------------------------------------------
 // What the source says at q (valid): false = the voxel is skipped.  s: the sample, ws: the weight of the voxel q lies in.
 template <bool FASTDIV>
-__device__ inline bool fuse_source(float qx, float qy, float qz, const float *__restrict__ sdist, const WeightView &wv, const Geom &sg,
-                                   const RayParams &rp, float &s, float &ws) {
-    const TriConst &tc = rp.tc;
-    // trilinear's voxel_for_point of a valid point (no clamping applies to it)
-    const int vx = f2i_sat(floorf(div_by<FASTDIV>(qx, tc.dx)));
-    const int vy = f2i_sat(floorf(div_by<FASTDIV>(qy, tc.dy)));
-    const int vz = f2i_sat(floorf(div_by<FASTDIV>(qz, tc.dz)));
-    // (a point within rounding of the upper bound can divide to `size` itself: no such voxel, the sample is NaN)
-    if (!((uint32_t)vx < sg.X && (uint32_t)vy < sg.Y && (uint32_t)vz < sg.Z)) return false;
+__device__ inline bool fuse_source(float qx, float qy, float qz, const FieldView &src, float &s, float &ws) {
+    const WeightView &wv = src.wv;
+    const Geom &sg = src.g;
+    const TriConst &tc = src.tc;
+    int vx, vy, vz;
+    if (!field_voxel<FASTDIV>(src, qx, qy, qz, vx, vy, vz)) return false;   // (the sample would be NaN)
     const size_t xy = tc.plane;
-    ws = weight_at(wv, xy, (size_t)tc.row * (uint32_t)vy + (uint32_t)vx, (uint32_t)vz);
+    ws = field_voxel_weight(src, vx, vy, vz);
     if (!(ws > 0.0f)) return false;   // one of the eight taps: a shell's empty space leaves here
     // trilinear's lower corner and tap clamping, the same expressions
     const float ccx = (vx + 0.5f) * sg.vs.x + 0.0f;
@@ -164,17 +155,16 @@ __device__ inline bool fuse_source(float qx, float qy, float qz, const float *__
                      weight_at(wv, xy, r0 + hx, lz) > 0.0f && weight_at(wv, xy, r0 + hx, hz) > 0.0f &&
                      weight_at(wv, xy, r1 + hx, lz) > 0.0f && weight_at(wv, xy, r1 + hx, hz) > 0.0f;
     if (!all) return false;
-    bool owned;
-    s = trilinear<false, false, FASTDIV>(qx, qy, qz, sdist, sg, tc, rp, owned, nullptr);
+    s = field_distance<FASTDIV>(src, qx, qy, qz);
     return !(s != s);
 }
 
 // DW: bits per destination weight, 0 = fp32.  One workgroup per listed brick, 64 x 4 lanes, lane <-> (x, y); the walk along z goes one
-// weight dword at a time.  rp: the source's TriConst (trilinear reads the rest for slabs alone).
+// weight dword at a time.
 template <int DW, bool FASTDIV>
 __global__ __launch_bounds__(256) void fuse_kernel(float *__restrict__ ddist, void *__restrict__ dweight, const Geom dg,
-                                                   const float *__restrict__ sdist, const WeightView wv, const Geom sg, const RayParams rp,
-                                                   const FuseMat fm, const uint32_t cap, const uint32_t bricks_x, const uint32_t bricks_y,
+                                                   const FieldView src, const FuseMat fm, const uint32_t cap, const uint32_t bricks_x,
+                                                   const uint32_t bricks_y,
                                                    const uint32_t *__restrict__ list, const uint32_t *__restrict__ count,
                                                    unsigned long long *__restrict__ fused) {
     if (blockIdx.x >= *count) return;
@@ -203,10 +193,10 @@ __global__ __launch_bounds__(256) void fuse_kernel(float *__restrict__ ddist, vo
                 if (z >= z_end) break;
                 const float cz = ((z + 0.5f) * dg.vs.z) + dg.offset.z;
                 const float px = (rx + m[8] * cz) + m[12], py = (ry + m[9] * cz) + m[13], pz = (rz + m[10] * cz) + m[14];
-                const float qx = px - sg.offset.x, qy = py - sg.offset.y, qz = pz - sg.offset.z;
-                if (!fuse_valid(qx, qy, qz, rp.tc)) continue;
+                const float qx = px - src.g.offset.x, qy = py - src.g.offset.y, qz = pz - src.g.offset.z;
+                if (!field_valid(src, qx, qy, qz)) continue;
                 float s, ws;
-                if (!fuse_source<FASTDIV>(qx, qy, qz, sdist, wv, sg, rp, s, ws)) continue;
+                if (!fuse_source<FASTDIV>(qx, qy, qz, src, s, ws)) continue;
                 s = fminf(fmaxf(s, -dg.trunc), dg.trunc);
                 if (!loaded) {
                     word = *wp;
@@ -230,10 +220,11 @@ __global__ __launch_bounds__(256) void fuse_kernel(float *__restrict__ ddist, vo
     if (threadIdx.x == 0 && n_fused) atomicAdd(fused, (unsigned long long)n_fused);
 }
 
-static int fuse_check(const tsdf_volume *v, const char *which) {
-    TSDF_REQUIRE(!v->slab && v->g.z_store_begin == 0 && v->g.z_store_end == v->g.Z,
-                 "tsdf_volume_fuse: %s is a Z-slab volume (tsdf_volume_create_slab): the taps of a sample cross slab boundaries", which);
-    TSDF_REQUIRE(!v->nodes, "tsdf_volume_fuse: %s has a materialised deformation-node array: voxel centres must be the implicit grid", which);
+// what: "tsdf_volume_fuse: the destination" / "... the source"
+static int fuse_check(const tsdf_volume *v, const char *what) {
+    const int rc = field_refuse_slab(v, what);
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(!v->nodes, "%s has a materialised deformation-node array: voxel centres must be the implicit grid", what);
     return TSDF_OK;
 }
 
@@ -259,8 +250,8 @@ extern "C" int tsdf_volume_fuse(tsdf_volume *dst, const tsdf_volume *src, const 
     TSDF_REQUIRE(dst && src && dst_to_src, "tsdf_volume_fuse: null argument");
     TSDF_REQUIRE(dst != src, "tsdf_volume_fuse: a volume cannot be fused into itself");
     TSDF_REQUIRE(dst->device == src->device, "tsdf_volume_fuse: the volumes are on different devices (%d and %d)", dst->device, src->device);
-    int rc = fuse_check(dst, "the destination");
-    if (rc == TSDF_OK) rc = fuse_check(src, "the source");
+    int rc = fuse_check(dst, "tsdf_volume_fuse: the destination");
+    if (rc == TSDF_OK) rc = fuse_check(src, "tsdf_volume_fuse: the source");
     if (rc != TSDF_OK) return rc;
     FuseMat fm;
     std::memcpy(fm.m, dst_to_src, sizeof(fm.m));
@@ -324,25 +315,23 @@ extern "C" int tsdf_volume_fuse(tsdf_volume *dst, const tsdf_volume *src, const 
     }
     if (dst->wmode != mode_before) dst->prepared_valid = 0;   // (a brick list prepared ahead came with the old storage)
 
-    const WeightView wv = {src->weight, src->wpacked, src->wmode};
+    const FieldView sv = make_field_view(src);
     {
         const size_t per = src->wmode == 0 ? 1 : 32 / src->wmode;
         const size_t n = (size_t)src->g.X * src->g.Y * ((src->g.Z + per - 1) / per);
         const dim3 grid((unsigned)std::min<size_t>((n + 255) / 256, 8192));
-        if (src->wmode == 0) hipLaunchKernelGGL(fuse_summary_kernel<0>, grid, dim3(256), 0, dst->stream, wv, src->g.X, src->g.Y, src->g.Z, fb.sbx, fb.sby, summary);
-        else if (src->wmode == 8) hipLaunchKernelGGL(fuse_summary_kernel<8>, grid, dim3(256), 0, dst->stream, wv, src->g.X, src->g.Y, src->g.Z, fb.sbx, fb.sby, summary);
-        else hipLaunchKernelGGL(fuse_summary_kernel<16>, grid, dim3(256), 0, dst->stream, wv, src->g.X, src->g.Y, src->g.Z, fb.sbx, fb.sby, summary);
+        if (src->wmode == 0) hipLaunchKernelGGL(fuse_summary_kernel<0>, grid, dim3(256), 0, dst->stream, sv.wv, src->g.X, src->g.Y, src->g.Z, fb.sbx, fb.sby, summary);
+        else if (src->wmode == 8) hipLaunchKernelGGL(fuse_summary_kernel<8>, grid, dim3(256), 0, dst->stream, sv.wv, src->g.X, src->g.Y, src->g.Z, fb.sbx, fb.sby, summary);
+        else hipLaunchKernelGGL(fuse_summary_kernel<16>, grid, dim3(256), 0, dst->stream, sv.wv, src->g.X, src->g.Y, src->g.Z, fb.sbx, fb.sby, summary);
         TSDF_HIP(hipGetLastError(), "fuse: source summary");
     }
     hipLaunchKernelGGL(fuse_cull_kernel, dim3((unsigned)((n_bricks + 255) / 256)), dim3(256), 0, dst->stream, dst->g, src->g, fm, fb, summary, list, count);
     TSDF_HIP(hipGetLastError(), "fuse: cull");
 
-    RayParams rp = {};
-    rp.tc = make_tri_const(src->g);
     const dim3 grid((unsigned)n_bricks), block(kIntBrickX, kIntBrickY);
 #define LAUNCH(DW, FD)                                                                                                                  \
     hipLaunchKernelGGL((fuse_kernel<DW, FD>), grid, block, 0, dst->stream, dst->dist, DW == 0 ? (void *)dst->weight : (void *)dst->wpacked, dst->g, \
-                       src->dist, wv, src->g, rp, fm, dst->weight_cap, fb.nx, fb.ny, list, count, fused)
+                       sv, fm, dst->weight_cap, fb.nx, fb.ny, list, count, fused)
     if (dst->wmode == 0) {
         if (src->fast_div) LAUNCH(0, true); else LAUNCH(0, false);
     } else if (dst->wmode == 8) {

@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void cell_cast_prepare_kernel(const Geom g, co
                     const float fx = px / g.vs.x, fy = py / g.vs.y, fz = pz / g.vs.z;
                     if (fx >= 0.0f && fy >= 0.0f && fz >= 0.0f && fx <= (float)g.X && fy <= (float)g.Y && fz <= (float)g.Z) continue;   // on the grid: the cells' / the shell's
                     bool owned;
-                    const float tsdf = trilinear<SLAB, false, false>(px, py, pz, cc.dist, g, rp.tc, rp, owned, nullptr);
+                    const float tsdf = trilinear<SLAB, false, false>(px, py, pz, cc.dist, g, rp.tc, rp.own_lo, rp.own_hi, owned, nullptr);
                     if (tsdf <= 0) {
                         lower_best(word, k, tsdf);
                         break;
@@ -531,7 +531,7 @@ __device__ inline void cast_shell_bricks(const float *__restrict__ dist, const G
                             // in this slab of this brick's (grown) voxel box
                             if (!(f_[0] >= slo[0] && f_[0] <= shi[0] && f_[1] >= slo[1] && f_[1] <= shi[1] && f_[2] >= slo[2] && f_[2] <= shi[2])) continue;
                             bool owned;
-                            const float tsdf = trilinear<SLAB, false, FASTDIV>(ppx, ppy, ppz, dist, g, tc, rp, owned, nullptr);
+                            const float tsdf = trilinear<SLAB, false, FASTDIV>(ppx, ppy, ppz, dist, g, tc, rp.own_lo, rp.own_hi, owned, nullptr);
                             if (tsdf <= 0) {
                                 RAY_MIX(41);
                                 lower_best(&best[idx], k, tsdf);
@@ -824,7 +824,7 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
                     // within eps of a face of the cell: the reference's own choice of cell and taps
                     RAY_MIX(39);
                     bool owned;
-                    const float tsdf = trilinear<SLAB, false, FASTDIV>(ppx, ppy, ppz, dist, g, tc, rp, owned, nullptr);
+                    const float tsdf = trilinear<SLAB, false, FASTDIV>(ppx, ppy, ppz, dist, g, tc, rp.own_lo, rp.own_hi, owned, nullptr);
                     if (tsdf <= 0) {
                         lower_best(&best[idx], k, tsdf);
                         break;

@@ -165,7 +165,7 @@ __device__ inline float process_sample(float t, int k, const RayState &r, const 
     }
     RAY_MIX(7);
     bool owned;
-    const float tsdf = trilinear<SLAB, STATS, FASTDIV>(px, py, pz, dist, g, tc, rp, owned, touched);
+    const float tsdf = trilinear<SLAB, STATS, FASTDIV>(px, py, pz, dist, g, tc, rp.own_lo, rp.own_hi, owned, touched);
     if (STATS && owned) work.samples++;
     return tsdf;
 }
@@ -267,7 +267,7 @@ __device__ inline float process_sample_eager(float t, const RayState &r, const S
     }
     RAY_MIX(15); if (mix0) RAY_MIX(23);
     bool owned;
-    return trilinear<SLAB, false, FASTDIV>(px, py, pz, dist, g, tc, rp, owned, nullptr);
+    return trilinear<SLAB, false, FASTDIV>(px, py, pz, dist, g, tc, rp.own_lo, rp.own_hi, owned, nullptr);
 }
 
 // One lane per pixel, a wave is an 8x8 pixel tile of coherent rays, a workgroup a 16x16 tile.  Every pass of the loop
@@ -437,7 +437,7 @@ __device__ inline void march_bulk(const float *__restrict__ dist, const Geom &g,
             if (__ballot(shell) == 0ull) break;
             if (shell) {
                 bool owned;
-                const float tsdf = trilinear<SLAB, false, FASTDIV>(px, py, pz, dist, g, tc, rp, owned, nullptr);
+                const float tsdf = trilinear<SLAB, false, FASTDIV>(px, py, pz, dist, g, tc, rp.own_lo, rp.own_hi, owned, nullptr);
                 if (tsdf <= 0) {
                     if (SEG) lower_best(&tail.best[idx], k, tsdf);
                     else refine_hit(t, tsdf, previous_tsdf, step_size, ray, rp, ix, iy, iz);

@@ -1,6 +1,6 @@
-// The ray cast's trilinear sample and what it needs, shared by raycast.hip (the march, the cell-parallel cast) and field.hip (the
-// field queries): the loop-invariant constants, the division by a voxel edge, RayParams and trilinear() itself.  Moved here from
-// raycast.hip unchanged, so that both translation units sample with the very same expressions.
+// The ray cast's trilinear sample and what it needs: the loop-invariant constants, the division by a voxel edge, RayParams and
+// trilinear() itself.  Shared by raycast.hip (the march, the cell-parallel cast) and, through field_sample.hpp, by field.hip,
+// align.hip and fuse.hip, so that every translation unit samples with the very same expressions.
 #pragma once
 
 #include "common.hpp"
@@ -77,10 +77,10 @@ __device__ inline float div_by(float a, const InvDiv &d) {
 
 // trilinearly_interpolate (src/RayCaster/GPURaycaster.cu:53-124) with voxel_for_point, centre_of_voxel_at and
 // tsdf_value_at (src/TSDF/TSDF_utilities.cu:10-53) inlined.  For SLAB, samples whose lower tap plane is not
-// owned are not evaluated (owned=false, result NaN).
+// owned (outside [own_lo, own_hi), RayParams' words) are not evaluated (owned=false, result NaN); otherwise the two are not read.
 template <bool SLAB, bool STATS, bool FASTDIV>
 __device__ inline float trilinear(float px, float py, float pz, const float *__restrict__ dist, const Geom &g,
-                                  const TriConst &tc, const RayParams &rp, bool &owned,
+                                  const TriConst &tc, uint32_t own_lo, uint32_t own_hi, bool &owned,
                                   unsigned int *__restrict__ touched) {
     float ax = px, ay = py, az = pz;
     if (px >= tc.max_x) ax = tc.clamp_x;
@@ -113,7 +113,7 @@ __device__ inline float trilinear(float px, float py, float pz, const float *__r
     lz = max(lz, 0);
 
     if (SLAB) {
-        if (!((uint32_t)lz >= rp.own_lo && (uint32_t)lz < rp.own_hi)) {
+        if (!((uint32_t)lz >= own_lo && (uint32_t)lz < own_hi)) {
             owned = false;
             return NAN;
         }
