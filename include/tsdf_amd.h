@@ -147,6 +147,19 @@ int tsdf_volume_set_weight_storage(tsdf_volume *volume, int bits_per_weight);
  * mantissa of the dividend (both signs, three exponents) and every divisor in [b_begin, b_end), 1 <= b_begin < b_end <= 2^17 + 1, and
  * returns the number of differences (0).  About a second for all 65536 divisors the 16-bit counts can reach. */
 int tsdf_selftest_count_division(uint32_t b_begin, uint32_t b_end, unsigned long long *mismatches);
+/* Self-tests of the bilateral filter's accumulation chain (bilateral_chain.hpp: the staged 15 x 15 kernel runs a half column of taps as
+ * fp32 fmas where a test proves that this rounds like the reference's float/double expression, and in double elsewhere).  Both run on
+ * the host, with the very expressions the kernel compiles, and need no GPU.
+ * _taps: for n taps (weight w in {0} or [2^-120, 1], v4 = 4 * intensity < 2^18, running sum s in {0} or [2^-120, 2^40]) the new sum by
+ * the fp32 tap, by the reference's tap, and whether the test certifies the tap (as a run of one) to be equal.
+ * _image: the whole staged kernel on a host image (8 or 16 bits per pixel; sigmas that select it: radius 7, smallest weight >= 2^-120):
+ * the filtered image (may be NULL) and, over interior waves (16 x 4 pixels, every tap inside the image),
+ * counts = {half columns of waves, those where some lane failed the test (the wave falls back to double), half columns of lanes,
+ * those that failed}. */
+int tsdf_selftest_bilateral_chain_taps(size_t n, const float *w, const uint32_t *v4, const float *s, float *s_f32, float *s_f64,
+                                       uint8_t *certified);
+int tsdf_selftest_bilateral_chain_image(float sigma_colour, float sigma_space, const void *image, int bits_per_pixel, int width, int height,
+                                        void *filtered, unsigned long long counts[4]);
 int tsdf_volume_deformation(tsdf_volume *volume, tsdf_deformation_node **device_ptr);
 /* Replace set_distance_data/set_weight_data/set_deformation (src/TSDF/TSDFVolume.cu:731-757):
  * blocking H2D of every resident voxel. */

@@ -89,6 +89,8 @@ _SIGS = {
     "tsdf_volume_set_weight_cap": (_i, [_vp, C.c_uint32]),
     "tsdf_volume_weight_cap": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "tsdf_selftest_count_division": (_i, [_u32, _u32, C.POINTER(C.c_uint64)]),
+    "tsdf_selftest_bilateral_chain_taps": (_i, [C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsdf_selftest_bilateral_chain_image": (_i, [_f, _f, _vp, _i, _i, _i, _vp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_deformation": (_i, [_vp, C.POINTER(_vp)]),
     "tsdf_volume_set_distance_data": (_i, [_vp, _vp]),
     "tsdf_volume_set_weight_data": (_i, [_vp, _vp]),

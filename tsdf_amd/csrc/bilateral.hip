@@ -15,12 +15,14 @@
 // writes one byte per pixel into a 2-byte-per-pixel buffer -- undefined behaviour.  Defined
 // semantics here: similarity(d) = exp(-d / sigma_colour^2) for every d in 0..65535
 // (a 65536-entry table whose first 256 entries are the reference's), 16-bit store per pixel.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <new>
 #include <type_traits>
 #include <vector>
 
+#include "bilateral_chain.hpp"
 #include "common.hpp"
 
 namespace tsdf {
@@ -28,6 +30,7 @@ namespace tsdf {
 constexpr int kBTile = 16;
 constexpr int kMaxRadius = 24;  // LDS tile (16+2*24)^2 * 12 B = 48 KiB
 
+constexpr float kMinStagedWeight = 0x1p-120f;   // the staged kernel runs only when every nonzero tap weight is at least this (tsdf_bilateral::scale_exact)
 constexpr int kSimLds = 4096;   // similarity entries staged in LDS (intensity differences below this; the rest stay in global memory)
 
 // One tap of the reference's accumulation (src/BilateralFilter.cpp:99-102):
@@ -204,11 +207,36 @@ __global__ __launch_bounds__(256) void bilateral_kernel(const PIX *__restrict__ 
                 }
             }
         };
-        auto chain = [&](const int i, auto first_row, auto count, const float *w, const unsigned *v4) {
+        // The chain of a half column (4 * intensity: `sum` runs as 4 * the reference's, see below).  A tap in the reference's mixed
+        // precision is three dependent double-rate operations (widen the sum, fma, narrow); a wave holds its registers, its slot and
+        // the workgroup's LDS for 225 of them.  Interior waves run the half column as one v_fma_f32 per tap and then ask
+        // chain_certified (bilateral_chain.hpp: the proof) whether that rounded like the reference -- one test per half column on its
+        // smallest weight and the sums before and after it.  If any lane's test fails the whole wave takes the sum back and redoes the
+        // half column in double (a uniform branch).  total_weight is an fp32 sum in both forms (bilateral_tap).
+        // Rim waves keep the double chain: they mask weights to 0 (whole half columns of them, which the test's lower bound on the
+        // weights would turn into a fallback every time), and they are a few per cent of the waves.
+        auto chain = [&](const int i, auto first_row, auto count, const float *w, const unsigned *v4, const auto rim) {
             constexpr int CNT = decltype(count)::value;
             (void)i;
+            if (decltype(rim)::value) {
 #pragma unroll
-            for (int j = 0; j < CNT; j++) bilateral_tap(w[j], (double)v4[j], sum, total_weight);   // (4 * intensity: `sum` runs as 4 * the reference's, see below)
+                for (int j = 0; j < CNT; j++) bilateral_tap(w[j], (double)v4[j], sum, total_weight);
+                return;
+            }
+            const float sum_before = sum;
+            unsigned w_min = __builtin_bit_cast(unsigned, w[0]);          // (weights are >= 0: their bits order like their values)
+#pragma unroll
+            for (int j = 1; j < CNT; j++) w_min = min(w_min, __builtin_bit_cast(unsigned, w[j]));
+#pragma unroll
+            for (int j = 0; j < CNT; j++) {
+                sum = chain_tap_f32(w[j], v4[j], sum);
+                total_weight = total_weight + w[j];
+            }
+            if (__builtin_expect(__any(!chain_certified(__builtin_bit_cast(float, w_min), sum_before, sum)), 0)) {
+                sum = sum_before;
+#pragma unroll
+                for (int j = 0; j < CNT; j++) sum = chain_tap_f64(w[j], v4[j], sum);
+            }
         };
         using Lo = std::integral_constant<int, 0>;
         using Hi = std::integral_constant<int, NA>;
@@ -219,13 +247,13 @@ __global__ __launch_bounds__(256) void bilateral_kernel(const PIX *__restrict__ 
 #pragma unroll 1
             for (int i = 0; i + 1 < N; i++) {              // conv_x: outer loop of the reference
                 fetch(i, Hi{}, CntB{}, w_b, v_b, rim);
-                chain(i, Lo{}, CntA{}, w_a, v_a);
+                chain(i, Lo{}, CntA{}, w_a, v_a, rim);
                 fetch(i + 1, Lo{}, CntA{}, w_a, v_a, rim);
-                chain(i, Hi{}, CntB{}, w_b, v_b);
+                chain(i, Hi{}, CntB{}, w_b, v_b, rim);
             }
             fetch(N - 1, Hi{}, CntB{}, w_b, v_b, rim);     // the last column, nothing left to prefetch
-            chain(N - 1, Lo{}, CntA{}, w_a, v_a);
-            chain(N - 1, Hi{}, CntB{}, w_b, v_b);
+            chain(N - 1, Lo{}, CntA{}, w_a, v_a, rim);
+            chain(N - 1, Hi{}, CntB{}, w_b, v_b, rim);
         };
         if (interior) {
             run(std::false_type{});
@@ -307,6 +335,95 @@ static int filter_host(const tsdf_bilateral *cf, PIX *host_image, int width, int
     return TSDF_OK;
 }
 
+// The filter's two tables as the reference's constructor computes them (src/BilateralFilter.cpp:17-40), and the smallest nonzero
+// weight a tap can have: the float product of the smallest nonzero entries of the two.
+static int bilateral_tables(float sigma_colour, float sigma_space, int *radius, std::vector<float> &kernel, std::vector<float> &similarity,
+                            float *min_weight) {
+    // src/BilateralFilter.cpp:17-23
+    int kernel_radius = (int)std::ceil(sigma_space * 1.5f);
+    TSDF_REQUIRE(kernel_radius <= kMaxRadius, "tsdf_bilateral_create: kernel radius %d exceeds %d", kernel_radius, kMaxRadius);
+    float inv_sigma_colour_squared = 1.0f / (sigma_colour * sigma_colour);
+    float inv_sigma_space_squared = 1.0f / (sigma_space * sigma_space);
+    int kernel_size = kernel_radius * 2 + 1;
+    int center = (kernel_size - 1) / 2;
+    kernel.resize((size_t)kernel_size * kernel_size);
+    int idx = 0;
+    for (int x = -center; x < kernel_size - center; x++) {
+        for (int y = -center; y < kernel_size - center; y++) {
+            float dist_squared = (float)(x * x + y * y);
+            kernel[idx] = std::exp(-dist_squared * inv_sigma_space_squared);  // :32
+            idx++;
+        }
+    }
+    similarity.resize(65536);
+    for (int i = 0; i < 65536; i++) similarity[i] = std::exp(-i * inv_sigma_colour_squared);  // :40
+    float min_k = 0.0f, min_s = 0.0f;
+    for (float k : kernel) if (k > 0.0f && (min_k == 0.0f || k < min_k)) min_k = k;
+    for (float x : similarity) if (x > 0.0f && (min_s == 0.0f || x < min_s)) min_s = x;
+    *radius = kernel_radius;
+    *min_weight = min_k * min_s;
+    return TSDF_OK;
+}
+
+// The staged kernel's chain on the host, wave by wave (16 x 4 pixels) and half column by half column, with the kernel's own tap
+// expressions and test (bilateral_chain.hpp).  Every pixel goes through the fp32 taps, the test and -- when any lane of its wave
+// fails it -- the double taps, rim pixels included (the kernel itself keeps rim waves on the double chain; counts[] covers interior
+// waves only, the ones that run the fp32 chain on the GPU).
+template <typename PIX>
+static void chain_image_host(const std::vector<float> &kernel, const std::vector<float> &similarity, const PIX *in, PIX *out, int width,
+                             int height, unsigned long long counts[4]) {
+    constexpr int R = 7, N = 2 * R + 1, NA = (N + 1) / 2;
+    for (int wy = 0; wy < height; wy += 4)
+        for (int wx = 0; wx < width; wx += kBTile) {
+            const int tx0 = wx - R, wy0 = wy - R;
+            const bool interior = tx0 >= 0 && tx0 + kBTile + 2 * R <= width && wy0 >= 0 && wy0 + 4 + 2 * R <= height;
+            float sum[64] = {0}, total[64] = {0};
+            for (int i = 0; i < N; i++)
+                for (int half = 0; half < 2; half++) {
+                    const int ja = half ? NA : 0, jb = half ? N : NA;
+                    float w[64][NA], before[64];
+                    uint32_t v4[64][NA];
+                    unsigned failed = 0;
+                    for (int l = 0; l < 64; l++) {
+                        const int x = wx + (l & 15), y = wy + (l >> 4);
+                        const bool inside = x < width && y < height;
+                        const int i0 = std::max(0, R - x), i1 = inside ? std::min(N - 1, width - 1 - x + R) : -1;
+                        const int j0 = std::max(0, R - y), j1 = inside ? std::min(N - 1, height - 1 - y + R) : -1;
+                        const int nyv = j1 - j0 + 1;
+                        before[l] = sum[l];
+                        float w_min = 0.0f;
+                        for (int j = ja; j < jb; j++) {
+                            const bool ok = i >= i0 && i <= i1 && j >= j0 && j <= j1;
+                            const int v = ok ? (int)in[(size_t)(y + j - R) * width + (x + i - R)] : 0;
+                            const int c = inside ? (int)in[(size_t)y * width + x] : 0;
+                            const float wt = ok ? kernel[(i - i0) * nyv + (j - j0)] * similarity[std::abs(v - c)] : 0.0f;
+                            w[l][j - ja] = wt;
+                            v4[l][j - ja] = 4u * (uint32_t)v;
+                            w_min = j == ja ? wt : std::min(w_min, wt);
+                            sum[l] = chain_tap_f32(wt, v4[l][j - ja], sum[l]);
+                            total[l] = total[l] + wt;
+                        }
+                        if (inside && !chain_certified(w_min, before[l], sum[l])) failed++;
+                    }
+                    if (interior) {
+                        counts[0]++;
+                        counts[1] += failed ? 1 : 0;
+                        counts[2] += 64;
+                        counts[3] += failed;
+                    }
+                    if (failed)
+                        for (int l = 0; l < 64; l++) {
+                            sum[l] = before[l];
+                            for (int j = ja; j < jb; j++) sum[l] = chain_tap_f64(w[l][j - ja], v4[l][j - ja], sum[l]);
+                        }
+                }
+            for (int l = 0; l < 64; l++) {
+                const int x = wx + (l & 15), y = wy + (l >> 4);
+                if (x < width && y < height && out) out[(size_t)y * width + x] = (PIX)(int)floorf(sum[l] * 0.25f / total[l]);
+            }
+        }
+}
+
 }  // namespace tsdf
 
 using namespace tsdf;
@@ -317,24 +434,11 @@ int tsdf_bilateral_create(float sigma_colour, float sigma_space, tsdf_bilateral 
     TSDF_REQUIRE(out, "tsdf_bilateral_create: null out pointer");
     *out = nullptr;
     TSDF_REQUIRE(sigma_colour > 0 && sigma_space > 0, "tsdf_bilateral_create: sigmas must be positive");
-    // src/BilateralFilter.cpp:17-23
-    int kernel_radius = (int)std::ceil(sigma_space * 1.5f);
-    TSDF_REQUIRE(kernel_radius <= kMaxRadius, "tsdf_bilateral_create: kernel radius %d exceeds %d", kernel_radius, kMaxRadius);
-    float inv_sigma_colour_squared = 1.0f / (sigma_colour * sigma_colour);
-    float inv_sigma_space_squared = 1.0f / (sigma_space * sigma_space);
-    int kernel_size = kernel_radius * 2 + 1;
-    int center = (kernel_size - 1) / 2;
-    std::vector<float> kernel((size_t)kernel_size * kernel_size);
-    int idx = 0;
-    for (int x = -center; x < kernel_size - center; x++) {
-        for (int y = -center; y < kernel_size - center; y++) {
-            float dist_squared = (float)(x * x + y * y);
-            kernel[idx] = std::exp(-dist_squared * inv_sigma_space_squared);  // :32
-            idx++;
-        }
-    }
-    std::vector<float> similarity(65536);
-    for (int i = 0; i < 65536; i++) similarity[i] = std::exp(-i * inv_sigma_colour_squared);  // :40
+    int kernel_radius = 0;
+    std::vector<float> kernel, similarity;
+    float min_weight = 0.0f;
+    int rc = bilateral_tables(sigma_colour, sigma_space, &kernel_radius, kernel, similarity, &min_weight);
+    if (rc != TSDF_OK) return rc;
 
     tsdf_bilateral *f = new (std::nothrow) tsdf_bilateral();
     if (!f) {
@@ -345,13 +449,7 @@ int tsdf_bilateral_create(float sigma_colour, float sigma_space, tsdf_bilateral 
     f->sigma_colour = sigma_colour;
     f->sigma_space = sigma_space;
     f->radius = kernel_radius;
-    {
-        // smallest nonzero weight a tap can have: the float product of the smallest nonzero entries of the two tables
-        float min_k = 0.0f, min_s = 0.0f;
-        for (float k : kernel) if (k > 0.0f && (min_k == 0.0f || k < min_k)) min_k = k;
-        for (float x : similarity) if (x > 0.0f && (min_s == 0.0f || x < min_s)) min_s = x;
-        f->scale_exact = (min_k * min_s >= 0x1p-120f) ? 1 : 0;
-    }
+    f->scale_exact = (min_weight >= kMinStagedWeight) ? 1 : 0;
     hipError_t e = hipGetDevice(&f->device);
     if (e == hipSuccess) e = hipMalloc((void **)&f->kernel_dev, kernel.size() * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&f->similarity_dev, similarity.size() * sizeof(float));
@@ -364,6 +462,37 @@ int tsdf_bilateral_create(float sigma_colour, float sigma_space, tsdf_bilateral 
         return rc;
     }
     *out = f;
+    return TSDF_OK;
+}
+
+int tsdf_selftest_bilateral_chain_taps(size_t n, const float *w, const uint32_t *v4, const float *s, float *s_f32, float *s_f64,
+                                       uint8_t *certified) {
+    TSDF_REQUIRE(w && v4 && s && s_f32 && s_f64 && certified, "tsdf_selftest_bilateral_chain_taps: null pointer");
+    for (size_t i = 0; i < n; i++) {
+        // what the proof of chain_certified assumes of the staged kernel's operands
+        TSDF_REQUIRE((w[i] == 0.0f || (w[i] >= kMinStagedWeight && w[i] <= 1.0f)) && v4[i] % 4u == 0 && v4[i] < (1u << 18) &&
+                         (s[i] == 0.0f || (s[i] >= kMinStagedWeight && s[i] <= 0x1p40f)),
+                     "tsdf_selftest_bilateral_chain_taps: tap %zu is outside the staged kernel's operand ranges", i);
+        s_f32[i] = chain_tap_f32(w[i], v4[i], s[i]);
+        s_f64[i] = chain_tap_f64(w[i], v4[i], s[i]);
+        certified[i] = chain_certified(w[i], s[i], s_f32[i]) ? 1 : 0;
+    }
+    return TSDF_OK;
+}
+
+int tsdf_selftest_bilateral_chain_image(float sigma_colour, float sigma_space, const void *image, int bits_per_pixel, int width, int height,
+                                        void *filtered, unsigned long long counts[4]) {
+    TSDF_REQUIRE(image && counts && width > 0 && height > 0 && (bits_per_pixel == 8 || bits_per_pixel == 16) && sigma_colour > 0 && sigma_space > 0,
+                 "tsdf_selftest_bilateral_chain_image: bad argument");
+    int radius = 0;
+    std::vector<float> kernel, similarity;
+    float min_weight = 0.0f;
+    int rc = bilateral_tables(sigma_colour, sigma_space, &radius, kernel, similarity, &min_weight);
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(radius == 7 && min_weight >= kMinStagedWeight, "tsdf_selftest_bilateral_chain_image: these sigmas do not take the staged kernel");
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (bits_per_pixel == 8) chain_image_host<uint8_t>(kernel, similarity, (const uint8_t *)image, (uint8_t *)filtered, width, height, counts);
+    else chain_image_host<uint16_t>(kernel, similarity, (const uint16_t *)image, (uint16_t *)filtered, width, height, counts);
     return TSDF_OK;
 }
 
