@@ -59,7 +59,7 @@ oracle:
 	$(MAKE) -C oracle -s all
 
 # C++ test program of the class surface (run by tests/test_cpp_surface.py on the GPU box)
-cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_fuse build/test_align build/kinfu_stream
+cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_rays build/test_fuse build/test_align build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
 build/kinfu_stream: tools/kinfu_stream.cpp $(LIBDIR)/libtsdf_host.so include/tsdf_amd.h
@@ -84,6 +84,11 @@ build/test_weight_cap: tests/cpp/test_weight_cap.cpp $(LIBDIR)/libtsdf_host.so
 build/test_field: tests/cpp/test_field.cpp $(LIBDIR)/libtsdf_host.so
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_field.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
+
+# C++ check of the ray queries through the class surface (run by tests/test_cpp_rays.py on the GPU box)
+build/test_rays: tests/cpp/test_rays.cpp $(LIBDIR)/libtsdf_host.so
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_rays.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
 # C++ check of volume fusion through the class surface (run by tests/test_cpp_fuse.py on the GPU box)
 build/test_fuse: tests/cpp/test_fuse.cpp $(LIBDIR)/libtsdf_host.so

@@ -390,6 +390,51 @@ int tsdf_volume_sample_field(const tsdf_volume *volume, uint64_t n, const float 
 int tsdf_raycast_gradient_normals_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
                                          const float kinv[9], float *device_vertices, float *device_normals);
 
+/* ---- ray queries (no reference counterpart: the reference casts the rays of a pinhole image only) ---------------------------------- */
+/* Where does THIS ray hit the surface?  n rays of the caller's own -- a spinning LiDAR or fisheye model, a visibility test between two
+ * points, a collision probe, a few rays around a tracked feature -- each marched as the image cast marches a pixel's ray.  Opt-in by
+ * being called: a volume on which these are never called does exactly what it did.
+ *   Frame: origins and directions are 3 n floats in world millimetres, the frame of ray-cast and mesh vertices (the volume's CURRENT
+ *     offset is the box's space_min, offset + physical size its space_max), like the points of "field queries".
+ *   The march of ray i: process_ray (src/RayCaster/GPURaycaster.cu:265-377) as tsdf_raycast evaluates it, with origin = origins[i] and
+ *     dir = directions[i] used AS GIVEN -- the reference normalises neither (Q6), so the step along the ray is 0.05 * trunc * |dir|:
+ *     the same ray/box test giving near_t and max_t, the same start point ((near_t * dir) + origin) - space_min, the same sample
+ *     parameters T[k] (T[0] = 0, T[k+1] = T[k] + step in fp32), the same trilinear sample S ("field queries"), the same stop at the first
+ *     sample <= 0, the same refinement of its parameter with previous_tsdf == trunc (Q7) giving th, the same `t >= max_t` and
+ *     4402-sample limits, every fp32 operation rounded on its own.  A ray given a pixel's origin and direction returns that pixel's
+ *     vertex of tsdf_raycast bit for bit.
+ *   points[i]: the reference's hit point ((th * dir) + start) + space_min, or (NaN, NaN, NaN) on a miss.
+ *   t[i]: near_t + th (one fp32 add), the ray parameter of the hit measured from the origin in units of dir -- millimetres for a
+ *     unit direction; NaN on a miss.
+ *   normals[i]: exactly what tsdf_volume_sample_field_device(..., TSDF_FIELD_UNIT_GRADIENT) returns at points[i] (the NaN triple
+ *     within a voxel of a face); the NaN triple on a miss.
+ *   t_max (n floats, or NULL = no limit): the march's FIRST hit counts only if t[i] <= t_max[i]; otherwise the ray is a miss (a
+ *     surface behind the limit is not looked for past an earlier one).  A NaN t_max[i] is therefore a miss, +inf no limit.
+ *   Decreed misses, decided before any march: a non-finite component of the origin or the direction; a direction of all zeros (-0.0
+ *     included).
+ *   Explicit deformation nodes are ignored, as the image cast ignores them.
+ *   Refused (TSDF_ERR_INVALID, with a message): a NULL volume; a Z-slab volume (tsdf_volume_create_slab); all three outputs NULL; NULL
+ *     origins or directions with n > 0; more rays than a launch holds (n > (2^31 - 1) * 256).  n == 0 is TSDF_OK and launches nothing.
+ *   Side effects: distances, weights, colours and counters are never written.  The brick occupancy the march skips by is refreshed as
+ *     the image cast refreshes it, so a query after an integrate, tsdf_volume_set_distance_data, tsdf_volume_mark_dirty or clear sees
+ *     the current field.  Nothing of the image cast's scheduling state changes: an image cast after a ray query takes the same kernels
+ *     (tsdf_volume_last_raycast_kind) and gives the same bits as without the query.  One thing the query does in the image cast's
+ *     place: the first ray cast of either kind after a bulk change of the distances (tsdf_volume_set_distance_data,
+ *     tsdf_volume_mark_dirty, clear, a loaded file) rebuilds the flags, counts the flagged bricks the image cast chooses its kernels
+ *     by, and waits for the volume's stream once -- so that one query blocks, also through the device entry point, and until the next
+ *     cell-parallel cast tsdf_volume_last_cell_list reports that count, not the list of a cast.
+ *   Output order is input order; the rays are not sorted.
+ *   Out of scope: slab or multi-GPU volumes, rays in the deformed space, colour at the hits (tsdf_volume_sample_colours_device takes
+ *     the hit points). */
+/* Device pointers; any of the three outputs may be NULL, not all.  Asynchronous on the volume's stream, like tsdf_raycast_device
+ * (and like it synchronising once after a bulk change of the distances: see "Side effects"). */
+int tsdf_volume_cast_rays_device(const tsdf_volume *volume, uint64_t n, const float *device_origins, const float *device_directions,
+                                 const float *device_t_max /* n floats, or NULL = no limit */,
+                                 float *device_points, float *device_t, float *device_normals);
+/* The same on host arrays, on the volume's stream; blocking. */
+int tsdf_volume_cast_rays(const tsdf_volume *volume, uint64_t n, const float *host_origins, const float *host_directions,
+                          const float *host_t_max, float *host_points, float *host_t, float *host_normals);
+
 /* ---- volume fusion (no reference counterpart: the reference's volume is filled from depth frames only) ------------------------------ */
 /* Resamples the field of `src` onto the grid of `dst` through a rigid transform and blends it in: merging a second session's volume or
  * a sub-map, re-posing a volume after a loop closure, moving a volume to a finer or coarser grid, re-centring the grid.  Opt-in by

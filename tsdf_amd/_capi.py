@@ -126,6 +126,8 @@ _SIGS = {
     "tsdf_volume_sample_field_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _i, _vp]),
     "tsdf_volume_sample_field": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _i]),
     "tsdf_raycast_gradient_normals_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
+    "tsdf_volume_cast_rays_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsdf_volume_cast_rays": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsdf_volume_fuse": (_i, [_vp, _vp, _fp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_last_fuse_bricks": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tsdf_aligner_create": (_i, [C.POINTER(_vp)]),

@@ -24,6 +24,21 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def direction_lengths(directions):
+    """fp32 lengths of (n, 3) float32 directions: sqrt((x x + y y) + z z), every operation rounded to float32."""
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        return np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+
+
+def unit_directions(directions):
+    """Each of (n, 3) float32 directions divided by its fp32 length (direction_lengths); a zero or non-finite direction comes out
+    non-finite, which a ray query answers with a miss."""
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        return np.ascontiguousarray(d / direction_lengths(d)[:, None], dtype=np.float32)
+
+
 def _camera_matrices(camera):
     """pose, inverse_pose, k, kinv of anything shaped like the reference's Camera (src/include/Camera.hpp)."""
     return (_mat(camera.pose(), 16), _mat(camera.inverse_pose(), 16), _mat(camera.k(), 9), _mat(camera.kinv(), 9))
@@ -372,6 +387,50 @@ class TSDFVolume:
         float32; a normal is the NaN triple within a voxel of the grid's faces."""
         V = self.extract_surface()
         return V, self.sample_field(V, weight=False, unit_gradient=True)[1]
+
+    # ---- ray queries (include/tsdf_amd.h, "ray queries"; not in the reference's class)
+    def cast_rays_device(self, n, origins_ptr, directions_ptr, t_max_ptr, points_ptr, t_ptr, normals_ptr):
+        """n rays (origins and directions 3 float32 each, t_max n float32 or None; device) -> points (3 n), t (n), normals (3 n): device
+        pointers, any of the three outputs may be None, not all.  Asynchronous on the volume's stream."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_volume_cast_rays_device(self._h, int(n), ptr(origins_ptr), ptr(directions_ptr), ptr(t_max_ptr), ptr(points_ptr),
+                                               ptr(t_ptr), ptr(normals_ptr)))
+
+    def cast_rays(self, origins, directions, t_max=None, normals=False, normalise=False):
+        """(n, 3) float32 origins and directions (world mm, the frame of ray-cast and mesh vertices) -> (points (n, 3), t (n,)[,
+        normals (n, 3)]), float32: where each ray first meets the surface, marched as the image cast marches a pixel's ray -- the
+        direction is used as given, t is the hit's ray parameter in units of it -- NaN on a miss.  t_max (n,): a hit counts only if
+        t <= t_max.  normals: the unit gradient of the field at the hit.  normalise: divide each direction by its fp32 length first,
+        so t is in millimetres."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        if len(d) != n:
+            raise ValueError("cast_rays: %d origins, %d directions" % (n, len(d)))
+        if normalise:
+            d = unit_directions(d)
+        m = None
+        if t_max is not None:
+            m = np.ascontiguousarray(t_max, dtype=np.float32).reshape(-1)
+            if len(m) != n:
+                raise ValueError("cast_rays: %d rays, %d range limits" % (n, len(m)))
+        # (one row more than asked for: the pointer of an empty array may be null, which the C ABI reads as "not asked for")
+        p = np.empty((n + 1, 3), np.float32)
+        t = np.empty(n + 1, np.float32)
+        g = np.empty((n + 1, 3), np.float32) if normals else None
+        check(lib.tsdf_volume_cast_rays(self._h, n, o.ctypes.data if n else None, d.ctypes.data if n else None,
+                                        m.ctypes.data if (m is not None and n) else None, p.ctypes.data, t.ctypes.data,
+                                        g.ctypes.data if normals else None))
+        return (p[:n], t[:n], g[:n]) if normals else (p[:n], t[:n])
+
+    def visible(self, a, b):
+        """(n, 3) points a and b -> bool (n,): True where no surface lies between them -- the ray from a along the normalised b - a
+        (fp32) with t_max = |b - a| hits nothing.  (a == b, or a non-finite point: a decreed miss, True.)"""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+        d = b - a
+        _, t = self.cast_rays(a, d, t_max=direction_lengths(d), normalise=True)
+        return np.isnan(t)
 
     # ---- field alignment (include/tsdf_amd.h, "field alignment"; not in the reference's class)
     def align_points(self, points, T0=None, iterations=10, gate=None):

@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "raycast_sample.hpp"
+#include "field_sample.hpp"
 
 namespace tsdf {
 
@@ -400,6 +401,7 @@ __device__ inline uint32_t load_best(const uint64_t *p) {   // (the index half: 
 __device__ inline void lower_best(uint64_t *p, int k, float tsdf) { atomicMin(reinterpret_cast<unsigned long long *>(p), (unsigned long long)hit_word(k, tsdf)); }
 
 #include "raycast_march.hpp"
+#include "raycast_rays.hpp"
 
 // render_to_depth_image, per pixel (src/RayCaster/GPURaycaster.cu:575-579 with Camera::world_to_camera, src/Camera.cpp:287-294):
 // camera-space z of the vertex (homogeneous product, divided by w), rounded half away from zero; no hit (NaN) -> 0.
@@ -1353,6 +1355,50 @@ int tsdf_merge_hits_normals_device(const tsdf_volume *v, const tsdf_hit_record *
                        (hipStream_t)hip_stream, reinterpret_cast<const uint2 *>(device_hits_all), n_slabs, rp, device_vertices,
                        device_normals);
     TSDF_HIP(hipGetLastError(), "merge hits + normals failed");
+    return TSDF_OK;
+}
+
+// ---- ray queries (include/tsdf_amd.h, "ray queries"; raycast_rays.hpp) --------------------------------------------------------------
+int tsdf_volume_cast_rays_device(const tsdf_volume *v, uint64_t n, const float *device_origins, const float *device_directions,
+                                 const float *device_t_max, float *device_points, float *device_t, float *device_normals) {
+    const int rc = cast_rays_check(v, n, device_origins, device_directions, device_points, device_t, device_normals);
+    if (rc != TSDF_OK) return rc;
+    if (n == 0) return TSDF_OK;
+    return cast_rays(const_cast<tsdf_volume *>(v), n, device_origins, device_directions, device_t_max, device_points, device_t, device_normals);
+}
+
+int tsdf_volume_cast_rays(const tsdf_volume *cv, uint64_t n, const float *host_origins, const float *host_directions,
+                          const float *host_t_max, float *host_points, float *host_t, float *host_normals) {
+    const int rc0 = cast_rays_check(cv, n, host_origins, host_directions, host_points, host_t, host_normals);
+    if (rc0 != TSDF_OK) return rc0;
+    if (n == 0) return TSDF_OK;
+    TSDF_REQUIRE(n <= ((uint64_t)1 << 40), "tsdf_volume_cast_rays: too many rays");
+    tsdf_volume *v = const_cast<tsdf_volume *>(cv);
+    // one allocation: origins (3n), directions (3n), then t_max (n), points (3n), t (n), normals (3n) as far as given / asked for
+    const size_t fn = (size_t)n;
+    const size_t o_m = 6 * fn, o_p = o_m + (host_t_max ? fn : 0), o_t = o_p + (host_points ? 3 * fn : 0), o_n = o_t + (host_t ? fn : 0),
+                 total = o_n + (host_normals ? 3 * fn : 0);
+    float *buf = nullptr;
+    if (hipMalloc((void **)&buf, total * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("tsdf_volume_cast_rays: couldn't allocate %zu bytes for the rays and results", total * sizeof(float));
+        return TSDF_ERR_NOMEM;
+    }
+    float *m = host_t_max ? buf + o_m : nullptr, *p = host_points ? buf + o_p : nullptr, *t = host_t ? buf + o_t : nullptr,
+          *nrm = host_normals ? buf + o_n : nullptr;
+    hipError_t e = hipMemcpyAsync(buf, host_origins, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(buf + 3 * fn, host_directions, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
+    if (e == hipSuccess && m) e = hipMemcpyAsync(m, host_t_max, fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
+    int rc = TSDF_OK;
+    if (e == hipSuccess) rc = cast_rays(v, n, buf, buf + 3 * fn, m, p, t, nrm);
+    if (rc == TSDF_OK && e == hipSuccess && p) e = hipMemcpyAsync(host_points, p, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
+    if (rc == TSDF_OK && e == hipSuccess && t) e = hipMemcpyAsync(host_t, t, fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
+    if (rc == TSDF_OK && e == hipSuccess && nrm) e = hipMemcpyAsync(host_normals, nrm, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
+    const hipError_t es = hipStreamSynchronize(v->stream);   // (before the buffer goes, whatever happened)
+    (void)hipFree(buf);
+    if (rc != TSDF_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "Ray query failed");
+    if (es != hipSuccess) return hip_fail(es, "Ray query failed");
     return TSDF_OK;
 }
 

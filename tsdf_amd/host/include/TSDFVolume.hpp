@@ -120,6 +120,14 @@ public:
     void sample_field(const std::vector<float3> &points, std::vector<float> *distances, std::vector<float3> *gradients,
                       std::vector<float> *weights, bool unit_gradient = false) const;
 
+    // Ray queries (include/tsdf_amd.h, "ray queries"; not in the reference's class): where each ray (origin and direction in world mm,
+    // the frame of ray-cast and mesh vertices; the direction is used as given) first meets the surface, marched as the image cast
+    // marches a pixel's ray.  points[i] is the hit point, (*t)[i] its ray parameter in units of the direction, (*normals)[i] the unit
+    // gradient of the field there; NaN on a miss.  With t_max a hit counts only if t <= (*t_max)[i].  Throws std::invalid_argument on
+    // a Z-slab and when origins, directions and t_max differ in length.
+    void cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
+                   std::vector<float> *t = nullptr, std::vector<float3> *normals = nullptr, const std::vector<float> *t_max = nullptr) const;
+
     // Volume fusion (include/tsdf_amd.h, "volume fusion"; not in the reference's class): resamples the field of `src` onto this volume's
     // grid through the rigid transform dst_to_src (this volume's world frame -> src's) and blends it in, weights added; returns the
     // number of voxels updated.  Grids, voxel sizes, offsets and truncation distances may differ; src is not changed.  Throws

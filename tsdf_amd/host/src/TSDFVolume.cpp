@@ -166,6 +166,25 @@ void TSDFVolume::sample_field(const std::vector<float3> &points, std::vector<flo
     if (weights) weights->resize(n);
 }
 
+void TSDFVolume::cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
+                           std::vector<float> *t, std::vector<float3> *normals, const std::vector<float> *t_max) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    const size_t n = origins.size();
+    if (directions.size() != n) throw std::invalid_argument("cast_rays: origins and directions differ in length");
+    if (t_max && t_max->size() != n) throw std::invalid_argument("cast_rays: t_max and the rays differ in length");
+    // (one element more than needed: data() of an empty vector may be null, which the C ABI reads as "not asked for")
+    points.assign(n + 1, float3{0.0f, 0.0f, 0.0f});
+    if (t) t->assign(n + 1, 0.0f);
+    if (normals) normals->assign(n + 1, float3{0.0f, 0.0f, 0.0f});
+    check(tsdf_volume_cast_rays(m_handle, n, reinterpret_cast<const float *>(origins.data()), reinterpret_cast<const float *>(directions.data()),
+                                (t_max && n) ? t_max->data() : nullptr, reinterpret_cast<float *>(points.data()), t ? t->data() : nullptr,
+                                normals ? reinterpret_cast<float *>(normals->data()) : nullptr),
+          "Couldn't cast the rays");
+    points.resize(n);
+    if (t) t->resize(n);
+    if (normals) normals->resize(n);
+}
+
 Eigen::Matrix4d TSDFVolume::align_points(const std::vector<float3> &points, const Eigen::Matrix4d &T0, uint32_t iterations, float gate,
                                          float *residual, float *inliers) const {
     static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
