@@ -470,6 +470,61 @@ int tsdf_volume_fuse(tsdf_volume *dst, const tsdf_volume *src, const float dst_t
  * (both 0 before the first fuse).  Synchronises dst's stream. */
 int tsdf_volume_last_fuse_bricks(const tsdf_volume *dst, uint32_t *listed_bricks, uint32_t *total_bricks);
 
+/* ---- ray integration (no reference counterpart: the reference's volume is filled from pinhole depth frames only) -------------------- */
+/* Fuses n rays of the caller's own -- a spinning LiDAR's scan, a fisheye depth sensor, a stereo point cloud, a merged scan, the point
+ * set tsdf_aligner_* has just posed -- into the volume: ray i runs from its origin (the sensor's position) to points[i] (the surface
+ * it measured).  Opt-in by being called: a volume on which these are never called does exactly what it did.
+ *   points: n xyz triples, fp32, world millimetres in the frame of ray-cast and mesh vertices (the volume's CURRENT offset), like the
+ *     points of "field queries" and the rays of "ray queries".  origins: one triple (n_origins == 1: one sensor position for the whole
+ *     scan) or n triples (n_origins == n).
+ *   updated_voxels may be NULL.  Non-NULL: the call synchronises and stores the number of voxels it changed, as tsdf_volume_fuse does
+ *     with fused_voxels; otherwise the device variant is asynchronous on the volume's stream, like tsdf_integrate_device.
+ *   ONE CALL IS ONE OBSERVATION PER VOXEL: a voxel that any number of the call's rays cross takes the mean of their observations and
+ *     its weight goes up by 1, exactly as a voxel seen by one depth frame.  Weights stay frame counts: the 8 / 16 / 32-bit storage,
+ *     its widening before a count could overflow and the weight cap all behave as for tsdf_integrate.
+ * The rules.  Every operation is separately rounded fp32 in the order written, unless marked as double; o is the ray's origin, p its
+ * point, N_k the grid's size, offset the current offset, trunc the truncation distance.
+ *   1. Ray: d = p - o per component; r = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z); u = d / r (three divisions).  The ray is a decreed skip,
+ *      before any walk, if a component of o or p is not finite, if r is zero or not finite, if r < min_range, if r > max_range (+inf:
+ *      no limit), or if either range is NaN.
+ *   2. Stretch: te = r + trunc; ts = 0, or fmaxf(r - trunc, 0) with TSDF_RAYS_BAND_ONLY.  The default is what the depth integrate does,
+ *      which updates every voxel with sdf >= -trunc, the free space in front of the surface included.
+ *   3. Grid coordinates: a_k = (o_k - offset_k) / voxel_size_k, s_k = u_k / voxel_size_k.
+ *   4. Clip of [t0, t1] = [ts, te] to the box [0, N_k]: an axis with s_k == 0 skips the ray unless 0 <= a_k < N_k; otherwise
+ *      ta = (0 - a_k) / s_k, tb = ((float)N_k - a_k) / s_k, t0 = fmaxf(t0, fminf(ta, tb)), t1 = fminf(t1, fmaxf(ta, tb)).  The ray is
+ *      skipped unless t0 < t1.
+ *   5. Walk (Amanatides-Woo, without drift): the start cell is i_k = clamp((int)floorf(a_k + t0 * s_k), 0, N_k - 1).  Repeat: visit i;
+ *      for each axis with s_k != 0, tn_k = ((float)(i_k + (s_k > 0 ? 1 : 0)) - a_k) / s_k -- recomputed from the integer cell every
+ *      time, never accumulated; take the axis with the smallest tn_k (on a tie x before y, y before z); stop if that tn_k > t1; step
+ *      that axis by sign(s_k); stop when the cell leaves the grid.  No ray visits more than X + Y + Z cells.
+ *   6. Observation of a visited voxel (x, y, z): its centre c.x = ((x + 0.5f) * voxel_size.x) + offset.x, likewise y and z (the
+ *      expression of "volume fusion"); e = c - o; sdf = r - ((e.x*u.x + e.y*u.y) + e.z*u.z).  No observation if sdf < -trunc.
+ *      tsdf = sdf > 0 ? fminf(sdf, trunc) : sdf;  q = (int)rintf((tsdf / trunc) * 32768.0f), an integer in [-32768, 32768].
+ *   7. Accumulation: per voxel, over the call's rays, the count n_v of observations and the exact integer sum S_v of their q.  Integer
+ *      sums have no order: the result does not depend on the order of the rays, nor on which lanes run them.
+ *   8. Apply, for every voxel with n_v >= 1: m = (float)(((double)S_v / (double)n_v) * ((double)trunc * (1.0 / 32768.0))) (double);
+ *      d' = ((d * w) + m) / (w + 1) with IEEE division; w' = w + 1, stored as min(w + 1, cap) under tsdf_volume_set_weight_cap (the
+ *      divisor stays w + 1).  Every other voxel keeps its distance and weight bit for bit.
+ * Left alone: colour; a prepared integrate (tsdf_integrate_prepare_device_tiles) is neither used nor discarded; explicit deformation
+ *   nodes are refused, not ignored.  The ray caster's summary is handed over as tsdf_volume_mark_dirty does: the next cast rebuilds
+ *   it from the distances.  The call does not count towards the periodic tightening of that summary.
+ * Scratch: 8 bytes per voxel (1 GiB at 512^3) plus one byte per 64 x 4 x 32-voxel brick, allocated zeroed by the first call, all zero
+ *   again whenever a call ends, kept until tsdf_volume_destroy or tsdf_volume_release_ray_scratch.
+ * Refused (TSDF_ERR_INVALID, with a message, nothing written): a NULL volume; unknown flag bits; n_origins neither 1 nor n; n > 2^23
+ *   (S_v then fits 40 bits beside a 24-bit count in one 64-bit word); NULL points or origins with n > 0; a Z-slab
+ *   (tsdf_volume_create_slab); a materialised deformation-node array (voxel centres must be the implicit grid, as for
+ *   tsdf_volume_fuse).  n == 0 is TSDF_OK and changes nothing.
+ * Out of scope: taking a ray set back out (tsdf_deintegrate* has no ray counterpart: the mean of a call's observations is not kept),
+ *   colour, slab or multi-GPU volumes, rays in the deformed space. */
+#define TSDF_RAYS_BAND_ONLY 1   /* update only within trunc of the end point: no free-space carving */
+int tsdf_integrate_rays_device(tsdf_volume *volume, uint64_t n, const float *device_origins, uint64_t n_origins,
+                               const float *device_points, float min_range, float max_range, int flags, uint64_t *updated_voxels);
+/* The same on host arrays, on the volume's stream; blocking. */
+int tsdf_integrate_rays(tsdf_volume *volume, uint64_t n, const float *host_origins, uint64_t n_origins, const float *host_points,
+                        float min_range, float max_range, int flags, uint64_t *updated_voxels);
+/* Frees the scratch of the two calls above (synchronises the volume's stream); the next call allocates it again. */
+int tsdf_volume_release_ray_scratch(tsdf_volume *volume);
+
 /* ---- field alignment (no reference counterpart: nothing in the reference produces a transform from the field itself) --------------- */
 /* The rigid pose that puts a point set on the zero level of the fused field: Gauss-Newton on sum S(T x)^2, which is point-to-plane ICP
  * with the association replaced by a trilinear sample (the field is the model: distance 0 on the surface, the gradient its normal).

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("TSDF_HIP_LIB") or os.path.join(_HERE, "lib", "libtsdf
 
 TSDF_OK, TSDF_ERR_INVALID, TSDF_ERR_DEVICE, TSDF_ERR_NOMEM = 0, 1, 2, 3
 TSDF_FIELD_UNIT_GRADIENT = 1
+TSDF_RAYS_BAND_ONLY = 1
 
 
 class TsdfError(RuntimeError):
@@ -130,6 +131,9 @@ _SIGS = {
     "tsdf_volume_cast_rays": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsdf_volume_fuse": (_i, [_vp, _vp, _fp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_last_fuse_bricks": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tsdf_integrate_rays_device": (_i, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _f, _f, _i, C.POINTER(C.c_uint64)]),
+    "tsdf_integrate_rays": (_i, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _f, _f, _i, C.POINTER(C.c_uint64)]),
+    "tsdf_volume_release_ray_scratch": (_i, [_vp]),
     "tsdf_aligner_create": (_i, [C.POINTER(_vp)]),
     "tsdf_aligner_destroy": (None, [_vp]),
     "tsdf_aligner_set_stream": (_i, [_vp, _vp]),

@@ -461,6 +461,36 @@ class TSDFVolume:
         check(lib.tsdf_volume_last_fuse_bricks(self._h, C.byref(listed), C.byref(total)))
         return int(listed.value), int(total.value)
 
+    # ---- ray integration (include/tsdf_amd.h, "ray integration"; not in the reference's class)
+    def integrate_rays_device(self, n, origins_ptr, n_origins, points_ptr, band_only=False, min_range=0.0, max_range=float("inf")):
+        """n rays on the device: origins (3 float32 each; n_origins = 1 for one sensor position, or n) and end points (3 n float32).
+        Asynchronous on the volume's stream; nothing is returned."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_integrate_rays_device(self._h, int(n), ptr(origins_ptr), int(n_origins), ptr(points_ptr), float(min_range),
+                                             float(max_range), _capi.TSDF_RAYS_BAND_ONLY if band_only else 0, None))
+
+    def integrate_rays(self, origins, points, band_only=False, min_range=0.0, max_range=float("inf")):
+        """Fuse a LiDAR scan or a point cloud: (n, 3) float32 end points (world mm, the frame of ray-cast and mesh vertices) measured from
+        `origins`, (3,) for one sensor position or (n, 3).  Every voxel the rays cross takes the mean of their observations as ONE
+        observation (weight + 1), free space in front of the points included; band_only: only within the truncation distance of each
+        point.  Rays shorter than min_range or longer than max_range are left out.  -> the number of voxels updated.  Raises ValueError
+        on the refusals."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        if o.ndim == 1 and o.size == 3:
+            o = o.reshape(1, 3)
+        if o.ndim != 2 or o.shape[1] != 3:
+            raise ValueError("integrate_rays: origins must be (3,) or (n, 3), got shape %s" % (o.shape,))
+        n = len(p)
+        updated = C.c_uint64()
+        check(lib.tsdf_integrate_rays(self._h, n, o.ctypes.data if n else None, len(o), p.ctypes.data if n else None, float(min_range),
+                                      float(max_range), _capi.TSDF_RAYS_BAND_ONLY if band_only else 0, C.byref(updated)))
+        return int(updated.value)
+
+    def release_ray_scratch(self):
+        """Free the scratch integrate_rays keeps between calls (8 bytes per voxel); the next call allocates it again."""
+        check(lib.tsdf_volume_release_ray_scratch(self._h))
+
     def occupancy(self):
         """(occupied, total) bricks of the ray caster's empty-space summary."""
         o, t = C.c_uint64(), C.c_uint64()

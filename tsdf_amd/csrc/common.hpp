@@ -371,6 +371,10 @@ struct tsdf_volume {
     void *fuse_scratch;
     size_t fuse_scratch_cap;
     uint32_t fuse_bricks_total;   // destination bricks of the last fuse (0: none yet)
+    // ray integration (integrate_rays.hip): the updated-voxel counter, one mark per integrate brick and one 64-bit accumulator per
+    // voxel; all zero between calls
+    void *rays_scratch;
+    size_t rays_scratch_cap;
     size_t resident_voxels() const { return (size_t)g.X * g.Y * (g.z_store_end - g.z_store_begin); }
 };
 

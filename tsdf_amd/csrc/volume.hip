@@ -945,6 +945,7 @@ int tsdf_volume_destroy(tsdf_volume *v) {
     if (v->colour) (void)hipFree(v->colour);
     if (v->rgb_buf) (void)hipFree(v->rgb_buf);
     if (v->fuse_scratch) (void)hipFree(v->fuse_scratch);
+    if (v->rays_scratch) (void)hipFree(v->rays_scratch);
     delete v;
     return TSDF_OK;
 }

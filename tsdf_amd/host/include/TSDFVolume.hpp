@@ -135,6 +135,17 @@ public:
     // matrix entry).
     uint64_t fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_src);
 
+    // Ray integration (include/tsdf_amd.h, "ray integration"; not in the reference's class): fuses a LiDAR scan or a point cloud --
+    // ray i runs from its origin (origins holds one sensor position for all, or one per point) to points[i], world mm in the frame of
+    // ray-cast and mesh vertices.  Every voxel the rays cross takes the mean of their observations as one observation (weight + 1);
+    // band_only: only within the truncation distance of each point.  Rays shorter than min_range or longer than max_range are left
+    // out.  Returns the number of voxels updated.  Throws std::invalid_argument on the refusals (origins neither one nor one per
+    // point, more than 2^23 points, a Z-slab, materialised deformation nodes).
+    uint64_t integrate_rays(const std::vector<float3> &origins, const std::vector<float3> &points, bool band_only = false,
+                            float min_range = 0.0f, float max_range = INFINITY);
+    // frees the scratch integrate_rays keeps between calls (8 bytes per voxel)
+    void release_ray_scratch();
+
     // Field alignment (include/tsdf_amd.h, "field alignment"; not in the reference's class): the rigid pose that puts `points` on this
     // volume's surface -- `iterations` Gauss-Newton steps on the squared field distance from T0 (points' frame -> the frame of ray-cast
     // and mesh vertices), points further than `gate` (<= 0: the truncation distance) from the surface left out.  residual / inliers

@@ -222,6 +222,18 @@ uint64_t TSDFVolume::fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_s
     return fused;
 }
 
+uint64_t TSDFVolume::integrate_rays(const std::vector<float3> &origins, const std::vector<float3> &points, bool band_only, float min_range,
+                                    float max_range) {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    uint64_t updated = 0;
+    check(tsdf_integrate_rays(m_handle, points.size(), reinterpret_cast<const float *>(origins.data()), origins.size(),
+                              reinterpret_cast<const float *>(points.data()), min_range, max_range, band_only ? TSDF_RAYS_BAND_ONLY : 0, &updated),
+          "Ray integration failed");
+    return updated;
+}
+
+void TSDFVolume::release_ray_scratch() { check(tsdf_volume_release_ray_scratch(m_handle), "Couldn't release the ray scratch"); }
+
 void TSDFVolume::weight_cap(uint32_t cap) { check(tsdf_volume_set_weight_cap(m_handle, cap), "Couldn't set the weight cap"); }
 
 uint32_t TSDFVolume::weight_cap() const {
