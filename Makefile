@@ -59,7 +59,7 @@ oracle:
 	$(MAKE) -C oracle -s all
 
 # C++ test program of the class surface (run by tests/test_cpp_surface.py on the GPU box)
-cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_rays build/test_fuse build/test_align build/test_integrate_rays build/kinfu_stream
+cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_rays build/test_fuse build/test_align build/test_integrate_rays build/test_rays_colour build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
 build/kinfu_stream: tools/kinfu_stream.cpp $(LIBDIR)/libtsdf_host.so include/tsdf_amd.h
@@ -104,6 +104,11 @@ build/test_align: tests/cpp/test_align.cpp $(LIBDIR)/libtsdf_host.so
 build/test_integrate_rays: tests/cpp/test_integrate_rays.cpp $(LIBDIR)/libtsdf_host.so
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_integrate_rays.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
+
+# C++ check of coloured ray integration and coloured ray queries through the class surface (run by tests/test_cpp_rays_colour.py on the GPU box)
+build/test_rays_colour: tests/cpp/test_rays_colour.cpp $(LIBDIR)/libtsdf_host.so
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_rays_colour.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
 clean:
 	rm -f $(HIP_OBJS) $(HOST_OBJS) $(LIBDIR)/*.so

@@ -322,6 +322,8 @@ int tsdf_deintegrate_device(tsdf_volume *volume, const uint16_t *device_depth, u
  *   Refused (TSDF_ERR_INVALID, with a message): enabling colour on a Z-slab volume (tsdf_volume_create_slab); colour integrate on a
  *     volume whose deformation nodes are explicit (tsdf_volume_deformation / tsdf_volume_set_deformation); colour integrate,
  *     sampling or data access on a volume without colour enabled.
+ *   Ray sets: tsdf_integrate_rays_colour* ("ray integration", rules 9 - 12) fuses a colour per point, tsdf_volume_cast_rays_colour*
+ *     ("ray queries") reads the colour at the hits of arbitrary rays.
  *   Out of scope: slab (multi-GPU) colour, in a volume or a sharded pipeline; colour sampled inside the cast kernels; trilinear colour
  *     interpolation; colour with explicit deformation nodes; RGB cameras with intrinsics or extrinsics of their own. */
 int tsdf_volume_enable_colour(tsdf_volume *volume, int enabled);   /* 1: allocate zeroed (kept if already enabled), 0: free */
@@ -424,8 +426,14 @@ int tsdf_raycast_gradient_normals_device(const tsdf_volume *volume, uint32_t wid
  *     by, and waits for the volume's stream once -- so that one query blocks, also through the device entry point, and until the next
  *     cell-parallel cast tsdf_volume_last_cell_list reports that count, not the list of a cast.
  *   Output order is input order; the rays are not sorted.
- *   Out of scope: slab or multi-GPU volumes, rays in the deformed space, colour at the hits (tsdf_volume_sample_colours_device takes
- *     the hit points). */
+ *   Colour at the hits (tsdf_volume_cast_rays_colour*): tsdf_volume_cast_rays* with the same arguments -- points, t and normals come out
+ *     bit for bit -- and then, one thread per ray on the same stream, rgb[3i..3i+2]: with q = points[i] - offset (the CURRENT offset),
+ *     if valid(q) in the sense of "field queries", the voxel (int)floorf(q[k] / voxel_size[k]) -- the one whose weight a field query
+ *     reports -- gives its {r, g, b} if its n > 0; (0, 0, 0) on a miss, when q is not valid, when an index reaches size[k], or when
+ *     n == 0.  This is the ray frame, the one rule 9 of "ray integration" writes in: nothing is done with offset_at_clear.  It equals
+ *     tsdf_volume_sample_colours_device (which subtracts offset_at_clear) wherever offset_at_clear is zero.  Refused as well: a volume
+ *     without colour enabled, NULL rgb, NULL points (the sample needs them).
+ *   Out of scope: slab or multi-GPU volumes, rays in the deformed space, trilinear colour. */
 /* Device pointers; any of the three outputs may be NULL, not all.  Asynchronous on the volume's stream, like tsdf_raycast_device
  * (and like it synchronising once after a bulk change of the distances: see "Side effects"). */
 int tsdf_volume_cast_rays_device(const tsdf_volume *volume, uint64_t n, const float *device_origins, const float *device_directions,
@@ -434,6 +442,12 @@ int tsdf_volume_cast_rays_device(const tsdf_volume *volume, uint64_t n, const fl
 /* The same on host arrays, on the volume's stream; blocking. */
 int tsdf_volume_cast_rays(const tsdf_volume *volume, uint64_t n, const float *host_origins, const float *host_directions,
                           const float *host_t_max, float *host_points, float *host_t, float *host_normals);
+/* The two calls above with the colour at every hit (3 n bytes); points and rgb must be given.  See "Colour at the hits". */
+int tsdf_volume_cast_rays_colour_device(const tsdf_volume *volume, uint64_t n, const float *device_origins,
+                                        const float *device_directions, const float *device_t_max /* or NULL */, float *device_points,
+                                        float *device_t, float *device_normals, uint8_t *device_rgb);
+int tsdf_volume_cast_rays_colour(const tsdf_volume *volume, uint64_t n, const float *host_origins, const float *host_directions,
+                                 const float *host_t_max, float *host_points, float *host_t, float *host_normals, uint8_t *host_rgb);
 
 /* ---- volume fusion (no reference counterpart: the reference's volume is filled from depth frames only) ------------------------------ */
 /* Resamples the field of `src` onto the grid of `dst` through a rigid transform and blends it in: merging a second session's volume or
@@ -505,25 +519,53 @@ int tsdf_volume_last_fuse_bricks(const tsdf_volume *dst, uint32_t *listed_bricks
  *   8. Apply, for every voxel with n_v >= 1: m = (float)(((double)S_v / (double)n_v) * ((double)trunc * (1.0 / 32768.0))) (double);
  *      d' = ((d * w) + m) / (w + 1) with IEEE division; w' = w + 1, stored as min(w + 1, cap) under tsdf_volume_set_weight_cap (the
  *      divisor stays w + 1).  Every other voxel keeps its distance and weight bit for bit.
- * Left alone: colour; a prepared integrate (tsdf_integrate_prepare_device_tiles) is neither used nor discarded; explicit deformation
- *   nodes are refused, not ignored.  The ray caster's summary is handed over as tsdf_volume_mark_dirty does: the next cast rebuilds
- *   it from the distances.  The call does not count towards the periodic tightening of that summary.
+ * Coloured (tsdf_integrate_rays_colour*): the plain call plus a colour update.  Distances, weights, the weight storage, the weight cap,
+ * updated_voxels and the occupancy hand-over come out with exactly the bits tsdf_integrate_rays* produces for the same arguments.
+ *   9. Colour observation: rgb[3i..3i+2] is the colour of points[i].  A visited voxel takes a colour observation from ray i iff rule 6
+ *      gave it an observation and its UNCLAMPED sdf also satisfies sdf <= trunc: the depth path's band -trunc <= sdf <= +trunc
+ *      ("colour fusion").  Free space in front of the surface is carved but keeps its colour.  The test is on sdf, not on q:
+ *      q == 32768 is also reached by rounding from below trunc.
+ *  10. Accumulation: per voxel, over the call's rays, the count c_v of colour observations and the exact integer sums R_v, G_v, B_v of
+ *      their channels.  Integer sums have no order.
+ *  11. One call is one colour observation: for every voxel with c_v >= 1, per channel in unsigned 64-bit arithmetic,
+ *      m = (2 * SUM_v + c_v) / (2 * c_v) -- the mean rounded half up, so m <= 255.
+ *  12. Blend: with old = {r, g, b, n} of that voxel's colour word, the depth path's blend in uint32 per channel:
+ *      new = (old * n + m + ((n + 1) >> 1)) / (n + 1), n' = min(n + 1, 255).  Every other colour word keeps its bits.
+ *   Which word: the colour word has the index of the distance the same call updates -- the cell (x, y, z) of rule 5 -- and nothing is
+ *     done with offset_at_clear.  (tsdf_volume_sample_colours_device subtracts offset_at_clear and this does not: the two agree
+ *     wherever offset_at_clear is zero; tsdf_volume_cast_rays_colour* reads in this frame.)
+ *   Refused as well (TSDF_ERR_INVALID, with a message, nothing written): a volume without colour enabled; NULL rgb with n > 0.
+ *   Scratch: the first coloured call adds 16 bytes per voxel (2 GiB at 512^3 on top of the plain 1 GiB), allocated zeroed, all zero
+ *     again whenever a call ends, freed by tsdf_volume_release_ray_scratch or with the volume.  tsdf_integrate_rays* never allocates
+ *     or touches it.  tsdf_volume_ray_scratch_bytes reports what is held (0 when none).
+ * Left alone by tsdf_integrate_rays*: colour.  By both: a prepared integrate (tsdf_integrate_prepare_device_tiles) is neither used nor
+ *   discarded; explicit deformation nodes are refused, not ignored.  The ray caster's summary is handed over as tsdf_volume_mark_dirty
+ *   does: the next cast rebuilds it from the distances.  The call does not count towards the periodic tightening of that summary.
  * Scratch: 8 bytes per voxel (1 GiB at 512^3) plus one byte per 64 x 4 x 32-voxel brick, allocated zeroed by the first call, all zero
  *   again whenever a call ends, kept until tsdf_volume_destroy or tsdf_volume_release_ray_scratch.
  * Refused (TSDF_ERR_INVALID, with a message, nothing written): a NULL volume; unknown flag bits; n_origins neither 1 nor n; n > 2^23
  *   (S_v then fits 40 bits beside a 24-bit count in one 64-bit word); NULL points or origins with n > 0; a Z-slab
  *   (tsdf_volume_create_slab); a materialised deformation-node array (voxel centres must be the implicit grid, as for
  *   tsdf_volume_fuse).  n == 0 is TSDF_OK and changes nothing.
- * Out of scope: taking a ray set back out (tsdf_deintegrate* has no ray counterpart: the mean of a call's observations is not kept),
- *   colour, slab or multi-GPU volumes, rays in the deformed space. */
+ * Out of scope: taking a ray set back out, coloured or not (tsdf_deintegrate* has no ray counterpart: the mean of a call's observations
+ *   is not kept), colour through tsdf_volume_fuse, trilinear colour, a brick-sparse scratch, slab or multi-GPU volumes, rays in the
+ *   deformed space. */
 #define TSDF_RAYS_BAND_ONLY 1   /* update only within trunc of the end point: no free-space carving */
 int tsdf_integrate_rays_device(tsdf_volume *volume, uint64_t n, const float *device_origins, uint64_t n_origins,
                                const float *device_points, float min_range, float max_range, int flags, uint64_t *updated_voxels);
 /* The same on host arrays, on the volume's stream; blocking. */
 int tsdf_integrate_rays(tsdf_volume *volume, uint64_t n, const float *host_origins, uint64_t n_origins, const float *host_points,
                         float min_range, float max_range, int flags, uint64_t *updated_voxels);
-/* Frees the scratch of the two calls above (synchronises the volume's stream); the next call allocates it again. */
+/* The two calls above with the colour of every point (3 n bytes): rules 9 - 12. */
+int tsdf_integrate_rays_colour_device(tsdf_volume *volume, uint64_t n, const float *device_origins, uint64_t n_origins,
+                                      const float *device_points, const uint8_t *device_rgb /* 3 n bytes */, float min_range,
+                                      float max_range, int flags, uint64_t *updated_voxels);
+int tsdf_integrate_rays_colour(tsdf_volume *volume, uint64_t n, const float *host_origins, uint64_t n_origins, const float *host_points,
+                               const uint8_t *host_rgb, float min_range, float max_range, int flags, uint64_t *updated_voxels);
+/* Frees the scratch of the four calls above (synchronises the volume's stream); the next call allocates it again. */
 int tsdf_volume_release_ray_scratch(tsdf_volume *volume);
+/* The bytes of ray-integration scratch the volume holds right now; 0 when none is held. */
+int tsdf_volume_ray_scratch_bytes(const tsdf_volume *volume, uint64_t *bytes);
 
 /* ---- field alignment (no reference counterpart: nothing in the reference produces a transform from the field itself) --------------- */
 /* The rigid pose that puts a point set on the zero level of the fused field: Gauss-Newton on sum S(T x)^2, which is point-to-plane ICP

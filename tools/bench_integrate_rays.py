@@ -14,7 +14,13 @@ the world frame by the camera's pose) and are fused as rays from the camera cent
 
 Medians of --reps calls, the four variants alternating.  Every call adds an observation to the volume, as a stream of frames does.
 
-    python tools/bench_integrate_rays.py [--size 512] [--frames 24] [--reps 30] [--warmup 5] [--scatter-us rays,band,shuffled]
+--colour: the volume is colour-enabled (the frames before the measurement are fused with their colour frames), every point carries the
+colour of its pixel in synth.colour_frame, and two variants join the alternation (default output profiles/integrate_rays_colour_bench.json):
+
+  colour_rays_ms       tsdf_integrate_rays_colour_device of the same rays with those colours, beside rays_ms, the plain call of the same run
+  integrate_colour_ms  the second yardstick: tsdf_integrate_colour_device of the same depth and colour frame
+
+    python tools/bench_integrate_rays.py [--colour] [--size 512] [--frames 24] [--reps 30] [--warmup 5] [--scatter-us rays,band,shuffled]
 """
 import argparse
 import json
@@ -34,8 +40,11 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scatter-us", default="", help="rays_scatter_kernel's time per variant from a kernel trace: rays,band_only,shuffled")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "integrate_rays_bench.json"))
+    ap.add_argument("--colour", action="store_true", help="a colour-enabled volume; adds the coloured call and the depth colour integrate")
+    ap.add_argument("--out", default=None, help="default: profiles/integrate_rays_bench.json, with --colour profiles/integrate_rays_colour_bench.json")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "integrate_rays_colour_bench.json" if a.colour else "integrate_rays_bench.json")
 
     import torch
     import tsdf_amd
@@ -47,9 +56,14 @@ def main():
     n = a.size
     vol = tsdf_amd.TSDFVolume((n,) * 3, (3000.0,) * 3)
     vol.set_stream(stream.cuda_stream)
+    if a.colour:
+        vol.enable_colour(True)
     for i in range(a.frames):
         d, cam = synth.depth_frame(i, PERIOD, seed=SEED)
-        vol.integrate(d, W, H, cam)
+        if a.colour:
+            vol.integrate_colour(d, synth.colour_frame(i, PERIOD, seed=SEED)[0], W, H, cam)
+        else:
+            vol.integrate(d, W, H, cam)
     vol.synchronize()
     depth, cam = synth.depth_frame(a.frames, PERIOD, seed=SEED)
     depth_dev = torch.from_numpy(depth.view(np.int16).copy()).to(dev)
@@ -60,6 +74,9 @@ def main():
         points = (cam_points @ pose[:3, :3].T + pose[:3, 3]).contiguous()
         origin = pose[:3, 3].contiguous()
         shuffled = points[torch.randperm(W * H, device=dev, generator=torch.Generator(device=dev).manual_seed(1))].contiguous()
+        if a.colour:
+            # point i is pixel i (tsdf_depth_to_points_device with stride 1 keeps the image's order): its colour is that pixel's
+            rgb_dev = torch.from_numpy(np.ascontiguousarray(synth.colour_frame(a.frames, PERIOD, seed=SEED)[0], dtype=np.uint8)).to(dev)
     stream.synchronize()
 
     info = vol.info()
@@ -101,6 +118,9 @@ def main():
         "shuffled": lambda: vol.integrate_rays_device(W * H, origin.data_ptr(), 1, shuffled.data_ptr()),
         "integrate": lambda: vol.integrate_device(depth_dev.data_ptr(), W, H, cam),
     }
+    if a.colour:
+        variants["colour_rays"] = lambda: vol.integrate_rays_device(W * H, origin.data_ptr(), 1, points.data_ptr(), rgb=rgb_dev.data_ptr())
+        variants["integrate_colour"] = lambda: vol.integrate_colour_device(depth_dev.data_ptr(), rgb_dev.data_ptr(), W, H, cam)
     times = {k: [] for k in variants}
     for rep in range(a.warmup + a.reps):
         for k, fn in variants.items():
@@ -110,12 +130,18 @@ def main():
 
     out = {"tool": "bench_integrate_rays", "size": n, "width": W, "height": H, "seed": "0x%X" % SEED, "frames_fused": a.frames,
            "reps": a.reps, "rays": W * H, "weight_storage_bits": vol.weight_storage()[0], "device": torch.cuda.get_device_name(0),
-           "truncation_mm": round(trunc, 3), "scratch_bytes": 8 * n ** 3}
+           "truncation_mm": round(trunc, 3), "scratch_bytes": vol.ray_scratch_bytes(), "colour": bool(a.colour)}
     for k, ts in times.items():
         out[k + "_ms"] = round(float(np.median(ts)), 4)
         out[k + "_ms_range"] = [round(min(ts), 4), round(max(ts), 4)]
     for k in ("rays", "band_only", "shuffled"):
         out[k + "_over_integrate"] = round(out[k + "_ms"] / out["integrate_ms"], 3)
+    if a.colour:
+        out["colour_rays_over_rays"] = round(out["colour_rays_ms"] / out["rays_ms"], 3)
+        out["colour_rays_over_integrate_colour"] = round(out["colour_rays_ms"] / out["integrate_colour_ms"], 3)
+        # per repetition the coloured call over the plain call next to it: the observed range of k in "coloured = plain x k"
+        ks = [c / p for c, p in zip(times["colour_rays"], times["rays"])]
+        out["colour_rays_over_rays_range"] = [round(min(ks), 3), round(max(ks), 3)]
     live, total = visits(False)
     live_b, total_b = visits(True)
     out["rays_not_skipped"] = live
@@ -126,7 +152,7 @@ def main():
         out["scatter_us_from_kernel_trace"] = dict(zip(("rays", "band_only", "shuffled"), us))
         out["atomics_per_s"] = {"rays": round(total / (us[0] * 1e-6), -6), "band_only": round(total_b / (us[1] * 1e-6), -6),
                                 "shuffled": round(total / (us[2] * 1e-6), -6)}
-    out["note"] = ("medians of event-bracketed asynchronous calls on one stream, the four variants alternating; the first ray call's "
+    out["note"] = ("medians of event-bracketed asynchronous calls on one stream, the variants alternating; the first ray call's "
                    "allocation and zeroing of the scratch is in the warm-up; visits are an estimate in float64 (an upper bound of the "
                    "atomics: a visited voxel more than trunc behind the point adds nothing)")
     vol.close()

@@ -129,11 +129,16 @@ _SIGS = {
     "tsdf_raycast_gradient_normals_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_volume_cast_rays_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsdf_volume_cast_rays": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsdf_volume_cast_rays_colour_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tsdf_volume_cast_rays_colour": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsdf_volume_fuse": (_i, [_vp, _vp, _fp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_last_fuse_bricks": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tsdf_integrate_rays_device": (_i, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _f, _f, _i, C.POINTER(C.c_uint64)]),
     "tsdf_integrate_rays": (_i, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _f, _f, _i, C.POINTER(C.c_uint64)]),
     "tsdf_volume_release_ray_scratch": (_i, [_vp]),
+    "tsdf_integrate_rays_colour_device": (_i, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _f, _f, _i, C.POINTER(C.c_uint64)]),
+    "tsdf_integrate_rays_colour": (_i, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _f, _f, _i, C.POINTER(C.c_uint64)]),
+    "tsdf_volume_ray_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_aligner_create": (_i, [C.POINTER(_vp)]),
     "tsdf_aligner_destroy": (None, [_vp]),
     "tsdf_aligner_set_stream": (_i, [_vp, _vp]),

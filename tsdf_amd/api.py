@@ -389,19 +389,25 @@ class TSDFVolume:
         return V, self.sample_field(V, weight=False, unit_gradient=True)[1]
 
     # ---- ray queries (include/tsdf_amd.h, "ray queries"; not in the reference's class)
-    def cast_rays_device(self, n, origins_ptr, directions_ptr, t_max_ptr, points_ptr, t_ptr, normals_ptr):
+    def cast_rays_device(self, n, origins_ptr, directions_ptr, t_max_ptr, points_ptr, t_ptr, normals_ptr, colours_ptr=None):
         """n rays (origins and directions 3 float32 each, t_max n float32 or None; device) -> points (3 n), t (n), normals (3 n): device
-        pointers, any of the three outputs may be None, not all.  Asynchronous on the volume's stream."""
+        pointers, any of the three outputs may be None, not all.  colours_ptr (3 n bytes, device): also the colour of the voxel each
+        hit lies in, (0, 0, 0) on a miss; needs colour enabled and the points.  Asynchronous on the volume's stream."""
         ptr = lambda p: C.c_void_p(int(p)) if p else None
-        check(lib.tsdf_volume_cast_rays_device(self._h, int(n), ptr(origins_ptr), ptr(directions_ptr), ptr(t_max_ptr), ptr(points_ptr),
-                                               ptr(t_ptr), ptr(normals_ptr)))
+        if colours_ptr is None:
+            check(lib.tsdf_volume_cast_rays_device(self._h, int(n), ptr(origins_ptr), ptr(directions_ptr), ptr(t_max_ptr),
+                                                   ptr(points_ptr), ptr(t_ptr), ptr(normals_ptr)))
+        else:
+            check(lib.tsdf_volume_cast_rays_colour_device(self._h, int(n), ptr(origins_ptr), ptr(directions_ptr), ptr(t_max_ptr),
+                                                          ptr(points_ptr), ptr(t_ptr), ptr(normals_ptr), ptr(colours_ptr)))
 
-    def cast_rays(self, origins, directions, t_max=None, normals=False, normalise=False):
+    def cast_rays(self, origins, directions, t_max=None, normals=False, normalise=False, colours=False):
         """(n, 3) float32 origins and directions (world mm, the frame of ray-cast and mesh vertices) -> (points (n, 3), t (n,)[,
         normals (n, 3)]), float32: where each ray first meets the surface, marched as the image cast marches a pixel's ray -- the
         direction is used as given, t is the hit's ray parameter in units of it -- NaN on a miss.  t_max (n,): a hit counts only if
         t <= t_max.  normals: the unit gradient of the field at the hit.  normalise: divide each direction by its fp32 length first,
-        so t is in millimetres."""
+        so t is in millimetres.  colours: the (n, 3) uint8 colour of the voxel each hit lies in ((0, 0, 0) on a miss) is appended to
+        the tuple; needs colour enabled."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         n = len(o)
@@ -418,10 +424,15 @@ class TSDFVolume:
         p = np.empty((n + 1, 3), np.float32)
         t = np.empty(n + 1, np.float32)
         g = np.empty((n + 1, 3), np.float32) if normals else None
-        check(lib.tsdf_volume_cast_rays(self._h, n, o.ctypes.data if n else None, d.ctypes.data if n else None,
-                                        m.ctypes.data if (m is not None and n) else None, p.ctypes.data, t.ctypes.data,
-                                        g.ctypes.data if normals else None))
-        return (p[:n], t[:n], g[:n]) if normals else (p[:n], t[:n])
+        args = (self._h, n, o.ctypes.data if n else None, d.ctypes.data if n else None, m.ctypes.data if (m is not None and n) else None,
+                p.ctypes.data, t.ctypes.data, g.ctypes.data if normals else None)
+        out = (p[:n], t[:n], g[:n]) if normals else (p[:n], t[:n])
+        if not colours:
+            check(lib.tsdf_volume_cast_rays(*args))
+            return out
+        c = np.zeros((n + 1, 3), np.uint8)
+        check(lib.tsdf_volume_cast_rays_colour(*args, c.ctypes.data))
+        return out + (c[:n],)
 
     def visible(self, a, b):
         """(n, 3) points a and b -> bool (n,): True where no surface lies between them -- the ray from a along the normalised b - a
@@ -462,19 +473,27 @@ class TSDFVolume:
         return int(listed.value), int(total.value)
 
     # ---- ray integration (include/tsdf_amd.h, "ray integration"; not in the reference's class)
-    def integrate_rays_device(self, n, origins_ptr, n_origins, points_ptr, band_only=False, min_range=0.0, max_range=float("inf")):
+    def integrate_rays_device(self, n, origins_ptr, n_origins, points_ptr, band_only=False, min_range=0.0, max_range=float("inf"),
+                              rgb=None):
         """n rays on the device: origins (3 float32 each; n_origins = 1 for one sensor position, or n) and end points (3 n float32).
+        rgb: a device pointer to 3 n bytes, the colour of every point, fused into a colour-enabled volume with the distances.
         Asynchronous on the volume's stream; nothing is returned."""
         ptr = lambda p: C.c_void_p(int(p)) if p else None
-        check(lib.tsdf_integrate_rays_device(self._h, int(n), ptr(origins_ptr), int(n_origins), ptr(points_ptr), float(min_range),
-                                             float(max_range), _capi.TSDF_RAYS_BAND_ONLY if band_only else 0, None))
+        flags = _capi.TSDF_RAYS_BAND_ONLY if band_only else 0
+        if rgb is None:
+            check(lib.tsdf_integrate_rays_device(self._h, int(n), ptr(origins_ptr), int(n_origins), ptr(points_ptr), float(min_range),
+                                                 float(max_range), flags, None))
+        else:
+            check(lib.tsdf_integrate_rays_colour_device(self._h, int(n), ptr(origins_ptr), int(n_origins), ptr(points_ptr), ptr(rgb),
+                                                        float(min_range), float(max_range), flags, None))
 
-    def integrate_rays(self, origins, points, band_only=False, min_range=0.0, max_range=float("inf")):
+    def integrate_rays(self, origins, points, band_only=False, min_range=0.0, max_range=float("inf"), rgb=None):
         """Fuse a LiDAR scan or a point cloud: (n, 3) float32 end points (world mm, the frame of ray-cast and mesh vertices) measured from
         `origins`, (3,) for one sensor position or (n, 3).  Every voxel the rays cross takes the mean of their observations as ONE
         observation (weight + 1), free space in front of the points included; band_only: only within the truncation distance of each
-        point.  Rays shorter than min_range or longer than max_range are left out.  -> the number of voxels updated.  Raises ValueError
-        on the refusals."""
+        point.  Rays shorter than min_range or longer than max_range are left out.  rgb: (n, 3) uint8, the colour of every point: the
+        voxels within the truncation distance of a point also take the mean colour of their rays as one colour observation (the volume
+        needs colour enabled).  -> the number of voxels updated.  Raises ValueError on the refusals."""
         p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         o = np.ascontiguousarray(origins, dtype=np.float32)
         if o.ndim == 1 and o.size == 3:
@@ -483,13 +502,28 @@ class TSDFVolume:
             raise ValueError("integrate_rays: origins must be (3,) or (n, 3), got shape %s" % (o.shape,))
         n = len(p)
         updated = C.c_uint64()
-        check(lib.tsdf_integrate_rays(self._h, n, o.ctypes.data if n else None, len(o), p.ctypes.data if n else None, float(min_range),
-                                      float(max_range), _capi.TSDF_RAYS_BAND_ONLY if band_only else 0, C.byref(updated)))
+        flags = _capi.TSDF_RAYS_BAND_ONLY if band_only else 0
+        if rgb is None:
+            check(lib.tsdf_integrate_rays(self._h, n, o.ctypes.data if n else None, len(o), p.ctypes.data if n else None, float(min_range),
+                                          float(max_range), flags, C.byref(updated)))
+            return int(updated.value)
+        c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        if len(c) != n:
+            raise ValueError("integrate_rays: %d points, %d colours" % (n, len(c)))
+        check(lib.tsdf_integrate_rays_colour(self._h, n, o.ctypes.data if n else None, len(o), p.ctypes.data if n else None,
+                                             c.ctypes.data if n else None, float(min_range), float(max_range), flags, C.byref(updated)))
         return int(updated.value)
 
     def release_ray_scratch(self):
-        """Free the scratch integrate_rays keeps between calls (8 bytes per voxel); the next call allocates it again."""
+        """Free the scratch integrate_rays keeps between calls (8 bytes per voxel, 16 more once colours were fused); the next call
+        allocates it again."""
         check(lib.tsdf_volume_release_ray_scratch(self._h))
+
+    def ray_scratch_bytes(self):
+        """Bytes of scratch integrate_rays holds on the device right now (0 before the first call and after release_ray_scratch)."""
+        n = C.c_uint64()
+        check(lib.tsdf_volume_ray_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
 
     def occupancy(self):
         """(occupied, total) bricks of the ray caster's empty-space summary."""

@@ -375,6 +375,9 @@ struct tsdf_volume {
     // voxel; all zero between calls
     void *rays_scratch;
     size_t rays_scratch_cap;
+    // coloured ray integration: two 64-bit accumulators per voxel, allocated by the first coloured call only; all zero between calls
+    void *rays_colour_scratch;
+    size_t rays_colour_scratch_cap;
     size_t resident_voxels() const { return (size_t)g.X * g.Y * (g.z_store_end - g.z_store_begin); }
 };
 

@@ -1367,39 +1367,70 @@ int tsdf_volume_cast_rays_device(const tsdf_volume *v, uint64_t n, const float *
     return cast_rays(const_cast<tsdf_volume *>(v), n, device_origins, device_directions, device_t_max, device_points, device_t, device_normals);
 }
 
-int tsdf_volume_cast_rays(const tsdf_volume *cv, uint64_t n, const float *host_origins, const float *host_directions,
-                          const float *host_t_max, float *host_points, float *host_t, float *host_normals) {
-    const int rc0 = cast_rays_check(cv, n, host_origins, host_directions, host_points, host_t, host_normals);
-    if (rc0 != TSDF_OK) return rc0;
-    if (n == 0) return TSDF_OK;
+// the host variants: rays up, results down through one device buffer, blocking; host_rgb != nullptr: with the colour at the hits
+static int cast_rays_host(tsdf_volume *v, uint64_t n, const float *host_origins, const float *host_directions, const float *host_t_max,
+                          float *host_points, float *host_t, float *host_normals, uint8_t *host_rgb) {
     TSDF_REQUIRE(n <= ((uint64_t)1 << 40), "tsdf_volume_cast_rays: too many rays");
-    tsdf_volume *v = const_cast<tsdf_volume *>(cv);
-    // one allocation: origins (3n), directions (3n), then t_max (n), points (3n), t (n), normals (3n) as far as given / asked for
+    // one allocation: origins (3n), directions (3n), then t_max (n), points (3n), t (n), normals (3n) as far as given / asked for, then
+    // the colours (3n bytes)
     const size_t fn = (size_t)n;
     const size_t o_m = 6 * fn, o_p = o_m + (host_t_max ? fn : 0), o_t = o_p + (host_points ? 3 * fn : 0), o_n = o_t + (host_t ? fn : 0),
-                 total = o_n + (host_normals ? 3 * fn : 0);
+                 total = o_n + (host_normals ? 3 * fn : 0), bytes = total * sizeof(float) + (host_rgb ? 3 * fn : 0);
     float *buf = nullptr;
-    if (hipMalloc((void **)&buf, total * sizeof(float)) != hipSuccess) {
+    if (hipMalloc((void **)&buf, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("tsdf_volume_cast_rays: couldn't allocate %zu bytes for the rays and results", total * sizeof(float));
+        set_error("tsdf_volume_cast_rays: couldn't allocate %zu bytes for the rays and results", bytes);
         return TSDF_ERR_NOMEM;
     }
     float *m = host_t_max ? buf + o_m : nullptr, *p = host_points ? buf + o_p : nullptr, *t = host_t ? buf + o_t : nullptr,
           *nrm = host_normals ? buf + o_n : nullptr;
+    uint8_t *const rgb = host_rgb ? reinterpret_cast<uint8_t *>(buf + total) : nullptr;
     hipError_t e = hipMemcpyAsync(buf, host_origins, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(buf + 3 * fn, host_directions, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
     if (e == hipSuccess && m) e = hipMemcpyAsync(m, host_t_max, fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
     int rc = TSDF_OK;
     if (e == hipSuccess) rc = cast_rays(v, n, buf, buf + 3 * fn, m, p, t, nrm);
+    if (rc == TSDF_OK && e == hipSuccess && rgb) rc = cast_rays_colour(v, n, p, rgb);
     if (rc == TSDF_OK && e == hipSuccess && p) e = hipMemcpyAsync(host_points, p, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
     if (rc == TSDF_OK && e == hipSuccess && t) e = hipMemcpyAsync(host_t, t, fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
     if (rc == TSDF_OK && e == hipSuccess && nrm) e = hipMemcpyAsync(host_normals, nrm, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
+    if (rc == TSDF_OK && e == hipSuccess && rgb) e = hipMemcpyAsync(host_rgb, rgb, 3 * fn, hipMemcpyDeviceToHost, v->stream);
     const hipError_t es = hipStreamSynchronize(v->stream);   // (before the buffer goes, whatever happened)
     (void)hipFree(buf);
     if (rc != TSDF_OK) return rc;
     if (e != hipSuccess) return hip_fail(e, "Ray query failed");
     if (es != hipSuccess) return hip_fail(es, "Ray query failed");
     return TSDF_OK;
+}
+
+int tsdf_volume_cast_rays(const tsdf_volume *cv, uint64_t n, const float *host_origins, const float *host_directions,
+                          const float *host_t_max, float *host_points, float *host_t, float *host_normals) {
+    const int rc0 = cast_rays_check(cv, n, host_origins, host_directions, host_points, host_t, host_normals);
+    if (rc0 != TSDF_OK) return rc0;
+    if (n == 0) return TSDF_OK;
+    return cast_rays_host(const_cast<tsdf_volume *>(cv), n, host_origins, host_directions, host_t_max, host_points, host_t, host_normals,
+                          nullptr);
+}
+
+// ---- colour at the hits of a ray query (include/tsdf_amd.h, "ray queries") -----------------------------------------------------------
+int tsdf_volume_cast_rays_colour_device(const tsdf_volume *v, uint64_t n, const float *device_origins, const float *device_directions,
+                                        const float *device_t_max, float *device_points, float *device_t, float *device_normals,
+                                        uint8_t *device_rgb) {
+    int rc = cast_rays_colour_check(v, n, device_origins, device_directions, device_points, device_t, device_normals, device_rgb);
+    if (rc != TSDF_OK) return rc;
+    if (n == 0) return TSDF_OK;
+    rc = cast_rays(const_cast<tsdf_volume *>(v), n, device_origins, device_directions, device_t_max, device_points, device_t, device_normals);
+    if (rc != TSDF_OK) return rc;
+    return cast_rays_colour(v, n, device_points, device_rgb);
+}
+
+int tsdf_volume_cast_rays_colour(const tsdf_volume *cv, uint64_t n, const float *host_origins, const float *host_directions,
+                                 const float *host_t_max, float *host_points, float *host_t, float *host_normals, uint8_t *host_rgb) {
+    const int rc0 = cast_rays_colour_check(cv, n, host_origins, host_directions, host_points, host_t, host_normals, host_rgb);
+    if (rc0 != TSDF_OK) return rc0;
+    if (n == 0) return TSDF_OK;
+    return cast_rays_host(const_cast<tsdf_volume *>(cv), n, host_origins, host_directions, host_t_max, host_points, host_t, host_normals,
+                          host_rgb);
 }
 
 }  // extern "C"

@@ -180,3 +180,44 @@ static int cast_rays(tsdf_volume *v, uint64_t n, const float *origins, const flo
     TSDF_HIP(hipGetLastError(), "Ray query kernel failed");
     return TSDF_OK;
 }
+
+// ---- colour at the hits (tsdf_volume_cast_rays_colour*) ---------------------------------------------------------------------------------
+// One thread per ray, behind cast_rays_kernel on the same stream: q = points[i] - offset (the current offset: the ray frame, the one
+// coloured ray integration writes in); the voxel a field query reports the weight of, its {r, g, b} if its n > 0; (0, 0, 0) on a miss
+// (a NaN point is not valid), for an invalid q, where an index reaches the size, and for n == 0.
+template <bool FASTDIV>
+__global__ __launch_bounds__(256) void cast_rays_colour_kernel(const FieldView f, const uint32_t *__restrict__ colour, const uint64_t n_rays,
+                                                               const float *__restrict__ points, uint8_t *__restrict__ rgb) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_rays) return;
+    const float x = points[3 * i + 0] - f.g.offset.x, y = points[3 * i + 1] - f.g.offset.y, z = points[3 * i + 2] - f.g.offset.z;
+    uint32_t c = 0;
+    int vx, vy, vz;
+    if (field_valid(f, x, y, z) && field_voxel<FASTDIV>(f, x, y, z, vx, vy, vz)) {
+        const uint32_t w = colour[(size_t)f.tc.plane * (uint32_t)vz + (size_t)f.tc.row * (uint32_t)vy + (uint32_t)vx];
+        if (w >> 24) c = w;
+    }
+    rgb[3 * i + 0] = (uint8_t)c;
+    rgb[3 * i + 1] = (uint8_t)(c >> 8);
+    rgb[3 * i + 2] = (uint8_t)(c >> 16);
+}
+
+static int cast_rays_colour_check(const tsdf_volume *v, uint64_t n, const float *origins, const float *directions, const float *points,
+                                  const float *t, const float *normals, const uint8_t *rgb) {
+    const int rc = cast_rays_check(v, n, origins, directions, points, t, normals);
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(v->colour, "tsdf_volume_cast_rays_colour: colour is not enabled on this volume (tsdf_volume_enable_colour)");
+    TSDF_REQUIRE(rgb, "tsdf_volume_cast_rays_colour: null rgb");
+    TSDF_REQUIRE(points, "tsdf_volume_cast_rays_colour: null points (the colour is sampled at them)");
+    return TSDF_OK;
+}
+
+// the sample of n hit points on the volume's stream; v has passed cast_rays_colour_check, n > 0
+static int cast_rays_colour(const tsdf_volume *v, uint64_t n, const float *points, uint8_t *rgb) {
+    const FieldView f = make_field_view(v);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (v->fast_div) hipLaunchKernelGGL(cast_rays_colour_kernel<true>, grid, block, 0, v->stream, f, v->colour, n, points, rgb);
+    else hipLaunchKernelGGL(cast_rays_colour_kernel<false>, grid, block, 0, v->stream, f, v->colour, n, points, rgb);
+    TSDF_HIP(hipGetLastError(), "Ray query colour kernel failed");
+    return TSDF_OK;
+}

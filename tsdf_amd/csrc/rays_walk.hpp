@@ -1,7 +1,8 @@
 // Rules 1 - 6 of ray integration (include/tsdf_amd.h, "ray integration") for one ray: the decreed skips, the stretch, the clip to the grid,
 // the drift-free Amanatides-Woo walk, and per visited voxel the quantised observation handed to `observe(ix, iy, iz, q)`.  Host and
 // device: rays_scatter_kernel (integrate_rays.hip) runs it a lane per ray; compiled for the host it is the same arithmetic, every
-// fp32 operation rounded on its own (-ffp-contract=off).
+// fp32 operation rounded on its own (-ffp-contract=off).  rays_walk_sdf is the same walk handing `observe(ix, iy, iz, q, sdf)` the
+// unclamped sdf of rule 6 as well: the band test of rule 9 (rays_scatter_colour_kernel) is on it, not on q.
 #pragma once
 
 #include "common.hpp"
@@ -26,9 +27,9 @@ __host__ __device__ inline int rays_start_cell(float a, float t0, float s, uint3
 }
 
 template <class Observe>
-__host__ __device__ inline void rays_walk(const Geom &g, const float ox, const float oy, const float oz, const float px, const float py,
-                                          const float pz, const float min_range, const float max_range, const int band_only,
-                                          Observe &&observe) {
+__host__ __device__ inline void rays_walk_sdf(const Geom &g, const float ox, const float oy, const float oz, const float px, const float py,
+                                              const float pz, const float min_range, const float max_range, const int band_only,
+                                              Observe &&observe) {
     // rule 1
     if (!(rays_finite(ox) && rays_finite(oy) && rays_finite(oz) && rays_finite(px) && rays_finite(py) && rays_finite(pz))) return;
     const float dx = px - ox, dy = py - oy, dz = pz - oz;
@@ -63,7 +64,7 @@ __host__ __device__ inline void rays_walk(const Geom &g, const float ox, const f
             const float tsdf = sdf > 0.0f ? fminf(sdf, trunc) : sdf;
             const int q = (int)rintf((tsdf / trunc) * 32768.0f);
             // (ix, iy, iz) is inside the grid: the start cell is clamped, and a step that leaves the grid ends the walk below
-            observe(ix, iy, iz, q);
+            observe(ix, iy, iz, q, sdf);
         }
         int axis = -1;
         float best = 0.0f;
@@ -97,6 +98,13 @@ __host__ __device__ inline void rays_walk(const Geom &g, const float ox, const f
             if (iz < 0 || iz >= (int)g.Z) break;
         }
     }
+}
+
+template <class Observe>
+__host__ __device__ inline void rays_walk(const Geom &g, const float ox, const float oy, const float oz, const float px, const float py,
+                                          const float pz, const float min_range, const float max_range, const int band_only,
+                                          Observe &&observe) {
+    rays_walk_sdf(g, ox, oy, oz, px, py, pz, min_range, max_range, band_only, [&](int ix, int iy, int iz, int q, float) { observe(ix, iy, iz, q); });
 }
 
 }  // namespace tsdf

@@ -946,6 +946,7 @@ int tsdf_volume_destroy(tsdf_volume *v) {
     if (v->rgb_buf) (void)hipFree(v->rgb_buf);
     if (v->fuse_scratch) (void)hipFree(v->fuse_scratch);
     if (v->rays_scratch) (void)hipFree(v->rays_scratch);
+    if (v->rays_colour_scratch) (void)hipFree(v->rays_colour_scratch);
     delete v;
     return TSDF_OK;
 }

@@ -127,6 +127,11 @@ public:
     // a Z-slab and when origins, directions and t_max differ in length.
     void cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
                    std::vector<float> *t = nullptr, std::vector<float3> *normals = nullptr, const std::vector<float> *t_max = nullptr) const;
+    // the same with colours[i] = the {r, g, b} of the voxel hit i lies in, (0, 0, 0) on a miss; also throws std::invalid_argument
+    // while colour is off
+    void cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
+                   std::vector<uchar3> &colours, std::vector<float> *t = nullptr, std::vector<float3> *normals = nullptr,
+                   const std::vector<float> *t_max = nullptr) const;
 
     // Volume fusion (include/tsdf_amd.h, "volume fusion"; not in the reference's class): resamples the field of `src` onto this volume's
     // grid through the rigid transform dst_to_src (this volume's world frame -> src's) and blends it in, weights added; returns the
@@ -143,8 +148,15 @@ public:
     // point, more than 2^23 points, a Z-slab, materialised deformation nodes).
     uint64_t integrate_rays(const std::vector<float3> &origins, const std::vector<float3> &points, bool band_only = false,
                             float min_range = 0.0f, float max_range = INFINITY);
-    // frees the scratch integrate_rays keeps between calls (8 bytes per voxel)
+    // the same with rgb[i] the colour of points[i]: the voxels within the truncation distance of a point also take the mean colour of
+    // their rays as one colour observation (rules 9 - 12).  Also throws std::invalid_argument while colour is off and when rgb and
+    // points differ in length.
+    uint64_t integrate_rays(const std::vector<float3> &origins, const std::vector<float3> &points, const std::vector<uchar3> &rgb,
+                            bool band_only = false, float min_range = 0.0f, float max_range = INFINITY);
+    // frees the scratch integrate_rays keeps between calls (8 bytes per voxel, 16 more once colours were fused)
     void release_ray_scratch();
+    // the bytes of that scratch held right now
+    uint64_t ray_scratch_bytes() const;
 
     // Field alignment (include/tsdf_amd.h, "field alignment"; not in the reference's class): the rigid pose that puts `points` on this
     // volume's surface -- `iterations` Gauss-Newton steps on the squared field distance from T0 (points' frame -> the frame of ray-cast

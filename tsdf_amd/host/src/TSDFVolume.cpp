@@ -185,6 +185,30 @@ void TSDFVolume::cast_rays(const std::vector<float3> &origins, const std::vector
     if (normals) normals->resize(n);
 }
 
+void TSDFVolume::cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
+                           std::vector<uchar3> &colours, std::vector<float> *t, std::vector<float3> *normals,
+                           const std::vector<float> *t_max) const {
+    static_assert(sizeof(uchar3) == 3, "uchar3 must be 3 packed bytes");
+    const size_t n = origins.size();
+    if (directions.size() != n) throw std::invalid_argument("cast_rays: origins and directions differ in length");
+    if (t_max && t_max->size() != n) throw std::invalid_argument("cast_rays: t_max and the rays differ in length");
+    // (one element more than needed: data() of an empty vector may be null, which the C ABI refuses or reads as "not asked for")
+    points.assign(n + 1, float3{0.0f, 0.0f, 0.0f});
+    colours.assign(n + 1, uchar3{0, 0, 0});
+    if (t) t->assign(n + 1, 0.0f);
+    if (normals) normals->assign(n + 1, float3{0.0f, 0.0f, 0.0f});
+    check(tsdf_volume_cast_rays_colour(m_handle, n, reinterpret_cast<const float *>(origins.data()),
+                                       reinterpret_cast<const float *>(directions.data()), (t_max && n) ? t_max->data() : nullptr,
+                                       reinterpret_cast<float *>(points.data()), t ? t->data() : nullptr,
+                                       normals ? reinterpret_cast<float *>(normals->data()) : nullptr,
+                                       reinterpret_cast<uint8_t *>(colours.data())),
+          "Couldn't cast the rays");
+    points.resize(n);
+    colours.resize(n);
+    if (t) t->resize(n);
+    if (normals) normals->resize(n);
+}
+
 Eigen::Matrix4d TSDFVolume::align_points(const std::vector<float3> &points, const Eigen::Matrix4d &T0, uint32_t iterations, float gate,
                                          float *residual, float *inliers) const {
     static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
@@ -230,6 +254,24 @@ uint64_t TSDFVolume::integrate_rays(const std::vector<float3> &origins, const st
                               reinterpret_cast<const float *>(points.data()), min_range, max_range, band_only ? TSDF_RAYS_BAND_ONLY : 0, &updated),
           "Ray integration failed");
     return updated;
+}
+
+uint64_t TSDFVolume::integrate_rays(const std::vector<float3> &origins, const std::vector<float3> &points, const std::vector<uchar3> &rgb,
+                                    bool band_only, float min_range, float max_range) {
+    static_assert(sizeof(uchar3) == 3, "uchar3 must be 3 packed bytes");
+    if (rgb.size() != points.size()) throw std::invalid_argument("integrate_rays: points and rgb differ in length");
+    uint64_t updated = 0;
+    check(tsdf_integrate_rays_colour(m_handle, points.size(), reinterpret_cast<const float *>(origins.data()), origins.size(),
+                                     reinterpret_cast<const float *>(points.data()), reinterpret_cast<const uint8_t *>(rgb.data()), min_range,
+                                     max_range, band_only ? TSDF_RAYS_BAND_ONLY : 0, &updated),
+          "Ray integration failed");
+    return updated;
+}
+
+uint64_t TSDFVolume::ray_scratch_bytes() const {
+    uint64_t bytes = 0;
+    check(tsdf_volume_ray_scratch_bytes(m_handle, &bytes), "Couldn't query the ray scratch");
+    return bytes;
 }
 
 void TSDFVolume::release_ray_scratch() { check(tsdf_volume_release_ray_scratch(m_handle), "Couldn't release the ray scratch"); }
