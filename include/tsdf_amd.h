@@ -683,6 +683,65 @@ int tsdf_volume_get_occupancy_data(const tsdf_volume *volume, int force_rebuild,
 int tsdf_volume_marching_cubes(const tsdf_volume *volume, const int8_t *table, uint64_t *n_vertices, float *host_vertices,
                                uint64_t capacity);
 
+/* ---- indexed mesh (no reference counterpart: the reference's extract_surface emits a triangle soup) ------------------------------- */
+/* Marching cubes whose output is an indexed mesh that stays on the device: shared vertices, an index buffer, optionally a normal and a
+ * colour per shared vertex, of the whole grid or of a box of it.  Opt-in by being called: tsdf_volume_marching_cubes and everything
+ * else do exactly what they did.
+ *   Contract: let S be the soup tsdf_volume_marching_cubes emits (cubes x fastest, then y, then z), restricted to the marched cubes.
+ *     The mesh is (V, I):
+ *     V: one vertex per lattice edge that a marched cube uses.  A lattice edge is (x, y, z, a): the voxel at its lower end and its
+ *       axis (0, 1, 2 = x, y, z); it is used when its two ends differ in d < 0 (NaN and both zeros are not < 0) and at least one of the
+ *       up to four cubes round it is marched.  Sorted by the key ((z * Y + y) * X + x) * 3 + a, X, Y the WHOLE grid's sizes.  The
+ *       position is the 12 bytes the soup has for that edge: every cube round an edge computes the same bytes, because all twelve cube
+ *       edges run in the positive direction of an axis, corner positions depend on the absolute voxel coordinate only and interpolate()
+ *       orders its end points by sign.
+ *     I: one uint32 per soup vertex, in soup order, with V[I[k]] == S[k] bit for bit.  Triangle t is (I[3t], I[3t+2], I[3t+1]), the
+ *       wiring extract_surface uses.
+ *     Welding is by lattice edge, NOT by position: where a voxel is exactly 0 the crossings of several edges fall on the same point;
+ *       they stay distinct vertices, and the triangles between them stay as degenerate as the reference makes them.
+ *   Box: {x0, y0, z0, x1, y1, z1} marches the cubes rooted at voxels in [x0, x1) x [y0, y1) x [z0, z1); the ends are clipped to
+ *     X - 1, Y - 1, Z - 1 (tsdf_mesh_info.box has the box as clipped); NULL is the whole grid.  A begin that is not below its end on
+ *     some axis, before clipping, is refused; a box that clips to nothing gives an empty mesh, as does a grid with an axis shorter than
+ *     2.  The keys are the whole grid's, so an edge has the same bytes in every box that holds it, and boxes that tile the grid give,
+ *     cube for cube, the whole soup.
+ *   TSDF_MESH_NORMALS: one normal per vertex of V: the bytes tsdf_volume_sample_field_device(..., TSDF_FIELD_UNIT_GRADIENT) gives there
+ *     (NaN triples included).  TSDF_MESH_COLOURS: the 3 bytes tsdf_volume_sample_colours_device gives there; refused on a volume
+ *     without colour.  Both are those entry points, called on V on the volume's stream.
+ *   The handle owns the device arrays and its scratch and keeps them between extractions; they only grow, so a per-frame re-mesh into
+ *     a warm handle allocates nothing.  Scratch: 32 bytes per 64 voxels of the marched range (three 64-bit masks of used edges and two
+ *     bases; a vertex's index is a base plus popcounts, no per-edge index array exists), 16 bytes per 65536 voxels, the table:
+ *     tsdf_mesh_scratch_bytes <= 1 byte per voxel of the whole grid + 64 KiB, whatever the box.
+ *   Stream order: tsdf_volume_extract_mesh enqueues on the volume's stream, synchronises it once (to size the arrays from the counts)
+ *     and returns with the kernels that fill the arrays enqueued.  tsdf_mesh_buffers and tsdf_mesh_download wait for them; a later
+ *     extraction into the same handle is ordered behind them.  A handle is used by one thread at a time, on the device it was made on.
+ *   The result is the same arrays on every run: no atomics, nothing depends on the order in which waves finish.  The volume is not
+ *     written: no distance, weight, occupancy flag, dirty mark or ray-cast state.
+ *   Refused (TSDF_ERR_INVALID, with a message): NULL volume, table or mesh; a Z-slab volume (tsdf_volume_create_slab:
+ *     tsdf_volume_marching_cubes serves those); a table tsdf_volume_marching_cubes refuses; unknown flags; more than 2^32 - 1 vertices
+ *     or indices (extract in boxes); tsdf_mesh_download into an array the mesh was extracted without.
+ *   Out of scope: slab volumes, skipping empty rows by the occupancy flags (their "low voxel" is not the sign test), welding by
+ *     position, simplification. */
+typedef struct tsdf_mesh tsdf_mesh;
+#define TSDF_MESH_NORMALS 1u
+#define TSDF_MESH_COLOURS 2u
+typedef struct tsdf_mesh_info {
+    uint64_t n_vertices, n_indices;
+    uint32_t flags;
+    uint32_t box[6];   /* as clipped */
+} tsdf_mesh_info;
+int tsdf_mesh_create(tsdf_mesh **out);   /* on the current device */
+void tsdf_mesh_destroy(tsdf_mesh *mesh);
+int tsdf_volume_extract_mesh(const tsdf_volume *volume, const int8_t *table, const uint32_t box[6], uint32_t flags, tsdf_mesh *mesh);
+int tsdf_mesh_get_info(const tsdf_mesh *mesh, tsdf_mesh_info *info);
+/* The device arrays of the last extraction: 3 floats per vertex, one uint32 per index, 3 floats / 3 bytes per vertex.  Any out pointer
+ * may be NULL; an array the mesh lacks (or any array of an empty mesh) gives NULL.  Valid until the next extraction into the handle. */
+int tsdf_mesh_buffers(const tsdf_mesh *mesh, const float **device_vertices, const uint32_t **device_indices,
+                      const float **device_normals, const uint8_t **device_rgb);
+/* Blocking copies to host arrays sized from tsdf_mesh_get_info; any may be NULL. */
+int tsdf_mesh_download(const tsdf_mesh *mesh, float *host_vertices, uint32_t *host_indices, float *host_normals, uint8_t *host_rgb);
+/* Device bytes the handle holds besides the four output arrays. */
+int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
+
 /* Multi-GPU raycast: a slab evaluates only the samples whose lower trilinear tap plane it owns and writes
  * one 8-byte record per pixel: k = index of the first owned sample with tsdf <= 0 (TSDF_NO_HIT if none), t = that sample's
  * refined ray parameter (src/RayCaster/GPURaycaster.cu:338-341).  After an all-gather of the records (layout

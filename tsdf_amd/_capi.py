@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("TSDF_HIP_LIB") or os.path.join(_HERE, "lib", "libtsdf
 TSDF_OK, TSDF_ERR_INVALID, TSDF_ERR_DEVICE, TSDF_ERR_NOMEM = 0, 1, 2, 3
 TSDF_FIELD_UNIT_GRADIENT = 1
 TSDF_RAYS_BAND_ONLY = 1
+TSDF_MESH_NORMALS, TSDF_MESH_COLOURS = 1, 2
 
 
 class TsdfError(RuntimeError):
@@ -28,6 +29,11 @@ class VolumeInfo(C.Structure):
                 ("max_weight", C.c_float), ("global_translation", C.c_float * 3),
                 ("global_rotation", C.c_float * 3), ("deformation_materialised", C.c_int32),
                 ("fast_division_verified", C.c_int32)]
+
+
+class MeshInfo(C.Structure):
+    """struct tsdf_mesh_info (include/tsdf_amd.h)."""
+    _fields_ = [("n_vertices", C.c_uint64), ("n_indices", C.c_uint64), ("flags", C.c_uint32), ("box", C.c_uint32 * 6)]
 
 
 class AlignStage(C.Structure):
@@ -160,6 +166,13 @@ _SIGS = {
     "tsdf_vertices_to_depth_device": (_i, [_u32, _u32, _vp, _vp, _vp, _vp]),
     "tsdf_raycast_depth_device": (_i, [_vp, _u32, _u32, _fp, _fp, _fp, _vp, _vp]),
     "tsdf_volume_marching_cubes": (_i, [_vp, _vp, _vp, _vp, C.c_uint64]),
+    "tsdf_mesh_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_mesh_destroy": (None, [_vp]),
+    "tsdf_volume_extract_mesh": (_i, [_vp, _vp, C.POINTER(_u32), _u32, _vp]),
+    "tsdf_mesh_get_info": (_i, [_vp, C.POINTER(MeshInfo)]),
+    "tsdf_mesh_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_mesh_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tsdf_mesh_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_merge_hits_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_merge_hits_normals_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_slab_exchange_unique_id": (_i, [_vp, C.c_char_p]),

@@ -388,6 +388,22 @@ class TSDFVolume:
         V = self.extract_surface()
         return V, self.sample_field(V, weight=False, unit_gradient=True)[1]
 
+    # ---- indexed mesh (include/tsdf_amd.h, "indexed mesh"; not in the reference's class)
+    def extract_mesh(self, box=None, normals=False, colours=False, into=None):
+        """The surface as an indexed mesh that stays on the device (tsdf_volume_extract_mesh): one vertex per lattice edge the surface
+        crosses, one index per vertex of extract_surface()'s soup, vertices[indices] being that soup bit for bit.  box = (x0, y0, z0,
+        x1, y1, z1) marches the cubes rooted in [x0, x1) x [y0, y1) x [z0, z1) only (ends clipped to the grid); normals / colours: the
+        unit gradient (sample_field) / the colour (sample_colours) at every shared vertex.  `into`: a Mesh to reuse -- its device
+        arrays are kept and only grow.  Returns the Mesh."""
+        mesh = Mesh() if into is None else into
+        b = None
+        if box is not None:
+            b = (C.c_uint32 * 6)(*[int(v) for v in box])
+        flags = (_capi.TSDF_MESH_NORMALS if normals else 0) | (_capi.TSDF_MESH_COLOURS if colours else 0)
+        table = marching_cubes_table()
+        check(lib.tsdf_volume_extract_mesh(self._h, table.ctypes.data, b, flags, mesh._h))
+        return mesh
+
     # ---- ray queries (include/tsdf_amd.h, "ray queries"; not in the reference's class)
     def cast_rays_device(self, n, origins_ptr, directions_ptr, t_max_ptr, points_ptr, t_ptr, normals_ptr, colours_ptr=None):
         """n rays (origins and directions 3 float32 each, t_max n float32 or None; device) -> points (3 n), t (n), normals (3 n): device
@@ -771,6 +787,86 @@ def marching_cubes_table():
     t = np.empty((256, 32), np.int8)
     _capi.host.tsdf_host_mc_table(t.ctypes.data)
     return t
+
+
+class Mesh:
+    """tsdf_mesh (include/tsdf_amd.h, "indexed mesh"): the device arrays of an indexed mesh and the scratch of its extraction, kept
+    between extractions (TSDFVolume.extract_mesh(into=mesh)).  The array properties are blocking downloads."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        check(lib.tsdf_mesh_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            lib.tsdf_mesh_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def info(self):
+        i = _capi.MeshInfo()
+        check(lib.tsdf_mesh_get_info(self._h, C.byref(i)))
+        return i
+
+    @property
+    def n_vertices(self):
+        return int(self.info().n_vertices)
+
+    @property
+    def n_indices(self):
+        return int(self.info().n_indices)
+
+    @property
+    def box(self):
+        """The marched box as clipped to the grid: (x0, y0, z0, x1, y1, z1)."""
+        return tuple(int(v) for v in self.info().box)
+
+    def _download(self, which, shape, dtype):
+        # (one element more than the mesh has: the pointer of an empty array may be null, which the C ABI reads as "not asked for")
+        out = np.empty(int(np.prod(shape)) + 1, dtype)
+        args = [None] * 4
+        args[which] = out.ctypes.data
+        check(lib.tsdf_mesh_download(self._h, *args))
+        return out[:-1].reshape(shape)
+
+    @property
+    def vertices(self):
+        """(n_vertices, 3) float32, sorted by lattice-edge key."""
+        return self._download(0, (self.n_vertices, 3), np.float32)
+
+    @property
+    def indices(self):
+        """(n_indices,) uint32, one per soup vertex in soup order."""
+        return self._download(1, (self.n_indices,), np.uint32)
+
+    @property
+    def normals(self):
+        """(n_vertices, 3) float32; ValueError unless the mesh was extracted with normals."""
+        return self._download(2, (self.n_vertices, 3), np.float32)
+
+    @property
+    def colours(self):
+        """(n_vertices, 3) uint8; ValueError unless the mesh was extracted with colours."""
+        return self._download(3, (self.n_vertices, 3), np.uint8)
+
+    def triangles(self):
+        """(n_indices / 3, 3) uint32, wired as extract_surface wires its soup: triangle t = (I[3t], I[3t+2], I[3t+1])."""
+        return np.ascontiguousarray(self.indices.reshape(-1, 3)[:, [0, 2, 1]])
+
+    def device_buffers(self):
+        """(vertices, indices, normals, colours) as raw device pointers (0: the mesh lacks the array, or is empty); valid until the
+        next extraction into this mesh.  Waits for the extraction's kernels."""
+        p = [C.c_void_p() for _ in range(4)]
+        check(lib.tsdf_mesh_buffers(self._h, *[C.byref(q) for q in p]))
+        return tuple(int(q.value or 0) for q in p)
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides its four output arrays."""
+        n = C.c_uint64(0)
+        check(lib.tsdf_mesh_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
 
 
 class _DeviceArray:

@@ -1,0 +1,500 @@
+// Indexed mesh extraction on the device (include/tsdf_amd.h, "indexed mesh"): marching cubes whose output is one
+// vertex per lattice edge the surface crosses plus one index per vertex of tsdf_volume_marching_cubes' triangle soup, such that
+// vertices[indices[k]] is the soup's k-th vertex bit for bit.
+//
+// Why that is possible: all twelve cube edges run in the positive direction of an axis (kMeshEdge below, from the reference's corner
+// and edge numbering, src/MarchingCubes/MarkAndSweepMC.cu:9-36 / :80-97), corner positions are a function of the absolute voxel
+// coordinate only, and interpolate() (:47-63) orders its end points by sign -- so every cube that touches a lattice edge computes the
+// same 12 bytes for the crossing on it, and a configuration uses exactly its sign-changing edges.  Welding is by lattice edge, never
+// by position.
+//
+// The voxels of the marched box's CLOSED range (one more than its cubes per axis) are numbered x fastest, then y, then z, and cut
+// into chunks of 64: one wave per chunk, lanes along the numbering (so along x, coalesced, wherever a row is long enough).  A chunk's
+// record holds three 64-bit masks -- which of its voxels have a used edge towards +x, +y, +z -- and two bases:
+//   mesh_edges_kernel      the masks (three __ballot), the chunk's vertex count (their popcount) and its soup-vertex count
+//   mesh_scan_*_kernel     exclusive scans of both counts over the chunks (1024 chunks a workgroup, then the workgroups' sums)
+//   mesh_vertices_kernel   every used edge writes its vertex at
+//                              base + popcount of the three masks below its lane + (axis > 0: x-bit) + (axis > 1: y-bit)
+//                          which is the order of the key ((z Y + y) X + x) 3 + axis: no per-edge index array is ever stored
+//   mesh_triangles_kernel  the cube walk of mc_rows_kernel; for each table entry the index of its edge by the same formula, from
+//                          the record of the chunk the edge's lower voxel lies in
+// Nothing depends on the order in which waves finish: no atomics, every output word has one writer.
+#include <cstring>
+#include <new>
+
+#include "common.hpp"
+
+namespace tsdf {
+
+struct MeshTable {
+    int8_t tri[256][32];   // edge numbers, three per triangle, -1 terminated
+    uint8_t count[256];    // vertices per configuration
+};
+
+// 32 bytes per 64 voxels of the marched range
+struct MeshChunk {
+    uint64_t mx, my, mz;   // bit l: the chunk's l-th voxel has a used edge towards +x / +y / +z
+    uint32_t vbase;        // mesh_edges_kernel: the chunk's vertices; after the scan: the index of its first vertex
+    uint32_t ibase;        // the same for the soup vertices (= indices) of the cubes rooted in the chunk
+};
+
+// the marched cubes [x0, x0 + bx) x [y0, y0 + by) x [z0, z0 + bz), all three counts >= 1, inside a grid of X x Y x Z voxels
+struct MeshBox {
+    uint32_t x0, y0, z0, bx, by, bz;
+    uint32_t X, Y;
+    uint64_t n_voxels;     // (bx + 1) (by + 1) (bz + 1): the closed range
+};
+
+// cube edge e: the offset of its lower end from the cube's root voxel and its axis (MarkAndSweepMC.cu:80-97 with :291-302)
+__constant__ uint8_t kMeshEdge[12][4] = {{0, 0, 1, 0}, {1, 0, 0, 2}, {0, 0, 0, 0}, {0, 0, 0, 2}, {0, 1, 1, 0}, {1, 1, 0, 2},
+                                         {0, 1, 0, 0}, {0, 1, 0, 2}, {0, 0, 1, 1}, {1, 0, 1, 1}, {1, 0, 0, 1}, {0, 0, 0, 1}};
+
+// The voxel a lane of chunk `chunk` owns, relative to the box's first voxel; false past the range's end.
+__device__ inline bool mesh_voxel(const MeshBox &b, uint32_t chunk, uint32_t lane, uint32_t &rx, uint32_t &ry, uint32_t &rz) {
+    const uint32_t W = b.bx + 1, H = b.by + 1;
+    const uint64_t first = (uint64_t)chunk * 64;
+    uint32_t rx0, ry0, rz0;
+    if (b.n_voxels <= 0xffffffffull) {
+        const uint32_t plane = W * H, f = (uint32_t)first;
+        rz0 = f / plane;
+        const uint32_t rem = f - rz0 * plane;
+        ry0 = rem / W;
+        rx0 = rem - ry0 * W;
+    } else {
+        const uint64_t plane = (uint64_t)W * H;
+        rz0 = (uint32_t)(first / plane);
+        const uint64_t rem = first - rz0 * plane;
+        ry0 = (uint32_t)(rem / W);
+        rx0 = (uint32_t)(rem - (uint64_t)ry0 * W);
+    }
+    const uint32_t t = rx0 + lane, q = t / W;   // (W >= 2: at most 32 rows further)
+    rx = t - q * W;
+    const uint32_t u = ry0 + q, q2 = u / H;
+    ry = u - q2 * H;
+    rz = rz0 + q2;
+    return first + lane < b.n_voxels;
+}
+
+__device__ inline uint32_t wave_inclusive_sum(uint32_t v, uint32_t lane) {
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(v, o);
+        if ((int)lane >= o) v += up;
+    }
+    return v;
+}
+
+// The configuration of the cube rooted at dist[base] (bit i: corner i negative, MarkAndSweepMC.cu:110-124).
+__device__ inline int mesh_cube_type(const float *__restrict__ dist, size_t base, size_t dy, size_t dz) {
+    return (dist[base + dz] < 0) | (dist[base + 1 + dz] < 0) << 1 | (dist[base + 1] < 0) << 2 | (dist[base] < 0) << 3 |
+           (dist[base + dy + dz] < 0) << 4 | (dist[base + 1 + dy + dz] < 0) << 5 | (dist[base + 1 + dy] < 0) << 6 | (dist[base + dy] < 0) << 7;
+}
+
+// An edge is used when its ends differ in d < 0 and one of the cubes round it is marched: for the voxels of the closed range
+// that is "the edge's upper end is in the range too".
+__global__ __launch_bounds__(256) void mesh_edges_kernel(const float *__restrict__ dist, const MeshBox b, const MeshTable *__restrict__ table,
+                                                         uint32_t n_chunks, MeshChunk *__restrict__ chunks) {
+    __shared__ uint8_t count[256];
+    count[threadIdx.x] = table->count[threadIdx.x];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= n_chunks) return;
+    uint32_t rx, ry, rz;
+    const bool valid = mesh_voxel(b, chunk, lane, rx, ry, rz);
+    const size_t dy = b.X, dz = (size_t)b.X * b.Y;
+    const size_t base = (size_t)(b.x0 + rx) + (b.y0 + ry) * dy + (b.z0 + rz) * dz;
+    const bool hx = valid && rx < b.bx, hy = valid && ry < b.by, hz = valid && rz < b.bz;
+    const bool s = valid && dist[base] < 0;
+    const uint64_t mx = __ballot(hx && (dist[base + 1] < 0) != s);
+    const uint64_t my = __ballot(hy && (dist[base + dy] < 0) != s);
+    const uint64_t mz = __ballot(hz && (dist[base + dz] < 0) != s);
+    uint32_t n = 0;
+    if (hx && hy && hz) n = count[mesh_cube_type(dist, base, dy, dz)];
+    n = wave_inclusive_sum(n, lane);
+    if (lane == 63) {
+        MeshChunk c;
+        c.mx = mx;
+        c.my = my;
+        c.mz = mz;
+        c.vbase = (uint32_t)(__popcll(mx) + __popcll(my) + __popcll(mz));
+        c.ibase = n;
+        chunks[chunk] = c;
+    }
+}
+
+// ---- the two exclusive scans (vertices, indices) over the chunks -----------------------------------------------------------------
+// part[2 p], part[2 p + 1]: the sums of workgroup p's 1024 chunks
+__global__ __launch_bounds__(1024) void mesh_scan_sums_kernel(const MeshChunk *__restrict__ chunks, uint32_t n_chunks, uint64_t *__restrict__ part) {
+    __shared__ uint32_t sv[16], si[16];
+    const uint32_t i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t v = wave_inclusive_sum(i < n_chunks ? chunks[i].vbase : 0u, lane);
+    const uint32_t t = wave_inclusive_sum(i < n_chunks ? chunks[i].ibase : 0u, lane);
+    if (lane == 63) {
+        sv[wave] = v;
+        si[wave] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t a = 0, c = 0;
+        for (int w = 0; w < 16; w++) {
+            a += sv[w];
+            c += si[w];
+        }
+        part[2 * blockIdx.x] = a;
+        part[2 * blockIdx.x + 1] = c;
+    }
+}
+
+// In place, one workgroup: part[2 p], part[2 p + 1] = the sums of the parts before p; part[2 n_parts], [2 n_parts + 1] = the totals.
+__global__ __launch_bounds__(1024) void mesh_scan_parts_kernel(uint64_t *__restrict__ part, uint32_t n_parts) {
+    __shared__ uint64_t wave_sum[2][16];
+    __shared__ uint64_t carry[2];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x < 2) carry[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t first = 0; first < n_parts; first += 1024) {
+        const uint32_t i = first + threadIdx.x;
+        uint64_t v[2], incl[2];
+        for (int k = 0; k < 2; k++) {
+            v[k] = i < n_parts ? part[2 * (size_t)i + k] : 0;
+            incl[k] = v[k];
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint64_t up = __shfl_up(incl[k], o);
+                if ((int)lane >= o) incl[k] += up;
+            }
+            if (lane == 63) wave_sum[k][wave] = incl[k];
+        }
+        __syncthreads();
+        uint64_t before[2];
+        for (int k = 0; k < 2; k++) {
+            before[k] = carry[k];
+            for (uint32_t w = 0; w < wave; w++) before[k] += wave_sum[k][w];
+            if (i < n_parts) part[2 * (size_t)i + k] = before[k] + incl[k] - v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x == 1023) {
+            carry[0] = before[0] + incl[0];
+            carry[1] = before[1] + incl[1];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) part[2 * (size_t)n_parts + threadIdx.x] = carry[threadIdx.x];
+}
+
+// counts -> bases.  (Totals above 2^32 - 1 wrap here; the host refuses them before anything reads a base.)
+__global__ __launch_bounds__(1024) void mesh_scan_apply_kernel(MeshChunk *__restrict__ chunks, uint32_t n_chunks, const uint64_t *__restrict__ part) {
+    __shared__ uint32_t sv[16], si[16];
+    const uint32_t i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t v = i < n_chunks ? chunks[i].vbase : 0u, t = i < n_chunks ? chunks[i].ibase : 0u;
+    const uint32_t iv = wave_inclusive_sum(v, lane), it = wave_inclusive_sum(t, lane);
+    if (lane == 63) {
+        sv[wave] = iv;
+        si[wave] = it;
+    }
+    __syncthreads();
+    uint32_t bv = (uint32_t)part[2 * blockIdx.x], bt = (uint32_t)part[2 * blockIdx.x + 1];
+    for (uint32_t w = 0; w < wave; w++) {
+        bv += sv[w];
+        bt += si[w];
+    }
+    if (i < n_chunks) {
+        chunks[i].vbase = bv + iv - v;
+        chunks[i].ibase = bt + it - t;
+    }
+}
+
+// interpolate (MarkAndSweepMC.cu:47-63) between the centres of voxel (x, y, z) and its neighbour along AXIS, the arithmetic of
+// mc_rows_kernel operation for operation (centre_of_voxel_at, src/TSDF/TSDF_utilities.cu:10-17; the swap by sign; three components)
+template <int AXIS>
+__device__ inline void mesh_write_vertex(float *__restrict__ dst, uint32_t x, uint32_t y, uint32_t z, float w0, float w1, const F3 &vs, const F3 &offset) {
+    float3 v0, v1;
+    v0.x = ((int)x + 0.5f) * vs.x + offset.x;
+    v0.y = ((int)y + 0.5f) * vs.y + offset.y;
+    v0.z = ((int)z + 0.5f) * vs.z + offset.z;
+    v1.x = ((int)(x + (AXIS == 0)) + 0.5f) * vs.x + offset.x;
+    v1.y = ((int)(y + (AXIS == 1)) + 0.5f) * vs.y + offset.y;
+    v1.z = ((int)(z + (AXIS == 2)) + 0.5f) * vs.z + offset.z;
+    if ((w0 > 0) && (w1 < 0)) {
+        const float tw = w0; w0 = w1; w1 = tw;
+        const float3 tv = v0; v0 = v1; v1 = tv;
+    }
+    const float ratio = -(w0) / (w1 - w0);
+    dst[0] = (ratio * (v1.x - v0.x)) + v0.x;
+    dst[1] = (ratio * (v1.y - v0.y)) + v0.y;
+    dst[2] = (ratio * (v1.z - v0.z)) + v0.z;
+}
+
+__global__ __launch_bounds__(256) void mesh_vertices_kernel(const float *__restrict__ dist, const MeshBox b, F3 vs, F3 offset, uint32_t n_chunks,
+                                                            const MeshChunk *__restrict__ chunks, float *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= n_chunks) return;
+    const MeshChunk c = chunks[chunk];
+    const uint32_t ex = (uint32_t)(c.mx >> lane) & 1u, ey = (uint32_t)(c.my >> lane) & 1u, ez = (uint32_t)(c.mz >> lane) & 1u;
+    if (!(ex | ey | ez)) return;
+    uint32_t rx, ry, rz;
+    (void)mesh_voxel(b, chunk, lane, rx, ry, rz);   // (a set bit is a voxel of the range)
+    const size_t dy = b.X, dz = (size_t)b.X * b.Y;
+    const uint32_t x = b.x0 + rx, y = b.y0 + ry, z = b.z0 + rz;
+    const size_t base = (size_t)x + y * dy + z * dz;
+    const uint64_t below = (1ull << lane) - 1;
+    const float w = dist[base];
+    float *dst = out + (size_t)(c.vbase + __popcll(c.mx & below) + __popcll(c.my & below) + __popcll(c.mz & below)) * 3;
+    if (ex) mesh_write_vertex<0>(dst, x, y, z, w, dist[base + 1], vs, offset);
+    if (ey) mesh_write_vertex<1>(dst + 3 * ex, x, y, z, w, dist[base + dy], vs, offset);
+    if (ez) mesh_write_vertex<2>(dst + 3 * (ex + ey), x, y, z, w, dist[base + dz], vs, offset);
+}
+
+__global__ __launch_bounds__(256) void mesh_triangles_kernel(const float *__restrict__ dist, const MeshBox b, const MeshTable *__restrict__ table,
+                                                             uint32_t n_chunks, const MeshChunk *__restrict__ chunks, uint32_t *__restrict__ out) {
+    __shared__ uint8_t count[256];
+    count[threadIdx.x] = table->count[threadIdx.x];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (chunk >= n_chunks) return;
+    uint32_t rx, ry, rz;
+    const bool valid = mesh_voxel(b, chunk, lane, rx, ry, rz);
+    const size_t dy = b.X, dz = (size_t)b.X * b.Y;
+    const bool cube = valid && rx < b.bx && ry < b.by && rz < b.bz;
+    int type = 0;
+    if (cube) type = mesh_cube_type(dist, (size_t)(b.x0 + rx) + (b.y0 + ry) * dy + (b.z0 + rz) * dz, dy, dz);
+    const uint32_t n = cube ? count[type] : 0u;
+    const uint32_t incl = wave_inclusive_sum(n, lane);
+    if (n == 0) return;
+    const uint64_t W = b.bx + 1, plane = W * (b.by + 1), lin = (uint64_t)chunk * 64 + lane;
+    uint32_t *dst = out + (size_t)chunks[chunk].ibase + (incl - n);
+    for (uint32_t i = 0; i < n; i++) {
+        const int e = table->tri[type][i];
+        // the edge's lower voxel: in the closed range because the cube is marched
+        const uint64_t at = lin + kMeshEdge[e][0] + kMeshEdge[e][1] * W + kMeshEdge[e][2] * plane;
+        const uint32_t axis = kMeshEdge[e][3], l = (uint32_t)at & 63u;
+        const MeshChunk c = chunks[at >> 6];
+        const uint64_t below = (1ull << l) - 1;
+        uint32_t index = c.vbase + __popcll(c.mx & below) + __popcll(c.my & below) + __popcll(c.mz & below);
+        if (axis > 0) index += (uint32_t)(c.mx >> l) & 1u;
+        if (axis > 1) index += (uint32_t)(c.my >> l) & 1u;
+        dst[i] = index;
+    }
+}
+
+}  // namespace tsdf
+
+using namespace tsdf;
+
+struct tsdf_mesh {
+    int device;
+    hipEvent_t done;        // recorded behind the last extraction's launches
+    int pending;            // ... and not waited for yet
+    float *vertices;
+    uint32_t *indices;
+    float *normals;
+    uint8_t *rgb;
+    size_t vertices_cap, indices_cap, normals_cap, rgb_cap;   // in elements of the arrays (vertices, indices)
+    MeshChunk *chunks;
+    size_t chunks_cap;
+    uint64_t *parts;        // two sums per 1024 chunks + the two totals
+    size_t parts_cap;       // in words
+    MeshTable *table;       // the device copy of host_table (uploaded again only when the caller's table changes)
+    MeshTable host_table;
+    int table_valid;
+    uint64_t *totals;       // pinned: where the two totals land
+    tsdf_mesh_info info;
+};
+
+namespace {
+
+// Arrays only grow; what they held is not kept.
+template <typename T>
+hipError_t mesh_reserve(T *&p, size_t &cap, size_t want) {
+    if (want <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+    if (e == hipSuccess) cap = want;
+    return e;
+}
+
+void mesh_free(tsdf_mesh *m) {
+    if (m->done) (void)hipEventSynchronize(m->done);
+    if (m->vertices) (void)hipFree(m->vertices);
+    if (m->indices) (void)hipFree(m->indices);
+    if (m->normals) (void)hipFree(m->normals);
+    if (m->rgb) (void)hipFree(m->rgb);
+    if (m->chunks) (void)hipFree(m->chunks);
+    if (m->parts) (void)hipFree(m->parts);
+    if (m->table) (void)hipFree(m->table);
+    if (m->totals) (void)hipHostFree(m->totals);
+    if (m->done) (void)hipEventDestroy(m->done);
+    delete m;
+}
+
+int mesh_wait(const tsdf_mesh *cm, const char *what) {
+    tsdf_mesh *m = const_cast<tsdf_mesh *>(cm);
+    if (m->pending) {
+        TSDF_HIP(hipEventSynchronize(m->done), what);
+        m->pending = 0;
+    }
+    return TSDF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_mesh_create(tsdf_mesh **out) {
+    TSDF_REQUIRE(out, "tsdf_mesh_create: null argument");
+    *out = nullptr;
+    tsdf_mesh *m = new (std::nothrow) tsdf_mesh();
+    if (!m) {
+        set_error("out of host memory");
+        return TSDF_ERR_NOMEM;
+    }
+    std::memset(m, 0, sizeof(*m));
+    hipError_t e = hipGetDevice(&m->device);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void **)&m->table, sizeof(MeshTable));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&m->totals, 2 * sizeof(uint64_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        mesh_free(m);
+        return hip_fail(e, "mesh alloc failed");
+    }
+    *out = m;
+    return TSDF_OK;
+}
+
+void tsdf_mesh_destroy(tsdf_mesh *m) {
+    if (m) mesh_free(m);
+}
+
+int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const uint32_t box[6], uint32_t flags, tsdf_mesh *m) {
+    TSDF_REQUIRE(cv && table && m, "tsdf_volume_extract_mesh: null argument");
+    tsdf_volume *v = const_cast<tsdf_volume *>(cv);
+    const Geom &g = v->g;
+    TSDF_REQUIRE((flags & ~(uint32_t)(TSDF_MESH_NORMALS | TSDF_MESH_COLOURS)) == 0, "tsdf_volume_extract_mesh: unknown flags %#x", flags);
+    TSDF_REQUIRE(!v->slab, "tsdf_volume_extract_mesh: a Z-slab volume (tsdf_volume_create_slab) is not supported; tsdf_volume_marching_cubes is");
+    TSDF_REQUIRE(v->device == m->device, "tsdf_volume_extract_mesh: the mesh was created on device %d, the volume on device %d", m->device, v->device);
+    TSDF_REQUIRE(!(flags & TSDF_MESH_COLOURS) || v->colour, "tsdf_volume_extract_mesh: TSDF_MESH_COLOURS on a volume without colour (tsdf_volume_enable_colour)");
+    MeshTable t;
+    memset(&t, 0, sizeof(t));
+    for (int c = 0; c < 256; c++) {   // the rules of tsdf_volume_marching_cubes
+        int n = 0;
+        while (n < 32 && table[c * 32 + n] >= 0) {
+            TSDF_REQUIRE(table[c * 32 + n] < 12, "tsdf_volume_extract_mesh: bad edge number in the table");
+            t.tri[c][n] = table[c * 32 + n];
+            n++;
+        }
+        TSDF_REQUIRE(n % 3 == 0, "tsdf_volume_extract_mesh: a configuration's vertices are not whole triangles");
+        for (int i = n; i < 32; i++) t.tri[c][i] = -1;
+        t.count[c] = (uint8_t)n;
+    }
+    const uint32_t last[3] = {g.X ? g.X - 1 : 0, g.Y ? g.Y - 1 : 0, g.Z ? g.Z - 1 : 0};   // cubes per axis
+    uint32_t lo[3] = {0, 0, 0}, hi[3] = {last[0], last[1], last[2]};
+    if (box) {
+        for (int a = 0; a < 3; a++) {
+            TSDF_REQUIRE(box[a] < box[a + 3], "tsdf_volume_extract_mesh: the box's begin (%u) is not below its end (%u) on axis %d", box[a], box[a + 3], a);
+            lo[a] = box[a];
+            hi[a] = box[a + 3] < last[a] ? box[a + 3] : last[a];
+        }
+    }
+    if (m->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, m->done, 0), "mesh stream order");   // what a previous extraction into this handle left in flight
+    m->info.n_vertices = m->info.n_indices = 0;
+    m->info.flags = flags;
+    for (int a = 0; a < 3; a++) {
+        m->info.box[a] = lo[a];
+        m->info.box[a + 3] = hi[a] > lo[a] ? hi[a] : lo[a];
+    }
+    if (!(lo[0] < hi[0] && lo[1] < hi[1] && lo[2] < hi[2])) return TSDF_OK;   // clipped to nothing, or an axis shorter than 2
+
+    MeshBox b;
+    b.x0 = lo[0]; b.y0 = lo[1]; b.z0 = lo[2];
+    b.bx = hi[0] - lo[0]; b.by = hi[1] - lo[1]; b.bz = hi[2] - lo[2];
+    b.X = g.X; b.Y = g.Y;
+    b.n_voxels = (uint64_t)(b.bx + 1) * (b.by + 1) * (b.bz + 1);
+    const uint64_t n_chunks64 = (b.n_voxels + 63) / 64;
+    TSDF_REQUIRE(n_chunks64 < (1ull << 32), "tsdf_volume_extract_mesh: the box holds too many voxels");
+    const uint32_t n_chunks = (uint32_t)n_chunks64, n_parts = (n_chunks + 1023) / 1024;
+    hipError_t e = mesh_reserve(m->chunks, m->chunks_cap, (size_t)n_chunks);
+    if (e == hipSuccess) e = mesh_reserve(m->parts, m->parts_cap, 2 * ((size_t)n_parts + 1));
+    if (e == hipSuccess && (!m->table_valid || memcmp(&t, &m->host_table, sizeof(t)) != 0)) {
+        m->table_valid = 0;
+        // (host_table outlives the copy; a handle is used by one thread at a time, and the stream waited for `done` above)
+        TSDF_HIP(hipStreamSynchronize(v->stream), "mesh table upload");
+        memcpy(&m->host_table, &t, sizeof(t));
+        e = hipMemcpyAsync(m->table, &m->host_table, sizeof(t), hipMemcpyHostToDevice, v->stream);
+        if (e == hipSuccess) m->table_valid = 1;
+    }
+    if (e != hipSuccess) return hip_fail(e, "mesh scratch alloc failed");
+    const float *dist = v->dist - (size_t)g.z_store_begin * g.X * g.Y;   // (z_store_begin is 0: no slab here)
+    const dim3 grid((n_chunks + 3) / 4);
+    hipLaunchKernelGGL(mesh_edges_kernel, grid, dim3(256), 0, v->stream, dist, b, m->table, n_chunks, m->chunks);
+    hipLaunchKernelGGL(mesh_scan_sums_kernel, dim3(n_parts), dim3(1024), 0, v->stream, m->chunks, n_chunks, m->parts);
+    hipLaunchKernelGGL(mesh_scan_parts_kernel, dim3(1), dim3(1024), 0, v->stream, m->parts, n_parts);
+    hipLaunchKernelGGL(mesh_scan_apply_kernel, dim3(n_parts), dim3(1024), 0, v->stream, m->chunks, n_chunks, m->parts);
+    TSDF_HIP(hipGetLastError(), "mesh count kernels failed");
+    TSDF_HIP(hipMemcpyAsync(m->totals, m->parts + 2 * (size_t)n_parts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, v->stream), "mesh counts download");
+    TSDF_HIP(hipStreamSynchronize(v->stream), "mesh count");   // the one synchronisation: the arrays are sized from the counts
+    const uint64_t n_vertices = m->totals[0], n_indices = m->totals[1];
+    TSDF_REQUIRE(n_vertices <= 0xffffffffull && n_indices <= 0xffffffffull,
+                 "tsdf_volume_extract_mesh: %llu vertices and %llu indices do not fit 32-bit indices: extract the volume in boxes",
+                 (unsigned long long)n_vertices, (unsigned long long)n_indices);
+    if (n_vertices == 0) return TSDF_OK;   // (no vertex, so no index either)
+    e = mesh_reserve(m->vertices, m->vertices_cap, (size_t)n_vertices * 3);
+    if (e == hipSuccess) e = mesh_reserve(m->indices, m->indices_cap, (size_t)n_indices);
+    if (e == hipSuccess && (flags & TSDF_MESH_NORMALS)) e = mesh_reserve(m->normals, m->normals_cap, (size_t)n_vertices * 3);
+    if (e == hipSuccess && (flags & TSDF_MESH_COLOURS)) e = mesh_reserve(m->rgb, m->rgb_cap, (size_t)n_vertices * 3);
+    if (e != hipSuccess) return hip_fail(e, "mesh array alloc failed");
+    hipLaunchKernelGGL(mesh_vertices_kernel, grid, dim3(256), 0, v->stream, dist, b, g.vs, g.offset, n_chunks, m->chunks, m->vertices);
+    hipLaunchKernelGGL(mesh_triangles_kernel, grid, dim3(256), 0, v->stream, dist, b, m->table, n_chunks, m->chunks, m->indices);
+    TSDF_HIP(hipGetLastError(), "mesh emit kernels failed");
+    int rc = TSDF_OK;
+    if (flags & TSDF_MESH_NORMALS)
+        rc = tsdf_volume_sample_field_device(cv, n_vertices, m->vertices, nullptr, m->normals, nullptr, TSDF_FIELD_UNIT_GRADIENT, v->stream);
+    if (rc == TSDF_OK && (flags & TSDF_MESH_COLOURS)) rc = tsdf_volume_sample_colours_device(cv, n_vertices, m->vertices, m->rgb, v->stream);
+    TSDF_HIP(hipEventRecord(m->done, v->stream), "mesh event");
+    m->pending = 1;
+    if (rc != TSDF_OK) return rc;
+    m->info.n_vertices = n_vertices;
+    m->info.n_indices = n_indices;
+    return TSDF_OK;
+}
+
+int tsdf_mesh_get_info(const tsdf_mesh *m, tsdf_mesh_info *info) {
+    TSDF_REQUIRE(m && info, "tsdf_mesh_get_info: null argument");
+    *info = m->info;
+    return TSDF_OK;
+}
+
+int tsdf_mesh_buffers(const tsdf_mesh *m, const float **device_vertices, const uint32_t **device_indices, const float **device_normals,
+                      const uint8_t **device_rgb) {
+    TSDF_REQUIRE(m, "tsdf_mesh_buffers: null mesh");
+    const int rc = mesh_wait(m, "mesh wait");
+    if (rc != TSDF_OK) return rc;
+    const bool any = m->info.n_vertices != 0;
+    if (device_vertices) *device_vertices = any ? m->vertices : nullptr;
+    if (device_indices) *device_indices = any ? m->indices : nullptr;
+    if (device_normals) *device_normals = any && (m->info.flags & TSDF_MESH_NORMALS) ? m->normals : nullptr;
+    if (device_rgb) *device_rgb = any && (m->info.flags & TSDF_MESH_COLOURS) ? m->rgb : nullptr;
+    return TSDF_OK;
+}
+
+int tsdf_mesh_download(const tsdf_mesh *m, float *host_vertices, uint32_t *host_indices, float *host_normals, uint8_t *host_rgb) {
+    TSDF_REQUIRE(m, "tsdf_mesh_download: null mesh");
+    TSDF_REQUIRE(!host_normals || (m->info.flags & TSDF_MESH_NORMALS), "tsdf_mesh_download: the mesh was extracted without TSDF_MESH_NORMALS");
+    TSDF_REQUIRE(!host_rgb || (m->info.flags & TSDF_MESH_COLOURS), "tsdf_mesh_download: the mesh was extracted without TSDF_MESH_COLOURS");
+    const int rc = mesh_wait(m, "mesh wait");
+    if (rc != TSDF_OK) return rc;
+    const size_t nv = (size_t)m->info.n_vertices, ni = (size_t)m->info.n_indices;
+    if (nv == 0) return TSDF_OK;
+    if (host_vertices) TSDF_HIP(hipMemcpy(host_vertices, m->vertices, nv * 3 * sizeof(float), hipMemcpyDeviceToHost), "mesh download");
+    if (host_indices) TSDF_HIP(hipMemcpy(host_indices, m->indices, ni * sizeof(uint32_t), hipMemcpyDeviceToHost), "mesh download");
+    if (host_normals) TSDF_HIP(hipMemcpy(host_normals, m->normals, nv * 3 * sizeof(float), hipMemcpyDeviceToHost), "mesh download");
+    if (host_rgb) TSDF_HIP(hipMemcpy(host_rgb, m->rgb, nv * 3, hipMemcpyDeviceToHost), "mesh download");
+    return TSDF_OK;
+}
+
+int tsdf_mesh_scratch_bytes(const tsdf_mesh *m, uint64_t *bytes) {
+    TSDF_REQUIRE(m && bytes, "tsdf_mesh_scratch_bytes: null argument");
+    *bytes = (uint64_t)m->chunks_cap * sizeof(MeshChunk) + (uint64_t)m->parts_cap * sizeof(uint64_t) + sizeof(MeshTable) + 2 * sizeof(uint64_t);
+    return TSDF_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,25 @@ void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, st
 void extract_surface(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
                      std::vector<float3> &normals, std::vector<uchar3> &colours);
 
+// The surface as an INDEXED mesh (tsdf_volume_extract_mesh, include/tsdf_amd.h "indexed mesh"; not in the reference): one vertex per
+// lattice edge the surface crosses, shared by the triangles round it, sorted by ((z * Y + y) * X + x) * 3 + axis of the edge's lower
+// voxel; triangles wired (I[3t], I[3t+2], I[3t+1]) like extract_surface's, so that vertices[triangle corner] are extract_surface's
+// vertices bit for bit.  Welding is by lattice edge, not by position: where a voxel is exactly 0 several vertices coincide and stay
+// distinct.  Normals (the unit gradient) and colours are sampled once per shared vertex, on the device.  The results go straight into
+// the write_to_ply overloads.
+void extract_surface_indexed(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles);
+void extract_surface_indexed(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                             std::vector<float3> &normals);
+void extract_surface_indexed(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                             std::vector<uchar3> &colours);
+void extract_surface_indexed(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles,
+                             std::vector<float3> &normals, std::vector<uchar3> &colours);
+// ... of the cubes rooted at voxels in [box[0], box[3]) x [box[1], box[4]) x [box[2], box[5]) only (ends clipped to the grid; a begin
+// that is not below its end throws std::invalid_argument); normals / colours may be null
+void extract_surface_indexed(const TSDFVolume *volume, const unsigned box[6], std::vector<float3> &vertices,
+                             std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
+                             std::vector<uchar3> *colours = nullptr);
+
 // The same marching cubes over a host distance array (x fastest, voxel centres at (i + 0.5) * voxel_size + offset):
 // appends three vertices per triangle.  extract_surface is this on the volume's distances.
 void tsdf_host_marching_cubes(const float *dist, unsigned X, unsigned Y, unsigned Z, const float voxel_size[3],
