@@ -742,6 +742,72 @@ int tsdf_mesh_download(const tsdf_mesh *mesh, float *host_vertices, uint32_t *ho
 /* Device bytes the handle holds besides the four output arrays. */
 int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
 
+/* ---- distance field (no reference counterpart: the reference's volume knows the truncated, projective distance only) ------------- */
+/* The Euclidean signed distance field (ESDF) of a whole volume: per voxel, how far the nearest surface is -- what a planner, a
+ * collision checker or a gripper asks -- computed on the device from the distances and weights where they lie.  Opt-in by being
+ * called: a volume on which these are never called does exactly what it did.
+ *   The value (a unique set of bits, whatever computes it): X x Y x Z voxels, voxel sizes vs[a] (the fp32 values of tsdf_volume_info),
+ *     distances d, weights w as every accessor reports them (the same in 8-bit, 16-bit and fp32 storage).
+ *     observed(v): w(v) > 0 (a NaN weight is not observed).  neg(v): d(v) < 0, the mesh's sign test (NaN and both zeros are not negative).
+ *     site(v): observed(v), and some 6-neighbour u inside the grid has observed(u) and neg(u) != neg(v): the ends of the lattice edges
+ *       the surface crosses between two OBSERVED voxels.  An observed / unobserved boundary is not a surface.
+ *     A[a] = vs[a] * vs[a] (one fp32 multiply).  For a voxel v and a site s with integer index differences dx, dy, dz the fp32 cost,
+ *       every operation rounded on its own, is
+ *           c(v, s) = A[2]*(float)(dz*dz) + (A[1]*(float)(dy*dy) + A[0]*(float)(dx*dx))
+ *       (the integer squares are exact in fp32: an axis longer than 4096 is refused).
+ *     q(v) = min over all sites of c(v, s), +inf when there are none.  e(v) = sqrtf(q(v)), correctly rounded; if !(e < max_distance),
+ *       e = max_distance.  max_distance only caps: it never changes a value below it.
+ *     Output: one fp32 per voxel in the volume's index order x + y X + z X Y: -e for an observed voxel with neg, +e for an observed
+ *       voxel without, NaN for an unobserved voxel (+e with TSDF_ESDF_FILL_UNKNOWN).  A site gets -+0.0 by the same rule.
+ *     The minimum is separable -- fp32 addition is monotone, so the minimum commutes with it -- and three passes along x, y and z give
+ *       exactly q.
+ *   Accuracy of the definition: sites are voxel centres next to the surface, not the surface, so against the true distance t to the
+ *     surface -max(vs) <= e - t <= |vs| (the voxel diagonal); -0.996 and +0.40 voxels measured on a sphere.  Within a voxel of the
+ *     surface the TSDF itself (tsdf_volume_sample_field) is the better answer.
+ *   max_distance: mm, > 0; INFINITY means no cap, and a volume without sites then gives +inf (or NaN).
+ *   The handle owns the output array and its scratch and keeps both between calls; both only grow, so a warm recompute allocates
+ *     nothing.  It snapshots the geometry (sizes, voxel sizes, offset), so sampling needs no volume and survives the volume's
+ *     destruction.  A handle is used by one thread at a time, on the device it was made on.  Scratch besides the 4 bytes a voxel of
+ *     output: at most 4 bytes a voxel + 64 KiB (tsdf_esdf_scratch_bytes).
+ *   Stream order: tsdf_volume_compute_esdf enqueues on the volume's stream and returns; tsdf_esdf_get_info, tsdf_esdf_buffer,
+ *     tsdf_esdf_download and tsdf_esdf_sample wait for it, tsdf_esdf_sample_device orders its stream behind it.  n_sites is counted
+ *     with an integer atomic; the distance array has one writer per word and is the same on every run.
+ *   The volume is not written: no distance, weight, weight storage mode, occupancy flag, dirty mark or ray-cast state.
+ *   Refused (TSDF_ERR_INVALID, with a message): NULL arguments; a Z-slab volume; a materialised deformation-node array; max_distance
+ *     that is not > 0 (NaN included); unknown flags; an axis longer than 4096; sampling or downloading a handle that has never been
+ *     computed.  tsdf_esdf_destroy(NULL) is ignored.
+ *   tsdf_esdf_sample[_device]: the trilinear distance and the central-difference gradient of the ESDF at world points, in the frame of
+ *     the field queries (p - offset, the snapshot's offset), by the field queries' own kernel on the ESDF array: bit for bit what
+ *     tsdf_volume_sample_field_device returns on a volume of the same geometry whose distance array holds the ESDF -- the same valid(q),
+ *     NaN outside, TSDF_FIELD_UNIT_GRADIENT, NULL-output and n == 0 rules.  NaN taps (unknown voxels) propagate; that is intended.
+ *   Out of scope: incremental updates, a box of the grid, Z-slabs, sub-voxel site positions, keeping TSDF values inside the band. */
+typedef struct tsdf_esdf tsdf_esdf;
+#define TSDF_ESDF_FILL_UNKNOWN 1u
+typedef struct tsdf_esdf_info {
+    uint32_t size[3];
+    uint32_t flags;
+    float voxel_size[3];
+    float offset[3];        /* the volume's current offset when computed */
+    float max_distance;
+    uint64_t n_sites;
+} tsdf_esdf_info;
+int tsdf_esdf_create(tsdf_esdf **out);   /* on the current device */
+void tsdf_esdf_destroy(tsdf_esdf *esdf);
+int tsdf_volume_compute_esdf(const tsdf_volume *volume, float max_distance, uint32_t flags, tsdf_esdf *esdf);
+int tsdf_esdf_get_info(const tsdf_esdf *esdf, tsdf_esdf_info *info);
+/* The device array of the last computation (NULL before the first); valid until the next computation into the handle. */
+int tsdf_esdf_buffer(const tsdf_esdf *esdf, const float **device_distance);
+/* Blocking copy to size[0] * size[1] * size[2] floats. */
+int tsdf_esdf_download(const tsdf_esdf *esdf, float *host_distance);
+/* n points (3 floats each) -> distance (n floats), gradient (3 n floats); either may be NULL, not both. */
+int tsdf_esdf_sample_device(const tsdf_esdf *esdf, uint64_t n, const float *device_points, float *device_distance,
+                            float *device_gradient, int flags, void *hip_stream);
+/* The same on host arrays; blocking. */
+int tsdf_esdf_sample(const tsdf_esdf *esdf, uint64_t n, const float *host_points, float *host_distance,
+                     float *host_gradient, int flags);
+/* Device bytes the handle holds besides the output array. */
+int tsdf_esdf_scratch_bytes(const tsdf_esdf *esdf, uint64_t *bytes);
+
 /* Multi-GPU raycast: a slab evaluates only the samples whose lower trilinear tap plane it owns and writes
  * one 8-byte record per pixel: k = index of the first owned sample with tsdf <= 0 (TSDF_NO_HIT if none), t = that sample's
  * refined ray parameter (src/RayCaster/GPURaycaster.cu:338-341).  After an all-gather of the records (layout

@@ -1,0 +1,92 @@
+"""The C ABI of the distance field (include/tsdf_amd.h, "distance field"): the header declares the ten entry points with the signatures
+the issue gives, the built library exports them, the Python binding carries the same argument lists, and null arguments are refused
+before a device is touched (no GPU needed)."""
+import ctypes as C
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXPECTED = {
+    "tsdf_esdf_create": ("int", ["tsdf_esdf **"]),
+    "tsdf_esdf_destroy": ("void", ["tsdf_esdf *"]),
+    "tsdf_volume_compute_esdf": ("int", ["const tsdf_volume *", "float", "uint32_t", "tsdf_esdf *"]),
+    "tsdf_esdf_get_info": ("int", ["const tsdf_esdf *", "tsdf_esdf_info *"]),
+    "tsdf_esdf_buffer": ("int", ["const tsdf_esdf *", "const float **"]),
+    "tsdf_esdf_download": ("int", ["const tsdf_esdf *", "float *"]),
+    "tsdf_esdf_sample_device": ("int", ["const tsdf_esdf *", "uint64_t", "const float *", "float *", "float *", "int", "void *"]),
+    "tsdf_esdf_sample": ("int", ["const tsdf_esdf *", "uint64_t", "const float *", "float *", "float *", "int"]),
+    "tsdf_esdf_scratch_bytes": ("int", ["const tsdf_esdf *", "uint64_t *"]),
+}
+
+
+def declarations():
+    """name -> (return type, argument types with the parameter names taken out) of every declaration in EXPECTED."""
+    text = open(os.path.join(ROOT, "include", "tsdf_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = {}
+    for ret, name, args in re.findall(r"\b(int|void)\s+(tsdf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        if name not in EXPECTED:
+            continue
+        types = []
+        for a in args.split(","):
+            a = " ".join(a.split())
+            m = re.match(r"^(.*?)([A-Za-z_][A-Za-z0-9_]*)(\[\d+\])?$", a)
+            types.append((m.group(1).strip() + (" " + m.group(3) if m.group(3) else "")).strip())
+        out[name] = (ret, types)
+    return text, out
+
+
+def test_the_header_declares_the_signatures():
+    text, decl = declarations()
+    for name, sig in EXPECTED.items():
+        assert name in decl, name
+        assert decl[name] == sig, (name, decl[name])
+    assert re.search(r"typedef\s+struct\s+tsdf_esdf\s+tsdf_esdf\s*;", text)
+    assert re.search(r"#define\s+TSDF_ESDF_FILL_UNKNOWN\s+1u\b", text)
+    info = re.search(r"typedef\s+struct\s+tsdf_esdf_info\s*\{(.*?)\}\s*tsdf_esdf_info\s*;", text, flags=re.S)
+    assert info and " ".join(info.group(1).split()) == ("uint32_t size[3]; uint32_t flags; float voxel_size[3]; float offset[3]; "
+                                                        "float max_distance; uint64_t n_sites;")
+
+
+def test_the_library_exports_them():
+    lib = C.CDLL(os.path.join(ROOT, "tsdf_amd", "lib", "libtsdf_hip.so"))
+    for name in EXPECTED:
+        assert hasattr(lib, name), name
+
+
+def test_the_binding_carries_the_same_arguments():
+    from tsdf_amd import _capi
+    vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
+    lib = _capi.lib
+    assert _capi.TSDF_ESDF_FILL_UNKNOWN == 1
+    for name in EXPECTED:
+        assert name in _capi.EXPORTS, name
+    assert lib.tsdf_esdf_create.argtypes == [C.POINTER(vp)] and lib.tsdf_esdf_create.restype == C.c_int
+    assert lib.tsdf_esdf_destroy.argtypes == [vp] and lib.tsdf_esdf_destroy.restype is None
+    assert lib.tsdf_volume_compute_esdf.argtypes == [vp, f32, u32, vp]
+    assert lib.tsdf_esdf_get_info.argtypes == [vp, C.POINTER(_capi.EsdfInfo)]
+    assert lib.tsdf_esdf_buffer.argtypes == [vp, C.POINTER(vp)]
+    assert lib.tsdf_esdf_download.argtypes == [vp, vp]
+    assert lib.tsdf_esdf_sample_device.argtypes == [vp, u64, vp, vp, vp, C.c_int, vp]
+    assert lib.tsdf_esdf_sample.argtypes == [vp, u64, vp, vp, vp, C.c_int]
+    assert lib.tsdf_esdf_scratch_bytes.argtypes == [vp, C.POINTER(u64)]
+    assert [(n, t) for n, t in _capi.EsdfInfo._fields_] == [("size", u32 * 3), ("flags", u32), ("voxel_size", f32 * 3), ("offset", f32 * 3),
+                                                           ("max_distance", f32), ("n_sites", u64)]
+    assert C.sizeof(_capi.EsdfInfo) == 56 and _capi.EsdfInfo.n_sites.offset == 48
+    # null arguments are refused before anything touches a device, and leave a message
+    invalid = _capi.TSDF_ERR_INVALID
+    assert lib.tsdf_esdf_create(None) == invalid
+    assert lib.tsdf_volume_compute_esdf(None, 1.0, 0, None) == invalid
+    assert "tsdf_volume_compute_esdf" in _capi.last_error()
+    assert lib.tsdf_esdf_get_info(None, None) == invalid
+    assert lib.tsdf_esdf_buffer(None, None) == invalid
+    assert lib.tsdf_esdf_download(None, None) == invalid
+    assert lib.tsdf_esdf_sample_device(None, 0, None, None, None, 0, None) == invalid
+    assert lib.tsdf_esdf_sample(None, 0, None, None, None, 0) == invalid
+    assert "tsdf_esdf_sample" in _capi.last_error()
+    assert lib.tsdf_esdf_scratch_bytes(None, None) == invalid
+    lib.tsdf_esdf_destroy(None)   # a null handle is ignored
+    import tsdf_amd
+    assert callable(tsdf_amd.TSDFVolume.compute_esdf)
+    for name in ("distances", "device_buffer", "sample", "sample_device", "info", "n_sites", "scratch_bytes"):
+        assert hasattr(tsdf_amd.ESDF, name), name

@@ -14,6 +14,7 @@ TSDF_OK, TSDF_ERR_INVALID, TSDF_ERR_DEVICE, TSDF_ERR_NOMEM = 0, 1, 2, 3
 TSDF_FIELD_UNIT_GRADIENT = 1
 TSDF_RAYS_BAND_ONLY = 1
 TSDF_MESH_NORMALS, TSDF_MESH_COLOURS = 1, 2
+TSDF_ESDF_FILL_UNKNOWN = 1
 
 
 class TsdfError(RuntimeError):
@@ -34,6 +35,12 @@ class VolumeInfo(C.Structure):
 class MeshInfo(C.Structure):
     """struct tsdf_mesh_info (include/tsdf_amd.h)."""
     _fields_ = [("n_vertices", C.c_uint64), ("n_indices", C.c_uint64), ("flags", C.c_uint32), ("box", C.c_uint32 * 6)]
+
+
+class EsdfInfo(C.Structure):
+    """struct tsdf_esdf_info (include/tsdf_amd.h)."""
+    _fields_ = [("size", C.c_uint32 * 3), ("flags", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
+                ("max_distance", C.c_float), ("n_sites", C.c_uint64)]
 
 
 class AlignStage(C.Structure):
@@ -173,6 +180,15 @@ _SIGS = {
     "tsdf_mesh_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_mesh_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "tsdf_mesh_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_esdf_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_esdf_destroy": (None, [_vp]),
+    "tsdf_volume_compute_esdf": (_i, [_vp, _f, _u32, _vp]),
+    "tsdf_esdf_get_info": (_i, [_vp, C.POINTER(EsdfInfo)]),
+    "tsdf_esdf_buffer": (_i, [_vp, C.POINTER(_vp)]),
+    "tsdf_esdf_download": (_i, [_vp, _vp]),
+    "tsdf_esdf_sample_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _i, _vp]),
+    "tsdf_esdf_sample": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _i]),
+    "tsdf_esdf_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_merge_hits_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_merge_hits_normals_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_slab_exchange_unique_id": (_i, [_vp, C.c_char_p]),

@@ -404,6 +404,16 @@ class TSDFVolume:
         check(lib.tsdf_volume_extract_mesh(self._h, table.ctypes.data, b, flags, mesh._h))
         return mesh
 
+    # ---- distance field (include/tsdf_amd.h, "distance field"; not in the reference's class)
+    def compute_esdf(self, max_distance=float("inf"), fill_unknown=False, into=None):
+        """The Euclidean signed distance field (tsdf_volume_compute_esdf): per voxel the distance (mm) to the nearest site -- an observed
+        voxel with an observed 6-neighbour of the other sign -- negative behind the surface, capped at max_distance (inf: no cap), NaN
+        where unobserved (fill_unknown: the positive distance).  It stays on the device.  `into`: an ESDF to reuse -- its arrays are
+        kept and only grow.  Returns the ESDF."""
+        esdf = ESDF() if into is None else into
+        check(lib.tsdf_volume_compute_esdf(self._h, float(max_distance), _capi.TSDF_ESDF_FILL_UNKNOWN if fill_unknown else 0, esdf._h))
+        return esdf
+
     # ---- ray queries (include/tsdf_amd.h, "ray queries"; not in the reference's class)
     def cast_rays_device(self, n, origins_ptr, directions_ptr, t_max_ptr, points_ptr, t_ptr, normals_ptr, colours_ptr=None):
         """n rays (origins and directions 3 float32 each, t_max n float32 or None; device) -> points (3 n), t (n), normals (3 n): device
@@ -866,6 +876,72 @@ class Mesh:
         """Device bytes the handle holds besides its four output arrays."""
         n = C.c_uint64(0)
         check(lib.tsdf_mesh_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+
+class ESDF:
+    """tsdf_esdf (include/tsdf_amd.h, "distance field"): the device array of a distance field, its scratch and the geometry it was
+    computed for, kept between computations (TSDFVolume.compute_esdf(into=esdf)).  Sampling needs no volume."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        check(lib.tsdf_esdf_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            lib.tsdf_esdf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def info(self):
+        """tsdf_esdf_info: size, flags, voxel_size, offset, max_distance, n_sites.  Waits for the computation."""
+        i = _capi.EsdfInfo()
+        check(lib.tsdf_esdf_get_info(self._h, C.byref(i)))
+        return i
+
+    @property
+    def n_sites(self):
+        return int(self.info.n_sites)
+
+    @property
+    def distances(self):
+        """(X * Y * Z,) float32 in index order x + y X + z X Y, shaped like TSDFVolume.get_distance_data(); a blocking download."""
+        sx, sy, sz = (int(v) for v in self.info.size)
+        out = np.empty(sx * sy * sz + 1, np.float32)   # (one element more: the pointer of an empty array may be null)
+        check(lib.tsdf_esdf_download(self._h, out.ctypes.data))
+        return out[:-1]
+
+    def device_buffer(self):
+        """The raw device pointer of the array (0 before the first computation); valid until the next computation into this handle."""
+        p = C.c_void_p()
+        check(lib.tsdf_esdf_buffer(self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def sample_device(self, n, points_ptr, distance_ptr=None, gradient_ptr=None, unit=False, stream=None):
+        """n points (3 float32 each, device) -> distance (n float32), gradient (3 n): device pointers, either may be None; on `stream`
+        (default: the null stream), ordered behind the computation."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_esdf_sample_device(self._h, int(n), ptr(points_ptr), ptr(distance_ptr), ptr(gradient_ptr),
+                                          _capi.TSDF_FIELD_UNIT_GRADIENT if unit else 0, C.c_void_p(int(stream) if stream else 0)))
+
+    def sample(self, points, gradient=False, unit=False):
+        """(n, 3) float32 world points (mm, the frame of ray-cast and mesh vertices when computed) -> the trilinear distance (n,), or
+        (distance, gradient (n, 3)) with gradient=True (unit: normalised).  NaN outside the grid and next to unobserved voxels."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        d = np.empty(n + 1, np.float32)
+        g = np.empty((n + 1, 3), np.float32) if gradient else None
+        check(lib.tsdf_esdf_sample(self._h, n, p.ctypes.data if n else None, d.ctypes.data, g.ctypes.data if gradient else None,
+                                   _capi.TSDF_FIELD_UNIT_GRADIENT if unit else 0))
+        return (d[:n], g[:n]) if gradient else d[:n]
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides the output array."""
+        n = C.c_uint64(0)
+        check(lib.tsdf_esdf_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
 
 

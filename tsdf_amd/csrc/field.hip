@@ -57,11 +57,10 @@ __global__ __launch_bounds__(256) void field_sample_kernel(const FieldView f, co
 }
 
 template <bool DIST, bool GRAD, bool WEIGHT>
-static void launch_field_instance(const tsdf_volume *v, uint64_t n, const float *points, float *d, float *grad, float *w, int unit,
-                                  hipStream_t stream) {
+static void launch_field_instance(const FieldView &f, bool fast_div, uint64_t n, const float *points, float *d, float *grad, float *w,
+                                  int unit, hipStream_t stream) {
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    const FieldView f = make_field_view(v);
-    if (v->fast_div)
+    if (fast_div)
         hipLaunchKernelGGL((field_sample_kernel<DIST, GRAD, WEIGHT, true>), grid, block, 0, stream, f, n, points, d, grad, w, unit);
     else
         hipLaunchKernelGGL((field_sample_kernel<DIST, GRAD, WEIGHT, false>), grid, block, 0, stream, f, n, points, d, grad, w, unit);
@@ -72,22 +71,28 @@ static int field_check(const tsdf_volume *v, const char *what) {
     return field_refuse_slab(v, what);
 }
 
-// the launch; v has passed field_check, at least one output is asked for, n > 0
-static int sample_field(const tsdf_volume *v, uint64_t n, const float *points, float *d, float *grad, float *w, int flags,
-                        hipStream_t stream) {
+// the launch on a view (field_sample.hpp: also the distance field's samples, esdf.hip); at least one output is asked for, n > 0
+int sample_field_view(const FieldView &v, bool fast_div, uint64_t n, const float *points, float *d, float *grad, float *w, int flags,
+                      hipStream_t stream) {
     TSDF_REQUIRE((n + 255) / 256 <= 0x7FFFFFFFull, "tsdf_volume_sample_field: too many points");
     const int unit = (flags & TSDF_FIELD_UNIT_GRADIENT) ? 1 : 0;
     switch ((d ? 1 : 0) | (grad ? 2 : 0) | (w ? 4 : 0)) {
-        case 1: launch_field_instance<true, false, false>(v, n, points, d, grad, w, unit, stream); break;
-        case 2: launch_field_instance<false, true, false>(v, n, points, d, grad, w, unit, stream); break;
-        case 3: launch_field_instance<true, true, false>(v, n, points, d, grad, w, unit, stream); break;
-        case 4: launch_field_instance<false, false, true>(v, n, points, d, grad, w, unit, stream); break;
-        case 5: launch_field_instance<true, false, true>(v, n, points, d, grad, w, unit, stream); break;
-        case 6: launch_field_instance<false, true, true>(v, n, points, d, grad, w, unit, stream); break;
-        default: launch_field_instance<true, true, true>(v, n, points, d, grad, w, unit, stream); break;
+        case 1: launch_field_instance<true, false, false>(v, fast_div, n, points, d, grad, w, unit, stream); break;
+        case 2: launch_field_instance<false, true, false>(v, fast_div, n, points, d, grad, w, unit, stream); break;
+        case 3: launch_field_instance<true, true, false>(v, fast_div, n, points, d, grad, w, unit, stream); break;
+        case 4: launch_field_instance<false, false, true>(v, fast_div, n, points, d, grad, w, unit, stream); break;
+        case 5: launch_field_instance<true, false, true>(v, fast_div, n, points, d, grad, w, unit, stream); break;
+        case 6: launch_field_instance<false, true, true>(v, fast_div, n, points, d, grad, w, unit, stream); break;
+        default: launch_field_instance<true, true, true>(v, fast_div, n, points, d, grad, w, unit, stream); break;
     }
     TSDF_HIP(hipGetLastError(), "Field sample kernel failed");
     return TSDF_OK;
+}
+
+// the launch; v has passed field_check, at least one output is asked for, n > 0
+static int sample_field(const tsdf_volume *v, uint64_t n, const float *points, float *d, float *grad, float *w, int flags,
+                        hipStream_t stream) {
+    return sample_field_view(make_field_view(v), v->fast_div != 0, n, points, d, grad, w, flags, stream);
 }
 
 }  // namespace tsdf

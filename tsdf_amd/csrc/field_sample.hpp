@@ -35,6 +35,11 @@ inline FieldView make_field_view(const tsdf_volume *v) {
     return {v->dist, {v->weight, v->wpacked, v->wmode}, v->g, make_tri_const(v->g)};
 }
 
+// field.hip: the field queries' launch on a view -- distance (n), gradient (3 n), weight (n) at n device points, any output may be
+// null but not all, n > 0; flags as tsdf_volume_sample_field_device.  fast_div: the volume's verified division (tsdf_volume::fast_div).
+int sample_field_view(const FieldView &f, bool fast_div, uint64_t n, const float *points, float *d, float *grad, float *w, int flags,
+                      hipStream_t stream);
+
 // The taps of a sample cross slab boundaries: every caller refuses a Z-slab volume, under its own name.
 inline int field_refuse_slab(const tsdf_volume *v, const char *what) {
     TSDF_REQUIRE(!v->slab && v->g.z_store_begin == 0 && v->g.z_store_end == v->g.Z,

@@ -18,6 +18,7 @@
 #include <vector>
 
 struct tsdf_volume;  // C-ABI handle (include/tsdf_amd.h)
+struct tsdf_esdf;    // distance-field handle (include/tsdf_amd.h)
 
 class TSDFVolume {
 public:
@@ -165,6 +166,14 @@ public:
     // Throws std::invalid_argument on the refusals (a Z-slab, a non-finite entry in T0's top three rows).
     Eigen::Matrix4d align_points(const std::vector<float3> &points, const Eigen::Matrix4d &T0, uint32_t iterations = 10, float gate = 0.0f,
                                  float *residual = nullptr, float *inliers = nullptr) const;
+
+    // Distance field (include/tsdf_amd.h, "distance field"; not in the reference's class): per voxel the Euclidean distance (mm) to the
+    // nearest site -- an observed voxel with an observed 6-neighbour of the other sign -- negative behind the surface, capped at
+    // max_distance (INFINITY: no cap), NaN where unobserved (fill_unknown: the positive distance); index order x + y X + z X Y.
+    // Throws std::invalid_argument on the refusals (a Z-slab, materialised deformation nodes, max_distance not > 0, an axis > 4096).
+    std::vector<float> compute_esdf(float max_distance, bool fill_unknown = false) const;
+    // the same into a caller's handle (tsdf_esdf_create), where it stays on the device: tsdf_esdf_buffer, tsdf_esdf_sample_device
+    void compute_esdf(float max_distance, bool fill_unknown, tsdf_esdf *esdf) const;
 
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);

@@ -166,6 +166,28 @@ void TSDFVolume::sample_field(const std::vector<float3> &points, std::vector<flo
     if (weights) weights->resize(n);
 }
 
+void TSDFVolume::compute_esdf(float max_distance, bool fill_unknown, tsdf_esdf *esdf) const {
+    check(tsdf_volume_compute_esdf(m_handle, max_distance, fill_unknown ? TSDF_ESDF_FILL_UNKNOWN : 0u, esdf), "Couldn't compute the distance field");
+}
+
+std::vector<float> TSDFVolume::compute_esdf(float max_distance, bool fill_unknown) const {
+    tsdf_esdf *esdf = nullptr;
+    check(tsdf_esdf_create(&esdf), "Couldn't compute the distance field");
+    int rc = tsdf_volume_compute_esdf(m_handle, max_distance, fill_unknown ? TSDF_ESDF_FILL_UNKNOWN : 0u, esdf);
+    tsdf_esdf_info info;
+    if (rc == TSDF_OK) rc = tsdf_esdf_get_info(esdf, &info);
+    std::vector<float> distances;
+    if (rc == TSDF_OK) {
+        // (one element more than needed: data() of an empty vector may be null)
+        distances.assign((size_t)info.size[0] * info.size[1] * info.size[2] + 1, 0.0f);
+        rc = tsdf_esdf_download(esdf, distances.data());
+        distances.pop_back();
+    }
+    tsdf_esdf_destroy(esdf);
+    check(rc, "Couldn't compute the distance field");
+    return distances;
+}
+
 void TSDFVolume::cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
                            std::vector<float> *t, std::vector<float3> *normals, const std::vector<float> *t_max) const {
     static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
