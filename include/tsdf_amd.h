@@ -739,8 +739,66 @@ int tsdf_mesh_buffers(const tsdf_mesh *mesh, const float **device_vertices, cons
                       const float **device_normals, const uint8_t **device_rgb);
 /* Blocking copies to host arrays sized from tsdf_mesh_get_info; any may be NULL. */
 int tsdf_mesh_download(const tsdf_mesh *mesh, float *host_vertices, uint32_t *host_indices, float *host_normals, uint8_t *host_rgb);
-/* Device bytes the handle holds besides the four output arrays. */
+/* Device bytes the handle holds besides the four output arrays.  After an extraction alone that is the bound above; the first
+ * components call (group "mesh components") adds 8 bytes per vertex (labels and sizes) and 32 bytes, a filter INTO the handle 12 bytes
+ * per 64 vertices and per 64 triples of its source. */
 int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
+
+/* ---- mesh components (no reference counterpart: the reference's soup has no connectivity to ask about) ----------------------------- */
+/* The connected pieces of an indexed mesh, labelled on the device, and a filter that drops the small ones (the floaters every fused
+ * scan of real depth data carries) without the mesh leaving the device.  Opt-in by being called: no other entry point, launch or
+ * result changes.
+ *   Graph: n_vertices vertices and n_indices indices, n_indices a multiple of 3.  Index triple t joins the three vertices I[3t],
+ *     I[3t+1], I[3t+2]; the wiring order does not matter.  Degenerate triples (a, a, b) and (a, a, a) and repeated triples all count as
+ *     triangles and join whatever distinct vertices they name.  A vertex that no triple names is a component of its own.
+ *   Outputs (unique values, whatever computes them):
+ *     L[v]: the smallest vertex index in v's component (uint32).
+ *     T[v]: the number of index triples whose first index lies in v's component -- so all three do -- the same for every vertex of the
+ *       component (uint32).
+ *     tsdf_components_info: n_components; n_triangles = n_indices / 3; largest_triangles and largest_label: the component with the most
+ *       triangles, ties going to the smallest label.  For n_vertices == 0: n_components = 0, largest_label = 0xFFFFFFFF,
+ *       largest_triangles = 0.  The largest component is found from T: a tsdf_label_components_device call without
+ *       device_component_triangles reports largest_triangles = 0 and largest_label = 0xFFFFFFFF.
+ *     Nothing depends on the order in which waves run: two runs give the same bytes.
+ *   How: a lock-free union-find over L itself, hooks towards the smaller index (DESIGN.md 20 argues the invariants): parent[v] <= v
+ *     always, a word changes only to a smaller member of the same component, so every chain strictly decreases, the final root is the
+ *     component's minimum and no lane ever waits for another.  Triangle counts are integer atomics.
+ *   tsdf_label_components_device: any index buffer on the device.  Blocking: it synchronises hip_stream once, to read the info and
+ *     the error word.  device_labels (n_vertices words) is its parent array, device_component_triangles (n_vertices words, may be NULL)
+ *     its counter array: the counts land at the roots and are broadcast in place.  Beyond those it holds 32 bytes of device scratch
+ *     for the duration of the call.  An index >= n_vertices is found on the device by the first kernel that reads I, before any lane
+ *     uses it as an address: the call returns TSDF_ERR_INVALID, the two arrays hold unspecified values inside [0, n_vertices) and
+ *     nothing outside that range has been touched.
+ *   tsdf_mesh_label_components: the handle's last extraction (or filter into it).  Labels and sizes are kept in the handle, allocated by
+ *     the first components call (never by tsdf_volume_extract_mesh), until the next extraction or filter into it;
+ *     tsdf_mesh_component_buffers gives the device arrays (NULL for an empty mesh), tsdf_mesh_component_download copies them (either
+ *     pointer may be NULL).  Both refuse a handle that has not been labelled since.
+ *   tsdf_mesh_filter_components: labels src first if it has not been labelled since its last extraction.  A component is kept iff
+ *     T >= min_triangles and, with TSDF_MESH_KEEP_LARGEST, it is the largest one.  dst receives the kept vertices in their order (the
+ *     sort by key survives), the kept triples in their order with indices remapped, normals and colours where src has them as the same
+ *     bytes, info.flags and info.box as src's.  So V'[I'[k]] is the soup's vertex for every kept soup vertex bit for bit, and
+ *     min_triangles == 0 without the flag gives dst equal to src array for array.  An empty src gives an empty dst.  dst keeps its
+ *     arrays and only grows them, as an extraction does.  At most two synchronisations: one for the labelling (when it is needed), one
+ *     for the two counts.  No atomics in the filter: keep flags by ballot over 64 vertices / triples, popcount bases, a chunk scan; a
+ *     new index is a base plus the popcount below the lane.  src and the volume are never written, apart from src's own label arrays.
+ *   Stream order: the mesh calls enqueue on hip_stream (NULL: the default stream) behind the handle's pending extraction, and later
+ *     tsdf_mesh_buffers / tsdf_mesh_download / extractions are ordered behind them in turn.
+ *   Refused (TSDF_ERR_INVALID, with a message): NULL device_labels, NULL device_indices with n_indices > 0, a NULL handle;
+ *     n_indices % 3 != 0; n_vertices or n_indices above 2^32 - 1; an index >= n_vertices; dst == src; unknown flags; handles made on
+ *     different devices.
+ *   Out of scope: slab volumes, welding by position, components of the volume's voxels, simplification and hole filling, labelling
+ *     inside tsdf_volume_extract_mesh, labels that stay stable across re-meshes. */
+typedef struct tsdf_components_info {
+    uint64_t n_components, n_triangles, largest_triangles;
+    uint32_t largest_label;
+} tsdf_components_info;
+#define TSDF_MESH_KEEP_LARGEST 1u
+int tsdf_label_components_device(uint64_t n_vertices, uint64_t n_indices, const uint32_t *device_indices, uint32_t *device_labels,
+                                 uint32_t *device_component_triangles, tsdf_components_info *info, void *hip_stream);
+int tsdf_mesh_label_components(tsdf_mesh *mesh, tsdf_components_info *info, void *hip_stream);
+int tsdf_mesh_component_buffers(const tsdf_mesh *mesh, const uint32_t **device_labels, const uint32_t **device_component_triangles);
+int tsdf_mesh_component_download(const tsdf_mesh *mesh, uint32_t *host_labels, uint32_t *host_component_triangles);
+int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t flags, tsdf_mesh *dst, void *hip_stream);
 
 /* ---- distance field (no reference counterpart: the reference's volume knows the truncated, projective distance only) ------------- */
 /* The Euclidean signed distance field (ESDF) of a whole volume: per voxel, how far the nearest surface is -- what a planner, a

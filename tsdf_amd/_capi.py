@@ -14,6 +14,7 @@ TSDF_OK, TSDF_ERR_INVALID, TSDF_ERR_DEVICE, TSDF_ERR_NOMEM = 0, 1, 2, 3
 TSDF_FIELD_UNIT_GRADIENT = 1
 TSDF_RAYS_BAND_ONLY = 1
 TSDF_MESH_NORMALS, TSDF_MESH_COLOURS = 1, 2
+TSDF_MESH_KEEP_LARGEST = 1
 TSDF_ESDF_FILL_UNKNOWN = 1
 
 
@@ -35,6 +36,12 @@ class VolumeInfo(C.Structure):
 class MeshInfo(C.Structure):
     """struct tsdf_mesh_info (include/tsdf_amd.h)."""
     _fields_ = [("n_vertices", C.c_uint64), ("n_indices", C.c_uint64), ("flags", C.c_uint32), ("box", C.c_uint32 * 6)]
+
+
+class ComponentsInfo(C.Structure):
+    """struct tsdf_components_info (include/tsdf_amd.h)."""
+    _fields_ = [("n_components", C.c_uint64), ("n_triangles", C.c_uint64), ("largest_triangles", C.c_uint64),
+                ("largest_label", C.c_uint32)]
 
 
 class EsdfInfo(C.Structure):
@@ -180,6 +187,11 @@ _SIGS = {
     "tsdf_mesh_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_mesh_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "tsdf_mesh_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_label_components_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.POINTER(ComponentsInfo), _vp]),
+    "tsdf_mesh_label_components": (_i, [_vp, C.POINTER(ComponentsInfo), _vp]),
+    "tsdf_mesh_component_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_mesh_component_download": (_i, [_vp, _vp, _vp]),
+    "tsdf_mesh_filter_components": (_i, [_vp, C.c_uint64, _u32, _vp, _vp]),
     "tsdf_esdf_create": (_i, [C.POINTER(_vp)]),
     "tsdf_esdf_destroy": (None, [_vp]),
     "tsdf_volume_compute_esdf": (_i, [_vp, _f, _u32, _vp]),

@@ -878,6 +878,48 @@ class Mesh:
         check(lib.tsdf_mesh_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
 
+    # ---- mesh components (include/tsdf_amd.h, "mesh components")
+    def label_components(self, stream=0):
+        """Label the connected pieces of the mesh on the device (tsdf_mesh_label_components): returns {n_components, n_triangles,
+        largest_triangles, largest_label}.  The labels and sizes stay in the handle until the next extraction or filter into it."""
+        i = _capi.ComponentsInfo()
+        check(lib.tsdf_mesh_label_components(self._h, C.byref(i), C.c_void_p(int(stream) if stream else 0)))
+        return _components_info(i)
+
+    def _component_download(self, which):
+        out = np.empty(self.n_vertices + 1, np.uint32)   # (see _download)
+        args = [None, None]
+        args[which] = out.ctypes.data
+        check(lib.tsdf_mesh_component_download(self._h, *args))
+        return out[:-1]
+
+    @property
+    def labels(self):
+        """(n_vertices,) uint32: the smallest vertex index of each vertex's component; ValueError unless the mesh was labelled."""
+        return self._component_download(0)
+
+    @property
+    def component_triangles(self):
+        """(n_vertices,) uint32: the triangles of each vertex's component; ValueError unless the mesh was labelled."""
+        return self._component_download(1)
+
+    def component_buffers(self):
+        """(labels, component_triangles) as raw device pointers (0 for an empty mesh); valid until the next extraction or filter into
+        this mesh.  ValueError unless the mesh was labelled."""
+        p = [C.c_void_p() for _ in range(2)]
+        check(lib.tsdf_mesh_component_buffers(self._h, *[C.byref(q) for q in p]))
+        return tuple(int(q.value or 0) for q in p)
+
+    def filter_components(self, min_triangles=0, keep_largest=False, into=None, stream=0):
+        """The mesh without its small pieces, on the device (tsdf_mesh_filter_components): the components with at least
+        `min_triangles` triangles -- with `keep_largest`, the largest one only, if it has that many -- as a Mesh of the kept vertices and
+        triples in their order, indices remapped, normals and colours carried along.  Labels this mesh first if need be.  `into`: a
+        Mesh to reuse (not this one)."""
+        dst = Mesh() if into is None else into
+        flags = _capi.TSDF_MESH_KEEP_LARGEST if keep_largest else 0
+        check(lib.tsdf_mesh_filter_components(self._h, int(min_triangles), flags, dst._h, C.c_void_p(int(stream) if stream else 0)))
+        return dst
+
 
 class ESDF:
     """tsdf_esdf (include/tsdf_amd.h, "distance field"): the device array of a distance field, its scratch and the geometry it was
@@ -968,6 +1010,35 @@ class _DeviceArray:
         if self.ptr.value:
             lib.tsdf_device_free(self.ptr)
             self.ptr = C.c_void_p()
+
+
+def _components_info(i):
+    return {"n_components": int(i.n_components), "n_triangles": int(i.n_triangles), "largest_triangles": int(i.largest_triangles),
+            "largest_label": int(i.largest_label)}
+
+
+def label_components_device(n_vertices, n_indices, indices_ptr, labels_ptr, component_triangles_ptr=0, stream=0):
+    """tsdf_label_components_device on device pointers (uint32 arrays: n_indices indices, n_vertices labels and -- or 0 -- n_vertices
+    sizes): blocking; returns the info dict.  ValueError for an index that is not below n_vertices."""
+    i = _capi.ComponentsInfo()
+    vp = lambda p: C.c_void_p(int(p) if p else 0)
+    check(lib.tsdf_label_components_device(int(n_vertices), int(n_indices), vp(indices_ptr), vp(labels_ptr), vp(component_triangles_ptr),
+                                           C.byref(i), vp(stream)))
+    return _components_info(i)
+
+
+def label_components(n_vertices, indices):
+    """The connected components of the graph whose index triples are `indices` (any integer array of 3 n values below n_vertices), on
+    the device: (labels (n_vertices,) uint32, sizes (n_vertices,) uint32, info)."""
+    I = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.uint32)
+    n = int(n_vertices)
+    labels, sizes = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    with _DeviceArray(I) as di, _DeviceArray(nbytes=4 * max(n, 1)) as dl, _DeviceArray(nbytes=4 * max(n, 1)) as dt:
+        info = label_components_device(n, I.size, di.ptr.value, dl.ptr.value, dt.ptr.value)
+        if n:
+            check(lib.tsdf_device_download(labels.ctypes.data, dl.ptr, labels.nbytes))
+            check(lib.tsdf_device_download(sizes.ctypes.data, dt.ptr, sizes.nbytes))
+    return labels, sizes, info
 
 
 def _pose16(T):

@@ -23,20 +23,9 @@
 #include <new>
 
 #include "common.hpp"
+#include "mesh_handle.hpp"
 
 namespace tsdf {
-
-struct MeshTable {
-    int8_t tri[256][32];   // edge numbers, three per triangle, -1 terminated
-    uint8_t count[256];    // vertices per configuration
-};
-
-// 32 bytes per 64 voxels of the marched range
-struct MeshChunk {
-    uint64_t mx, my, mz;   // bit l: the chunk's l-th voxel has a used edge towards +x / +y / +z
-    uint32_t vbase;        // mesh_edges_kernel: the chunk's vertices; after the scan: the index of its first vertex
-    uint32_t ibase;        // the same for the soup vertices (= indices) of the cubes rooted in the chunk
-};
 
 // the marched cubes [x0, x0 + bx) x [y0, y0 + by) x [z0, z0 + bz), all three counts >= 1, inside a grid of X x Y x Z voxels
 struct MeshBox {
@@ -279,39 +268,7 @@ __global__ __launch_bounds__(256) void mesh_triangles_kernel(const float *__rest
 
 using namespace tsdf;
 
-struct tsdf_mesh {
-    int device;
-    hipEvent_t done;        // recorded behind the last extraction's launches
-    int pending;            // ... and not waited for yet
-    float *vertices;
-    uint32_t *indices;
-    float *normals;
-    uint8_t *rgb;
-    size_t vertices_cap, indices_cap, normals_cap, rgb_cap;   // in elements of the arrays (vertices, indices)
-    MeshChunk *chunks;
-    size_t chunks_cap;
-    uint64_t *parts;        // two sums per 1024 chunks + the two totals
-    size_t parts_cap;       // in words
-    MeshTable *table;       // the device copy of host_table (uploaded again only when the caller's table changes)
-    MeshTable host_table;
-    int table_valid;
-    uint64_t *totals;       // pinned: where the two totals land
-    tsdf_mesh_info info;
-};
-
 namespace {
-
-// Arrays only grow; what they held is not kept.
-template <typename T>
-hipError_t mesh_reserve(T *&p, size_t &cap, size_t want) {
-    if (want <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-}
 
 void mesh_free(tsdf_mesh *m) {
     if (m->done) (void)hipEventSynchronize(m->done);
@@ -322,6 +279,11 @@ void mesh_free(tsdf_mesh *m) {
     if (m->chunks) (void)hipFree(m->chunks);
     if (m->parts) (void)hipFree(m->parts);
     if (m->table) (void)hipFree(m->table);
+    if (m->labels) (void)hipFree(m->labels);
+    if (m->sizes) (void)hipFree(m->sizes);
+    if (m->component_words) (void)hipFree(m->component_words);
+    if (m->keep_masks) (void)hipFree(m->keep_masks);
+    if (m->keep_bases) (void)hipFree(m->keep_bases);
     if (m->totals) (void)hipHostFree(m->totals);
     if (m->done) (void)hipEventDestroy(m->done);
     delete m;
@@ -397,6 +359,7 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
     }
     if (m->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, m->done, 0), "mesh stream order");   // what a previous extraction into this handle left in flight
     m->info.n_vertices = m->info.n_indices = 0;
+    m->labelled = 0;   // (mesh_components.hip)
     m->info.flags = flags;
     for (int a = 0; a < 3; a++) {
         m->info.box[a] = lo[a];
@@ -493,7 +456,10 @@ int tsdf_mesh_download(const tsdf_mesh *m, float *host_vertices, uint32_t *host_
 
 int tsdf_mesh_scratch_bytes(const tsdf_mesh *m, uint64_t *bytes) {
     TSDF_REQUIRE(m && bytes, "tsdf_mesh_scratch_bytes: null argument");
-    *bytes = (uint64_t)m->chunks_cap * sizeof(MeshChunk) + (uint64_t)m->parts_cap * sizeof(uint64_t) + sizeof(MeshTable) + 2 * sizeof(uint64_t);
+    *bytes = (uint64_t)m->chunks_cap * sizeof(MeshChunk) + (uint64_t)m->parts_cap * sizeof(uint64_t) + sizeof(MeshTable) + 2 * sizeof(uint64_t) +
+             // mesh components: labels and sizes, the labelling's words, the keep masks and bases of a filter into the handle
+             (uint64_t)(m->labels_cap + m->sizes_cap) * sizeof(uint32_t) + (m->component_words ? kComponentWords * sizeof(uint64_t) : 0) +
+             (uint64_t)m->keep_masks_cap * sizeof(uint64_t) + (uint64_t)m->keep_bases_cap * sizeof(uint32_t);
     return TSDF_OK;
 }
 

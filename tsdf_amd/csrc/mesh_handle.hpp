@@ -1,0 +1,63 @@
+// struct tsdf_mesh: what mesh.hip (extraction) and mesh_components.hip (labelling, filtering) share.
+#pragma once
+
+#include "common.hpp"
+
+namespace tsdf {
+
+struct MeshTable {
+    int8_t tri[256][32];   // edge numbers, three per triangle, -1 terminated
+    uint8_t count[256];    // vertices per configuration
+};
+
+// 32 bytes per 64 voxels of the marched range
+struct MeshChunk {
+    uint64_t mx, my, mz;   // bit l: the chunk's l-th voxel has a used edge towards +x / +y / +z
+    uint32_t vbase;        // mesh_edges_kernel: the chunk's vertices; after the scan: the index of its first vertex
+    uint32_t ibase;        // the same for the soup vertices (= indices) of the cubes rooted in the chunk
+};
+
+// Arrays only grow; what they held is not kept.
+template <typename T>
+hipError_t mesh_reserve(T *&p, size_t &cap, size_t want) {
+    if (want <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+    if (e == hipSuccess) cap = want;
+    return e;
+}
+
+constexpr size_t kComponentWords = 4;   // tsdf_mesh::component_words, and what tsdf_label_components_device holds for a call
+
+}  // namespace tsdf
+
+struct tsdf_mesh {
+    int device;
+    hipEvent_t done;        // recorded behind the last extraction's (labelling's, filter's) launches
+    int pending;            // ... and not waited for yet
+    float *vertices;
+    uint32_t *indices;
+    float *normals;
+    uint8_t *rgb;
+    size_t vertices_cap, indices_cap, normals_cap, rgb_cap;   // in elements of the arrays (vertices, indices)
+    tsdf::MeshChunk *chunks;
+    size_t chunks_cap;
+    uint64_t *parts;        // two sums per 1024 chunks + the two totals
+    size_t parts_cap;       // in words
+    tsdf::MeshTable *table;       // the device copy of host_table (uploaded again only when the caller's table changes)
+    tsdf::MeshTable host_table;
+    int table_valid;
+    uint64_t *totals;       // pinned: where the two totals land
+    tsdf_mesh_info info;
+    // mesh components (mesh_components.hip): all null until the first components call on / filter into the handle
+    uint32_t *labels, *sizes;          // L and T of the arrays above, one word per vertex each
+    size_t labels_cap, sizes_cap;
+    uint64_t *component_words;         // kComponentWords: error, roots, the largest component's packed word
+    int labelled;                      // labels / sizes / components are those of the arrays above
+    tsdf_components_info components;
+    uint64_t *keep_masks;              // a filter into this handle: one keep mask per 64 vertices, then one per 64 triples, of its source
+    uint32_t *keep_bases;              // ... and their counts / bases
+    size_t keep_masks_cap, keep_bases_cap;
+};

@@ -41,6 +41,15 @@ void extract_surface_indexed(const TSDFVolume *volume, const unsigned box[6], st
                              std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
                              std::vector<uchar3> *colours = nullptr);
 
+// The indexed mesh without its small connected pieces -- the floaters that sensor noise leaves in a fused scan (include/tsdf_amd.h
+// "mesh components"; not in the reference): extracted, labelled and filtered on the device, downloaded once.  A piece is kept when
+// it has at least min_triangles triangles and, with keep_largest, is the one with the most (ties: the one holding the smallest vertex
+// index).  Kept vertices and triangles stay in extract_surface_indexed's order, triangles wired (i, i+2, i+1) as there; box, normals
+// and colours may be null.  The results go straight into the write_to_ply overloads.
+void extract_surface_components(const TSDFVolume *volume, const unsigned box[6], size_t min_triangles, bool keep_largest,
+                                std::vector<float3> &vertices, std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
+                                std::vector<uchar3> *colours = nullptr);
+
 // The same marching cubes over a host distance array (x fastest, voxel centres at (i + 0.5) * voxel_size + offset):
 // appends three vertices per triangle.  extract_surface is this on the volume's distances.
 void tsdf_host_marching_cubes(const float *dist, unsigned X, unsigned Y, unsigned Z, const float voxel_size[3],
