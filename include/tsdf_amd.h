@@ -719,8 +719,8 @@ int tsdf_volume_marching_cubes(const tsdf_volume *volume, const int8_t *table, u
  *   Refused (TSDF_ERR_INVALID, with a message): NULL volume, table or mesh; a Z-slab volume (tsdf_volume_create_slab:
  *     tsdf_volume_marching_cubes serves those); a table tsdf_volume_marching_cubes refuses; unknown flags; more than 2^32 - 1 vertices
  *     or indices (extract in boxes); tsdf_mesh_download into an array the mesh was extracted without.
- *   Out of scope: slab volumes, skipping empty rows by the occupancy flags (their "low voxel" is not the sign test), welding by
- *     position, simplification. */
+ *   Out of scope: slab volumes, skipping empty rows by the occupancy flags (their "low voxel" is not the sign test).  Welding by
+ *     position and simplification are the group "mesh simplification" below. */
 typedef struct tsdf_mesh tsdf_mesh;
 #define TSDF_MESH_NORMALS 1u
 #define TSDF_MESH_COLOURS 2u
@@ -741,7 +741,7 @@ int tsdf_mesh_buffers(const tsdf_mesh *mesh, const float **device_vertices, cons
 int tsdf_mesh_download(const tsdf_mesh *mesh, float *host_vertices, uint32_t *host_indices, float *host_normals, uint8_t *host_rgb);
 /* Device bytes the handle holds besides the four output arrays.  After an extraction alone that is the bound above; the first
  * components call (group "mesh components") adds 8 bytes per vertex (labels and sizes) and 32 bytes, a filter INTO the handle 12 bytes
- * per 64 vertices and per 64 triples of its source. */
+ * per 64 vertices and per 64 triples of its source, a simplification INTO the handle what the group "mesh simplification" states. */
 int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
 
 /* ---- mesh components (no reference counterpart: the reference's soup has no connectivity to ask about) ----------------------------- */
@@ -786,8 +786,8 @@ int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
  *   Refused (TSDF_ERR_INVALID, with a message): NULL device_labels, NULL device_indices with n_indices > 0, a NULL handle;
  *     n_indices % 3 != 0; n_vertices or n_indices above 2^32 - 1; an index >= n_vertices; dst == src; unknown flags; handles made on
  *     different devices.
- *   Out of scope: slab volumes, welding by position, components of the volume's voxels, simplification and hole filling, labelling
- *     inside tsdf_volume_extract_mesh, labels that stay stable across re-meshes. */
+ *   Out of scope: slab volumes, components of the volume's voxels, hole filling, labelling inside tsdf_volume_extract_mesh, labels
+ *     that stay stable across re-meshes.  Welding by position and simplification are the group "mesh simplification" below. */
 typedef struct tsdf_components_info {
     uint64_t n_components, n_triangles, largest_triangles;
     uint32_t largest_label;
@@ -799,6 +799,65 @@ int tsdf_mesh_label_components(tsdf_mesh *mesh, tsdf_components_info *info, void
 int tsdf_mesh_component_buffers(const tsdf_mesh *mesh, const uint32_t **device_labels, const uint32_t **device_component_triangles);
 int tsdf_mesh_component_download(const tsdf_mesh *mesh, uint32_t *host_labels, uint32_t *host_component_triangles);
 int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t flags, tsdf_mesh *dst, void *hip_stream);
+
+/* ---- mesh simplification (no reference counterpart: the reference's soup goes to a file as it is) ---------------------------------- */
+/* A level of detail of an indexed mesh, made on the device: vertex clustering on a grid of cubic cells (Rossignac-Borrel).  The vertices
+ * of one cell become one vertex, the mean of its members; triples that no longer have three corners are dropped.  Opt-in by being
+ * called: no other entry point, launch or result changes.
+ *   The result (unique values, whatever computes them), with h = cell_size, fp32, finite and > 0:
+ *   1. Cell.  f_a = floorf(V_a / h) per axis a: one fp32 divide, correctly rounded, then floor.  A vertex is LOOSE if any coordinate is
+ *     not finite, or any |f_a| is not < 2^20, or any |V_a| is not < 2^21 (tested in float, before anything becomes an integer); a
+ *     loose vertex is a cluster of its own.  Every other vertex has the 63-bit key ((f_z + 2^20) << 42) | ((f_y + 2^20) << 21) |
+ *     (f_x + 2^20); vertices with equal keys form a cluster.  (Extracted meshes carry loose vertices: the NaN crossings next to a NaN
+ *     voxel.)
+ *   2. Order.  A cluster's representative is its member with the smallest source index; output vertex j is the cluster whose
+ *     representative is the j-th smallest.  So the order of an extracted mesh (sorted by lattice-edge key) survives as far as it can.
+ *     A cluster is an output vertex whether or not a kept triple names it: tsdf_mesh_filter_components(dst, 1, 0, ...) removes the
+ *     unreferenced ones.
+ *   3. Position.  A cluster of one member (a loose vertex included) keeps that member's 12 bytes: -0.0, NaN and denormals survive.
+ *     Otherwise, per axis, q = llrintf(V_a * 1024.0f) (the product is exact, the rounding to nearest-even), S the int64 sum of q over
+ *     the n members, and the output is (float)(((double)S / (double)n) / 1024.0).  Integers are summed, so no arrival order can change
+ *     the sum; a member moves by at most 2^-11 of the unit (mm), fp32's own spacing at 4 m.
+ *   4. Normals (when given).  A cluster of one keeps the bytes.  Otherwise d_a = the sum of llrintf(N_a * 1048576.0f) over the members
+ *     whose normal is finite in all three components, as doubles; L = sqrt(d_x * d_x + d_y * d_y + d_z * d_z) in double arithmetic, no
+ *     contraction, added left to right; the output is (float)(d_a / L), and a NaN triple when L == 0 (no finite member, or the normals
+ *     cancel).  Normals are expected to be of unit size or thereabouts: a component at or above 2^20 may overflow a sum.
+ *   5. Colours (when given).  Per channel (2 S + n) / (2 n) in integers, S the sum of the members' bytes: the mean rounded half up, as
+ *     the colour blend rounds.  A cluster of one is its own byte.
+ *   6. Triples.  Each index is replaced by its cluster's output index; a triple with two equal new indices is dropped (one that was
+ *     degenerate in the source included); the rest stay in their order, wiring and winding untouched.  Two triples on the same three
+ *     clusters are both kept.
+ *   7. The position weld.  With a cell so small that no two distinct positions share one, the result is the source minus its exactly
+ *     coincident vertices (which an extracted mesh has where a voxel is exactly 0: "welding is by lattice edge") and the triples that
+ *     die with them.
+ *   8. dst->info: n_vertices = the clusters, n_indices = 3 x the kept triples, flags = TSDF_MESH_NORMALS / TSDF_MESH_COLOURS according to
+ *     the arrays given; dst is not labelled.  An empty source gives an empty dst; vertices with n_indices == 0 are legal.
+ *   tsdf_simplify_mesh_device: any arrays on the device (3 floats per vertex, one uint32 per index, 3 floats / 3 bytes per vertex or
+ *     NULL); dst->info.box is all zero.  tsdf_mesh_simplify: src's arrays, normals and colours where src has them, info.box = src's.
+ *   How: no sort.  One lane per vertex puts its key into an open-addressed table of the smallest power of two >= 2 n_vertices slots
+ *     with one 64-bit compare-and-swap per probe, linear probing; a probe ends on "was empty" or "was my key", anything else moves on.
+ *     No lane waits for another: at load <= 1/2 an empty slot lies on every walk.  The slot's representative word takes
+ *     an atomicMin of the vertex index.  Keep bits by ballot over 64, popcount bases and the chunk scan are the components filter's;
+ *     the sums are integer atomics into dense per-cluster rows; one lane per cluster divides.  No float is ever added atomically.
+ *   At most one synchronisation of hip_stream (NULL: the default stream), to size dst's arrays from the two counts and read the error
+ *     word; the call returns with the kernels that fill the arrays enqueued, and stream order is that of the components filter.  src
+ *     and the volume are never written.  dst keeps its arrays and scratch and only grows them: a warm re-simplify allocates nothing.
+ *   Scratch of a simplification into dst, counted by tsdf_mesh_scratch_bytes(dst), with P the smallest power of two >= 2 n_vertices
+ *     (so P < 4 n_vertices) and n_clusters the output's vertices:
+ *       12 P + 4 n_vertices + 80 n_clusters + 12 (ceil(n_vertices / 64) + ceil(n_triples / 64)) + 16 (ceil(chunks / 1024) + 1) + 8
+ *     bytes, chunks the larger of the two ceilings (8 bytes of key and 4 of representative per slot, 4 per vertex, up to 10 words per
+ *     cluster, the filter's masks and bases, the scan's parts), on top of what the handle held before.
+ *   Refused (TSDF_ERR_INVALID, with a message, before any device work where the host can tell): NULL dst or src; NULL vertices with
+ *     n_vertices > 0, NULL indices with n_indices > 0; n_indices % 3 != 0; counts above 2^32 - 1; more than 2^30 vertices (the table's
+ *     slots are numbered in 32 bits: simplify in boxes); cell_size not finite or not > 0; flags other than 0 (there are none yet);
+ *     dst == src; handles made on different devices; an index >= n_vertices -- found on the device by the first kernel that reads I,
+ *     before any lane uses it as an address: the call returns the error and dst is left empty.
+ *   Out of scope: removing duplicate triangles, quadric error placement, edge collapse, smoothing, preserving boundaries or
+ *     manifoldness, simplifying inside tsdf_volume_extract_mesh, slab volumes (they have no indexed mesh). */
+int tsdf_simplify_mesh_device(uint64_t n_vertices, uint64_t n_indices, const float *device_vertices, const uint32_t *device_indices,
+                              const float *device_normals, const uint8_t *device_rgb, float cell_size, uint32_t flags, tsdf_mesh *dst,
+                              void *hip_stream);
+int tsdf_mesh_simplify(tsdf_mesh *src, float cell_size, uint32_t flags, tsdf_mesh *dst, void *hip_stream);
 
 /* ---- distance field (no reference counterpart: the reference's volume knows the truncated, projective distance only) ------------- */
 /* The Euclidean signed distance field (ESDF) of a whole volume: per voxel, how far the nearest surface is -- what a planner, a

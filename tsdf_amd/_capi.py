@@ -192,6 +192,8 @@ _SIGS = {
     "tsdf_mesh_component_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_mesh_component_download": (_i, [_vp, _vp, _vp]),
     "tsdf_mesh_filter_components": (_i, [_vp, C.c_uint64, _u32, _vp, _vp]),
+    "tsdf_simplify_mesh_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_float, _u32, _vp, _vp]),
+    "tsdf_mesh_simplify": (_i, [_vp, C.c_float, _u32, _vp, _vp]),
     "tsdf_esdf_create": (_i, [C.POINTER(_vp)]),
     "tsdf_esdf_destroy": (None, [_vp]),
     "tsdf_volume_compute_esdf": (_i, [_vp, _f, _u32, _vp]),

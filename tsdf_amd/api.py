@@ -920,6 +920,16 @@ class Mesh:
         check(lib.tsdf_mesh_filter_components(self._h, int(min_triangles), flags, dst._h, C.c_void_p(int(stream) if stream else 0)))
         return dst
 
+    # ---- mesh simplification (include/tsdf_amd.h, "mesh simplification")
+    def simplify(self, cell_size, into=None, stream=0):
+        """A level of detail of the mesh, on the device (tsdf_mesh_simplify): the vertices of each cubic cell of side `cell_size` (mm)
+        become one vertex -- the mean of their positions, normals and colours -- and the triples left with fewer than three corners are
+        dropped.  Returns a Mesh (`into`: one to reuse, not this one); vertices no triple names any more stay until
+        filter_components(1) removes them.  A tiny cell welds exactly coincident vertices and changes nothing else."""
+        dst = Mesh() if into is None else into
+        check(lib.tsdf_mesh_simplify(self._h, float(cell_size), 0, dst._h, C.c_void_p(int(stream) if stream else 0)))
+        return dst
+
 
 class ESDF:
     """tsdf_esdf (include/tsdf_amd.h, "distance field"): the device array of a distance field, its scratch and the geometry it was
@@ -1039,6 +1049,37 @@ def label_components(n_vertices, indices):
             check(lib.tsdf_device_download(labels.ctypes.data, dl.ptr, labels.nbytes))
             check(lib.tsdf_device_download(sizes.ctypes.data, dt.ptr, sizes.nbytes))
     return labels, sizes, info
+
+
+def simplify_mesh_device(n_vertices, n_indices, vertices_ptr, indices_ptr, cell_size, into, normals_ptr=0, colours_ptr=0, stream=0):
+    """tsdf_simplify_mesh_device on device pointers (float32 x 3 vertices, uint32 indices, float32 x 3 normals or 0, uint8 x 3 colours
+    or 0) into the Mesh `into`, which is returned.  ValueError for an index that is not below n_vertices."""
+    vp = lambda p: C.c_void_p(int(p) if p else 0)
+    check(lib.tsdf_simplify_mesh_device(int(n_vertices), int(n_indices), vp(vertices_ptr), vp(indices_ptr), vp(normals_ptr), vp(colours_ptr),
+                                        float(cell_size), 0, into._h, vp(stream)))
+    return into
+
+
+def simplify_mesh(vertices, indices, cell_size, normals=None, colours=None):
+    """Vertex clustering of host arrays on the device (upload, tsdf_simplify_mesh_device, download): (n, 3) float32 vertices, 3 m
+    indices, optionally (n, 3) float32 normals and (n, 3) uint8 colours -> (vertices, indices, normals or None, colours or None)."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    I = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.uint32)
+    N = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    RGB = None if colours is None else np.ascontiguousarray(colours, np.uint8).reshape(-1, 3)
+    for a, what in ((N, "normals"), (RGB, "colours")):
+        if a is not None and len(a) != len(V):
+            raise ValueError("%d %s for %d vertices" % (len(a), what, len(V)))
+    dst = Mesh()
+    try:
+        with _DeviceArray(V) as dv, _DeviceArray(I) as di, _DeviceArray(nbytes=4) as none:
+            with _DeviceArray(N if N is not None and len(V) else None, 0) as dn, _DeviceArray(RGB if RGB is not None and len(V) else None, 0) as dc:
+                # (an empty array given is still "given": any non-null pointer says so, nothing is read through it)
+                given = lambda a, d: 0 if a is None else (d.ptr.value or none.ptr.value)
+                simplify_mesh_device(len(V), I.size, dv.ptr.value, di.ptr.value, cell_size, dst, given(N, dn), given(RGB, dc))
+                return dst.vertices, dst.indices, None if N is None else dst.normals, None if RGB is None else dst.colours
+    finally:
+        dst.close()
 
 
 def _pose16(T):

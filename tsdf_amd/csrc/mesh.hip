@@ -284,6 +284,10 @@ void mesh_free(tsdf_mesh *m) {
     if (m->component_words) (void)hipFree(m->component_words);
     if (m->keep_masks) (void)hipFree(m->keep_masks);
     if (m->keep_bases) (void)hipFree(m->keep_bases);
+    if (m->cell_keys) (void)hipFree(m->cell_keys);
+    if (m->cell_reps) (void)hipFree(m->cell_reps);
+    if (m->cluster_of) (void)hipFree(m->cluster_of);
+    if (m->cluster_sums) (void)hipFree(m->cluster_sums);
     if (m->totals) (void)hipHostFree(m->totals);
     if (m->done) (void)hipEventDestroy(m->done);
     delete m;
@@ -459,7 +463,10 @@ int tsdf_mesh_scratch_bytes(const tsdf_mesh *m, uint64_t *bytes) {
     *bytes = (uint64_t)m->chunks_cap * sizeof(MeshChunk) + (uint64_t)m->parts_cap * sizeof(uint64_t) + sizeof(MeshTable) + 2 * sizeof(uint64_t) +
              // mesh components: labels and sizes, the labelling's words, the keep masks and bases of a filter into the handle
              (uint64_t)(m->labels_cap + m->sizes_cap) * sizeof(uint32_t) + (m->component_words ? kComponentWords * sizeof(uint64_t) : 0) +
-             (uint64_t)m->keep_masks_cap * sizeof(uint64_t) + (uint64_t)m->keep_bases_cap * sizeof(uint32_t);
+             (uint64_t)m->keep_masks_cap * sizeof(uint64_t) + (uint64_t)m->keep_bases_cap * sizeof(uint32_t) +
+             // mesh simplification: the cell table, the per-vertex cluster word and the per-cluster sums of a simplification into the handle
+             (uint64_t)m->cell_keys_cap * sizeof(uint64_t) + (uint64_t)(m->cell_reps_cap + m->cluster_of_cap) * sizeof(uint32_t) +
+             (uint64_t)m->cluster_sums_cap * sizeof(int64_t);
     return TSDF_OK;
 }
 

@@ -19,11 +19,13 @@
 //      the word smaller, and the loop goes on from the value it returned; every loop is bounded by a strictly decreasing index.
 // The results are unique values (a minimum, integer sums, a maximum with a total order), so two runs give the same bytes.
 //
-// The filter has no atomics: keep flags per vertex and per triple by ballot over 64, popcount bases, the chunk scan of mesh.hip, and
-// a stable compaction in which a new index is a base plus the popcount below the lane.
+// The filter has no atomics: keep flags per vertex and per triple by ballot over 64, popcount bases, the chunk scan of mesh.hip (the two
+// scans live in mesh_compact.hpp, which mesh_simplify.hip shares), and a stable compaction in which a new index is a base plus the
+// popcount below the lane.
 #include <new>
 
 #include "common.hpp"
+#include "mesh_compact.hpp"
 #include "mesh_handle.hpp"
 
 namespace tsdf {
@@ -138,14 +140,6 @@ struct KeepRule {
     __device__ bool keeps(uint32_t label, uint32_t count) const { return count >= min_triangles && (!only || label == only_label); }
 };
 
-__device__ inline uint32_t keep_inclusive_sum(uint32_t v, uint32_t lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(v, o);
-        if ((int)lane >= o) v += up;
-    }
-    return v;
-}
-
 // One wave per chunk of 64 vertices and, with the same number, of 64 triples: the keep masks and their popcounts.
 __global__ __launch_bounds__(256) void components_keep_kernel(uint32_t n_vertices, uint32_t n_triples, const uint32_t *__restrict__ indices,
                                                               const uint32_t *__restrict__ labels, const uint32_t *__restrict__ sizes, const KeepRule rule,
@@ -172,87 +166,6 @@ __global__ __launch_bounds__(256) void components_keep_kernel(uint32_t n_vertice
             t_base[chunk] = (uint32_t)__popcll(m);
         }
     }
-}
-
-// The two exclusive scans, in the shape of mesh_scan_*_kernel (mesh.hip), over two arrays of their own lengths.
-// part[2 p], part[2 p + 1]: the sums of workgroup p's 1024 chunks
-__global__ __launch_bounds__(1024) void components_scan_sums_kernel(const uint32_t *__restrict__ v_base, uint32_t v_chunks, const uint32_t *__restrict__ t_base,
-                                                                    uint32_t t_chunks, uint64_t *__restrict__ part) {
-    __shared__ uint32_t sv[16], st[16];
-    const uint32_t i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t v = keep_inclusive_sum(i < v_chunks ? v_base[i] : 0u, lane);
-    const uint32_t t = keep_inclusive_sum(i < t_chunks ? t_base[i] : 0u, lane);
-    if (lane == 63) {
-        sv[wave] = v;
-        st[wave] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t a = 0, c = 0;
-        for (int w = 0; w < 16; w++) {
-            a += sv[w];
-            c += st[w];
-        }
-        part[2 * blockIdx.x] = a;
-        part[2 * blockIdx.x + 1] = c;
-    }
-}
-
-// In place, one workgroup: part[2 p], part[2 p + 1] = the sums of the parts before p; part[2 n_parts], [2 n_parts + 1] = the totals.
-__global__ __launch_bounds__(1024) void components_scan_parts_kernel(uint64_t *__restrict__ part, uint32_t n_parts) {
-    __shared__ uint64_t wave_sum[2][16];
-    __shared__ uint64_t carry[2];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x < 2) carry[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t first = 0; first < n_parts; first += 1024) {
-        const uint32_t i = first + threadIdx.x;
-        uint64_t v[2], incl[2];
-        for (int k = 0; k < 2; k++) {
-            v[k] = i < n_parts ? part[2 * (size_t)i + k] : 0;
-            incl[k] = v[k];
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint64_t up = __shfl_up(incl[k], o);
-                if ((int)lane >= o) incl[k] += up;
-            }
-            if (lane == 63) wave_sum[k][wave] = incl[k];
-        }
-        __syncthreads();
-        uint64_t before[2];
-        for (int k = 0; k < 2; k++) {
-            before[k] = carry[k];
-            for (uint32_t w = 0; w < wave; w++) before[k] += wave_sum[k][w];
-            if (i < n_parts) part[2 * (size_t)i + k] = before[k] + incl[k] - v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) {
-            carry[0] = before[0] + incl[0];
-            carry[1] = before[1] + incl[1];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 2) part[2 * (size_t)n_parts + threadIdx.x] = carry[threadIdx.x];
-}
-
-// counts -> bases (the totals are at most the source's counts, which fit 32 bits)
-__global__ __launch_bounds__(1024) void components_scan_apply_kernel(uint32_t *__restrict__ v_base, uint32_t v_chunks, uint32_t *__restrict__ t_base,
-                                                                     uint32_t t_chunks, const uint64_t *__restrict__ part) {
-    __shared__ uint32_t sv[16], st[16];
-    const uint32_t i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t v = i < v_chunks ? v_base[i] : 0u, t = i < t_chunks ? t_base[i] : 0u;
-    const uint32_t iv = keep_inclusive_sum(v, lane), it = keep_inclusive_sum(t, lane);
-    if (lane == 63) {
-        sv[wave] = iv;
-        st[wave] = it;
-    }
-    __syncthreads();
-    uint32_t bv = (uint32_t)part[2 * blockIdx.x], bt = (uint32_t)part[2 * blockIdx.x + 1];
-    for (uint32_t w = 0; w < wave; w++) {
-        bv += sv[w];
-        bt += st[w];
-    }
-    if (i < v_chunks) v_base[i] = bv + iv - v;
-    if (i < t_chunks) t_base[i] = bt + it - t;
 }
 
 // Stable compaction: a kept vertex goes to its chunk's base plus the kept vertices below its lane; normals and colours go with it.
@@ -293,8 +206,6 @@ using namespace tsdf;
 
 namespace {
 
-inline dim3 grid_for(uint64_t n, uint32_t per_block) { return dim3((uint32_t)((n + per_block - 1) / per_block)); }
-
 // The five launches and the one synchronisation.  `words`: kComponentWords device words.  n_vertices > 0.
 int label_on(uint32_t n_vertices, uint32_t n_indices, const uint32_t *indices, uint32_t *labels, uint32_t *sizes, uint64_t *words,
              tsdf_components_info *info, hipStream_t stream, const char *who) {
@@ -322,18 +233,6 @@ int label_on(uint32_t n_vertices, uint32_t n_indices, const uint32_t *indices, u
 }
 
 const tsdf_components_info kNoComponents = {0, 0, 0, 0xffffffffu};
-
-// the stream waits for what is in flight on the handle
-int mesh_join(tsdf_mesh *m, hipStream_t stream) {
-    if (m->pending) TSDF_HIP(hipStreamWaitEvent(stream, m->done, 0), "mesh stream order");
-    return TSDF_OK;
-}
-
-int mesh_leave(tsdf_mesh *m, hipStream_t stream) {
-    TSDF_HIP(hipEventRecord(m->done, stream), "mesh event");
-    m->pending = 1;
-    return TSDF_OK;
-}
 
 int mesh_label(tsdf_mesh *m, hipStream_t stream, const char *who) {
     m->labelled = 0;

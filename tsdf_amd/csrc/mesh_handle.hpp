@@ -1,4 +1,4 @@
-// struct tsdf_mesh: what mesh.hip (extraction) and mesh_components.hip (labelling, filtering) share.
+// struct tsdf_mesh: what mesh.hip (extraction), mesh_components.hip (labelling, filtering) and mesh_simplify.hip (clustering) share.
 #pragma once
 
 #include "common.hpp"
@@ -60,4 +60,12 @@ struct tsdf_mesh {
     uint64_t *keep_masks;              // a filter into this handle: one keep mask per 64 vertices, then one per 64 triples, of its source
     uint32_t *keep_bases;              // ... and their counts / bases
     size_t keep_masks_cap, keep_bases_cap;
+    // mesh simplification (mesh_simplify.hip): all null until the first simplification INTO the handle; of its source:
+    uint64_t *cell_keys;               // the open-addressed table of cell keys, a power of two >= 2 n_vertices words
+    uint32_t *cell_reps;               // ... and per slot the smallest vertex index that holds the key
+    size_t cell_keys_cap, cell_reps_cap;
+    uint32_t *cluster_of;              // per vertex: its slot, then its cluster's representative, then its output index
+    size_t cluster_of_cap;
+    int64_t *cluster_sums;             // per cluster: the count and the integer sums of positions (normals, colours)
+    size_t cluster_sums_cap;           // in words
 };

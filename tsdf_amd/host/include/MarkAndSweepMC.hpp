@@ -50,6 +50,16 @@ void extract_surface_components(const TSDFVolume *volume, const unsigned box[6],
                                 std::vector<float3> &vertices, std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
                                 std::vector<uchar3> *colours = nullptr);
 
+// A level of detail of the indexed mesh (include/tsdf_amd.h "mesh simplification"; not in the reference): extracted and clustered on the
+// device, downloaded once.  The vertices of each cubic cell of side cell_size (mm) become one vertex -- the mean of their positions,
+// normals and colours -- in the order of each cell's first vertex; triangles left with fewer than three corners are dropped, the rest
+// stay in extract_surface_indexed's order, wired (i, i+2, i+1) as there.  Vertices that no triangle names any more stay in the
+// arrays.  box, normals and colours may be null; a cell_size that is not a finite length above 0 throws std::invalid_argument.  The
+// results go straight into the write_to_ply overloads.
+void extract_surface_simplified(const TSDFVolume *volume, const unsigned box[6], float cell_size, std::vector<float3> &vertices,
+                                std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
+                                std::vector<uchar3> *colours = nullptr);
+
 // The same marching cubes over a host distance array (x fastest, voxel centres at (i + 0.5) * voxel_size + offset):
 // appends three vertices per triangle.  extract_surface is this on the volume's distances.
 void tsdf_host_marching_cubes(const float *dist, unsigned X, unsigned Y, unsigned Z, const float voxel_size[3],
