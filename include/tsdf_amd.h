@@ -741,7 +741,8 @@ int tsdf_mesh_buffers(const tsdf_mesh *mesh, const float **device_vertices, cons
 int tsdf_mesh_download(const tsdf_mesh *mesh, float *host_vertices, uint32_t *host_indices, float *host_normals, uint8_t *host_rgb);
 /* Device bytes the handle holds besides the four output arrays.  After an extraction alone that is the bound above; the first
  * components call (group "mesh components") adds 8 bytes per vertex (labels and sizes) and 32 bytes, a filter INTO the handle 12 bytes
- * per 64 vertices and per 64 triples of its source, a simplification INTO the handle what the group "mesh simplification" states. */
+ * per 64 vertices and per 64 triples of its source, a simplification INTO the handle what the group "mesh simplification" states, a
+ * scene-flow call WITH the handle what the group "scene flow" states. */
 int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
 
 /* ---- mesh components (no reference counterpart: the reference's soup has no connectivity to ask about) ----------------------------- */
@@ -858,6 +859,62 @@ int tsdf_simplify_mesh_device(uint64_t n_vertices, uint64_t n_indices, const flo
                               const float *device_normals, const uint8_t *device_rgb, float cell_size, uint32_t flags, tsdf_mesh *dst,
                               void *hip_stream);
 int tsdf_mesh_simplify(tsdf_mesh *src, float cell_size, uint32_t flags, tsdf_mesh *dst, void *hip_stream);
+
+/* ---- scene flow (replaces the device part of process_frames, src/SceneFusion/SceneFusion_krnl.cu:235-401) ------------------------- */
+/* One frame of the reference's non-rigid step: the mesh vertices a depth frame sees take the scene flow at their pixel, and the flow
+ * is pushed into the deformation nodes of the two voxels that bracket each vertex -- the reference's update made deterministic.  Opt-in
+ * by being called: a volume on which these are never called allocates and launches nothing new.
+ *   Inputs: a whole volume; a mesh handle holding an indexed extraction of that volume's WHOLE grid (tsdf_volume_extract_mesh with a
+ *     NULL box: V, I and the handle's per-64-voxel edge records are used); a depth image (uint16, width * height, 0 = invalid); a
+ *     scene-flow image (width * height float triples, row major, world units); pose, inv_pose, k, kinv as tsdf_integrate takes them;
+ *     threshold > 0 (the reference hard-codes 10).
+ *   The result (a unique set of bits, whatever computes it; all arithmetic fp32, every operation rounded on its own):
+ *   1. Correspondence (find_mesh_vertex_correspondences, :74-114).  For shared vertex e with position p: pix = world_to_pixel(p,
+ *     inv_pose, k) in the reference's operation order (src/Utilities/cuda_coordinate_transforms.cu:10-30; roundf, saturating
+ *     conversion, NaN -> 0).  e corresponds iff pix is inside the image, the depth there is > 0 and
+ *     fabsf(pixel_to_world(pix, pose, kinv, depth).z - p.z) < threshold (:40-67, its division by w included) -- and, ours, the flow
+ *     triple at pix is finite in all three components.  Its pixel index is pix.y * width + pix.x.
+ *     TSDF_SCENE_FLOW_DEFORMED: p is V[e] pushed through the volume's current deformation first (the arithmetic of
+ *     tsdf_volume_deform_points_device, global rotation and translation included, on a scratch copy: the handle's vertices do not
+ *     change) -- what the second and later frames of a sequence need.  Without it p is the canonical vertex, as in the reference.
+ *   2. Multiplicity.  m(e) = the number of k with I[k] == e: the soup vertices on edge e (the reference counts soup vertices,
+ *     src/MarchingCubes/MarkAndSweepMC.cu:297-298).  count[v] = the sum of m(e) over the up to six used edges that end in voxel v.
+ *   3. Update.  For every voxel v with count[v] > 0, its incident edges taken in the order -x, +x, -y, +y, -z, +z: acc = 0; for
+ *     every used incident edge that corresponds, per component, acc = acc + (float)m(e) * flow[pix(e)]; then
+ *     translation = translation + (1.0f / (float)count[v]) * acc.  rotation is untouched; a node none of whose edges corresponds
+ *     keeps its bytes.  This is the reference's sum with one thread running at a time, up to the order of the additions.
+ *   Side effects: the node array is materialised as tsdf_volume_deformation does it, a brick list prepared ahead is discarded as
+ *     tsdf_volume_set_deformation does it.  Distances, weights and colours are never written.
+ *   info (may be NULL): the mesh's vertices, the vertices that correspond, the nodes written (those with a corresponding edge).
+ *   How: one lane per vertex finds its pixel; integer atomic adds over I count m; one wave per 64-voxel record GATHERS each voxel's
+ *     six edges from mask bits (an edge's vertex index is a base plus popcounts, as in the extraction), so every node has one writer
+ *     and no float is added atomically; a wave with no used edge near its 64 voxels leaves after reading the masks.  The same bytes on
+ *     every run.
+ *   Scratch lives in the mesh handle, only grows and is counted by tsdf_mesh_scratch_bytes: 8 bytes per vertex (pixel index and
+ *     multiplicity), 12 more per vertex once TSDF_SCENE_FLOW_DEFORMED was asked for, 16 bytes of counters; the host variant also
+ *     keeps its uploads of the two images (14 bytes per pixel).
+ *   Stream order: tsdf_volume_apply_scene_flow uploads and enqueues on the volume's stream.  tsdf_volume_apply_scene_flow_device
+ *     enqueues on hip_stream (NULL: the default stream) behind the handle's pending extraction; ordering hip_stream against other
+ *     work on the volume's stream is the caller's.  Either synchronises its stream once, to read the info; with info == NULL the
+ *     device variant returns with its kernels enqueued.  (The first call on a volume whose nodes are still implicit also waits for
+ *     their materialisation, as tsdf_volume_deformation does.)  A later extraction into the handle is ordered behind the kernels.
+ *   Refused (TSDF_ERR_INVALID, with a message, before any device work): NULL arguments other than info; a Z-slab volume; a mesh that
+ *     is not a whole-grid extraction of a volume of these dimensions (a box, a filter's or a simplification's output, a handle never
+ *     extracted into); a non-finite matrix entry; a threshold that is not > 0 (NaN included); unknown flags; an image of no pixels or
+ *     of 2^32 - 1 or more; handles made on different devices; TSDF_SCENE_FLOW_DEFORMED with more than 2^31 - 1 vertices.  An empty mesh
+ *     is a successful no-op: nothing is allocated, launched or materialised, the info is all zero.
+ *   Out of scope: the SceneFusion class, RGBDDevice and MockKinect, the scene-flow file loaders and TinyXml, rotations of nodes, ray
+ *     casts in the deformed space, use inside the tracker or kinfu_stream. */
+#define TSDF_SCENE_FLOW_DEFORMED 1u
+typedef struct tsdf_scene_flow_info {
+    uint64_t n_vertices, n_correspondences, n_nodes_moved;
+} tsdf_scene_flow_info;
+int tsdf_volume_apply_scene_flow(tsdf_volume *volume, tsdf_mesh *mesh, const uint16_t *host_depth, const float *host_flow, uint32_t width,
+                                 uint32_t height, const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9],
+                                 float threshold, uint32_t flags, tsdf_scene_flow_info *info);
+int tsdf_volume_apply_scene_flow_device(tsdf_volume *volume, tsdf_mesh *mesh, const uint16_t *device_depth, const float *device_flow,
+                                        uint32_t width, uint32_t height, const float pose[16], const float inv_pose[16], const float k[9],
+                                        const float kinv[9], float threshold, uint32_t flags, tsdf_scene_flow_info *info, void *hip_stream);
 
 /* ---- distance field (no reference counterpart: the reference's volume knows the truncated, projective distance only) ------------- */
 /* The Euclidean signed distance field (ESDF) of a whole volume: per voxel, how far the nearest surface is -- what a planner, a

@@ -16,6 +16,7 @@ TSDF_RAYS_BAND_ONLY = 1
 TSDF_MESH_NORMALS, TSDF_MESH_COLOURS = 1, 2
 TSDF_MESH_KEEP_LARGEST = 1
 TSDF_ESDF_FILL_UNKNOWN = 1
+TSDF_SCENE_FLOW_DEFORMED = 1
 
 
 class TsdfError(RuntimeError):
@@ -42,6 +43,11 @@ class ComponentsInfo(C.Structure):
     """struct tsdf_components_info (include/tsdf_amd.h)."""
     _fields_ = [("n_components", C.c_uint64), ("n_triangles", C.c_uint64), ("largest_triangles", C.c_uint64),
                 ("largest_label", C.c_uint32)]
+
+
+class SceneFlowInfo(C.Structure):
+    """struct tsdf_scene_flow_info (include/tsdf_amd.h)."""
+    _fields_ = [("n_vertices", C.c_uint64), ("n_correspondences", C.c_uint64), ("n_nodes_moved", C.c_uint64)]
 
 
 class EsdfInfo(C.Structure):
@@ -194,6 +200,8 @@ _SIGS = {
     "tsdf_mesh_filter_components": (_i, [_vp, C.c_uint64, _u32, _vp, _vp]),
     "tsdf_simplify_mesh_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_float, _u32, _vp, _vp]),
     "tsdf_mesh_simplify": (_i, [_vp, C.c_float, _u32, _vp, _vp]),
+    "tsdf_volume_apply_scene_flow": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _f, _u32, C.POINTER(SceneFlowInfo)]),
+    "tsdf_volume_apply_scene_flow_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _f, _u32, C.POINTER(SceneFlowInfo), _vp]),
     "tsdf_esdf_create": (_i, [C.POINTER(_vp)]),
     "tsdf_esdf_destroy": (None, [_vp]),
     "tsdf_volume_compute_esdf": (_i, [_vp, _f, _u32, _vp]),

@@ -205,6 +205,14 @@ class TSDFVolume:
         a = self._host(nodes, 6)
         check(lib.tsdf_volume_set_deformation(self._h, a.ctypes.data))
 
+    def get_deformation(self):
+        """The deformation nodes as (voxels, 6) float32 (tsdf_volume_get_deformation_planes over the resident planes): what
+        set_deformation takes; the regular grid while the nodes are implicit.  Blocking."""
+        z0, z1 = self.resident_planes()
+        a = np.empty((self.resident_voxels(), 6), np.float32)
+        check(lib.tsdf_volume_get_deformation_planes(self._h, 0, z1 - z0, a.ctypes.data))
+        return a
+
     def extract_surface(self):
         """extract_surface on the device (tsdf_volume_marching_cubes): (3*T, 3) float32 vertices, triangle t = rows 3t,
         3t+1, 3t+2, cubes in the reference's order -- the same array as marching_cubes() on the downloaded distances."""
@@ -403,6 +411,47 @@ class TSDFVolume:
         table = marching_cubes_table()
         check(lib.tsdf_volume_extract_mesh(self._h, table.ctypes.data, b, flags, mesh._h))
         return mesh
+
+    # ---- scene flow (include/tsdf_amd.h, "scene flow"; the device part of the reference's process_frames)
+    def _scene_flow(self, call, depth, flow, width, height, camera, threshold, deformed, mesh, *tail):
+        own = mesh is None
+        if own:
+            mesh = self.extract_mesh()
+        info = _capi.SceneFlowInfo()
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        try:
+            check(call(self._h, mesh._h, depth, flow, width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv), float(threshold),
+                       _capi.TSDF_SCENE_FLOW_DEFORMED if deformed else 0, C.byref(info), *tail))
+        finally:
+            if own:
+                mesh.close()
+        return {"n_vertices": int(info.n_vertices), "n_correspondences": int(info.n_correspondences),
+                "n_nodes_moved": int(info.n_nodes_moved)}
+
+    def apply_scene_flow(self, depth, flow, camera, threshold=10.0, deformed=False, mesh=None):
+        """One frame of the reference's scene fusion (tsdf_volume_apply_scene_flow): the mesh vertices the depth frame (height x width
+        uint16, 0 = invalid) sees take the scene flow (height x width x 3 float32, world units) at their pixel, and it is added,
+        weighted by how many triangle corners lie on each edge, to the translations of the deformation nodes of the two voxels that
+        bracket each vertex -- deterministically.  threshold: how far (along z) the depth's point may lie from the vertex; deformed:
+        the vertices go through the current deformation before they are projected (the later frames of a sequence).  mesh: a Mesh
+        holding extract_mesh() of this volume's whole grid (None: extracted into a private one).  Blocking.  Returns
+        {n_vertices, n_correspondences, n_nodes_moved}."""
+        d = np.ascontiguousarray(depth, dtype=np.uint16)
+        if d.ndim != 2:
+            raise ValueError("the depth image must be (height, width)")
+        height, width = d.shape
+        f = np.ascontiguousarray(flow, dtype=np.float32)
+        if f.shape != (height, width, 3):
+            raise ValueError("the scene flow must be (%d, %d, 3), got %r" % (height, width, f.shape))
+        return self._scene_flow(lib.tsdf_volume_apply_scene_flow, d.ctypes.data, f.ctypes.data, width, height, camera, threshold,
+                                deformed, mesh)
+
+    def apply_scene_flow_device(self, depth_ptr, flow_ptr, width, height, camera, threshold=10.0, deformed=False, mesh=None, stream=None):
+        """apply_scene_flow on device images (width * height uint16, 3 * width * height float32), enqueued on `stream` (None: the
+        volume's); blocks for the counts."""
+        s = self.stream_ptr() if stream is None else stream
+        return self._scene_flow(lib.tsdf_volume_apply_scene_flow_device, C.c_void_p(int(depth_ptr)), C.c_void_p(int(flow_ptr)), width,
+                                height, camera, threshold, deformed, mesh, C.c_void_p(int(s) if s else 0))
 
     # ---- distance field (include/tsdf_amd.h, "distance field"; not in the reference's class)
     def compute_esdf(self, max_distance=float("inf"), fill_unknown=False, into=None):

@@ -82,6 +82,7 @@ struct EntryParams;
 int occupancy_refresh(struct ::tsdf_volume *v, const EntryParams *entry = nullptr);
 int occupancy_flags_refresh(struct ::tsdf_volume *v);   // volume.hip: the flags only (fine, cell), not the reach summary: what the cell-parallel cast reads
 int build_t_table(struct ::tsdf_volume *v);      // volume.hip
+int deform_points_on(const struct ::tsdf_volume *v, int num_points, float *device_points, hipStream_t stream);   // volume.hip
 // timing helpers (volume.hip).  When timing is on, a launch of kernel `which` carries a start and a stop event that take the
 // dispatch's own begin / end timestamps (hipExtLaunchKernel: what rocprofv3's kernel trace reads), TSDF_LAUNCH_TIMED below.
 // (Up to round 2h the launch was bracketed with two hipEventRecord calls: that interval also holds the two barrier packets and

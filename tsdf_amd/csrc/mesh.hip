@@ -288,6 +288,12 @@ void mesh_free(tsdf_mesh *m) {
     if (m->cell_reps) (void)hipFree(m->cell_reps);
     if (m->cluster_of) (void)hipFree(m->cluster_of);
     if (m->cluster_sums) (void)hipFree(m->cluster_sums);
+    if (m->flow_vertex) (void)hipFree(m->flow_vertex);
+    if (m->flow_points) (void)hipFree(m->flow_points);
+    if (m->flow_counts) (void)hipFree(m->flow_counts);
+    if (m->flow_depth) (void)hipFree(m->flow_depth);
+    if (m->flow_image) (void)hipFree(m->flow_image);
+    if (m->flow_totals) (void)hipHostFree(m->flow_totals);
     if (m->totals) (void)hipHostFree(m->totals);
     if (m->done) (void)hipEventDestroy(m->done);
     delete m;
@@ -369,6 +375,11 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
         m->info.box[a] = lo[a];
         m->info.box[a + 3] = hi[a] > lo[a] ? hi[a] : lo[a];
     }
+    // (scene_flow.hip) the whole grid: what follows leaves the records of every voxel, or an empty mesh
+    const bool whole = lo[0] == 0 && lo[1] == 0 && lo[2] == 0 && hi[0] == last[0] && hi[1] == last[1] && hi[2] == last[2];
+    m->grid[0] = whole ? g.X : 0;
+    m->grid[1] = whole ? g.Y : 0;
+    m->grid[2] = whole ? g.Z : 0;
     if (!(lo[0] < hi[0] && lo[1] < hi[1] && lo[2] < hi[2])) return TSDF_OK;   // clipped to nothing, or an axis shorter than 2
 
     MeshBox b;
@@ -466,7 +477,10 @@ int tsdf_mesh_scratch_bytes(const tsdf_mesh *m, uint64_t *bytes) {
              (uint64_t)m->keep_masks_cap * sizeof(uint64_t) + (uint64_t)m->keep_bases_cap * sizeof(uint32_t) +
              // mesh simplification: the cell table, the per-vertex cluster word and the per-cluster sums of a simplification into the handle
              (uint64_t)m->cell_keys_cap * sizeof(uint64_t) + (uint64_t)(m->cell_reps_cap + m->cluster_of_cap) * sizeof(uint32_t) +
-             (uint64_t)m->cluster_sums_cap * sizeof(int64_t);
+             (uint64_t)m->cluster_sums_cap * sizeof(int64_t) +
+             // scene flow: 8 bytes per vertex, 12 more with TSDF_SCENE_FLOW_DEFORMED, the two counts, the host variant's two images
+             (uint64_t)m->flow_vertex_cap * sizeof(uint2) + (uint64_t)m->flow_points_cap * sizeof(float) + (m->flow_counts ? 2 * sizeof(uint64_t) : 0) +
+             (uint64_t)m->flow_depth_cap * sizeof(uint16_t) + (uint64_t)m->flow_image_cap * sizeof(float);
     return TSDF_OK;
 }
 

@@ -327,6 +327,7 @@ int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t
     if (rc == TSDF_OK) rc = mesh_join(dst, stream);
     if (rc != TSDF_OK) return rc;
     dst->labelled = 0;
+    dst->grid[0] = dst->grid[1] = dst->grid[2] = 0;   // (scene_flow.hip: not an extraction's arrays and records any more)
     dst->info = src->info;
     dst->info.n_vertices = dst->info.n_indices = 0;
     const uint64_t nv = src->info.n_vertices, n_triples = src->info.n_indices / 3;

@@ -68,4 +68,16 @@ struct tsdf_mesh {
     size_t cluster_of_cap;
     int64_t *cluster_sums;             // per cluster: the count and the integer sums of positions (normals, colours)
     size_t cluster_sums_cap;           // in words
+    // scene flow (scene_flow.hip): grid is kept by every extraction; the arrays are null until the first scene-flow call with the handle
+    uint32_t grid[3];                  // the arrays and chunk records are an extraction of the WHOLE grid of a volume of these sizes
+                                       // (all zero: a box, or the output of a filter or a simplification)
+    uint2 *flow_vertex;                // per vertex: {its pixel index or 0xffffffff, the soup vertices on its edge}
+    size_t flow_vertex_cap;
+    float *flow_points;                // TSDF_SCENE_FLOW_DEFORMED: the vertices pushed through the deformation field
+    size_t flow_points_cap;            // in floats
+    uint64_t *flow_counts;             // correspondences, nodes moved
+    uint64_t *flow_totals;             // pinned: where the two land
+    uint16_t *flow_depth;              // the host variant's uploads of the depth and scene-flow images
+    float *flow_image;
+    size_t flow_depth_cap, flow_image_cap;   // in pixels, in floats
 };

@@ -318,6 +318,7 @@ int simplify_checked(uint64_t n_vertices, uint64_t n_indices, const float *verti
     int rc = mesh_join(dst, stream);
     if (rc != TSDF_OK) return rc;
     dst->labelled = 0;
+    dst->grid[0] = dst->grid[1] = dst->grid[2] = 0;   // (scene_flow.hip: not an extraction's arrays and records any more)
     std::memset(&dst->info, 0, sizeof(dst->info));
     dst->info.flags = (normals ? TSDF_MESH_NORMALS : 0u) | (rgb ? TSDF_MESH_COLOURS : 0u);
     if (n_vertices == 0) {

@@ -1100,6 +1100,13 @@ static void rotation_products(const float r[3], float m[9]) {
 
 int tsdf_volume_deform_points_device(const tsdf_volume *v, int num_points, float *device_points) {
     TSDF_REQUIRE(v && device_points && num_points >= 0, "tsdf_volume_deform_points: bad argument");
+    return deform_points_on(v, num_points, device_points, v->stream);
+}
+
+}  // extern "C"
+
+// tsdf_volume_deform_points_device on a stream of the caller's choice (scene_flow.hip deforms a copy of the mesh vertices on its own)
+int tsdf::deform_points_on(const tsdf_volume *v, int num_points, float *device_points, hipStream_t stream) {
     TSDF_REQUIRE(v->z_begin == 0 && v->z_end == v->g.Z, "tsdf_volume_deform_points needs a whole volume");
     if (num_points == 0) return TSDF_OK;
     float m[9];
@@ -1109,11 +1116,13 @@ int tsdf_volume_deform_points_device(const tsdf_volume *v, int num_points, float
     rot.m21 = m[3]; rot.m22 = m[4]; rot.m23 = m[5];
     rot.m31 = m[6]; rot.m32 = m[7]; rot.m33 = m[8];
     const F3 t = {v->global_translation[0], v->global_translation[1], v->global_translation[2]};
-    hipLaunchKernelGGL(deform_points_kernel, dim3((unsigned)((num_points + 255) / 256)), dim3(256), 0, v->stream, v->nodes, v->g, rot, t,
+    hipLaunchKernelGGL(deform_points_kernel, dim3((unsigned)((num_points + 255) / 256)), dim3(256), 0, stream, v->nodes, v->g, rot, t,
                        num_points, device_points);
     TSDF_HIP(hipGetLastError(), "Deformation kernel failed");
     return TSDF_OK;
 }
+
+extern "C" {
 
 int tsdf_volume_deform_points(const tsdf_volume *v, int num_points, float *host_points) {
     TSDF_REQUIRE(v && host_points && num_points >= 0, "tsdf_volume_deform_points: bad argument");

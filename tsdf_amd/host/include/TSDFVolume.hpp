@@ -19,6 +19,7 @@
 
 struct tsdf_volume;  // C-ABI handle (include/tsdf_amd.h)
 struct tsdf_esdf;    // distance-field handle (include/tsdf_amd.h)
+struct tsdf_mesh;    // indexed-mesh handle (include/tsdf_amd.h)
 
 class TSDFVolume {
 public:
@@ -174,6 +175,16 @@ public:
     std::vector<float> compute_esdf(float max_distance, bool fill_unknown = false) const;
     // the same into a caller's handle (tsdf_esdf_create), where it stays on the device: tsdf_esdf_buffer, tsdf_esdf_sample_device
     void compute_esdf(float max_distance, bool fill_unknown, tsdf_esdf *esdf) const;
+
+    // Scene flow (include/tsdf_amd.h, "scene flow"; the device part of the reference's process_frames, SceneFusion_krnl.hpp): the
+    // vertices of `mesh` -- a handle holding tsdf_volume_extract_mesh of this volume's whole grid -- that the depth frame sees take the
+    // scene flow (width * height float3, row major, world units) at their pixel, and it is added, weighted, to the translations of the
+    // deformation nodes of the voxels that bracket them.  threshold: how far (mm, along z) the depth's point may lie from the vertex;
+    // deformed: the vertices are pushed through the current deformation before they are projected (the later frames of a sequence).
+    // Returns the number of nodes written; correspondences (may be null) receives the number of vertices that found a pixel.  Throws
+    // std::invalid_argument on the refusals (a mesh that is not the whole grid's, a threshold not > 0, a non-finite matrix entry).
+    uint64_t apply_scene_flow(tsdf_mesh *mesh, const uint16_t *depth_map, const float3 *scene_flow, uint32_t width, uint32_t height,
+                              const Camera &camera, float threshold = 10.0f, bool deformed = false, uint64_t *correspondences = nullptr);
 
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);

@@ -345,6 +345,19 @@ void TSDFVolume::deform_mesh(const int num_points, float3 *points) const {
     check(tsdf_volume_deform_points(m_handle, num_points, reinterpret_cast<float *>(points)), "Deformation kernel failed");
 }
 
+// ---- scene flow (include/tsdf_amd.h, "scene flow")
+uint64_t TSDFVolume::apply_scene_flow(tsdf_mesh *mesh, const uint16_t *depth_map, const float3 *scene_flow, uint32_t width, uint32_t height,
+                                      const Camera &camera, float threshold, bool deformed, uint64_t *correspondences) {
+    static_assert(sizeof(float3) == 12, "packed vector types");
+    const Eigen::Matrix3f k = camera.k(), kinv = camera.kinv();
+    tsdf_scene_flow_info info;
+    check(tsdf_volume_apply_scene_flow(m_handle, mesh, depth_map, reinterpret_cast<const float *>(scene_flow), width, height, camera.pose().data(),
+                                       camera.inverse_pose().data(), k.data(), kinv.data(), threshold, deformed ? TSDF_SCENE_FLOW_DEFORMED : 0u, &info),
+          "Scene flow kernels failed");
+    if (correspondences) *correspondences = info.n_correspondences;
+    return info.n_nodes_moved;
+}
+
 // ---- file format (reference: src/TSDF/TSDFVolume.cu:911-1027 writer, :463-664 reader):
 // 68-byte header {dim3 size, float3 physical, float3 offset, float trunc, float max_weight,
 // float3 global_translation, float3 global_rotation} then float dist[N], float weight[N],
