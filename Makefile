@@ -11,7 +11,7 @@ CSRC      = tsdf_amd/csrc
 ifeq ($(DIAG),1)
 HIPFLAGS += -DTSDF_DIAGNOSTICS
 endif
-HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/esdf.hip $(CSRC)/scene_flow.hip
+HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/esdf.hip $(CSRC)/scene_flow.hip
 HIP_OBJS  = $(HIP_SRCS:.hip=.o)
 LIBDIR    = tsdf_amd/lib
 
@@ -59,7 +59,7 @@ oracle:
 	$(MAKE) -C oracle -s all
 
 # C++ test program of the class surface (run by tests/test_cpp_surface.py on the GPU box)
-cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_rays build/test_fuse build/test_align build/test_integrate_rays build/test_rays_colour build/test_mesh build/test_esdf build/test_components build/test_simplify build/test_scene_flow build/kinfu_stream
+cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_rays build/test_fuse build/test_align build/test_integrate_rays build/test_rays_colour build/test_mesh build/test_esdf build/test_components build/test_simplify build/test_smooth build/test_scene_flow build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
 build/kinfu_stream: tools/kinfu_stream.cpp $(LIBDIR)/libtsdf_host.so include/tsdf_amd.h
@@ -129,6 +129,11 @@ build/test_components: tests/cpp/test_components.cpp $(LIBDIR)/libtsdf_host.so
 build/test_simplify: tests/cpp/test_simplify.cpp $(LIBDIR)/libtsdf_host.so
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_simplify.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
+
+# C++ check of the mesh smoothing through the class surface (run by tests/test_cpp_smooth.py on the GPU box)
+build/test_smooth: tests/cpp/test_smooth.cpp $(LIBDIR)/libtsdf_host.so
+	@mkdir -p build
+	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_smooth.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
 # C++ check of the scene-flow step through the class surface (run by tests/test_cpp_scene_flow.py on the GPU box)
 build/test_scene_flow: tests/cpp/test_scene_flow.cpp $(LIBDIR)/libtsdf_host.so

@@ -742,7 +742,8 @@ int tsdf_mesh_download(const tsdf_mesh *mesh, float *host_vertices, uint32_t *ho
 /* Device bytes the handle holds besides the four output arrays.  After an extraction alone that is the bound above; the first
  * components call (group "mesh components") adds 8 bytes per vertex (labels and sizes) and 32 bytes, a filter INTO the handle 12 bytes
  * per 64 vertices and per 64 triples of its source, a simplification INTO the handle what the group "mesh simplification" states, a
- * scene-flow call WITH the handle what the group "scene flow" states. */
+ * smoothing INTO the handle (or tsdf_mesh_compute_normals ON it) what the group "mesh smoothing" states, a scene-flow call WITH the
+ * handle what the group "scene flow" states. */
 int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
 
 /* ---- mesh components (no reference counterpart: the reference's soup has no connectivity to ask about) ----------------------------- */
@@ -853,12 +854,92 @@ int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t
  *     slots are numbered in 32 bits: simplify in boxes); cell_size not finite or not > 0; flags other than 0 (there are none yet);
  *     dst == src; handles made on different devices; an index >= n_vertices -- found on the device by the first kernel that reads I,
  *     before any lane uses it as an address: the call returns the error and dst is left empty.
- *   Out of scope: removing duplicate triangles, quadric error placement, edge collapse, smoothing, preserving boundaries or
- *     manifoldness, simplifying inside tsdf_volume_extract_mesh, slab volumes (they have no indexed mesh). */
+ *   Out of scope: removing duplicate triangles, quadric error placement, edge collapse, preserving boundaries or manifoldness,
+ *     simplifying inside tsdf_volume_extract_mesh, slab volumes (they have no indexed mesh).  Smoothing is the group "mesh smoothing"
+ *     below. */
 int tsdf_simplify_mesh_device(uint64_t n_vertices, uint64_t n_indices, const float *device_vertices, const uint32_t *device_indices,
                               const float *device_normals, const uint8_t *device_rgb, float cell_size, uint32_t flags, tsdf_mesh *dst,
                               void *hip_stream);
 int tsdf_mesh_simplify(tsdf_mesh *src, float cell_size, uint32_t flags, tsdf_mesh *dst, void *hip_stream);
+
+/* ---- mesh smoothing (no reference counterpart: the reference's soup goes to a file as it is) --------------------------------------- */
+/* lambda|mu (Taubin) smoothing of an indexed mesh on the device, an option to pin its open border, and area-weighted vertex normals
+ * from the faces: what takes the voxel-scale stair-stepping and the sensor noise out of an extracted surface (or of a clustered level
+ * of detail of one) without the mesh leaving the device.  Opt-in by being called: no other entry point, launch or result changes.
+ *   The result (unique values, whatever computes them), for n_vertices positions, n_indices indices (a multiple of 3), iterations, the
+ *   fp32 factors lambda and mu, and flags:
+ *   1. Loose vertices and live triples.  A vertex is LOOSE if any coordinate is not finite or any |V_a| is not < 2^21 (the
+ *     simplification's test, in float, on the source positions, once).  An index triple is LIVE iff its three indices are pairwise
+ *     different and none of its corners is loose; only live triples count, everywhere below, and a repeated live triple counts as often
+ *     as it appears.  deg(v) = 2 x the live triples that name v.
+ *   2. One pass with factor f.  Every vertex is computed from the previous pass's positions (Jacobi, never in place); a pass whose
+ *     factor is exactly 0.0f or -0.0f is not run.  A vertex with deg(v) == 0, a loose vertex or a pinned vertex (4) keeps its 12
+ *     bytes.  Otherwise, per axis: q(u) = llrintf(P_a(u) * 1024.0f) (the product is exact, the rounding to nearest-even); S the int64 sum
+ *     of q(u1) + q(u2) over the live triples that name v, u1 and u2 the triple's other two corners; d = ((double)S / (double)deg) /
+ *     1024.0; out = (float)((double)p + (double)f * (d - (double)p)), double arithmetic, no contraction, in exactly that order.
+ *     Integers are summed, so no arrival order can change a sum: permuting the triples does not change a byte.  This is the umbrella
+ *     operator weighted by edge multiplicity: an interior edge counts twice, a border edge once.
+ *   3. Guard.  If any of the three out values is not finite or not < 2^21 in magnitude, the vertex keeps its previous position for
+ *     this pass, all three coordinates.  So a position that is not loose stays below 2^21, q below 2^31, and no sum can overflow.
+ *   4. TSDF_SMOOTH_PIN_BOUNDARY.  m{u, v} is the number of live triples that name both u and v; a vertex is PINNED iff it is an end of
+ *     an edge with m == 1 (edges with m >= 3 do not pin).  Pins come from the source connectivity, once, and hold for all passes.  A
+ *     mesh extracted in a box keeps the bytes of its open border, so neighbouring boxes still agree on the edges they share.
+ *   5. The call runs `iterations` times: a pass with lambda, then a pass with mu.  iterations == 0, or both factors zero, gives dst
+ *     equal to the source array for array.  dst receives the smoothed positions, the indices as the same bytes, colours where given as
+ *     the same bytes, normals as the source's bytes where given -- with TSDF_SMOOTH_NORMALS they are (6) on the smoothed positions,
+ *     whether or not the source had any, and dst->info.flags says so.  info.box is the source's (all zero for
+ *     tsdf_smooth_mesh_device); dst is not labelled.
+ *   6. Vertex normals from faces, area-weighted.  For a live triple A = V[I[3t]], B = V[I[3t+2]], C = V[I[3t+1]] (the wiring
+ *     extract_surface uses); in double, without contraction, e1 = B - A, e2 = C - A, c = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *     e1.x e2.y - e1.y e2.x); k_a = llrint(c_a * 65536.0).  For each vertex d_a is the int64 sum of k_a over the live triples that
+ *     name it, as a double; L = sqrt(d_x d_x + d_y d_y + d_z d_z), added left to right; the output is (float)(d_a / L), and a NaN
+ *     triple when L == 0 (loose vertices, vertices no live triple names, faces that cancel).  On an extracted mesh the normal points
+ *     out of the surface, like the field queries' unit gradient.  The 2^-16 quantisation is the price of order independence: it moves
+ *     a component by a few 1e-7 at 10 mm voxels and a few 1e-4 at 0.5 mm voxels.  |c_a| is at most twice the product of two edge
+ *     lengths, and a sum may wrap once the |c_a| round a vertex add up to 2^47: faces with edges below 2^16 units (65 m in mm) stay
+ *     below 2^33 each, which leaves room for 2^14 of them round one vertex.
+ *   tsdf_smooth_mesh_device: any arrays on the device (3 floats per vertex, one uint32 per index, 3 floats / 3 bytes per vertex or
+ *     NULL).  tsdf_mesh_smooth: src's arrays, normals and colours where src has them.  tsdf_vertex_normals_device: (6) of any arrays
+ *     into device_normals_out (3 floats per vertex); blocking, it holds 24 bytes per vertex + 8 of device scratch for the duration of
+ *     the call; when it refuses an index the n_vertices triples hold unspecified values and nothing outside them has been touched.tsdf_mesh_compute_normals: (6) of the handle's own arrays; it replaces or creates the handle's normal array and sets
+ *     TSDF_MESH_NORMALS (labels stay: the connectivity is untouched); blocking.
+ *   How: neighbour rows are built once per call -- integer atomic counts, the chunk scan of the components filter, a fill with an
+ *     atomic cursor that writes the other two corners of every live triple into each corner's row (the order inside a row is that of
+ *     arrival, harmless because every sum is an integer sum).  Each pass is a gather without atomics, one lane per vertex, between two
+ *     position buffers; a row of more than 64 pairs (a fan's hub) is walked by its whole wave.  Pins: the simplification's
+ *     open-addressed table with the key (min << 32) | max and a count per slot, load <= 1/2, so no lane waits for another;
+ *     slots counted once flag both ends.  Normals: nine 64-bit integer atomic adds per live triple.  No float is ever added atomically.
+ *   Kernels are enqueued on hip_stream (NULL: the default stream) behind a pending extraction; at most one synchronisation, for the
+ *     error word, after the rows are built; the call returns with the passes enqueued, and stream order is that of the components
+ *     filter.  src and the volume are never written.  dst keeps its arrays and scratch and only grows them: a warm repeat allocates
+ *     nothing.
+ *   Scratch of a smoothing into dst, counted by tsdf_mesh_scratch_bytes(dst), with passes = iterations x the factors that are not
+ *     zero (0 for a mesh without triples):
+ *       16 (ceil(ceil(n_vertices / 64) / 1024) + 1) + 8                         the scan's parts and the error word, always
+ *       + 8 n_vertices + 8 n_indices + 4 ceil(n_vertices / 64)                  passes > 0: row bounds, one pair per index, chunk bases
+ *       + 12 n_vertices                                                         passes > 1: the second position buffer
+ *       + n_vertices + 12 E                                                     passes > 0 with TSDF_SMOOTH_PIN_BOUNDARY: the pin flags and
+ *                                                                               the edge table, E the smallest power of two >= 2 n_indices
+ *       + 24 n_vertices                                                         TSDF_SMOOTH_NORMALS (and tsdf_mesh_compute_normals ON a handle)
+ *     bytes, on top of what the handle held before (the edge table is the simplification's cell table: a handle that has both holds
+ *     the larger).
+ *   Refused (TSDF_ERR_INVALID, with a message, before any device work where the host can tell): NULL dst, src or mesh; NULL arrays
+ *     with non-zero counts; n_indices % 3 != 0; counts above 2^32 - 1; lambda or mu not finite; iterations above 1024; unknown flags;
+ *     dst == src; handles made on different devices; an index >= n_vertices -- found on the device by the first kernel that reads I,
+ *     before any lane uses it as an address: the call returns the error and dst is left empty.  An empty source gives an empty dst;
+ *     vertices with n_indices == 0 are legal.
+ *   Out of scope: cotangent or other geometric weights, feature-preserving or bilateral mesh filters, smoothing the distance field,
+ *     smoothing inside tsdf_volume_extract_mesh, in-place smoothing (dst == src), slab volumes, hole filling, removing duplicate
+ *     triangles. */
+#define TSDF_SMOOTH_PIN_BOUNDARY 1u
+#define TSDF_SMOOTH_NORMALS 2u
+int tsdf_smooth_mesh_device(uint64_t n_vertices, uint64_t n_indices, const float *device_vertices, const uint32_t *device_indices,
+                            const float *device_normals, const uint8_t *device_rgb, uint32_t iterations, float lambda, float mu,
+                            uint32_t flags, tsdf_mesh *dst, void *hip_stream);
+int tsdf_mesh_smooth(tsdf_mesh *src, uint32_t iterations, float lambda, float mu, uint32_t flags, tsdf_mesh *dst, void *hip_stream);
+int tsdf_vertex_normals_device(uint64_t n_vertices, uint64_t n_indices, const float *device_vertices, const uint32_t *device_indices,
+                               float *device_normals_out, void *hip_stream);
+int tsdf_mesh_compute_normals(tsdf_mesh *mesh, void *hip_stream);
 
 /* ---- scene flow (replaces the device part of process_frames, src/SceneFusion/SceneFusion_krnl.cu:235-401) ------------------------- */
 /* One frame of the reference's non-rigid step: the mesh vertices a depth frame sees take the scene flow at their pixel, and the flow

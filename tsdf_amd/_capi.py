@@ -15,6 +15,7 @@ TSDF_FIELD_UNIT_GRADIENT = 1
 TSDF_RAYS_BAND_ONLY = 1
 TSDF_MESH_NORMALS, TSDF_MESH_COLOURS = 1, 2
 TSDF_MESH_KEEP_LARGEST = 1
+TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
 TSDF_SCENE_FLOW_DEFORMED = 1
 
@@ -200,6 +201,10 @@ _SIGS = {
     "tsdf_mesh_filter_components": (_i, [_vp, C.c_uint64, _u32, _vp, _vp]),
     "tsdf_simplify_mesh_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_float, _u32, _vp, _vp]),
     "tsdf_mesh_simplify": (_i, [_vp, C.c_float, _u32, _vp, _vp]),
+    "tsdf_smooth_mesh_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _u32, C.c_float, C.c_float, _u32, _vp, _vp]),
+    "tsdf_mesh_smooth": (_i, [_vp, _u32, C.c_float, C.c_float, _u32, _vp, _vp]),
+    "tsdf_vertex_normals_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "tsdf_mesh_compute_normals": (_i, [_vp, _vp]),
     "tsdf_volume_apply_scene_flow": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _f, _u32, C.POINTER(SceneFlowInfo)]),
     "tsdf_volume_apply_scene_flow_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _f, _u32, C.POINTER(SceneFlowInfo), _vp]),
     "tsdf_esdf_create": (_i, [C.POINTER(_vp)]),

@@ -979,6 +979,24 @@ class Mesh:
         check(lib.tsdf_mesh_simplify(self._h, float(cell_size), 0, dst._h, C.c_void_p(int(stream) if stream else 0)))
         return dst
 
+    # ---- mesh smoothing (include/tsdf_amd.h, "mesh smoothing")
+    def smooth(self, iterations=10, lam=0.5, mu=-0.53, pin_boundary=False, normals=False, into=None, stream=0):
+        """The mesh smoothed on the device (tsdf_mesh_smooth): `iterations` times a pass with factor `lam`, then one with `mu` (Taubin's
+        pair: the second undoes the shrinking of the first; mu=0 is the plain Laplacian).  `pin_boundary` keeps the bytes of the open
+        border, so meshes extracted in neighbouring boxes still fit; `normals` computes area-weighted normals from the smoothed faces
+        (otherwise the source's normals are carried along).  Indices and colours are carried along.  Returns a Mesh (`into`: one to
+        reuse, not this one)."""
+        dst = Mesh() if into is None else into
+        check(lib.tsdf_mesh_smooth(self._h, int(iterations), float(lam), float(mu), _smooth_flags(pin_boundary, normals), dst._h,
+                                   C.c_void_p(int(stream) if stream else 0)))
+        return dst
+
+    def compute_normals(self, stream=0):
+        """Area-weighted vertex normals from the mesh's own faces (tsdf_mesh_compute_normals): they replace the normals the mesh has, or
+        give it some -- after a simplification or for arrays that came without.  Returns the mesh."""
+        check(lib.tsdf_mesh_compute_normals(self._h, C.c_void_p(int(stream) if stream else 0)))
+        return self
+
 
 class ESDF:
     """tsdf_esdf (include/tsdf_amd.h, "distance field"): the device array of a distance field, its scratch and the geometry it was
@@ -1129,6 +1147,56 @@ def simplify_mesh(vertices, indices, cell_size, normals=None, colours=None):
                 return dst.vertices, dst.indices, None if N is None else dst.normals, None if RGB is None else dst.colours
     finally:
         dst.close()
+
+
+def _smooth_flags(pin_boundary, normals):
+    return (_capi.TSDF_SMOOTH_PIN_BOUNDARY if pin_boundary else 0) | (_capi.TSDF_SMOOTH_NORMALS if normals else 0)
+
+
+def smooth_mesh_device(n_vertices, n_indices, vertices_ptr, indices_ptr, into, iterations=10, lam=0.5, mu=-0.53, pin_boundary=False,
+                       face_normals=False, normals_ptr=0, colours_ptr=0, stream=0):
+    """tsdf_smooth_mesh_device on device pointers (float32 x 3 vertices, uint32 indices, float32 x 3 normals or 0, uint8 x 3 colours or
+    0) into the Mesh `into`, which is returned.  ValueError for an index that is not below n_vertices."""
+    vp = lambda p: C.c_void_p(int(p) if p else 0)
+    check(lib.tsdf_smooth_mesh_device(int(n_vertices), int(n_indices), vp(vertices_ptr), vp(indices_ptr), vp(normals_ptr), vp(colours_ptr),
+                                      int(iterations), float(lam), float(mu), _smooth_flags(pin_boundary, face_normals), into._h, vp(stream)))
+    return into
+
+
+def smooth_mesh(vertices, indices, iterations=10, lam=0.5, mu=-0.53, pin_boundary=False, face_normals=False, normals=None, colours=None):
+    """Taubin smoothing of host arrays on the device (upload, tsdf_smooth_mesh_device, download): (n, 3) float32 vertices, 3 m indices,
+    optionally (n, 3) float32 normals and (n, 3) uint8 colours -> (vertices, indices, normals or None, colours or None); with
+    `face_normals` the normals are those of the smoothed faces, whether or not any were given."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    I = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.uint32)
+    N = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    RGB = None if colours is None else np.ascontiguousarray(colours, np.uint8).reshape(-1, 3)
+    for a, what in ((N, "normals"), (RGB, "colours")):
+        if a is not None and len(a) != len(V):
+            raise ValueError("%d %s for %d vertices" % (len(a), what, len(V)))
+    dst = Mesh()
+    try:
+        with _DeviceArray(V) as dv, _DeviceArray(I) as di, _DeviceArray(nbytes=4) as none:
+            with _DeviceArray(N if N is not None and len(V) else None, 0) as dn, _DeviceArray(RGB if RGB is not None and len(V) else None, 0) as dc:
+                given = lambda a, d: 0 if a is None else (d.ptr.value or none.ptr.value)      # (see simplify_mesh)
+                smooth_mesh_device(len(V), I.size, dv.ptr.value, di.ptr.value, dst, iterations, lam, mu, pin_boundary, face_normals,
+                                   given(N, dn), given(RGB, dc))
+                return dst.vertices, dst.indices, dst.normals if N is not None or face_normals else None, None if RGB is None else dst.colours
+    finally:
+        dst.close()
+
+
+def vertex_normals(vertices, indices):
+    """Area-weighted vertex normals of host arrays, computed on the device (tsdf_vertex_normals_device): (n, 3) float32, the NaN triple
+    where no face gives a direction.  Triangle t is (I[3t], I[3t+2], I[3t+1]), as Mesh.triangles() wires it."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    I = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.uint32)
+    out = np.empty((len(V), 3), np.float32)
+    with _DeviceArray(V) as dv, _DeviceArray(I) as di, _DeviceArray(nbytes=out.nbytes) as dn:
+        check(lib.tsdf_vertex_normals_device(len(V), I.size, dv.ptr, di.ptr, dn.ptr, None))
+        if len(V):
+            check(lib.tsdf_device_download(out.ctypes.data, dn.ptr, out.nbytes))
+    return out
 
 
 def _pose16(T):

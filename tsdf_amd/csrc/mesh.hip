@@ -288,6 +288,12 @@ void mesh_free(tsdf_mesh *m) {
     if (m->cell_reps) (void)hipFree(m->cell_reps);
     if (m->cluster_of) (void)hipFree(m->cluster_of);
     if (m->cluster_sums) (void)hipFree(m->cluster_sums);
+    if (m->row_begin) (void)hipFree(m->row_begin);
+    if (m->row_end) (void)hipFree(m->row_end);
+    if (m->rows) (void)hipFree(m->rows);
+    if (m->smooth_positions) (void)hipFree(m->smooth_positions);
+    if (m->pinned) (void)hipFree(m->pinned);
+    if (m->normal_sums) (void)hipFree(m->normal_sums);
     if (m->flow_vertex) (void)hipFree(m->flow_vertex);
     if (m->flow_points) (void)hipFree(m->flow_points);
     if (m->flow_counts) (void)hipFree(m->flow_counts);
@@ -478,6 +484,9 @@ int tsdf_mesh_scratch_bytes(const tsdf_mesh *m, uint64_t *bytes) {
              // mesh simplification: the cell table, the per-vertex cluster word and the per-cluster sums of a simplification into the handle
              (uint64_t)m->cell_keys_cap * sizeof(uint64_t) + (uint64_t)(m->cell_reps_cap + m->cluster_of_cap) * sizeof(uint32_t) +
              (uint64_t)m->cluster_sums_cap * sizeof(int64_t) +
+             // mesh smoothing: the neighbour rows, the second position buffer, the pin flags, the normal sums (the pins' edge table is the cell table)
+             (uint64_t)(m->row_begin_cap + m->row_end_cap) * sizeof(uint32_t) + (uint64_t)m->rows_cap * sizeof(uint2) +
+             (uint64_t)m->smooth_positions_cap * sizeof(float) + (uint64_t)m->pinned_cap + (uint64_t)m->normal_sums_cap * sizeof(int64_t) +
              // scene flow: 8 bytes per vertex, 12 more with TSDF_SCENE_FLOW_DEFORMED, the two counts, the host variant's two images
              (uint64_t)m->flow_vertex_cap * sizeof(uint2) + (uint64_t)m->flow_points_cap * sizeof(float) + (m->flow_counts ? 2 * sizeof(uint64_t) : 0) +
              (uint64_t)m->flow_depth_cap * sizeof(uint16_t) + (uint64_t)m->flow_image_cap * sizeof(float);

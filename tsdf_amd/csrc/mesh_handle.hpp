@@ -1,4 +1,5 @@
-// struct tsdf_mesh: what mesh.hip (extraction), mesh_components.hip (labelling, filtering) and mesh_simplify.hip (clustering) share.
+// struct tsdf_mesh: what mesh.hip (extraction), mesh_components.hip (labelling, filtering), mesh_simplify.hip (clustering) and
+// mesh_smooth.hip (smoothing, face normals) share.
 #pragma once
 
 #include "common.hpp"
@@ -68,6 +69,18 @@ struct tsdf_mesh {
     size_t cluster_of_cap;
     int64_t *cluster_sums;             // per cluster: the count and the integer sums of positions (normals, colours)
     size_t cluster_sums_cap;           // in words
+    // mesh smoothing (mesh_smooth.hip): all null until the first smoothing INTO the handle; of its source (the edge table of the pins is
+    // cell_keys and cell_reps above):
+    uint32_t *row_begin, *row_end;     // per vertex: where its row of neighbour pairs begins and ends
+    size_t row_begin_cap, row_end_cap;
+    uint2 *rows;                       // one pair per live triple and corner: the triple's other two corners
+    size_t rows_cap;                   // in pairs
+    float *smooth_positions;           // the second position buffer the passes alternate with `vertices`
+    size_t smooth_positions_cap;       // in floats
+    uint8_t *pinned;                   // TSDF_SMOOTH_PIN_BOUNDARY: per vertex, 1 at an end of an edge that one live triple names
+    size_t pinned_cap;
+    int64_t *normal_sums;              // face normals (also tsdf_mesh_compute_normals ON the handle): three integer sums per vertex
+    size_t normal_sums_cap;            // in words
     // scene flow (scene_flow.hip): grid is kept by every extraction; the arrays are null until the first scene-flow call with the handle
     uint32_t grid[3];                  // the arrays and chunk records are an extraction of the WHOLE grid of a volume of these sizes
                                        // (all zero: a box, or the output of a filter or a simplification)

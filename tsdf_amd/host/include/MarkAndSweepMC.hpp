@@ -60,6 +60,16 @@ void extract_surface_simplified(const TSDFVolume *volume, const unsigned box[6],
                                 std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
                                 std::vector<uchar3> *colours = nullptr);
 
+// The indexed mesh smoothed (include/tsdf_amd.h "mesh smoothing"; not in the reference): extracted and smoothed on the device, downloaded
+// once.  `iterations` times a pass with factor lambda, then one with mu (Taubin: 0.5 and -0.53 smooth without shrinking; mu = 0 is the
+// plain Laplacian); vertices, triangles and colours stay in extract_surface_indexed's order, only the positions move.  pin_boundary
+// keeps the bytes of the open border, so meshes of neighbouring boxes still fit.  Normals, when asked for, are the area-weighted normals
+// of the smoothed faces.  box, normals and colours may be null; factors that are not finite and more than 1024 iterations throw
+// std::invalid_argument.  The results go straight into the write_to_ply overloads.
+void extract_surface_smoothed(const TSDFVolume *volume, const unsigned box[6], unsigned iterations, float lambda, float mu, bool pin_boundary,
+                              std::vector<float3> &vertices, std::vector<int3> &triangles, std::vector<float3> *normals = nullptr,
+                              std::vector<uchar3> *colours = nullptr);
+
 // The same marching cubes over a host distance array (x fastest, voxel centres at (i + 0.5) * voxel_size + offset):
 // appends three vertices per triangle.  extract_surface is this on the volume's distances.
 void tsdf_host_marching_cubes(const float *dist, unsigned X, unsigned Y, unsigned Z, const float voxel_size[3],

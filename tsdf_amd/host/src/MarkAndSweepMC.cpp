@@ -329,6 +329,44 @@ void extract_surface_simplified(const TSDFVolume *volume, const unsigned box[6],
     for (size_t i = 0; i + 2 < indices.size(); i += 3) triangles.push_back(int3{(int)indices[i], (int)indices[i + 2], (int)indices[i + 1]});
 }
 
+// ---- ... smoothed on the device before the download --------------------------------------------------------------------------------
+void extract_surface_smoothed(const TSDFVolume *volume, const unsigned box[6], unsigned iterations, float lambda, float mu, bool pin_boundary,
+                              std::vector<float3> &vertices, std::vector<int3> &triangles, std::vector<float3> *normals,
+                              std::vector<uchar3> *colours) {
+    vertices.clear();
+    triangles.clear();
+    if (normals) normals->clear();
+    if (colours) colours->clear();
+    tsdf_mesh *mesh = nullptr, *smoothed = nullptr;
+    tsdf_host::check(tsdf_mesh_create(&mesh), "Couldn't extract the surface");
+    int rc = tsdf_mesh_create(&smoothed);
+    // (the normals are those of the smoothed faces: none are sampled from the field)
+    if (rc == TSDF_OK)
+        rc = tsdf_volume_extract_mesh(volume->handle(), tsdf_host_mc_triangle_table(), reinterpret_cast<const uint32_t *>(box),
+                                      colours ? TSDF_MESH_COLOURS : 0u, mesh);
+    void *stream = nullptr;
+    if (rc == TSDF_OK) rc = tsdf_volume_stream(volume->handle(), &stream);
+    const uint32_t flags = (pin_boundary ? TSDF_SMOOTH_PIN_BOUNDARY : 0u) | (normals ? TSDF_SMOOTH_NORMALS : 0u);
+    if (rc == TSDF_OK) rc = tsdf_mesh_smooth(mesh, iterations, lambda, mu, flags, smoothed, stream);
+    tsdf_mesh_info info;
+    if (rc == TSDF_OK) rc = tsdf_mesh_get_info(smoothed, &info);
+    std::vector<uint32_t> indices;
+    if (rc == TSDF_OK && info.n_vertices != 0) {
+        vertices.resize((size_t)info.n_vertices);
+        indices.resize((size_t)info.n_indices);
+        if (normals) normals->resize(vertices.size());
+        if (colours) colours->resize(vertices.size());
+        rc = tsdf_mesh_download(smoothed, reinterpret_cast<float *>(vertices.data()), indices.data(),
+                                normals ? reinterpret_cast<float *>(normals->data()) : nullptr,
+                                colours ? reinterpret_cast<uint8_t *>(colours->data()) : nullptr);
+    }
+    tsdf_mesh_destroy(smoothed);
+    tsdf_mesh_destroy(mesh);
+    tsdf_host::check(rc, "Couldn't extract the surface");
+    triangles.reserve(indices.size() / 3);
+    for (size_t i = 0; i + 2 < indices.size(); i += 3) triangles.push_back(int3{(int)indices[i], (int)indices[i + 2], (int)indices[i + 1]});
+}
+
 void extract_surface_indexed(const TSDFVolume *volume, std::vector<float3> &vertices, std::vector<int3> &triangles) {
     extract_surface_indexed(volume, nullptr, vertices, triangles, nullptr, nullptr);
 }
