@@ -11,7 +11,7 @@ CSRC      = tsdf_amd/csrc
 ifeq ($(DIAG),1)
 HIPFLAGS += -DTSDF_DIAGNOSTICS
 endif
-HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/esdf.hip $(CSRC)/scene_flow.hip
+HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_scan.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/esdf.hip $(CSRC)/scene_flow.hip
 HIP_OBJS  = $(HIP_SRCS:.hip=.o)
 LIBDIR    = tsdf_amd/lib
 
@@ -58,87 +58,19 @@ $(LIBDIR)/libtsdf_hip.so: $(HIP_OBJS)
 oracle:
 	$(MAKE) -C oracle -s all
 
-# C++ test program of the class surface (run by tests/test_cpp_surface.py on the GPU box)
-cpptest: build/test_surface build/test_colour build/test_weight_cap build/test_field build/test_rays build/test_fuse build/test_align build/test_integrate_rays build/test_rays_colour build/test_mesh build/test_esdf build/test_components build/test_simplify build/test_smooth build/test_scene_flow build/kinfu_stream
+CPPTESTS  = surface colour weight_cap field rays fuse align integrate_rays rays_colour mesh esdf components simplify smooth scene_flow
+cpptest: $(CPPTESTS:%=build/test_%) build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
 build/kinfu_stream: tools/kinfu_stream.cpp $(LIBDIR)/libtsdf_host.so include/tsdf_amd.h
 	@mkdir -p build
 	$(CXX) $(HOSTFLAGS) -o $@ tools/kinfu_stream.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
-build/test_surface: tests/cpp/test_surface.cpp $(LIBDIR)/libtsdf_host.so
+# C++ checks through the class surface, one program per tests/cpp/test_NAME.cpp (run by tests/test_cpp_*.py and
+# tests/test_colour_fusion.py on the GPU box)
+build/test_%: tests/cpp/test_%.cpp $(LIBDIR)/libtsdf_host.so
 	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_surface.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of colour fusion through the class surface (run by tests/test_colour_fusion.py on the GPU box)
-build/test_colour: tests/cpp/test_colour.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_colour.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the weight cap through the class surface (run by tests/test_cpp_weight_cap.py on the GPU box)
-build/test_weight_cap: tests/cpp/test_weight_cap.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_weight_cap.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the field queries through the class surface (run by tests/test_cpp_field.py on the GPU box)
-build/test_field: tests/cpp/test_field.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_field.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the ray queries through the class surface (run by tests/test_cpp_rays.py on the GPU box)
-build/test_rays: tests/cpp/test_rays.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_rays.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of volume fusion through the class surface (run by tests/test_cpp_fuse.py on the GPU box)
-build/test_fuse: tests/cpp/test_fuse.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_fuse.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of field alignment through the class surface (run by tests/test_cpp_align.py on the GPU box)
-build/test_align: tests/cpp/test_align.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_align.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of ray integration through the class surface (run by tests/test_cpp_integrate_rays.py on the GPU box)
-build/test_integrate_rays: tests/cpp/test_integrate_rays.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_integrate_rays.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of coloured ray integration and coloured ray queries through the class surface (run by tests/test_cpp_rays_colour.py on the GPU box)
-build/test_rays_colour: tests/cpp/test_rays_colour.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_rays_colour.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the indexed mesh through the class surface (run by tests/test_cpp_mesh.py on the GPU box)
-build/test_mesh: tests/cpp/test_mesh.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_mesh.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the distance field through the class surface (run by tests/test_cpp_esdf.py on the GPU box)
-build/test_esdf: tests/cpp/test_esdf.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_esdf.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the mesh components through the class surface (run by tests/test_cpp_components.py on the GPU box)
-build/test_components: tests/cpp/test_components.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_components.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the mesh simplification through the class surface (run by tests/test_cpp_simplify.py on the GPU box)
-build/test_simplify: tests/cpp/test_simplify.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_simplify.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the mesh smoothing through the class surface (run by tests/test_cpp_smooth.py on the GPU box)
-build/test_smooth: tests/cpp/test_smooth.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_smooth.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
-
-# C++ check of the scene-flow step through the class surface (run by tests/test_cpp_scene_flow.py on the GPU box)
-build/test_scene_flow: tests/cpp/test_scene_flow.cpp $(LIBDIR)/libtsdf_host.so
-	@mkdir -p build
-	$(CXX) $(HOSTFLAGS) -o $@ tests/cpp/test_scene_flow.cpp -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
+	$(CXX) $(HOSTFLAGS) -o $@ $< -L$(LIBDIR) -ltsdf_host -ltsdf_hip -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
 # Host-side sanitizer run of the scene-flow argument checks and refusals (they all return before any device work): a stand-alone
 # program linked with scene_flow.hip alone, address and undefined-behaviour sanitizers on the host code only.  Needs no GPU.

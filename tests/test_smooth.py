@@ -2,7 +2,8 @@
 hand-made cases through tsdf_smooth_mesh_device (the smallest meshes at which the rows, the scans, the edge table and the sums can go
 wrong) with and without each flag, every one run twice; tsdf_vertex_normals_device on the same cases; the refusals; then meshes of
 random fields, of the sphere scene and of a fused scene through Mesh.smooth, a box mesh with its border pinned, Mesh.compute_normals
-after a simplification, a chain with the simplification and the components filter, and a reused handle with its scratch formula."""
+after a simplification, a chain with the simplification and the components filter, a reused handle with its scratch formula, and
+two handles that serve every operation in turn."""
 import collections
 
 import numpy as np
@@ -16,7 +17,7 @@ from tests.helpers import assert_same_floats
 from tests.test_components_ref_host import MESH_GRIDS, mesh_seed
 from tests.test_mesh_indexed import fused_scene, volume_of
 from tests.test_smooth_ref_host import large_sphere
-from tests.test_simplify import FRESH_HANDLE, Device, mesh_arrays, same_bytes
+from tests.test_simplify import FRESH_HANDLE, Device, assert_simplified, mesh_arrays, same_bytes
 from tsdf_amd import _capi
 
 pytestmark = pytest.mark.gpu
@@ -343,6 +344,56 @@ def test_a_reused_handle_is_exact_and_its_scratch_follows_the_formula(scene, sph
     # ... and the big one again, warm: the same bytes, no growth
     big.smooth(*TAUBIN, pin_boundary=True, normals=True, into=dst)
     assert same_bytes(mesh_arrays(dst), first) and dst.scratch_bytes == held
+
+
+def test_two_handles_serve_every_operation_in_turn(sphere):
+    """Each handle is in turn the output of an extraction, a filter, a simplification and a smoothing, so every operation finds the
+    scratch (parts, keep masks and bases, the table) as another one sized and left it."""
+    a, b = tsdf_amd.Mesh(), tsdf_amd.Mesh()
+    taubin = (5, 0.5, -0.53)
+
+    def assert_filtered(got, src, min_triangles, what):
+        V, I, N, _ = src
+        L, T, info = components_ref.label(len(V), I)
+        (fV, fN), fI, _ = components_ref.filter_mesh(L, T, info, I, [V, N], min_triangles)
+        assert np.array_equal(bits(got[0]), bits(fV)) and np.array_equal(got[1], fI) and got[1].dtype == np.uint32, what
+        assert_same_floats(got[2], fN, what + ": normals")
+        assert got[3] is None and 0 < len(fV) <= len(V), what
+
+    def chain(verify):
+        steps = []
+        assert sphere.extract_mesh(normals=True, into=a) is a
+        steps.append(mesh_arrays(a))
+        assert a.filter_components(components_ref.SCENE_MIN_TRIANGLES, into=b) is b
+        steps.append(mesh_arrays(b))
+        assert b.simplify(20.0, into=a) is a
+        steps.append(mesh_arrays(a))
+        assert a.smooth(*taubin, pin_boundary=True, normals=True, into=b) is b
+        steps.append(mesh_arrays(b))
+        assert b.compute_normals() is b
+        steps.append(mesh_arrays(b))
+        assert b.simplify(40.0, into=a) is a
+        steps.append(mesh_arrays(a))
+        assert a.filter_components(1, into=b) is b
+        steps.append(mesh_arrays(b))
+        assert a.box == b.box == (0, 0, 0, 63, 63, 63) and a.info().flags == b.info().flags == 1
+        if verify:
+            assert (len(steps[0][0]), len(steps[0][1]) // 3) == (4422, 8824)
+            assert_filtered(steps[1], steps[0], components_ref.SCENE_MIN_TRIANGLES, "filtered")
+            assert_simplified(steps[2], steps[1], 20.0, "simplified")
+            rV = assert_smoothed(steps[3], steps[2], taubin, PIN | NORMALS, "smoothed")
+            assert (bits(rV) != bits(steps[2][0])).any()                    # (the kept spheres are closed: the pins find no border)
+            assert same_bytes(steps[4][:2], steps[3][:2])
+            assert_same_floats(steps[4][2], ref.vertex_normals(steps[3][0], steps[3][1]), "compute_normals")
+            assert_simplified(steps[5], steps[4], 40.0, "simplified again")
+            assert_filtered(steps[6], steps[5], 1, "filtered again")
+        return steps
+
+    first = chain(True)
+    held = (a.scratch_bytes, b.scratch_bytes)
+    again = chain(False)
+    assert all(same_bytes(x, y) for x, y in zip(first, again))         # warm scratch of other operations: the same bytes
+    assert (a.scratch_bytes, b.scratch_bytes) == held
 
 
 def test_an_empty_mesh():

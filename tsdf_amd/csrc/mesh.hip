@@ -12,7 +12,7 @@
 // into chunks of 64: one wave per chunk, lanes along the numbering (so along x, coalesced, wherever a row is long enough).  A chunk's
 // record holds three 64-bit masks -- which of its voxels have a used edge towards +x, +y, +z -- and two bases:
 //   mesh_edges_kernel      the masks (three __ballot), the chunk's vertex count (their popcount) and its soup-vertex count
-//   mesh_scan_*_kernel     exclusive scans of both counts over the chunks (1024 chunks a workgroup, then the workgroups' sums)
+//   mesh_scan_*_kernel     exclusive scans of both counts over the chunks (mesh_scan.hip)
 //   mesh_vertices_kernel   every used edge writes its vertex at
 //                              base + popcount of the three masks below its lane + (axis > 0: x-bit) + (axis > 1: y-bit)
 //                          which is the order of the key ((z Y + y) X + x) 3 + axis: no per-edge index array is ever stored
@@ -23,6 +23,7 @@
 #include <new>
 
 #include "common.hpp"
+#include "mesh_device.hpp"
 #include "mesh_handle.hpp"
 
 namespace tsdf {
@@ -64,14 +65,6 @@ __device__ inline bool mesh_voxel(const MeshBox &b, uint32_t chunk, uint32_t lan
     return first + lane < b.n_voxels;
 }
 
-__device__ inline uint32_t wave_inclusive_sum(uint32_t v, uint32_t lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(v, o);
-        if ((int)lane >= o) v += up;
-    }
-    return v;
-}
-
 // The configuration of the cube rooted at dist[base] (bit i: corner i negative, MarkAndSweepMC.cu:110-124).
 __device__ inline int mesh_cube_type(const float *__restrict__ dist, size_t base, size_t dy, size_t dz) {
     return (dist[base + dz] < 0) | (dist[base + 1 + dz] < 0) << 1 | (dist[base + 1] < 0) << 2 | (dist[base] < 0) << 3 |
@@ -107,87 +100,6 @@ __global__ __launch_bounds__(256) void mesh_edges_kernel(const float *__restrict
         c.vbase = (uint32_t)(__popcll(mx) + __popcll(my) + __popcll(mz));
         c.ibase = n;
         chunks[chunk] = c;
-    }
-}
-
-// ---- the two exclusive scans (vertices, indices) over the chunks -----------------------------------------------------------------
-// part[2 p], part[2 p + 1]: the sums of workgroup p's 1024 chunks
-__global__ __launch_bounds__(1024) void mesh_scan_sums_kernel(const MeshChunk *__restrict__ chunks, uint32_t n_chunks, uint64_t *__restrict__ part) {
-    __shared__ uint32_t sv[16], si[16];
-    const uint32_t i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t v = wave_inclusive_sum(i < n_chunks ? chunks[i].vbase : 0u, lane);
-    const uint32_t t = wave_inclusive_sum(i < n_chunks ? chunks[i].ibase : 0u, lane);
-    if (lane == 63) {
-        sv[wave] = v;
-        si[wave] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t a = 0, c = 0;
-        for (int w = 0; w < 16; w++) {
-            a += sv[w];
-            c += si[w];
-        }
-        part[2 * blockIdx.x] = a;
-        part[2 * blockIdx.x + 1] = c;
-    }
-}
-
-// In place, one workgroup: part[2 p], part[2 p + 1] = the sums of the parts before p; part[2 n_parts], [2 n_parts + 1] = the totals.
-__global__ __launch_bounds__(1024) void mesh_scan_parts_kernel(uint64_t *__restrict__ part, uint32_t n_parts) {
-    __shared__ uint64_t wave_sum[2][16];
-    __shared__ uint64_t carry[2];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x < 2) carry[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t first = 0; first < n_parts; first += 1024) {
-        const uint32_t i = first + threadIdx.x;
-        uint64_t v[2], incl[2];
-        for (int k = 0; k < 2; k++) {
-            v[k] = i < n_parts ? part[2 * (size_t)i + k] : 0;
-            incl[k] = v[k];
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint64_t up = __shfl_up(incl[k], o);
-                if ((int)lane >= o) incl[k] += up;
-            }
-            if (lane == 63) wave_sum[k][wave] = incl[k];
-        }
-        __syncthreads();
-        uint64_t before[2];
-        for (int k = 0; k < 2; k++) {
-            before[k] = carry[k];
-            for (uint32_t w = 0; w < wave; w++) before[k] += wave_sum[k][w];
-            if (i < n_parts) part[2 * (size_t)i + k] = before[k] + incl[k] - v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) {
-            carry[0] = before[0] + incl[0];
-            carry[1] = before[1] + incl[1];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 2) part[2 * (size_t)n_parts + threadIdx.x] = carry[threadIdx.x];
-}
-
-// counts -> bases.  (Totals above 2^32 - 1 wrap here; the host refuses them before anything reads a base.)
-__global__ __launch_bounds__(1024) void mesh_scan_apply_kernel(MeshChunk *__restrict__ chunks, uint32_t n_chunks, const uint64_t *__restrict__ part) {
-    __shared__ uint32_t sv[16], si[16];
-    const uint32_t i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t v = i < n_chunks ? chunks[i].vbase : 0u, t = i < n_chunks ? chunks[i].ibase : 0u;
-    const uint32_t iv = wave_inclusive_sum(v, lane), it = wave_inclusive_sum(t, lane);
-    if (lane == 63) {
-        sv[wave] = iv;
-        si[wave] = it;
-    }
-    __syncthreads();
-    uint32_t bv = (uint32_t)part[2 * blockIdx.x], bt = (uint32_t)part[2 * blockIdx.x + 1];
-    for (uint32_t w = 0; w < wave; w++) {
-        bv += sv[w];
-        bt += si[w];
-    }
-    if (i < n_chunks) {
-        chunks[i].vbase = bv + iv - v;
-        chunks[i].ibase = bt + it - t;
     }
 }
 
@@ -305,15 +217,6 @@ void mesh_free(tsdf_mesh *m) {
     delete m;
 }
 
-int mesh_wait(const tsdf_mesh *cm, const char *what) {
-    tsdf_mesh *m = const_cast<tsdf_mesh *>(cm);
-    if (m->pending) {
-        TSDF_HIP(hipEventSynchronize(m->done), what);
-        m->pending = 0;
-    }
-    return TSDF_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -373,7 +276,8 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
             hi[a] = box[a + 3] < last[a] ? box[a + 3] : last[a];
         }
     }
-    if (m->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, m->done, 0), "mesh stream order");   // what a previous extraction into this handle left in flight
+    const int rcj = mesh_join(m, v->stream);   // what a previous extraction into this handle left in flight
+    if (rcj != TSDF_OK) return rcj;
     m->info.n_vertices = m->info.n_indices = 0;
     m->labelled = 0;   // (mesh_components.hip)
     m->info.flags = flags;
@@ -395,7 +299,7 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
     b.n_voxels = (uint64_t)(b.bx + 1) * (b.by + 1) * (b.bz + 1);
     const uint64_t n_chunks64 = (b.n_voxels + 63) / 64;
     TSDF_REQUIRE(n_chunks64 < (1ull << 32), "tsdf_volume_extract_mesh: the box holds too many voxels");
-    const uint32_t n_chunks = (uint32_t)n_chunks64, n_parts = (n_chunks + 1023) / 1024;
+    const uint32_t n_chunks = (uint32_t)n_chunks64, n_parts = mesh_scan_parts(n_chunks);
     hipError_t e = mesh_reserve(m->chunks, m->chunks_cap, (size_t)n_chunks);
     if (e == hipSuccess) e = mesh_reserve(m->parts, m->parts_cap, 2 * ((size_t)n_parts + 1));
     if (e == hipSuccess && (!m->table_valid || memcmp(&t, &m->host_table, sizeof(t)) != 0)) {
@@ -410,9 +314,7 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
     const float *dist = v->dist - (size_t)g.z_store_begin * g.X * g.Y;   // (z_store_begin is 0: no slab here)
     const dim3 grid((n_chunks + 3) / 4);
     hipLaunchKernelGGL(mesh_edges_kernel, grid, dim3(256), 0, v->stream, dist, b, m->table, n_chunks, m->chunks);
-    hipLaunchKernelGGL(mesh_scan_sums_kernel, dim3(n_parts), dim3(1024), 0, v->stream, m->chunks, n_chunks, m->parts);
-    hipLaunchKernelGGL(mesh_scan_parts_kernel, dim3(1), dim3(1024), 0, v->stream, m->parts, n_parts);
-    hipLaunchKernelGGL(mesh_scan_apply_kernel, dim3(n_parts), dim3(1024), 0, v->stream, m->chunks, n_chunks, m->parts);
+    mesh_scan(ChunkCounts{m->chunks, n_chunks}, n_parts, m->parts, v->stream);
     TSDF_HIP(hipGetLastError(), "mesh count kernels failed");
     TSDF_HIP(hipMemcpyAsync(m->totals, m->parts + 2 * (size_t)n_parts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, v->stream), "mesh counts download");
     TSDF_HIP(hipStreamSynchronize(v->stream), "mesh count");   // the one synchronisation: the arrays are sized from the counts
@@ -433,8 +335,8 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
     if (flags & TSDF_MESH_NORMALS)
         rc = tsdf_volume_sample_field_device(cv, n_vertices, m->vertices, nullptr, m->normals, nullptr, TSDF_FIELD_UNIT_GRADIENT, v->stream);
     if (rc == TSDF_OK && (flags & TSDF_MESH_COLOURS)) rc = tsdf_volume_sample_colours_device(cv, n_vertices, m->vertices, m->rgb, v->stream);
-    TSDF_HIP(hipEventRecord(m->done, v->stream), "mesh event");
-    m->pending = 1;
+    const int rcl = mesh_leave(m, v->stream);
+    if (rcl != TSDF_OK) return rcl;
     if (rc != TSDF_OK) return rc;
     m->info.n_vertices = n_vertices;
     m->info.n_indices = n_indices;
@@ -450,7 +352,7 @@ int tsdf_mesh_get_info(const tsdf_mesh *m, tsdf_mesh_info *info) {
 int tsdf_mesh_buffers(const tsdf_mesh *m, const float **device_vertices, const uint32_t **device_indices, const float **device_normals,
                       const uint8_t **device_rgb) {
     TSDF_REQUIRE(m, "tsdf_mesh_buffers: null mesh");
-    const int rc = mesh_wait(m, "mesh wait");
+    const int rc = mesh_wait(m);
     if (rc != TSDF_OK) return rc;
     const bool any = m->info.n_vertices != 0;
     if (device_vertices) *device_vertices = any ? m->vertices : nullptr;
@@ -464,7 +366,7 @@ int tsdf_mesh_download(const tsdf_mesh *m, float *host_vertices, uint32_t *host_
     TSDF_REQUIRE(m, "tsdf_mesh_download: null mesh");
     TSDF_REQUIRE(!host_normals || (m->info.flags & TSDF_MESH_NORMALS), "tsdf_mesh_download: the mesh was extracted without TSDF_MESH_NORMALS");
     TSDF_REQUIRE(!host_rgb || (m->info.flags & TSDF_MESH_COLOURS), "tsdf_mesh_download: the mesh was extracted without TSDF_MESH_COLOURS");
-    const int rc = mesh_wait(m, "mesh wait");
+    const int rc = mesh_wait(m);
     if (rc != TSDF_OK) return rc;
     const size_t nv = (size_t)m->info.n_vertices, ni = (size_t)m->info.n_indices;
     if (nv == 0) return TSDF_OK;

@@ -19,13 +19,12 @@
 //      the word smaller, and the loop goes on from the value it returned; every loop is bounded by a strictly decreasing index.
 // The results are unique values (a minimum, integer sums, a maximum with a total order), so two runs give the same bytes.
 //
-// The filter has no atomics: keep flags per vertex and per triple by ballot over 64, popcount bases, the chunk scan of mesh.hip (the two
-// scans live in mesh_compact.hpp, which mesh_simplify.hip shares), and a stable compaction in which a new index is a base plus the
-// popcount below the lane.
+// The filter has no atomics: keep flags per vertex and per triple by ballot over 64, popcount bases, the chunk scan (mesh_scan.hip),
+// and a stable compaction in which a new index is a base plus the popcount below the lane (mesh_device.hpp).
 #include <new>
 
 #include "common.hpp"
-#include "mesh_compact.hpp"
+#include "mesh_device.hpp"
 #include "mesh_handle.hpp"
 
 namespace tsdf {
@@ -76,13 +75,13 @@ __global__ __launch_bounds__(256) void components_hook_kernel(uint32_t n_vertice
                                                               uint32_t *parent, uint64_t *__restrict__ words) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_triples) return;
-    const uint32_t a = indices[3 * t], b = indices[3 * t + 1], c = indices[3 * t + 2];
-    if (a >= n_vertices || b >= n_vertices || c >= n_vertices) {   // before any of them is an address
-        atomicMax((unsigned long long *)(words + kWordError), 1ull);
+    uint32_t c[3];
+    if (!load_triple(n_vertices, indices, t, c)) {
+        raise_error(words + kWordError, kErrorIndex);
         return;
     }
-    if (a != b) components_unite(parent, a, b);
-    if (a != c) components_unite(parent, a, c);
+    if (c[0] != c[1]) components_unite(parent, c[0], c[1]);
+    if (c[0] != c[2]) components_unite(parent, c[0], c[2]);
 }
 
 __global__ __launch_bounds__(256) void components_flatten_kernel(uint32_t n_vertices, uint32_t *labels, uint64_t *__restrict__ words) {
@@ -147,37 +146,27 @@ __global__ __launch_bounds__(256) void components_keep_kernel(uint32_t n_vertice
                                                               uint32_t *__restrict__ v_base, uint64_t *__restrict__ t_mask, uint32_t *__restrict__ t_base) {
     const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint64_t at = (uint64_t)chunk * 64 + lane;
-    if (chunk < v_chunks) {
-        const uint64_t m = __ballot(at < n_vertices && rule.keeps(labels[at], sizes[at]));
-        if (lane == 0) {
-            v_mask[chunk] = m;
-            v_base[chunk] = (uint32_t)__popcll(m);
-        }
-    }
+    if (chunk < v_chunks) store_keep_mask(at < n_vertices && rule.keeps(labels[at], sizes[at]), lane, chunk, v_mask, v_base);
     if (chunk < t_chunks) {
         bool keep = false;
         if (at < n_triples) {
             const uint32_t a = indices[3 * at];
             keep = rule.keeps(labels[a], sizes[a]);
         }
-        const uint64_t m = __ballot(keep);
-        if (lane == 0) {
-            t_mask[chunk] = m;
-            t_base[chunk] = (uint32_t)__popcll(m);
-        }
+        store_keep_mask(keep, lane, chunk, t_mask, t_base);
     }
 }
 
-// Stable compaction: a kept vertex goes to its chunk's base plus the kept vertices below its lane; normals and colours go with it.
+// Stable compaction: a kept vertex goes where compact_index says; normals and colours go with it.
 __global__ __launch_bounds__(256) void components_compact_vertices_kernel(uint32_t v_chunks, const uint64_t *__restrict__ v_mask, const uint32_t *__restrict__ v_base,
                                                                           const float *__restrict__ vertices, const float *__restrict__ normals,
                                                                           const uint8_t *__restrict__ rgb, float *__restrict__ out_vertices,
                                                                           float *__restrict__ out_normals, uint8_t *__restrict__ out_rgb) {
     const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (chunk >= v_chunks) return;
-    const uint64_t m = v_mask[chunk];
-    if (!((m >> lane) & 1u)) return;
-    const size_t from = ((size_t)chunk * 64 + lane) * 3, to = ((size_t)v_base[chunk] + __popcll(m & ((1ull << lane) - 1))) * 3;
+    if (!((v_mask[chunk] >> lane) & 1u)) return;
+    const uint32_t at = chunk * 64 + lane;
+    const size_t from = (size_t)at * 3, to = (size_t)compact_index(v_mask, v_base, at) * 3;
     for (int k = 0; k < 3; k++) out_vertices[to + k] = vertices[from + k];
     if (normals)
         for (int k = 0; k < 3; k++) out_normals[to + k] = normals[from + k];
@@ -191,13 +180,10 @@ __global__ __launch_bounds__(256) void components_compact_indices_kernel(uint32_
                                                                          const uint32_t *__restrict__ indices, uint32_t *__restrict__ out_indices) {
     const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (chunk >= t_chunks) return;
-    const uint64_t m = t_mask[chunk];
-    if (!((m >> lane) & 1u)) return;
-    const size_t from = ((size_t)chunk * 64 + lane) * 3, to = ((size_t)t_base[chunk] + __popcll(m & ((1ull << lane) - 1))) * 3;
-    for (int k = 0; k < 3; k++) {
-        const uint32_t v = indices[from + k], l = v & 63u;
-        out_indices[to + k] = v_base[v >> 6] + (uint32_t)__popcll(v_mask[v >> 6] & ((1ull << l) - 1));
-    }
+    if (!((t_mask[chunk] >> lane) & 1u)) return;
+    const uint32_t at = chunk * 64 + lane;
+    const size_t from = (size_t)at * 3, to = (size_t)compact_index(t_mask, t_base, at) * 3;
+    for (int k = 0; k < 3; k++) out_indices[to + k] = compact_index(v_mask, v_base, indices[from + k]);
 }
 
 }  // namespace tsdf
@@ -220,9 +206,8 @@ int label_on(uint32_t n_vertices, uint32_t n_indices, const uint32_t *indices, u
         hipLaunchKernelGGL(components_broadcast_kernel, grid_for(n_vertices, 256), dim3(256), 0, stream, n_vertices, labels, sizes, words);
     }
     TSDF_HIP(hipGetLastError(), "components kernels failed");
-    TSDF_HIP(hipMemcpyAsync(host, words, sizeof(host), hipMemcpyDeviceToHost, stream), "components download");
-    TSDF_HIP(hipStreamSynchronize(stream), "components");   // the one synchronisation
-    TSDF_REQUIRE(host[kWordError] == 0, "%s: an index is not below n_vertices (%u)", who, n_vertices);
+    const int rc = error_word_checked(who, n_vertices, words, host, kComponentWords, kWordError, stream);   // the one synchronisation
+    if (rc != TSDF_OK) return rc;
     if (info) {
         info->n_components = host[kWordRoots];
         info->n_triangles = n_triples;
@@ -264,13 +249,10 @@ extern "C" {
 int tsdf_label_components_device(uint64_t n_vertices, uint64_t n_indices, const uint32_t *device_indices, uint32_t *device_labels,
                                  uint32_t *device_component_triangles, tsdf_components_info *info, void *hip_stream) {
     TSDF_REQUIRE(device_labels, "tsdf_label_components_device: null device_labels");
-    TSDF_REQUIRE(device_indices || n_indices == 0, "tsdf_label_components_device: null device_indices with n_indices = %llu", (unsigned long long)n_indices);
-    TSDF_REQUIRE(n_indices % 3 == 0, "tsdf_label_components_device: n_indices (%llu) is not a multiple of 3", (unsigned long long)n_indices);
-    TSDF_REQUIRE(n_vertices <= 0xffffffffull && n_indices <= 0xffffffffull,
-                 "tsdf_label_components_device: %llu vertices and %llu indices do not fit 32-bit indices",
-                 (unsigned long long)n_vertices, (unsigned long long)n_indices);
+    const int rcc = indices_checked("tsdf_label_components_device", n_vertices, n_indices, device_indices);
+    if (rcc != TSDF_OK) return rcc;
     if (n_vertices == 0) {
-        TSDF_REQUIRE(n_indices == 0, "tsdf_label_components_device: an index is not below n_vertices (0)");
+        if (n_indices) return index_refused("tsdf_label_components_device", 0);
         if (info) *info = kNoComponents;
         return TSDF_OK;
     }
@@ -292,14 +274,11 @@ int tsdf_mesh_label_components(tsdf_mesh *m, tsdf_components_info *info, void *h
 int tsdf_mesh_component_buffers(const tsdf_mesh *cm, const uint32_t **device_labels, const uint32_t **device_component_triangles) {
     TSDF_REQUIRE(cm, "tsdf_mesh_component_buffers: null mesh");
     TSDF_REQUIRE(cm->labelled, "tsdf_mesh_component_buffers: the mesh has not been labelled since its last extraction (tsdf_mesh_label_components)");
-    tsdf_mesh *m = const_cast<tsdf_mesh *>(cm);
-    if (m->pending) {
-        TSDF_HIP(hipEventSynchronize(m->done), "mesh wait");
-        m->pending = 0;
-    }
-    const bool any = m->info.n_vertices != 0;
-    if (device_labels) *device_labels = any ? m->labels : nullptr;
-    if (device_component_triangles) *device_component_triangles = any ? m->sizes : nullptr;
+    const int rc = mesh_wait(cm);
+    if (rc != TSDF_OK) return rc;
+    const bool any = cm->info.n_vertices != 0;
+    if (device_labels) *device_labels = any ? cm->labels : nullptr;
+    if (device_component_triangles) *device_component_triangles = any ? cm->sizes : nullptr;
     return TSDF_OK;
 }
 
@@ -326,16 +305,15 @@ int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t
     if (rc == TSDF_OK) rc = mesh_join(src, stream);
     if (rc == TSDF_OK) rc = mesh_join(dst, stream);
     if (rc != TSDF_OK) return rc;
-    dst->labelled = 0;
-    dst->grid[0] = dst->grid[1] = dst->grid[2] = 0;   // (scene_flow.hip: not an extraction's arrays and records any more)
-    dst->info = src->info;
-    dst->info.n_vertices = dst->info.n_indices = 0;
+    mesh_reset(dst);
+    dst->info.flags = src->info.flags;
+    std::memcpy(dst->info.box, src->info.box, sizeof(dst->info.box));
     const uint64_t nv = src->info.n_vertices, n_triples = src->info.n_indices / 3;
     if (nv == 0) return TSDF_OK;
 
     const bool has_normals = (src->info.flags & TSDF_MESH_NORMALS) != 0, has_rgb = (src->info.flags & TSDF_MESH_COLOURS) != 0;
     const uint32_t v_chunks = (uint32_t)((nv + 63) / 64), t_chunks = (uint32_t)((n_triples + 63) / 64);
-    const uint32_t chunks = v_chunks > t_chunks ? v_chunks : t_chunks, n_parts = (chunks + 1023) / 1024;
+    const uint32_t chunks = v_chunks > t_chunks ? v_chunks : t_chunks, n_parts = mesh_scan_parts(chunks);
     hipError_t e = mesh_reserve(dst->keep_masks, dst->keep_masks_cap, (size_t)v_chunks + t_chunks);
     if (e == hipSuccess) e = mesh_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks + t_chunks);
     if (e == hipSuccess) e = mesh_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1));
@@ -349,9 +327,7 @@ int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t
     const dim3 grid((chunks + 3) / 4);
     hipLaunchKernelGGL(components_keep_kernel, grid, dim3(256), 0, stream, (uint32_t)nv, (uint32_t)n_triples, src->indices, src->labels, src->sizes, rule,
                        v_chunks, t_chunks, v_mask, v_base, t_mask, t_base);
-    hipLaunchKernelGGL(components_scan_sums_kernel, dim3(n_parts), dim3(1024), 0, stream, v_base, v_chunks, t_base, t_chunks, dst->parts);
-    hipLaunchKernelGGL(components_scan_parts_kernel, dim3(1), dim3(1024), 0, stream, dst->parts, n_parts);
-    hipLaunchKernelGGL(components_scan_apply_kernel, dim3(n_parts), dim3(1024), 0, stream, v_base, v_chunks, t_base, t_chunks, dst->parts);
+    mesh_scan(ArrayCounts{v_base, v_chunks, t_base, t_chunks}, n_parts, dst->parts, stream);
     TSDF_HIP(hipGetLastError(), "mesh filter count kernels failed");
     TSDF_HIP(hipMemcpyAsync(dst->totals, dst->parts + 2 * (size_t)n_parts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "mesh filter counts download");
     TSDF_HIP(hipStreamSynchronize(stream), "mesh filter count");   // the arrays are sized from the counts

@@ -1,32 +1,29 @@
 // Mesh simplification by vertex clustering on a cell grid (Rossignac-Borrel), on the device (include/tsdf_amd.h, "mesh
 // simplification").  Vertices whose cell floorf(V / h) is the same become one output vertex: the mean of their
 // positions (normals, colours); triples that lose a corner to a neighbour are dropped.  No sort, no float atomics, nothing waits.
-//   simplify_cluster_kernel        one lane per vertex: the 63-bit cell key goes into an open-addressed table (one 64-bit compare-and-
-//                                  swap per probe, linear probing), atomicMin of the vertex index into the slot's representative word,
-//                                  the slot stored per vertex.  A loose vertex (no cell: non-finite, too far out) touches no table.
+//   simplify_cluster_kernel        one lane per vertex: the 63-bit cell key goes into the open-addressed table (table_claim,
+//                                  mesh_device.hpp), atomicMin of the vertex index into the slot's representative word, the slot
+//                                  stored per vertex.  A loose vertex (no cell: non-finite, too far out) touches no table.
 //   simplify_keep_vertices_kernel  per vertex its cluster's representative (a loose vertex: itself); keep bit "I am the representative"
 //                                  by ballot over 64, popcounts
 //   simplify_keep_triples_kernel   validates the triple (the first kernel that reads I), keep bit "three distinct representatives"
-//   components_scan_*_kernel       the chunk scans of mesh_compact.hpp; then the one synchronisation: the two counts and the error word
+//   mesh_scan_*_kernel             the chunk scans (mesh_scan.hip); then the one synchronisation: the two counts and the error word
 //   simplify_accumulate_kernel     per vertex its output index (its representative's base plus popcount) and integer atomic adds of the
 //                                  quantised position (normal, colour) into that cluster's words, neighbouring lanes of one cluster
 //                                  summed in registers first
 //   simplify_emit_vertices_kernel  one lane per representative: a cluster of one keeps its member's bytes, the others divide their sums
 //   simplify_emit_triples_kernel   the stable compaction of the kept triples, indices replaced by output indices
-// The table never makes a lane wait: a probe ends on "was empty" (the compare-and-swap has just claimed the slot) or "was my key", and
-// anything else moves on to the next slot.  A slot, once it holds a key, holds it for the rest of the call; at most n_vertices keys
-// exist and the table has at least twice as many slots, so an empty slot lies on every walk and the walk ends within n_vertices + 1
-// probes whatever the other lanes do.  The representative word is only ever made smaller (atomicMin) and is read by later kernels only.
+// The table never makes a lane wait (the argument is at table_claim): at most n_vertices keys exist and the table has at least twice as
+// many slots.  The representative word is only ever made smaller (atomicMin) and is read by later kernels only.
 // Every result is a unique value -- a minimum, integer sums, a division of exact integers -- so two runs give the same bytes.
 #include <cmath>
 
 #include "common.hpp"
-#include "mesh_compact.hpp"
+#include "mesh_device.hpp"
 #include "mesh_handle.hpp"
 
 namespace tsdf {
 
-constexpr unsigned long long kEmptyKey = ~0ull;   // no key has bit 63
 constexpr uint32_t kLoose = 0xffffffffu;          // tsdf_mesh::cluster_of of a loose vertex, before the representatives are known
 constexpr uint64_t kSimplifyMaxVertices = 1ull << 30;   // the table's slots are numbered in 32 bits, below kLoose
 
@@ -41,7 +38,7 @@ __device__ inline bool cell_key(float x, float y, float z, float h, unsigned lon
     unsigned long long k = 0;
     for (int a = 2; a >= 0; a--) {
         const float f = floorf(c[a] / h);
-        if (!(fabsf(c[a]) < 2097152.0f) || !(fabsf(f) < 1048576.0f)) return false;   // (NaN fails both)
+        if (!coordinate_in_range(c[a]) || !(fabsf(f) < 1048576.0f)) return false;   // (NaN fails both)
         k = k << 21 | (unsigned long long)((int)f + 1048576);
     }
     *key = k;
@@ -58,22 +55,14 @@ __global__ __launch_bounds__(256) void simplify_cluster_kernel(uint32_t n_vertic
         cluster_of[v] = kLoose;
         return;
     }
-    const uint32_t mask = (uint32_t)((1ull << bits) - 1);
-    uint32_t slot = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - bits));
-    // Bounded by the table's size on top of the argument above: every trip finishes or advances, none waits.
-    uint64_t tries = 0;
-    for (; tries <= mask; tries++) {
-        const unsigned long long old = atomicCAS(keys + slot, kEmptyKey, key);
-        if (old == kEmptyKey || old == key) break;
-        slot = (slot + 1) & mask;
-    }
-    if (tries > mask) {   // (a table without an empty slot: not reachable at load <= 1/2)
-        atomicMax((unsigned long long *)error, 2ull);
+    uint64_t slot;
+    if (!table_claim(keys, bits, key, &slot)) {
+        raise_error(error, kErrorTableFull);
         cluster_of[v] = kLoose;
         return;
     }
     atomicMin(reps + slot, (uint32_t)v);
-    cluster_of[v] = slot;
+    cluster_of[v] = (uint32_t)slot;   // (at most 2^31 slots: kSimplifyMaxVertices)
 }
 
 // cluster_of: slot -> representative, in place (each lane rewrites its own word; reps is complete: the kernel boundary)
@@ -89,11 +78,7 @@ __global__ __launch_bounds__(256) void simplify_keep_vertices_kernel(uint32_t n_
         cluster_of[at] = rep;
         keep = rep == (uint32_t)at;
     }
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) {
-        v_mask[chunk] = m;
-        v_base[chunk] = (uint32_t)__popcll(m);
-    }
+    store_keep_mask(keep, lane, chunk, v_mask, v_base);
 }
 
 // (an index >= n_vertices raises the error word before it is an address; the host reads the word before anything is emitted)
@@ -105,19 +90,15 @@ __global__ __launch_bounds__(256) void simplify_keep_triples_kernel(uint32_t n_v
     const uint64_t at = (uint64_t)chunk * 64 + lane;
     bool keep = false;
     if (at < n_triples) {
-        const uint32_t a = indices[3 * at], b = indices[3 * at + 1], c = indices[3 * at + 2];
-        if (a >= n_vertices || b >= n_vertices || c >= n_vertices) {
-            atomicMax((unsigned long long *)error, 1ull);
+        uint32_t c[3];
+        if (!load_triple(n_vertices, indices, at, c)) {
+            raise_error(error, kErrorIndex);
         } else {
-            const uint32_t ra = cluster_of[a], rb = cluster_of[b], rc = cluster_of[c];
+            const uint32_t ra = cluster_of[c[0]], rb = cluster_of[c[1]], rc = cluster_of[c[2]];
             keep = ra != rb && ra != rc && rb != rc;
         }
     }
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) {
-        t_mask[chunk] = m;
-        t_base[chunk] = (uint32_t)__popcll(m);
-    }
+    store_keep_mask(keep, lane, chunk, t_mask, t_base);
 }
 
 __device__ inline void cluster_add(int64_t *word, long long q) { atomicAdd((unsigned long long *)word, (unsigned long long)q); }
@@ -141,9 +122,9 @@ __global__ __launch_bounds__(256) void simplify_accumulate_kernel(uint32_t n_ver
         live = cell_key(x, y, z, h, &key);
         if (live) {
             q[0] = 1;
-            q[1] = llrintf(x * 1024.0f);   // |V| < 2^21: the product is exact and below 2^31
-            q[2] = llrintf(y * 1024.0f);
-            q[3] = llrintf(z * 1024.0f);
+            q[1] = quantise_coordinate(x);
+            q[2] = quantise_coordinate(y);
+            q[3] = quantise_coordinate(z);
             if (row.normals) {
                 const float nx = normals[3 * v], ny = normals[3 * v + 1], nz = normals[3 * v + 2];
                 if (isfinite(nx) && isfinite(ny) && isfinite(nz)) {
@@ -190,9 +171,9 @@ __global__ __launch_bounds__(256) void simplify_emit_vertices_kernel(uint32_t v_
                                                                      uint8_t *__restrict__ out_rgb) {
     const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (chunk >= v_chunks) return;
-    const uint64_t m = v_mask[chunk];
-    if (!((m >> lane) & 1u)) return;
-    const size_t from = ((size_t)chunk * 64 + lane) * 3, j = (size_t)v_base[chunk] + __popcll(m & ((1ull << lane) - 1)), to = j * 3;
+    if (!((v_mask[chunk] >> lane) & 1u)) return;
+    const uint32_t at = chunk * 64 + lane;
+    const size_t from = (size_t)at * 3, j = compact_index(v_mask, v_base, at), to = j * 3;
     const int64_t *s = sums + j * row.words;
     const uint64_t n = (uint64_t)s[0];
     if (n <= 1) {   // a cluster of one (0: a loose vertex) keeps its member's bytes
@@ -204,14 +185,7 @@ __global__ __launch_bounds__(256) void simplify_emit_vertices_kernel(uint32_t v_
         return;
     }
     for (int k = 0; k < 3; k++) out_vertices[to + k] = (float)(((double)s[1 + k] / (double)n) / 1024.0);
-    if (row.normals) {
-        const double dx = (double)s[row.normals], dy = (double)s[row.normals + 1], dz = (double)s[row.normals + 2];
-        const double length = sqrt(dx * dx + dy * dy + dz * dz);
-        const float none = __uint_as_float(0x7fc00000u);
-        out_normals[to] = length == 0.0 ? none : (float)(dx / length);
-        out_normals[to + 1] = length == 0.0 ? none : (float)(dy / length);
-        out_normals[to + 2] = length == 0.0 ? none : (float)(dz / length);
-    }
+    if (row.normals) store_unit_or_nan(out_normals + to, (double)s[row.normals], (double)s[row.normals + 1], (double)s[row.normals + 2]);
     if (row.rgb)
         for (int k = 0; k < 3; k++) out_rgb[to + k] = (uint8_t)((2 * (uint64_t)s[row.rgb + k] + n) / (2 * n));
 }
@@ -221,9 +195,9 @@ __global__ __launch_bounds__(256) void simplify_emit_triples_kernel(uint32_t t_c
                                                                     uint32_t *__restrict__ out_indices) {
     const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (chunk >= t_chunks) return;
-    const uint64_t m = t_mask[chunk];
-    if (!((m >> lane) & 1u)) return;
-    const size_t from = ((size_t)chunk * 64 + lane) * 3, to = ((size_t)t_base[chunk] + __popcll(m & ((1ull << lane) - 1))) * 3;
+    if (!((t_mask[chunk] >> lane) & 1u)) return;
+    const uint32_t at = chunk * 64 + lane;
+    const size_t from = (size_t)at * 3, to = (size_t)compact_index(t_mask, t_base, at) * 3;
     for (int k = 0; k < 3; k++) out_indices[to + k] = cluster_of[indices[from + k]];
 }
 
@@ -236,11 +210,10 @@ namespace {
 // Everything between the argument checks and the counts in dst->info.  n_vertices > 0; dst->info is already that of an empty mesh.
 int simplify_on(uint32_t nv, uint32_t n_triples, const float *vertices, const uint32_t *indices, const float *normals, const uint8_t *rgb, float h,
                 tsdf_mesh *dst, hipStream_t stream, const char *who) {
-    uint32_t bits = 1;
-    while ((1ull << bits) < 2 * (uint64_t)nv) bits++;
+    const uint32_t bits = mesh_table_bits(nv);
     const size_t slots = (size_t)1 << bits;
     const uint32_t v_chunks = (nv + 63) / 64, t_chunks = (n_triples + 63) / 64;
-    const uint32_t chunks = v_chunks > t_chunks ? v_chunks : t_chunks, n_parts = (chunks + 1023) / 1024;
+    const uint32_t chunks = v_chunks > t_chunks ? v_chunks : t_chunks, n_parts = mesh_scan_parts(chunks);
     hipError_t e = mesh_reserve(dst->cell_keys, dst->cell_keys_cap, slots);
     if (e == hipSuccess) e = mesh_reserve(dst->cell_reps, dst->cell_reps_cap, slots);
     if (e == hipSuccess) e = mesh_reserve(dst->cluster_of, dst->cluster_of_cap, (size_t)nv);
@@ -261,14 +234,11 @@ int simplify_on(uint32_t nv, uint32_t n_triples, const float *vertices, const ui
     if (t_chunks)
         hipLaunchKernelGGL(simplify_keep_triples_kernel, dim3((t_chunks + 3) / 4), dim3(256), 0, stream, nv, n_triples, indices, dst->cluster_of, t_chunks,
                            t_mask, t_base, error);
-    hipLaunchKernelGGL(components_scan_sums_kernel, dim3(n_parts), dim3(1024), 0, stream, v_base, v_chunks, t_base, t_chunks, dst->parts);
-    hipLaunchKernelGGL(components_scan_parts_kernel, dim3(1), dim3(1024), 0, stream, dst->parts, n_parts);
-    hipLaunchKernelGGL(components_scan_apply_kernel, dim3(n_parts), dim3(1024), 0, stream, v_base, v_chunks, t_base, t_chunks, dst->parts);
+    mesh_scan(ArrayCounts{v_base, v_chunks, t_base, t_chunks}, n_parts, dst->parts, stream);
     TSDF_HIP(hipGetLastError(), "mesh simplify count kernels failed");
     uint64_t host[3] = {0, 0, 0};
-    TSDF_HIP(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, stream), "mesh simplify counts download");
-    TSDF_HIP(hipStreamSynchronize(stream), "mesh simplify count");   // the one synchronisation: the arrays are sized from the counts
-    TSDF_REQUIRE(host[2] != 1, "%s: an index is not below n_vertices (%u)", who, nv);
+    const int rc = error_word_checked(who, nv, totals, host, 3, 2, stream);   // the one synchronisation: the arrays are sized from the counts
+    if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(host[2] == 0, "%s: the cell table overflowed", who);
     const uint64_t n_clusters = host[0], kept_triples = host[1];
 
@@ -303,35 +273,18 @@ int simplify_on(uint32_t nv, uint32_t n_triples, const float *vertices, const ui
     return TSDF_OK;
 }
 
-// the checks both entry points share, and the run with dst's stream order round it
+// the checks both entry points share, and the run as a call into dst
 int simplify_checked(uint64_t n_vertices, uint64_t n_indices, const float *vertices, const uint32_t *indices, const float *normals, const uint8_t *rgb,
                      float cell_size, uint32_t flags, tsdf_mesh *dst, hipStream_t stream, const char *who) {
-    TSDF_REQUIRE(vertices || n_vertices == 0, "%s: null device_vertices with n_vertices = %llu", who, (unsigned long long)n_vertices);
-    TSDF_REQUIRE(indices || n_indices == 0, "%s: null device_indices with n_indices = %llu", who, (unsigned long long)n_indices);
-    TSDF_REQUIRE(n_indices % 3 == 0, "%s: n_indices (%llu) is not a multiple of 3", who, (unsigned long long)n_indices);
-    TSDF_REQUIRE(n_vertices <= 0xffffffffull && n_indices <= 0xffffffffull, "%s: %llu vertices and %llu indices do not fit 32-bit indices", who,
-                 (unsigned long long)n_vertices, (unsigned long long)n_indices);
+    const int rc = arrays_checked(who, n_vertices, n_indices, vertices, indices);
+    if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(std::isfinite(cell_size) && cell_size > 0.0f, "%s: cell_size (%g) is not a finite length above 0", who, (double)cell_size);
     TSDF_REQUIRE(flags == 0, "%s: unknown flags %#x", who, flags);
     TSDF_REQUIRE(n_vertices <= kSimplifyMaxVertices, "%s: %llu vertices are more than the 2^30 one call takes: simplify the mesh in boxes", who,
                  (unsigned long long)n_vertices);
-    int rc = mesh_join(dst, stream);
-    if (rc != TSDF_OK) return rc;
-    dst->labelled = 0;
-    dst->grid[0] = dst->grid[1] = dst->grid[2] = 0;   // (scene_flow.hip: not an extraction's arrays and records any more)
-    std::memset(&dst->info, 0, sizeof(dst->info));
-    dst->info.flags = (normals ? TSDF_MESH_NORMALS : 0u) | (rgb ? TSDF_MESH_COLOURS : 0u);
-    if (n_vertices == 0) {
-        TSDF_REQUIRE(n_indices == 0, "%s: an index is not below n_vertices (0)", who);
-        return TSDF_OK;
-    }
-    rc = simplify_on((uint32_t)n_vertices, (uint32_t)(n_indices / 3), vertices, indices, normals, rgb, cell_size, dst, stream, who);
-    const int rc2 = mesh_leave(dst, stream);
-    if (rc != TSDF_OK) {
-        dst->info.n_vertices = dst->info.n_indices = 0;
-        return rc;
-    }
-    return rc2;
+    return mesh_into(who, n_vertices, n_indices, (normals ? TSDF_MESH_NORMALS : 0u) | (rgb ? TSDF_MESH_COLOURS : 0u), dst, stream, [&] {
+        return simplify_on((uint32_t)n_vertices, (uint32_t)(n_indices / 3), vertices, indices, normals, rgb, cell_size, dst, stream, who);
+    });
 }
 
 }  // namespace
@@ -346,22 +299,12 @@ int tsdf_simplify_mesh_device(uint64_t n_vertices, uint64_t n_indices, const flo
 }
 
 int tsdf_mesh_simplify(tsdf_mesh *src, float cell_size, uint32_t flags, tsdf_mesh *dst, void *hip_stream) {
-    TSDF_REQUIRE(src, "tsdf_mesh_simplify: null src");
-    TSDF_REQUIRE(dst, "tsdf_mesh_simplify: null dst");
-    TSDF_REQUIRE(src != dst, "tsdf_mesh_simplify: dst is src (simplify into another handle)");
-    TSDF_REQUIRE(src->device == dst->device, "tsdf_mesh_simplify: src was created on device %d, dst on device %d", src->device, dst->device);
+    const char *who = "tsdf_mesh_simplify";
     hipStream_t stream = (hipStream_t)hip_stream;
-    int rc = mesh_join(src, stream);
-    if (rc != TSDF_OK) return rc;
-    const bool any = src->info.n_vertices != 0;
-    const bool has_normals = (src->info.flags & TSDF_MESH_NORMALS) != 0, has_rgb = (src->info.flags & TSDF_MESH_COLOURS) != 0;
-    rc = simplify_checked(src->info.n_vertices, src->info.n_indices, any ? src->vertices : nullptr, any ? src->indices : nullptr,
-                          any && has_normals ? src->normals : nullptr, any && has_rgb ? src->rgb : nullptr, cell_size, flags, dst, stream, "tsdf_mesh_simplify");
-    const int rc2 = any ? mesh_leave(src, stream) : TSDF_OK;   // src's arrays are read by what has just been enqueued
-    if (rc != TSDF_OK) return rc;
-    dst->info.flags = src->info.flags;
-    std::memcpy(dst->info.box, src->info.box, sizeof(dst->info.box));
-    return rc2;
+    return mesh_from_handle(who, "simplify", src, dst, 0u, stream,
+                            [&](uint64_t nv, uint64_t ni, const float *vertices, const uint32_t *indices, const float *normals, const uint8_t *rgb) {
+                                return simplify_checked(nv, ni, vertices, indices, normals, rgb, cell_size, flags, dst, stream, who);
+                            });
 }
 
 }  // extern "C"

@@ -3,45 +3,40 @@
 // the mean of the other two corners of the live triples that name it, computed from the previous pass's positions.
 //   smooth_count_kernel         one lane per triple: validates it (the first kernel that reads I), and a live one -- three different
 //                               corners, none loose -- adds 1 to the row length of each corner (integer atomics)
-//   smooth_row_sums_kernel      the row lengths of 64 vertices summed; components_scan_*_kernel (mesh_compact.hpp) turn the sums into bases
+//   smooth_row_sums_kernel      the row lengths of 64 vertices summed; mesh_scan_*_kernel (mesh_scan.hip) turn the sums into bases
 //   smooth_row_starts_kernel    per vertex where its row begins: its chunk's base plus the lengths below it in the chunk
 //   smooth_fill_kernel          one lane per triple: the other two corners into each corner's row at an atomic cursor.  The order inside a
 //                               row is that of arrival, which no result depends on: every sum over a row is an integer sum
-//   smooth_edges_kernel         TSDF_SMOOTH_PIN_BOUNDARY: the three edges of every live triple counted in mesh_simplify.hip's open-addressed
-//   smooth_pin_kernel           table (key (min << 32) | max, one compare-and-swap per probe); a slot counted once flags both its ends
+//   smooth_edges_kernel         TSDF_SMOOTH_PIN_BOUNDARY: the three edges of every live triple counted in the open-addressed table
+//   smooth_pin_kernel           (key (min << 32) | max; table_claim, mesh_device.hpp); a slot counted once flags both its ends
 //   smooth_pass_kernel          the hot path, 2 x iterations launches: one lane per vertex walks its row and gathers 12 bytes per neighbour
 //                               from the previous buffer; no atomics.  A row longer than a wave is walked by the whole wave
 //   smooth_face_normals_kernel  one lane per live triple: the cross product in double, quantised, nine 64-bit integer atomic adds
 //   smooth_emit_normals_kernel  one lane per vertex: the sums normalised
-// No lane waits for another anywhere: the table's walk ends on "was empty" or "was my key" (DESIGN.md 21 has the argument), everything
+// No lane waits for another anywhere: the table's walk ends on "was empty" or "was my key" (the argument is at table_claim), everything
 // else is atomic adds.  Every result is a unique value -- integer sums, double arithmetic on them in a fixed order -- so two runs give the
 // same bytes whatever order the waves run in.
 #include <cmath>
 
 #include "common.hpp"
-#include "mesh_compact.hpp"
+#include "mesh_device.hpp"
 #include "mesh_handle.hpp"
 
 namespace tsdf {
 
-constexpr unsigned long long kNoEdge = ~0ull;   // no edge has 0xffffffff as its smaller end
 constexpr uint32_t kWaveRow = 64;               // a row with more pairs than this is walked by its whole wave
 constexpr uint32_t kSmoothMaxIterations = 1024;
 
 // rule 1, in float on the positions given (NaN fails the comparison)
 __device__ inline bool smooth_loose(const float *__restrict__ vertices, uint32_t v) {
-    return !(fabsf(vertices[3 * (size_t)v]) < 2097152.0f) || !(fabsf(vertices[3 * (size_t)v + 1]) < 2097152.0f) ||
-           !(fabsf(vertices[3 * (size_t)v + 2]) < 2097152.0f);
+    return !coordinate_in_range(vertices[3 * (size_t)v]) || !coordinate_in_range(vertices[3 * (size_t)v + 1]) ||
+           !coordinate_in_range(vertices[3 * (size_t)v + 2]);
 }
 
-// The corners of triple t when it is live.  An index that is not below n_vertices makes the triple dead before it is an address
-// (*bad says so: the first kernel that reads I raises the error word, the host reads it before it returns).
+// The corners of triple t when it is live.  An index that is not below n_vertices makes the triple dead (load_triple; *bad says so).
 __device__ inline bool smooth_live(uint32_t n_vertices, const uint32_t *__restrict__ indices, const float *__restrict__ vertices, uint64_t t, uint32_t c[3],
                                    bool *bad) {
-    c[0] = indices[3 * t];
-    c[1] = indices[3 * t + 1];
-    c[2] = indices[3 * t + 2];
-    *bad = c[0] >= n_vertices || c[1] >= n_vertices || c[2] >= n_vertices;
+    *bad = !load_triple(n_vertices, indices, t, c);
     if (*bad || c[0] == c[1] || c[0] == c[2] || c[1] == c[2]) return false;
     return !smooth_loose(vertices, c[0]) && !smooth_loose(vertices, c[1]) && !smooth_loose(vertices, c[2]);
 }
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256) void smooth_count_kernel(uint32_t n_vertices, 
     uint32_t c[3];
     bool bad;
     if (!smooth_live(n_vertices, indices, vertices, t, c, &bad)) {
-        if (bad) atomicMax((unsigned long long *)error, 1ull);
+        if (bad) raise_error(error, kErrorIndex);
         return;
     }
     if (!counts) return;   // (a call without passes only validates)
@@ -66,7 +61,7 @@ __global__ __launch_bounds__(256) void smooth_row_sums_kernel(uint32_t n_vertice
     const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (chunk >= v_chunks) return;
     const uint64_t at = (uint64_t)chunk * 64 + lane;
-    const uint32_t sum = keep_inclusive_sum(at < n_vertices ? counts[at] : 0u, lane);
+    const uint32_t sum = wave_inclusive_sum(at < n_vertices ? counts[at] : 0u, lane);
     if (lane == 63) v_base[chunk] = sum;
 }
 
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(256) void smooth_row_starts_kernel(uint32_t n_verti
     if (chunk >= v_chunks) return;
     const uint64_t at = (uint64_t)chunk * 64 + lane;
     const uint32_t count = at < n_vertices ? cursor[at] : 0u;
-    const uint32_t begin = v_base[chunk] + keep_inclusive_sum(count, lane) - count;
+    const uint32_t begin = v_base[chunk] + wave_inclusive_sum(count, lane) - count;
     if (at < n_vertices) row_begin[at] = cursor[at] = begin;
 }
 
@@ -91,8 +86,7 @@ __global__ __launch_bounds__(256) void smooth_fill_kernel(uint32_t n_vertices, u
     for (int k = 0; k < 3; k++) rows[atomicAdd(cursor + c[k], 1u)] = make_uint2(c[(k + 1) % 3], c[(k + 2) % 3]);
 }
 
-// The table's walk is simplify_cluster_kernel's: every trip finishes or advances, none waits; at load <= 1/2 an empty slot lies on every
-// walk.
+// (three edges per live triple: at most n_indices keys in a table of at least twice as many slots)
 __global__ __launch_bounds__(256) void smooth_edges_kernel(uint32_t n_vertices, uint32_t n_triples, const uint32_t *__restrict__ indices,
                                                            const float *__restrict__ vertices, uint32_t bits, unsigned long long *keys, uint32_t *counts,
                                                            uint64_t *__restrict__ error) {
@@ -101,19 +95,12 @@ __global__ __launch_bounds__(256) void smooth_edges_kernel(uint32_t n_vertices, 
     uint32_t c[3];
     bool bad;
     if (!smooth_live(n_vertices, indices, vertices, t, c, &bad)) return;
-    const uint64_t mask = (1ull << bits) - 1;
     for (int k = 0; k < 3; k++) {
         const uint32_t u = c[k], w = c[(k + 1) % 3];
         const unsigned long long key = (unsigned long long)(u < w ? u : w) << 32 | (u < w ? w : u);
-        uint64_t slot = (key * 0x9E3779B97F4A7C15ull) >> (64 - bits);
-        uint64_t tries = 0;
-        for (; tries <= mask; tries++) {
-            const unsigned long long old = atomicCAS(keys + slot, kNoEdge, key);
-            if (old == kNoEdge || old == key) break;
-            slot = (slot + 1) & mask;
-        }
-        if (tries > mask) {   // (a table without an empty slot: not reachable at load <= 1/2)
-            atomicMax((unsigned long long *)error, 2ull);
+        uint64_t slot;
+        if (!table_claim(keys, bits, key, &slot)) {
+            raise_error(error, kErrorTableFull);
             return;
         }
         atomicAdd(counts + slot, 1u);
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(256) void smooth_pin_kernel(uint64_t slots, const u
     const uint64_t slot = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (slot >= slots) return;
     const unsigned long long key = keys[slot];
-    if (key == kNoEdge || counts[slot] != 1u) return;
+    if (key == kEmptyKey || counts[slot] != 1u) return;
     pinned[key >> 32] = 1;
     pinned[key & 0xffffffffull] = 1;
 }
@@ -134,7 +121,7 @@ __global__ __launch_bounds__(256) void smooth_pin_kernel(uint64_t slots, const u
 // q of rule 2 for the two neighbours of one pair (|P| < 2^21: the products are exact and below 2^31)
 __device__ inline void smooth_gather(const float *__restrict__ from, const uint2 pair, long long sum[3]) {
     const float *a = from + 3 * (size_t)pair.x, *b = from + 3 * (size_t)pair.y;
-    for (int k = 0; k < 3; k++) sum[k] += llrintf(a[k] * 1024.0f) + llrintf(b[k] * 1024.0f);
+    for (int k = 0; k < 3; k++) sum[k] += quantise_coordinate(a[k]) + quantise_coordinate(b[k]);
 }
 
 // One pass with factor f, rules 2 and 3.  One lane per vertex; a row of more than kWaveRow pairs (a fan's hub) is left out of the lane's
@@ -176,7 +163,7 @@ __global__ __launch_bounds__(256) void smooth_pass_kernel(uint32_t n_vertices, c
         for (int k = 0; k < 3; k++) {
             const double d = ((double)sum[k] / degree) / 1024.0;
             out[k] = (float)((double)p[k] + (double)f * (d - (double)p[k]));
-            good = good && fabsf(out[k]) < 2097152.0f;   // rule 3 (NaN and inf fail it)
+            good = good && coordinate_in_range(out[k]);   // rule 3 (NaN and inf fail it)
         }
         if (!good)
             for (int k = 0; k < 3; k++) out[k] = p[k];
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(256) void smooth_face_normals_kernel(uint32_t n_ver
     uint32_t c[3];
     bool bad;
     if (!smooth_live(n_vertices, indices, vertices, t, c, &bad)) {
-        if (bad) atomicMax((unsigned long long *)error, 1ull);
+        if (bad) raise_error(error, kErrorIndex);
         return;
     }
     const float *A = vertices + 3 * (size_t)c[0], *B = vertices + 3 * (size_t)c[2], *C = vertices + 3 * (size_t)c[1];   // extract_surface's wiring
@@ -212,12 +199,7 @@ __global__ __launch_bounds__(256) void smooth_face_normals_kernel(uint32_t n_ver
 __global__ __launch_bounds__(256) void smooth_emit_normals_kernel(uint32_t n_vertices, const int64_t *__restrict__ sums, float *__restrict__ normals) {
     const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= n_vertices) return;
-    const double dx = (double)sums[3 * v], dy = (double)sums[3 * v + 1], dz = (double)sums[3 * v + 2];
-    const double length = sqrt(dx * dx + dy * dy + dz * dz);
-    const float none = __uint_as_float(0x7fc00000u);
-    normals[3 * v] = length == 0.0 ? none : (float)(dx / length);
-    normals[3 * v + 1] = length == 0.0 ? none : (float)(dy / length);
-    normals[3 * v + 2] = length == 0.0 ? none : (float)(dz / length);
+    store_unit_or_nan(normals + 3 * v, (double)sums[3 * v], (double)sums[3 * v + 1], (double)sums[3 * v + 2]);
 }
 
 }  // namespace tsdf
@@ -243,10 +225,9 @@ int smooth_on(uint32_t nv, uint32_t n_triples, const float *vertices, const uint
     const float factor[2] = {lambda, mu};
     const uint64_t passes = n_triples ? (uint64_t)iterations * ((lambda != 0.0f) + (mu != 0.0f)) : 0;   // (without a triple nothing moves)
     const bool pins = passes != 0 && (flags & TSDF_SMOOTH_PIN_BOUNDARY), face_normals = (flags & TSDF_SMOOTH_NORMALS) != 0;
-    const uint32_t v_chunks = (nv + 63) / 64, n_parts = (v_chunks + 1023) / 1024;
+    const uint32_t v_chunks = (nv + 63) / 64, n_parts = mesh_scan_parts(v_chunks);
     const size_t n_indices = (size_t)n_triples * 3;
-    uint32_t bits = 1;
-    while ((1ull << bits) < 2 * (uint64_t)n_indices) bits++;   // three edges per triple, load <= 1/2
+    const uint32_t bits = mesh_table_bits(n_indices);   // three edges per triple
     const size_t slots = (size_t)1 << bits;
     hipError_t e = mesh_reserve(dst->vertices, dst->vertices_cap, (size_t)nv * 3);
     if (e == hipSuccess) e = mesh_reserve(dst->indices, dst->indices_cap, n_indices ? n_indices : 1);
@@ -280,9 +261,7 @@ int smooth_on(uint32_t nv, uint32_t n_triples, const float *vertices, const uint
         if (passes) {
             uint32_t *v_base = dst->keep_bases;
             hipLaunchKernelGGL(smooth_row_sums_kernel, dim3((v_chunks + 3) / 4), dim3(256), 0, stream, nv, cursor, v_chunks, v_base);
-            hipLaunchKernelGGL(components_scan_sums_kernel, dim3(n_parts), dim3(1024), 0, stream, v_base, v_chunks, (const uint32_t *)nullptr, 0u, dst->parts);
-            hipLaunchKernelGGL(components_scan_parts_kernel, dim3(1), dim3(1024), 0, stream, dst->parts, n_parts);
-            hipLaunchKernelGGL(components_scan_apply_kernel, dim3(n_parts), dim3(1024), 0, stream, v_base, v_chunks, (uint32_t *)nullptr, 0u, dst->parts);
+            mesh_scan(ArrayCounts{v_base, v_chunks, nullptr, 0u}, n_parts, dst->parts, stream);
             hipLaunchKernelGGL(smooth_row_starts_kernel, dim3((v_chunks + 3) / 4), dim3(256), 0, stream, nv, v_chunks, v_base, dst->row_begin, cursor);
             hipLaunchKernelGGL(smooth_fill_kernel, grid_for(n_triples, 256), dim3(256), 0, stream, nv, n_triples, indices, vertices, cursor, dst->rows);
         }
@@ -297,9 +276,8 @@ int smooth_on(uint32_t nv, uint32_t n_triples, const float *vertices, const uint
         }
         TSDF_HIP(hipGetLastError(), "mesh smooth row kernels failed");
         uint64_t host = 0;
-        TSDF_HIP(hipMemcpyAsync(&host, error, sizeof(host), hipMemcpyDeviceToHost, stream), "mesh smooth error word download");
-        TSDF_HIP(hipStreamSynchronize(stream), "mesh smooth rows");   // the one synchronisation: no pass runs on a mesh that is refused
-        TSDF_REQUIRE(host != 1, "%s: an index is not below n_vertices (%u)", who, nv);
+        const int rc = error_word_checked(who, nv, error, &host, 1, 0, stream);   // the one synchronisation: no pass runs on a mesh that is refused
+        if (rc != TSDF_OK) return rc;
         TSDF_REQUIRE(host == 0, "%s: the edge table overflowed", who);
     }
 
@@ -329,49 +307,24 @@ int smooth_on(uint32_t nv, uint32_t n_triples, const float *vertices, const uint
     return TSDF_OK;
 }
 
-int arrays_checked(uint64_t n_vertices, uint64_t n_indices, const float *vertices, const uint32_t *indices, const char *who) {
-    TSDF_REQUIRE(vertices || n_vertices == 0, "%s: null device_vertices with n_vertices = %llu", who, (unsigned long long)n_vertices);
-    TSDF_REQUIRE(indices || n_indices == 0, "%s: null device_indices with n_indices = %llu", who, (unsigned long long)n_indices);
-    TSDF_REQUIRE(n_indices % 3 == 0, "%s: n_indices (%llu) is not a multiple of 3", who, (unsigned long long)n_indices);
-    TSDF_REQUIRE(n_vertices <= 0xffffffffull && n_indices <= 0xffffffffull, "%s: %llu vertices and %llu indices do not fit 32-bit indices", who,
-                 (unsigned long long)n_vertices, (unsigned long long)n_indices);
-    return TSDF_OK;
-}
-
-// the checks both entry points share, and the run with dst's stream order round it
+// the checks both entry points share, and the run as a call into dst
 int smooth_checked(uint64_t n_vertices, uint64_t n_indices, const float *vertices, const uint32_t *indices, const float *normals, const uint8_t *rgb,
                    uint32_t iterations, float lambda, float mu, uint32_t flags, tsdf_mesh *dst, hipStream_t stream, const char *who) {
-    int rc = arrays_checked(n_vertices, n_indices, vertices, indices, who);
+    const int rc = arrays_checked(who, n_vertices, n_indices, vertices, indices);
     if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(std::isfinite(lambda) && std::isfinite(mu), "%s: lambda (%g) and mu (%g) must be finite", who, (double)lambda, (double)mu);
     TSDF_REQUIRE(iterations <= kSmoothMaxIterations, "%s: %u iterations are more than the %u one call takes", who, iterations, kSmoothMaxIterations);
     TSDF_REQUIRE((flags & ~(uint32_t)(TSDF_SMOOTH_PIN_BOUNDARY | TSDF_SMOOTH_NORMALS)) == 0, "%s: unknown flags %#x", who, flags);
-    rc = mesh_join(dst, stream);
-    if (rc != TSDF_OK) return rc;
-    dst->labelled = 0;
-    dst->grid[0] = dst->grid[1] = dst->grid[2] = 0;   // (scene_flow.hip: not an extraction's arrays and records any more)
-    std::memset(&dst->info, 0, sizeof(dst->info));
-    dst->info.flags = (normals || (flags & TSDF_SMOOTH_NORMALS) ? TSDF_MESH_NORMALS : 0u) | (rgb ? TSDF_MESH_COLOURS : 0u);
-    if (n_vertices == 0) {
-        TSDF_REQUIRE(n_indices == 0, "%s: an index is not below n_vertices (0)", who);
-        return TSDF_OK;
-    }
-    rc = smooth_on((uint32_t)n_vertices, (uint32_t)(n_indices / 3), vertices, indices, normals, rgb, iterations, lambda, mu, flags, dst, stream, who);
-    const int rc2 = mesh_leave(dst, stream);
-    if (rc != TSDF_OK) {
-        dst->info.n_vertices = dst->info.n_indices = 0;
-        return rc;
-    }
-    return rc2;
+    const uint32_t info_flags = (normals || (flags & TSDF_SMOOTH_NORMALS) ? TSDF_MESH_NORMALS : 0u) | (rgb ? TSDF_MESH_COLOURS : 0u);
+    return mesh_into(who, n_vertices, n_indices, info_flags, dst, stream, [&] {
+        return smooth_on((uint32_t)n_vertices, (uint32_t)(n_indices / 3), vertices, indices, normals, rgb, iterations, lambda, mu, flags, dst, stream, who);
+    });
 }
 
 // the error word of a normals call, read back: the one synchronisation
 int normals_verdict(const uint64_t *error, uint64_t n_vertices, hipStream_t stream, const char *who) {
     uint64_t host = 0;
-    TSDF_HIP(hipMemcpyAsync(&host, error, sizeof(host), hipMemcpyDeviceToHost, stream), "mesh normals error word download");
-    TSDF_HIP(hipStreamSynchronize(stream), "mesh normals");
-    TSDF_REQUIRE(host == 0, "%s: an index is not below n_vertices (%llu)", who, (unsigned long long)n_vertices);
-    return TSDF_OK;
+    return error_word_checked(who, n_vertices, error, &host, 1, 0, stream);
 }
 
 }  // namespace
@@ -387,35 +340,21 @@ int tsdf_smooth_mesh_device(uint64_t n_vertices, uint64_t n_indices, const float
 }
 
 int tsdf_mesh_smooth(tsdf_mesh *src, uint32_t iterations, float lambda, float mu, uint32_t flags, tsdf_mesh *dst, void *hip_stream) {
-    TSDF_REQUIRE(src, "tsdf_mesh_smooth: null src");
-    TSDF_REQUIRE(dst, "tsdf_mesh_smooth: null dst");
-    TSDF_REQUIRE(src != dst, "tsdf_mesh_smooth: dst is src (smooth into another handle)");
-    TSDF_REQUIRE(src->device == dst->device, "tsdf_mesh_smooth: src was created on device %d, dst on device %d", src->device, dst->device);
+    const char *who = "tsdf_mesh_smooth";
     hipStream_t stream = (hipStream_t)hip_stream;
-    int rc = mesh_join(src, stream);
-    if (rc != TSDF_OK) return rc;
-    const bool any = src->info.n_vertices != 0;
-    const bool has_normals = (src->info.flags & TSDF_MESH_NORMALS) != 0, has_rgb = (src->info.flags & TSDF_MESH_COLOURS) != 0;
-    rc = smooth_checked(src->info.n_vertices, src->info.n_indices, any ? src->vertices : nullptr, any ? src->indices : nullptr,
-                        any && has_normals ? src->normals : nullptr, any && has_rgb ? src->rgb : nullptr, iterations, lambda, mu, flags, dst, stream,
-                        "tsdf_mesh_smooth");
-    const int rc2 = any ? mesh_leave(src, stream) : TSDF_OK;   // src's arrays are read by what has just been enqueued
-    if (rc != TSDF_OK) return rc;
-    dst->info.flags = src->info.flags | (flags & TSDF_SMOOTH_NORMALS ? TSDF_MESH_NORMALS : 0u);
-    std::memcpy(dst->info.box, src->info.box, sizeof(dst->info.box));
-    return rc2;
+    return mesh_from_handle(who, "smooth", src, dst, flags & TSDF_SMOOTH_NORMALS ? TSDF_MESH_NORMALS : 0u, stream,
+                            [&](uint64_t nv, uint64_t ni, const float *vertices, const uint32_t *indices, const float *normals, const uint8_t *rgb) {
+                                return smooth_checked(nv, ni, vertices, indices, normals, rgb, iterations, lambda, mu, flags, dst, stream, who);
+                            });
 }
 
 int tsdf_vertex_normals_device(uint64_t n_vertices, uint64_t n_indices, const float *device_vertices, const uint32_t *device_indices,
                                float *device_normals_out, void *hip_stream) {
     const char *who = "tsdf_vertex_normals_device";
-    int rc = arrays_checked(n_vertices, n_indices, device_vertices, device_indices, who);
+    int rc = arrays_checked(who, n_vertices, n_indices, device_vertices, device_indices);
     if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(device_normals_out || n_vertices == 0, "%s: null device_normals_out with n_vertices = %llu", who, (unsigned long long)n_vertices);
-    if (n_vertices == 0) {
-        TSDF_REQUIRE(n_indices == 0, "%s: an index is not below n_vertices (0)", who);
-        return TSDF_OK;
-    }
+    if (n_vertices == 0) return n_indices ? index_refused(who, 0) : TSDF_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     int64_t *sums = nullptr;   // three sums per vertex and the error word, for the duration of the call
     TSDF_HIP(hipMalloc((void **)&sums, ((size_t)n_vertices * 3 + 1) * sizeof(int64_t)), "mesh normals scratch alloc failed");

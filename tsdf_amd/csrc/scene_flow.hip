@@ -192,7 +192,8 @@ int apply_scene_flow(tsdf_volume *v, tsdf_mesh *m, const uint16_t *depth, const 
     if (e == hipSuccess && !m->flow_totals) e = hipHostMalloc((void **)&m->flow_totals, 2 * sizeof(uint64_t), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "scene flow scratch alloc failed");
 
-    if (m->pending) TSDF_HIP(hipStreamWaitEvent(stream, m->done, 0), "scene flow stream order");   // the extraction's kernels
+    const int rcj = mesh_join(m, stream);   // the extraction's kernels
+    if (rcj != TSDF_OK) return rcj;
     const float *points = m->vertices;
     if (flags & TSDF_SCENE_FLOW_DEFORMED) {
         TSDF_HIP(hipMemcpyAsync(m->flow_points, m->vertices, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream), "scene flow vertices copy");
@@ -218,8 +219,8 @@ int apply_scene_flow(tsdf_volume *v, tsdf_mesh *m, const uint16_t *depth, const 
                        (uint64_t)v->g.X * v->g.Y, m->flow_vertex, nv, flow, nodes, counts);
     TSDF_HIP(hipGetLastError(), "scene flow kernels failed");
     // later extractions into the handle (they overwrite the records and the arrays) are ordered behind these launches
-    TSDF_HIP(hipEventRecord(m->done, stream), "scene flow event");
-    m->pending = 1;
+    const int rcl = mesh_leave(m, stream);
+    if (rcl != TSDF_OK) return rcl;
     if (!info) return TSDF_OK;
     TSDF_HIP(hipMemcpyAsync(m->flow_totals, m->flow_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "scene flow counts download");
     TSDF_HIP(hipStreamSynchronize(stream), "scene flow");   // the one synchronisation
