@@ -1,0 +1,140 @@
+// Stand-alone host program for a sanitizer build (make sanitize-device-buffer): the branches of tsdf_amd/csrc/device_buffer.hpp that a
+// machine WITH a device never takes.  Run where there is no device, every hipMalloc fails; the program checks what a failed growth
+// leaves behind, that releasing an empty handle does nothing, and the order in which the frame of a host variant reports errors.
+// With a device the allocations succeed and the same invariants are checked on that side.  Nothing is launched.
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+#include "device_buffer.hpp"
+
+static char g_message[512];
+static hipError_t g_failed_with = hipSuccess;   // what hip_fail was last given
+static const char *g_failed_what = nullptr;
+
+namespace tsdf {
+void set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_message, sizeof(g_message), fmt, ap);
+    va_end(ap);
+}
+int hip_fail(hipError_t e, const char *what) {
+    g_failed_with = e;
+    g_failed_what = what;
+    return e == hipErrorOutOfMemory ? TSDF_ERR_NOMEM : TSDF_ERR_DEVICE;
+}
+}  // namespace tsdf
+
+using namespace tsdf;
+
+static int failures = 0;
+#define EXPECT(cond, what)                                         \
+    do {                                                           \
+        if (!(cond)) {                                             \
+            std::printf("FAIL %s (line %d)\n", what, __LINE__);    \
+            failures++;                                            \
+        }                                                          \
+    } while (0)
+
+// a handle as the library makes them: a plain struct, all zero
+struct Handle {
+    float *floats;
+    size_t floats_cap;
+    void *bytes;
+    size_t bytes_cap;
+    unsigned *pairs;
+    size_t pairs_cap;
+};
+
+int main() {
+    Handle h;
+    std::memset(&h, 0, sizeof(h));
+
+    // release and free-all of an empty handle: nothing happens, nothing is touched
+    device_release(h.floats, h.floats_cap);
+    device_release(h.bytes, h.bytes_cap);
+    device_free_all(h.floats, h.bytes, h.pairs);
+    Handle zero;
+    std::memset(&zero, 0, sizeof(zero));
+    EXPECT(std::memcmp(&h, &zero, sizeof(h)) == 0, "release of an empty handle changes it");
+
+    // want <= cap: nothing is done, not even with a pointer that is no allocation
+    h.floats = reinterpret_cast<float *>(&h);
+    h.floats_cap = 8;
+    EXPECT(device_reserve(h.floats, h.floats_cap, (size_t)8) == hipSuccess && h.floats == reinterpret_cast<float *>(&h) && h.floats_cap == 8,
+           "a reserve within the capacity touched the array");
+    h.floats = nullptr;
+    h.floats_cap = 0;
+    EXPECT(device_reserve(h.floats, h.floats_cap, (size_t)0) == hipSuccess && !h.floats && h.floats_cap == 0, "a reserve of nothing");
+
+    // growth, twice: a failure leaves the array empty, and the next call tries (and fails) again
+    for (int round = 0; round < 2; round++) {
+        const hipError_t e = device_reserve(h.floats, h.floats_cap, (size_t)100);
+        if (e == hipSuccess) EXPECT(h.floats && h.floats_cap == 100, "a successful reserve");
+        else EXPECT(!h.floats && h.floats_cap == 0, "a failed reserve does not leave the array empty");
+        const hipError_t eb = device_reserve_bytes(h.bytes, h.bytes_cap, (size_t)100);
+        if (eb == hipSuccess) EXPECT(h.bytes && h.bytes_cap == 100, "a successful reserve in bytes");
+        else EXPECT(!h.bytes && h.bytes_cap == 0, "a failed reserve in bytes does not leave the array empty");
+        const hipError_t eu = device_reserve_units(h.pairs, h.pairs_cap, (size_t)100, 2 * sizeof(unsigned));
+        if (eu == hipSuccess) EXPECT(h.pairs && h.pairs_cap == 100, "a successful reserve in units");
+        else EXPECT(!h.pairs && h.pairs_cap == 0, "a failed reserve in units does not leave the array empty");
+        EXPECT(e == eb && e == eu, "the three forms disagree");
+        if (round == 0) std::printf("hipMalloc here: %s\n", hipGetErrorString(e));
+    }
+    device_release(h.floats, h.floats_cap);
+    device_release(h.bytes, h.bytes_cap);
+    device_free_all(h.pairs);
+    h.pairs_cap = 0;
+    EXPECT(std::memcmp(&h, &zero, sizeof(h)) == 0, "release does not leave an empty handle");
+
+    // the frame of a host variant
+    const hipError_t sync_here = hipStreamSynchronize(nullptr);
+    (void)hipGetLastError();
+    HostStage st;
+    g_message[0] = 0;
+    const int rc = st.begin(nullptr, 4096, "caller: couldn't allocate %zu bytes");
+    if (rc != TSDF_OK) {
+        EXPECT(rc == TSDF_ERR_NOMEM && !st.buf && std::strcmp(g_message, "caller: couldn't allocate 4096 bytes") == 0,
+               "a failed begin: TSDF_ERR_NOMEM with the caller's text");
+    } else {
+        EXPECT(st.buf && st.ok(), "a successful begin");
+    }
+    // (finish on whatever begin left -- a null buffer is fine -- in the order: the call's rc, the first copy failure, the synchronisation)
+    char host[16] = {0};
+    auto staged = [&](hipError_t copy_error) {
+        HostStage s;
+        s.stream = nullptr;
+        s.buf = nullptr;
+        s.e = copy_error;
+        g_failed_with = hipSuccess;
+        g_failed_what = nullptr;
+        return s;
+    };
+    {
+        HostStage s = staged(hipErrorInvalidValue);
+        EXPECT(s.finish(TSDF_ERR_INVALID, "what") == TSDF_ERR_INVALID && g_failed_what == nullptr, "finish: the call's rc comes first");
+    }
+    {
+        HostStage s = staged(hipErrorInvalidValue);
+        EXPECT(s.finish(TSDF_OK, "what") == TSDF_ERR_DEVICE && g_failed_with == hipErrorInvalidValue && g_failed_what && !std::strcmp(g_failed_what, "what"),
+               "finish: then the first copy failure");
+    }
+    {
+        HostStage s = staged(hipSuccess);
+        const int got = s.finish(TSDF_OK, "what");
+        if (sync_here == hipSuccess) EXPECT(got == TSDF_OK && g_failed_what == nullptr, "finish: nothing failed");
+        else EXPECT(got != TSDF_OK && g_failed_with == sync_here && g_failed_what && !std::strcmp(g_failed_what, "what"), "finish: then the synchronisation's failure");
+    }
+    {   // a copy that failed stops the copies behind it: the first failure is the one reported
+        HostStage s = staged(hipErrorInvalidValue);
+        s.up(host, host, sizeof(host));
+        s.down(host, host, sizeof(host));
+        EXPECT(s.e == hipErrorInvalidValue && !s.ok(), "up / down after a failure");
+    }
+    (void)st.finish(TSDF_OK, "what");
+    (void)hipGetLastError();
+
+    std::printf(failures ? "device buffer host checks: %d FAILED\n" : "device buffer host checks ok\n", failures);
+    return failures ? 1 : 0;
+}

@@ -161,9 +161,8 @@ __global__ __launch_bounds__(256) void depth_to_points_kernel(const uint16_t *__
 }
 
 static void free_aligner(tsdf_aligner *a) {
-    if (a->partial) (void)hipFree(a->partial);
-    if (a->state) (void)hipFree(a->state);
-    if (a->host_io) (void)hipHostFree(a->host_io);
+    device_free_all(a->partial, a->state);
+    (void)hipHostFree(a->host_io);
     delete a;
 }
 

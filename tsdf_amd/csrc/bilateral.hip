@@ -318,13 +318,11 @@ static int filter_host(const tsdf_bilateral *cf, PIX *host_image, int width, int
     TSDF_REQUIRE(cf && host_image && width > 0 && height > 0, "tsdf_bilateral_filter: bad argument");
     tsdf_bilateral *f = const_cast<tsdf_bilateral *>(cf);
     size_t bytes = (size_t)width * height * sizeof(PIX);
-    if (f->img_cap < bytes) {
-        if (f->img_in) (void)hipFree(f->img_in);
-        if (f->img_out) (void)hipFree(f->img_out);
-        f->img_in = f->img_out = nullptr;
+    if (f->img_cap < bytes) {   // two arrays under one capacity word: it is 0 unless both are there, so a failure replaces both next time
+        size_t in_cap = 0, out_cap = 0;   // (capacities of 0: each call below replaces its array)
         f->img_cap = 0;
-        TSDF_HIP(hipMalloc(&f->img_in, bytes), "bilateral image alloc");
-        TSDF_HIP(hipMalloc(&f->img_out, bytes), "bilateral image alloc");
+        TSDF_HIP(device_reserve_bytes(f->img_in, in_cap, bytes), "bilateral image alloc");
+        TSDF_HIP(device_reserve_bytes(f->img_out, out_cap, bytes), "bilateral image alloc");
         f->img_cap = bytes;
     }
     TSDF_HIP(hipMemcpy(f->img_in, host_image, bytes, hipMemcpyHostToDevice), "bilateral H2D");
@@ -498,10 +496,7 @@ int tsdf_selftest_bilateral_chain_image(float sigma_colour, float sigma_space, c
 
 int tsdf_bilateral_destroy(tsdf_bilateral *f) {
     if (!f) return TSDF_OK;
-    if (f->kernel_dev) (void)hipFree(f->kernel_dev);
-    if (f->similarity_dev) (void)hipFree(f->similarity_dev);
-    if (f->img_in) (void)hipFree(f->img_in);
-    if (f->img_out) (void)hipFree(f->img_out);
+    device_free_all(f->kernel_dev, f->similarity_dev, f->img_in, f->img_out);
     delete f;
     return TSDF_OK;
 }

@@ -224,20 +224,8 @@ int tsdf_integrate_colour(tsdf_volume *v, const uint16_t *host_depth, const uint
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate_colour: empty depth map");
     TSDF_REQUIRE(!v->nodes, "tsdf_integrate_colour: not supported once the deformation nodes are explicit (deformation() / set_deformation())");
     const size_t pixels = (size_t)width * height;
-    if (v->depth_cap < pixels * sizeof(uint16_t)) {
-        if (v->depth_buf) (void)hipFree(v->depth_buf);
-        v->depth_buf = nullptr;
-        v->depth_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->depth_buf, pixels * sizeof(uint16_t)), "Couldn't allocate storage for depth map");
-        v->depth_cap = pixels * sizeof(uint16_t);
-    }
-    if (v->rgb_cap < pixels * 3) {
-        if (v->rgb_buf) (void)hipFree(v->rgb_buf);
-        v->rgb_buf = nullptr;
-        v->rgb_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->rgb_buf, pixels * 3), "Couldn't allocate storage for colour frame");
-        v->rgb_cap = pixels * 3;
-    }
+    TSDF_HIP(device_reserve_bytes(v->depth_buf, v->depth_cap, pixels * sizeof(uint16_t)), "Couldn't allocate storage for depth map");
+    TSDF_HIP(device_reserve(v->rgb_buf, v->rgb_cap, pixels * 3), "Couldn't allocate storage for colour frame");
     TSDF_HIP(hipMemcpyAsync(v->depth_buf, host_depth, pixels * sizeof(uint16_t), hipMemcpyHostToDevice, v->stream),
              "Failed to copy depth map to GPU");
     TSDF_HIP(hipMemcpyAsync(v->rgb_buf, host_rgb, pixels * 3, hipMemcpyHostToDevice, v->stream), "Failed to copy colour frame to GPU");
@@ -275,13 +263,7 @@ int tsdf_raycast_colour(const tsdf_volume *cv, uint32_t width, uint32_t height, 
     // tsdf_raycast leaves the vertex map in the handle's vertex buffer: the colours are sampled from there
     int rc = tsdf_raycast(v, width, height, pose, kinv, host_vertices, host_normals);
     if (rc != TSDF_OK) return rc;
-    if (v->rgb_cap < pixels * 3) {
-        if (v->rgb_buf) (void)hipFree(v->rgb_buf);
-        v->rgb_buf = nullptr;
-        v->rgb_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->rgb_buf, pixels * 3), "Couldn't allocate storage for colour map");
-        v->rgb_cap = pixels * 3;
-    }
+    TSDF_HIP(device_reserve(v->rgb_buf, v->rgb_cap, pixels * 3), "Couldn't allocate storage for colour map");
     rc = sample_colours(v, pixels, v->vert_buf, v->rgb_buf, v->stream);
     if (rc != TSDF_OK) return rc;
     TSDF_HIP(hipMemcpyAsync(host_rgb, v->rgb_buf, pixels * 3, hipMemcpyDeviceToHost, v->stream), "Colours Memcpy failed");

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "tsdf_amd.h"
+#include "device_buffer.hpp"
 
 struct tsdf_volume;
 

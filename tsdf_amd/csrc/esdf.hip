@@ -156,22 +156,10 @@ struct tsdf_esdf {
 
 namespace {
 
-hipError_t esdf_reserve(float *&p, size_t &cap, size_t want) {
-    if (want <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc((void **)&p, want * sizeof(float));
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
 void esdf_free(tsdf_esdf *s) {
     if (s->done) (void)hipEventSynchronize(s->done);
-    if (s->out) (void)hipFree(s->out);
-    if (s->work) (void)hipFree(s->work);
-    if (s->aux) (void)hipFree(s->aux);
-    if (s->n_sites_host) (void)hipHostFree(s->n_sites_host);
+    device_free_all(s->out, s->work, s->aux);
+    (void)hipHostFree(s->n_sites_host);
     if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
@@ -249,8 +237,8 @@ int tsdf_volume_compute_esdf(const tsdf_volume *cv, float max_distance, uint32_t
     TSDF_REQUIRE(v->device == s->device, "tsdf_volume_compute_esdf: the handle was created on device %d, the volume on device %d", s->device, v->device);
     if (s->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, s->done, 0), "esdf stream order");   // what a previous computation into this handle left in flight
     const size_t n = (size_t)g.X * g.Y * g.Z;
-    hipError_t e = esdf_reserve(s->out, s->out_cap, n);
-    if (e == hipSuccess) e = esdf_reserve(s->work, s->work_cap, n);
+    hipError_t e = device_reserve(s->out, s->out_cap, n);
+    if (e == hipSuccess) e = device_reserve(s->work, s->work_cap, n);
     if (e != hipSuccess) {
         s->computed = 0;
         return hip_fail(e, "esdf array alloc failed");
@@ -334,24 +322,18 @@ int tsdf_esdf_sample(const tsdf_esdf *s, uint64_t n, const float *host_points, f
     // one allocation: points (3n), then distance (n) and gradient (3n) as far as asked for; on the null stream, blocking
     const size_t fn = (size_t)n;
     const size_t o_d = 3 * fn, o_g = o_d + (host_distance ? fn : 0), total = o_g + (host_gradient ? 3 * fn : 0);
-    float *buf = nullptr;
-    if (hipMalloc((void **)&buf, total * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("tsdf_esdf_sample: couldn't allocate %zu bytes for the points and results", total * sizeof(float));
-        return TSDF_ERR_NOMEM;
-    }
-    float *d = host_distance ? buf + o_d : nullptr, *g = host_gradient ? buf + o_g : nullptr;
-    hipError_t e = hipMemcpy(buf, host_points, 3 * fn * sizeof(float), hipMemcpyHostToDevice);
-    int rc = TSDF_OK;
-    if (e == hipSuccess) rc = sample_field_view(esdf_view(s), s->fast_div != 0, n, buf, d, g, nullptr, flags, nullptr);
-    if (rc == TSDF_OK && e == hipSuccess && d) e = hipMemcpy(host_distance, d, fn * sizeof(float), hipMemcpyDeviceToHost);
-    if (rc == TSDF_OK && e == hipSuccess && g) e = hipMemcpy(host_gradient, g, 3 * fn * sizeof(float), hipMemcpyDeviceToHost);
-    const hipError_t es = hipStreamSynchronize(nullptr);   // (before the buffer goes, whatever happened)
-    (void)hipFree(buf);
+    HostStage st;
+    int rc = st.begin(nullptr, total * sizeof(float), "tsdf_esdf_sample: couldn't allocate %zu bytes for the points and results");
     if (rc != TSDF_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "Distance field sample failed");
-    if (es != hipSuccess) return hip_fail(es, "Distance field sample failed");
-    return TSDF_OK;
+    float *const buf = static_cast<float *>(st.buf);
+    float *d = host_distance ? buf + o_d : nullptr, *g = host_gradient ? buf + o_g : nullptr;
+    st.up(buf, host_points, 3 * fn * sizeof(float));
+    if (st.ok()) rc = sample_field_view(esdf_view(s), s->fast_div != 0, n, buf, d, g, nullptr, flags, nullptr);
+    if (rc == TSDF_OK) {
+        if (d) st.down(host_distance, d, fn * sizeof(float));
+        if (g) st.down(host_gradient, g, 3 * fn * sizeof(float));
+    }
+    return st.finish(rc, "Distance field sample failed");
 }
 
 int tsdf_esdf_scratch_bytes(const tsdf_esdf *s, uint64_t *bytes) {

@@ -122,25 +122,19 @@ int tsdf_volume_sample_field(const tsdf_volume *v, uint64_t n, const float *host
     // one allocation: points (3n), then distance (n), gradient (3n), weight (n) as far as asked for
     const size_t fn = (size_t)n;
     const size_t o_d = 3 * fn, o_g = o_d + (host_distance ? fn : 0), o_w = o_g + (host_gradient ? 3 * fn : 0), total = o_w + (host_weight ? fn : 0);
-    float *buf = nullptr;
-    if (hipMalloc((void **)&buf, total * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("tsdf_volume_sample_field: couldn't allocate %zu bytes for the points and results", total * sizeof(float));
-        return TSDF_ERR_NOMEM;
-    }
-    float *d = host_distance ? buf + o_d : nullptr, *g = host_gradient ? buf + o_g : nullptr, *w = host_weight ? buf + o_w : nullptr;
-    hipError_t e = hipMemcpyAsync(buf, host_points, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
-    int rc = TSDF_OK;
-    if (e == hipSuccess) rc = sample_field(v, n, buf, d, g, w, flags, v->stream);
-    if (rc == TSDF_OK && e == hipSuccess && d) e = hipMemcpyAsync(host_distance, d, fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (rc == TSDF_OK && e == hipSuccess && g) e = hipMemcpyAsync(host_gradient, g, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (rc == TSDF_OK && e == hipSuccess && w) e = hipMemcpyAsync(host_weight, w, fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    const hipError_t es = hipStreamSynchronize(v->stream);   // (before the buffer goes, whatever happened)
-    (void)hipFree(buf);
+    HostStage st;
+    int rc = st.begin(v->stream, total * sizeof(float), "tsdf_volume_sample_field: couldn't allocate %zu bytes for the points and results");
     if (rc != TSDF_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "Field sample failed");
-    if (es != hipSuccess) return hip_fail(es, "Field sample failed");
-    return TSDF_OK;
+    float *const buf = static_cast<float *>(st.buf);
+    float *d = host_distance ? buf + o_d : nullptr, *g = host_gradient ? buf + o_g : nullptr, *w = host_weight ? buf + o_w : nullptr;
+    st.up(buf, host_points, 3 * fn * sizeof(float));
+    if (st.ok()) rc = sample_field(v, n, buf, d, g, w, flags, v->stream);
+    if (rc == TSDF_OK) {
+        if (d) st.down(host_distance, d, fn * sizeof(float));
+        if (g) st.down(host_gradient, g, 3 * fn * sizeof(float));
+        if (w) st.down(host_weight, w, fn * sizeof(float));
+    }
+    return st.finish(rc, "Field sample failed");
 }
 
 int tsdf_raycast_gradient_normals_device(const tsdf_volume *v, uint32_t width, uint32_t height, const float pose[16], const float kinv[9],

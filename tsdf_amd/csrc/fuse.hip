@@ -231,14 +231,8 @@ static int fuse_check(const tsdf_volume *v, const char *what) {
 // header {fused voxels (u64), list length, pad}, the brick list, the source summary
 static int fuse_scratch(tsdf_volume *dst, size_t bytes) {
     if (dst->fuse_scratch_cap >= bytes) return TSDF_OK;
-    if (dst->fuse_scratch) {
-        TSDF_HIP(hipStreamSynchronize(dst->stream), "fuse scratch");
-        (void)hipFree(dst->fuse_scratch);
-        dst->fuse_scratch = nullptr;
-        dst->fuse_scratch_cap = 0;
-    }
-    TSDF_HIP(hipMalloc(&dst->fuse_scratch, bytes), "Couldn't allocate the scratch of tsdf_volume_fuse");
-    dst->fuse_scratch_cap = bytes;
+    if (dst->fuse_scratch) TSDF_HIP(hipStreamSynchronize(dst->stream), "fuse scratch");   // (launches that read it may be in flight)
+    TSDF_HIP(device_reserve_bytes(dst->fuse_scratch, dst->fuse_scratch_cap, bytes), "Couldn't allocate the scratch of tsdf_volume_fuse");
     return TSDF_OK;
 }
 

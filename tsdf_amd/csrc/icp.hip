@@ -276,17 +276,9 @@ __global__ __launch_bounds__(kIcpThreads) void icp_finish_kernel(const double *_
 }
 
 static void free_icp(tsdf_icp *f) {
-    for (int i = 0; i < kIcpLevels; i++) {
-        if (f->depth[i]) (void)hipFree(f->depth[i]);
-        if (f->vmap_prev[i]) (void)hipFree(f->vmap_prev[i]);
-        if (f->nmap_prev[i]) (void)hipFree(f->nmap_prev[i]);
-        if (f->vmap_curr[i]) (void)hipFree(f->vmap_curr[i]);
-        if (f->nmap_curr[i]) (void)hipFree(f->nmap_curr[i]);
-    }
-    if (f->upload) (void)hipFree(f->upload);
-    if (f->partial) (void)hipFree(f->partial);
-    if (f->state) (void)hipFree(f->state);
-    if (f->host_io) (void)hipHostFree(f->host_io);
+    for (int i = 0; i < kIcpLevels; i++) device_free_all(f->depth[i], f->vmap_prev[i], f->nmap_prev[i], f->vmap_curr[i], f->nmap_curr[i]);
+    device_free_all(f->upload, f->partial, f->state);
+    (void)hipHostFree(f->host_io);
     delete f;
 }
 

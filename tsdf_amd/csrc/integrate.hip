@@ -353,7 +353,7 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     bool fresh_scratch = false;   // scratch allocated (and zeroed, on the volume's stream) by this very call
     if (!v->touched || v->touched_nx != bg.nx || v->touched_ny != bg.ny || v->touched_nz != bg.nz) {
         fresh_scratch = true;
-        if (v->touched) (void)hipFree(v->touched);
+        (void)hipFree(v->touched);
         v->touched = nullptr;
         TSDF_HIP(hipMalloc((void **)&v->touched, n_bricks), "touched bricks alloc");
         TSDF_HIP(hipMemsetAsync(v->touched, 0, n_bricks, v->stream), "touched bricks alloc");
@@ -364,24 +364,14 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     const uint32_t tiles_x = (width + kDepthTile - 1) / kDepthTile, tiles_y = (height + kDepthTile - 1) / kDepthTile;
     if (v->brick_list_cap < n_bricks + 2) {
         fresh_scratch = true;
-        if (v->brick_list) (void)hipFree(v->brick_list);
-        v->brick_list = nullptr;
-        v->brick_list_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->brick_list, (n_bricks + 2) * sizeof(uint32_t)), "brick list alloc");
+        TSDF_HIP(device_reserve(v->brick_list, v->brick_list_cap, n_bricks + 2), "brick list alloc");
         TSDF_HIP(hipMemsetAsync(v->brick_list + n_bricks, 0, 2 * sizeof(uint32_t), v->stream), "brick list alloc");   // both length words
-        v->brick_list_cap = n_bricks + 2;
         v->brick_count_side = 0;
     }
-    if (v->tile_max_cap < (size_t)tiles_x * tiles_y) {
-        if (v->tile_max) (void)hipFree(v->tile_max);
-        v->tile_max = nullptr;
-        v->tile_max_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->tile_max, (size_t)tiles_x * tiles_y * sizeof(uint16_t)), "depth tile alloc");
-        v->tile_max_cap = (size_t)tiles_x * tiles_y;
-    }
+    TSDF_HIP(device_reserve(v->tile_max, v->tile_max_cap, (size_t)tiles_x * tiles_y), "depth tile alloc");
     if (v->wmode != 0 && !v->nodes && (!v->depth_pad || v->depth_pad_w != width || v->depth_pad_h != height)) {
         // (re)allocated between frames only: the culling that fills it and the integrate_packed_kernel that reads it belong to one frame
-        if (v->depth_pad) (void)hipFree(v->depth_pad);
+        (void)hipFree(v->depth_pad);
         v->depth_pad = nullptr;
         v->prepared_valid = 0;
         const size_t pad_bytes = (size_t)(width + 2u) * (height + 2u) * sizeof(uint16_t);
@@ -402,13 +392,8 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     if (phase == kIntBoth) v->prepared_valid = 0;     // (used up, or stale)
     if (prepared) v->brick_count_side = 1u - v->brick_count_side;   // back to the side the prepare call appended behind (toggled again below)
     uint32_t *count = v->brick_list + n_bricks + v->brick_count_side, *count_next = v->brick_list + n_bricks + (1u - v->brick_count_side);
-    if (v->brick_box_cap < n_bricks) {
-        if (v->brick_boxes) (void)hipFree(v->brick_boxes);
-        v->brick_boxes = nullptr;
-        v->brick_box_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->brick_boxes, n_bricks * 6 * sizeof(uint32_t)), "brick box alloc");   // (boxes, then the bricks' coordinates)
-        v->brick_box_cap = n_bricks;
-    }
+    // (per brick: its box, four words, then -- behind all the boxes -- its coordinates, two)
+    TSDF_HIP(device_reserve_units(v->brick_boxes, v->brick_box_cap, n_bricks, 6 * sizeof(uint32_t)), "brick box alloc");
     uint4 *boxes = reinterpret_cast<uint4 *>(v->brick_boxes);
     uint2 *coords = reinterpret_cast<uint2 *>(v->brick_boxes + 4 * v->brick_box_cap);   // per listed brick: {bx | by << 16, bz}, for integrate_packed_kernel
     const uint32_t n_plane_const = g.z_store_end - g.z_store_begin + kBatchZ;  // padded: a batch may run past the last plane
@@ -602,45 +587,31 @@ int tsdf_integrate_discard_prepared(tsdf_volume *v) {
     return TSDF_OK;
 }
 
-int tsdf_integrate(tsdf_volume *v, const uint16_t *host_depth, uint32_t width, uint32_t height,
-                   const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]) {
-    TSDF_REQUIRE(v && host_depth && inv_pose && k && kinv, "tsdf_integrate: null argument");
-    TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate: empty depth map");
-    size_t bytes = (size_t)width * height * sizeof(uint16_t);
-    if (v->depth_cap < bytes) {
-        if (v->depth_buf) (void)hipFree(v->depth_buf);
-        v->depth_buf = nullptr;
-        v->depth_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->depth_buf, bytes), "Couldn't allocate storage for depth map");
-        v->depth_cap = bytes;
-    }
+// the host variants of integrate and de-integrate (remove): the frame through the volume's cached depth buffer, blocking
+static int integrate_host(tsdf_volume *v, const uint16_t *host_depth, uint32_t width, uint32_t height, const float pose[16],
+                          const float inv_pose[16], const float k[9], const float kinv[9], bool remove, const char *who, const char *sync_what) {
+    TSDF_REQUIRE(v && host_depth && inv_pose && k && kinv, "%s: null argument", who);
+    TSDF_REQUIRE(width > 0 && height > 0, "%s: empty depth map", who);
+    TSDF_REQUIRE(!remove || v->weight_cap == 0, "tsdf_deintegrate: the volume has a weight cap (a saturated count is not a frame count: tsdf_volume_set_weight_cap(volume, 0) first)");
+    const size_t bytes = (size_t)width * height * sizeof(uint16_t);
+    TSDF_HIP(device_reserve_bytes(v->depth_buf, v->depth_cap, bytes), "Couldn't allocate storage for depth map");
     TSDF_HIP(hipMemcpyAsync(v->depth_buf, host_depth, bytes, hipMemcpyHostToDevice, v->stream),
              "Failed to copy depth map to GPU");
-    int rc = tsdf_integrate_device(v, v->depth_buf, width, height, pose, inv_pose, k, kinv);
+    const int rc = remove ? tsdf_deintegrate_device(v, v->depth_buf, width, height, pose, inv_pose, k, kinv)
+                          : tsdf_integrate_device(v, v->depth_buf, width, height, pose, inv_pose, k, kinv);
     if (rc != TSDF_OK) return rc;
-    TSDF_HIP(hipStreamSynchronize(v->stream), "Integrate kernel failed");
+    TSDF_HIP(hipStreamSynchronize(v->stream), sync_what);
     return TSDF_OK;
+}
+
+int tsdf_integrate(tsdf_volume *v, const uint16_t *host_depth, uint32_t width, uint32_t height,
+                   const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]) {
+    return integrate_host(v, host_depth, width, height, pose, inv_pose, k, kinv, false, "tsdf_integrate", "Integrate kernel failed");
 }
 
 int tsdf_deintegrate(tsdf_volume *v, const uint16_t *host_depth, uint32_t width, uint32_t height,
                      const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]) {
-    TSDF_REQUIRE(v && host_depth && inv_pose && k && kinv, "tsdf_deintegrate: null argument");
-    TSDF_REQUIRE(width > 0 && height > 0, "tsdf_deintegrate: empty depth map");
-    TSDF_REQUIRE(v->weight_cap == 0, "tsdf_deintegrate: the volume has a weight cap (a saturated count is not a frame count: tsdf_volume_set_weight_cap(volume, 0) first)");
-    size_t bytes = (size_t)width * height * sizeof(uint16_t);
-    if (v->depth_cap < bytes) {
-        if (v->depth_buf) (void)hipFree(v->depth_buf);
-        v->depth_buf = nullptr;
-        v->depth_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->depth_buf, bytes), "Couldn't allocate storage for depth map");
-        v->depth_cap = bytes;
-    }
-    TSDF_HIP(hipMemcpyAsync(v->depth_buf, host_depth, bytes, hipMemcpyHostToDevice, v->stream),
-             "Failed to copy depth map to GPU");
-    int rc = tsdf_deintegrate_device(v, v->depth_buf, width, height, pose, inv_pose, k, kinv);
-    if (rc != TSDF_OK) return rc;
-    TSDF_HIP(hipStreamSynchronize(v->stream), "De-integrate kernel failed");
-    return TSDF_OK;
+    return integrate_host(v, host_depth, width, height, pose, inv_pose, k, kinv, true, "tsdf_deintegrate", "De-integrate kernel failed");
 }
 
 }  // extern "C"

@@ -204,9 +204,7 @@ static int rays_scratch(tsdf_volume *v, RaysScratch &s) {
     if (v->rays_scratch_cap != bytes) {
         if (v->rays_scratch) {
             TSDF_HIP(hipStreamSynchronize(v->stream), "ray integration scratch");
-            (void)hipFree(v->rays_scratch);
-            v->rays_scratch = nullptr;
-            v->rays_scratch_cap = 0;
+            device_release(v->rays_scratch, v->rays_scratch_cap);
         }
         if (hipMalloc(&v->rays_scratch, bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -230,9 +228,7 @@ static int rays_colour_scratch(tsdf_volume *v, unsigned long long *&col) {
     if (v->rays_colour_scratch_cap != bytes) {
         if (v->rays_colour_scratch) {
             TSDF_HIP(hipStreamSynchronize(v->stream), "ray integration colour scratch");
-            (void)hipFree(v->rays_colour_scratch);
-            v->rays_colour_scratch = nullptr;
-            v->rays_colour_scratch_cap = 0;
+            device_release(v->rays_colour_scratch, v->rays_colour_scratch_cap);
         }
         if (hipMalloc(&v->rays_colour_scratch, bytes) != hipSuccess) {
             (void)hipGetLastError();
@@ -335,27 +331,19 @@ static int rays_integrate_host(tsdf_volume *v, uint64_t n, const float *host_ori
                                const uint8_t *host_rgb, float min_range, float max_range, int flags, uint64_t *updated_voxels) {
     // one allocation: the origins, then the points, then the colours
     const size_t fo = 3 * (size_t)n_origins, fp = 3 * (size_t)n, bytes = (fo + fp) * sizeof(float) + (host_rgb ? 3 * (size_t)n : 0);
-    float *buf = nullptr;
-    if (hipMalloc((void **)&buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("tsdf_integrate_rays: couldn't allocate %zu bytes for the rays", bytes);
-        return TSDF_ERR_NOMEM;
-    }
-    uint8_t *const rgb = host_rgb ? reinterpret_cast<uint8_t *>(buf + fo + fp) : nullptr;
-    hipError_t e = hipMemcpyAsync(buf, host_origins, fo * sizeof(float), hipMemcpyHostToDevice, v->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(buf + fo, host_points, fp * sizeof(float), hipMemcpyHostToDevice, v->stream);
-    if (e == hipSuccess && rgb) e = hipMemcpyAsync(rgb, host_rgb, 3 * (size_t)n, hipMemcpyHostToDevice, v->stream);
-    int rc = TSDF_OK;
-    uint64_t updated = 0;
-    if (e == hipSuccess)
-        rc = rays_integrate(v, n, buf, n_origins, buf + fo, rgb, min_range, max_range, flags, updated_voxels ? &updated : nullptr);
-    const hipError_t es = hipStreamSynchronize(v->stream);   // (before the buffer goes, whatever happened)
-    (void)hipFree(buf);
+    HostStage st;
+    int rc = st.begin(v->stream, bytes, "tsdf_integrate_rays: couldn't allocate %zu bytes for the rays");
     if (rc != TSDF_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "Ray integration failed");
-    if (es != hipSuccess) return hip_fail(es, "Ray integration failed");
-    if (updated_voxels) *updated_voxels = updated;
-    return TSDF_OK;
+    float *const buf = static_cast<float *>(st.buf);
+    uint8_t *const rgb = host_rgb ? reinterpret_cast<uint8_t *>(buf + fo + fp) : nullptr;
+    st.up(buf, host_origins, fo * sizeof(float));
+    st.up(buf + fo, host_points, fp * sizeof(float));
+    if (rgb) st.up(rgb, host_rgb, 3 * (size_t)n);
+    uint64_t updated = 0;
+    if (st.ok()) rc = rays_integrate(v, n, buf, n_origins, buf + fo, rgb, min_range, max_range, flags, updated_voxels ? &updated : nullptr);
+    rc = st.finish(rc, "Ray integration failed");
+    if (rc == TSDF_OK && updated_voxels) *updated_voxels = updated;
+    return rc;
 }
 
 }  // namespace tsdf
@@ -419,12 +407,8 @@ int tsdf_volume_release_ray_scratch(tsdf_volume *v) {
     TSDF_REQUIRE(v, "tsdf_volume_release_ray_scratch: null volume");
     if (!v->rays_scratch && !v->rays_colour_scratch) return TSDF_OK;
     TSDF_HIP(hipStreamSynchronize(v->stream), "ray integration scratch");
-    if (v->rays_scratch) (void)hipFree(v->rays_scratch);
-    v->rays_scratch = nullptr;
-    v->rays_scratch_cap = 0;
-    if (v->rays_colour_scratch) (void)hipFree(v->rays_colour_scratch);
-    v->rays_colour_scratch = nullptr;
-    v->rays_colour_scratch_cap = 0;
+    device_release(v->rays_scratch, v->rays_scratch_cap);
+    device_release(v->rays_colour_scratch, v->rays_colour_scratch_cap);
     return TSDF_OK;
 }
 

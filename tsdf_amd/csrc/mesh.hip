@@ -184,35 +184,11 @@ namespace {
 
 void mesh_free(tsdf_mesh *m) {
     if (m->done) (void)hipEventSynchronize(m->done);
-    if (m->vertices) (void)hipFree(m->vertices);
-    if (m->indices) (void)hipFree(m->indices);
-    if (m->normals) (void)hipFree(m->normals);
-    if (m->rgb) (void)hipFree(m->rgb);
-    if (m->chunks) (void)hipFree(m->chunks);
-    if (m->parts) (void)hipFree(m->parts);
-    if (m->table) (void)hipFree(m->table);
-    if (m->labels) (void)hipFree(m->labels);
-    if (m->sizes) (void)hipFree(m->sizes);
-    if (m->component_words) (void)hipFree(m->component_words);
-    if (m->keep_masks) (void)hipFree(m->keep_masks);
-    if (m->keep_bases) (void)hipFree(m->keep_bases);
-    if (m->cell_keys) (void)hipFree(m->cell_keys);
-    if (m->cell_reps) (void)hipFree(m->cell_reps);
-    if (m->cluster_of) (void)hipFree(m->cluster_of);
-    if (m->cluster_sums) (void)hipFree(m->cluster_sums);
-    if (m->row_begin) (void)hipFree(m->row_begin);
-    if (m->row_end) (void)hipFree(m->row_end);
-    if (m->rows) (void)hipFree(m->rows);
-    if (m->smooth_positions) (void)hipFree(m->smooth_positions);
-    if (m->pinned) (void)hipFree(m->pinned);
-    if (m->normal_sums) (void)hipFree(m->normal_sums);
-    if (m->flow_vertex) (void)hipFree(m->flow_vertex);
-    if (m->flow_points) (void)hipFree(m->flow_points);
-    if (m->flow_counts) (void)hipFree(m->flow_counts);
-    if (m->flow_depth) (void)hipFree(m->flow_depth);
-    if (m->flow_image) (void)hipFree(m->flow_image);
-    if (m->flow_totals) (void)hipHostFree(m->flow_totals);
-    if (m->totals) (void)hipHostFree(m->totals);
+    device_free_all(m->vertices, m->indices, m->normals, m->rgb, m->chunks, m->parts, m->table, m->labels, m->sizes, m->component_words,
+                    m->keep_masks, m->keep_bases, m->cell_keys, m->cell_reps, m->cluster_of, m->cluster_sums, m->row_begin, m->row_end, m->rows,
+                    m->smooth_positions, m->pinned, m->normal_sums, m->flow_vertex, m->flow_points, m->flow_counts, m->flow_depth, m->flow_image);
+    (void)hipHostFree(m->flow_totals);
+    (void)hipHostFree(m->totals);
     if (m->done) (void)hipEventDestroy(m->done);
     delete m;
 }
@@ -300,8 +276,8 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
     const uint64_t n_chunks64 = (b.n_voxels + 63) / 64;
     TSDF_REQUIRE(n_chunks64 < (1ull << 32), "tsdf_volume_extract_mesh: the box holds too many voxels");
     const uint32_t n_chunks = (uint32_t)n_chunks64, n_parts = mesh_scan_parts(n_chunks);
-    hipError_t e = mesh_reserve(m->chunks, m->chunks_cap, (size_t)n_chunks);
-    if (e == hipSuccess) e = mesh_reserve(m->parts, m->parts_cap, 2 * ((size_t)n_parts + 1));
+    hipError_t e = device_reserve(m->chunks, m->chunks_cap, (size_t)n_chunks);
+    if (e == hipSuccess) e = device_reserve(m->parts, m->parts_cap, 2 * ((size_t)n_parts + 1));
     if (e == hipSuccess && (!m->table_valid || memcmp(&t, &m->host_table, sizeof(t)) != 0)) {
         m->table_valid = 0;
         // (host_table outlives the copy; a handle is used by one thread at a time, and the stream waited for `done` above)
@@ -323,10 +299,10 @@ int tsdf_volume_extract_mesh(const tsdf_volume *cv, const int8_t *table, const u
                  "tsdf_volume_extract_mesh: %llu vertices and %llu indices do not fit 32-bit indices: extract the volume in boxes",
                  (unsigned long long)n_vertices, (unsigned long long)n_indices);
     if (n_vertices == 0) return TSDF_OK;   // (no vertex, so no index either)
-    e = mesh_reserve(m->vertices, m->vertices_cap, (size_t)n_vertices * 3);
-    if (e == hipSuccess) e = mesh_reserve(m->indices, m->indices_cap, (size_t)n_indices);
-    if (e == hipSuccess && (flags & TSDF_MESH_NORMALS)) e = mesh_reserve(m->normals, m->normals_cap, (size_t)n_vertices * 3);
-    if (e == hipSuccess && (flags & TSDF_MESH_COLOURS)) e = mesh_reserve(m->rgb, m->rgb_cap, (size_t)n_vertices * 3);
+    e = device_reserve(m->vertices, m->vertices_cap, (size_t)n_vertices * 3);
+    if (e == hipSuccess) e = device_reserve(m->indices, m->indices_cap, (size_t)n_indices);
+    if (e == hipSuccess && (flags & TSDF_MESH_NORMALS)) e = device_reserve(m->normals, m->normals_cap, (size_t)n_vertices * 3);
+    if (e == hipSuccess && (flags & TSDF_MESH_COLOURS)) e = device_reserve(m->rgb, m->rgb_cap, (size_t)n_vertices * 3);
     if (e != hipSuccess) return hip_fail(e, "mesh array alloc failed");
     hipLaunchKernelGGL(mesh_vertices_kernel, grid, dim3(256), 0, v->stream, dist, b, g.vs, g.offset, n_chunks, m->chunks, m->vertices);
     hipLaunchKernelGGL(mesh_triangles_kernel, grid, dim3(256), 0, v->stream, dist, b, m->table, n_chunks, m->chunks, m->indices);

@@ -230,8 +230,8 @@ int mesh_label(tsdf_mesh *m, hipStream_t stream, const char *who) {
     }
     int rc = mesh_join(m, stream);
     if (rc != TSDF_OK) return rc;
-    hipError_t e = mesh_reserve(m->labels, m->labels_cap, (size_t)nv);
-    if (e == hipSuccess) e = mesh_reserve(m->sizes, m->sizes_cap, (size_t)nv);
+    hipError_t e = device_reserve(m->labels, m->labels_cap, (size_t)nv);
+    if (e == hipSuccess) e = device_reserve(m->sizes, m->sizes_cap, (size_t)nv);
     if (e == hipSuccess && !m->component_words) e = hipMalloc((void **)&m->component_words, kComponentWords * sizeof(uint64_t));
     if (e != hipSuccess) return hip_fail(e, "mesh components alloc failed");
     rc = label_on((uint32_t)nv, (uint32_t)ni, m->indices, m->labels, m->sizes, m->component_words, &m->components, stream, who);
@@ -314,9 +314,9 @@ int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t
     const bool has_normals = (src->info.flags & TSDF_MESH_NORMALS) != 0, has_rgb = (src->info.flags & TSDF_MESH_COLOURS) != 0;
     const uint32_t v_chunks = (uint32_t)((nv + 63) / 64), t_chunks = (uint32_t)((n_triples + 63) / 64);
     const uint32_t chunks = v_chunks > t_chunks ? v_chunks : t_chunks, n_parts = mesh_scan_parts(chunks);
-    hipError_t e = mesh_reserve(dst->keep_masks, dst->keep_masks_cap, (size_t)v_chunks + t_chunks);
-    if (e == hipSuccess) e = mesh_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks + t_chunks);
-    if (e == hipSuccess) e = mesh_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1));
+    hipError_t e = device_reserve(dst->keep_masks, dst->keep_masks_cap, (size_t)v_chunks + t_chunks);
+    if (e == hipSuccess) e = device_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks + t_chunks);
+    if (e == hipSuccess) e = device_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1));
     if (e != hipSuccess) return hip_fail(e, "mesh filter scratch alloc failed");
     uint64_t *v_mask = dst->keep_masks, *t_mask = dst->keep_masks + v_chunks;
     uint32_t *v_base = dst->keep_bases, *t_base = dst->keep_bases + v_chunks;
@@ -333,10 +333,10 @@ int tsdf_mesh_filter_components(tsdf_mesh *src, uint64_t min_triangles, uint32_t
     TSDF_HIP(hipStreamSynchronize(stream), "mesh filter count");   // the arrays are sized from the counts
     const uint64_t kept_vertices = dst->totals[0], kept_triples = dst->totals[1];
     if (kept_vertices == 0) return mesh_leave(src, stream);
-    e = mesh_reserve(dst->vertices, dst->vertices_cap, (size_t)kept_vertices * 3);
-    if (e == hipSuccess) e = mesh_reserve(dst->indices, dst->indices_cap, (size_t)(kept_triples ? kept_triples * 3 : 1));
-    if (e == hipSuccess && has_normals) e = mesh_reserve(dst->normals, dst->normals_cap, (size_t)kept_vertices * 3);
-    if (e == hipSuccess && has_rgb) e = mesh_reserve(dst->rgb, dst->rgb_cap, (size_t)kept_vertices * 3);
+    e = device_reserve(dst->vertices, dst->vertices_cap, (size_t)kept_vertices * 3);
+    if (e == hipSuccess) e = device_reserve(dst->indices, dst->indices_cap, (size_t)(kept_triples ? kept_triples * 3 : 1));
+    if (e == hipSuccess && has_normals) e = device_reserve(dst->normals, dst->normals_cap, (size_t)kept_vertices * 3);
+    if (e == hipSuccess && has_rgb) e = device_reserve(dst->rgb, dst->rgb_cap, (size_t)kept_vertices * 3);
     if (e != hipSuccess) return hip_fail(e, "mesh array alloc failed");
     hipLaunchKernelGGL(components_compact_vertices_kernel, dim3((v_chunks + 3) / 4), dim3(256), 0, stream, v_chunks, v_mask, v_base, src->vertices,
                        has_normals ? src->normals : nullptr, has_rgb ? src->rgb : nullptr, dst->vertices, dst->normals, dst->rgb);

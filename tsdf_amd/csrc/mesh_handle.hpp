@@ -22,18 +22,6 @@ struct MeshChunk {
     uint32_t ibase;        // the same for the soup vertices (= indices) of the cubes rooted in the chunk
 };
 
-// Arrays only grow; what they held is not kept.
-template <typename T>
-hipError_t mesh_reserve(T *&p, size_t &cap, size_t want) {
-    if (want <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
 constexpr size_t kComponentWords = 4;   // tsdf_mesh::component_words, and what tsdf_label_components_device holds for a call
 
 // ---- the chunk scan (mesh_scan.hip) ------------------------------------------------------------------------------------------------

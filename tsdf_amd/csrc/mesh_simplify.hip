@@ -214,12 +214,12 @@ int simplify_on(uint32_t nv, uint32_t n_triples, const float *vertices, const ui
     const size_t slots = (size_t)1 << bits;
     const uint32_t v_chunks = (nv + 63) / 64, t_chunks = (n_triples + 63) / 64;
     const uint32_t chunks = v_chunks > t_chunks ? v_chunks : t_chunks, n_parts = mesh_scan_parts(chunks);
-    hipError_t e = mesh_reserve(dst->cell_keys, dst->cell_keys_cap, slots);
-    if (e == hipSuccess) e = mesh_reserve(dst->cell_reps, dst->cell_reps_cap, slots);
-    if (e == hipSuccess) e = mesh_reserve(dst->cluster_of, dst->cluster_of_cap, (size_t)nv);
-    if (e == hipSuccess) e = mesh_reserve(dst->keep_masks, dst->keep_masks_cap, (size_t)v_chunks + t_chunks);
-    if (e == hipSuccess) e = mesh_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks + t_chunks);
-    if (e == hipSuccess) e = mesh_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1) + 1);   // the sums, the two totals, the error word
+    hipError_t e = device_reserve(dst->cell_keys, dst->cell_keys_cap, slots);
+    if (e == hipSuccess) e = device_reserve(dst->cell_reps, dst->cell_reps_cap, slots);
+    if (e == hipSuccess) e = device_reserve(dst->cluster_of, dst->cluster_of_cap, (size_t)nv);
+    if (e == hipSuccess) e = device_reserve(dst->keep_masks, dst->keep_masks_cap, (size_t)v_chunks + t_chunks);
+    if (e == hipSuccess) e = device_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks + t_chunks);
+    if (e == hipSuccess) e = device_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1) + 1);   // the sums, the two totals, the error word
     if (e != hipSuccess) return hip_fail(e, "mesh simplify scratch alloc failed");
     uint64_t *v_mask = dst->keep_masks, *t_mask = dst->keep_masks + v_chunks;
     uint32_t *v_base = dst->keep_bases, *t_base = dst->keep_bases + v_chunks;
@@ -253,11 +253,11 @@ int simplify_on(uint32_t nv, uint32_t n_triples, const float *vertices, const ui
         row.rgb = row.words;
         row.words += 3;
     }
-    e = mesh_reserve(dst->cluster_sums, dst->cluster_sums_cap, (size_t)n_clusters * row.words);
-    if (e == hipSuccess) e = mesh_reserve(dst->vertices, dst->vertices_cap, (size_t)n_clusters * 3);
-    if (e == hipSuccess) e = mesh_reserve(dst->indices, dst->indices_cap, (size_t)(kept_triples ? kept_triples * 3 : 1));
-    if (e == hipSuccess && normals) e = mesh_reserve(dst->normals, dst->normals_cap, (size_t)n_clusters * 3);
-    if (e == hipSuccess && rgb) e = mesh_reserve(dst->rgb, dst->rgb_cap, (size_t)n_clusters * 3);
+    e = device_reserve(dst->cluster_sums, dst->cluster_sums_cap, (size_t)n_clusters * row.words);
+    if (e == hipSuccess) e = device_reserve(dst->vertices, dst->vertices_cap, (size_t)n_clusters * 3);
+    if (e == hipSuccess) e = device_reserve(dst->indices, dst->indices_cap, (size_t)(kept_triples ? kept_triples * 3 : 1));
+    if (e == hipSuccess && normals) e = device_reserve(dst->normals, dst->normals_cap, (size_t)n_clusters * 3);
+    if (e == hipSuccess && rgb) e = device_reserve(dst->rgb, dst->rgb_cap, (size_t)n_clusters * 3);
     if (e != hipSuccess) return hip_fail(e, "mesh array alloc failed");
     TSDF_HIP(hipMemsetAsync(dst->cluster_sums, 0, (size_t)n_clusters * row.words * sizeof(int64_t), stream), "mesh simplify sums");
     hipLaunchKernelGGL(simplify_accumulate_kernel, grid_for(nv, 256), dim3(256), 0, stream, nv, vertices, normals, rgb, h, v_mask, v_base, dst->cluster_of, row,

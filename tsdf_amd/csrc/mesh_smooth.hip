@@ -229,21 +229,21 @@ int smooth_on(uint32_t nv, uint32_t n_triples, const float *vertices, const uint
     const size_t n_indices = (size_t)n_triples * 3;
     const uint32_t bits = mesh_table_bits(n_indices);   // three edges per triple
     const size_t slots = (size_t)1 << bits;
-    hipError_t e = mesh_reserve(dst->vertices, dst->vertices_cap, (size_t)nv * 3);
-    if (e == hipSuccess) e = mesh_reserve(dst->indices, dst->indices_cap, n_indices ? n_indices : 1);
-    if (e == hipSuccess && (normals || face_normals)) e = mesh_reserve(dst->normals, dst->normals_cap, (size_t)nv * 3);
-    if (e == hipSuccess && rgb) e = mesh_reserve(dst->rgb, dst->rgb_cap, (size_t)nv * 3);
+    hipError_t e = device_reserve(dst->vertices, dst->vertices_cap, (size_t)nv * 3);
+    if (e == hipSuccess) e = device_reserve(dst->indices, dst->indices_cap, n_indices ? n_indices : 1);
+    if (e == hipSuccess && (normals || face_normals)) e = device_reserve(dst->normals, dst->normals_cap, (size_t)nv * 3);
+    if (e == hipSuccess && rgb) e = device_reserve(dst->rgb, dst->rgb_cap, (size_t)nv * 3);
     if (e != hipSuccess) return hip_fail(e, "mesh array alloc failed");
-    e = mesh_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1) + 1);   // the sums, the two totals, the error word
-    if (e == hipSuccess && passes) e = mesh_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks);
-    if (e == hipSuccess && passes) e = mesh_reserve(dst->row_begin, dst->row_begin_cap, (size_t)nv);
-    if (e == hipSuccess && passes) e = mesh_reserve(dst->row_end, dst->row_end_cap, (size_t)nv);
-    if (e == hipSuccess && passes) e = mesh_reserve(dst->rows, dst->rows_cap, n_indices);
-    if (e == hipSuccess && passes > 1) e = mesh_reserve(dst->smooth_positions, dst->smooth_positions_cap, (size_t)nv * 3);
-    if (e == hipSuccess && pins) e = mesh_reserve(dst->pinned, dst->pinned_cap, (size_t)nv);
-    if (e == hipSuccess && pins) e = mesh_reserve(dst->cell_keys, dst->cell_keys_cap, slots);
-    if (e == hipSuccess && pins) e = mesh_reserve(dst->cell_reps, dst->cell_reps_cap, slots);
-    if (e == hipSuccess && face_normals) e = mesh_reserve(dst->normal_sums, dst->normal_sums_cap, (size_t)nv * 3);
+    e = device_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1) + 1);   // the sums, the two totals, the error word
+    if (e == hipSuccess && passes) e = device_reserve(dst->keep_bases, dst->keep_bases_cap, (size_t)v_chunks);
+    if (e == hipSuccess && passes) e = device_reserve(dst->row_begin, dst->row_begin_cap, (size_t)nv);
+    if (e == hipSuccess && passes) e = device_reserve(dst->row_end, dst->row_end_cap, (size_t)nv);
+    if (e == hipSuccess && passes) e = device_reserve(dst->rows, dst->rows_cap, n_indices);
+    if (e == hipSuccess && passes > 1) e = device_reserve(dst->smooth_positions, dst->smooth_positions_cap, (size_t)nv * 3);
+    if (e == hipSuccess && pins) e = device_reserve(dst->pinned, dst->pinned_cap, (size_t)nv);
+    if (e == hipSuccess && pins) e = device_reserve(dst->cell_keys, dst->cell_keys_cap, slots);
+    if (e == hipSuccess && pins) e = device_reserve(dst->cell_reps, dst->cell_reps_cap, slots);
+    if (e == hipSuccess && face_normals) e = device_reserve(dst->normal_sums, dst->normal_sums_cap, (size_t)nv * 3);
     if (e != hipSuccess) return hip_fail(e, "mesh smooth scratch alloc failed");
     uint64_t *error = dst->parts + 2 * ((size_t)n_parts + 1);
     TSDF_HIP(hipMemsetAsync(error, 0, sizeof(uint64_t), stream), "mesh smooth error word");
@@ -377,12 +377,12 @@ int tsdf_mesh_compute_normals(tsdf_mesh *m, void *hip_stream) {
         m->info.flags |= TSDF_MESH_NORMALS;
         return TSDF_OK;
     }
-    hipError_t e = mesh_reserve(m->normal_sums, m->normal_sums_cap, nv * 3);
-    if (e == hipSuccess) e = mesh_reserve(m->parts, m->parts_cap, (size_t)1);   // the error word
+    hipError_t e = device_reserve(m->normal_sums, m->normal_sums_cap, nv * 3);
+    if (e == hipSuccess) e = device_reserve(m->parts, m->parts_cap, (size_t)1);   // the error word
     if (e != hipSuccess) return hip_fail(e, "mesh normals scratch alloc failed");
     if (m->normals_cap < nv * 3) {   // (with the array gone the mesh has no normals, should anything below fail)
         m->info.flags &= ~(uint32_t)TSDF_MESH_NORMALS;
-        e = mesh_reserve(m->normals, m->normals_cap, nv * 3);
+        e = device_reserve(m->normals, m->normals_cap, nv * 3);
         if (e != hipSuccess) return hip_fail(e, "mesh array alloc failed");
     }
     TSDF_HIP(hipMemsetAsync(m->parts, 0, sizeof(uint64_t), stream), "mesh normals error word");

@@ -439,15 +439,13 @@ int tsdf_pipeline_destroy(tsdf_pipeline *p) {
         p->volume->attached = nullptr;
     }
     for (int b = 0; b < 2; b++) {
-        if (p->filtered[b]) (void)hipFree(p->filtered[b]);
-        if (p->tile_max[b]) (void)hipFree(p->tile_max[b]);
+        device_free_all(p->filtered[b], p->tile_max[b]);
         if (p->done[b]) (void)hipEventDestroy(p->done[b]);
         if (p->ready[b]) (void)hipEventDestroy(p->ready[b]);
     }
     if (p->cast) (void)hipEventDestroy(p->cast);
     if (p->merged) (void)hipEventDestroy(p->merged);
-    if (p->hits_mine) (void)hipFree(p->hits_mine);
-    if (p->hits_all) (void)hipFree(p->hits_all);
+    device_free_all(p->hits_mine, p->hits_all);
     if (p->side) (void)hipStreamDestroy(p->side);
     if (p->xstream) (void)hipStreamDestroy(p->xstream);
     if (p->main) (void)hipStreamDestroy(p->main);
@@ -663,17 +661,14 @@ int tsdf_tracker_destroy(tsdf_tracker *t) {
         if (t->icp) (void)tsdf_icp_set_stream(t->icp, t->icp_stream_before);   // (the ICP's own previous stream, not the volume's)
     }
     for (int b = 0; b < 2; b++) {
-        if (t->filtered[b]) (void)hipFree(t->filtered[b]);
-        if (t->tile_max[b]) (void)hipFree(t->tile_max[b]);
+        device_free_all(t->filtered[b], t->tile_max[b]);
         if (t->integrated[b]) (void)hipEventDestroy(t->integrated[b]);
     }
     if (t->ready) (void)hipEventDestroy(t->ready);
-    if (t->model) (void)hipFree(t->model);
-    if (t->ring) (void)hipFree(t->ring);
+    device_free_all(t->model, t->ring);
     delete[] t->ring_cam;
     if (t->aligner) tsdf_aligner_destroy(t->aligner);
-    for (int i = 0; i < 3; i++)
-        if (t->align_points[i]) (void)hipFree(t->align_points[i]);
+    device_free_all(t->align_points[0], t->align_points[1], t->align_points[2]);
     if (t->side) (void)hipStreamDestroy(t->side);
     if (t->main) (void)hipStreamDestroy(t->main);
     delete t;

@@ -775,9 +775,7 @@ static bool prepare_entry_bound(tsdf_volume *v, RayParams &rp, EntryParams &ep, 
     if (!view_projection(v, rp, ep)) return false;
     const size_t n_words = (size_t)ep.tiles_x * ep.tiles_y + 1;
     if (v->ztile_words != n_words) {   // (first use, or another image size: both copies start reset)
-        if (v->ztile) (void)hipFree(v->ztile);
-        v->ztile = nullptr;
-        v->ztile_words = 0;
+        device_release(v->ztile, v->ztile_words);
         if (hipMalloc((void **)&v->ztile, 2 * n_words * sizeof(uint32_t)) != hipSuccess) { rc = hip_fail(hipErrorOutOfMemory, "entry bound alloc"); return false; }
         std::vector<uint32_t> init(2 * n_words, kEntryFar);
         init[n_words - 1] = init[2 * n_words - 1] = 1u;
@@ -950,41 +948,20 @@ static int march_and_resolve(tsdf_volume *v, RayParams &rp, float *out, float *n
     const int max_pieces = std::min(kTailPieces, (max_len + tail_piece_min() - 1) / tail_piece_min());
     const size_t n_entries = n_pix * n_segments * (size_t)std::max(max_pieces, 1);
     if (v->ray_best_cap < n_pix) {
-        if (v->ray_best) (void)hipFree(v->ray_best);
-        v->ray_best = nullptr;
-        v->ray_best_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->ray_best, 2 * n_pix * sizeof(uint64_t)), "ray result alloc");   // (double buffered)
-        v->ray_best_cap = n_pix;
+        TSDF_HIP(device_reserve_units(v->ray_best, v->ray_best_cap, n_pix, 2 * sizeof(uint64_t)), "ray result alloc");   // (double buffered)
         v->ray_best_dirty = 1;
     }
     if (cells) {
         const size_t n_bricks_max = cell_list_capacity(v->occ.fine_count());
-        if (v->cell_rays_cap < n_pix) {
-            if (v->cell_rays) (void)hipFree(v->cell_rays);
-            v->cell_rays = nullptr;
-            v->cell_rays_cap = 0;
-            TSDF_HIP(hipMalloc(&v->cell_rays, n_pix * sizeof(RayRecord)), "ray record alloc");
-            v->cell_rays_cap = n_pix;
-        }
-        if (v->cell_bricks_cap < n_bricks_max) {
-            if (v->cell_bricks) (void)hipFree(v->cell_bricks);
-            v->cell_bricks = nullptr;
-            v->cell_bricks_cap = 0;
-            TSDF_HIP(hipMalloc((void **)&v->cell_bricks, 2 * n_bricks_max * sizeof(uint2)), "brick list alloc");   // (the list, and the list as built when it is sorted)
-            v->cell_bricks_cap = n_bricks_max;
-        }
+        TSDF_HIP(device_reserve_units(v->cell_rays, v->cell_rays_cap, n_pix, sizeof(RayRecord)), "ray record alloc");
+        // (the list, and the list as built when it is sorted)
+        TSDF_HIP(device_reserve_units(v->cell_bricks, v->cell_bricks_cap, n_bricks_max, 2 * sizeof(uint2)), "brick list alloc");
         if (!v->cell_cast_host) {
             TSDF_HIP(hipHostMalloc((void **)&v->cell_cast_host, sizeof(uint32_t), hipHostMallocDefault), "brick count mirror alloc");
             *v->cell_cast_host = 0;
         }
     }
-    if (v->tail_cap < n_entries) {
-        if (v->tail_entries) (void)hipFree(v->tail_entries);
-        v->tail_entries = nullptr;
-        v->tail_cap = 0;
-        TSDF_HIP(hipMalloc(&v->tail_entries, n_entries * sizeof(uint2)), "ray tail queue alloc");
-        v->tail_cap = n_entries;
-    }
+    TSDF_HIP(device_reserve_units(v->tail_entries, v->tail_cap, n_entries, sizeof(uint2)), "ray tail queue alloc");
     if (!v->tail_count) {
         TSDF_HIP(hipMalloc((void **)&v->tail_count, kTailSignals * sizeof(uint32_t)), "ray tail counter alloc");
         v->ray_best_dirty = 1;
@@ -1006,10 +983,7 @@ static int march_and_resolve(tsdf_volume *v, RayParams &rp, float *out, float *n
     OrderJob order_job = {nullptr, nullptr, 0, 0, 0};
     if (learn_order && n_tiles <= 65535u && (uint32_t)n_segments <= kOrderMaxRanges) {
         if (!v->ray_heavy || v->ray_order_tiles != n_tiles || v->ray_order_ranges != (uint32_t)n_segments) {
-            if (v->ray_heavy) (void)hipFree(v->ray_heavy);
-            if (v->ray_order) (void)hipFree(v->ray_order);
-            v->ray_heavy = nullptr;
-            v->ray_order = nullptr;
+            device_free_all(v->ray_heavy, v->ray_order);
             v->ray_order_valid = 0;
             TSDF_HIP(hipMalloc((void **)&v->ray_heavy, (size_t)2 * n_tiles * n_segments), "ray order alloc");
             TSDF_HIP(hipMalloc((void **)&v->ray_order, (size_t)n_tiles * n_segments * sizeof(uint32_t)), "ray order alloc");
@@ -1184,13 +1158,11 @@ int tsdf_raycast(const tsdf_volume *cv, uint32_t width, uint32_t height, const f
     TSDF_REQUIRE(host_vertices, "tsdf_raycast: null vertex buffer");
     tsdf_volume *v = const_cast<tsdf_volume *>(cv);  // per-call temporaries are cached in the handle
     size_t bytes = (size_t)width * height * 3 * sizeof(float);
-    if (v->ray_cap < bytes) {
-        if (v->vert_buf) (void)hipFree(v->vert_buf);
-        if (v->norm_buf) (void)hipFree(v->norm_buf);
-        v->vert_buf = v->norm_buf = nullptr;
+    if (v->ray_cap < bytes) {   // two arrays under one capacity word: it is 0 unless both are there, so a failure replaces both next time
+        size_t vert_cap = 0, norm_cap = 0;   // (capacities of 0: each call below replaces its array)
         v->ray_cap = 0;
-        TSDF_HIP(hipMalloc((void **)&v->vert_buf, bytes), "Vertices alloc failed");
-        TSDF_HIP(hipMalloc((void **)&v->norm_buf, bytes), "Normals alloc failed");
+        TSDF_HIP(device_reserve_bytes(v->vert_buf, vert_cap, bytes), "Vertices alloc failed");
+        TSDF_HIP(device_reserve_bytes(v->norm_buf, norm_cap, bytes), "Normals alloc failed");
         v->ray_cap = bytes;
     }
     rc = tsdf_raycast_device(v, width, height, pose, kinv, v->vert_buf, host_normals ? v->norm_buf : nullptr);
@@ -1376,31 +1348,25 @@ static int cast_rays_host(tsdf_volume *v, uint64_t n, const float *host_origins,
     const size_t fn = (size_t)n;
     const size_t o_m = 6 * fn, o_p = o_m + (host_t_max ? fn : 0), o_t = o_p + (host_points ? 3 * fn : 0), o_n = o_t + (host_t ? fn : 0),
                  total = o_n + (host_normals ? 3 * fn : 0), bytes = total * sizeof(float) + (host_rgb ? 3 * fn : 0);
-    float *buf = nullptr;
-    if (hipMalloc((void **)&buf, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("tsdf_volume_cast_rays: couldn't allocate %zu bytes for the rays and results", bytes);
-        return TSDF_ERR_NOMEM;
-    }
+    HostStage st;
+    int rc = st.begin(v->stream, bytes, "tsdf_volume_cast_rays: couldn't allocate %zu bytes for the rays and results");
+    if (rc != TSDF_OK) return rc;
+    float *const buf = static_cast<float *>(st.buf);
     float *m = host_t_max ? buf + o_m : nullptr, *p = host_points ? buf + o_p : nullptr, *t = host_t ? buf + o_t : nullptr,
           *nrm = host_normals ? buf + o_n : nullptr;
     uint8_t *const rgb = host_rgb ? reinterpret_cast<uint8_t *>(buf + total) : nullptr;
-    hipError_t e = hipMemcpyAsync(buf, host_origins, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(buf + 3 * fn, host_directions, 3 * fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
-    if (e == hipSuccess && m) e = hipMemcpyAsync(m, host_t_max, fn * sizeof(float), hipMemcpyHostToDevice, v->stream);
-    int rc = TSDF_OK;
-    if (e == hipSuccess) rc = cast_rays(v, n, buf, buf + 3 * fn, m, p, t, nrm);
-    if (rc == TSDF_OK && e == hipSuccess && rgb) rc = cast_rays_colour(v, n, p, rgb);
-    if (rc == TSDF_OK && e == hipSuccess && p) e = hipMemcpyAsync(host_points, p, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (rc == TSDF_OK && e == hipSuccess && t) e = hipMemcpyAsync(host_t, t, fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (rc == TSDF_OK && e == hipSuccess && nrm) e = hipMemcpyAsync(host_normals, nrm, 3 * fn * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (rc == TSDF_OK && e == hipSuccess && rgb) e = hipMemcpyAsync(host_rgb, rgb, 3 * fn, hipMemcpyDeviceToHost, v->stream);
-    const hipError_t es = hipStreamSynchronize(v->stream);   // (before the buffer goes, whatever happened)
-    (void)hipFree(buf);
-    if (rc != TSDF_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "Ray query failed");
-    if (es != hipSuccess) return hip_fail(es, "Ray query failed");
-    return TSDF_OK;
+    st.up(buf, host_origins, 3 * fn * sizeof(float));
+    st.up(buf + 3 * fn, host_directions, 3 * fn * sizeof(float));
+    if (m) st.up(m, host_t_max, fn * sizeof(float));
+    if (st.ok()) rc = cast_rays(v, n, buf, buf + 3 * fn, m, p, t, nrm);
+    if (rc == TSDF_OK && st.ok() && rgb) rc = cast_rays_colour(v, n, p, rgb);
+    if (rc == TSDF_OK) {
+        if (p) st.down(host_points, p, 3 * fn * sizeof(float));
+        if (t) st.down(host_t, t, fn * sizeof(float));
+        if (nrm) st.down(host_normals, nrm, 3 * fn * sizeof(float));
+        if (rgb) st.down(host_rgb, rgb, 3 * fn);
+    }
+    return st.finish(rc, "Ray query failed");
 }
 
 int tsdf_volume_cast_rays(const tsdf_volume *cv, uint64_t n, const float *host_origins, const float *host_directions,

@@ -186,8 +186,8 @@ int apply_scene_flow(tsdf_volume *v, tsdf_mesh *m, const uint16_t *depth, const 
     if (rcn != TSDF_OK) return rcn;
     v->prepared_valid = 0;
 
-    hipError_t e = mesh_reserve(m->flow_vertex, m->flow_vertex_cap, (size_t)n_vertices);
-    if (e == hipSuccess && (flags & TSDF_SCENE_FLOW_DEFORMED)) e = mesh_reserve(m->flow_points, m->flow_points_cap, (size_t)n_vertices * 3);
+    hipError_t e = device_reserve(m->flow_vertex, m->flow_vertex_cap, (size_t)n_vertices);
+    if (e == hipSuccess && (flags & TSDF_SCENE_FLOW_DEFORMED)) e = device_reserve(m->flow_points, m->flow_points_cap, (size_t)n_vertices * 3);
     if (e == hipSuccess && !m->flow_counts) e = hipMalloc((void **)&m->flow_counts, 2 * sizeof(uint64_t));
     if (e == hipSuccess && !m->flow_totals) e = hipHostMalloc((void **)&m->flow_totals, 2 * sizeof(uint64_t), hipHostMallocDefault);
     if (e != hipSuccess) return hip_fail(e, "scene flow scratch alloc failed");
@@ -252,8 +252,8 @@ int tsdf_volume_apply_scene_flow(tsdf_volume *v, tsdf_mesh *m, const uint16_t *h
         return TSDF_OK;
     }
     const size_t pixels = (size_t)width * height;
-    hipError_t e = mesh_reserve(m->flow_depth, m->flow_depth_cap, pixels);
-    if (e == hipSuccess) e = mesh_reserve(m->flow_image, m->flow_image_cap, pixels * 3);
+    hipError_t e = device_reserve(m->flow_depth, m->flow_depth_cap, pixels);
+    if (e == hipSuccess) e = device_reserve(m->flow_image, m->flow_image_cap, pixels * 3);
     if (e != hipSuccess) return hip_fail(e, "scene flow image alloc failed");
     TSDF_HIP(hipMemcpyAsync(m->flow_depth, host_depth, pixels * sizeof(uint16_t), hipMemcpyHostToDevice, v->stream), "scene flow depth upload");
     TSDF_HIP(hipMemcpyAsync(m->flow_image, host_flow, pixels * 3 * sizeof(float), hipMemcpyHostToDevice, v->stream), "scene flow upload");

@@ -908,45 +908,19 @@ int tsdf_volume_destroy(tsdf_volume *v) {
     if (!v) return TSDF_OK;
     if (v->occ_tighten_pending) (void)hipEventSynchronize(v->occ_tightened);
     if (v->occ_tightened) (void)hipEventDestroy(v->occ_tightened);
-    if (v->dist) (void)hipFree(v->dist);
+    device_free_all(v->dist);
     weights_destroy(v);
-    if (v->nodes) (void)hipFree(v->nodes);
-    if (v->depth_buf) (void)hipFree(v->depth_buf);
-    if (v->vert_buf) (void)hipFree(v->vert_buf);
-    if (v->norm_buf) (void)hipFree(v->norm_buf);
-    if (v->counter_dev) (void)hipFree(v->counter_dev);
-    if (v->occ.fine) (void)hipFree(v->occ.fine);
-    if (v->occ.cell) (void)hipFree(v->occ.cell);
-    if (v->occ.reach) (void)hipFree(v->occ.reach);
-    if (v->occ_bits) (void)hipFree(v->occ_bits);
-    if (v->occ_rim_bits) (void)hipFree(v->occ_rim_bits);
-    if (v->touched) (void)hipFree(v->touched);
-    if (v->plane_const) (void)hipFree(v->plane_const);
-    if (v->depth_pad) (void)hipFree(v->depth_pad);
-    if (v->tail_entries) (void)hipFree(v->tail_entries);
-    if (v->tail_count) (void)hipFree(v->tail_count);
-    if (v->cell_rays) (void)hipFree(v->cell_rays);
-    if (v->cell_bricks) (void)hipFree(v->cell_bricks);
-    if (v->cell_count_scratch) (void)hipFree(v->cell_count_scratch);
-    if (v->cell_cast_host) (void)hipHostFree(v->cell_cast_host);
-    if (v->ray_heavy) (void)hipFree(v->ray_heavy);
-    if (v->ray_order) (void)hipFree(v->ray_order);
-    if (v->ztile) (void)hipFree(v->ztile);
-    if (v->t_table) (void)hipFree(v->t_table);
-    if (v->ray_best) (void)hipFree(v->ray_best);
+    device_free_all(v->nodes, v->depth_buf, v->vert_buf, v->norm_buf, v->counter_dev, v->occ.fine, v->occ.cell, v->occ.reach, v->occ_bits,
+                    v->occ_rim_bits, v->touched, v->plane_const, v->depth_pad, v->tail_entries, v->tail_count, v->cell_rays, v->cell_bricks,
+                    v->cell_count_scratch);
+    (void)hipHostFree(v->cell_cast_host);
+    device_free_all(v->ray_heavy, v->ray_order, v->ztile, v->t_table, v->ray_best);
     for (int w = 0; w < 3; w++)
         if (v->tev[w]) {
             for (hipEvent_t e : *v->tev[w]) (void)hipEventDestroy(e);
             delete v->tev[w];
         }
-    if (v->brick_list) (void)hipFree(v->brick_list);
-    if (v->brick_boxes) (void)hipFree(v->brick_boxes);
-    if (v->tile_max) (void)hipFree(v->tile_max);
-    if (v->colour) (void)hipFree(v->colour);
-    if (v->rgb_buf) (void)hipFree(v->rgb_buf);
-    if (v->fuse_scratch) (void)hipFree(v->fuse_scratch);
-    if (v->rays_scratch) (void)hipFree(v->rays_scratch);
-    if (v->rays_colour_scratch) (void)hipFree(v->rays_colour_scratch);
+    device_free_all(v->brick_list, v->brick_boxes, v->tile_max, v->colour, v->rgb_buf, v->fuse_scratch, v->rays_scratch, v->rays_colour_scratch);
     delete v;
     return TSDF_OK;
 }
