@@ -58,7 +58,7 @@ $(LIBDIR)/libtsdf_hip.so: $(HIP_OBJS)
 oracle:
 	$(MAKE) -C oracle -s all
 
-CPPTESTS  = surface colour weight_cap field rays fuse align integrate_rays rays_colour mesh esdf components simplify smooth scene_flow
+CPPTESTS  = surface colour weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf components simplify smooth scene_flow
 cpptest: $(CPPTESTS:%=build/test_%) build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp

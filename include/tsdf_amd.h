@@ -596,7 +596,7 @@ int tsdf_volume_ray_scratch_bytes(const tsdf_volume *volume, uint64_t *bytes);
  *     orders behind the integrates it wants seen.
  *   Refused (TSDF_ERR_INVALID, with a message, nothing written): null arguments; a Z-slab volume; a non-finite entry in T's top three
  *     rows; gate not > 0; more than 8 stages; step == 0; volume and aligner on different devices.
- *   Out of scope: robust weights, colour terms, slab volumes, the deformed space. */
+ *   Out of scope: robust weights, slab volumes, the deformed space.  (A colour term: "colour alignment", below.) */
 typedef struct tsdf_aligner tsdf_aligner;   /* opaque: partial sums, the double-buffered state, a pinned in/out block and a stream */
 int tsdf_aligner_create(tsdf_aligner **out);   /* on the current device */
 void tsdf_aligner_destroy(tsdf_aligner *aligner);
@@ -625,6 +625,76 @@ int tsdf_aligner_run(tsdf_aligner *aligner, const tsdf_volume *volume, uint32_t 
  * on hip_stream. */
 int tsdf_depth_to_points_device(uint32_t width, uint32_t height, const uint16_t *device_depth, const float kinv[9], uint32_t step,
                                 float depth_cutoff, float *device_points, void *hip_stream);
+
+/* ---- colour alignment (no reference counterpart) ------------------------------------------------------------------------------------ */
+/* Field alignment with a photometric row per point beside the geometric one, sampled from the fused colour field ("colour fusion")
+ * exactly where the distance is sampled.  Where the geometry does not constrain the pose -- a flat wall, a floor, a corridor: the
+ * distance gradient has no in-plane component, the normal matrix is singular there and the solve zeroes those directions -- the
+ * texture can.  Opt-in by being called: tsdf_aligner_step, tsdf_aligner_run, tsdf_tracker_align_field and their kernels are as they
+ * were.  Every fp32 operation below is rounded on its own.
+ *   Intensity of a colour: Y(r, g, b) = (float)(77 r + 150 g + 29 b) * 0x1p-8f -- exact in fp32 (an integer <= 65280 times a power of
+ *     two).  A voxel's intensity is Y of its colour word {r, g, b, n}; it is defined only when n > 0.
+ *   Intensity of the field at q (the frame of "field queries"): with the trilinear cell of the distance sample S(q) -- the same lower
+ *     voxel l, the same u, v, w and the same clamped tap offsets that the ray cast's trilinear sample forms -- and I_ijk the intensity
+ *     of the voxel at l + (i, j, k) (a tap past the far face is clamped onto its lower neighbour),
+ *         I(q) = I000 (1-u)(1-v)(1-w) + I001 (1-u)(1-v) w + I010 (1-u) v (1-w) + I011 (1-u) v w
+ *              + I100 u (1-v)(1-w) + I101 u (1-v) w + I110 u v (1-w) + I111 u v w,
+ *     the distance sample's eight-term expression term for term: each term multiplied left to right, the terms added left to right.
+ *     The gradient is the exact derivative of that interpolant inside the cell, not a central difference:
+ *         gx = ((I100-I000)(1-v)(1-w) + (I101-I001)(1-v) w + (I110-I010) v (1-w) + (I111-I011) v w) / voxel_size.x
+ *         gy = ((I010-I000)(1-u)(1-w) + (I011-I001)(1-u) w + (I110-I100) u (1-w) + (I111-I101) u w) / voxel_size.y
+ *         gz = ((I001-I000)(1-u)(1-v) + (I011-I010)(1-u) v + (I101-I100) u (1-v) + (I111-I110) u v) / voxel_size.z
+ *     each term multiplied left to right, the four added left to right, the division the sampler's own for that axis (it equals the
+ *     IEEE quotient).  The tap differences are exact in fp32.  A tap clamped onto its lower neighbour gives a zero difference: that is
+ *     the definition, not an error.  Valid iff valid(q) ("field queries"), the volume has colour enabled and all eight taps have
+ *     n > 0; otherwise the intensity is NaN and the gradient the NaN triple (so too where valid(q) divides to size[i] itself and
+ *     the distance is NaN).  Eight colour dwords a point.
+ *   Photometric row of a point x with observed intensity y: u and q are those of the geometric row ("field alignment");
+ *         c = I(q), e = c - y, gc = the gradient above,
+ *         row_c = (gcx, gcy, gcz, u1 * gcz - u2 * gcy, u2 * gcx - u0 * gcz, u0 * gcy - u1 * gcx, -e).
+ *     The point is a colour inlier iff it is a geometric inlier (the colour term acts at the surface only, within `gate`), I(q) is
+ *     valid, y is finite (a NaN y marks a point without colour) and fabsf(e) < colour_gate.  A zero colour gradient is allowed: it
+ *     adds e^2 and the count only.
+ *   Sums: a second block of 29 -- the 28 products of row_c in the geometric block's order (the sum of e^2 at entry 27) and the colour
+ *     inlier count at entry 28 -- accumulated beside the geometric block in exactly its order (per-thread strided fp32, the wave64
+ *     shuffle tree, ((w0 + w1) + w2) + w3, 8 groups of 32 workgroups in double, narrowed to fp32).  The system handed to the solve is,
+ *     per entry of A and b, (float)((double)S_g + (double)colour_weight * (double)S_c); colour_weight == 0 therefore reproduces
+ *     tsdf_aligner_run's pose bit for bit.  The solve, the SE3 exponential and the update are those of "field alignment".
+ *     Residuals and inlier counts are reported per term and never combined.  colour_weight is in (volume units)^2 per intensity^2
+ *     (mm^2 per intensity^2 with the usual millimetres) and scene-dependent: it trades a distance residual against a brightness one.
+ *   Nothing of the volume is written; distances, weights and colour words are read on the aligner's stream.
+ *   Refused (TSDF_ERR_INVALID, with a message, nothing written): everything tsdf_aligner_* refuses; a volume without colour enabled;
+ *     NULL intensities; colour_gate not > 0; colour_weight negative or not finite; both outputs of a sample NULL.
+ *   Out of scope: robust weights, colour in ICP's projective path, slab volumes, the deformed space, trilinear colour for rendering. */
+/* I(q) (n floats) and its gradient (3 n floats) at n world points (q = p - offset as in "field queries"); either output may be NULL,
+ * not both.  n == 0 is TSDF_OK and launches nothing.  Asynchronous on hip_stream (NULL = the default stream). */
+int tsdf_volume_sample_intensity_device(const tsdf_volume *volume, uint64_t n, const float *device_points, float *device_intensity,
+                                        float *device_gradient, void *hip_stream);
+/* The same on host arrays, on the volume's stream; blocking. */
+int tsdf_volume_sample_intensity(const tsdf_volume *volume, uint64_t n, const float *host_points, float *host_intensity,
+                                 float *host_gradient);
+/* Pixel (x * step, y * step) of an RGB frame (3 bytes a pixel) -> Y: ceil(width / step) x ceil(height / step) floats, row-major -- the
+ * order and count of tsdf_depth_to_points_device's points, so the two arrays pair up.  Asynchronous on hip_stream. */
+int tsdf_rgb_to_intensity_device(uint32_t width, uint32_t height, const uint8_t *device_rgb, uint32_t step, float *device_intensity,
+                                 void *hip_stream);
+/* tsdf_aligner_step with the colour term: A and b are the combined system, residual_inliers = {sum of d^2, inliers, sum of e^2, colour
+ * inliers}.  device_intensity: n floats, the observed intensity of every point (NaN: none).  device_rows (may be NULL): 14 n floats,
+ * the geometric then the photometric row of every point; an outlier of a term gets the NaN row for that term.  Blocking. */
+int tsdf_aligner_step_colour(tsdf_aligner *aligner, const tsdf_volume *volume, uint32_t n, const float *device_points,
+                             const float *device_intensity, const double T[16], float gate, float colour_gate, float colour_weight,
+                             float A[36], float b[6], float residual_inliers[4], float *device_rows);
+typedef struct tsdf_align_colour_stage {
+    const float *device_points;      /* n points of 3 floats */
+    const float *device_intensity;   /* n floats */
+    uint32_t n;
+    uint32_t iterations;
+} tsdf_align_colour_stage;
+/* tsdf_aligner_run with the colour term: the chaining, the skipping of empty stages, the rule that a chain that never moved the pose
+ * returns T as given bit for bit, and the pinned in/out block are its.  residual / inliers (either may be NULL): {geometric, colour}
+ * of the last step. */
+int tsdf_aligner_run_colour(tsdf_aligner *aligner, const tsdf_volume *volume, uint32_t n_stages, const tsdf_align_colour_stage *stages,
+                            float gate, float colour_gate, float colour_weight, double T[16] /* in: start, out */, float residual[2],
+                            float inliers[2]);
 
 /* ---- raycast ---------------------------------------------------------------------------- */
 /* Replaces GPURaycaster::raycast = get_vertices/process_ray + compute_normals
@@ -1196,6 +1266,13 @@ int tsdf_tracker_align(tsdf_tracker *tracker, const tsdf_camera_matrices *previo
  * change). */
 int tsdf_tracker_align_field(tsdf_tracker *tracker, const float kinv[9], double T_world_cam[16] /* in: prediction, out */,
                              float *residual, float *inliers);
+/* tsdf_tracker_align_field with the colour term ("colour alignment"): the same points at steps 4, 2 and 1 with 4 / 5 / 10 iterations,
+ * the intensities of device_rgb (3 * width * height bytes, registered to the depth image) at the same steps through
+ * tsdf_rgb_to_intensity_device, then tsdf_aligner_run_colour.  residual / inliers (either may be NULL): {geometric, colour}.  The three
+ * intensity buffers are created on the first call.  Refused as tsdf_aligner_run_colour refuses, and with a NULL rgb frame. */
+int tsdf_tracker_align_field_colour(tsdf_tracker *tracker, const float kinv[9], const uint8_t *device_rgb, float colour_gate,
+                                    float colour_weight, double T_world_cam[16] /* in: prediction, out */, float residual[2],
+                                    float inliers[2]);
 int tsdf_tracker_integrate(tsdf_tracker *tracker, const tsdf_camera_matrices *camera);
 /* tsdf_tracker_integrate plus the colour of device_rgb (as tsdf_pipeline_step_colour: the filtered frame, rgb valid until the
  * integrate has run on the tracker's stream; refused without colour enabled or with a NULL rgb frame). */

@@ -8,7 +8,10 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W]
+//   --colour-weight W (with --track --field): W > 0 aligns every tracked frame with the colour term as well (tsdf_tracker_align_field_colour:
+//           the frame's rgb picture as intensities, colour gate 64, weight W in mm^2 per intensity^2); implies --colour; refused
+//           without --field, and when W is negative or not finite; the line gains "colour_weight": W and the colour term's inliers.
 //   --field (with --track): every tracked frame is aligned to the volume's distance field (tsdf_tracker_align_field: the filtered frame's
 //           pixels as points, no model ray cast, no ICP) from the previous pose; refused without --track and with --ranks; the line
 //           gains "align": "field" and reports the last step's inliers and sum of squared distances in the ICP fields.
@@ -125,6 +128,8 @@ int main(int argc, char **argv) {
     unsigned planes = 0;
     long weight_cap = 0;
     long window = 0;
+    double colour_weight = 0.0;
+    bool colour_weight_given = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&]() -> const char * {
@@ -151,8 +156,12 @@ int main(int argc, char **argv) {
         else if (a == "--colour") colour = true;
         else if (a == "--weight-cap") weight_cap = std::atol(value());
         else if (a == "--window") window = std::atol(value());
+        else if (a == "--colour-weight") {
+            colour_weight = std::atof(value());
+            colour_weight_given = true;
+        }
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W]\n");
             return 2;
         }
     }
@@ -172,6 +181,13 @@ int main(int argc, char **argv) {
     if (field && (!track || ranks > 1)) {
         std::fprintf(stderr, "kinfu_stream: --field needs --track and does not go with --ranks\n");
         return 2;
+    }
+    if (colour_weight_given) {
+        if (!field || !(colour_weight >= 0.0) || !(colour_weight < (double)INFINITY)) {
+            std::fprintf(stderr, "kinfu_stream: --colour-weight needs --track --field and a finite weight >= 0\n");
+            return 2;
+        }
+        colour = true;   // the colour term reads the fused colours
     }
     if (colour && ranks > 1) {
         std::fprintf(stderr, "kinfu_stream: --colour is single-volume (colour is not supported on Z-slabs): drop --ranks\n");
@@ -320,7 +336,7 @@ int main(int argc, char **argv) {
         if (window) ok(tsdf_tracker_set_window(trk, (uint32_t)window), "window");
         const size_t n_track = std::min(F, (size_t)K);
         std::vector<float> tracked;
-        float error = 0.f, inliers = 0.f;
+        float error = 0.f, inliers = 0.f, colour_inliers = 0.f;
         camera->set_pose(truth[0]);
         std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         const size_t first_timed = n_track > 4 ? 4 : 1;     // (the first frames also allocate scratch and build the ray caster's flags)
@@ -335,7 +351,16 @@ int main(int argc, char **argv) {
                 const tsdf_camera_matrices prev = matrices_of(*camera);
                 double T[16];
                 for (int j = 0; j < 16; j++) T[j] = prev.pose[j];
-                ok(tsdf_tracker_align_field(trk, prev.kinv, T, &error, &inliers), "align to the field");
+                if (colour_weight > 0.0) {
+                    float residual2[2], inliers2[2];
+                    ok(tsdf_tracker_align_field_colour(trk, prev.kinv, rgb_dev + i * n_pix * 3, 64.0f, (float)colour_weight, T, residual2, inliers2),
+                       "align to the field with colour");
+                    error = residual2[0];
+                    inliers = inliers2[0];
+                    colour_inliers = inliers2[1];
+                } else {
+                    ok(tsdf_tracker_align_field(trk, prev.kinv, T, &error, &inliers), "align to the field");
+                }
                 Eigen::Matrix4f next;
                 for (int j = 0; j < 16; j++) next.data()[j] = (float)T[j];
                 camera->set_pose(next);
@@ -371,6 +396,7 @@ int main(int argc, char **argv) {
         if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
         if (window) std::printf(", \"window\": %ld", window);
         if (field) std::printf(", \"align\": \"field\"");
+        if (colour_weight_given) std::printf(", \"colour_weight\": %g, \"last_colour_inliers\": %.0f", colour_weight, colour_inliers);
         std::printf(colour ? ", \"colour\": true}\n" : "}\n");
         if (!dump_dir.empty()) {
             dump(dump_dir + "/poses.f32", tracked.data(), tracked.size() * sizeof(float));

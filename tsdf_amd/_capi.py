@@ -62,6 +62,11 @@ class AlignStage(C.Structure):
     _fields_ = [("device_points", C.c_void_p), ("n", C.c_uint32), ("iterations", C.c_uint32)]
 
 
+class AlignColourStage(C.Structure):
+    """struct tsdf_align_colour_stage (include/tsdf_amd.h)."""
+    _fields_ = [("device_points", C.c_void_p), ("device_intensity", C.c_void_p), ("n", C.c_uint32), ("iterations", C.c_uint32)]
+
+
 class CameraMatrices(C.Structure):
     """struct tsdf_camera_matrices (include/tsdf_amd.h)."""
     _fields_ = [("pose", C.c_float * 16), ("inv_pose", C.c_float * 16), ("k", C.c_float * 9), ("kinv", C.c_float * 9)]
@@ -173,6 +178,11 @@ _SIGS = {
     "tsdf_aligner_step": (_i, [_vp, _vp, _u32, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "tsdf_aligner_run": (_i, [_vp, _vp, _u32, _vp, _f, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tsdf_depth_to_points_device": (_i, [_u32, _u32, _vp, _vp, _u32, _f, _vp, _vp]),
+    "tsdf_volume_sample_intensity_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "tsdf_volume_sample_intensity": (_i, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    "tsdf_rgb_to_intensity_device": (_i, [_u32, _u32, _vp, _u32, _vp, _vp]),
+    "tsdf_aligner_step_colour": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "tsdf_aligner_run_colour": (_i, [_vp, _vp, _u32, _vp, _f, _f, _f, _vp, _vp, _vp]),
     "tsdf_raycast": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_raycast_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_normals_device": (_i, [_u32, _u32, _vp, _vp, _vp]),
@@ -238,6 +248,7 @@ _SIGS = {
     "tsdf_tracker_filter": (_i, [_vp, _vp]),
     "tsdf_tracker_align": (_i, [_vp, C.POINTER(CameraMatrices), _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "tsdf_tracker_align_field": (_i, [_vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "tsdf_tracker_align_field_colour": (_i, [_vp, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "tsdf_tracker_integrate": (_i, [_vp, C.POINTER(CameraMatrices)]),
     "tsdf_tracker_integrate_colour": (_i, [_vp, C.POINTER(CameraMatrices), _vp]),
     "tsdf_tracker_set_window": (_i, [_vp, _u32]),

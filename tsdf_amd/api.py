@@ -519,12 +519,36 @@ class TSDFVolume:
         return np.isnan(t)
 
     # ---- field alignment (include/tsdf_amd.h, "field alignment"; not in the reference's class)
-    def align_points(self, points, T0=None, iterations=10, gate=None):
+    def align_points(self, points, T0=None, iterations=10, gate=None, intensity=None, colour_gate=None, colour_weight=None):
         """The rigid pose that puts (n, 3) float32 points on this volume's surface: `iterations` Gauss-Newton steps on the squared
         field distance from T0 (4 x 4, points' frame -> the frame of mesh and ray-cast vertices; default identity), points further
         than `gate` (default: the truncation distance) from the surface left out.  -> (T 4 x 4 float64, residual, inliers) of the
-        last step; inliers == 0 means the chain ended blind.  Raises ValueError on the refusals."""
-        return FieldAligner().run(self, [(points, int(iterations))], T0, gate)
+        last step; inliers == 0 means the chain ended blind.  Raises ValueError on the refusals.  `intensity` ((n,) float32, NaN: none):
+        with the colour term (FieldAligner.run); residual and inliers are then pairs (geometric, colour)."""
+        if intensity is None:
+            return FieldAligner().run(self, [(points, int(iterations))], T0, gate)
+        return FieldAligner().run(self, [(points, int(iterations))], T0, gate, intensity=[intensity], colour_gate=colour_gate,
+                                  colour_weight=colour_weight)
+
+    # ---- colour alignment (include/tsdf_amd.h, "colour alignment"; not in the reference's class)
+    def sample_intensity_device(self, n, points_ptr, intensity_ptr=None, gradient_ptr=None, stream=None):
+        """n points (3 float32 each, device) -> intensity (n float32), gradient (3 n): device pointers, either may be None; on `stream`
+        (default: the volume's).  Points are in the frame of sample_field."""
+        s = self.stream_ptr() if stream is None else stream
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_volume_sample_intensity_device(self._h, int(n), ptr(points_ptr), ptr(intensity_ptr), ptr(gradient_ptr),
+                                                      C.c_void_p(int(s) if s else 0)))
+
+    def sample_intensity(self, points, gradient=True):
+        """(n, 3) float32 world points (mm) -> (intensity (n,), gradient (n, 3) or None), float32: the trilinear intensity
+        Y = (77 r + 150 g + 29 b) / 256 of the fused colours in the cell sample_field's distance comes from and the exact derivative of
+        that interpolant; NaN outside the grid and where one of the eight voxels was never observed in colour."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        c = np.empty(n + 1, np.float32)     # (one more than asked for: see sample_field)
+        g = np.empty((n + 1, 3), np.float32) if gradient else None
+        check(lib.tsdf_volume_sample_intensity(self._h, n, p.ctypes.data if n else None, c.ctypes.data, g.ctypes.data if gradient else None))
+        return c[:n], g[:n] if gradient else None
 
     def register(self, src, T0=None, iterations=10, gate=None):
         """Volume-to-volume registration: align the mesh vertices of `src` (another TSDFVolume) to this volume's field from T0.
@@ -1207,6 +1231,14 @@ def _pose16(T):
     return np.ascontiguousarray(T.T.reshape(-1))
 
 
+#: Defaults of the colour term ("colour alignment").  The sweep of the CPU reference on two synthetic scenes hardly tells the weights
+#: apart, and the one noisy-depth sequence tracked on a GPU ends nearer the truth than without colour at 0.001 and 0.01 and farther
+#: at 0.1 and 1: hence 0.01.  Measured on nothing else: they are scene-dependent.  COLOUR_GATE is in intensity units
+#: (0 .. 255), COLOUR_WEIGHT in mm^2 per intensity^2 -- it trades a squared distance residual against a squared brightness residual.
+COLOUR_GATE = 64.0
+COLOUR_WEIGHT = 0.01
+
+
 class FieldAligner:
     """tsdf_aligner (include/tsdf_amd.h, "field alignment"): Gauss-Newton alignment of point sets to a volume's field.  Every call
     runs on the volume's stream."""
@@ -1238,10 +1270,52 @@ class FieldAligner:
                                     A.ctypes.data, b.ctypes.data, ri.ctypes.data, C.c_void_p(int(rows_ptr)) if rows_ptr else None))
         return A.reshape(6, 6), b, float(ri[0]), float(ri[1])
 
-    def step(self, volume, points, T=None, gate=None, rows=False):
-        """(n, 3) float32 host points -> (A, b, residual, inliers) and, with rows=True, the (n, 7) rows (NaN rows for outliers)."""
+    def _colour(self, colour_gate, colour_weight):
+        return (float(COLOUR_GATE if colour_gate is None else colour_gate), float(COLOUR_WEIGHT if colour_weight is None else colour_weight))
+
+    def step_colour_device(self, volume, n, points_ptr, intensity_ptr, T=None, gate=None, colour_gate=None, colour_weight=None, rows_ptr=None):
+        """tsdf_aligner_step_colour over n device points and intensities: (A 6x6, b 6 of the combined system, (residual, colour
+        residual), (inliers, colour inliers)); rows_ptr: 14 n floats or None."""
+        gate = self._on(volume, gate)
+        cg, cw = self._colour(colour_gate, colour_weight)
+        Tc = _pose16(T)
+        A, b, ri = np.zeros(36, np.float32), np.zeros(6, np.float32), np.zeros(4, np.float32)
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_aligner_step_colour(self._h, volume._h, int(n), ptr(points_ptr), ptr(intensity_ptr), Tc.ctypes.data, gate, cg, cw,
+                                           A.ctypes.data, b.ctypes.data, ri.ctypes.data, ptr(rows_ptr)))
+        return A.reshape(6, 6), b, (float(ri[0]), float(ri[2])), (float(ri[1]), float(ri[3]))
+
+    def run_colour_device(self, volume, stages, T0=None, gate=None, colour_gate=None, colour_weight=None):
+        """stages: up to 8 (points_ptr, intensity_ptr, n, iterations) run as one chain -> (T 4x4 float64, (residual, colour residual),
+        (inliers, colour inliers)) of the last step."""
+        gate = self._on(volume, gate)
+        cg, cw = self._colour(colour_gate, colour_weight)
+        st = (_capi.AlignColourStage * max(1, len(stages)))()
+        for i, (ptr, iptr, n, it) in enumerate(stages):
+            st[i].device_points, st[i].device_intensity = (int(ptr) if ptr else None), (int(iptr) if iptr else None)
+            st[i].n, st[i].iterations = int(n), int(it)
+        Tc = _pose16(T0)
+        res, inl = np.zeros(2, np.float32), np.zeros(2, np.float32)
+        check(lib.tsdf_aligner_run_colour(self._h, volume._h, len(stages), st, gate, cg, cw, Tc.ctypes.data, res.ctypes.data, inl.ctypes.data))
+        return Tc.reshape(4, 4).T.copy(), (float(res[0]), float(res[1])), (float(inl[0]), float(inl[1]))
+
+    def step(self, volume, points, T=None, gate=None, rows=False, intensity=None, colour_gate=None, colour_weight=None):
+        """(n, 3) float32 host points -> (A, b, residual, inliers) and, with rows=True, the (n, 7) rows (NaN rows for outliers).
+        `intensity` ((n,) float32; NaN: a point without colour): the step with the colour term ("colour alignment") -- A and b are the
+        combined system, residual and inliers pairs (geometric, colour), the rows (n, 14): both rows of every point.  colour_gate,
+        colour_weight: see COLOUR_GATE, COLOUR_WEIGHT."""
         p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
         n = len(p)
+        if intensity is not None:
+            y = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+            if len(y) != n:
+                raise ValueError("expected %d intensities, got %d" % (n, len(y)))
+            out = np.empty((n, 14), np.float32)
+            with _DeviceArray(p) as dp, _DeviceArray(y) as dy, _DeviceArray(nbytes=out.nbytes if rows else 0) as dr:
+                res = self.step_colour_device(volume, n, dp.ptr.value, dy.ptr.value, T, gate, colour_gate, colour_weight, dr.ptr.value)
+                if rows and n:
+                    check(lib.tsdf_device_download(out.ctypes.data, dr.ptr, out.nbytes))
+            return res + (out,) if rows else res
         out = np.empty((n, 7), np.float32)
         with _DeviceArray(p) as dp, _DeviceArray(nbytes=out.nbytes if rows else 0) as dr:
             res = self.step_device(volume, n, dp.ptr.value, T, gate, dr.ptr.value)
@@ -1260,10 +1334,19 @@ class FieldAligner:
         check(lib.tsdf_aligner_run(self._h, volume._h, len(stages), st, gate, Tc.ctypes.data, C.byref(res), C.byref(inl)))
         return Tc.reshape(4, 4).T.copy(), float(res.value), float(inl.value)
 
-    def run(self, volume, stages, T0=None, gate=None):
-        """stages: up to 8 ((n, 3) float32 host points, iterations)."""
+    def run(self, volume, stages, T0=None, gate=None, intensity=None, colour_gate=None, colour_weight=None):
+        """stages: up to 8 ((n, 3) float32 host points, iterations).  `intensity`: one (n,) float32 array per stage -- the chain with
+        the colour term (run_colour_device); residual and inliers are then pairs (geometric, colour)."""
         import contextlib
         hosts = [(np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3), int(it)) for p, it in stages]
+        if intensity is not None:
+            ys = [np.ascontiguousarray(y, dtype=np.float32).reshape(-1) for y in intensity]
+            if len(ys) != len(hosts) or any(len(y) != len(p) for y, (p, _) in zip(ys, hosts)):
+                raise ValueError("run: one intensity per point of every stage is needed")
+            with contextlib.ExitStack() as stack:
+                dev = [(stack.enter_context(_DeviceArray(p)).ptr.value, stack.enter_context(_DeviceArray(y)).ptr.value, len(p), it)
+                       for (p, it), y in zip(hosts, ys)]
+                return self.run_colour_device(volume, dev, T0, gate, colour_gate, colour_weight)
         with contextlib.ExitStack() as stack:
             dev = [(stack.enter_context(_DeviceArray(p)).ptr.value, len(p), it) for p, it in hosts]
             return self.run_device(volume, dev, T0, gate)
@@ -1291,6 +1374,30 @@ def depth_to_points(depth, width, height, kinv, step=1, depth_cutoff=float("inf"
         depth_to_points_device(width, height, dd.ptr.value, kinv, step, depth_cutoff, dp.ptr.value)
         check(lib.tsdf_stream_synchronize(None))
         check(lib.tsdf_device_download(out.ctypes.data, dp.ptr, out.nbytes))
+    return out
+
+
+def rgb_to_intensity_device(width, height, rgb_ptr, step, intensity_ptr, stream=0):
+    """tsdf_rgb_to_intensity_device: every step-th pixel of an RGB frame (3 bytes a pixel) -> its intensity, in the order and count of
+    depth_to_points_device's points; asynchronous on `stream`."""
+    check(lib.tsdf_rgb_to_intensity_device(int(width), int(height), C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, int(step),
+                                           C.c_void_p(int(intensity_ptr)) if intensity_ptr else None, C.c_void_p(int(stream) if stream else 0)))
+
+
+def rgb_to_intensity(rgb, width, height, step=1):
+    """Host RGB frame (uint8, width * height * 3) -> (ceil(height / step), ceil(width / step)) float32: Y = (77 r + 150 g + 29 b) / 256
+    of every step-th pixel, pairing up with depth_to_points at the same step."""
+    c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1)
+    width, height, step = int(width), int(height), int(step)
+    if c.size != 3 * width * height:
+        raise ValueError("rgb has %d bytes, expected %d" % (c.size, 3 * width * height))
+    if step <= 0:
+        raise ValueError("rgb_to_intensity: step is 0")
+    out = np.empty((-(-height // step), -(-width // step)), np.float32)
+    with _DeviceArray(c) as dc, _DeviceArray(nbytes=out.nbytes) as dy:
+        rgb_to_intensity_device(width, height, dc.ptr.value, step, dy.ptr.value)
+        check(lib.tsdf_stream_synchronize(None))
+        check(lib.tsdf_device_download(out.ctypes.data, dy.ptr, out.nbytes))
     return out
 
 

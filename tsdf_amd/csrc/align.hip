@@ -11,6 +11,11 @@
 //     goes in and comes out through a pinned coherent block, so a run is its launches and one synchronise.
 //   * The pose is kept about the centre of the volume's box (the host shifts it in double both ways): the rotation columns of the
 //     normal matrix are u x g, and with u measured from the world origin they would carry the distance to it.
+//   * The colour term (include/tsdf_amd.h, "colour alignment") is a kernel of its own, align_colour_reduce_kernel: align_row, then for a
+//     geometric inlier the intensity of the fused colours in the cell of the distance sample and the exact derivative of that interpolant
+//     (eight colour dwords), the photometric row against the point's observed intensity and a second block of 29 sums in the same
+//     order; 64 floats a workgroup.  Its prologue and align_colour_finish_kernel combine the two blocks (icp_finish_step<true>).
+//     align_reduce_kernel and the plain entry points are what they were.  58 accumulators and two rows: 141 - 148 VGPRs, no scratch.
 // Nothing of the volume is written.  Per-point arithmetic is separately rounded fp32 (contraction is off).
 #include <cmath>
 #include <cstring>
@@ -26,8 +31,9 @@ struct tsdf_aligner {
     float *partial;        // 2 x kIcpBlocks x 32 floats: per-workgroup sums of the 29 entries (two steps)
     double *state;         // device, 2 x kIcpStateDoubles, laid out as tsdf_icp's: [0..15] T_c, [16] residual, [17] inliers, [18..53] A, [54..59] b
     int side;              // which copy of state / partial holds the latest step
-    double *host_io;       // pinned, coherent: [0..15] the pose a chain starts from, [16..33] its result (pose, residual, inliers)
+    double *host_io;       // pinned, coherent: [0..15] the pose a chain starts from, [16..35] its result (pose, residual, inliers; the colour term's two behind them)
     double *host_io_dev;
+    float *partial_c;      // colour alignment: 2 x kIcpBlocks x 64 floats (both blocks of sums), made by the first colour call
 };
 
 namespace tsdf {
@@ -137,6 +143,173 @@ __global__ __launch_bounds__(kIcpThreads) void align_reduce_kernel(const double 
     }
 }
 
+// ---- the colour term (include/tsdf_amd.h, "colour alignment") ---------------------------------------------------------------------
+// the colour term's constants of a call
+struct AlignColour {
+    const uint32_t *colour;   // the volume's colour words
+    float gate;
+    float weight;
+};
+
+// The photometric row of a geometric inlier with observed intensity y (u as align_row forms it); false for a colour outlier.
+template <bool FASTDIV>
+__device__ inline bool align_colour_row(float u0, float u1, float u2, float y, const FieldView &f, const AlignField &a, const AlignColour &ac,
+                                        float *row) {
+    FieldCell cell;
+    if (!field_cell<FASTDIV>(f, u0 + a.h.x, u1 + a.h.y, u2 + a.h.z, cell)) return false;
+    float c = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    if (!field_intensity<FASTDIV, true, true>(f, ac.colour, cell, c, gx, gy, gz)) return false;
+    const float e = c - y;
+    if (!(fabsf(y) < INFINITY && fabsf(e) < ac.gate)) return false;   // (false for a NaN y: a point without colour)
+    row[0] = gx;
+    row[1] = gy;
+    row[2] = gz;
+    row[3] = u1 * gz - u2 * gy;
+    row[4] = u2 * gx - u0 * gz;
+    row[5] = u0 * gy - u1 * gx;
+    row[6] = -e;
+    return true;
+}
+
+// align_reduce_kernel with the photometric row beside the geometric one: a second block of 29 sums in the same order, 64 floats a
+// workgroup (the geometric block at [0, 29), the colour block at [32, 61)).  The colour taps are read for geometric inliers only.  The
+// prologue combines the two blocks of the step before (icp_finish_step<true>).  ROWS: 14 floats a point, both rows.
+template <bool FASTDIV, bool ROWS>
+__global__ __launch_bounds__(kIcpThreads) void align_colour_reduce_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
+                                                                         const float *__restrict__ partial_prev, int pending, int prev_blocks,
+                                                                         const FieldView f, const AlignField a, const AlignColour ac,
+                                                                         const uint32_t n, const float *__restrict__ points,
+                                                                         const float *__restrict__ intensity, float *__restrict__ rows,
+                                                                         float *__restrict__ partial) {
+    __shared__ double pose[16];
+    if (pending) {
+        icp_finish_step<true>(partial_prev, prev_blocks, state_in, 1, pose, blockIdx.x == 0 ? state_out : nullptr, ac.weight);
+    } else {
+        if (threadIdx.x < 16) {
+            pose[threadIdx.x] = state_in[threadIdx.x];
+            if (blockIdx.x == 0) state_out[threadIdx.x] = state_in[threadIdx.x];
+        }
+    }
+    __syncthreads();
+    __shared__ float shared[4][64];
+    float R[9], t[3];  // column-major
+    for (int c = 0; c < 3; c++)
+        for (int r = 0; r < 3; r++) R[c * 3 + r] = (float)pose[c * 4 + r];
+    for (int r = 0; r < 3; r++) t[r] = (float)pose[12 + r];
+
+    float sum[29], sum_c[29];
+#pragma unroll
+    for (int i = 0; i < 29; i++) sum[i] = sum_c[i] = 0.0f;
+    const uint32_t stride = (uint32_t)kIcpThreads * gridDim.x;   // <= 65536
+    for (uint64_t i = (uint64_t)blockIdx.x * kIcpThreads + threadIdx.x; i < n; i += stride) {
+        float row[7], row_c[7];
+        const float x0 = points[3 * i + 0], x1 = points[3 * i + 1], x2 = points[3 * i + 2];
+        const bool in = align_row<FASTDIV>(R, t, x0, x1, x2, f, a, row);
+        bool in_c = false;
+        if (in) {
+            // align_row's u (the same expressions: the compiler keeps one copy)
+            const float u0 = ((R[0] * x0 + R[3] * x1) + R[6] * x2) + t[0];
+            const float u1 = ((R[1] * x0 + R[4] * x1) + R[7] * x2) + t[1];
+            const float u2 = ((R[2] * x0 + R[5] * x1) + R[8] * x2) + t[2];
+            in_c = align_colour_row<FASTDIV>(u0, u1, u2, intensity[i], f, a, ac, row_c);
+        }
+        if (ROWS) {
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                rows[14 * i + k] = in ? row[k] : NAN;
+                rows[14 * i + 7 + k] = in_c ? row_c[k] : NAN;
+            }
+        }
+        if (in) {
+            int s = 0;
+#pragma unroll
+            for (int o = 0; o < 7; o++)
+#pragma unroll
+                for (int k = o; k < 7; k++) sum[s++] += row[o] * row[k];
+            sum[28] += 1.0f;
+        }
+        if (in_c) {
+            int s = 0;
+#pragma unroll
+            for (int o = 0; o < 7; o++)
+#pragma unroll
+                for (int k = o; k < 7; k++) sum_c[s++] += row_c[o] * row_c[k];
+            sum_c[28] += 1.0f;
+        }
+    }
+    // both blocks as align_reduce_kernel adds its one: the wave64 shuffle tree, then the four waves in a fixed order
+#pragma unroll
+    for (int i = 0; i < 29; i++) {
+        float v = sum[i], c = sum_c[i];
+        for (int o = 32; o > 0; o >>= 1) {
+            v += __shfl_down(v, o);
+            c += __shfl_down(c, o);
+        }
+        sum[i] = v;
+        sum_c[i] = c;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 29; i++) {
+            shared[wave][i] = sum[i];
+            shared[wave][32 + i] = sum_c[i];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 64 && (threadIdx.x & 31) < 29) {
+        partial[blockIdx.x * 64 + threadIdx.x] =
+            ((shared[0][threadIdx.x] + shared[1][threadIdx.x]) + shared[2][threadIdx.x]) + shared[3][threadIdx.x];
+    }
+}
+
+// icp_finish_kernel for the two blocks: one workgroup; `mirror` (pinned, or null) gets the pose, then residual and inliers of the
+// geometric and of the colour term
+__global__ __launch_bounds__(kIcpThreads) void align_colour_finish_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
+                                                                         const float *__restrict__ partial_prev, int n_blocks, int update,
+                                                                         float colour_weight, double *__restrict__ mirror) {
+    __shared__ double pose[16];
+    icp_finish_step<true>(partial_prev, n_blocks, state_in, update, pose, state_out, colour_weight);
+    if (mirror && threadIdx.x == 0) {   // (thread 0 solved the step: what it has just written)
+#pragma unroll
+        for (int i = 0; i < 16; i++) mirror[i] = pose[i];
+        mirror[16] = state_out[16];
+        mirror[17] = state_out[17];
+        mirror[18] = state_out[60];
+        mirror[19] = state_out[61];
+    }
+}
+
+// The intensity of the colour field and its gradient at world points, one thread per point (the frame of the field queries).
+template <bool VALUE, bool GRAD, bool FASTDIV>
+__global__ __launch_bounds__(256) void intensity_sample_kernel(const FieldView f, const uint32_t *__restrict__ colour, const uint64_t n_points,
+                                                               const float *__restrict__ points, float *__restrict__ out_intensity,
+                                                               float *__restrict__ out_gradient) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_points) return;
+    const float qx = points[3 * i + 0] - f.g.offset.x;
+    const float qy = points[3 * i + 1] - f.g.offset.y;
+    const float qz = points[3 * i + 2] - f.g.offset.z;
+    float c = NAN, gx = NAN, gy = NAN, gz = NAN;
+    FieldCell cell;
+    if (field_valid(f, qx, qy, qz) && field_cell<FASTDIV>(f, qx, qy, qz, cell)) (void)field_intensity<FASTDIV, VALUE, GRAD>(f, colour, cell, c, gx, gy, gz);
+    if (VALUE) out_intensity[i] = c;
+    if (GRAD) {
+        out_gradient[3 * i + 0] = gx;
+        out_gradient[3 * i + 1] = gy;
+        out_gradient[3 * i + 2] = gz;
+    }
+}
+
+// Y of every step-th pixel of an RGB frame (3 bytes a pixel), in the order and count of depth_to_points_kernel's points
+__global__ __launch_bounds__(256) void rgb_to_intensity_kernel(const uint8_t *__restrict__ rgb, uint32_t width, uint32_t out_w, uint32_t out_h,
+                                                               uint32_t step, float *__restrict__ intensity) {
+    const uint32_t ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (ox >= out_w || oy >= out_h) return;
+    const uint8_t *p = rgb + 3 * ((size_t)(oy * step) * width + ox * step);
+    intensity[(size_t)oy * out_w + ox] = colour_intensity((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16));
+}
+
 // orc-style pixel_to_camera of every step-th pixel: (kinv * (x, y, 1)) * (depth / its z), the NaN triple for depth 0 or above the cutoff
 __global__ __launch_bounds__(256) void depth_to_points_kernel(const uint16_t *__restrict__ depth, uint32_t width, uint32_t out_w,
                                                               uint32_t out_h, uint32_t step, const Mat33 kinv, float depth_cutoff,
@@ -161,7 +334,7 @@ __global__ __launch_bounds__(256) void depth_to_points_kernel(const uint16_t *__
 }
 
 static void free_aligner(tsdf_aligner *a) {
-    device_free_all(a->partial, a->state);
+    device_free_all(a->partial, a->state, a->partial_c);
     (void)hipHostFree(a->host_io);
     delete a;
 }
@@ -236,6 +409,81 @@ static void launch_align_finish(tsdf_aligner *a, int n_blocks, int update, doubl
     a->side = out;
 }
 
+// ---- the colour term's host side ------------------------------------------------------------------------------------------------
+// what the colour calls refuse beyond align_setup, and the sums' second home
+static int align_colour_setup(tsdf_aligner *a, const tsdf_volume *v, float colour_gate, float colour_weight, const char *what, AlignColour &ac) {
+    TSDF_REQUIRE(v->colour, "%s: colour is not enabled on this volume (tsdf_volume_enable_colour)", what);
+    TSDF_REQUIRE(colour_gate > 0.0f, "%s: the colour gate must be > 0", what);   // (false for NaN)
+    TSDF_REQUIRE(colour_weight >= 0.0f && colour_weight < INFINITY, "%s: the colour weight must be finite and >= 0", what);
+    if (!a->partial_c) {
+        const size_t bytes = (size_t)2 * kIcpBlocks * 64 * sizeof(float);
+        TSDF_HIP(hipMalloc((void **)&a->partial_c, bytes), "aligner: the colour sums");
+        const hipError_t e = hipMemset(a->partial_c, 0, bytes);
+        if (e != hipSuccess) {
+            device_free_all(a->partial_c);
+            return hip_fail(e, "aligner: the colour sums");
+        }
+    }
+    ac.colour = v->colour;
+    ac.gate = colour_gate;
+    ac.weight = colour_weight;
+    return TSDF_OK;
+}
+
+static void launch_align_colour_step(tsdf_aligner *a, const AlignSetup &s, const AlignColour &ac, uint32_t n, const float *points,
+                                     const float *intensity, float *rows, int pending, int prev_blocks, const double *start) {
+    const int in = a->side, out = 1 - a->side;
+    const double *state_in = start ? start : a->state + in * kIcpStateDoubles;
+    double *state_out = a->state + out * kIcpStateDoubles;
+    const float *partial_prev = a->partial_c + (size_t)in * kIcpBlocks * 64;
+    float *partial = a->partial_c + (size_t)out * kIcpBlocks * 64;
+    const dim3 grid((unsigned)align_blocks(n)), block(kIcpThreads);
+#define TSDF_ALIGN_LAUNCH(FD, RW) \
+    hipLaunchKernelGGL((align_colour_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, state_out, partial_prev, pending, prev_blocks, s.f, s.a, ac, n, points, intensity, rows, partial)
+    if (rows) {
+        if (s.fast_div) TSDF_ALIGN_LAUNCH(true, true);
+        else TSDF_ALIGN_LAUNCH(false, true);
+    } else {
+        if (s.fast_div) TSDF_ALIGN_LAUNCH(true, false);
+        else TSDF_ALIGN_LAUNCH(false, false);
+    }
+#undef TSDF_ALIGN_LAUNCH
+    a->side = out;
+}
+
+static void launch_align_colour_finish(tsdf_aligner *a, const AlignColour &ac, int n_blocks, int update, double *mirror) {
+    const int in = a->side, out = 1 - a->side;
+    hipLaunchKernelGGL(align_colour_finish_kernel, dim3(1), dim3(kIcpThreads), 0, a->stream, a->state + in * kIcpStateDoubles,
+                       a->state + out * kIcpStateDoubles, a->partial_c + (size_t)in * kIcpBlocks * 64, n_blocks, update, ac.weight, mirror);
+    a->side = out;
+}
+
+static int sample_intensity_check(const tsdf_volume *v, const char *what) {
+    TSDF_REQUIRE(v, "%s: null volume", what);
+    const int rc = field_refuse_slab(v, what);
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(v->colour, "%s: colour is not enabled on this volume (tsdf_volume_enable_colour)", what);
+    return TSDF_OK;
+}
+
+// the launch: at least one output, n > 0
+static int sample_intensity(const tsdf_volume *v, uint64_t n, const float *points, float *intensity, float *gradient, hipStream_t stream) {
+    TSDF_REQUIRE((n + 255) / 256 <= 0x7FFFFFFFull, "tsdf_volume_sample_intensity: too many points");
+    const FieldView f = make_field_view(v);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+#define TSDF_INTENSITY_LAUNCH(VAL, GR) \
+    do { \
+        if (v->fast_div) hipLaunchKernelGGL((intensity_sample_kernel<VAL, GR, true>), grid, block, 0, stream, f, v->colour, n, points, intensity, gradient); \
+        else hipLaunchKernelGGL((intensity_sample_kernel<VAL, GR, false>), grid, block, 0, stream, f, v->colour, n, points, intensity, gradient); \
+    } while (0)
+    if (intensity && gradient) TSDF_INTENSITY_LAUNCH(true, true);
+    else if (intensity) TSDF_INTENSITY_LAUNCH(true, false);
+    else TSDF_INTENSITY_LAUNCH(false, true);
+#undef TSDF_INTENSITY_LAUNCH
+    TSDF_HIP(hipGetLastError(), "Intensity sample kernel failed");
+    return TSDF_OK;
+}
+
 }  // namespace tsdf
 
 using namespace tsdf;
@@ -256,8 +504,8 @@ int tsdf_aligner_create(tsdf_aligner **out) {
     if (e == hipSuccess) e = hipMemset(a->partial, 0, (size_t)2 * kIcpBlocks * 32 * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&a->state, 2 * kIcpStateDoubles * sizeof(double));
     if (e == hipSuccess) e = hipMemset(a->state, 0, 2 * kIcpStateDoubles * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&a->host_io, (16 + 18) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) std::memset(a->host_io, 0, (16 + 18) * sizeof(double));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&a->host_io, (16 + 20) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) std::memset(a->host_io, 0, (16 + 20) * sizeof(double));
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&a->host_io_dev, a->host_io, 0);
     if (e != hipSuccess) {
         free_aligner(a);
@@ -369,6 +617,143 @@ int tsdf_depth_to_points_device(uint32_t width, uint32_t height, const uint16_t 
     hipLaunchKernelGGL(depth_to_points_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(256), 0, (hipStream_t)hip_stream, device_depth, width,
                        out_w, out_h, step, m, depth_cutoff, device_points);
     TSDF_HIP(hipGetLastError(), "depth_to_points kernel failed");
+    return TSDF_OK;
+}
+
+// ---- colour alignment -----------------------------------------------------------------------------------------------------------
+int tsdf_volume_sample_intensity_device(const tsdf_volume *v, uint64_t n, const float *device_points, float *device_intensity,
+                                        float *device_gradient, void *hip_stream) {
+    const int rc = sample_intensity_check(v, "tsdf_volume_sample_intensity");
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(device_intensity || device_gradient, "tsdf_volume_sample_intensity: no output asked for (both are NULL)");
+    TSDF_REQUIRE(n == 0 || device_points, "tsdf_volume_sample_intensity: null points");
+    if (n == 0) return TSDF_OK;
+    return sample_intensity(v, n, device_points, device_intensity, device_gradient, (hipStream_t)hip_stream);
+}
+
+int tsdf_volume_sample_intensity(const tsdf_volume *v, uint64_t n, const float *host_points, float *host_intensity, float *host_gradient) {
+    const int rc0 = sample_intensity_check(v, "tsdf_volume_sample_intensity");
+    if (rc0 != TSDF_OK) return rc0;
+    TSDF_REQUIRE(host_intensity || host_gradient, "tsdf_volume_sample_intensity: no output asked for (both are NULL)");
+    TSDF_REQUIRE(n == 0 || host_points, "tsdf_volume_sample_intensity: null points");
+    if (n == 0) return TSDF_OK;
+    TSDF_REQUIRE(n <= ((uint64_t)1 << 40), "tsdf_volume_sample_intensity: too many points");
+    // one allocation: points (3n), then intensity (n) and gradient (3n) as far as asked for
+    const size_t fn = (size_t)n;
+    const size_t o_i = 3 * fn, o_g = o_i + (host_intensity ? fn : 0), total = o_g + (host_gradient ? 3 * fn : 0);
+    HostStage st;
+    int rc = st.begin(v->stream, total * sizeof(float), "tsdf_volume_sample_intensity: couldn't allocate %zu bytes for the points and results");
+    if (rc != TSDF_OK) return rc;
+    float *const buf = static_cast<float *>(st.buf);
+    float *c = host_intensity ? buf + o_i : nullptr, *g = host_gradient ? buf + o_g : nullptr;
+    st.up(buf, host_points, 3 * fn * sizeof(float));
+    if (st.ok()) rc = sample_intensity(v, n, buf, c, g, v->stream);
+    if (rc == TSDF_OK) {
+        if (c) st.down(host_intensity, c, fn * sizeof(float));
+        if (g) st.down(host_gradient, g, 3 * fn * sizeof(float));
+    }
+    return st.finish(rc, "Intensity sample failed");
+}
+
+int tsdf_rgb_to_intensity_device(uint32_t width, uint32_t height, const uint8_t *device_rgb, uint32_t step, float *device_intensity,
+                                 void *hip_stream) {
+    TSDF_REQUIRE(device_rgb && device_intensity, "tsdf_rgb_to_intensity: null argument");
+    TSDF_REQUIRE(step != 0, "tsdf_rgb_to_intensity: step is 0");
+    TSDF_REQUIRE(width > 0 && height > 0 && width <= 65535 && height <= 65535, "tsdf_rgb_to_intensity: bad image size");
+    const uint32_t out_w = (uint32_t)(((uint64_t)width + step - 1) / step), out_h = (uint32_t)(((uint64_t)height + step - 1) / step);
+    hipLaunchKernelGGL(rgb_to_intensity_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(256), 0, (hipStream_t)hip_stream, device_rgb, width,
+                       out_w, out_h, step, device_intensity);
+    TSDF_HIP(hipGetLastError(), "rgb_to_intensity kernel failed");
+    return TSDF_OK;
+}
+
+int tsdf_aligner_step_colour(tsdf_aligner *a, const tsdf_volume *v, uint32_t n, const float *device_points, const float *device_intensity,
+                             const double T[16], float gate, float colour_gate, float colour_weight, float A[36], float b[6],
+                             float residual_inliers[4], float *device_rows) {
+    TSDF_REQUIRE(A && b && residual_inliers, "tsdf_aligner_step_colour: null argument");
+    TSDF_REQUIRE(n == 0 || device_points, "tsdf_aligner_step_colour: null points");
+    TSDF_REQUIRE(n == 0 || device_intensity, "tsdf_aligner_step_colour: null intensities");
+    AlignSetup s;
+    AlignColour ac;
+    int rc = align_setup(a, v, T, gate, "tsdf_aligner_step_colour", s);
+    if (rc == TSDF_OK) rc = align_colour_setup(a, v, colour_gate, colour_weight, "tsdf_aligner_step_colour", ac);
+    if (rc != TSDF_OK) return rc;
+    if (n == 0) {
+        std::memset(A, 0, 36 * sizeof(float));
+        std::memset(b, 0, 6 * sizeof(float));
+        std::memset(residual_inliers, 0, 4 * sizeof(float));
+        return TSDF_OK;
+    }
+    align_pose_in(a, s, T);
+    launch_align_colour_step(a, s, ac, n, device_points, device_intensity, device_rows, 0, 0, a->host_io_dev);
+    launch_align_colour_finish(a, ac, align_blocks(n), 0, nullptr);
+    TSDF_HIP(hipGetLastError(), "align kernels failed");
+    double out[kIcpStateDoubles];
+    TSDF_HIP(hipMemcpyAsync(out, a->state + a->side * kIcpStateDoubles, sizeof(out), hipMemcpyDeviceToHost, a->stream), "align result download");
+    TSDF_HIP(hipStreamSynchronize(a->stream), "align step");
+    residual_inliers[0] = (float)out[16];
+    residual_inliers[1] = (float)out[17];
+    residual_inliers[2] = (float)out[60];
+    residual_inliers[3] = (float)out[61];
+    for (int i = 0; i < 36; i++) A[i] = (float)out[18 + i];
+    for (int i = 0; i < 6; i++) b[i] = (float)out[54 + i];
+    return TSDF_OK;
+}
+
+int tsdf_aligner_run_colour(tsdf_aligner *a, const tsdf_volume *v, uint32_t n_stages, const tsdf_align_colour_stage *stages, float gate,
+                            float colour_gate, float colour_weight, double T[16], float residual[2], float inliers[2]) {
+    TSDF_REQUIRE(n_stages <= (uint32_t)kAlignMaxStages, "tsdf_aligner_run_colour: more than %d stages", kAlignMaxStages);
+    TSDF_REQUIRE(n_stages == 0 || stages, "tsdf_aligner_run_colour: null stages");
+    for (uint32_t i = 0; i < n_stages; i++) {
+        const bool empty = stages[i].n == 0 || stages[i].iterations == 0;
+        TSDF_REQUIRE(empty || stages[i].device_points, "tsdf_aligner_run_colour: stage %u has null points", i);
+        TSDF_REQUIRE(empty || stages[i].device_intensity, "tsdf_aligner_run_colour: stage %u has null intensities", i);
+    }
+    AlignSetup s;
+    AlignColour ac;
+    int rc = align_setup(a, v, T, gate, "tsdf_aligner_run_colour", s);
+    if (rc == TSDF_OK) rc = align_colour_setup(a, v, colour_gate, colour_weight, "tsdf_aligner_run_colour", ac);
+    if (rc != TSDF_OK) return rc;
+    align_pose_in(a, s, T);   // (the pinned block, as tsdf_aligner_run)
+    int pending = 0, prev_blocks = 0;
+    for (uint32_t i = 0; i < n_stages; i++) {
+        if (stages[i].n == 0) continue;
+        for (uint32_t j = 0; j < stages[i].iterations; j++) {
+            launch_align_colour_step(a, s, ac, stages[i].n, stages[i].device_points, stages[i].device_intensity, nullptr, pending, prev_blocks,
+                                     pending ? nullptr : a->host_io_dev);
+            pending = 1;
+            prev_blocks = align_blocks(stages[i].n);
+        }
+    }
+    if (!pending) {   // nothing to do: the pose stays as given
+        if (residual) residual[0] = residual[1] = 0.0f;
+        if (inliers) inliers[0] = inliers[1] = 0.0f;
+        return TSDF_OK;
+    }
+    launch_align_colour_finish(a, ac, prev_blocks, 1, a->host_io_dev + 16);
+    TSDF_HIP(hipGetLastError(), "align kernels failed");
+    TSDF_HIP(hipStreamSynchronize(a->stream), "align");
+    double out[20];
+    std::memcpy(out, a->host_io + 16, sizeof(out));   // (the 20 doubles behind the pose: pose, then residual and inliers of both terms)
+    // A chain that did not move the pose hands the caller's matrix back as given, as tsdf_aligner_run does.
+    bool moved = false;
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++) moved = moved || out[c * 4 + r] != a->host_io[c * 4 + r];
+    if (moved) {
+        for (int c = 0; c < 4; c++) {
+            for (int r = 0; r < 3; r++) T[c * 4 + r] = out[c * 4 + r];
+            T[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
+        }
+        for (int r = 0; r < 3; r++) T[12 + r] = out[12 + r] + s.pivot[r];
+    }
+    if (residual) {
+        residual[0] = (float)out[16];
+        residual[1] = (float)out[18];
+    }
+    if (inliers) {
+        inliers[0] = (float)out[17];
+        inliers[1] = (float)out[19];
+    }
     return TSDF_OK;
 }
 

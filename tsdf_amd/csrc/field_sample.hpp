@@ -2,7 +2,8 @@
 // align.hip (field alignment) and fuse.hip (the source side of volume fusion).  Each rule is here once: where the weights are, which
 // points are valid, which voxel a valid point lies in and its weight, the distance sample (the ray cast's own trilinear(),
 // raycast_sample.hpp, so that a read agrees bit for bit with what the cast saw) and the central-difference gradient.  Points are in
-// the frame of the grid's lower corner (world - offset).  Contraction is off: every expression rounds as written.
+// the frame of the grid's lower corner (world - offset).  Contraction is off: every expression rounds as written.  At the end: the
+// intensity of the fused colours in the cell of the distance sample, for align.hip's colour term.
 #pragma once
 
 #include "raycast_sample.hpp"
@@ -107,6 +108,75 @@ __device__ inline void field_gradient(const FieldView &f, const FieldStencil &s,
     gx = (sxp - sxm) / (f.g.vs.x + f.g.vs.x);
     gy = (syp - sym) / (f.g.vs.y + f.g.vs.y);
     gz = (szp - szm) / (f.g.vs.z + f.g.vs.z);
+}
+
+// ---- the intensity of the fused colour field (include/tsdf_amd.h, "colour alignment") ------------------------------------------
+
+// Y = (77 r + 150 g + 29 b) / 256 of a colour word {r, g, b, n}: an integer <= 65280 times a power of two, exact in fp32
+__device__ inline float colour_intensity(uint32_t c) {
+    return (float)(77u * (c & 0xFFu) + 150u * ((c >> 8) & 0xFFu) + 29u * ((c >> 16) & 0xFFu)) * 0x1p-8f;
+}
+
+// The trilinear cell of the distance sample at a valid point: trilinear()'s lower voxel, u, v, w and clamped tap offsets, by its
+// expressions (a valid point is never clamped).  False where trilinear() finds no voxel (the distance there is NaN).
+struct FieldCell {
+    size_t base;            // index of tap 000, x fastest
+    uint32_t ox, oy, oz;    // offsets of the upper taps; 0 where the tap is clamped onto the lower one
+    float u, v, w;
+};
+
+template <bool FASTDIV>
+__device__ inline bool field_cell(const FieldView &f, float px, float py, float pz, FieldCell &c) {
+    int vx, vy, vz;
+    if (!field_voxel<FASTDIV>(f, px, py, pz, vx, vy, vz)) return false;
+    const float ccx = (vx + 0.5f) * f.g.vs.x + 0.0f;
+    const float ccy = (vy + 0.5f) * f.g.vs.y + 0.0f;
+    const float ccz = (vz + 0.5f) * f.g.vs.z + 0.0f;
+    const int lx = max((px < ccx) ? vx - 1 : vx, 0);
+    const int ly = max((py < ccy) ? vy - 1 : vy, 0);
+    const int lz = max((pz < ccz) ? vz - 1 : vz, 0);
+    const float lcx = (lx + 0.5f) * f.g.vs.x + 0.0f;
+    const float lcy = (ly + 0.5f) * f.g.vs.y + 0.0f;
+    const float lcz = (lz + 0.5f) * f.g.vs.z + 0.0f;
+    c.u = div_by<FASTDIV>(px - lcx, f.tc.dx);
+    c.v = div_by<FASTDIV>(py - lcy, f.tc.dy);
+    c.w = div_by<FASTDIV>(pz - lcz, f.tc.dz);
+    c.ox = ((uint32_t)lx + 1 < f.g.X) ? 1u : 0u;
+    c.oy = ((uint32_t)ly + 1 < f.g.Y) ? f.tc.row : 0u;
+    c.oz = ((uint32_t)lz + 1 < f.g.Z) ? f.tc.plane : 0u;
+    c.base = (size_t)f.tc.plane * (uint32_t)lz + ((size_t)f.tc.row * (uint32_t)ly + (uint32_t)lx);
+    return true;
+}
+
+// The intensity at a cell and the exact derivative of the interpolant inside it: eight colour dwords.  False (outputs untouched)
+// where a tap was never observed (n == 0).  VALUE / GRAD: an instance asked for one of the two has none of the other's code.
+template <bool FASTDIV, bool VALUE, bool GRAD>
+__device__ inline bool field_intensity(const FieldView &f, const uint32_t *__restrict__ colour, const FieldCell &c, float &value, float &gx,
+                                       float &gy, float &gz) {
+    const uint32_t *b000 = colour + c.base;
+    const uint32_t k000 = b000[0], k001 = b000[c.oz], k010 = b000[c.oy], k011 = b000[c.oy + c.oz];
+    const uint32_t k100 = b000[c.ox], k101 = b000[c.ox + c.oz], k110 = b000[c.ox + c.oy], k111 = b000[c.ox + c.oy + c.oz];
+    // (n > 0 in all eight: the smallest of the eight counts is not zero)
+    if (min(min(min(k000, k001), min(k010, k011)), min(min(k100, k101), min(k110, k111))) < (1u << 24)) return false;
+    const float i000 = colour_intensity(k000), i001 = colour_intensity(k001), i010 = colour_intensity(k010), i011 = colour_intensity(k011);
+    const float i100 = colour_intensity(k100), i101 = colour_intensity(k101), i110 = colour_intensity(k110), i111 = colour_intensity(k111);
+    const float u = c.u, v = c.v, w = c.w;
+    if (VALUE) {
+        value = i000 * (1 - u) * (1 - v) * (1 - w) +
+                i001 * (1 - u) * (1 - v) * w +
+                i010 * (1 - u) * v * (1 - w) +
+                i011 * (1 - u) * v * w +
+                i100 * u * (1 - v) * (1 - w) +
+                i101 * u * (1 - v) * w +
+                i110 * u * v * (1 - w) +
+                i111 * u * v * w;
+    }
+    if (GRAD) {
+        gx = div_by<FASTDIV>((i100 - i000) * (1 - v) * (1 - w) + (i101 - i001) * (1 - v) * w + (i110 - i010) * v * (1 - w) + (i111 - i011) * v * w, f.tc.dx);
+        gy = div_by<FASTDIV>((i010 - i000) * (1 - u) * (1 - w) + (i011 - i001) * (1 - u) * w + (i110 - i100) * u * (1 - w) + (i111 - i101) * u * w, f.tc.dy);
+        gz = div_by<FASTDIV>((i001 - i000) * (1 - u) * (1 - v) + (i011 - i010) * (1 - u) * v + (i101 - i100) * u * (1 - v) + (i111 - i110) * u * v, f.tc.dz);
+    }
+    return true;
 }
 
 }  // namespace tsdf

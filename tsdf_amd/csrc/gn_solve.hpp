@@ -183,8 +183,13 @@ __device__ inline void se3_exp(const double *a, double *E) {
 // getIncrementalTransformation: A, b, residual, inliers; when `update` != 0 also x = A^-1 b and T <- exp(x) * T.
 // Run by all 256 threads of a workgroup; the pose after the step goes to pose_out (shared memory, for the caller's
 // __syncthreads), the whole state to state_out when that is not null.  The sums were written by the previous launch.
+// COLOUR (align.hip's colour term; the default is the function as it always was): a workgroup's sums are 64 floats, the geometric
+// block at [0, 29) and the colour block at [32, 61); each block is added as above, then every entry of A and b handed to the solve is
+// (float)((double)S_g + (double)colour_weight * (double)S_c); state_out[60], [61] get the colour block's residual and count.
+template <bool COLOUR = false>
 __device__ __forceinline__ void icp_finish_step(const float *partial, int n_blocks, const double *state_in, int update, double *pose_out,
-                                       double *state_out) {
+                                       double *state_out, float colour_weight = 0.0f) {
+    constexpr int kStride = COLOUR ? 64 : 32;   // floats a workgroup
     // 29 entries x 8 groups of blocks: thread (entry, group) adds its 32 blocks in order (loads issued together), then
     // one thread per entry adds the 8 group sums in order -- a fixed tree, in double
     __shared__ double group_sum[8][32];
@@ -205,12 +210,26 @@ __device__ __forceinline__ void icp_finish_step(const float *partial, int n_bloc
 #pragma unroll
         for (int i = 0; i < 32; i++) {
             const int b = group * 32 + i, bb = b < n_blocks ? b : 0;
-            v[i] = partial[bb * 32 + entry];
+            v[i] = partial[bb * kStride + entry];
         }
         double s = 0.0;
 #pragma unroll
         for (int i = 0; i < 32; i++) s += (double)(group * 32 + i < n_blocks ? v[i] : 0.0f);
         group_sum[group][entry] = s;
+    }
+    __shared__ double group_sum_c[COLOUR ? 8 : 1][32];
+    __shared__ float total_c[32];
+    if (COLOUR && entry < 29) {
+        float v[32];
+#pragma unroll
+        for (int i = 0; i < 32; i++) {
+            const int b = group * 32 + i, bb = b < n_blocks ? b : 0;
+            v[i] = partial[bb * kStride + 32 + entry];
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < 32; i++) s += (double)(group * 32 + i < n_blocks ? v[i] : 0.0f);
+        group_sum_c[group][entry] = s;
     }
     __syncthreads();
     if (threadIdx.x < 29) {
@@ -218,9 +237,23 @@ __device__ __forceinline__ void icp_finish_step(const float *partial, int n_bloc
 #pragma unroll
         for (int g = 0; g < 8; g++) s += group_sum[g][threadIdx.x];
         total[threadIdx.x] = (float)s;  // the reference hands fp32 sums to the host
+        if (COLOUR) {
+            double c = 0.0;
+#pragma unroll
+            for (int g = 0; g < 8; g++) c += group_sum_c[g][threadIdx.x];
+            total_c[threadIdx.x] = (float)c;
+        }
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
+    if (COLOUR) {
+        if (state_out) {
+            state_out[60] = total_c[27];
+            state_out[61] = total_c[28];
+        }
+        // (the residual and the count stay per term: entries 27 and 28 are not combined)
+        for (int i = 0; i < 27; i++) total[i] = (float)((double)total[i] + (double)colour_weight * (double)total_c[i]);
+    }
     float A[36], b[6];
     int shift = 0;
     for (int i = 0; i < 6; ++i)

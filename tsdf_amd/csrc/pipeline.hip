@@ -148,6 +148,7 @@ struct tsdf_tracker {
     // tsdf_tracker_align_field: made on its first call (nullptr before)
     tsdf_aligner *aligner;
     float *align_points[3];     // the filtered frame as camera-frame points at steps 1, 2, 4
+    float *align_intensity[3];  // tsdf_tracker_align_field_colour: the rgb frame's intensities at the same steps (made on its first call)
 };
 
 using namespace tsdf;
@@ -669,6 +670,7 @@ int tsdf_tracker_destroy(tsdf_tracker *t) {
     delete[] t->ring_cam;
     if (t->aligner) tsdf_aligner_destroy(t->aligner);
     device_free_all(t->align_points[0], t->align_points[1], t->align_points[2]);
+    device_free_all(t->align_intensity[0], t->align_intensity[1], t->align_intensity[2]);
     if (t->side) (void)hipStreamDestroy(t->side);
     if (t->main) (void)hipStreamDestroy(t->main);
     delete t;
@@ -788,27 +790,57 @@ int tsdf_tracker_align(tsdf_tracker *t, const tsdf_camera_matrices *previous, do
     return tsdf_icp_get_incremental_transformation(t->icp, T_prev_curr, last_error, last_inliers);
 }
 
-int tsdf_tracker_align_field(tsdf_tracker *t, const float kinv[9], double T_world_cam[16], float *residual, float *inliers) {
-    TSDF_REQUIRE(t && kinv && T_world_cam, "tsdf_tracker_align_field: null argument");
-    TSDF_REQUIRE(t->have_frame && t->frames > 0, "tsdf_tracker_align_field: no frame filtered, or nothing integrated to align it to");
+// What both field alignments do in front of their chain: the aligner and the buffers on the first call, the join, then the filtered frame
+// as points at steps 4, 2 and 1 -- and, with an rgb frame, its intensities at the same steps -- on the main stream.  count[i]: the
+// points at step 1 << i.
+static int tracker_align_inputs(tsdf_tracker *t, const float kinv[9], const uint8_t *device_rgb, uint32_t count[3]) {
     const uint32_t steps[3] = {1, 2, 4};
-    uint32_t count[3];
     for (int i = 0; i < 3; i++) count[i] = ((t->width + steps[i] - 1) / steps[i]) * ((t->height + steps[i] - 1) / steps[i]);
     if (!t->aligner) {
         int rc = tsdf_aligner_create(&t->aligner);
         if (rc != TSDF_OK) return rc;
         (void)tsdf_aligner_set_stream(t->aligner, t->main);
     }
-    for (int i = 0; i < 3; i++)
-        if (!t->align_points[i]) TSDF_HIP(hipMalloc((void **)&t->align_points[i], (size_t)count[i] * 3 * sizeof(float)), "tsdf_tracker_align_field: point buffers");
+    for (int i = 0; i < 3; i++) {
+        if (!t->align_points[i]) TSDF_HIP(hipMalloc((void **)&t->align_points[i], (size_t)count[i] * 3 * sizeof(float)), "tracker field alignment: point buffers");
+        if (device_rgb && !t->align_intensity[i]) TSDF_HIP(hipMalloc((void **)&t->align_intensity[i], (size_t)count[i] * sizeof(float)), "tracker field alignment: intensity buffers");
+    }
     int rc = tracker_join(t);
     if (rc != TSDF_OK) return rc;
     for (int i = 2; i >= 0; i--) {
         rc = tsdf_depth_to_points_device(t->width, t->height, t->filtered[t->cur], kinv, steps[i], t->depth_cutoff * 1000.0f, t->align_points[i], t->main);
+        if (rc == TSDF_OK && device_rgb) rc = tsdf_rgb_to_intensity_device(t->width, t->height, device_rgb, steps[i], t->align_intensity[i], t->main);
         if (rc != TSDF_OK) return rc;
     }
+    return TSDF_OK;
+}
+
+int tsdf_tracker_align_field(tsdf_tracker *t, const float kinv[9], double T_world_cam[16], float *residual, float *inliers) {
+    TSDF_REQUIRE(t && kinv && T_world_cam, "tsdf_tracker_align_field: null argument");
+    TSDF_REQUIRE(t->have_frame && t->frames > 0, "tsdf_tracker_align_field: no frame filtered, or nothing integrated to align it to");
+    uint32_t count[3];
+    const int rc = tracker_align_inputs(t, kinv, nullptr, count);
+    if (rc != TSDF_OK) return rc;
     const tsdf_align_stage stages[3] = {{t->align_points[2], count[2], 4}, {t->align_points[1], count[1], 5}, {t->align_points[0], count[0], 10}};   // ICP's 4 / 5 / 10, coarse to fine
     return tsdf_aligner_run(t->aligner, t->volume, 3, stages, t->volume->g.trunc, T_world_cam, residual, inliers);
+}
+
+int tsdf_tracker_align_field_colour(tsdf_tracker *t, const float kinv[9], const uint8_t *device_rgb, float colour_gate, float colour_weight,
+                                    double T_world_cam[16], float residual[2], float inliers[2]) {
+    TSDF_REQUIRE(t && kinv && T_world_cam, "tsdf_tracker_align_field_colour: null argument");
+    TSDF_REQUIRE(device_rgb, "tsdf_tracker_align_field_colour: null rgb frame");
+    TSDF_REQUIRE(t->have_frame && t->frames > 0, "tsdf_tracker_align_field_colour: no frame filtered, or nothing integrated to align it to");
+    // (refused here, in front of the first allocation and launch; tsdf_aligner_run_colour checks again)
+    TSDF_REQUIRE(t->volume->colour, "tsdf_tracker_align_field_colour: colour is not enabled on this volume (tsdf_volume_enable_colour)");
+    TSDF_REQUIRE(colour_gate > 0.0f, "tsdf_tracker_align_field_colour: the colour gate must be > 0");
+    TSDF_REQUIRE(colour_weight >= 0.0f && colour_weight < INFINITY, "tsdf_tracker_align_field_colour: the colour weight must be finite and >= 0");
+    uint32_t count[3];
+    const int rc = tracker_align_inputs(t, kinv, device_rgb, count);
+    if (rc != TSDF_OK) return rc;
+    const tsdf_align_colour_stage stages[3] = {{t->align_points[2], t->align_intensity[2], count[2], 4},
+                                               {t->align_points[1], t->align_intensity[1], count[1], 5},
+                                               {t->align_points[0], t->align_intensity[0], count[0], 10}};   // ICP's 4 / 5 / 10, coarse to fine
+    return tsdf_aligner_run_colour(t->aligner, t->volume, 3, stages, t->volume->g.trunc, colour_gate, colour_weight, T_world_cam, residual, inliers);
 }
 
 // tsdf_tracker_integrate (rgb == nullptr) and tsdf_tracker_integrate_colour

@@ -167,6 +167,19 @@ public:
     // Throws std::invalid_argument on the refusals (a Z-slab, a non-finite entry in T0's top three rows).
     Eigen::Matrix4d align_points(const std::vector<float3> &points, const Eigen::Matrix4d &T0, uint32_t iterations = 10, float gate = 0.0f,
                                  float *residual = nullptr, float *inliers = nullptr) const;
+    // Colour alignment (include/tsdf_amd.h, "colour alignment"): align_points with a photometric row per point beside the geometric one --
+    // intensity[i] is the observed intensity Y = (77 r + 150 g + 29 b) / 256 of points[i] (NaN: none), compared with the intensity of
+    // the fused colours where the point lands; differences of colour_gate and more are left out, colour_weight (volume units squared per
+    // intensity squared; scene-dependent) scales the colour term's sums.  residual / inliers (may be null): two floats each, the
+    // geometric and the colour term's.  Also throws std::invalid_argument while colour is off, when intensity and points differ in
+    // length, when colour_gate is not > 0 and when colour_weight is negative or not finite.
+    Eigen::Matrix4d align_points(const std::vector<float3> &points, const std::vector<float> &intensity, const Eigen::Matrix4d &T0,
+                                 float colour_gate, float colour_weight, uint32_t iterations = 10, float gate = 0.0f,
+                                 float *residual = nullptr, float *inliers = nullptr) const;
+    // The intensity of the fused colours at world points (the frame of ray-cast and mesh vertices) and, when `gradient` is given, the
+    // exact derivative of that trilinear interpolant; NaN outside the grid and where one of the eight voxels has no colour.  Throws
+    // std::invalid_argument while colour is off.
+    std::vector<float> sample_intensity(const std::vector<float3> &points, std::vector<float3> *gradient = nullptr) const;
 
     // Distance field (include/tsdf_amd.h, "distance field"; not in the reference's class): per voxel the Euclidean distance (mm) to the
     // nearest site -- an observed voxel with an observed 6-neighbour of the other sign -- negative behind the surface, capped at

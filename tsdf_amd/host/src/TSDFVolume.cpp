@@ -262,6 +262,55 @@ Eigen::Matrix4d TSDFVolume::align_points(const std::vector<float3> &points, cons
     return T;
 }
 
+Eigen::Matrix4d TSDFVolume::align_points(const std::vector<float3> &points, const std::vector<float> &intensity, const Eigen::Matrix4d &T0,
+                                         float colour_gate, float colour_weight, uint32_t iterations, float gate, float *residual,
+                                         float *inliers) const {
+    if (points.size() > 0xFFFFFFFFull) throw std::invalid_argument("align_points: too many points");
+    if (intensity.size() != points.size()) throw std::invalid_argument("align_points: points and intensities differ in length");
+    tsdf_volume_info info;
+    check(tsdf_volume_get_info(m_handle, &info), "Couldn't read the volume's geometry");
+    struct Scratch {
+        tsdf_aligner *aligner = nullptr;
+        void *points = nullptr, *intensity = nullptr;
+        ~Scratch() {
+            if (aligner) tsdf_aligner_destroy(aligner);
+            if (points) tsdf_device_free(points);
+            if (intensity) tsdf_device_free(intensity);
+        }
+    } s;
+    check(tsdf_aligner_create(&s.aligner), "Couldn't create the aligner");
+    void *stream = nullptr;
+    check(tsdf_volume_stream(m_handle, &stream), "Couldn't read the volume's stream");
+    check(tsdf_aligner_set_stream(s.aligner, stream), "Couldn't set the aligner's stream");
+    if (!points.empty()) {
+        check(tsdf_device_alloc(points.size() * sizeof(float3), &s.points), "Couldn't allocate the points");
+        check(tsdf_device_upload(s.points, points.data(), points.size() * sizeof(float3)), "Couldn't upload the points");
+        check(tsdf_device_alloc(intensity.size() * sizeof(float), &s.intensity), "Couldn't allocate the intensities");
+        check(tsdf_device_upload(s.intensity, intensity.data(), intensity.size() * sizeof(float)), "Couldn't upload the intensities");
+    }
+    Eigen::Matrix4d T = T0;
+    const tsdf_align_colour_stage stage = {static_cast<const float *>(s.points), static_cast<const float *>(s.intensity),
+                                           (uint32_t)points.size(), iterations};
+    check(tsdf_aligner_run_colour(s.aligner, m_handle, 1, &stage, gate <= 0.0f ? info.truncation_distance : gate, colour_gate, colour_weight,
+                                  T.data(), residual, inliers),
+          "Align kernels failed");
+    return T;
+}
+
+std::vector<float> TSDFVolume::sample_intensity(const std::vector<float3> &points, std::vector<float3> *gradient) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    const size_t n = points.size();
+    // (one element more than needed: data() of an empty vector may be null, which the C ABI reads as "not asked for")
+    std::vector<float> intensity(n + 1, 0.0f);
+    if (gradient) gradient->assign(n + 1, float3{0.0f, 0.0f, 0.0f});
+    check(tsdf_volume_sample_intensity(m_handle, n, reinterpret_cast<const float *>(points.data()), intensity.data(),
+                                       gradient ? reinterpret_cast<float *>(gradient->data()) : nullptr),
+          "Couldn't sample the intensity");
+    intensity.resize(n);
+    if (gradient) gradient->resize(n);
+    return intensity;
+}
+
 uint64_t TSDFVolume::fuse(const TSDFVolume &src, const Eigen::Matrix4f &dst_to_src) {
     uint64_t fused = 0;
     check(tsdf_volume_fuse(m_handle, src.m_handle, dst_to_src.data(), &fused), "Fuse kernel failed");

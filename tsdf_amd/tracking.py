@@ -27,11 +27,20 @@ from .pipeline import OVERLAP, _matrices
 
 class FrameToModelTracker:
     def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True, window=0,
-                 method="icp"):
+                 method="icp", colour_weight=0.0, colour_gate=None):
         import torch
         if method not in ("icp", "field"):
             raise ValueError("method is 'icp' or 'field', got %r" % (method,))
+        colour_weight = float(colour_weight)
+        if not (colour_weight >= 0.0 and colour_weight < float("inf")):
+            raise ValueError("colour_weight must be finite and >= 0, got %r" % (colour_weight,))
+        if colour_weight > 0.0 and method != "field":
+            raise ValueError("colour_weight needs method='field' (the colour term belongs to field alignment)")
         self.method = method
+        # > 0: frames processed with rgb are aligned with the colour term (include/tsdf_amd.h, "colour alignment") from the second on
+        self.colour_weight = colour_weight
+        self.colour_gate = float(api.COLOUR_GATE if colour_gate is None else colour_gate)
+        self.last_colour_error, self.last_colour_inliers = 0.0, 0.0
         self.torch = torch
         self.volume = volume
         self.width, self.height = int(width), int(height)
@@ -93,10 +102,18 @@ class FrameToModelTracker:
         elif self.method == "field":
             Tc = np.ascontiguousarray(self.pose().T.reshape(-1))     # column-major double: the previous pose is the prediction
             kinv = np.ascontiguousarray(self.camera.kinv(), np.float32).reshape(-1)
-            res, inl = C.c_float(), C.c_float()
-            check(lib.tsdf_tracker_align_field(self._h, kinv.ctypes.data, Tc.ctypes.data, C.byref(res), C.byref(inl)))
+            if self.colour_weight > 0.0 and rgb_ptr is not None:
+                res2, inl2 = np.zeros(2, np.float32), np.zeros(2, np.float32)
+                check(lib.tsdf_tracker_align_field_colour(self._h, kinv.ctypes.data, C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, self.colour_gate,
+                                                          self.colour_weight, Tc.ctypes.data, res2.ctypes.data, inl2.ctypes.data))
+                self.last_error, self.last_inliers = float(res2[0]), float(inl2[0])
+                self.last_colour_error, self.last_colour_inliers = float(res2[1]), float(inl2[1])   # sum of e^2, colour inliers
+            else:
+                res, inl = C.c_float(), C.c_float()
+                check(lib.tsdf_tracker_align_field(self._h, kinv.ctypes.data, Tc.ctypes.data, C.byref(res), C.byref(inl)))
+                self.last_error, self.last_inliers = float(res.value), float(inl.value)   # sum of squared distances (mm^2), inliers
+                self.last_colour_error, self.last_colour_inliers = 0.0, 0.0               # (a frame without rgb, or weight 0: no colour term)
             self.last_T = None
-            self.last_error, self.last_inliers = float(res.value), float(inl.value)   # sum of squared distances (mm^2), inliers
             self.camera.set_pose_rows(Tc.reshape(4, 4).T.copy())
         else:
             prev = _matrices(self.camera)
