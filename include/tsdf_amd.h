@@ -160,6 +160,16 @@ int tsdf_selftest_bilateral_chain_taps(size_t n, const float *w, const uint32_t 
                                        uint8_t *certified);
 int tsdf_selftest_bilateral_chain_image(float sigma_colour, float sigma_space, const void *image, int bits_per_pixel, int width, int height,
                                         void *filtered, unsigned long long counts[4]);
+/* Self-test of the pixel boxes of the cell-parallel ray cast (cell_boxes.hpp: which pixels a mixed cell can be seen by -- a bound, whose
+ * arithmetic is chosen for speed and has to err on the wide side).  Runs on the host, with the very expressions the kernel compiles, and
+ * needs no GPU.  r = rows 1-3 of world -> camera (3 x 4), k = rows 1-2 of the intrinsics (2 x 3), grid = voxels per axis; z_clip and
+ * z_near as the cast chooses them (no sample of the view is nearer than z_clip; in front of z_near > 0 a cell takes the fast bound).
+ * For each of n cells (the lower voxel's coordinates, 3 per cell, each + 1 below the grid's size): boxes = {u0, v0, width, height}
+ * (zeros when no pixel sees the cell) and seen = 1 when some pixel does, + 2 when the cell took the corners' bound (at or behind z_near;
+ * corners_only != 0 asks for it everywhere). */
+int tsdf_selftest_cell_boxes(const float *r, const float *k, const float *voxel_size, const float *offset, const uint32_t *grid,
+                             uint32_t width, uint32_t height, float z_clip, float z_near, size_t n, const uint32_t *cells, int corners_only,
+                             int32_t *boxes, uint8_t *seen);
 int tsdf_volume_deformation(tsdf_volume *volume, tsdf_deformation_node **device_ptr);
 /* Replace set_distance_data/set_weight_data/set_deformation (src/TSDF/TSDFVolume.cu:731-757):
  * blocking H2D of every resident voxel. */

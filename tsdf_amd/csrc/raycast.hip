@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "raycast_sample.hpp"
 #include "field_sample.hpp"
+#include "cell_boxes.hpp"
 
 namespace tsdf {
 
@@ -358,7 +359,7 @@ __device__ inline SkipCtx make_skip_ctx(const Geom &g, float step_size) {
     sc.inv_step = __builtin_amdgcn_rcpf(step_size);
     // guard band at the cell faces: the dual-cell index computed approximately (coordinates up to max(X,Y,Z) voxels, a
     // handful of roundings of 2^-24 relative each) must agree with the reference's exact one
-    sc.eps = fmaxf(1.0e-3f, 2.0e-6f * (float)max(g.X, max(g.Y, g.Z)));
+    sc.eps = cell_guard_eps(g.X, g.Y, g.Z);
     sc.tx = sc.ty = sc.tz = INFINITY;
     sc.su = sc.sv = sc.sw = INFINITY;
     sc.posx = sc.posy = sc.posz = 1.0f;
@@ -1397,6 +1398,40 @@ int tsdf_volume_cast_rays_colour(const tsdf_volume *cv, uint64_t n, const float 
     if (n == 0) return TSDF_OK;
     return cast_rays_host(const_cast<tsdf_volume *>(cv), n, host_origins, host_directions, host_t_max, host_points, host_t, host_normals,
                           host_rgb);
+}
+
+// ---- the cells' pixel boxes on the host (include/tsdf_amd.h, "self-tests") ----------------------------------------------------------
+int tsdf_selftest_cell_boxes(const float *r, const float *k, const float *voxel_size, const float *offset, const uint32_t *grid,
+                             uint32_t width, uint32_t height, float z_clip, float z_near, size_t n, const uint32_t *cells, int corners_only,
+                             int32_t *boxes, uint8_t *seen) {
+    TSDF_REQUIRE(r && k && voxel_size && offset && grid && cells && boxes && seen, "tsdf_selftest_cell_boxes: null pointer");
+    TSDF_REQUIRE(width >= 1 && height >= 1 && grid[0] >= 2 && grid[1] >= 2 && grid[2] >= 2, "tsdf_selftest_cell_boxes: empty image or grid");
+    TSDF_REQUIRE(z_near > 0.0f && z_near >= z_clip && z_clip >= 0.0f, "tsdf_selftest_cell_boxes: 0 <= z_clip <= z_near, 0 < z_near");
+    EntryParams ep{};
+    for (int j = 0; j < 3; j++)
+        for (int a = 0; a < 4; a++) ep.r[j][a] = r[4 * j + a];
+    for (int j = 0; j < 2; j++)
+        for (int a = 0; a < 3; a++) ep.k[j][a] = k[3 * j + a];
+    ep.vs = {voxel_size[0], voxel_size[1], voxel_size[2]};
+    ep.offset = {offset[0], offset[1], offset[2]};
+    ep.width = width;
+    ep.height = height;
+    ep.z_clip = z_clip;
+    ep.z_near = z_near;
+    CellBoxConsts c;
+    cell_box_consts(c, ep, voxel_size[0], voxel_size[1], voxel_size[2], grid[0], grid[1], grid[2], cell_guard_eps(grid[0], grid[1], grid[2]));
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t lx = cells[3 * i], ly = cells[3 * i + 1], lz = cells[3 * i + 2];
+        TSDF_REQUIRE(lx + 1u < grid[0] && ly + 1u < grid[1] && lz + 1u < grid[2], "tsdf_selftest_cell_boxes: cell %zu is not a cell of the grid", i);
+        PixelBox pb = {0, 0, 0, 0};
+        bool near = true, any = false;
+        if (!corners_only) any = cell_box_front(c.fast, lx, ly, lz, pb, near);
+        if (near) any = cell_box_near(c, lx, ly, lz, pb);
+        if (!any) pb = {0, 0, 0, 0};
+        boxes[4 * i] = pb.u0; boxes[4 * i + 1] = pb.v0; boxes[4 * i + 2] = pb.w; boxes[4 * i + 3] = pb.h;
+        seen[i] = (uint8_t)((any ? 1 : 0) | (near ? 2 : 0));
+    }
+    return TSDF_OK;
 }
 
 }  // extern "C"

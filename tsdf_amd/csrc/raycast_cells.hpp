@@ -70,81 +70,7 @@ __device__ inline uint32_t depth_bin(const CellCast &cc, const EntryParams &ep, 
 constexpr uint32_t kMaxParts = 1024, kPartsRoom = 1024;
 __host__ __device__ inline size_t cell_list_capacity(size_t n_bricks) { return n_bricks + (size_t)kPartsRoom * ((n_bricks + 1023) / 1024); }
 
-// pixel box of the axis-aligned box [lo, hi] (grid millimetres) under the view's projection: false = no pixel can see it.
-// A sample's camera depth is its ray parameter t >= z_clip >= 0 (the last row of kinv is (0, 0, 1): view_projection; z_clip > 0 when
-// the camera is outside the volume, choose_cell_cast): only the part of the box with depth D >= z_clip can hold samples.
-//   * wholly behind that plane: none;
-//   * wholly in front of z_near > 0: the integers inside the hull of its 8 projected corners;
-//   * otherwise (the box straddles the plane, or comes within a quarter voxel of the camera plane): u = N(P) / D(P), N and D affine in
-//     P, so for any u*, u - u* = F(P) / D(P) with F = N - u* D affine too: over the box F lies in [F_c - h, F_c + h] (its value at the
-//     centre -+ half the sum of its coefficients along the box's edges) and D in (max(z_min, z_clip), z_max].  F_c - h > 0: the box is
-//     to the right of u* for every sample in it, by at least (F_c - h) / z_max; F_c + h < 0: to the left; the far side is bounded by
-//     the nearest depth when that is positive, not at all otherwise (a box that holds the camera asks every pixel).  u* = the image's
-//     centre: a box beside or behind the camera that reaches across the camera plane lies far off the image and is dropped here.
-struct PixelBox {
-    int u0, v0, w, h;
-};
-template <bool HULL = true>   // (false: the bound from the centre only -- wider in front of z_near, where the cells' kernel has its own)
-__device__ inline bool project_box(const EntryParams &ep, float lox, float loy, float loz, float hix, float hiy, float hiz, PixelBox &pb) {
-    const float mx = 0.5f * (lox + hix) + ep.offset.x, my = 0.5f * (loy + hiy) + ep.offset.y, mz = 0.5f * (loz + hiz) + ep.offset.z;
-    const float ccx = ep.r[0][0] * mx + ep.r[0][1] * my + ep.r[0][2] * mz + ep.r[0][3];
-    const float ccy = ep.r[1][0] * mx + ep.r[1][1] * my + ep.r[1][2] * mz + ep.r[1][3];
-    const float ccz = ep.r[2][0] * mx + ep.r[2][1] * my + ep.r[2][2] * mz + ep.r[2][3];
-    const float ext[3] = {hix - lox, hiy - loy, hiz - loz};
-    const float hz = 0.5f * ((fabsf(ep.r[2][0] * ext[0]) + fabsf(ep.r[2][1] * ext[1])) + fabsf(ep.r[2][2] * ext[2]));
-    // (the centre's coordinates are good to a few ulps of the largest term: 1e-5 of the camera's distance covers it with room)
-    const float zslack = 1.0e-5f * (((fabsf(ep.r[2][0] * mx) + fabsf(ep.r[2][1] * my)) + fabsf(ep.r[2][2] * mz)) + fabsf(ep.r[2][3])) + 1.0e-5f * hz;
-    const float zmin = ccz - hz - zslack, zmax = ccz + hz + zslack;
-    if (!(ccx == ccx && ccy == ccy && zmin == zmin && zmax == zmax) || fabsf(ccx) == INFINITY || fabsf(ccy) == INFINITY || zmax == INFINITY || zmin == -INFINITY) {
-        pb.u0 = 0; pb.v0 = 0; pb.w = (int)ep.width; pb.h = (int)ep.height;   // (something not finite: every pixel is asked)
-        return true;
-    }
-    if (zmax < ep.z_clip) return false;
-    float a0, a1, b0, b1;
-    const float kMargin = 0.05f;   // (the projection is the double-precision inverse of the matrices the rays are formed with, evaluated in fp32: 1e-2 px at most)
-    if (HULL && zmin > ep.z_near) {
-        float umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            const float wx = ((c & 1) ? hix : lox) + ep.offset.x, wy = ((c & 2) ? hiy : loy) + ep.offset.y, wz = ((c & 4) ? hiz : loz) + ep.offset.z;
-            const float cx = ep.r[0][0] * wx + ep.r[0][1] * wy + ep.r[0][2] * wz + ep.r[0][3];
-            const float cy = ep.r[1][0] * wx + ep.r[1][1] * wy + ep.r[1][2] * wz + ep.r[1][3];
-            const float cz = fmaxf(ep.r[2][0] * wx + ep.r[2][1] * wy + ep.r[2][2] * wz + ep.r[2][3], 0.5f * ep.z_near);
-            const float rz = __builtin_amdgcn_rcpf(cz);   // (a bound, not a result: the margin below covers the last bits)
-            const float u = (ep.k[0][0] * cx + ep.k[0][1] * cy + ep.k[0][2] * cz) * rz, w = (ep.k[1][0] * cx + ep.k[1][1] * cy + ep.k[1][2] * cz) * rz;
-            umin = fminf(umin, u); umax = fmaxf(umax, u);
-            vmin = fminf(vmin, w); vmax = fmaxf(vmax, w);
-        }
-        // a ray exists per INTEGER pixel: the integers inside the hull's box
-        a0 = ceilf(umin - kMargin); a1 = floorf(umax + kMargin); b0 = ceilf(vmin - kMargin); b1 = floorf(vmax + kMargin);
-    } else {
-        const float us = 0.5f * (float)ep.width, vs_ = 0.5f * (float)ep.height;
-        const float dlo = fmaxf(zmin, ep.z_clip), rhi = 1.0f / (zmax * 1.0001f), rlo = dlo > 0.0f ? 1.0001f / dlo : INFINITY;
-        auto side = [&](const float *kr, float centre, float &lo_, float &hi_) {
-            const float t0 = kr[0] * ccx, t1 = kr[1] * ccy, t2 = kr[2] * ccz, t3 = centre * ccz;
-            const float fc = ((t0 + t1) + t2) - t3;
-            float h = 0.0f;
-#pragma unroll
-            for (int a_ = 0; a_ < 3; a_++) {
-                const float ex_ = ep.r[0][a_] * ext[a_], ey_ = ep.r[1][a_] * ext[a_], ez_ = ep.r[2][a_] * ext[a_];
-                h += 0.5f * fabsf(((kr[0] * ex_ + kr[1] * ey_) + kr[2] * ez_) - centre * ez_);
-            }
-            const float slack = 1.0e-5f * ((((fabsf(t0) + fabsf(t1)) + fabsf(t2)) + fabsf(t3)) + h) + (fabsf(kr[0]) + fabsf(kr[1]) + fabsf(kr[2]) + centre) * zslack;
-            const float fmin_ = fc - h - slack, fmax_ = fc + h + slack;
-            lo_ = fmin_ > 0.0f ? fmin_ * rhi : (dlo > 0.0f ? fmin_ * rlo : -INFINITY);
-            hi_ = fmax_ < 0.0f ? fmax_ * rhi : (dlo > 0.0f ? fmax_ * rlo : INFINITY);
-        };
-        float ul, uh, vl, vh;
-        side(ep.k[0], us, ul, uh);
-        side(ep.k[1], vs_, vl, vh);
-        a0 = ceilf(us + ul - kMargin); a1 = floorf(us + uh + kMargin); b0 = ceilf(vs_ + vl - kMargin); b1 = floorf(vs_ + vh + kMargin);
-    }
-    const float wmax = (float)(ep.width - 1u), hmax = (float)(ep.height - 1u);
-    if (!(a0 <= a1 && b0 <= b1) || a1 < 0.0f || b1 < 0.0f || a0 > wmax || b0 > hmax) return false;
-    pb.u0 = (int)fmaxf(a0, 0.0f); pb.v0 = (int)fmaxf(b0, 0.0f);
-    pb.w = (int)fminf(a1, wmax) - pb.u0 + 1; pb.h = (int)fminf(b1, hmax) - pb.v0 + 1;
-    return true;
-}
+// (PixelBox, project_box and the cells' own boxes: cell_boxes.hpp, which the host can run too)
 // inclusive scans over a wave's 64 lanes with data-parallel-primitive operands: four shifts inside a row of 16, then lane 15 of a
 // row into the row behind it and lane 31 into the upper half (row_bcast: a GFX9 form).  A lane without a source keeps the identity 0.
 template <int CTRL, int ROW_MASK>
@@ -547,8 +473,8 @@ __device__ inline void cast_shell_bricks(const float *__restrict__ dist, const G
 
 // One wave per flagged brick; the four waves of a workgroup share the table and nothing else.
 // How many workgroups (TSDF_RAY_CELLS_GRID; round 6, profiles/r06_cells_*): a wave's preamble -- the table, the view's constants, the
-// scalar registers that do not fit parked in vector lanes -- is 300 vector instructions, a brick's turn 630 and a round of 64 pairs
-// 600; a wave per brick (8 192 workgroups, 36 864 waves for 20 000 bricks: round 5) spent a quarter of the kernel's 37.5 M vector
+// scalar registers that do not fit parked in vector lanes -- was 300 vector instructions, a brick's turn 630 and a round of 64 pairs
+// 600 (the turn since the view's constants moved to LDS: 150 for the cells' boxes, profiles/cells_turn_constants.txt); a wave per brick (8 192 workgroups, 36 864 waves for 20 000 bricks: round 5) spent a quarter of the kernel's 37.5 M vector
 // instructions on preambles.  2 048 workgroups (each wave two or three bricks, the next one's voxels requested a turn ahead) is the
 // measured optimum at 512^3 and 256^3: 0.083 -> 0.076 ms; as many waves as the chip holds (1 024) with every n-th entry dealt out in
 // advance ends when its unluckiest wave does (0.080), and the same with the list taken a chunk at a time from eight counters is
@@ -577,13 +503,36 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
     __shared__ float corner[4][128];       // the brick's 5^3 voxels, x fastest
     __shared__ __attribute__((aligned(16))) int box_of[4][64][4];   // per cell lane: its pixel box
     __shared__ int prefix[4][64];          // pairs of the cells before this one
+    __shared__ CellBoxConsts view_c;       // the view, as a brick's turn needs it (cell_boxes.hpp)
 #if TSDF_CELLS_SCAN_DECODE
     __shared__ uint32_t mark[4][64];       // per place in the round's window: (round << 6 | cell) of the cell whose pairs start there
     mark[threadIdx.x >> 6][threadIdx.x & 63u] = 0u;
     uint32_t round = 0u;                   // (a wave's rounds are numbered through: a place written in an earlier round loses the max)
 #endif
     static_assert(kTableLen % 4 == 0, "the table in 16-byte pieces");
-    for (int i = (int)threadIdx.x; i < kTableLen / 4; i += 256) reinterpret_cast<float4 *>(T)[i] = reinterpret_cast<const float4 *>(t_table)[i];
+    // (the table's loads all in flight before the first is waited for -- a load, a wait and a store per turn of a loop was five round
+    // trips in a row in every workgroup -- and the view's block, one thread's arithmetic, formed while they are)
+    constexpr int kTableTurns = (kTableLen / 4 + 255) / 256;
+    float4 table_part[kTableTurns];
+#pragma unroll
+    for (int j = 0; j < kTableTurns; j++) {
+        const int i = (int)threadIdx.x + 256 * j;
+        table_part[j] = reinterpret_cast<const float4 *>(t_table)[min(i, kTableLen / 4 - 1)];   // (every thread a load every turn: the parts stay in registers)
+    }
+    // The pixel box of a cell without projecting its 8 corners (cell_boxes.hpp has the bound).  What it needs of the view is uniform, is
+    // read once per brick and never by a round: it lives in LDS and not in scalar registers for the whole of the kernel -- the compiler
+    // had 150 scalars too many and parked them in vector lanes, a v_readlane at every use.
+    if (blockIdx.x >= kShellWorkgroups && threadIdx.x == 0) cell_box_consts(view_c, ep, g.vs.x, g.vs.y, g.vs.z, g.X, g.Y, g.Z, cell_guard_eps(g.X, g.Y, g.Z));
+#pragma unroll
+    for (int j = 0; j < kTableTurns; j++) {
+        // (the parts are asked for here, behind the block's arithmetic: left to itself the compiler moves every load down to its store)
+        asm volatile("" : "+v"(table_part[j].x), "+v"(table_part[j].y), "+v"(table_part[j].z), "+v"(table_part[j].w));
+    }
+#pragma unroll
+    for (int j = 0; j < kTableTurns; j++) {
+        const int i = (int)threadIdx.x + 256 * j;
+        if (256 * j + 255 < kTableLen / 4 || i < kTableLen / 4) reinterpret_cast<float4 *>(T)[i] = table_part[j];
+    }
     const uint32_t n_bricks = *cc.n_bricks;
     if (cc.n_bricks_host && blockIdx.x == 0 && threadIdx.x == 0) *cc.n_bricks_host = n_bricks;
     static_assert(sizeof(box_of) >= 256 * sizeof(uint2), "a shell workgroup's list of bricks");
@@ -598,21 +547,7 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
     const SkipCtx sc = make_skip_ctx(g, step_size);
     const float e = sc.eps;
     const size_t plane = (size_t)g.X * g.Y;
-    // The pixel box of a cell without projecting its 8 corners.  u = N(P) / D(P), N and D affine in P, D the camera depth: for P in the
-    // (grown) cell |u(P) - u(centre)| = |N(P) - u_c D(P)| / D(P) <= S / D_min, S = half the sum over the axes of |the coefficient of
-    // N - u_c D along the cell's edge| -- the edges are the same for every cell: uniform registers.
-    const float ex = (1.0f + 2.0f * e) * g.vs.x, ey = (1.0f + 2.0f * e) * g.vs.y, ez = (1.0f + 2.0f * e) * g.vs.z;
-    float nu_[3], nv_[3], nz_[3];
-#pragma unroll
-    for (int a_ = 0; a_ < 3; a_++) {
-        const float ext = a_ == 0 ? ex : a_ == 1 ? ey : ez;
-        const float cxa = ep.r[0][a_] * ext, cya = ep.r[1][a_] * ext, cza = ep.r[2][a_] * ext;
-        nu_[a_] = ep.k[0][0] * cxa + ep.k[0][1] * cya + ep.k[0][2] * cza;
-        nv_[a_] = ep.k[1][0] * cxa + ep.k[1][1] * cya + ep.k[1][2] * cza;
-        nz_[a_] = cza;
-    }
-    const float half_dz = 0.5f * ((fabsf(nz_[0]) + fabsf(nz_[1])) + fabsf(nz_[2]));
-    __syncthreads();   // (the table; from here on the four waves go their own ways: every other array is a wave's own)
+    __syncthreads();   // (the table, the view's block; from here on the four waves go their own ways: every other array is a wave's own)
     // LDS traffic inside one wave is in program order; the fence keeps the compiler from moving a lane's read above another lane's write
     auto wave_sync = [] {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -659,6 +594,11 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
         wave_sync();   // (the previous turn's readers of corner / box_of / prefix)
         corner[wave][lane] = va;
         corner[wave][lane + 64u] = vb;
+        // the view's five rows, every lane the same address: in flight while the wave waits for its voxels' writes anyway, and dead
+        // again before the first round
+        CellBoxFast bf;
+#pragma unroll
+        for (int i = 0; i < 5; i++) reinterpret_cast<float4 *>(&bf)[i] = reinterpret_cast<const float4 *>(&view_c.fast)[i];
         wave_sync();
         // ---- the brick's mixed cells, one per lane ----
         const uint32_t cx = lane & 3u, cy = (lane >> 2) & 3u, cz = lane >> 4;
@@ -673,30 +613,9 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
         }
         PixelBox pb = {0, 0, 0, 0};
         if (mixed) {
-            // the cell's centre (voxel centres lx + 1/2 .. lx + 3/2) in the camera's frame
-            const float wx = ((float)lx + 1.0f) * g.vs.x + ep.offset.x, wy = ((float)ly + 1.0f) * g.vs.y + ep.offset.y, wz = ((float)lz + 1.0f) * g.vs.z + ep.offset.z;
-            const float ccx = ep.r[0][0] * wx + ep.r[0][1] * wy + ep.r[0][2] * wz + ep.r[0][3];
-            const float ccy = ep.r[1][0] * wx + ep.r[1][1] * wy + ep.r[1][2] * wz + ep.r[1][3];
-            const float ccz = ep.r[2][0] * wx + ep.r[2][1] * wy + ep.r[2][2] * wz + ep.r[2][3];
-            const float zmin = ccz - half_dz;
-            if (zmin > ep.z_near) {
-                const float rz = __builtin_amdgcn_rcpf(ccz), rm = __builtin_amdgcn_rcpf(zmin);
-                const float uc = (ep.k[0][0] * ccx + ep.k[0][1] * ccy + ep.k[0][2] * ccz) * rz, vc = (ep.k[1][0] * ccx + ep.k[1][1] * ccy + ep.k[1][2] * ccz) * rz;
-                const float su = 0.5f * ((fabsf(nu_[0] - uc * nz_[0]) + fabsf(nu_[1] - uc * nz_[1])) + fabsf(nu_[2] - uc * nz_[2]));
-                const float sv = 0.5f * ((fabsf(nv_[0] - vc * nz_[0]) + fabsf(nv_[1] - vc * nz_[1])) + fabsf(nv_[2] - vc * nz_[2]));
-                // (a ray exists per INTEGER pixel; 0.05 px over the fp32 evaluation: coordinates < 2^16, reciprocals to an ulp)
-                const float hu = su * rm * 1.0001f + 0.05f, hv = sv * rm * 1.0001f + 0.05f;
-                const float a0 = fmaxf(ceilf(uc - hu), 0.0f), a1 = fminf(floorf(uc + hu), (float)(ep.width - 1u));
-                const float b0 = fmaxf(ceilf(vc - hv), 0.0f), b1 = fminf(floorf(vc + hv), (float)(ep.height - 1u));
-                mixed = a0 <= a1 && b0 <= b1;   // (false also for anything not a number)
-                if (mixed) { pb.u0 = (int)a0; pb.v0 = (int)b0; pb.w = (int)a1 - (int)a0 + 1; pb.h = (int)b1 - (int)b0 + 1; }
-            } else {
-                // at or behind the plane in front of which the view's samples lie: the 8 corners, the part in front of the plane
-                const float clx = ((float)lx + 0.5f - e) * g.vs.x, chx = ((float)lx + 1.5f + e) * g.vs.x;
-                const float cly = ((float)ly + 0.5f - e) * g.vs.y, chy = ((float)ly + 1.5f + e) * g.vs.y;
-                const float clz = ((float)lz + 0.5f - e) * g.vs.z, chz = ((float)lz + 1.5f + e) * g.vs.z;
-                mixed = project_box<false>(ep, clx, cly, clz, chx, chy, chz, pb);
-            }
+            bool near;
+            mixed = cell_box_front(bf, lx, ly, lz, pb, near);
+            if (near) mixed = cell_box_near(view_c, lx, ly, lz, pb);   // (its constants from the block where it is taken: all but never)
         }
         if (lane == 0) { RAY_MIX(32); }
         if (mixed) { RAY_MIX(33); }
