@@ -170,6 +170,14 @@ int tsdf_selftest_bilateral_chain_image(float sigma_colour, float sigma_space, c
 int tsdf_selftest_cell_boxes(const float *r, const float *k, const float *voxel_size, const float *offset, const uint32_t *grid,
                              uint32_t width, uint32_t height, float z_clip, float z_near, size_t n, const uint32_t *cells, int corners_only,
                              int32_t *boxes, uint8_t *seen);
+/* Self-test of the Gauss-Newton back end that ICP and the field aligners share (gn_solve.hpp: icp_finish_step -- the second stage of the
+ * 29-entry reduction, the unpivoted and the pivoted 6 x 6 LDL^T, the SE3 exponential, T <- exp(x) * T).  One launch of the very kernel
+ * ICP and the plain aligner finish a step with, on sums the caller makes up: partial = n_blocks x 32 floats (a workgroup's 29 sums in
+ * [0, 29): the upper triangle of (A | b) row by row, the residual, the inlier count), 1 <= n_blocks <= 256; the device buffer always has
+ * 256 blocks and those at and past n_blocks hold a large finite value that the kernel has to leave out.  T_in: 4 x 4 column-major;
+ * update != 0: solve and T <- exp(x) * T.  state_out[64]: [0, 16) the pose, [16] residual, [17] inliers, [18, 54) A (float values),
+ * [54, 60) b. */
+int tsdf_selftest_gn_finish(const float *partial, int n_blocks, const double T_in[16], int update, double state_out[64]);
 int tsdf_volume_deformation(tsdf_volume *volume, tsdf_deformation_node **device_ptr);
 /* Replace set_distance_data/set_weight_data/set_deformation (src/TSDF/TSDFVolume.cu:731-757):
  * blocking H2D of every resident voxel. */

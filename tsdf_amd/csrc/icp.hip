@@ -472,4 +472,29 @@ int tsdf_icp_get_incremental_transformation(tsdf_icp *f, double T_prev_curr[16],
     return TSDF_OK;
 }
 
+int tsdf_selftest_gn_finish(const float *partial, int n_blocks, const double T_in[16], int update, double state_out[64]) {
+    TSDF_REQUIRE(partial && T_in && state_out && n_blocks >= 1 && n_blocks <= kIcpBlocks, "tsdf_selftest_gn_finish: 1 .. 256 blocks of sums");
+    // the whole buffer a step leaves, the blocks nobody wrote poisoned: the kernel must not let them into the sums
+    float sums[kIcpBlocks * 32];
+    for (int i = 0; i < kIcpBlocks * 32; i++) sums[i] = i < n_blocks * 32 ? partial[i] : 1.0e30f;
+    double state[kIcpStateDoubles] = {0};
+    std::memcpy(state, T_in, 16 * sizeof(double));
+    float *sums_dev = nullptr;
+    double *state_dev = nullptr;   // [0, 64) in, [64, 128) out
+    hipError_t e = hipMalloc((void **)&sums_dev, sizeof(sums));
+    if (e == hipSuccess) e = hipMalloc((void **)&state_dev, 2 * sizeof(state));
+    if (e == hipSuccess) e = hipMemset(state_dev, 0, 2 * sizeof(state));
+    if (e == hipSuccess) e = hipMemcpy(sums_dev, sums, sizeof(sums), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(state_dev, state, sizeof(state), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_gn_finish(nullptr, state_dev, state_dev + kIcpStateDoubles, sums_dev, n_blocks, update, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(state_out, state_dev + kIcpStateDoubles, sizeof(state), hipMemcpyDeviceToHost);
+    device_free_all(sums_dev, state_dev);
+    if (e != hipSuccess) return hip_fail(e, "tsdf_selftest_gn_finish");
+    return TSDF_OK;
+}
+
 }  // extern "C"
