@@ -1151,6 +1151,76 @@ int tsdf_esdf_sample(const tsdf_esdf *esdf, uint64_t n, const float *host_points
 /* Device bytes the handle holds besides the output array. */
 int tsdf_esdf_scratch_bytes(const tsdf_esdf *esdf, uint64_t *bytes);
 
+/* ---- sparse snapshot (no reference counterpart: the reference saves a volume densely, and cannot load one) ------------------------ */
+/* The state of a whole volume as the bricks that hold anything but what clear() leaves: taken out of the dense arrays on the device,
+ * put back, downloaded and uploaded.  What it is for: checkpoint and resume, rolling back after a lost track, parking a finished
+ * sub-map.  Lossless: every word is carried as its bits.  Opt-in by being called.
+ *   The value (a unique set of bytes, whatever computes it): the grid is X x Y x Z; bricks are 8 x 8 x 8 voxels aligned to multiples
+ *     of 8, nb[a] = ceil(size[a] / 8) per axis, brick id b = bx + by nb[0] + bz nb[0] nb[1].
+ *     fill = the volume's truncation distance when the snapshot is taken.  A voxel is CLEARED iff its distance has exactly the bits of
+ *       fill, its weight is zero -- a packed count of 0; in fp32 storage the bits 0x00000000, so -0.0 and NaN are not cleared -- and,
+ *       when colour is enabled, its colour word is 0.
+ *     A brick is LIVE iff one of its voxels inside the grid is not cleared.  The snapshot holds the live brick ids in ascending order
+ *       and, per brick in list order, 512 distances (fp32, the volume's bits), 512 weights in the volume's own element type when taken
+ *       (uint8 for 8-bit storage, uint16 for 16-bit, the fp32 bits for fp32) and, with colour, 512 colour words {r, g, b, n}.  Voxel
+ *       (lx, ly, lz) of a brick sits at lx + 8 ly + 64 lz; positions of a partial brick beyond the grid hold fill, 0 and 0.
+ *     The handle also records weight_bound (the volume's own upper bound of every count; 0 for fp32), the geometry (size, voxel size,
+ *       current offset) and fill.
+ *   tsdf_volume_snapshot writes nothing of the volume: no distance, weight, storage mode, occupancy flag, dirty mark, prepared cull or
+ *     ray-cast state.  It enqueues on the volume's stream and synchronises once, to learn n_bricks and size the arrays.  The handle keeps
+ *     its arrays and scratch between calls and only grows them: a warm handle that is large enough allocates nothing.  Scratch beyond
+ *     the four arrays: 8 bytes a brick of the grid and 16 bytes per 1024 bricks (tsdf_snapshot_scratch_bytes).
+ *   tsdf_volume_restore: afterwards every accessor reports the state the volume had when the snapshot was taken, bit for bit; voxels
+ *     of bricks that are not stored get fill, weight 0 and colour 0.  The grid size must equal the snapshot's.  Header fields, offsets,
+ *     offset_at_clear, the weight cap, the stream and attachments are not touched (a caller who wants the snapshot's offset sets it).
+ *     Weight storage: an unpinned volume ends in the wider of its present mode and the snapshot's weight_bits, a pinned one stays fp32;
+ *     counts are converted exactly, never narrowed; weight_bound becomes the snapshot's.  A snapshot with colour enables colour on the
+ *     volume, one without zeroes an enabled colour array.  The occupancy flags are rebuilt from everything before the next ray cast and
+ *     a prepared brick list is discarded, as after tsdf_volume_set_distance_data and tsdf_volume_set_weight_data.  Asynchronous on the
+ *     volume's stream unless the storage has to change.
+ *   Stream order: the handle records an event behind whatever was enqueued last on it; tsdf_snapshot_get_info, tsdf_snapshot_download
+ *     and tsdf_snapshot_buffers wait for it, a snapshot or restore from a volume on another stream orders itself behind it.  A handle
+ *     is used by one thread at a time, on the device it was made on.
+ *   tsdf_snapshot_upload: the host arrays of a download (or of a file) into a handle.  From info it takes size, flags, weight_bits,
+ *     fill_distance, voxel_size, offset and n_bricks; for counts it sets weight_bound to the largest weight in the array.  Checked on
+ *     the host before a device is touched: sizes in 1 .. 65535, weight_bits 8, 16 or 32, n_bricks at most the brick count, ids strictly
+ *     ascending and below the brick count.
+ *   Refused (TSDF_ERR_INVALID, with a message naming the function): NULL arguments (host_colours / device_colours results aside when
+ *     there is no colour); flags other than 0; a Z-slab volume; a materialised deformation-node array; restore into a grid of another
+ *     size; restore, download or buffers from a handle that was never filled.  tsdf_snapshot_destroy(NULL) is ignored.
+ *   Out of scope: shifting bricks on restore, a box of the grid, merging into live data (tsdf_volume_fuse), Z-slabs, deformation
+ *     nodes, compression, incremental snapshots. */
+typedef struct tsdf_snapshot tsdf_snapshot;
+#define TSDF_SNAPSHOT_BRICK 8
+#define TSDF_SNAPSHOT_COLOUR 1u            /* info.flags: colour words are carried */
+typedef struct tsdf_snapshot_info {
+    uint32_t size[3];
+    uint32_t bricks[3];
+    uint32_t flags;
+    uint32_t weight_bits;                  /* 8, 16 or 32 */
+    uint32_t weight_bound;
+    float fill_distance;
+    float voxel_size[3];
+    float offset[3];
+    uint64_t n_bricks;
+    uint64_t bytes;                        /* device bytes of the id, distance, weight and colour arrays */
+} tsdf_snapshot_info;                      /* 80 bytes, n_bricks at 64 */
+int tsdf_snapshot_create(tsdf_snapshot **out);   /* on the current device */
+void tsdf_snapshot_destroy(tsdf_snapshot *snapshot);
+int tsdf_volume_snapshot(const tsdf_volume *volume, uint32_t flags, tsdf_snapshot *snapshot);   /* flags: 0 */
+int tsdf_volume_restore(tsdf_volume *volume, const tsdf_snapshot *snapshot);
+int tsdf_snapshot_get_info(const tsdf_snapshot *snapshot, tsdf_snapshot_info *info);
+/* The device arrays (NULL for an empty snapshot, device_colours also without colour); valid until the handle is filled again. */
+int tsdf_snapshot_buffers(const tsdf_snapshot *snapshot, const uint32_t **device_bricks, const float **device_distances,
+                          const void **device_weights, const uint32_t **device_colours);
+/* Blocking copies: n_bricks ids, and 512 n_bricks distances, weights (weight_bits / 8 bytes each) and colour words. */
+int tsdf_snapshot_download(const tsdf_snapshot *snapshot, uint32_t *host_bricks, float *host_distances, void *host_weights,
+                           uint32_t *host_colours);
+int tsdf_snapshot_upload(tsdf_snapshot *snapshot, const tsdf_snapshot_info *info, const uint32_t *host_bricks,
+                         const float *host_distances, const void *host_weights, const uint32_t *host_colours);
+/* Device bytes the handle holds besides the four arrays. */
+int tsdf_snapshot_scratch_bytes(const tsdf_snapshot *snapshot, uint64_t *bytes);
+
 /* Multi-GPU raycast: a slab evaluates only the samples whose lower trilinear tap plane it owns and writes
  * one 8-byte record per pixel: k = index of the first owned sample with tsdf <= 0 (TSDF_NO_HIT if none), t = that sample's
  * refined ray parameter (src/RayCaster/GPURaycaster.cu:338-341).  After an all-gather of the records (layout

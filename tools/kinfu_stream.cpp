@@ -8,7 +8,9 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE]
+//   --save-sparse FILE: at the end of the run the volume's live bricks and header as a .tsdfs file (TSDFVolume::save_sparse);
+//           the line gains "sparse_file_bytes"; refused with --ranks above 1 (Z-slabs have no snapshot).
 //   --colour-weight W (with --track --field): W > 0 aligns every tracked frame with the colour term as well (tsdf_tracker_align_field_colour:
 //           the frame's rgb picture as intensities, colour gate 64, weight W in mm^2 per intensity^2); implies --colour; refused
 //           without --field, and when W is negative or not finite; the line gains "colour_weight": W and the colour term's inliers.
@@ -63,6 +65,7 @@
 #include "Camera.hpp"
 #include "DepthImage.hpp"
 #include "TUMDataLoader.hpp"
+#include "TSDFVolume.hpp"
 #include "tsdf_amd.h"
 
 static void ok(int rc, const char *what) {
@@ -117,8 +120,18 @@ static int shm_all_gather(void *user, const tsdf_hit_record *device_mine, tsdf_h
     return TSDF_OK;
 }
 
+// --save-sparse: the volume as a .tsdfs file; returns the file's length (the run ends when it cannot be written)
+static long long save_sparse_file(const tsdf_volume *vol, const std::string &file_name) {
+    if (!TSDFVolume::save_sparse(vol, file_name)) {
+        std::fprintf(stderr, "kinfu_stream: --save-sparse %s failed\n", file_name.c_str());
+        std::exit(1);
+    }
+    std::ifstream f(file_name, std::ios::binary | std::ios::ate);
+    return (long long)f.tellg();
+}
+
 int main(int argc, char **argv) {
-    std::string dir, dump_dir;
+    std::string dir, dump_dir, sparse_file;
     int ranks = 1;
     bool share_gpu = false;
     unsigned n = 512;
@@ -156,12 +169,13 @@ int main(int argc, char **argv) {
         else if (a == "--colour") colour = true;
         else if (a == "--weight-cap") weight_cap = std::atol(value());
         else if (a == "--window") window = std::atol(value());
+        else if (a == "--save-sparse") sparse_file = value();
         else if (a == "--colour-weight") {
             colour_weight = std::atof(value());
             colour_weight_given = true;
         }
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE]\n");
             return 2;
         }
     }
@@ -188,6 +202,10 @@ int main(int argc, char **argv) {
             return 2;
         }
         colour = true;   // the colour term reads the fused colours
+    }
+    if (!sparse_file.empty() && ranks > 1) {
+        std::fprintf(stderr, "kinfu_stream: --save-sparse is single-volume (a Z-slab has no snapshot): drop --ranks\n");
+        return 2;
     }
     if (colour && ranks > 1) {
         std::fprintf(stderr, "kinfu_stream: --colour is single-volume (colour is not supported on Z-slabs): drop --ranks\n");
@@ -397,6 +415,7 @@ int main(int argc, char **argv) {
         if (window) std::printf(", \"window\": %ld", window);
         if (field) std::printf(", \"align\": \"field\"");
         if (colour_weight_given) std::printf(", \"colour_weight\": %g, \"last_colour_inliers\": %.0f", colour_weight, colour_inliers);
+        if (!sparse_file.empty()) std::printf(", \"sparse_file_bytes\": %lld", save_sparse_file(vol, sparse_file));
         std::printf(colour ? ", \"colour\": true}\n" : "}\n");
         if (!dump_dir.empty()) {
             dump(dump_dir + "/poses.f32", tracked.data(), tracked.size() * sizeof(float));
@@ -502,6 +521,7 @@ int main(int argc, char **argv) {
                     n, planes, W, H, F, K, Wu, overlap ? "true" : "false", cull_ahead ? "true" : "false", ms, voxels * K / elapsed / 1e6, bits_v, bits_n, hits);
         if (colour) std::printf(", \"colour\": true, \"last_frame_colour_bits\": %lld", bits_c);
         if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
+        if (!sparse_file.empty()) std::printf(", \"sparse_file_bytes\": %lld", save_sparse_file(vol, sparse_file));
         std::printf("}\n");
     }
 

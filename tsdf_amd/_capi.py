@@ -18,6 +18,7 @@ TSDF_MESH_KEEP_LARGEST = 1
 TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
 TSDF_SCENE_FLOW_DEFORMED = 1
+TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
 
 
 class TsdfError(RuntimeError):
@@ -55,6 +56,21 @@ class EsdfInfo(C.Structure):
     """struct tsdf_esdf_info (include/tsdf_amd.h)."""
     _fields_ = [("size", C.c_uint32 * 3), ("flags", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
                 ("max_distance", C.c_float), ("n_sites", C.c_uint64)]
+
+
+class SnapshotInfo(C.Structure):
+    """struct tsdf_snapshot_info (include/tsdf_amd.h)."""
+    _fields_ = [("size", C.c_uint32 * 3), ("bricks", C.c_uint32 * 3), ("flags", C.c_uint32), ("weight_bits", C.c_uint32),
+                ("weight_bound", C.c_uint32), ("fill_distance", C.c_float), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
+                ("n_bricks", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class HostSparseInfo(C.Structure):
+    """struct tsdf_host_sparse_info (tsdf_amd/host/src/host_capi.cpp): the header of a .tsdfs file."""
+    _fields_ = [("size", C.c_uint32 * 3), ("physical_size", C.c_float * 3), ("offset", C.c_float * 3), ("truncation_distance", C.c_float),
+                ("max_weight", C.c_float), ("global_translation", C.c_float * 3), ("global_rotation", C.c_float * 3), ("brick", C.c_uint32),
+                ("flags", C.c_uint32), ("weight_bits", C.c_uint32), ("weight_bound", C.c_uint32), ("fill_distance", C.c_float),
+                ("reserved", C.c_uint32), ("n_bricks", C.c_uint64)]
 
 
 class AlignStage(C.Structure):
@@ -228,6 +244,15 @@ _SIGS = {
     "tsdf_esdf_sample_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _i, _vp]),
     "tsdf_esdf_sample": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _i]),
     "tsdf_esdf_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_snapshot_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_snapshot_destroy": (None, [_vp]),
+    "tsdf_volume_snapshot": (_i, [_vp, _u32, _vp]),
+    "tsdf_volume_restore": (_i, [_vp, _vp]),
+    "tsdf_snapshot_get_info": (_i, [_vp, C.POINTER(SnapshotInfo)]),
+    "tsdf_snapshot_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_snapshot_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tsdf_snapshot_upload": (_i, [_vp, C.POINTER(SnapshotInfo), _vp, _vp, _vp, _vp]),
+    "tsdf_snapshot_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_merge_hits_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_merge_hits_normals_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_slab_exchange_unique_id": (_i, [_vp, C.c_char_p]),
@@ -339,6 +364,7 @@ _HOST_SIGS = {
     "tsdf_host_read_last_line": (C.c_size_t, [C.c_char_p, C.c_char_p, C.POINTER(_i), C.c_char_p, C.c_size_t]),
     "tsdf_host_files_in_directory": (C.c_size_t, [C.c_char_p, C.c_char_p, _i, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "tsdf_host_file_exists": (_i, [C.c_char_p, C.POINTER(_i)]),
+    "tsdf_host_read_sparse_info": (_i, [C.c_char_p, C.POINTER(HostSparseInfo), C.c_char_p, C.c_size_t]),
 }
 for _name, (_res, _args) in _HOST_SIGS.items():
     _fn = getattr(host, _name)

@@ -6,6 +6,8 @@ reference's own.  Matrices are column-major float32 vectors (what Eigen's .data(
 Every call runs the HIP kernels in tsdf_amd/lib/libtsdf_hip.so; there is no CPU path.
 """
 import ctypes as C
+import os
+import struct
 
 import numpy as np
 
@@ -462,6 +464,54 @@ class TSDFVolume:
         esdf = ESDF() if into is None else into
         check(lib.tsdf_volume_compute_esdf(self._h, float(max_distance), _capi.TSDF_ESDF_FILL_UNKNOWN if fill_unknown else 0, esdf._h))
         return esdf
+
+    # ---- sparse snapshots (include/tsdf_amd.h, "sparse snapshot"; not in the reference's class)
+    def _file_header(self):
+        """The fields of the .tsdf header as the volume reports them now."""
+        i = self.info()
+        return {"physical_size": tuple(i.physical_size), "offset": tuple(i.offset), "truncation_distance": float(i.truncation_distance),
+                "max_weight": float(i.max_weight), "global_translation": tuple(i.global_translation),
+                "global_rotation": tuple(i.global_rotation)}
+
+    def snapshot(self, into=None):
+        """The live bricks of the volume -- those of 8^3 voxels that hold anything but what clear() leaves -- as compact device arrays
+        (tsdf_volume_snapshot).  Nothing of the volume is written.  `into`: a Snapshot to reuse -- its arrays are kept and only grow.
+        Returns the Snapshot."""
+        snap = Snapshot() if into is None else into
+        check(lib.tsdf_volume_snapshot(self._h, 0, snap._h))
+        snap.header = self._file_header()
+        return snap
+
+    def restore(self, snapshot):
+        """Put a Snapshot of a grid of this size back (tsdf_volume_restore): every accessor then reports the state the snapshot was
+        taken from, bit for bit.  The offset and the other header fields, the weight cap and the stream are not touched."""
+        check(lib.tsdf_volume_restore(self._h, snapshot._h))
+
+    def save_sparse(self, path):
+        """Write the volume's live bricks and header to a .tsdfs file.  Deformation nodes are not stored."""
+        if self.info().deformation_materialised:
+            raise ValueError("save_sparse: the volume has a materialised deformation-node array, which a .tsdfs file does not carry")
+        snap = self.snapshot()
+        try:
+            snap.save(path)
+        finally:
+            snap.close()
+
+    @classmethod
+    def load_sparse(cls, path):
+        """A new volume of the size, physical size and header of a .tsdfs file, holding its state."""
+        snap = Snapshot.load(path)
+        try:
+            h = snap.header
+            vol = cls(size=tuple(int(v) for v in snap.info.size), physical_size=h["physical_size"])
+            f3 = lambda v: _fp(np.array(v, np.float32))
+            check(lib.tsdf_volume_set_header(vol._h, f3(h["offset"]), h["truncation_distance"], h["max_weight"], f3(h["global_translation"]),
+                                             f3(h["global_rotation"])))
+            vol.restore(snap)
+            vol.synchronize()
+        finally:
+            snap.close()
+        return vol
 
     # ---- ray queries (include/tsdf_amd.h, "ray queries"; not in the reference's class)
     def cast_rays_device(self, n, origins_ptr, directions_ptr, t_max_ptr, points_ptr, t_ptr, normals_ptr, colours_ptr=None):
@@ -1086,6 +1136,202 @@ class ESDF:
         n = C.c_uint64(0)
         check(lib.tsdf_esdf_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
+
+
+SPARSE_MAGIC = b"TSDFSPR1"
+_SPARSE_HEADER = "<3I3f3fff3f3f" "IIIIfIQ"   # the 68-byte header of .tsdf, then brick, flags, weight_bits, weight_bound, fill, 0, n_bricks
+_WEIGHT_DTYPES = {8: np.uint8, 16: np.uint16, 32: np.float32}
+
+
+def _check_snapshot_layout(who, size, weight_bits, n_bricks):
+    """What tsdf_snapshot_upload checks of a header, without a device; returns the grid's brick count."""
+    if not all(1 <= int(s) <= 65535 for s in size):
+        raise ValueError("%s: size %s is not in 1 .. 65535" % (who, tuple(int(s) for s in size)))
+    if weight_bits not in _WEIGHT_DTYPES:
+        raise ValueError("%s: weight_bits = %d is not 8, 16 or 32" % (who, weight_bits))
+    total = 1
+    for s in size:
+        total *= (int(s) + 7) // 8
+    if n_bricks > total:
+        raise ValueError("%s: n_bricks = %d, the grid has %d bricks" % (who, n_bricks, total))
+    return total
+
+
+def _check_snapshot_ids(who, ids, total):
+    if len(ids) and (int(ids[-1]) >= total or np.any(ids[1:] <= ids[:-1])):
+        raise ValueError("%s: brick ids are not strictly ascending and below the brick count %d" % (who, total))
+
+
+def write_sparse_file(path, size, header, weight_bound, fill_distance, ids, distances, weights, colours=None):
+    """Write a .tsdfs file from host arrays (what Snapshot.download() returns); nothing is checked and no device is touched.
+    `header`: the .tsdf fields physical_size, offset, truncation_distance, max_weight, global_translation, global_rotation."""
+    weights = np.asarray(weights)
+    bits = 8 * weights.dtype.itemsize
+    with open(path, "wb") as f:
+        f.write(SPARSE_MAGIC)
+        f.write(struct.pack(_SPARSE_HEADER, *(int(s) for s in size), *header["physical_size"], *header["offset"], header["truncation_distance"],
+                            header["max_weight"], *header["global_translation"], *header["global_rotation"], _capi.TSDF_SNAPSHOT_BRICK,
+                            _capi.TSDF_SNAPSHOT_COLOUR if colours is not None else 0, bits, int(weight_bound), float(fill_distance), 0, len(ids)))
+        for a, dtype in ((ids, np.uint32), (distances, np.float32), (weights, weights.dtype), (colours, np.uint32)):
+            if a is not None:
+                np.ascontiguousarray(a, np.dtype(dtype).newbyteorder("<")).tofile(f)
+
+
+def read_sparse_file(path):
+    """Parse and validate a .tsdfs file without touching a device: (header dict, SnapshotInfo, ids, distances, weights, colours or
+    None).  The magic, the brick size, the sizes, weight_bits, n_bricks against the grid and the file's length against what the header
+    implies are checked before anything is allocated; then the ids (strictly ascending, below the brick count).  ValueError otherwise."""
+    who = "read_sparse_file(%s)" % path
+    n_head = len(SPARSE_MAGIC) + struct.calcsize(_SPARSE_HEADER)
+    length = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(n_head)
+        if len(head) < n_head or head[:8] != SPARSE_MAGIC:
+            raise ValueError("%s: not a .tsdfs file (magic %r, %d bytes)" % (who, head[:8], length))
+        v = struct.unpack(_SPARSE_HEADER, head[8:])
+        size, brick, flags, weight_bits, weight_bound, fill, n_bricks = v[0:3], v[17], v[18], v[19], v[20], v[21], v[23]
+        if brick != _capi.TSDF_SNAPSHOT_BRICK:
+            raise ValueError("%s: brick size %d, expected %d" % (who, brick, _capi.TSDF_SNAPSHOT_BRICK))
+        if flags & ~_capi.TSDF_SNAPSHOT_COLOUR:
+            raise ValueError("%s: unknown flags %#x" % (who, flags))
+        total = _check_snapshot_layout(who, size, weight_bits, n_bricks)
+        colour = bool(flags & _capi.TSDF_SNAPSHOT_COLOUR)
+        expect = n_head + n_bricks * (4 + 512 * (4 + weight_bits // 8 + (4 if colour else 0)))
+        if length != expect:
+            raise ValueError("%s: the file has %d bytes, its header implies %d" % (who, length, expect))
+        ids = np.fromfile(f, np.uint32, n_bricks)
+        _check_snapshot_ids(who, ids, total)
+        dist = np.fromfile(f, np.float32, 512 * n_bricks)
+        weights = np.fromfile(f, _WEIGHT_DTYPES[weight_bits], 512 * n_bricks)
+        colours = np.fromfile(f, np.uint32, 512 * n_bricks) if colour else None
+    header = {"physical_size": v[3:6], "offset": v[6:9], "truncation_distance": v[9], "max_weight": v[10], "global_translation": v[11:14],
+              "global_rotation": v[14:17]}
+    info = _capi.SnapshotInfo()
+    info.size[:] = size
+    info.flags, info.weight_bits, info.weight_bound, info.fill_distance, info.n_bricks = flags, weight_bits, weight_bound, fill, n_bricks
+    info.voxel_size[:] = [np.float32(p) / np.float32(s) for p, s in zip(v[3:6], size)]
+    info.offset[:] = v[6:9]
+    return header, info, ids, dist, weights, colours
+
+
+class Snapshot:
+    """tsdf_snapshot (include/tsdf_amd.h, "sparse snapshot"): the live bricks of a volume as compact device arrays -- ids, distances,
+    weights in the volume's own element type, colour words -- with the scratch that fills them, kept between snapshots
+    (TSDFVolume.snapshot(into=snap)).  `header`: the .tsdf header fields that go into a file (set by TSDFVolume.snapshot and load)."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        self.header = None
+        check(lib.tsdf_snapshot_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            lib.tsdf_snapshot_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def info(self):
+        """tsdf_snapshot_info: size, bricks, flags, weight_bits, weight_bound, fill_distance, voxel_size, offset, n_bricks, bytes."""
+        i = _capi.SnapshotInfo()
+        check(lib.tsdf_snapshot_get_info(self._h, C.byref(i)))
+        return i
+
+    @property
+    def n_bricks(self):
+        return int(self.info.n_bricks)
+
+    def download(self):
+        """(ids (n,) uint32, distances (n, 512) float32, weights (n, 512) uint8 / uint16 / float32, colours (n, 512) uint32 or None):
+        one blocking download."""
+        i = self.info
+        n, colour = int(i.n_bricks), bool(i.flags & _capi.TSDF_SNAPSHOT_COLOUR)
+        ids = np.empty(n + 1, np.uint32)   # (one element more: the pointer of an empty array may be null)
+        dist = np.empty((n + 1, 512), np.float32)
+        weights = np.empty((n + 1, 512), _WEIGHT_DTYPES[int(i.weight_bits) or 32])
+        colours = np.empty((n + 1, 512), np.uint32) if colour else None
+        check(lib.tsdf_snapshot_download(self._h, ids.ctypes.data, dist.ctypes.data, weights.ctypes.data, colours.ctypes.data if colour else None))
+        return ids[:n], dist[:n], weights[:n], colours[:n] if colour else None
+
+    @property
+    def bricks(self):
+        return self.download()[0]
+
+    @property
+    def distances(self):
+        return self.download()[1]
+
+    @property
+    def weights(self):
+        return self.download()[2]
+
+    @property
+    def colours(self):
+        return self.download()[3]
+
+    def device_buffers(self):
+        """(ids, distances, weights, colours) as raw device pointers (0 where there is none); valid until the handle is filled again."""
+        p = [C.c_void_p() for _ in range(4)]
+        check(lib.tsdf_snapshot_buffers(self._h, *(C.byref(q) for q in p)))
+        return tuple(int(q.value or 0) for q in p)
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides the four arrays."""
+        n = C.c_uint64(0)
+        check(lib.tsdf_snapshot_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    @classmethod
+    def from_arrays(cls, size, bricks, distances, weights, colours=None, fill_distance=0.0, voxel_size=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0),
+                    header=None, into=None):
+        """A Snapshot from host arrays (tsdf_snapshot_upload): what download() returns, or a file holds.  The element type of `weights`
+        (uint8, uint16 or float32) is the snapshot's weight_bits.  The arrays are checked on the host first."""
+        weights = np.asarray(weights)
+        bits = {np.dtype(np.uint8): 8, np.dtype(np.uint16): 16, np.dtype(np.float32): 32}.get(weights.dtype)
+        if bits is None:
+            raise ValueError("Snapshot.from_arrays: weights must be uint8, uint16 or float32, not %s" % weights.dtype)
+        ids = np.ascontiguousarray(bricks, np.uint32).reshape(-1)
+        n = len(ids)
+        total = _check_snapshot_layout("Snapshot.from_arrays", size, bits, n)
+        _check_snapshot_ids("Snapshot.from_arrays", ids, total)
+        dist = np.ascontiguousarray(distances, np.float32).reshape(-1)
+        weights = np.ascontiguousarray(weights).reshape(-1)
+        col = None if colours is None else np.ascontiguousarray(colours, np.uint32).reshape(-1)
+        for name, a in (("distances", dist), ("weights", weights), ("colours", col)):
+            if a is not None and a.size != 512 * n:
+                raise ValueError("Snapshot.from_arrays: %s has %d elements, expected %d" % (name, a.size, 512 * n))
+        info = _capi.SnapshotInfo()
+        info.size[:] = [int(s) for s in size]
+        info.flags = _capi.TSDF_SNAPSHOT_COLOUR if col is not None else 0
+        info.weight_bits, info.fill_distance, info.n_bricks = bits, float(fill_distance), n
+        info.voxel_size[:] = [float(v) for v in voxel_size]
+        info.offset[:] = [float(v) for v in offset]
+        snap = cls() if into is None else into
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        check(lib.tsdf_snapshot_upload(snap._h, C.byref(info), ptr(ids), ptr(dist), ptr(weights), ptr(col)))
+        snap.header = header
+        return snap
+
+    def save(self, path):
+        """Write a .tsdfs file: little-endian, no padding; "TSDFSPR1", the 68-byte header of .tsdf, brick = 8, flags,
+        weight_bits, weight_bound, fill_distance, 0, n_bricks, then the id, distance, weight and colour arrays.  The .tsdf fields come
+        from `header`; without one they are made from the snapshot's own geometry."""
+        i = self.info
+        size = [int(s) for s in i.size]
+        h = self.header or {"physical_size": tuple(float(np.float32(v) * np.float32(s)) for v, s in zip(i.voxel_size, size)),
+                            "offset": tuple(i.offset), "truncation_distance": float(i.fill_distance), "max_weight": 0.0,
+                            "global_translation": (0.0, 0.0, 0.0), "global_rotation": (0.0, 0.0, 0.0)}
+        ids, dist, weights, colours = self.download()
+        write_sparse_file(path, size, h, int(i.weight_bound), float(i.fill_distance), ids, dist, weights, colours)
+
+    @classmethod
+    def load(cls, path, into=None):
+        """A Snapshot from a .tsdfs file, validated on the host first (read_sparse_file); `header` holds the file's .tsdf fields."""
+        header, info, ids, dist, weights, colours = read_sparse_file(path)
+        return cls.from_arrays(tuple(info.size), ids, dist, weights, colours, fill_distance=info.fill_distance, voxel_size=tuple(info.voxel_size),
+                               offset=tuple(info.offset), header=header, into=into)
 
 
 class _DeviceArray:

@@ -20,6 +20,7 @@
 struct tsdf_volume;  // C-ABI handle (include/tsdf_amd.h)
 struct tsdf_esdf;    // distance-field handle (include/tsdf_amd.h)
 struct tsdf_mesh;    // indexed-mesh handle (include/tsdf_amd.h)
+struct tsdf_snapshot;  // sparse-snapshot handle (include/tsdf_amd.h)
 
 class TSDFVolume {
 public:
@@ -201,6 +202,40 @@ public:
 
     bool save_to_file(const std::string &file_name) const;
     bool load_from_file(const std::string &file_name);
+
+    // Sparse snapshots (include/tsdf_amd.h, "sparse snapshot"; not in the reference's class): the bricks of 8^3 voxels that hold anything
+    // but what clear() leaves, as compact device arrays in a handle that keeps them and its scratch between calls.
+    class Snapshot {
+    public:
+        Snapshot();    // throws std::invalid_argument / exits like every device failure when the handle cannot be made
+        ~Snapshot();
+        Snapshot(const Snapshot &) = delete;
+        Snapshot &operator=(const Snapshot &) = delete;
+        inline tsdf_snapshot *handle() const { return m_handle; }
+        uint64_t n_bricks() const;
+        uint64_t bytes() const;          // of the four device arrays
+        uint32_t weight_bits() const;    // 8, 16 or 32: the element type of the weights
+        bool has_colour() const;
+        // blocking download: n_bricks ids, 512 n_bricks distances, weights (weight_bits / 8 bytes each) and, with colour, colour words
+        void download(std::vector<uint32_t> &bricks, std::vector<float> &distances, std::vector<unsigned char> &weights,
+                      std::vector<uint32_t> &colours) const;
+
+    private:
+        tsdf_snapshot *m_handle;
+    };
+    // Take the live bricks into `into` (nothing of the volume is written) / put the state of `from` back, bit for bit; the header
+    // fields, the offset, the weight cap and the stream are not touched.  Both throw std::invalid_argument on the refusals (a Z-slab,
+    // materialised deformation nodes, a snapshot of a grid of another size, a handle that was never filled).
+    void snapshot(Snapshot &into) const;
+    void restore(const Snapshot &from);
+    // The volume's live bricks and header as a .tsdfs file; false with a message when the volume cannot be saved so
+    // (materialised deformation nodes are not stored) or the file cannot be written.
+    bool save_sparse(const std::string &file_name) const;
+    // the same for a volume held as a C-ABI handle (tools/kinfu_stream.cpp)
+    static bool save_sparse(const tsdf_volume *handle, const std::string &file_name);
+    // The state and header of a .tsdfs file of this volume's grid size; false with a message when the file does not validate (the
+    // checks touch no device) or is of another size.  The volume is unchanged then.
+    bool load_sparse(const std::string &file_name);
 
     // ray cast the zero crossing from `camera`: 3 x (width*height) vertices and normals
     void raycast(uint16_t width, uint16_t height, const Camera &camera,

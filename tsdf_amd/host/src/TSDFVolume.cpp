@@ -10,6 +10,7 @@
 
 #include "GPURaycaster.hpp"
 #include "host_common.hpp"
+#include "SparseFile.hpp"
 
 using tsdf_host::check;
 
@@ -590,4 +591,146 @@ bool TSDFVolume::load_from_file(const std::string &file_name) {
     (void)file_name;
     std::cout << "Not yet implemented: load_from_file" << std::endl;
     return false;
+}
+
+// ---- sparse snapshots (include/tsdf_amd.h, "sparse snapshot")
+TSDFVolume::Snapshot::Snapshot() : m_handle{nullptr} { check(tsdf_snapshot_create(&m_handle), "Couldn't create the snapshot handle"); }
+
+TSDFVolume::Snapshot::~Snapshot() { tsdf_snapshot_destroy(m_handle); }
+
+namespace {
+tsdf_snapshot_info snapshot_info(const tsdf_snapshot *s) {
+    tsdf_snapshot_info info;
+    check(tsdf_snapshot_get_info(s, &info), "Couldn't query the snapshot");
+    return info;
+}
+}  // namespace
+
+uint64_t TSDFVolume::Snapshot::n_bricks() const { return snapshot_info(m_handle).n_bricks; }
+uint64_t TSDFVolume::Snapshot::bytes() const { return snapshot_info(m_handle).bytes; }
+uint32_t TSDFVolume::Snapshot::weight_bits() const { return snapshot_info(m_handle).weight_bits; }
+bool TSDFVolume::Snapshot::has_colour() const { return (snapshot_info(m_handle).flags & TSDF_SNAPSHOT_COLOUR) != 0; }
+
+void TSDFVolume::Snapshot::download(std::vector<uint32_t> &bricks, std::vector<float> &distances, std::vector<unsigned char> &weights,
+                                    std::vector<uint32_t> &colours) const {
+    const tsdf_snapshot_info info = snapshot_info(m_handle);
+    const size_t n = (size_t)info.n_bricks, pad = n ? 0 : 1;   // (an empty vector's pointer may be null)
+    const bool colour = (info.flags & TSDF_SNAPSHOT_COLOUR) != 0;
+    bricks.resize(n + pad);
+    distances.resize(n * 512 + pad);
+    weights.resize(n * 512 * (info.weight_bits / 8) + pad);
+    colours.resize(colour ? n * 512 + pad : 0);
+    check(tsdf_snapshot_download(m_handle, bricks.data(), distances.data(), weights.data(), colour ? colours.data() : nullptr),
+          "Couldn't download the snapshot");
+    bricks.resize(n);
+    distances.resize(n * 512);
+    weights.resize(n * 512 * (info.weight_bits / 8));
+    if (colour) colours.resize(n * 512);
+}
+
+void TSDFVolume::snapshot(Snapshot &into) const { check(tsdf_volume_snapshot(m_handle, 0u, into.handle()), "Couldn't take the snapshot"); }
+
+void TSDFVolume::restore(const Snapshot &from) { check(tsdf_volume_restore(m_handle, from.handle()), "Couldn't restore the snapshot"); }
+
+bool TSDFVolume::save_sparse(const std::string &file_name) const { return save_sparse(m_handle, file_name); }
+
+bool TSDFVolume::save_sparse(const tsdf_volume *handle, const std::string &file_name) {
+    tsdf_volume_info vi;
+    if (!handle || tsdf_volume_get_info(handle, &vi) != TSDF_OK) return false;
+    if (vi.deformation_materialised) {
+        std::cout << "save_sparse: the volume has a materialised deformation-node array, which a .tsdfs file does not carry" << std::endl;
+        return false;
+    }
+    std::vector<uint32_t> ids, colours;
+    std::vector<float> dist;
+    std::vector<unsigned char> weights;
+    tsdf_snapshot_info si;
+    try {
+        Snapshot snap;
+        check(tsdf_volume_snapshot(handle, 0u, snap.handle()), "Couldn't take the snapshot");
+        si = snapshot_info(snap.handle());
+        snap.download(ids, dist, weights, colours);
+    } catch (const std::invalid_argument &e) {
+        std::cout << "save_sparse: " << e.what() << std::endl;
+        return false;
+    }
+    tsdf_host::SparseFileInfo fi;
+    std::memset(&fi, 0, sizeof(fi));
+    for (int a = 0; a < 3; a++) {
+        fi.size[a] = vi.size[a];
+        fi.physical_size[a] = vi.physical_size[a];
+        fi.offset[a] = vi.offset[a];
+        fi.global_translation[a] = vi.global_translation[a];
+        fi.global_rotation[a] = vi.global_rotation[a];
+    }
+    fi.truncation_distance = vi.truncation_distance;
+    fi.max_weight = vi.max_weight;
+    fi.brick = TSDF_SNAPSHOT_BRICK;
+    fi.flags = si.flags;
+    fi.weight_bits = si.weight_bits;
+    fi.weight_bound = si.weight_bound;
+    fi.fill_distance = si.fill_distance;
+    fi.n_bricks = si.n_bricks;
+    unsigned char head[tsdf_host::kSparseHeaderBytes];
+    tsdf_host::pack_sparse_header(fi, head);
+    std::ofstream ofs{file_name, std::ios::out | std::ios::binary};
+    if (!ofs.good()) {
+        std::cout << "save_sparse: couldn't open " << file_name << std::endl;
+        return false;
+    }
+    ofs.write((const char *)head, sizeof(head));
+    ofs.write((const char *)ids.data(), ids.size() * sizeof(uint32_t));
+    ofs.write((const char *)dist.data(), dist.size() * sizeof(float));
+    ofs.write((const char *)weights.data(), weights.size());
+    ofs.write((const char *)colours.data(), colours.size() * sizeof(uint32_t));
+    ofs.close();
+    return ofs.good();
+}
+
+bool TSDFVolume::load_sparse(const std::string &file_name) {
+    tsdf_host::SparseFileInfo fi;
+    std::vector<uint32_t> ids, colours;
+    std::vector<float> dist;
+    std::vector<unsigned char> weights;
+    const std::string why = tsdf_host::read_sparse_file(file_name, fi, &ids, &dist, &weights, &colours);
+    if (!why.empty()) {
+        std::cout << "load_sparse: " << file_name << ": " << why << std::endl;
+        return false;
+    }
+    if (fi.size[0] != m_size.x || fi.size[1] != m_size.y || fi.size[2] != m_size.z) {
+        std::cout << "load_sparse: " << file_name << " holds a " << fi.size[0] << "x" << fi.size[1] << "x" << fi.size[2] << " grid, the volume is "
+                  << m_size.x << "x" << m_size.y << "x" << m_size.z << std::endl;
+        return false;
+    }
+    tsdf_volume_info vi;
+    if (tsdf_volume_get_info(m_handle, &vi) != TSDF_OK) return false;
+    if (vi.deformation_materialised || vi.z_store_begin != 0 || vi.z_store_end != vi.size[2]) {
+        std::cout << "load_sparse: not supported on a Z-slab or a volume with a materialised deformation-node array" << std::endl;
+        return false;
+    }
+    tsdf_snapshot_info si;
+    std::memset(&si, 0, sizeof(si));
+    for (int a = 0; a < 3; a++) {
+        si.size[a] = fi.size[a];
+        si.voxel_size[a] = fi.physical_size[a] / (float)fi.size[a];
+        si.offset[a] = fi.offset[a];
+    }
+    si.flags = fi.flags;
+    si.weight_bits = fi.weight_bits;
+    si.fill_distance = fi.fill_distance;
+    si.n_bricks = fi.n_bricks;
+    try {
+        Snapshot snap;
+        check(tsdf_snapshot_upload(snap.handle(), &si, ids.data(), dist.data(), weights.data(), colours.empty() ? nullptr : colours.data()),
+              "Couldn't upload the snapshot");
+        check(tsdf_volume_set_header(m_handle, fi.offset, fi.truncation_distance, fi.max_weight, fi.global_translation, fi.global_rotation),
+              "Couldn't set the header");
+        restore(snap);
+        check(tsdf_volume_synchronize(m_handle), "Couldn't restore the snapshot");
+    } catch (const std::invalid_argument &e) {
+        std::cout << "load_sparse: " << e.what() << std::endl;
+        return false;
+    }
+    refresh_from_handle();
+    return true;
 }

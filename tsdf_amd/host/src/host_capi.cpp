@@ -13,6 +13,7 @@
 #include "DepthMapUtilities.hpp"
 #include "ply.hpp"
 #include "FileUtilities.hpp"
+#include "SparseFile.hpp"
 #include <string>
 
 const int8_t *tsdf_host_mc_triangle_table();
@@ -94,6 +95,50 @@ int tsdf_host_block_loader_parse(const char *file_name, unsigned size[3], float 
         memcpy(weights, loader.weights().data(), n * sizeof(float));
     }
     return ok ? 1 : 0;
+}
+
+// The header of a .tsdfs file for bindings, parsed and validated by the reader's own step (SparseFile.hpp: no device is touched, and
+// nothing larger than the file is allocated).  0: the file validates and *info holds its header; -1: refused, and `message` (when it
+// holds `capacity` > 0 bytes) says why.  No exception crosses the C ABI.
+typedef struct tsdf_host_sparse_info {
+    uint32_t size[3];
+    float physical_size[3];
+    float offset[3];
+    float truncation_distance;
+    float max_weight;
+    float global_translation[3];
+    float global_rotation[3];
+    uint32_t brick, flags, weight_bits, weight_bound;
+    float fill_distance;
+    uint32_t reserved;
+    uint64_t n_bricks;
+} tsdf_host_sparse_info;
+int tsdf_host_read_sparse_info(const char *file_name, tsdf_host_sparse_info *info, char *message, size_t capacity) {
+    auto say = [&](const std::string &why) {
+        if (message && capacity) {
+            const size_t n = why.size() < capacity - 1 ? why.size() : capacity - 1;
+            memcpy(message, why.data(), n);
+            message[n] = 0;
+        }
+    };
+    try {
+        if (!file_name || !info) {
+            say("tsdf_host_read_sparse_info: null argument");
+            return -1;
+        }
+        static_assert(sizeof(tsdf_host_sparse_info) == sizeof(tsdf_host::SparseFileInfo), "the binding's struct is the reader's");
+        tsdf_host::SparseFileInfo fi;
+        const std::string why = tsdf_host::read_sparse_file(file_name, fi);
+        memcpy(info, &fi, sizeof(fi));
+        say(why);
+        return why.empty() ? 0 : -1;
+    } catch (const std::exception &e) {
+        say(std::string("tsdf_host_read_sparse_info: ") + e.what());
+        return -1;
+    } catch (...) {
+        say("tsdf_host_read_sparse_info: unknown exception");
+        return -1;
+    }
 }
 
 // TUMDataLoader for bindings (bench.py --tum-dir: the frames and poses tools/kinfu_stream.cpp sees, through the same loader).
