@@ -3,23 +3,26 @@
 // association replaced by a trilinear sample: no ray cast, no model maps, no projective association.  No reference counterpart.
 //
 //   * One hot kernel, align_reduce_kernel: per point the pose product (ICP's expression), the field query of field.hip (the ray cast's
-//     trilinear(), the central-difference gradient: seven samples), seven weight reads at the same points (field_sample.hpp), the row
-//     (g, u x g, -d) and its 28 products + the inlier count, summed in icp_accumulate's order: per-thread fp32 over a strided share
-//     of the points, the wave64 shuffle tree, the four waves in a fixed order.  B = min(256, ceil(n / 256)) workgroups.
-//   * The chain is ICP's: every launch first finishes the step before it in every workgroup (icp_finish_step of gn_solve.hpp: second
-//     reduction stage, 6 x 6 solve, T <- exp(x) T, the same bits in every workgroup), the last step gets icp_finish_kernel; the pose
-//     goes in and comes out through a pinned coherent block, so a run is its launches and one synchronise.
+//     trilinear(), the central-difference gradient: seven samples), seven weight reads at the same points (field_sample.hpp) and the row
+//     (g, u x g, -d): align_row.  B = min(256, ceil(n / 256)) workgroups.
+//   * The chain is gn_solve.hpp's, shared with icp.hip: gn_step_begin (every launch first finishes the step before it in every
+//     workgroup: second reduction stage, 6 x 6 solve, T <- exp(x) T, the same bits in every workgroup; align_reduce_kernel alone has
+//     it written out, for its speed), gn_add_row (the 28 products +
+//     the inlier count, per-thread fp32 over a strided share of the points), gn_block_sums (the wave64 shuffle tree, the four waves in
+//     a fixed order), gn_finish_kernel for the last step, and GnChain on the host: the pose goes in and comes out through its pinned
+//     coherent block, so a run is its launches and one synchronise.
 //   * The pose is kept about the centre of the volume's box (the host shifts it in double both ways): the rotation columns of the
 //     normal matrix are u x g, and with u measured from the world origin they would carry the distance to it.
-//   * The colour term (include/tsdf_amd.h, "colour alignment") is a kernel of its own, align_colour_reduce_kernel: align_row, then for a
-//     geometric inlier the intensity of the fused colours in the cell of the distance sample and the exact derivative of that interpolant
-//     (eight colour dwords), the photometric row against the point's observed intensity and a second block of 29 sums in the same
-//     order; 64 floats a workgroup.  Its prologue and align_colour_finish_kernel combine the two blocks (icp_finish_step<true>).
-//     align_reduce_kernel and the plain entry points are what they were.  58 accumulators and two rows: 141 - 148 VGPRs, no scratch.
+//   * The colour term (include/tsdf_amd.h, "colour alignment") is a kernel of its own, align_colour_reduce_kernel: align_row, then for a geometric inlier
+//     the intensity of the fused colours in the cell of the distance sample and the exact derivative of that interpolant (eight colour
+//     dwords), the photometric row against the point's observed intensity (align_colour_row) and a second block of 29 sums in the same
+//     order; 64 floats a workgroup, combined by gn_step_begin<true> / gn_finish_kernel<true>.  58 accumulators and two rows: 141 - 148
+//     VGPRs, no scratch.
 // Nothing of the volume is written.  Per-point arithmetic is separately rounded fp32 (contraction is off).
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "common.hpp"
 #include "gn_solve.hpp"
@@ -28,12 +31,7 @@
 struct tsdf_aligner {
     int device;
     hipStream_t stream;
-    float *partial;        // 2 x kIcpBlocks x 32 floats: per-workgroup sums of the 29 entries (two steps)
-    double *state;         // device, 2 x kIcpStateDoubles, laid out as tsdf_icp's: [0..15] T_c, [16] residual, [17] inliers, [18..53] A, [54..59] b
-    int side;              // which copy of state / partial holds the latest step
-    double *host_io;       // pinned, coherent: [0..15] the pose a chain starts from, [16..35] its result (pose, residual, inliers; the colour term's two behind them)
-    double *host_io_dev;
-    float *partial_c;      // colour alignment: 2 x kIcpBlocks x 64 floats (both blocks of sums), made by the first colour call
+    tsdf::GnChain chain;   // the pose is T_c; the pinned result is 20 doubles wide (the colour term's residual and inliers last)
 };
 
 namespace tsdf {
@@ -46,13 +44,12 @@ struct AlignField {
     float gate;
 };
 
-// The row of one point at the pose (R, t about the pivot); false for an outlier (row then undefined).
+// The row of point x at the pose (R, t about the pivot), and the point there, u; false for an outlier (row then undefined).
 template <bool FASTDIV>
-__device__ inline bool align_row(const float *R, const float *t, float x0, float x1, float x2, const FieldView &f, const AlignField &a,
-                                 float *row) {
-    const float u0 = ((R[0] * x0 + R[3] * x1) + R[6] * x2) + t[0];
-    const float u1 = ((R[1] * x0 + R[4] * x1) + R[7] * x2) + t[1];
-    const float u2 = ((R[2] * x0 + R[5] * x1) + R[8] * x2) + t[2];
+__device__ inline bool align_row(const float *R, const float *t, const float *x, const FieldView &f, const AlignField &a, float *row, float *u) {
+    const float u0 = u[0] = ((R[0] * x[0] + R[3] * x[1]) + R[6] * x[2]) + t[0];
+    const float u1 = u[1] = ((R[1] * x[0] + R[4] * x[1]) + R[7] * x[2]) + t[1];
+    const float u2 = u[2] = ((R[2] * x[0] + R[5] * x[1]) + R[8] * x[2]) + t[2];
     const FieldStencil s = field_stencil(f, u0 + a.h.x, u1 + a.h.y, u2 + a.h.z);
     if (!field_stencil_valid(f, s)) return false;
     // an unobserved neighbourhood holds the cleared distance, not a surface
@@ -78,16 +75,17 @@ __device__ inline bool align_row(const float *R, const float *t, float x0, float
     return true;
 }
 
-// One Gauss-Newton step's sums over `n` points (3 floats each).  `pending` != 0: the launch before left the sums of its
-// `prev_blocks` workgroups in partial_prev and the pose they were taken at in state_in; every workgroup finishes that step first
-// (icp_reduce_kernel's prologue).  ROWS: also the row of every point (seven floats, the NaN row for an outlier) to `rows`: the
-// tests' hook for the per-point arithmetic; the instance without it has none of that code.
+// One Gauss-Newton step's sums over `n` points (3 floats each), behind gn_step_begin's job: `pending` != 0 says that the launch before left
+// the sums of its `prev_blocks` workgroups in partial_prev.  ROWS: also the row of every point (seven floats, the NaN row for an
+// outlier) to `rows`: the tests' hook for the per-point arithmetic; the instance without it has none of that code.
 template <bool FASTDIV, bool ROWS>
 __global__ __launch_bounds__(kIcpThreads) void align_reduce_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
                                                                   const float *__restrict__ partial_prev, int pending, int prev_blocks,
                                                                   const FieldView f, const AlignField a, const uint32_t n,
                                                                   const float *__restrict__ points, float *__restrict__ rows,
                                                                   float *__restrict__ partial) {
+    // gn_step_begin, written out: through the helper this kernel's code differs only before and behind the per-point loop, yet a step
+    // over 300 000 points and more measured 0.7 % slower than before the helper existed, in three visits (LABNOTES.md)
     __shared__ double pose[16];
     if (pending) {
         icp_finish_step(partial_prev, prev_blocks, state_in, 1, pose, blockIdx.x == 0 ? state_out : nullptr);
@@ -98,49 +96,24 @@ __global__ __launch_bounds__(kIcpThreads) void align_reduce_kernel(const double 
         }
     }
     __syncthreads();
-    __shared__ float shared[4][32];
     float R[9], t[3];  // column-major
     for (int c = 0; c < 3; c++)
         for (int r = 0; r < 3; r++) R[c * 3 + r] = (float)pose[c * 4 + r];
     for (int r = 0; r < 3; r++) t[r] = (float)pose[12 + r];
-
     float sum[29];
 #pragma unroll
     for (int i = 0; i < 29; i++) sum[i] = 0.0f;
     const uint32_t stride = (uint32_t)kIcpThreads * gridDim.x;   // <= 65536
     for (uint64_t i = (uint64_t)blockIdx.x * kIcpThreads + threadIdx.x; i < n; i += stride) {
-        float row[7];
-        const bool in = align_row<FASTDIV>(R, t, points[3 * i + 0], points[3 * i + 1], points[3 * i + 2], f, a, row);
+        float row[7], u[3];
+        const bool in = align_row<FASTDIV>(R, t, points + 3 * i, f, a, row, u);
         if (ROWS) {
 #pragma unroll
             for (int k = 0; k < 7; k++) rows[7 * i + k] = in ? row[k] : NAN;
         }
-        if (in) {
-            int s = 0;
-#pragma unroll
-            for (int o = 0; o < 7; o++)
-#pragma unroll
-                for (int k = o; k < 7; k++) sum[s++] += row[o] * row[k];
-            sum[28] += 1.0f;
-        }
+        if (in) gn_add_row(row, sum);
     }
-    // wave64 shuffle tree, then the four waves of the workgroup in a fixed order (icp_accumulate's)
-#pragma unroll
-    for (int i = 0; i < 29; i++) {
-        float v = sum[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        sum[i] = v;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 29; i++) shared[wave][i] = sum[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < 29) {
-        partial[blockIdx.x * 32 + threadIdx.x] =
-            ((shared[0][threadIdx.x] + shared[1][threadIdx.x]) + shared[2][threadIdx.x]) + shared[3][threadIdx.x];
-    }
+    gn_block_sums(sum, nullptr, partial);
 }
 
 // ---- the colour term (include/tsdf_amd.h, "colour alignment") ---------------------------------------------------------------------
@@ -173,7 +146,7 @@ __device__ inline bool align_colour_row(float u0, float u1, float u2, float y, c
 
 // align_reduce_kernel with the photometric row beside the geometric one: a second block of 29 sums in the same order, 64 floats a
 // workgroup (the geometric block at [0, 29), the colour block at [32, 61)).  The colour taps are read for geometric inliers only.  The
-// prologue combines the two blocks of the step before (icp_finish_step<true>).  ROWS: 14 floats a point, both rows.
+// prologue combines the two blocks of the step before (gn_step_begin<true>).  ROWS: 14 floats a point, both rows.
 template <bool FASTDIV, bool ROWS>
 __global__ __launch_bounds__(kIcpThreads) void align_colour_reduce_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
                                                                          const float *__restrict__ partial_prev, int pending, int prev_blocks,
@@ -182,37 +155,16 @@ __global__ __launch_bounds__(kIcpThreads) void align_colour_reduce_kernel(const 
                                                                          const float *__restrict__ intensity, float *__restrict__ rows,
                                                                          float *__restrict__ partial) {
     __shared__ double pose[16];
-    if (pending) {
-        icp_finish_step<true>(partial_prev, prev_blocks, state_in, 1, pose, blockIdx.x == 0 ? state_out : nullptr, ac.weight);
-    } else {
-        if (threadIdx.x < 16) {
-            pose[threadIdx.x] = state_in[threadIdx.x];
-            if (blockIdx.x == 0) state_out[threadIdx.x] = state_in[threadIdx.x];
-        }
-    }
-    __syncthreads();
-    __shared__ float shared[4][64];
-    float R[9], t[3];  // column-major
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) R[c * 3 + r] = (float)pose[c * 4 + r];
-    for (int r = 0; r < 3; r++) t[r] = (float)pose[12 + r];
-
+    float R[9], t[3];
+    gn_step_begin<true>(state_in, state_out, partial_prev, pending, prev_blocks, ac.weight, pose, R, t);
     float sum[29], sum_c[29];
 #pragma unroll
     for (int i = 0; i < 29; i++) sum[i] = sum_c[i] = 0.0f;
     const uint32_t stride = (uint32_t)kIcpThreads * gridDim.x;   // <= 65536
     for (uint64_t i = (uint64_t)blockIdx.x * kIcpThreads + threadIdx.x; i < n; i += stride) {
-        float row[7], row_c[7];
-        const float x0 = points[3 * i + 0], x1 = points[3 * i + 1], x2 = points[3 * i + 2];
-        const bool in = align_row<FASTDIV>(R, t, x0, x1, x2, f, a, row);
-        bool in_c = false;
-        if (in) {
-            // align_row's u (the same expressions: the compiler keeps one copy)
-            const float u0 = ((R[0] * x0 + R[3] * x1) + R[6] * x2) + t[0];
-            const float u1 = ((R[1] * x0 + R[4] * x1) + R[7] * x2) + t[1];
-            const float u2 = ((R[2] * x0 + R[5] * x1) + R[8] * x2) + t[2];
-            in_c = align_colour_row<FASTDIV>(u0, u1, u2, intensity[i], f, a, ac, row_c);
-        }
+        float row[7], row_c[7], u[3];
+        const bool in = align_row<FASTDIV>(R, t, points + 3 * i, f, a, row, u);
+        const bool in_c = in && align_colour_row<FASTDIV>(u[0], u[1], u[2], intensity[i], f, a, ac, row_c);
         if (ROWS) {
 #pragma unroll
             for (int k = 0; k < 7; k++) {
@@ -220,64 +172,10 @@ __global__ __launch_bounds__(kIcpThreads) void align_colour_reduce_kernel(const 
                 rows[14 * i + 7 + k] = in_c ? row_c[k] : NAN;
             }
         }
-        if (in) {
-            int s = 0;
-#pragma unroll
-            for (int o = 0; o < 7; o++)
-#pragma unroll
-                for (int k = o; k < 7; k++) sum[s++] += row[o] * row[k];
-            sum[28] += 1.0f;
-        }
-        if (in_c) {
-            int s = 0;
-#pragma unroll
-            for (int o = 0; o < 7; o++)
-#pragma unroll
-                for (int k = o; k < 7; k++) sum_c[s++] += row_c[o] * row_c[k];
-            sum_c[28] += 1.0f;
-        }
+        if (in) gn_add_row(row, sum);
+        if (in_c) gn_add_row(row_c, sum_c);
     }
-    // both blocks as align_reduce_kernel adds its one: the wave64 shuffle tree, then the four waves in a fixed order
-#pragma unroll
-    for (int i = 0; i < 29; i++) {
-        float v = sum[i], c = sum_c[i];
-        for (int o = 32; o > 0; o >>= 1) {
-            v += __shfl_down(v, o);
-            c += __shfl_down(c, o);
-        }
-        sum[i] = v;
-        sum_c[i] = c;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 29; i++) {
-            shared[wave][i] = sum[i];
-            shared[wave][32 + i] = sum_c[i];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64 && (threadIdx.x & 31) < 29) {
-        partial[blockIdx.x * 64 + threadIdx.x] =
-            ((shared[0][threadIdx.x] + shared[1][threadIdx.x]) + shared[2][threadIdx.x]) + shared[3][threadIdx.x];
-    }
-}
-
-// icp_finish_kernel for the two blocks: one workgroup; `mirror` (pinned, or null) gets the pose, then residual and inliers of the
-// geometric and of the colour term
-__global__ __launch_bounds__(kIcpThreads) void align_colour_finish_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
-                                                                         const float *__restrict__ partial_prev, int n_blocks, int update,
-                                                                         float colour_weight, double *__restrict__ mirror) {
-    __shared__ double pose[16];
-    icp_finish_step<true>(partial_prev, n_blocks, state_in, update, pose, state_out, colour_weight);
-    if (mirror && threadIdx.x == 0) {   // (thread 0 solved the step: what it has just written)
-#pragma unroll
-        for (int i = 0; i < 16; i++) mirror[i] = pose[i];
-        mirror[16] = state_out[16];
-        mirror[17] = state_out[17];
-        mirror[18] = state_out[60];
-        mirror[19] = state_out[61];
-    }
+    gn_block_sums<true>(sum, sum_c, partial);
 }
 
 // The intensity of the colour field and its gradient at world points, one thread per point (the frame of the field queries).
@@ -334,8 +232,7 @@ __global__ __launch_bounds__(256) void depth_to_points_kernel(const uint16_t *__
 }
 
 static void free_aligner(tsdf_aligner *a) {
-    device_free_all(a->partial, a->state, a->partial_c);
-    (void)hipHostFree(a->host_io);
+    a->chain.free();
     delete a;
 }
 
@@ -352,7 +249,9 @@ struct AlignSetup {
     int fast_div;
 };
 
-static int align_setup(const tsdf_aligner *a, const tsdf_volume *v, const double *T, float gate, const char *what, AlignSetup &s) {
+// `ac` (the colour calls; null without the term) comes with its gate and weight and leaves with the volume's colours; the chain's
+// colour sums are made here, by the first such call.
+static int align_setup(tsdf_aligner *a, const tsdf_volume *v, AlignColour *ac, const double *T, float gate, const char *what, AlignSetup &s) {
     TSDF_REQUIRE(a && v && T, "%s: null argument", what);
     const int rc = field_refuse_slab(v, what);
     if (rc != TSDF_OK) return rc;
@@ -360,6 +259,13 @@ static int align_setup(const tsdf_aligner *a, const tsdf_volume *v, const double
     for (int c = 0; c < 4; c++)
         for (int r = 0; r < 3; r++) TSDF_REQUIRE(std::isfinite(T[c * 4 + r]), "%s: T has a non-finite entry in its top three rows", what);
     TSDF_REQUIRE(gate > 0.0f, "%s: the gate must be > 0", what);   // (false for NaN)
+    if (ac) {
+        TSDF_REQUIRE(v->colour, "%s: colour is not enabled on this volume (tsdf_volume_enable_colour)", what);
+        TSDF_REQUIRE(ac->gate > 0.0f, "%s: the colour gate must be > 0", what);   // (false for NaN)
+        TSDF_REQUIRE(ac->weight >= 0.0f && ac->weight < INFINITY, "%s: the colour weight must be finite and >= 0", what);
+        TSDF_HIP(a->chain.alloc_colour(), "aligner: the colour sums");
+        ac->colour = v->colour;
+    }
     s.f = make_field_view(v);
     s.a.h = {0.5f * s.f.tc.max_x, 0.5f * s.f.tc.max_y, 0.5f * s.f.tc.max_z};
     s.a.gate = gate;
@@ -372,7 +278,7 @@ static int align_setup(const tsdf_aligner *a, const tsdf_volume *v, const double
 
 // T (the caller's, points' frame -> the frame of the field queries) -> T_c about the pivot, into the pinned block
 static void align_pose_in(tsdf_aligner *a, const AlignSetup &s, const double *T) {
-    double *io = a->host_io;
+    double *io = a->chain.host_io;
     for (int c = 0; c < 4; c++) {
         for (int r = 0; r < 3; r++) io[c * 4 + r] = T[c * 4 + r];
         io[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
@@ -380,82 +286,109 @@ static void align_pose_in(tsdf_aligner *a, const AlignSetup &s, const double *T)
     for (int r = 0; r < 3; r++) io[12 + r] = T[12 + r] - s.pivot[r];
 }
 
-// The sums of one step over `n` > 0 points at the pose the pending step (if any) leads to.
-static void launch_align_step(tsdf_aligner *a, const AlignSetup &s, uint32_t n, const float *points, float *rows, int pending, int prev_blocks,
-                              const double *start) {
-    const int in = a->side, out = 1 - a->side;
-    const double *state_in = start ? start : a->state + in * kIcpStateDoubles;
-    double *state_out = a->state + out * kIcpStateDoubles;
-    const float *partial_prev = a->partial + (size_t)in * kIcpBlocks * 32;
-    float *partial = a->partial + (size_t)out * kIcpBlocks * 32;
-    const dim3 grid((unsigned)align_blocks(n)), block(kIcpThreads);
-#define TSDF_ALIGN_LAUNCH(FD, RW) \
-    hipLaunchKernelGGL((align_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, state_out, partial_prev, pending, prev_blocks, s.f, s.a, n, points, rows, partial)
-    if (rows) {
-        if (s.fast_div) TSDF_ALIGN_LAUNCH(true, true);
-        else TSDF_ALIGN_LAUNCH(false, true);
-    } else {
-        if (s.fast_div) TSDF_ALIGN_LAUNCH(true, false);
-        else TSDF_ALIGN_LAUNCH(false, false);
+// T_c as a chain left it behind the pose it started from -> the caller's T.  A chain that did not move the pose (no step had an inlier)
+// hands the caller's matrix back as given, not through the two shifts.
+static void align_pose_out(const tsdf_aligner *a, const AlignSetup &s, const double *out, double *T) {
+    bool moved = false;
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++) moved = moved || out[c * 4 + r] != a->chain.host_io[c * 4 + r];
+    if (!moved) return;
+    for (int c = 0; c < 4; c++) {
+        for (int r = 0; r < 3; r++) T[c * 4 + r] = out[c * 4 + r];
+        T[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
     }
-#undef TSDF_ALIGN_LAUNCH
-    a->side = out;
+    for (int r = 0; r < 3; r++) T[12 + r] = out[12 + r] + s.pivot[r];
 }
 
-static void launch_align_finish(tsdf_aligner *a, int n_blocks, int update, double *mirror) {
-    const int in = a->side, out = 1 - a->side;
-    launch_gn_finish(a->stream, a->state + in * kIcpStateDoubles, a->state + out * kIcpStateDoubles, a->partial + (size_t)in * kIcpBlocks * 32,
-                     n_blocks, update, mirror);
-    a->side = out;
+// launch(fd, rw) with the volume's division and the rows hook as compile-time constants
+template <typename F>
+static void align_dispatch(bool fast_div, bool rows, F launch) {
+    if (rows) {
+        if (fast_div) launch(std::true_type(), std::true_type());
+        else launch(std::false_type(), std::true_type());
+    } else {
+        if (fast_div) launch(std::true_type(), std::false_type());
+        else launch(std::false_type(), std::false_type());
+    }
 }
 
-// ---- the colour term's host side ------------------------------------------------------------------------------------------------
-// what the colour calls refuse beyond align_setup, and the sums' second home
-static int align_colour_setup(tsdf_aligner *a, const tsdf_volume *v, float colour_gate, float colour_weight, const char *what, AlignColour &ac) {
-    TSDF_REQUIRE(v->colour, "%s: colour is not enabled on this volume (tsdf_volume_enable_colour)", what);
-    TSDF_REQUIRE(colour_gate > 0.0f, "%s: the colour gate must be > 0", what);   // (false for NaN)
-    TSDF_REQUIRE(colour_weight >= 0.0f && colour_weight < INFINITY, "%s: the colour weight must be finite and >= 0", what);
-    if (!a->partial_c) {
-        const size_t bytes = (size_t)2 * kIcpBlocks * 64 * sizeof(float);
-        TSDF_HIP(hipMalloc((void **)&a->partial_c, bytes), "aligner: the colour sums");
-        const hipError_t e = hipMemset(a->partial_c, 0, bytes);
-        if (e != hipSuccess) {
-            device_free_all(a->partial_c);
-            return hip_fail(e, "aligner: the colour sums");
+// The sums of one step over `n` > 0 points at the pose the pending step (if any) leads to; with `ac` both terms' (`intensity` is theirs).
+static void launch_align_step(tsdf_aligner *a, const AlignSetup &s, const AlignColour *ac, uint32_t n, const float *points, const float *intensity,
+                              float *rows, int pending, int prev_blocks, const double *start) {
+    GnChain &c = a->chain;
+    const double *state_in = start ? start : c.state_in();
+    const dim3 grid((unsigned)align_blocks(n)), block(kIcpThreads);
+    align_dispatch(s.fast_div != 0, rows != nullptr, [&](auto fd, auto rw) {
+        constexpr bool FD = decltype(fd)::value, RW = decltype(rw)::value;
+        if (ac)
+            hipLaunchKernelGGL((align_colour_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, c.state_out(), c.partial_in(true), pending,
+                               prev_blocks, s.f, s.a, *ac, n, points, intensity, rows, c.partial_out(true));
+        else
+            hipLaunchKernelGGL((align_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, c.state_out(), c.partial_in(), pending, prev_blocks,
+                               s.f, s.a, n, points, rows, c.partial_out());
+    });
+    c.flip();
+}
+
+// tsdf_aligner_step[_colour] behind the caller's own refusals: `what` is its name, residual_inliers two floats a term
+static int align_step(tsdf_aligner *a, const tsdf_volume *v, AlignColour *ac, uint32_t n, const float *points, const float *intensity,
+                      const double *T, float gate, float *A, float *b, float *residual_inliers, float *rows, const char *what) {
+    AlignSetup s;
+    const int rc = align_setup(a, v, ac, T, gate, what, s);
+    if (rc != TSDF_OK) return rc;
+    const int terms = ac ? 2 : 1;
+    if (n == 0) {
+        std::memset(A, 0, 36 * sizeof(float));
+        std::memset(b, 0, 6 * sizeof(float));
+        std::memset(residual_inliers, 0, 2 * terms * sizeof(float));
+        return TSDF_OK;
+    }
+    align_pose_in(a, s, T);
+    launch_align_step(a, s, ac, n, points, intensity, rows, 0, 0, a->chain.host_io_dev);
+    a->chain.finish(a->stream, align_blocks(n), 0, nullptr, ac ? &ac->weight : nullptr);
+    TSDF_HIP(hipGetLastError(), "align kernels failed");
+    return a->chain.download(a->stream, A, b, residual_inliers, terms, "align result download", "align step");
+}
+
+// a stage of either kind (intensity null without the colour term)
+struct AlignStage {
+    const float *points, *intensity;
+    uint32_t n, iterations;
+};
+
+// tsdf_aligner_run[_colour] behind the caller's own refusals; residual / inliers (either may be null): one float a term
+static int align_run(tsdf_aligner *a, const tsdf_volume *v, AlignColour *ac, uint32_t n_stages, const AlignStage *stages, float gate, double *T,
+                     float *residual, float *inliers, const char *what) {
+    AlignSetup s;
+    const int rc = align_setup(a, v, ac, T, gate, what, s);
+    if (rc != TSDF_OK) return rc;
+    GnChain &c = a->chain;
+    const int terms = ac ? 2 : 1;
+    // The pose goes to the device and the result comes back through the pinned block (every call ends with the stream idle, so the
+    // host may write it here), as tsdf_icp_get_incremental_transformation does.
+    align_pose_in(a, s, T);
+    int pending = 0, prev_blocks = 0;   // every launch finishes the step before it, the last step gets a launch of its own
+    for (uint32_t i = 0; i < n_stages; i++) {
+        if (stages[i].n == 0) continue;
+        for (uint32_t j = 0; j < stages[i].iterations; j++) {
+            launch_align_step(a, s, ac, stages[i].n, stages[i].points, stages[i].intensity, nullptr, pending, prev_blocks, pending ? nullptr : c.host_io_dev);
+            pending = 1;
+            prev_blocks = align_blocks(stages[i].n);
         }
     }
-    ac.colour = v->colour;
-    ac.gate = colour_gate;
-    ac.weight = colour_weight;
-    return TSDF_OK;
-}
-
-static void launch_align_colour_step(tsdf_aligner *a, const AlignSetup &s, const AlignColour &ac, uint32_t n, const float *points,
-                                     const float *intensity, float *rows, int pending, int prev_blocks, const double *start) {
-    const int in = a->side, out = 1 - a->side;
-    const double *state_in = start ? start : a->state + in * kIcpStateDoubles;
-    double *state_out = a->state + out * kIcpStateDoubles;
-    const float *partial_prev = a->partial_c + (size_t)in * kIcpBlocks * 64;
-    float *partial = a->partial_c + (size_t)out * kIcpBlocks * 64;
-    const dim3 grid((unsigned)align_blocks(n)), block(kIcpThreads);
-#define TSDF_ALIGN_LAUNCH(FD, RW) \
-    hipLaunchKernelGGL((align_colour_reduce_kernel<FD, RW>), grid, block, 0, a->stream, state_in, state_out, partial_prev, pending, prev_blocks, s.f, s.a, ac, n, points, intensity, rows, partial)
-    if (rows) {
-        if (s.fast_div) TSDF_ALIGN_LAUNCH(true, true);
-        else TSDF_ALIGN_LAUNCH(false, true);
-    } else {
-        if (s.fast_div) TSDF_ALIGN_LAUNCH(true, false);
-        else TSDF_ALIGN_LAUNCH(false, false);
+    double out[20] = {0};   // the pose, then residual and inliers of every term (zeros for a chain with nothing to do: the pose stays as given)
+    if (pending) {
+        c.finish(a->stream, prev_blocks, 1, c.host_io_dev + 16, ac ? &ac->weight : nullptr);
+        TSDF_HIP(hipGetLastError(), "align kernels failed");
+        TSDF_HIP(hipStreamSynchronize(a->stream), "align");
+        std::memcpy(out, c.host_io + 16, (16 + 2 * terms) * sizeof(double));
+        align_pose_out(a, s, out, T);
     }
-#undef TSDF_ALIGN_LAUNCH
-    a->side = out;
-}
-
-static void launch_align_colour_finish(tsdf_aligner *a, const AlignColour &ac, int n_blocks, int update, double *mirror) {
-    const int in = a->side, out = 1 - a->side;
-    hipLaunchKernelGGL(align_colour_finish_kernel, dim3(1), dim3(kIcpThreads), 0, a->stream, a->state + in * kIcpStateDoubles,
-                       a->state + out * kIcpStateDoubles, a->partial_c + (size_t)in * kIcpBlocks * 64, n_blocks, update, ac.weight, mirror);
-    a->side = out;
+    for (int k = 0; k < terms; k++) {
+        if (residual) residual[k] = (float)out[16 + 2 * k];
+        if (inliers) inliers[k] = (float)out[17 + 2 * k];
+    }
+    return TSDF_OK;
 }
 
 static int sample_intensity_check(const tsdf_volume *v, const char *what) {
@@ -500,13 +433,7 @@ int tsdf_aligner_create(tsdf_aligner **out) {
     }
     std::memset(a, 0, sizeof(*a));
     hipError_t e = hipGetDevice(&a->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&a->partial, (size_t)2 * kIcpBlocks * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(a->partial, 0, (size_t)2 * kIcpBlocks * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&a->state, 2 * kIcpStateDoubles * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(a->state, 0, 2 * kIcpStateDoubles * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&a->host_io, (16 + 20) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) std::memset(a->host_io, 0, (16 + 20) * sizeof(double));
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&a->host_io_dev, a->host_io, 0);
+    if (e == hipSuccess) e = a->chain.alloc(20);
     if (e != hipSuccess) {
         free_aligner(a);
         return hip_fail(e, "aligner alloc failed");
@@ -535,74 +462,19 @@ int tsdf_aligner_step(tsdf_aligner *a, const tsdf_volume *v, uint32_t n, const f
                       float A[36], float b[6], float residual_inliers[2], float *device_rows) {
     TSDF_REQUIRE(A && b && residual_inliers, "tsdf_aligner_step: null argument");
     TSDF_REQUIRE(n == 0 || device_points, "tsdf_aligner_step: null points");
-    AlignSetup s;
-    const int rc = align_setup(a, v, T, gate, "tsdf_aligner_step", s);
-    if (rc != TSDF_OK) return rc;
-    if (n == 0) {
-        std::memset(A, 0, 36 * sizeof(float));
-        std::memset(b, 0, 6 * sizeof(float));
-        residual_inliers[0] = residual_inliers[1] = 0.0f;
-        return TSDF_OK;
-    }
-    align_pose_in(a, s, T);
-    launch_align_step(a, s, n, device_points, device_rows, 0, 0, a->host_io_dev);
-    launch_align_finish(a, align_blocks(n), 0, nullptr);
-    TSDF_HIP(hipGetLastError(), "align kernels failed");
-    double out[kIcpStateDoubles];
-    TSDF_HIP(hipMemcpyAsync(out, a->state + a->side * kIcpStateDoubles, sizeof(out), hipMemcpyDeviceToHost, a->stream), "align result download");
-    TSDF_HIP(hipStreamSynchronize(a->stream), "align step");
-    residual_inliers[0] = (float)out[16];
-    residual_inliers[1] = (float)out[17];
-    for (int i = 0; i < 36; i++) A[i] = (float)out[18 + i];
-    for (int i = 0; i < 6; i++) b[i] = (float)out[54 + i];
-    return TSDF_OK;
+    return align_step(a, v, nullptr, n, device_points, nullptr, T, gate, A, b, residual_inliers, device_rows, "tsdf_aligner_step");
 }
 
 int tsdf_aligner_run(tsdf_aligner *a, const tsdf_volume *v, uint32_t n_stages, const tsdf_align_stage *stages, float gate, double T[16],
                      float *residual, float *inliers) {
     TSDF_REQUIRE(n_stages <= (uint32_t)kAlignMaxStages, "tsdf_aligner_run: more than %d stages", kAlignMaxStages);
     TSDF_REQUIRE(n_stages == 0 || stages, "tsdf_aligner_run: null stages");
-    for (uint32_t i = 0; i < n_stages; i++)
-        TSDF_REQUIRE(stages[i].n == 0 || stages[i].iterations == 0 || stages[i].device_points, "tsdf_aligner_run: stage %u has null points", i);
-    AlignSetup s;
-    const int rc = align_setup(a, v, T, gate, "tsdf_aligner_run", s);
-    if (rc != TSDF_OK) return rc;
-    // The pose goes to the device and the result comes back through the pinned block (every call ends with the stream idle, so the
-    // host may write it here), as tsdf_icp_get_incremental_transformation does.
-    align_pose_in(a, s, T);
-    int pending = 0, prev_blocks = 0;   // every launch finishes the step before it, the last step gets a launch of its own
+    AlignStage st[kAlignMaxStages];
     for (uint32_t i = 0; i < n_stages; i++) {
-        if (stages[i].n == 0) continue;
-        for (uint32_t j = 0; j < stages[i].iterations; j++) {
-            launch_align_step(a, s, stages[i].n, stages[i].device_points, nullptr, pending, prev_blocks, pending ? nullptr : a->host_io_dev);
-            pending = 1;
-            prev_blocks = align_blocks(stages[i].n);
-        }
+        TSDF_REQUIRE(stages[i].n == 0 || stages[i].iterations == 0 || stages[i].device_points, "tsdf_aligner_run: stage %u has null points", i);
+        st[i] = {stages[i].device_points, nullptr, stages[i].n, stages[i].iterations};
     }
-    if (!pending) {   // nothing to do: the pose stays as given
-        if (residual) *residual = 0.0f;
-        if (inliers) *inliers = 0.0f;
-        return TSDF_OK;
-    }
-    launch_align_finish(a, prev_blocks, 1, a->host_io_dev + 16);
-    TSDF_HIP(hipGetLastError(), "align kernels failed");
-    TSDF_HIP(hipStreamSynchronize(a->stream), "align");
-    double out[18];
-    std::memcpy(out, a->host_io + 16, sizeof(out));
-    // A chain that did not move the pose (no step had an inlier) hands the caller's matrix back as given, not through the two shifts.
-    bool moved = false;
-    for (int c = 0; c < 4; c++)
-        for (int r = 0; r < 3; r++) moved = moved || out[c * 4 + r] != a->host_io[c * 4 + r];
-    if (moved) {
-        for (int c = 0; c < 4; c++) {
-            for (int r = 0; r < 3; r++) T[c * 4 + r] = out[c * 4 + r];
-            T[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
-        }
-        for (int r = 0; r < 3; r++) T[12 + r] = out[12 + r] + s.pivot[r];
-    }
-    if (residual) *residual = (float)out[16];
-    if (inliers) *inliers = (float)out[17];
-    return TSDF_OK;
+    return align_run(a, v, nullptr, n_stages, st, gate, T, residual, inliers, "tsdf_aligner_run");
 }
 
 int tsdf_depth_to_points_device(uint32_t width, uint32_t height, const uint16_t *device_depth, const float kinv[9], uint32_t step,
@@ -673,88 +545,23 @@ int tsdf_aligner_step_colour(tsdf_aligner *a, const tsdf_volume *v, uint32_t n, 
     TSDF_REQUIRE(A && b && residual_inliers, "tsdf_aligner_step_colour: null argument");
     TSDF_REQUIRE(n == 0 || device_points, "tsdf_aligner_step_colour: null points");
     TSDF_REQUIRE(n == 0 || device_intensity, "tsdf_aligner_step_colour: null intensities");
-    AlignSetup s;
-    AlignColour ac;
-    int rc = align_setup(a, v, T, gate, "tsdf_aligner_step_colour", s);
-    if (rc == TSDF_OK) rc = align_colour_setup(a, v, colour_gate, colour_weight, "tsdf_aligner_step_colour", ac);
-    if (rc != TSDF_OK) return rc;
-    if (n == 0) {
-        std::memset(A, 0, 36 * sizeof(float));
-        std::memset(b, 0, 6 * sizeof(float));
-        std::memset(residual_inliers, 0, 4 * sizeof(float));
-        return TSDF_OK;
-    }
-    align_pose_in(a, s, T);
-    launch_align_colour_step(a, s, ac, n, device_points, device_intensity, device_rows, 0, 0, a->host_io_dev);
-    launch_align_colour_finish(a, ac, align_blocks(n), 0, nullptr);
-    TSDF_HIP(hipGetLastError(), "align kernels failed");
-    double out[kIcpStateDoubles];
-    TSDF_HIP(hipMemcpyAsync(out, a->state + a->side * kIcpStateDoubles, sizeof(out), hipMemcpyDeviceToHost, a->stream), "align result download");
-    TSDF_HIP(hipStreamSynchronize(a->stream), "align step");
-    residual_inliers[0] = (float)out[16];
-    residual_inliers[1] = (float)out[17];
-    residual_inliers[2] = (float)out[60];
-    residual_inliers[3] = (float)out[61];
-    for (int i = 0; i < 36; i++) A[i] = (float)out[18 + i];
-    for (int i = 0; i < 6; i++) b[i] = (float)out[54 + i];
-    return TSDF_OK;
+    AlignColour ac = {nullptr, colour_gate, colour_weight};
+    return align_step(a, v, &ac, n, device_points, device_intensity, T, gate, A, b, residual_inliers, device_rows, "tsdf_aligner_step_colour");
 }
 
 int tsdf_aligner_run_colour(tsdf_aligner *a, const tsdf_volume *v, uint32_t n_stages, const tsdf_align_colour_stage *stages, float gate,
                             float colour_gate, float colour_weight, double T[16], float residual[2], float inliers[2]) {
     TSDF_REQUIRE(n_stages <= (uint32_t)kAlignMaxStages, "tsdf_aligner_run_colour: more than %d stages", kAlignMaxStages);
     TSDF_REQUIRE(n_stages == 0 || stages, "tsdf_aligner_run_colour: null stages");
+    AlignStage st[kAlignMaxStages];
     for (uint32_t i = 0; i < n_stages; i++) {
         const bool empty = stages[i].n == 0 || stages[i].iterations == 0;
         TSDF_REQUIRE(empty || stages[i].device_points, "tsdf_aligner_run_colour: stage %u has null points", i);
         TSDF_REQUIRE(empty || stages[i].device_intensity, "tsdf_aligner_run_colour: stage %u has null intensities", i);
+        st[i] = {stages[i].device_points, stages[i].device_intensity, stages[i].n, stages[i].iterations};
     }
-    AlignSetup s;
-    AlignColour ac;
-    int rc = align_setup(a, v, T, gate, "tsdf_aligner_run_colour", s);
-    if (rc == TSDF_OK) rc = align_colour_setup(a, v, colour_gate, colour_weight, "tsdf_aligner_run_colour", ac);
-    if (rc != TSDF_OK) return rc;
-    align_pose_in(a, s, T);   // (the pinned block, as tsdf_aligner_run)
-    int pending = 0, prev_blocks = 0;
-    for (uint32_t i = 0; i < n_stages; i++) {
-        if (stages[i].n == 0) continue;
-        for (uint32_t j = 0; j < stages[i].iterations; j++) {
-            launch_align_colour_step(a, s, ac, stages[i].n, stages[i].device_points, stages[i].device_intensity, nullptr, pending, prev_blocks,
-                                     pending ? nullptr : a->host_io_dev);
-            pending = 1;
-            prev_blocks = align_blocks(stages[i].n);
-        }
-    }
-    if (!pending) {   // nothing to do: the pose stays as given
-        if (residual) residual[0] = residual[1] = 0.0f;
-        if (inliers) inliers[0] = inliers[1] = 0.0f;
-        return TSDF_OK;
-    }
-    launch_align_colour_finish(a, ac, prev_blocks, 1, a->host_io_dev + 16);
-    TSDF_HIP(hipGetLastError(), "align kernels failed");
-    TSDF_HIP(hipStreamSynchronize(a->stream), "align");
-    double out[20];
-    std::memcpy(out, a->host_io + 16, sizeof(out));   // (the 20 doubles behind the pose: pose, then residual and inliers of both terms)
-    // A chain that did not move the pose hands the caller's matrix back as given, as tsdf_aligner_run does.
-    bool moved = false;
-    for (int c = 0; c < 4; c++)
-        for (int r = 0; r < 3; r++) moved = moved || out[c * 4 + r] != a->host_io[c * 4 + r];
-    if (moved) {
-        for (int c = 0; c < 4; c++) {
-            for (int r = 0; r < 3; r++) T[c * 4 + r] = out[c * 4 + r];
-            T[c * 4 + 3] = c == 3 ? 1.0 : 0.0;
-        }
-        for (int r = 0; r < 3; r++) T[12 + r] = out[12 + r] + s.pivot[r];
-    }
-    if (residual) {
-        residual[0] = (float)out[16];
-        residual[1] = (float)out[18];
-    }
-    if (inliers) {
-        inliers[0] = (float)out[17];
-        inliers[1] = (float)out[19];
-    }
-    return TSDF_OK;
+    AlignColour ac = {nullptr, colour_gate, colour_weight};
+    return align_run(a, v, &ac, n_stages, st, gate, T, residual, inliers, "tsdf_aligner_run_colour");
 }
 
 }  // extern "C"

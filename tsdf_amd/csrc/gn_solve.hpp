@@ -1,9 +1,16 @@
-// The Gauss-Newton back end shared by icp.hip (frame-to-model ICP) and align.hip (field alignment): the second stage of the
-// 29-entry reduction, the 6 x 6 LDL^T solvers, the SE3 exponential and T <- exp(x) * T (icp_finish_step), with the constants of the
-// reduction's shape.  Moved here from icp.hip unchanged, so that both translation units finish a step with the very same expressions.
+// One Gauss-Newton chain with the pose kept on the device, shared by icp.hip (frame-to-model ICP) and align.hip (field alignment and
+// its colour term).  A feature supplies the row of a point; everything round it is here, once:
+//   * the front end of a step: gn_step_begin (finish the pending step in every workgroup or copy the pose, the barrier, the pose
+//     narrowed to R, t), gn_add_row (row -> 28 products + count) and gn_block_sums (wave64 shuffle tree, the four waves in a fixed
+//     order) for one or two blocks of 29 sums;
+//   * the back end: the second stage of the 29-entry reduction, the 6 x 6 LDL^T solvers, the SE3 exponential and T <- exp(x) * T
+//     (icp_finish_step), and gn_finish_kernel for the last step of a chain, which has no next launch to finish it;
+//   * the host's side: GnChain, the two-sided device state, the partial sums, the pinned in/out block and their slot arithmetic.
+// The expressions and the order of the additions are those icp.hip had: every translation unit steps with the very same bits.
 #pragma once
 
 #include <cmath>
+#include <cstring>
 
 #include "common.hpp"
 
@@ -13,10 +20,11 @@ constexpr int kIcpBlocks = 256;   // one workgroup per CU (icp_finish_step adds 
 constexpr int kIcpThreads = 256;
 constexpr int kIcpStateDoubles = 64;
 
-// icp.hip: launches icp_finish_kernel (one workgroup: icp_finish_step of the sums in partial_prev, state_in -> state_out; `mirror`,
-// pinned host memory or null, also gets pose, residual and inliers) on `stream`
+// icp.hip: launches gn_finish_kernel (one workgroup: icp_finish_step of the sums in partial_prev, state_in -> state_out; `mirror`,
+// pinned host memory or null, also gets pose, residual and inliers) on `stream`.  colour_weight null: one block of sums a workgroup and
+// a mirror of 18 doubles; else two blocks combined with that weight and 20 doubles, the colour term's residual and count last.
 void launch_gn_finish(hipStream_t stream, const double *state_in, double *state_out, const float *partial_prev, int n_blocks, int update,
-                      double *mirror);
+                      double *mirror, const float *colour_weight = nullptr);
 
 // x = A^-1 b, 6x6 symmetric positive (semi-)definite, LDL^T with diagonal pivoting in double -- the job of
 // `A_icp.cast<double>().ldlt().solve(b_icp.cast<double>())` (ICPOdometry.cpp:131).  Zero pivots give zero components.
@@ -286,5 +294,154 @@ __device__ __forceinline__ void icp_finish_step(const float *partial, int n_bloc
         if (state_out) state_out[i] = out[i];
     }
 }
+
+// The start of a step's launch.  `pending` != 0: the launch before left the sums of its `prev_blocks` workgroups in partial_prev and the
+// pose they were taken at in state_in; EVERY workgroup finishes that step first (icp_finish_step, the same fixed-order arithmetic, so
+// all arrive at the same pose) and workgroup 0 records it in state_out.  Else the pose is copied.  The kernel boundary orders the two
+// launches -- no fence, no ticket, no workgroup waiting for the others across the chip's eight L2s (that hand-over cost more than the
+// whole reduction: 24 -> 14 us per step).  Then the pose narrowed to float like `rotationMatrix().cast<float>()`: R column-major.
+// `pose`: 16 doubles of LDS, declared by the kernel (declared here, the compiler lays the LDS out differently and the shuffle tree of
+// gn_block_sums comes out with some forty more s_waitcnt: LABNOTES.md).
+template <bool COLOUR = false>
+__device__ __forceinline__ void gn_step_begin(const double *__restrict__ state_in, double *__restrict__ state_out,
+                                              const float *__restrict__ partial_prev, int pending, int prev_blocks, float colour_weight,
+                                              double *pose, float *R, float *t) {
+    if (pending) {
+        icp_finish_step<COLOUR>(partial_prev, prev_blocks, state_in, 1, pose, blockIdx.x == 0 ? state_out : nullptr, colour_weight);
+    } else {
+        if (threadIdx.x < 16) {
+            pose[threadIdx.x] = state_in[threadIdx.x];
+            if (blockIdx.x == 0) state_out[threadIdx.x] = state_in[threadIdx.x];
+        }
+    }
+    __syncthreads();
+    for (int c = 0; c < 3; c++)
+        for (int r = 0; r < 3; r++) R[c * 3 + r] = (float)pose[c * 4 + r];
+    for (int r = 0; r < 3; r++) t[r] = (float)pose[12 + r];
+}
+
+// An inlier's row into a thread's 29 fp32 sums: the 28 upper-triangular products in the reference's order, then the count.
+__device__ __forceinline__ void gn_add_row(const float *row, float *sum) {
+    int s = 0;
+#pragma unroll
+    for (int o = 0; o < 7; o++)
+#pragma unroll
+        for (int k = o; k < 7; k++) sum[s++] += row[o] * row[k];
+    sum[28] += 1.0f;
+}
+
+// A workgroup's 29 sums to partial[32 blockIdx.x ..): the wave64 shuffle tree, lane 0 of each wave to LDS, then the four waves of the
+// workgroup in a fixed order.  COLOUR: two blocks, 64 floats a workgroup, sum at [0, 29) and sum_c at [32, 61), their shuffles interleaved.
+template <bool COLOUR = false>
+__device__ __forceinline__ void gn_block_sums(float *sum, float *sum_c, float *__restrict__ partial) {
+    constexpr int kStride = COLOUR ? 64 : 32;   // floats a workgroup
+    __shared__ float shared[4][kStride];
+#pragma unroll
+    for (int i = 0; i < 29; i++) {
+        float v = sum[i], c = COLOUR ? sum_c[i] : 0.0f;
+        for (int o = 32; o > 0; o >>= 1) {
+            v += __shfl_down(v, o);
+            if (COLOUR) c += __shfl_down(c, o);
+        }
+        sum[i] = v;
+        if (COLOUR) sum_c[i] = c;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 29; i++) {
+            shared[wave][i] = sum[i];
+            if (COLOUR) shared[wave][32 + i] = sum_c[i];
+        }
+    }
+    __syncthreads();
+    if (COLOUR ? threadIdx.x < 64 && (threadIdx.x & 31) < 29 : threadIdx.x < 29) {
+        partial[blockIdx.x * kStride + threadIdx.x] =
+            ((shared[0][threadIdx.x] + shared[1][threadIdx.x]) + shared[2][threadIdx.x]) + shared[3][threadIdx.x];
+    }
+}
+
+// Finishes the last step of a sequence (nothing follows whose prologue would): one workgroup.
+// `mirror` (pinned host memory, or null): pose, residual and inliers also go there, for the host to read after the stream's end;
+// COLOUR: the colour term's residual and inliers behind them.
+template <bool COLOUR>
+__global__ __launch_bounds__(kIcpThreads) void gn_finish_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
+                                                               const float *__restrict__ partial_prev, int n_blocks, int update,
+                                                               float colour_weight, double *__restrict__ mirror) {
+    __shared__ double pose[16];
+    icp_finish_step<COLOUR>(partial_prev, n_blocks, state_in, update, pose, state_out, colour_weight);
+    if (mirror && threadIdx.x == 0) {   // (thread 0 solved the step: what it has just written)
+#pragma unroll
+        for (int i = 0; i < 16; i++) mirror[i] = pose[i];
+        mirror[16] = state_out[16];
+        mirror[17] = state_out[17];
+        if (COLOUR) {
+            mirror[18] = state_out[60];
+            mirror[19] = state_out[61];
+        }
+    }
+}
+
+// The host's side of a chain; tsdf_icp and tsdf_aligner embed one (plain, memset to zero with its handle).
+struct GnChain {
+    double *state;         // device, 2 x kIcpStateDoubles: [0..15] T (column-major), [16] residual, [17] inliers, [18..53] A (float
+                           //         values), [54..59] b, [60], [61] the colour term's residual and inliers
+    float *partial;        // 2 x kIcpBlocks x 32 floats: per-workgroup sums of the 29 entries (two steps)
+    float *partial_c;      // colour alignment: 2 x kIcpBlocks x 64 floats (both blocks of sums), made by the first colour call
+    int side;              // which copy of state / partial holds the latest step
+    double *host_io;       // pinned host memory the device reads and writes in place: [0..15] the pose a chain starts from, behind it
+    double *host_io_dev;   // the result (pose, residual, inliers: `mirror` doubles) -- no copy launches either side of the chain (4-5 us each)
+
+    hipError_t alloc(int mirror) {
+        hipError_t e = hipMalloc((void **)&partial, (size_t)2 * kIcpBlocks * 32 * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(partial, 0, (size_t)2 * kIcpBlocks * 32 * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void **)&state, 2 * kIcpStateDoubles * sizeof(double));
+        if (e == hipSuccess) e = hipMemset(state, 0, 2 * kIcpStateDoubles * sizeof(double));
+        // (fine-grained: the device reads and writes it past its caches)
+        if (e == hipSuccess) e = hipHostMalloc((void **)&host_io, (16 + mirror) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) std::memset(host_io, 0, (16 + mirror) * sizeof(double));
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&host_io_dev, host_io, 0);
+        return e;
+    }
+    hipError_t alloc_colour() {
+        if (partial_c) return hipSuccess;
+        const size_t bytes = (size_t)2 * kIcpBlocks * 64 * sizeof(float);
+        hipError_t e = hipMalloc((void **)&partial_c, bytes);
+        if (e == hipSuccess) e = hipMemset(partial_c, 0, bytes);
+        if (e != hipSuccess) device_free_all(partial_c);
+        return e;
+    }
+    void free() {
+        device_free_all(partial, state, partial_c);
+        (void)hipHostFree(host_io);
+        host_io = host_io_dev = nullptr;
+    }
+    // the slots of a launch: it reads the latest step's (`in`), writes the other side's, and flip() makes that the latest
+    double *state_in() const { return state + side * kIcpStateDoubles; }
+    double *state_out() const { return state + (1 - side) * kIcpStateDoubles; }
+    float *sums(int s, bool colour) const { return colour ? partial_c + (size_t)s * kIcpBlocks * 64 : partial + (size_t)s * kIcpBlocks * 32; }
+    const float *partial_in(bool colour = false) const { return sums(side, colour); }
+    float *partial_out(bool colour = false) const { return sums(1 - side, colour); }
+    void flip() { side = 1 - side; }
+
+    // Finishes the step whose sums the last launch left (with or without the pose update).
+    void finish(hipStream_t stream, int n_blocks, int update, double *mirror, const float *colour_weight = nullptr) {
+        launch_gn_finish(stream, state_in(), state_out(), partial_in(colour_weight != nullptr), n_blocks, update, mirror, colour_weight);
+        flip();
+    }
+    // The latest step's system to the host: A, b, then {residual, inliers} of n_terms terms.  Blocking.
+    int download(hipStream_t stream, float A[36], float b[6], float *residual_inliers, int n_terms, const char *what_copy, const char *what_sync) {
+        double out[kIcpStateDoubles];
+        TSDF_HIP(hipMemcpyAsync(out, state_in(), sizeof(out), hipMemcpyDeviceToHost, stream), what_copy);
+        TSDF_HIP(hipStreamSynchronize(stream), what_sync);
+        for (int k = 0; k < n_terms; k++) {
+            residual_inliers[2 * k] = (float)out[k ? 60 : 16];
+            residual_inliers[2 * k + 1] = (float)out[k ? 61 : 17];
+        }
+        for (int i = 0; i < 36; i++) A[i] = (float)out[18 + i];
+        for (int i = 0; i < 6; i++) b[i] = (float)out[54 + i];
+        return TSDF_OK;
+    }
+};
 
 }  // namespace tsdf

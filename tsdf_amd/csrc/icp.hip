@@ -5,9 +5,10 @@
 // What is different from the reference's shape, and why:
 //   * The reference runs 19 iterations (10/5/4 over three pyramid levels), each = reduction kernel, second reduction
 //     kernel, device synchronise, 116-byte download, 6x6 LDLT + SE3 exponential on the host, next launch.  Here the
-//     pose lives on the device: the last workgroup of icp_reduce_kernel to finish adds up the partial sums, solves the
-//     6x6 system in double and applies T <- exp(x) * T in place, so a frame is 19 launches queued back to back with no
-//     host round trip; the host reads the pose once at the end.
+//     pose lives on the device: every workgroup of icp_reduce_kernel first finishes the step before it -- adds up the partial
+//     sums, solves the 6x6 system in double and applies T <- exp(x) * T -- so a frame is 19 launches and a finishing one
+//     queued back to back with no host round trip; the host reads the pose once at the end.  That chain is gn_solve.hpp's,
+//     shared with align.hip: this file supplies the projective association that makes a point's row, and the maps.
 //   * The reduction is deterministic: a fixed grid, per-thread fp32 partial sums (as in the reference), wave64 shuffle
 //     tree, fixed-order cross-wave and cross-block sums (the last stage in double).  The reference's sums depend on the
 //     threads x blocks the caller passes; those two arguments are accepted and ignored.
@@ -19,7 +20,7 @@
 #include <new>
 
 #include "common.hpp"
-#include "gn_solve.hpp"   // icp_finish_step, the solvers, se3_exp, kIcpBlocks / kIcpThreads / kIcpStateDoubles
+#include "gn_solve.hpp"   // the chain: gn_step_begin, gn_add_row, gn_block_sums, gn_finish_kernel, GnChain
 
 struct tsdf_icp {
     int width, height;
@@ -31,12 +32,7 @@ struct tsdf_icp {
     uint16_t *upload;                        // the host variants' image on the device
     float *vmap_prev[3], *nmap_prev[3];      // model
     float *vmap_curr[3], *nmap_curr[3];      // current frame
-    float *partial;                          // 2 x kIcpBlocks x 32 floats: per-block sums of the 29 products (two steps)
-    double *state;                           // device, 2 x kIcpStateDoubles: [0..15] T (column-major), [16..17] residual,
-                                             //         inliers, [18..53] A (float values), [54..59] b
-    int side;                                // which copy of state / partial holds the latest step
-    double *host_io;                         // pinned host memory the device reads and writes in place: [0..15] the pose an alignment starts from,
-    double *host_io_dev;                     // [16..33] its result (pose, residual, inliers) -- no copy launches either side of the chain (4-5 us each)
+    tsdf::GnChain chain;                     // state, partial sums and the pinned in/out block (its result 18 doubles wide)
 };
 
 namespace tsdf {
@@ -155,22 +151,11 @@ __device__ inline int float2int_rn(float f) {
 }
 
 // Reduction::operator() (Cuda/estimate.cu:139-209): projective association of the current frame's vertices into the
-// model, distance / angle gates, the 27 upper-triangular products of the row (n, v x n, n.(v_prev - v)) + inlier count.
-// The pose is read from the device state (T as doubles, narrowed to float like `rotationMatrix().cast<float>()`).
-// The sums of one Gauss-Newton step over this workgroup's share of the pixels, at the pose in `pose` (shared memory, doubles): per-thread
-// fp32 partial sums as the reference's, wave64 shuffle tree, the four waves in a fixed order -> partial_out[29] of this workgroup.
-__device__ __forceinline__ void icp_accumulate(const double *pose, const float *__restrict__ vmap_curr, const float *__restrict__ nmap_curr,
+// model, distance / angle gates, the row (n, v x n, n.(v_prev - v)) of every inlier into the thread's 29 sums, over this
+// workgroup's share of the pixels at the pose R, t.  Per-pixel arithmetic as the reference's.
+__device__ __forceinline__ void icp_accumulate(const float *R, const float *t, const float *__restrict__ vmap_curr, const float *__restrict__ nmap_curr,
                                                const float *__restrict__ vmap_prev, const float *__restrict__ nmap_prev, int rows, int cols,
-                                               float fx, float fy, float cx, float cy, float dist_thresh, float angle_thresh,
-                                               float *__restrict__ partial_out, float (*shared)[32]) {
-    float R[9], t[3];  // column-major
-    for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) R[c * 3 + r] = (float)pose[c * 4 + r];
-    for (int r = 0; r < 3; r++) t[r] = (float)pose[12 + r];
-
-    float sum[29];
-#pragma unroll
-    for (int i = 0; i < 29; i++) sum[i] = 0.0f;
+                                               float fx, float fy, float cx, float cy, float dist_thresh, float angle_thresh, float *sum) {
     const int N = rows * cols;
     for (int i = blockIdx.x * kIcpThreads + threadIdx.x; i < N; i += kIcpThreads * gridDim.x) {
         const int y = i / cols, x = i - y * cols;
@@ -204,39 +189,14 @@ __device__ __forceinline__ void icp_accumulate(const double *pose, const float *
                 row[4] = p2 * q0 - p0 * q2;
                 row[5] = p0 * q1 - p1 * q0;
                 row[6] = (q0 * d0 + q1 * d1) + q2 * d2;
-                int s = 0;
-#pragma unroll
-                for (int o = 0; o < 7; o++)
-#pragma unroll
-                    for (int in = o; in < 7; in++) sum[s++] += row[o] * row[in];
-                sum[28] += 1.0f;
+                gn_add_row(row, sum);
             }
         }
     }
-    // wave64 shuffle tree, then the four waves of the workgroup in a fixed order
-#pragma unroll
-    for (int i = 0; i < 29; i++) {
-        float v = sum[i];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        sum[i] = v;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 29; i++) shared[wave][i] = sum[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < 29) {
-        partial_out[threadIdx.x] =
-            ((shared[0][threadIdx.x] + shared[1][threadIdx.x]) + shared[2][threadIdx.x]) + shared[3][threadIdx.x];
-    }
 }
 
-// One Gauss-Newton step's sums.  `pending` != 0: the previous launch left its per-workgroup sums in partial_prev and the
-// pose they were taken at in state_in; EVERY workgroup finishes that step first (second reduction stage, solve, pose
-// update: icp_finish_step, the same fixed-order arithmetic, so all arrive at the same pose) and workgroup 0 records
-// it in state_out.  The kernel boundary orders the two launches -- no fence, no ticket, no workgroup waiting for the others
-// across the chip's eight L2s (that hand-over cost more than the whole reduction: 24 -> 14 us per step).
+// One Gauss-Newton step's sums: gn_step_begin (the step before is finished by every workgroup of this launch), the rows, the
+// workgroup's sums to partial[29] of this workgroup.
 __global__ __launch_bounds__(kIcpThreads) void icp_reduce_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
                                                                 const float *__restrict__ partial_prev, int pending,
                                                                 const float *__restrict__ vmap_curr,
@@ -246,39 +206,19 @@ __global__ __launch_bounds__(kIcpThreads) void icp_reduce_kernel(const double *_
                                                                 float fx, float fy, float cx, float cy, float dist_thresh,
                                                                 float angle_thresh, float *__restrict__ partial) {
     __shared__ double pose[16];
-    if (pending) {
-        icp_finish_step(partial_prev, (int)gridDim.x, state_in, 1, pose, blockIdx.x == 0 ? state_out : nullptr);
-    } else {
-        if (threadIdx.x < 16) {
-            pose[threadIdx.x] = state_in[threadIdx.x];
-            if (blockIdx.x == 0) state_out[threadIdx.x] = state_in[threadIdx.x];
-        }
-    }
-    __syncthreads();
-    __shared__ float shared[4][32];
-    icp_accumulate(pose, vmap_curr, nmap_curr, vmap_prev, nmap_prev, rows, cols, fx, fy, cx, cy, dist_thresh, angle_thresh,
-                   partial + blockIdx.x * 32, shared);
-}
-
-// Finishes the last step of a sequence (nothing follows whose prologue would): one workgroup.
-// `mirror` (pinned host memory, or null): pose, residual and inliers also go there, for the host to read after the stream's end.
-__global__ __launch_bounds__(kIcpThreads) void icp_finish_kernel(const double *__restrict__ state_in, double *__restrict__ state_out,
-                                                                const float *__restrict__ partial_prev, int n_blocks, int update,
-                                                                double *__restrict__ mirror) {
-    __shared__ double pose[16];
-    icp_finish_step(partial_prev, n_blocks, state_in, update, pose, state_out);
-    if (mirror && threadIdx.x == 0) {   // (thread 0 solved the step: what it has just written)
+    float R[9], t[3];
+    gn_step_begin(state_in, state_out, partial_prev, pending, (int)gridDim.x, 0.0f, pose, R, t);
+    float sum[29];
 #pragma unroll
-        for (int i = 0; i < 16; i++) mirror[i] = pose[i];
-        mirror[16] = state_out[16];
-        mirror[17] = state_out[17];
-    }
+    for (int i = 0; i < 29; i++) sum[i] = 0.0f;
+    icp_accumulate(R, t, vmap_curr, nmap_curr, vmap_prev, nmap_prev, rows, cols, fx, fy, cx, cy, dist_thresh, angle_thresh, sum);
+    gn_block_sums(sum, nullptr, partial);
 }
 
 static void free_icp(tsdf_icp *f) {
     for (int i = 0; i < kIcpLevels; i++) device_free_all(f->depth[i], f->vmap_prev[i], f->nmap_prev[i], f->vmap_curr[i], f->nmap_curr[i]);
-    device_free_all(f->upload, f->partial, f->state);
-    (void)hipHostFree(f->host_io);
+    device_free_all(f->upload);
+    f->chain.free();
     delete f;
 }
 
@@ -312,25 +252,19 @@ static int build_maps(tsdf_icp *f, const uint16_t *depth0, float **vmaps, float 
 // `start` (pending == 0 only): where the pose to start from lies, if not in the device state (the host's pinned copy).
 static void launch_step(tsdf_icp *f, int level, int pending, const double *start = nullptr) {
     const int rows = f->height >> level, cols = f->width >> level, div = 1 << level;
-    const int in = f->side, out = 1 - f->side;
-    hipLaunchKernelGGL(icp_reduce_kernel, dim3(kIcpBlocks), dim3(kIcpThreads), 0, f->stream, start ? start : f->state + in * kIcpStateDoubles,
-                       f->state + out * kIcpStateDoubles, f->partial + (size_t)in * kIcpBlocks * 32, pending, f->vmap_curr[level],
-                       f->nmap_curr[level], f->vmap_prev[level], f->nmap_prev[level], rows, cols, f->fx / div, f->fy / div,
-                       f->cx / div, f->cy / div, f->dist_thresh, f->angle_thresh, f->partial + (size_t)out * kIcpBlocks * 32);
-    f->side = out;
-}
-
-// Finishes the step whose sums the last launch_step left (with or without the pose update).
-static void launch_finish(tsdf_icp *f, int update, double *mirror = nullptr) {
-    const int in = f->side, out = 1 - f->side;
-    hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(kIcpThreads), 0, f->stream, f->state + in * kIcpStateDoubles,
-                       f->state + out * kIcpStateDoubles, f->partial + (size_t)in * kIcpBlocks * 32, kIcpBlocks, update, mirror);
-    f->side = out;
+    GnChain &c = f->chain;
+    hipLaunchKernelGGL(icp_reduce_kernel, dim3(kIcpBlocks), dim3(kIcpThreads), 0, f->stream, start ? start : c.state_in(), c.state_out(),
+                       c.partial_in(), pending, f->vmap_curr[level], f->nmap_curr[level], f->vmap_prev[level], f->nmap_prev[level], rows, cols,
+                       f->fx / div, f->fy / div, f->cx / div, f->cy / div, f->dist_thresh, f->angle_thresh, c.partial_out());
+    c.flip();
 }
 
 void launch_gn_finish(hipStream_t stream, const double *state_in, double *state_out, const float *partial_prev, int n_blocks, int update,
-                      double *mirror) {
-    hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(kIcpThreads), 0, stream, state_in, state_out, partial_prev, n_blocks, update, mirror);
+                      double *mirror, const float *colour_weight) {
+    if (colour_weight)
+        hipLaunchKernelGGL(gn_finish_kernel<true>, dim3(1), dim3(kIcpThreads), 0, stream, state_in, state_out, partial_prev, n_blocks, update, *colour_weight, mirror);
+    else
+        hipLaunchKernelGGL(gn_finish_kernel<false>, dim3(1), dim3(kIcpThreads), 0, stream, state_in, state_out, partial_prev, n_blocks, update, 0.0f, mirror);
 }
 
 }  // namespace tsdf
@@ -361,12 +295,7 @@ int tsdf_icp_create(int width, int height, float cx, float cy, float fx, float f
             if (e == hipSuccess) e = hipMemset(*maps[m], 0, px * 3 * sizeof(float));
         }
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&f->partial, (size_t)2 * kIcpBlocks * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->state, 2 * kIcpStateDoubles * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(f->state, 0, 2 * kIcpStateDoubles * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&f->host_io, (16 + 18) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);   // (fine-grained: the device reads and writes it past its caches)
-    if (e == hipSuccess) std::memset(f->host_io, 0, (16 + 18) * sizeof(double));
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&f->host_io_dev, f->host_io, 0);
+    if (e == hipSuccess) e = f->chain.alloc(18);
     if (e != hipSuccess) {
         free_icp(f);
         return hip_fail(e, "ICP alloc failed");
@@ -433,18 +362,11 @@ int tsdf_icp_estimate_step(tsdf_icp *f, int level, const float R[9], const float
         for (int r = 0; r < 3; r++) T[c * 4 + r] = R[c * 3 + r];
     for (int r = 0; r < 3; r++) T[12 + r] = t[r];
     T[15] = 1.0;
-    TSDF_HIP(hipMemcpyAsync(f->state + f->side * kIcpStateDoubles, T, sizeof(T), hipMemcpyHostToDevice, f->stream), "ICP pose upload");
+    TSDF_HIP(hipMemcpyAsync(f->chain.state_in(), T, sizeof(T), hipMemcpyHostToDevice, f->stream), "ICP pose upload");
     launch_step(f, level, 0);
-    launch_finish(f, 0);
+    f->chain.finish(f->stream, kIcpBlocks, 0, nullptr);
     TSDF_HIP(hipGetLastError(), "ICP estimate kernels failed");
-    double out[kIcpStateDoubles];
-    TSDF_HIP(hipMemcpyAsync(out, f->state + f->side * kIcpStateDoubles, sizeof(out), hipMemcpyDeviceToHost, f->stream), "ICP result download");
-    TSDF_HIP(hipStreamSynchronize(f->stream), "ICP estimate");
-    residual_inliers[0] = (float)out[16];
-    residual_inliers[1] = (float)out[17];
-    for (int i = 0; i < 36; i++) A[i] = (float)out[18 + i];
-    for (int i = 0; i < 6; i++) b[i] = (float)out[54 + i];
-    return TSDF_OK;
+    return f->chain.download(f->stream, A, b, residual_inliers, 1, "ICP result download", "ICP estimate");
 }
 
 int tsdf_icp_get_incremental_transformation(tsdf_icp *f, double T_prev_curr[16], float *last_error, float *last_inliers) {
@@ -453,18 +375,18 @@ int tsdf_icp_get_incremental_transformation(tsdf_icp *f, double T_prev_curr[16],
     // The pose goes to the device and the result comes back through pinned host memory that the first and the last launch of the chain
     // address directly (every call ends with the stream idle, so the host may write it here): the two 128-byte copies were launches of
     // their own on the stream, 4-5 us each plus their boundaries, on the path every tracked frame waits for.
-    std::memcpy(f->host_io, T_prev_curr, 16 * sizeof(double));
+    std::memcpy(f->chain.host_io, T_prev_curr, 16 * sizeof(double));
     int pending = 0;   // every launch finishes the step before it, the last step gets a launch of its own
     for (int i = kIcpLevels - 1; i >= 0; i--)
         for (int j = 0; j < iterations[i]; j++) {
-            launch_step(f, i, pending, pending ? nullptr : f->host_io_dev);
+            launch_step(f, i, pending, pending ? nullptr : f->chain.host_io_dev);
             pending = 1;
         }
-    launch_finish(f, 1, f->host_io_dev + 16);
+    f->chain.finish(f->stream, kIcpBlocks, 1, f->chain.host_io_dev + 16);
     TSDF_HIP(hipGetLastError(), "ICP kernels failed");
     TSDF_HIP(hipStreamSynchronize(f->stream), "ICP");   // (polling a ticket in the pinned block instead: 0.5-1 %, not kept)
     double out[18];
-    std::memcpy(out, f->host_io + 16, sizeof(out));
+    std::memcpy(out, f->chain.host_io + 16, sizeof(out));
     std::memcpy(T_prev_curr, out, 16 * sizeof(double));
     // lastError = sqrt(residual) / inliers, lastInliers = inliers of the last iteration (ICPOdometry.cpp:127-128)
     if (last_error) *last_error = sqrtf((float)out[16]) / (float)out[17];
