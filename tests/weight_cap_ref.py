@@ -12,10 +12,10 @@ import numpy as np
 from tests.helpers import H, W
 
 
-def oracle_step(O, ov, depth, cam, cap=0):
+def oracle_step(O, ov, depth, cam, cap=0, width=W, height=H):
     """One integrate of `ov` (oracle.Volume) with weight cap `cap` (0: none)."""
     before = ov.weight.view(np.uint32).copy()
-    ov.integrate(depth, W, H, cam.inverse_pose(), cam.k(), cam.kinv(), nthreads=O.max_threads())
+    ov.integrate(depth, width, height, cam.inverse_pose(), cam.k(), cam.kinv(), nthreads=O.max_threads())
     if cap:
         updated = ov.weight.view(np.uint32) != before
         w = ov.weight.copy()

@@ -328,7 +328,7 @@ struct tsdf_volume {
     int occ_tighten_pending;    // ... that the volume's own stream has not waited for yet
     int reach_dirty; // 1 = `fine` changed since `reach` was computed
     uint16_t *occ_bits;              // 16 summary bits per brick, kept between rebuilds (volume.hip)
-    uint8_t *occ_rim_bits;           // 8 more: which 2^3-voxel octants hold a voxel that is not flat (read for boundary bricks only)
+    uint8_t *occ_rim_bits;           // 8 more: which 2^3-voxel octants hold a voxel that is not flat (read for boundary bricks only; kept current beside them too)
     // A rebuild reads only the distances integrate has written since the previous one: integrate_kernel marks its brick in
     // `touched` (one byte per integrate brick, index order) when it stored a distance there -- a store that would write back
     // the same bits is skipped -- the scan skips the others and their summary bits stand.

@@ -184,7 +184,18 @@ __global__ __launch_bounds__(256) void occupancy_scan_kernel(const float *__rest
         // (or, in the rim zone, not flat) -- so a brick whose flag is clear holds no such voxel now, held none when its flag was last
         // computed (b lies inside its own grown box), and its summary bits, all zero since then, still say so.  2 % of the bricks
         // integrate touches hold a flag: the scan of a 512^3 stream fell from 40-60 us to a few.
-        scan = scan && bx < occ.nbx && occ.fine[((size_t)bz * occ.nby + by) * occ.nbx + bx] != 0;
+        // That argument is about the bits of `bits`.  The rim bits of a brick NEXT TO a boundary brick are read by that neighbour, and such
+        // a brick's own flag says nothing about them: it is clear while the brick holds values that are safely positive but not flat.
+        // When a writer that keeps the invariant lifts those back into the flat band -- a removal, a blend towards +trunc -- it marks
+        // nothing, and skipping the brick would leave its rim bits standing and the boundary brick flagged for good: a superset still,
+        // but not what a rebuild promises (tests/test_op_sequences.py::test_a_rebuild_clears_the_flag_of_a_boundary_brick...).  So a
+        // brick within one of the boundary is also scanned when its rim bits are not zero.
+        if (scan && bx < occ.nbx) {
+            const size_t at = ((size_t)bz * occ.nby + by) * occ.nbx + bx;
+            const bool beside_rim = bx <= 1u || by <= 1u || bz <= 1u || bx + 2u >= occ.nbx || by + 2u >= occ.nby || bz + 2u >= occ.nbz;
+            scan = occ.fine[at] != 0 || (beside_rim && rim_bits[at] != 0);
+        } else
+            scan = false;
         if (__syncthreads_or(scan) == 0) continue;   // nothing in reach of this row needs a look
     }
     if (threadIdx.x < 64) acc[threadIdx.x] = 0;
