@@ -315,6 +315,67 @@ int tsdf_deintegrate(tsdf_volume *volume, const uint16_t *host_depth, uint32_t w
 int tsdf_deintegrate_device(tsdf_volume *volume, const uint16_t *device_depth, uint32_t width, uint32_t height,
                             const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]);
 
+/* ---- weighted integration (what the reference's current_weight was for: src/TSDF/TSDFVolume.cu:375-381 sets it to 1.0f) ------------- */
+/* tsdf_integrate_weighted* takes the arguments of tsdf_integrate_colour* plus one fp32 weight per pixel (width * height floats, row
+ * major like the depth image; rgb may be NULL).  A volume on which it is never called launches and allocates nothing new.
+ *   - valid pixels: a pixel takes part iff its depth is > 0 and its weight p is finite and > 0.  Every other pixel -- p = 0, -0,
+ *     negative, NaN, +-inf -- is treated exactly as if its depth were 0: for culling, the distance update, the colour update and the
+ *     counters.  (The call works on a masked copy of the depth image in scratch owned by the volume.)  The caller's arrays are only read;
+ *   - blend: on every voxel tsdf_integrate would update for that masked image, with p the weight of the voxel's pixel, w = prior_weight
+ *     and D = prior_distance, in fp32, every operation rounded on its own, no contraction, in this order:
+ *           nw = w + p
+ *           new_distance = ((D * w) + (tsdf * p)) / nw
+ *           stored weight = nw                                        without a weight cap
+ *                         = nw > (float)cap ? (float)cap : nw         with one (tsdf_volume_set_weight_cap: the cap's comparison form;
+ *                                                                     the divisor is never clamped, a NaN weight stays NaN)
+ *   - unit property: with every p == 1.0f, distances, weights, colour words, occupancy marks and counters are bit for bit what
+ *     tsdf_integrate* / tsdf_integrate_colour* leave on a volume with fp32 weights;
+ *   - storage: the call moves the volume to fp32 weights first (tsdf_volume_weight_storage reports 32); counts already fused keep their
+ *     values as floats.  It never narrows; tsdf_volume_clear returns an unpinned volume to its starting mode, as after any widening;
+ *   - volumes with explicit deformation nodes, cameras not of the standard shape and Z-slab volumes are served (a slab updates its own
+ *     planes; the caller integrates on every slab of a grid);
+ *   - a distance whose bits stay is not stored, a weight whose bits stay neither; occupancy stays a conservative superset: a ray cast
+ *     after weighted frames gives exactly the picture it gives after a forced rebuild of the flags;
+ *   - colour: rgb != NULL on a colour volume gives exactly the colour words tsdf_integrate_colour gives for the masked image; the
+ *     colour counts are not weighted.  On a volume without colour (or with explicit nodes) rgb != NULL is refused, as
+ *     tsdf_integrate_colour is;
+ *   - tsdf_volume_last_updated_voxels / tsdf_volume_last_distance_stores count as for tsdf_integrate of the masked image;
+ *   - there is no weighted removal: fl(fl(w + p) - p) is not w.  tsdf_deintegrate* keeps its formula on whatever weights it finds;
+ *   - refused (TSDF_ERR_INVALID, with a message): a NULL weight array, and whatever tsdf_integrate refuses;
+ *   - tsdf_pipeline_step* does not take weights (its prepared culling recognises a frame by its pointer); tsdf_tracker_set_weighting does.
+ * Host variant: blocking, arrays in host memory.  Device variant: arrays in HBM, asynchronous on the volume's stream; the arrays must
+ * stay valid until the call's work on that stream is done. */
+int tsdf_integrate_weighted(tsdf_volume *volume, const uint16_t *host_depth, const float *host_pixel_weight, const uint8_t *host_rgb /* or NULL */,
+                            uint32_t width, uint32_t height, const float pose[16], const float inv_pose[16], const float k[9],
+                            const float kinv[9]);
+int tsdf_integrate_weighted_device(tsdf_volume *volume, const uint16_t *device_depth, const float *device_pixel_weight,
+                                   const uint8_t *device_rgb /* or NULL */, uint32_t width, uint32_t height, const float pose[16],
+                                   const float inv_pose[16], const float k[9], const float kinv[9]);
+/* The standard weight models of a depth frame, for callers without a confidence plane: one fp32 weight per pixel, 0 where the depth
+ * is 0, else the product of the factors `flags` selects (flags == 0: 1).  fp32, every operation rounded on its own (division and sqrtf
+ * correctly rounded), in exactly this order, d = (float)depth:
+ *       w = 1
+ *   TSDF_WEIGHTS_INVERSE_SQUARE (the sensor's noise grows with z^2):
+ *       r = z_ref / d ;  f = r * r ;  f = f > 1 ? 1 : f ;  w = w * f
+ *     z_ref is in depth units (readings at or nearer than z_ref count fully); not finite or not > 0 is refused with this flag.
+ *   TSDF_WEIGHTS_COSINE (the cosine of the incidence angle, from central differences of the back-projected image):
+ *       P(x, y) = (ip * (d(x, y) / ip.z)) with ip = ((kinv.m11 * x + kinv.m12 * y) + kinv.m13, ... rows 2 and 3 alike), each component
+ *                 ip.c * scale -- the point tsdf_depth_to_points_device forms
+ *       a = P(x + 1, y) - P(x - 1, y) ;  b = P(x, y + 1) - P(x, y - 1)
+ *       n = (a.y * b.z - a.z * b.y,  a.z * b.x - a.x * b.z,  a.x * b.y - a.y * b.x)
+ *       np = (n.x * P.x + n.y * P.y) + n.z * P.z ;  nn = (n.x * n.x + n.y * n.y) + n.z * n.z ;  pp = (P.x * P.x + P.y * P.y) + P.z * P.z
+ *       c = fabsf(np) / (sqrtf(nn) * sqrtf(pp)) ;  c = c > 1 ? 1 : c ;  c = c > 0 ? c : 0 ;  w = w * c
+ *     A pixel with a neighbour off the image or of depth 0 has c = 0 (silhouettes and flying pixels are not fused), and so has one
+ *     whose c is not > 0 (NaN included).
+ * With both flags the inverse-square factor is multiplied in first.  Unknown flag bits, NULL arrays and images wider or higher than
+ * 65535 are refused.  The depth image is only read.  Device variant: asynchronous on hip_stream; host variant: blocking. */
+#define TSDF_WEIGHTS_INVERSE_SQUARE 1u
+#define TSDF_WEIGHTS_COSINE 2u
+int tsdf_depth_weights_device(uint32_t width, uint32_t height, const uint16_t *device_depth, const float kinv[9], uint32_t flags, float z_ref,
+                              float *device_weight, void *hip_stream);
+int tsdf_depth_weights(uint32_t width, uint32_t height, const uint16_t *host_depth, const float kinv[9], uint32_t flags, float z_ref,
+                       float *host_weight);
+
 /* ---- colour fusion (no reference counterpart: the reference allocates a uchar3 colour per voxel, src/include/TSDFVolume.hpp:290-293,
  * that none of its kernels writes) --------------------------------------------------------------------------------------------- */
 /* Opt-in per volume.  A volume that never enables colour behaves exactly as without this group: no allocation, no launch.
@@ -1374,6 +1435,14 @@ int tsdf_tracker_integrate_colour(tsdf_tracker *tracker, const tsdf_camera_matri
  * is left as it is. */
 int tsdf_tracker_set_window(tsdf_tracker *tracker, uint32_t n);
 int tsdf_tracker_window(const tsdf_tracker *tracker, uint32_t *n);
+/* Weighted tracking ("weighted integration"): flags = 0 (the default) is off -- the plain integrate, nothing allocated.  With flags a
+ * combination of TSDF_WEIGHTS_*, tsdf_tracker_integrate and tsdf_tracker_integrate_colour compute that model's weights from the filtered
+ * frame they hold (tsdf_depth_weights_device with the camera's kinv and z_ref, on the tracker's main stream, into a buffer made on the
+ * first such frame) and fuse it with tsdf_integrate_weighted_device: the volume goes to fp32 weights.  Refused with a message
+ * (TSDF_ERR_INVALID) as tsdf_depth_weights refuses flags and z_ref, and together with a window, in either order: there is no weighted
+ * removal. */
+int tsdf_tracker_set_weighting(tsdf_tracker *tracker, uint32_t flags, float z_ref);
+int tsdf_tracker_weighting(const tsdf_tracker *tracker, uint32_t *flags, float *z_ref /* or NULL */);
 int tsdf_tracker_synchronize(tsdf_tracker *tracker);
 int tsdf_tracker_streams(const tsdf_tracker *tracker, void **main_stream, void **side_stream);
 /* The ICP inputs of the last aligned frame: the rendered model depth and the filtered frame (width * height uint16, device). */

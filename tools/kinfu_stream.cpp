@@ -8,7 +8,11 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE] [--weights inverse-square[,cosine]] [--weight-ref MM]
+//   --weights LIST (with --track): tsdf_tracker_set_weighting -- every tracked frame is fused with the weights of the standard models in
+//           LIST (inverse-square, cosine, comma separated: tsdf_depth_weights_device on the filtered frame, tsdf_integrate_weighted_device);
+//           --weight-ref MM is the inverse-square model's z_ref in millimetres (required with it, > 0); refused without --track, with
+//           --window (there is no weighted removal) and with an unknown model; the line gains "weights": "LIST" and "weight_ref": MM.
 //   --save-sparse FILE: at the end of the run the volume's live bricks and header as a .tsdfs file (TSDFVolume::save_sparse);
 //           the line gains "sparse_file_bytes"; refused with --ranks above 1 (Z-slabs have no snapshot).
 //   --colour-weight W (with --track --field): W > 0 aligns every tracked frame with the colour term as well (tsdf_tracker_align_field_colour:
@@ -143,6 +147,9 @@ int main(int argc, char **argv) {
     long window = 0;
     double colour_weight = 0.0;
     bool colour_weight_given = false;
+    std::string weights_list;
+    double weight_ref = 0.0;
+    unsigned weight_flags = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&]() -> const char * {
@@ -170,12 +177,14 @@ int main(int argc, char **argv) {
         else if (a == "--weight-cap") weight_cap = std::atol(value());
         else if (a == "--window") window = std::atol(value());
         else if (a == "--save-sparse") sparse_file = value();
+        else if (a == "--weights") weights_list = value();
+        else if (a == "--weight-ref") weight_ref = std::atof(value());
         else if (a == "--colour-weight") {
             colour_weight = std::atof(value());
             colour_weight_given = true;
         }
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE] [--weights inverse-square[,cosine]] [--weight-ref MM]\n");
             return 2;
         }
     }
@@ -190,6 +199,25 @@ int main(int argc, char **argv) {
     }
     if (window < 0 || window > 65535 || (window && (!track || weight_cap || ranks > 1))) {
         std::fprintf(stderr, "kinfu_stream: --window is 0 (off) or 1 .. 65535 frames; it needs --track and goes with neither --weight-cap nor --ranks\n");
+        return 2;
+    }
+    if (!weights_list.empty()) {
+        bool known = true;
+        for (size_t at = 0; at <= weights_list.size();) {
+            const size_t comma = std::min(weights_list.find(',', at), weights_list.size());
+            const std::string name = weights_list.substr(at, comma - at);
+            if (name == "inverse-square") weight_flags |= TSDF_WEIGHTS_INVERSE_SQUARE;
+            else if (name == "cosine") weight_flags |= TSDF_WEIGHTS_COSINE;
+            else known = false;
+            at = comma + 1;
+        }
+        const bool ref_ok = !(weight_flags & TSDF_WEIGHTS_INVERSE_SQUARE) || (weight_ref > 0.0 && weight_ref < 1.0e30);
+        if (!known || !track || window || !ref_ok) {
+            std::fprintf(stderr, "kinfu_stream: --weights takes inverse-square and cosine (comma separated); it needs --track, does not go with --window, and inverse-square needs --weight-ref MM > 0\n");
+            return 2;
+        }
+    } else if (weight_ref != 0.0) {
+        std::fprintf(stderr, "kinfu_stream: --weight-ref goes with --weights inverse-square\n");
         return 2;
     }
     if (field && (!track || ranks > 1)) {
@@ -352,6 +380,7 @@ int main(int argc, char **argv) {
         ok(tsdf_icp_create((int)W, (int)H, k(0, 2), k(1, 2), k(0, 0), k(1, 1), 0.10f, sinf(20.f * 3.14159254f / 180.f), &icp), "ICP");   // ICPOdometry.h:27
         ok(tsdf_tracker_create(vol, bil, icp, W, H, 20.0f, overlap ? TSDF_PIPELINE_OVERLAP : 0, &trk), "tracker");
         if (window) ok(tsdf_tracker_set_window(trk, (uint32_t)window), "window");
+        if (weight_flags) ok(tsdf_tracker_set_weighting(trk, weight_flags, (float)weight_ref), "weighting");
         const size_t n_track = std::min(F, (size_t)K);
         std::vector<float> tracked;
         float error = 0.f, inliers = 0.f, colour_inliers = 0.f;
@@ -413,6 +442,7 @@ int main(int argc, char **argv) {
                     inliers, error);
         if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
         if (window) std::printf(", \"window\": %ld", window);
+        if (weight_flags) std::printf(", \"weights\": \"%s\", \"weight_ref\": %g", weights_list.c_str(), weight_ref);
         if (field) std::printf(", \"align\": \"field\"");
         if (colour_weight_given) std::printf(", \"colour_weight\": %g, \"last_colour_inliers\": %.0f", colour_weight, colour_inliers);
         if (!sparse_file.empty()) std::printf(", \"sparse_file_bytes\": %lld", save_sparse_file(vol, sparse_file));

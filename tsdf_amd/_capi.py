@@ -19,6 +19,7 @@ TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
 TSDF_SCENE_FLOW_DEFORMED = 1
 TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
+TSDF_WEIGHTS_INVERSE_SQUARE, TSDF_WEIGHTS_COSINE = 1, 2
 
 
 class TsdfError(RuntimeError):
@@ -156,6 +157,10 @@ _SIGS = {
     "tsdf_integrate_device": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
     "tsdf_deintegrate": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
     "tsdf_deintegrate_device": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_integrate_weighted": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_integrate_weighted_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_depth_weights": (_i, [_u32, _u32, _vp, _fp, _u32, _f, _vp]),
+    "tsdf_depth_weights_device": (_i, [_u32, _u32, _vp, _fp, _u32, _f, _vp, _vp]),
     "tsdf_integrate_device_tiles": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _vp]),
     "tsdf_integrate_prepare_device_tiles": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _vp, _vp]),
     "tsdf_integrate_discard_prepared": (_i, [_vp]),
@@ -280,6 +285,8 @@ _SIGS = {
     "tsdf_tracker_integrate_colour": (_i, [_vp, C.POINTER(CameraMatrices), _vp]),
     "tsdf_tracker_set_window": (_i, [_vp, _u32]),
     "tsdf_tracker_window": (_i, [_vp, C.POINTER(C.c_uint32)]),
+    "tsdf_tracker_set_weighting": (_i, [_vp, _u32, _f]),
+    "tsdf_tracker_weighting": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "tsdf_tracker_synchronize": (_i, [_vp]),
     "tsdf_tracker_streams": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_tracker_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -280,6 +280,33 @@ class TSDFVolume:
         pose, ipose, k, kinv = _camera_matrices(camera)
         check(lib.tsdf_deintegrate_device(self._h, C.c_void_p(int(depth_ptr)), width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
 
+    # ---- weighted integration (include/tsdf_amd.h, "weighted integration"; not in the reference's class)
+    def integrate_weighted(self, depth_map, weights, width, height, camera, rgb=None):
+        """integrate() with one float32 weight per pixel: a pixel whose weight is not finite and > 0 counts as a pixel without depth.
+        `rgb` (uint8, width*height*3) adds the colour update on a colour volume.  The volume goes to fp32 weights.  Blocking."""
+        d = np.ascontiguousarray(depth_map, dtype=np.uint16).reshape(-1)
+        if weights is None:
+            raise ValueError("integrate_weighted: weights is None")
+        p = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if d.size != width * height or p.size != width * height:
+            raise ValueError("expected %d depth pixels and as many weights, got %d and %d" % (width * height, d.size, p.size))
+        c = None
+        if rgb is not None:
+            c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1)
+            if c.size != 3 * width * height:
+                raise ValueError("expected %d colour bytes, got %d" % (3 * width * height, c.size))
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_integrate_weighted(self._h, d.ctypes.data, p.ctypes.data, c.ctypes.data if c is not None else None, width, height,
+                                          _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
+    def integrate_weighted_device(self, depth_ptr, weights_ptr, width, height, camera, rgb_ptr=None):
+        """Asynchronous on the volume's stream; device pointers to width*height uint16, width*height float32 and (optionally)
+        width*height*3 uint8."""
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_integrate_weighted_device(self._h, C.c_void_p(int(depth_ptr)) if depth_ptr else None,
+                                                 C.c_void_p(int(weights_ptr)) if weights_ptr else None,
+                                                 C.c_void_p(int(rgb_ptr)) if rgb_ptr else None, width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
     def integrate_prepare_device(self, depth_ptr, width, height, camera, tile_max_ptr, stream):
         """The brick culling of integrate_device(depth_ptr, ..., tile_max_ptr=...) ahead of time, on `stream` (see
         tsdf_integrate_prepare_device_tiles); the matching integrate_device call then launches the integrate kernel alone."""
@@ -1620,6 +1647,30 @@ def depth_to_points(depth, width, height, kinv, step=1, depth_cutoff=float("inf"
         depth_to_points_device(width, height, dd.ptr.value, kinv, step, depth_cutoff, dp.ptr.value)
         check(lib.tsdf_stream_synchronize(None))
         check(lib.tsdf_device_download(out.ctypes.data, dp.ptr, out.nbytes))
+    return out
+
+
+#: tsdf_depth_weights flags (include/tsdf_amd.h, "weighted integration")
+WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE = _capi.TSDF_WEIGHTS_INVERSE_SQUARE, _capi.TSDF_WEIGHTS_COSINE
+
+
+def depth_weights_device(width, height, depth_ptr, kinv, flags, z_ref, weights_ptr, stream=0):
+    """tsdf_depth_weights_device: the standard weight models of a uint16 depth image on the device -> width * height float32;
+    asynchronous on `stream`."""
+    check(lib.tsdf_depth_weights_device(int(width), int(height), C.c_void_p(int(depth_ptr)) if depth_ptr else None, _fp(_mat(kinv, 9)),
+                                        int(flags), float(z_ref), C.c_void_p(int(weights_ptr)) if weights_ptr else None,
+                                        C.c_void_p(int(stream) if stream else 0)))
+
+
+def depth_weights(depth, width, height, kinv, flags=0, z_ref=0.0):
+    """Host uint16 depth image -> (height, width) float32 weights: 0 where the depth is 0, else the product of the factors `flags`
+    selects (WEIGHTS_INVERSE_SQUARE: min(1, (z_ref / depth)^2); WEIGHTS_COSINE: the cosine of the incidence angle, 0 on silhouettes)."""
+    d = np.ascontiguousarray(depth, dtype=np.uint16).reshape(-1)
+    width, height = int(width), int(height)
+    if d.size != width * height:
+        raise ValueError("depth has %d pixels, expected %d" % (d.size, width * height))
+    out = np.empty((height, width), np.float32)
+    check(lib.tsdf_depth_weights(width, height, d.ctypes.data, _fp(_mat(kinv, 9)), int(flags), float(z_ref), out.ctypes.data))
     return out
 
 

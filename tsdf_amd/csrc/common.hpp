@@ -369,6 +369,12 @@ struct tsdf_volume {
     uint8_t *rgb_buf;
     size_t rgb_cap;
     int slab;                 // made by tsdf_volume_create_slab (colour is refused there)
+    // weighted integration (integrate_weighted.hip): the frame's depth with the pixels of invalid weight zeroed, and the host variant's
+    // upload of the pixel weights; both empty until the first weighted frame
+    uint16_t *wdepth_buf;
+    size_t wdepth_cap;
+    float *pweight_buf;
+    size_t pweight_cap;
     // volume fusion (fuse.hip), as the destination: the fused-voxel counter, the list of destination bricks and the source's summary
     void *fuse_scratch;
     size_t fuse_scratch_cap;

@@ -296,8 +296,9 @@ __global__ __launch_bounds__(256) void brick_cull_kernel(const Geom g, const Bri
         const uint32_t *__restrict__ count, const float4 *__restrict__ plane_const, uint8_t *__restrict__ touched
 template <bool DEFORM, bool COUNT, bool STD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_kernel(TSDF_INTEGRATE_PARAMS) {
-    constexpr bool CAPPED = false, REMOVE = false;
+    constexpr bool CAPPED = false, REMOVE = false, WEIGHTED = false;
     const float capf = 0.0f;
+    const float *const pweight = nullptr;
 #include "integrate_body.hpp"
 }
 
@@ -305,7 +306,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // clamped to the cap.  A kernel of its own name: the plain kernels and their rocprof rows stay as they are.  capf = (float)cap, exact.
 template <bool DEFORM, bool COUNT, bool STD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_capped_kernel(TSDF_INTEGRATE_PARAMS, const float capf) {
-    constexpr bool CAPPED = true, REMOVE = false;
+    constexpr bool CAPPED = true, REMOVE = false, WEIGHTED = false;
+    const float *const pweight = nullptr;
 #include "integrate_body.hpp"
 }
 
@@ -314,8 +316,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // its own name: the plain kernels and their rocprof rows stay as they are.
 template <bool DEFORM, bool COUNT, bool STD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_remove_kernel(TSDF_INTEGRATE_PARAMS) {
-    constexpr bool CAPPED = false, REMOVE = true;
+    constexpr bool CAPPED = false, REMOVE = true, WEIGHTED = false;
     const float capf = 0.0f;
+    const float *const pweight = nullptr;
+#include "integrate_body.hpp"
+}
+
+// Weighted integration (include/tsdf_amd.h, "weighted integration"): the same walk on fp32 weights, the frame's `1.0f` replaced by the
+// weight of the voxel's pixel.  `depth` is the masked image (integrate_weighted.hip: 0 wherever the pixel's weight is not finite and
+// > 0), so every weight read here is a valid one.  pweight is gathered from L2 (1.2 MB at 640 x 480) with the batch's distance and weight
+// loads: an fp32 tile beside the 16 KiB depth tile would cost the 6 waves a SIMD the walk is built for.  The stored weight takes the
+// cap's comparison form; capf = +INFINITY is "no cap".  A kernel of its own name: the plain kernels and their rocprof rows stay as they are.
+template <bool DEFORM, bool COUNT, bool STD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void integrate_weighted_kernel(TSDF_INTEGRATE_PARAMS, const float capf,
+                                                                                                            const float *__restrict__ pweight) {
+    constexpr bool CAPPED = true, REMOVE = false, WEIGHTED = true;
 #include "integrate_body.hpp"
 }
 #undef TSDF_INTEGRATE_PARAMS
@@ -330,7 +345,8 @@ enum IntegratePhase { kIntBoth = 0, kIntPrepare = 1 };
 static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t width, uint32_t height,
                             const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *caller_tile_max = nullptr,
                             IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr, const uint8_t *d_rgb = nullptr,
-                            bool remove = false) {
+                            bool remove = false, const float *d_pweight = nullptr) {
+    // d_pweight: tsdf_integrate_weighted* -- d_depth is then the masked image and the weights are fp32 already (integrate_weighted below)
     Mat44 ip;
     Mat33 mk, mkinv;
     memcpy(&ip, inv_pose, sizeof(ip));
@@ -480,7 +496,11 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     const float capf = (float)v->weight_cap;   // (at most 65535: exact)
 #define LAUNCH(DEF, CNT, STDC)                                                                                       \
     do {                                                                                                             \
-        if (remove)                                                                                                  \
+        if (d_pweight)                                                                                               \
+            TSDF_LAUNCH_TIMED(v, 0, (integrate_weighted_kernel<DEF, CNT, STDC>), grid, block, v->dist, v->weight, v->nodes, g, bg, ip, mk, mkinv, \
+                              width, height, d_depth, counter_arg, v->occ, v->brick_list, boxes, count, plane_const, v->touched,               \
+                              v->weight_cap ? capf : INFINITY, d_pweight);                                                                    \
+        else if (remove)                                                                                             \
             TSDF_LAUNCH_TIMED(v, 0, (integrate_remove_kernel<DEF, CNT, STDC>), grid, block, v->dist, v->weight, v->nodes, \
                               g, bg, ip, mk, mkinv, width, height, d_depth, counter_arg, v->occ, v->brick_list, boxes, count, plane_const, v->touched); \
         else if (v->weight_cap)                                                                                      \
@@ -537,6 +557,16 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
 int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
                           const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max) {
     return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, tile_max, kIntBoth, nullptr, d_rgb);
+}
+
+// tsdf_integrate_weighted_device (integrate_weighted.hip): d_masked is the depth image with the pixels of invalid weight zeroed; the
+// volume goes to fp32 weights first (it stays there until clear(), as after any widening), then the usual culling, integrate_weighted_kernel
+// and -- with d_rgb -- the colour pass over the masked image
+int integrate_weighted(tsdf_volume *v, const uint16_t *d_masked, const float *d_pweight, const uint8_t *d_rgb, uint32_t width, uint32_t height,
+                       const float inv_pose[16], const float k[9], const float kinv[9]) {
+    const int rc = weights_require_f32(v);
+    if (rc != TSDF_OK) return rc;
+    return launch_integrate(v, d_masked, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, d_rgb, false, d_pweight);
 }
 
 }  // namespace tsdf

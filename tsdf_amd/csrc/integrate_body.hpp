@@ -1,6 +1,8 @@
 // The body of integrate_kernel and integrate_capped_kernel (integrate.hip), included inside each of the two: not a header (see
 // integrate_packed_body.hpp).  The including kernel declares `constexpr bool CAPPED`, `capf`, the weight cap as a float, and
-// `constexpr bool REMOVE` (integrate_remove_kernel: the frame is taken back out, include/tsdf_amd.h "de-integration").
+// `constexpr bool REMOVE` (integrate_remove_kernel: the frame is taken back out, include/tsdf_amd.h "de-integration") and
+// `constexpr bool WEIGHTED` with `pweight` (integrate_weighted_kernel: one weight per pixel of the frame, include/tsdf_amd.h "weighted
+// integration"; the other kernels declare it false and never read the pointer).
     // Depth tile of the current brick: the pixel box the cull kernel derived for it, staged once per brick with
     // coalesced row loads; the per-voxel depth look-ups then read LDS instead of gathering from L2.
     __shared__ uint16_t tile[kTilePixels + 2];  // [kTilePixels] stays 0: where look-ups that miss the box are pointed
@@ -13,6 +15,8 @@
     // see round_quotients: thr = 4e-7 * (max(width, height) + 2); the float just below 1/2 - thr
     const float round_near_half = __uint_as_float(__float_as_uint(0.5f - 4.0e-7f * ((float)max(width, height) + 2.0f)) - 1u);   // (positive: one ulp down)
     uint32_t updated = 0, stores = 0;   // (COUNT: voxels updated, distances stored)
+    // a batch's prior weights; WEIGHTED: behind them, the weights of the voxels' pixels (pw_[kBatchZ + j] goes with plane j)
+    constexpr int kWeightSlots = WEIGHTED ? 2 * kBatchZ : kBatchZ;
 
     for (uint32_t i = blockIdx.x; i < n_active; i += gridDim.x) {
         const unsigned long long dbg_t0 = (!COUNT && counter) ? wall_clock64() : 0ull;   // (diagnostics, TSDF_DEBUG_BRICKS=3: per-brick clocks)
@@ -114,7 +118,7 @@
         // HBM loads, are all in flight together instead of one dependent chain per plane.  The batches are software
         // pipelined: the loads of batch b+1 are issued before batch b is blended and stored, so that there is always a
         // batch of loads in flight (two register sets, used alternately).
-        auto project_and_load = [&](const uint32_t zb, float (&tsdf_)[kBatchZ], float (&pw_)[kBatchZ], float (&pd_)[kBatchZ]) {
+        auto project_and_load = [&](const uint32_t zb, float (&tsdf_)[kBatchZ], float (&pw_)[kWeightSlots], float (&pd_)[kBatchZ]) {
             const size_t idx_b = idx + plane * (size_t)(zb - z0);
             float camz_[kBatchZ], cz_[kBatchZ];
             int px_[kBatchZ], py_[kBatchZ];
@@ -199,14 +203,17 @@
                 // (sdf > 0) ? min(sdf, trunc) : sdf  ==  sdf < trunc ? sdf : trunc   (trunc > 0)
                 tsdf_[j] = update ? (sdf < g.trunc ? sdf : g.trunc) : NAN;
                 pw_[j] = pd_[j] = 0.f;
+                if constexpr (WEIGHTED) pw_[kBatchZ + j] = 0.f;
                 if (update) {
                     const size_t pb = brick_base + plane * (size_t)(zb - z0 + j);
                     pw_[j] = (weight + pb)[lane_off];
                     pd_[j] = (dist + pb)[lane_off];
+                    // the pixel's weight, gathered beside the two loads above (a depth > 0 was read at this pixel: it lies in the image)
+                    if constexpr (WEIGHTED) pw_[kBatchZ + j] = pweight[(uint32_t)py_[j] * width + (uint32_t)px_[j]];
                 }
             }
         };
-        auto blend_and_store = [&](const uint32_t zb, const float (&tsdf_)[kBatchZ], const float (&pw_)[kBatchZ], const float (&pd_)[kBatchZ]) {
+        auto blend_and_store = [&](const uint32_t zb, const float (&tsdf_)[kBatchZ], const float (&pw_)[kWeightSlots], const float (&pd_)[kBatchZ]) {
             // (uniform) a batch with a plane in the z part of the rim zone -- z < 6 or z >= 4 (nbz - 1) - 2 -- takes the flat test on every lane
             const bool z_rim = zb < (uint32_t)(kBrick + kBrickGrow) || zb + (uint32_t)kBatchZ - 1u + (uint32_t)kBrickGrow >= (uint32_t)kBrick * (occ.nbz - 1u);
             const float lo = z_rim ? flat_lo_open : mark_lo, hi = z_rim ? occ.flat_hi : mark_hi;
@@ -233,8 +240,10 @@
                             if (COUNT) updated++;
                         }
                     } else {
-                    const float new_weight = pw_[j] + 1.0f;
-                    const float new_distance = ((pd_[j] * pw_[j]) + (tsdf_[j] * 1.0f)) / new_weight;
+                    float current_weight = 1.0f;   // (the reference's name for it, src/TSDF/TSDFVolume.cu:375)
+                    if constexpr (WEIGHTED) current_weight = pw_[kBatchZ + j];
+                    const float new_weight = pw_[j] + current_weight;
+                    const float new_distance = ((pd_[j] * pw_[j]) + (tsdf_[j] * current_weight)) / new_weight;
                     const size_t pb = brick_base + plane * (size_t)(zb - z0 + j);
                     if constexpr (CAPPED) {
                         // only the stored weight is clamped, never the divisor (include/tsdf_amd.h, "weight cap"); the comparison keeps
@@ -259,7 +268,7 @@
             }
         };
         static_assert(kChunkZ % (2 * kBatchZ) == 0, "the pipeline alternates two register sets");
-        float tsdf_a[kBatchZ], pw_a[kBatchZ], pd_a[kBatchZ], tsdf_b[kBatchZ], pw_b[kBatchZ], pd_b[kBatchZ];
+        float tsdf_a[kBatchZ], pw_a[kWeightSlots], pd_a[kBatchZ], tsdf_b[kBatchZ], pw_b[kWeightSlots], pd_b[kBatchZ];
         project_and_load(z0, tsdf_a, pw_a, pd_a);
 #pragma unroll
         for (uint32_t o = 0; o < (uint32_t)kChunkZ; o += 2 * kBatchZ) {

@@ -149,6 +149,11 @@ struct tsdf_tracker {
     tsdf_aligner *aligner;
     float *align_points[3];     // the filtered frame as camera-frame points at steps 1, 2, 4
     float *align_intensity[3];  // tsdf_tracker_align_field_colour: the rgb frame's intensities at the same steps (made on its first call)
+    // tsdf_tracker_set_weighting: the model (TSDF_WEIGHTS_*) the filtered frame's pixel weights are computed with; weighting_on = 0: plain
+    int weighting_on;
+    uint32_t weighting_flags;
+    float weighting_z_ref;
+    float *pixel_weights;       // width * height, made by the first weighted integrate
 };
 
 using namespace tsdf;
@@ -666,7 +671,7 @@ int tsdf_tracker_destroy(tsdf_tracker *t) {
         if (t->integrated[b]) (void)hipEventDestroy(t->integrated[b]);
     }
     if (t->ready) (void)hipEventDestroy(t->ready);
-    device_free_all(t->model, t->ring);
+    device_free_all(t->model, t->ring, t->pixel_weights);
     delete[] t->ring_cam;
     if (t->aligner) tsdf_aligner_destroy(t->aligner);
     device_free_all(t->align_points[0], t->align_points[1], t->align_points[2]);
@@ -849,7 +854,14 @@ static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera
     int rc = tracker_join(t);
     if (rc != TSDF_OK) return rc;
     const int b = t->cur;
-    if (rgb)
+    if (t->weighting_on) {
+        // the model's weights of the filtered frame, then the weighted integrate, both on the step's stream
+        if (!t->pixel_weights) TSDF_HIP(hipMalloc((void **)&t->pixel_weights, (size_t)t->width * t->height * sizeof(float)), "tracker: pixel weights");
+        rc = tsdf_depth_weights_device(t->width, t->height, t->filtered[b], camera->kinv, t->weighting_flags, t->weighting_z_ref, t->pixel_weights, t->main);
+        if (rc == TSDF_OK)
+            rc = tsdf_integrate_weighted_device(t->volume, t->filtered[b], t->pixel_weights, rgb, t->width, t->height, camera->pose, camera->inv_pose,
+                                                camera->k, camera->kinv);
+    } else if (rgb)
         rc = integrate_with_colour(t->volume, t->filtered[b], rgb, t->width, t->height, camera->inv_pose, camera->k, camera->kinv, t->tile_max[b]);
     else
         rc = tsdf_integrate_device_tiles(t->volume, t->filtered[b], t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
@@ -879,6 +891,7 @@ static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera
 int tsdf_tracker_set_window(tsdf_tracker *t, uint32_t n) {
     TSDF_REQUIRE(t, "tsdf_tracker_set_window: null tracker");
     TSDF_REQUIRE(!t->have_frame, "tsdf_tracker_set_window: a frame has been filtered and not yet integrated (call it between frames)");
+    TSDF_REQUIRE(n == 0 || !t->weighting_on, "tsdf_tracker_set_window: weighting is on (tsdf_tracker_set_weighting), and there is no weighted removal");
     TSDF_REQUIRE(n == 0 || t->volume->weight_cap == 0, "tsdf_tracker_set_window: the volume has a weight cap (a window takes frames back out: tsdf_deintegrate)");
     TSDF_HIP(hipStreamSynchronize(t->main), "tsdf_tracker_set_window");   // (a removal may still read the old ring)
     if (t->ring) (void)hipFree(t->ring);
@@ -899,6 +912,31 @@ int tsdf_tracker_set_window(tsdf_tracker *t, uint32_t n) {
     t->ring = ring;
     t->ring_cam = cams;
     t->window = n;
+    return TSDF_OK;
+}
+
+int tsdf_tracker_set_weighting(tsdf_tracker *t, uint32_t flags, float z_ref) {
+    TSDF_REQUIRE(t, "tsdf_tracker_set_weighting: null tracker");
+    if (flags == 0) {   // off: the plain integrate from the next frame on
+        t->weighting_on = 0;
+        t->weighting_flags = 0;
+        t->weighting_z_ref = 0.0f;
+        return TSDF_OK;
+    }
+    TSDF_REQUIRE(t->window == 0, "tsdf_tracker_set_weighting: the tracker keeps a window (tsdf_tracker_set_window), and there is no weighted removal");
+    TSDF_REQUIRE((flags & ~(uint32_t)(TSDF_WEIGHTS_INVERSE_SQUARE | TSDF_WEIGHTS_COSINE)) == 0, "tsdf_tracker_set_weighting: unknown flag bits %#x", flags);
+    TSDF_REQUIRE(!(flags & TSDF_WEIGHTS_INVERSE_SQUARE) || (z_ref > 0.0f && z_ref < INFINITY),
+                 "tsdf_tracker_set_weighting: z_ref must be finite and > 0 (depth units) for TSDF_WEIGHTS_INVERSE_SQUARE");
+    t->weighting_on = 1;
+    t->weighting_flags = flags;
+    t->weighting_z_ref = z_ref;
+    return TSDF_OK;
+}
+
+int tsdf_tracker_weighting(const tsdf_tracker *t, uint32_t *flags, float *z_ref) {
+    TSDF_REQUIRE(t && flags, "tsdf_tracker_weighting: null argument");
+    *flags = t->weighting_flags;
+    if (z_ref) *z_ref = t->weighting_z_ref;
     return TSDF_OK;
 }
 

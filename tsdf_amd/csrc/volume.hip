@@ -932,6 +932,7 @@ int tsdf_volume_destroy(tsdf_volume *v) {
             delete v->tev[w];
         }
     device_free_all(v->brick_list, v->brick_boxes, v->tile_max, v->colour, v->rgb_buf, v->fuse_scratch, v->rays_scratch, v->rays_colour_scratch);
+    device_free_all(v->wdepth_buf, v->pweight_buf);
     delete v;
     return TSDF_OK;
 }

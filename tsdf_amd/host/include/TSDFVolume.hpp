@@ -110,6 +110,17 @@ public:
     // the same depth map at the same camera -- back out.  Throws std::invalid_argument on a volume with a weight cap.
     void deintegrate(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera);
 
+    // Weighted integration (include/tsdf_amd.h, "weighted integration"; what the reference's current_weight was for): integrate() with
+    // one fp32 weight per pixel (width * height); a pixel whose weight is not finite and > 0 counts as a pixel without depth.  `rgb` (or
+    // nullptr) as in the coloured integrate().  The volume goes to fp32 weights.  Throws std::invalid_argument on null weights.
+    void integrate_weighted(const uint16_t *depth_map, const float *weights, uint32_t width, uint32_t height, const Camera &camera,
+                            const uint8_t *rgb = nullptr);
+    // The standard weight models of a depth frame (tsdf_depth_weights): `flags` a combination of TSDF_WEIGHTS_INVERSE_SQUARE and
+    // TSDF_WEIGHTS_COSINE, z_ref in depth units; the result has width * height entries, 0 where the depth is 0.  Throws
+    // std::invalid_argument on unknown flags and on a z_ref that is not finite and > 0 with the inverse-square flag.
+    static std::vector<float> depth_weights(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera, uint32_t flags,
+                                            float z_ref = 0.0f);
+
     // Weight cap (include/tsdf_amd.h, "weight cap"; what the reference's m_max_weight was for): integrate stores min(weight + 1, cap),
     // the blend's divisor stays weight + 1.  0 = off (the default), 1 .. 65535; throws std::invalid_argument above that.
     void weight_cap(uint32_t cap);

@@ -382,6 +382,23 @@ void TSDFVolume::integrate(const uint16_t *depth_map, const uint8_t *rgb, uint32
           "Integrate kernel failed");
 }
 
+void TSDFVolume::integrate_weighted(const uint16_t *depth_map, const float *weights, uint32_t width, uint32_t height, const Camera &camera,
+                                    const uint8_t *rgb) {
+    assert(depth_map);
+    const Eigen::Matrix3f k = camera.k(), kinv = camera.kinv();
+    check(tsdf_integrate_weighted(m_handle, depth_map, weights, rgb, width, height, camera.pose().data(), camera.inverse_pose().data(), k.data(),
+                                  kinv.data()),
+          "Weighted integrate failed");
+}
+
+std::vector<float> TSDFVolume::depth_weights(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera, uint32_t flags,
+                                             float z_ref) {
+    std::vector<float> weights((size_t)width * height);
+    const Eigen::Matrix3f kinv = camera.kinv();
+    check(tsdf_depth_weights(width, height, depth_map, kinv.data(), flags, z_ref, weights.data()), "Depth weights failed");
+    return weights;
+}
+
 // reference: src/TSDF/TSDFVolume.cu:1054-1058
 void TSDFVolume::raycast(uint16_t width, uint16_t height, const Camera &camera,
                          Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,

@@ -27,7 +27,7 @@ from .pipeline import OVERLAP, _matrices
 
 class FrameToModelTracker:
     def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True, window=0,
-                 method="icp", colour_weight=0.0, colour_gate=None):
+                 method="icp", colour_weight=0.0, colour_gate=None, weighting=None):
         import torch
         if method not in ("icp", "field"):
             raise ValueError("method is 'icp' or 'field', got %r" % (method,))
@@ -61,6 +61,8 @@ class FrameToModelTracker:
         self.stream = torch.cuda.ExternalStream(m.value, device=torch.device("cuda", torch.cuda.current_device()))
         if window:
             self.set_window(window)
+        if weighting is not None:
+            self.set_weighting(*weighting)
         self.frames = 0
         self.last_error, self.last_inliers = 0.0, 0.0
         self.last_T = None          # the last incremental transformation (4x4, metres) as ICPOdometry returned it
@@ -84,6 +86,17 @@ class FrameToModelTracker:
         n = C.c_uint32()
         check(lib.tsdf_tracker_window(self._h, C.byref(n)))
         return int(n.value)
+
+    def set_weighting(self, flags, z_ref=0.0):
+        """Integrate every frame with the weights of a standard model (include/tsdf_amd.h, "weighted integration"): `flags` a combination
+        of api.WEIGHTS_INVERSE_SQUARE / api.WEIGHTS_COSINE (0: off, the default), `z_ref` in depth units.  Refused together with a window."""
+        check(lib.tsdf_tracker_set_weighting(self._h, int(flags), float(z_ref)))
+
+    def weighting(self):
+        """(flags, z_ref) of set_weighting; (0, 0.0) when off."""
+        f, z = C.c_uint32(), C.c_float()
+        check(lib.tsdf_tracker_weighting(self._h, C.byref(f), C.byref(z)))
+        return int(f.value), float(z.value)
 
     def pose(self):
         """Current camera pose, 4x4 float64 (camera -> world, millimetres)."""
