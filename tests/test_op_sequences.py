@@ -35,7 +35,8 @@ pytestmark = pytest.mark.gpu
 F32, U32 = np.float32, np.uint32
 DEPTH_TILE = 16          # TSDF_DEPTH_TILE (include/tsdf_amd.h)
 REFUSALS = {"remove": "tsdf_deintegrate: the volume has a weight cap", "rays_colour": "tsdf_integrate_rays_colour: colour is not enabled",
-            "restore_other": "tsdf_volume_restore: the snapshot is of a 8 x 8 x 8 grid"}
+            "restore_other": "tsdf_volume_restore: the snapshot is of a 8 x 8 x 8 grid",
+            "depth_weighted_colour": "tsdf_integrate_weighted: colour is not enabled"}
 _SEEN = {"seeds": set(), "modes": {}, "casts": {True: 0, False: 0}}
 
 
@@ -105,6 +106,10 @@ class Sequenced:
             gv.integrate(op[1], w, h, Cam(*op[2]))
         elif kind == "depth_colour":
             gv.integrate_colour(op[1], op[2], w, h, Cam(*op[3]))
+        elif kind == "depth_weighted":
+            gv.integrate_weighted(op[1], op[2], w, h, Cam(*op[3]))
+        elif kind == "depth_weighted_colour":
+            gv.integrate_weighted(op[1], op[2], w, h, Cam(*op[4]), rgb=op[3])
         elif kind == "remove":
             gv.deintegrate(op[1], w, h, Cam(*op[2]))
         elif kind == "rays":
@@ -199,6 +204,8 @@ class Sequenced:
                 gv.deintegrate(op[1], self.width, self.height, Cam(*op[2]))
             elif op[0] == "rays_colour":
                 gv.integrate_rays(op[1], op[2], band_only=op[4], min_range=op[5], max_range=op[6], rgb=op[3])
+            elif op[0] == "depth_weighted_colour":
+                gv.integrate_weighted(op[1], op[2], self.width, self.height, Cam(*op[4]), rgb=op[3])
             else:
                 other = tsdf_amd.TSDFVolume(op[1], (200.0, 200.0, 200.0))
                 other.set_weight_data(np.ones(other.resident_voxels(), F32))

@@ -1,18 +1,22 @@
 """One CPU model of a whole volume: every writer, switch and observer of tsdf_amd.TSDFVolume on plain (dist, weight, colour) arrays, each
 delegated to the reference that already pins that operation on its own -- oracle/ for integrate, ray cast and marching cubes,
-weight_cap_ref, colour_ref, deintegrate_ref, rays_integrate_ref, rays_colour_ref, fuse_ref, snapshot_ref, and the flag definition of
-tests/test_occupancy.py.  No arithmetic of its own: what is new is only that the references act on ONE state, in any order
-(tests/op_sequences.py, tests/test_op_sequences.py).  How the weights are stored must not show in a single bit, so the model has no
-storage.  `mutant=` switches in one plausible defect at a time (tests/test_op_sequences_host.py shows that the sequences see each).
+weight_cap_ref, colour_ref, deintegrate_ref, weighted_ref, rays_integrate_ref, rays_colour_ref, fuse_ref, snapshot_ref, and the flag
+definition of tests/test_occupancy.py.  No arithmetic of its own: what is new is only that the references act on ONE state, in any
+order (tests/op_sequences.py, tests/test_op_sequences.py; tests/weighted_sequences.py, tests/test_weighted_fuzz.py).  How the weights
+are stored must not show in a single bit, so the model has no storage.  `mutant=` switches in one plausible defect at a time
+(tests/test_op_sequences_host.py and tests/test_weighted_fuzz_host.py show that the sequences see each).
 Test infrastructure only."""
 import numpy as np
 
-from tests import colour_ref, deintegrate_ref, fuse_ref, rays_colour_ref, rays_integrate_ref, snapshot_ref
+from tests import colour_ref, deintegrate_ref, fuse_ref, rays_colour_ref, rays_integrate_ref, snapshot_ref, weighted_ref
 from tests.field_ref import geometry as field_geometry
 from tests.weight_cap_ref import oracle_step
 
 F32, U32 = np.float32, np.uint32
-MUTANTS = ("counts_wrap_at_256", "restore_keeps_colour", "rays_ignore_cap", "remove_keeps_distance")
+MUTANTS = ("counts_wrap_at_256", "restore_keeps_colour", "rays_ignore_cap", "remove_keeps_distance",
+           # switched in only inside integrate_weighted (tests/test_weighted_fuzz_host.py shows that its sequences and cases see each)
+           "weighted_cap_clamps_divisor", "weighted_invalid_pixel_colours", "weighted_next_pixel")
+WEIGHTED_MUTANTS = MUTANTS[4:]
 
 
 class Refused(Exception):
@@ -28,6 +32,7 @@ class VolumeModel:
             self.ov.offset(*offset)          # (set without a clear, as the ray and fuse tests do: offset_at_clear stays zero)
         self.colour = None                   # uint32 words, or None while colour is not enabled
         self.cap = 0
+        self.last_stores = None              # distance stores of the last integrate_weighted
 
     # ---- the state
     @property
@@ -63,6 +68,28 @@ class VolumeModel:
             raise Refused("colour integrate on a volume without colour enabled")
         self.colour = colour_ref.integrate_colour(self.O, self.colour, self._colour_geometry(), depth, rgb, width, height, cam)[0]
         return self.integrate(depth, width, height, cam)
+
+    def integrate_weighted(self, depth, weights, width, height, cam, rgb=None):
+        """tsdf_integrate_weighted: tests/weighted_ref.py's frame and blend, tests/colour_ref.py on the masked image."""
+        if rgb is not None and self.colour is None:
+            raise Refused("tsdf_integrate_weighted: colour is not enabled on this volume")
+        p_image = np.asarray(weights, F32).reshape(-1)
+        in_set, tsdf, pidx = weighted_ref.frame(self.O, self.ov, depth, p_image, cam, width, height)
+        if self.mutant == "weighted_next_pixel":             # the weight of pixel (px + 1, py), clamped to the row
+            pidx = (pidx // width) * width + np.minimum(pidx % width + 1, width - 1)
+        keep_d, keep_w = self.dist.copy(), self.weight.copy()
+        p = p_image[pidx]
+        updated, self.last_stores = weighted_ref.blend(self.ov, in_set, tsdf, p, self.cap)
+        if self.mutant == "weighted_cap_clamps_divisor" and self.cap:
+            with np.errstate(all="ignore"):
+                nw = (keep_w + p).astype(F32)
+                clamped = in_set & (nw > F32(self.cap))
+                d = (((keep_d * keep_w).astype(F32) + (tsdf * p).astype(F32)).astype(F32) / F32(self.cap)).astype(F32)
+            self.dist[clamped] = d[clamped]
+        if rgb is not None:
+            image = np.asarray(depth, np.uint16).reshape(-1) if self.mutant == "weighted_invalid_pixel_colours" else weighted_ref.masked_depth(depth, p_image)
+            self.colour = colour_ref.integrate_colour(self.O, self.colour, self._colour_geometry(), image, rgb, width, height, cam)[0]
+        return updated
 
     def deintegrate(self, depth, width, height, cam):
         if self.cap:
@@ -193,6 +220,10 @@ class ModelRun:
             return m.integrate(op[1], w, h, self.Cam(*op[2]))
         if kind == "depth_colour":
             return m.integrate_colour(op[1], op[2], w, h, self.Cam(*op[3]))
+        if kind == "depth_weighted":
+            return m.integrate_weighted(op[1], op[2], w, h, self.Cam(*op[3]))
+        if kind == "depth_weighted_colour":
+            return m.integrate_weighted(op[1], op[2], w, h, self.Cam(*op[4]), op[3])
         if kind == "remove":
             return m.deintegrate(op[1], w, h, self.Cam(*op[2]))
         if kind == "rays":
