@@ -426,6 +426,75 @@ int tsdf_raycast_colour(const tsdf_volume *volume, uint32_t width, uint32_t heig
 int tsdf_raycast_colour_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
                                const float kinv[9], float *device_vertices, float *device_normals, uint8_t *device_rgb);
 
+/* ---- class fusion (no reference counterpart; what Voxblox++, Kimera and SemanticFusion keep beside their distances) ------------------ */
+/* Fuses the per-pixel class ids of a segmentation network and reads the fused class back where colour is read.  Opt-in per volume: a
+ * volume that never enables classes behaves exactly as without this group: no allocation, no launch.
+ *   Storage: one dword per voxel {class, votes} -- class in bits 0-15, votes in bits 16-31 -- x fastest like the distances; allocated
+ *     and zeroed by tsdf_volume_enable_classes(v, 1) (kept if already enabled; 4 bytes a voxel: 512 MiB at 512^3), freed by (v, 0) and
+ *     by destroy, zeroed by tsdf_volume_clear.  A word with votes == 0 is always 0x00000000: there is one "unclassified" word.  Valid
+ *     class ids are 0..65534; TSDF_CLASS_VOID marks a pixel without a class, and a sample without one.
+ *   Integrate: tsdf_integrate_classes* takes the arguments of tsdf_integrate_colour* plus classes (uint16, width * height, row-major,
+ *     registered to the depth image) and confidence (uint8, width * height, or NULL: every pixel has strength 1).  rgb may be NULL.
+ *     Distances, weights, weight storage, weight cap, occupancy and counters end up with exactly the bits tsdf_integrate leaves.  With
+ *     rgb != NULL on a colour volume the colour words are exactly those of tsdf_integrate_colour.  The class update visits exactly the
+ *     voxels the colour update visits -- in the frustum, depth > 0, -trunc <= sdf <= +trunc, sdf and pixel being the bits integrate
+ *     computed -- free space keeps its word.  For such a voxel with pixel p, k = classes[p] and s = confidence ? confidence[p] : 1:
+ *     if k == TSDF_CLASS_VOID or s == 0 the word is untouched; otherwise, with the old word (c, n), in uint32:
+ *         n == 0          -> (k, s)
+ *         c == k          -> (k, min(n + s, 65535))
+ *         c != k, n >  s  -> (c, n - s)
+ *         c != k, n == s  -> 0x00000000
+ *         c != k, n <  s  -> (k, s - n)
+ *     the weighted Boyer-Moore majority vote.  One writer per word and no atomics: a call's result is a unique set of bits.  The
+ *     update is a pass of its own (class_integrate_kernel) behind the integrate kernel -- and behind the colour update, when rgb is
+ *     given -- on the volume's stream over the frame's brick list, for standard and general cameras and all three weight storages.
+ *   Sampling: tsdf_volume_sample_classes_device reads the voxel tsdf_volume_sample_colours_device reads -- the same frame
+ *     (offset_at_clear subtracted), the same index expression -- and gives (TSDF_CLASS_VOID, 0) for a NaN coordinate, an off-grid
+ *     index or a word with votes == 0.  device_votes may be NULL.  n == 0 is TSDF_OK and launches nothing.
+ *   Ray cast: tsdf_raycast_classes* is tsdf_raycast*, then the sampling of every vertex; misses give VOID.  The cast's kernel choice
+ *     and state are those of tsdf_raycast*.
+ *   Counts: counts[k], k < n_classes, = the resident voxels whose word has class == k and votes >= max(min_votes, 1): the volume a
+ *     class occupies in the band, in voxels.  counts is overwritten, not accumulated; n_classes in 1..65535, classes >= n_classes are
+ *     not counted.  Integer atomics only, so the counts are unique (class_counts_kernel: a histogram per workgroup in LDS up to 4096
+ *     classes, global atomics beyond).
+ *   Refused (TSDF_ERR_INVALID, with a message naming the function, nothing written): enabling classes on a Z-slab volume
+ *     (tsdf_volume_create_slab); class integrate on a volume whose deformation nodes are explicit; any call of this group, enabling
+ *     aside, on a volume without classes enabled; NULL depth or classes; an empty image; rgb != NULL on a volume without colour;
+ *     n_classes out of range; NULL outputs.
+ *   Left alone: tsdf_integrate*, tsdf_integrate_colour*, tsdf_integrate_weighted*, tsdf_deintegrate* (a vote is not invertible),
+ *     tsdf_integrate_rays*, tsdf_volume_fuse, snapshots and restore, the .tsdf and .tsdfs files, tsdf_pipeline_step* and
+ *     tsdf_tracker_* neither read nor write class words.
+ *   Out of scope: classes in the pipeline step, the tracker and kinfu_stream; classes from ray sets; classes through fuse, snapshots
+ *     and files; a per-vertex class array inside the mesh handle and a filter by class; the class at tsdf_volume_cast_rays* hits. */
+#define TSDF_CLASS_VOID 0xFFFFu
+int tsdf_volume_enable_classes(tsdf_volume *volume, int enabled);   /* 1: allocate zeroed (kept if already enabled), 0: free */
+int tsdf_volume_classes_enabled(const tsdf_volume *volume, int *enabled);
+int tsdf_volume_classes(const tsdf_volume *volume, uint32_t **device_ptr);   /* the device array, one dword per resident voxel */
+/* Blocking copies of the whole array (resident voxels x 4 bytes). */
+int tsdf_volume_get_class_data(const tsdf_volume *volume, uint32_t *host);
+int tsdf_volume_set_class_data(tsdf_volume *volume, const uint32_t *host);
+/* tsdf_integrate / tsdf_integrate_device (tsdf_integrate_colour* with rgb) with the class vote of the same frame. */
+int tsdf_integrate_classes(tsdf_volume *volume, const uint16_t *host_depth, const uint8_t *host_rgb /* or NULL */,
+                           const uint16_t *host_classes, const uint8_t *host_confidence /* or NULL */, uint32_t width, uint32_t height,
+                           const float pose[16], const float inv_pose[16], const float k[9], const float kinv[9]);
+int tsdf_integrate_classes_device(tsdf_volume *volume, const uint16_t *device_depth, const uint8_t *device_rgb /* or NULL */,
+                                  const uint16_t *device_classes, const uint8_t *device_confidence /* or NULL */, uint32_t width,
+                                  uint32_t height, const float pose[16], const float inv_pose[16], const float k[9],
+                                  const float kinv[9]);
+/* n points (3 floats each, device) -> a class and a vote count each (device), one thread per point, on hip_stream. */
+int tsdf_volume_sample_classes_device(const tsdf_volume *volume, uint64_t n, const float *device_points, uint16_t *device_classes,
+                                      uint16_t *device_votes /* or NULL */, void *hip_stream);
+/* tsdf_raycast / tsdf_raycast_device, then the sampling of every vertex; width * height classes and (or NULL) votes. */
+int tsdf_raycast_classes(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16], const float kinv[9],
+                         float *host_vertices, float *host_normals, uint16_t *host_classes, uint16_t *host_votes /* or NULL */);
+int tsdf_raycast_classes_device(const tsdf_volume *volume, uint32_t width, uint32_t height, const float pose[16],
+                                const float kinv[9], float *device_vertices, float *device_normals, uint16_t *device_classes,
+                                uint16_t *device_votes /* or NULL */);
+/* Voxels per class: n_classes 64-bit counts (host: blocking, on the volume's stream; device: on hip_stream). */
+int tsdf_volume_class_counts(const tsdf_volume *volume, uint32_t n_classes, uint32_t min_votes, uint64_t *host_counts);
+int tsdf_volume_class_counts_device(const tsdf_volume *volume, uint32_t n_classes, uint32_t min_votes, uint64_t *device_counts,
+                                    void *hip_stream);
+
 /* ---- field queries (no reference counterpart: the reference's volume can be fused into, rendered and meshed, not asked) ---------- */
 /* The trilinear distance, its gradient and the weight of the fused field at world points.  Opt-in by being called: a volume on which
  * these are never called does exactly what it did.

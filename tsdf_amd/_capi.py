@@ -15,6 +15,7 @@ TSDF_FIELD_UNIT_GRADIENT = 1
 TSDF_RAYS_BAND_ONLY = 1
 TSDF_MESH_NORMALS, TSDF_MESH_COLOURS = 1, 2
 TSDF_MESH_KEEP_LARGEST = 1
+TSDF_CLASS_VOID = 0xFFFF
 TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
 TSDF_SCENE_FLOW_DEFORMED = 1
@@ -179,6 +180,18 @@ _SIGS = {
     "tsdf_volume_sample_colours_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp]),
     "tsdf_raycast_colour": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_raycast_colour_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
+    "tsdf_volume_enable_classes": (_i, [_vp, _i]),
+    "tsdf_volume_classes_enabled": (_i, [_vp, C.POINTER(_i)]),
+    "tsdf_volume_classes": (_i, [_vp, C.POINTER(_vp)]),
+    "tsdf_volume_get_class_data": (_i, [_vp, _vp]),
+    "tsdf_volume_set_class_data": (_i, [_vp, _vp]),
+    "tsdf_integrate_classes": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_integrate_classes_device": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp]),
+    "tsdf_volume_sample_classes_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "tsdf_raycast_classes": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp, _vp]),
+    "tsdf_raycast_classes_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp, _vp, _vp]),
+    "tsdf_volume_class_counts": (_i, [_vp, _u32, _u32, _vp]),
+    "tsdf_volume_class_counts_device": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "tsdf_volume_sample_field_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _i, _vp]),
     "tsdf_volume_sample_field": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _i]),
     "tsdf_raycast_gradient_normals_device": (_i, [_vp, _u32, _u32, _fp, _fp, _vp, _vp]),

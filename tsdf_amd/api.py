@@ -392,6 +392,109 @@ class TSDFVolume:
         V = self.extract_surface()
         return V, self.sample_colours(V)
 
+    # ---- class fusion (include/tsdf_amd.h, "class fusion"; not in the reference's class)
+    def enable_classes(self, enabled=True):
+        """Allocate the {class, votes} dword per voxel, zeroed (False: free it).  Refused on a Z-slab."""
+        check(lib.tsdf_volume_enable_classes(self._h, 1 if enabled else 0))
+        self.synchronize()
+
+    def classes_enabled(self):
+        e = C.c_int()
+        check(lib.tsdf_volume_classes_enabled(self._h, C.byref(e)))
+        return bool(e.value)
+
+    def class_data(self):
+        """Device pointer to the class dwords."""
+        p = C.c_void_p()
+        check(lib.tsdf_volume_classes(self._h, C.byref(p)))
+        return p.value
+
+    def get_class_data(self):
+        """uint32 per resident voxel: class | votes << 16; 0 where nothing was voted."""
+        a = np.empty(self.resident_voxels(), np.uint32)
+        check(lib.tsdf_volume_get_class_data(self._h, a.ctypes.data))
+        return a
+
+    def set_class_data(self, class_data):
+        a = np.ascontiguousarray(class_data, dtype=np.uint32).reshape(-1)
+        if a.size != self.resident_voxels():
+            raise ValueError("expected %d class words, got %d" % (self.resident_voxels(), a.size))
+        check(lib.tsdf_volume_set_class_data(self._h, a.ctypes.data))
+
+    def integrate_classes(self, depth_map, classes, width, height, camera, confidence=None, rgb=None):
+        """integrate() plus the vote of classes (uint16 per pixel, CLASS_VOID = no class, registered to the depth map) with the
+        strength confidence (uint8 per pixel; None: 1 everywhere); rgb (uint8, width*height*3) adds integrate_colour()'s colour
+        update on a colour volume.  Blocking."""
+        d = np.ascontiguousarray(depth_map, dtype=np.uint16).reshape(-1)
+        c = np.ascontiguousarray(classes, dtype=np.uint16).reshape(-1)
+        if d.size != width * height or c.size != width * height:
+            raise ValueError("expected %d depth pixels and %d classes, got %d and %d" % (width * height, width * height, d.size, c.size))
+        s = r = None
+        if confidence is not None:
+            s = np.ascontiguousarray(confidence, dtype=np.uint8).reshape(-1)
+            if s.size != width * height:
+                raise ValueError("expected %d confidences, got %d" % (width * height, s.size))
+        if rgb is not None:
+            r = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1)
+            if r.size != 3 * width * height:
+                raise ValueError("expected %d colour bytes, got %d" % (3 * width * height, r.size))
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_integrate_classes(self._h, d.ctypes.data, r.ctypes.data if r is not None else None, c.ctypes.data,
+                                         s.ctypes.data if s is not None else None, width, height, _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
+    def integrate_classes_device(self, depth_ptr, classes_ptr, width, height, camera, confidence_ptr=None, rgb_ptr=None):
+        """Asynchronous on the volume's stream; device pointers to width*height uint16 depths and classes, optionally width*height
+        uint8 confidences and width*height*3 uint8 colours."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        pose, ipose, k, kinv = _camera_matrices(camera)
+        check(lib.tsdf_integrate_classes_device(self._h, ptr(depth_ptr), ptr(rgb_ptr), ptr(classes_ptr), ptr(confidence_ptr), width, height,
+                                                _fp(pose), _fp(ipose), _fp(k), _fp(kinv)))
+
+    def sample_classes_device(self, n, points_ptr, classes_ptr, votes_ptr=None, stream=None):
+        """n points (3 float32 each) -> a uint16 class and (optionally) a uint16 vote count each, device pointers; on `stream`
+        (default: the volume's)."""
+        s = self.stream_ptr() if stream is None else stream
+        check(lib.tsdf_volume_sample_classes_device(self._h, int(n), C.c_void_p(int(points_ptr)) if points_ptr else None,
+                                                    C.c_void_p(int(classes_ptr)) if classes_ptr else None,
+                                                    C.c_void_p(int(votes_ptr)) if votes_ptr else None, C.c_void_p(int(s) if s else 0)))
+
+    def sample_classes(self, points):
+        """(n, 3) float32 world points (mm) -> (classes (n,) uint16, votes (n,) uint16): the class of the voxel each lies in and its
+        votes, (CLASS_VOID, 0) for NaN, off-grid and unclassified voxels."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.empty((2, len(p)), np.uint16)
+        if not len(p):
+            if not self.classes_enabled():
+                raise ValueError("sample_classes: classes are not enabled on this volume")
+            return out[0], out[1]
+        dp, dc = C.c_void_p(), C.c_void_p()
+        check(lib.tsdf_device_alloc(p.nbytes, C.byref(dp)))
+        try:
+            check(lib.tsdf_device_alloc(out.nbytes, C.byref(dc)))
+            check(lib.tsdf_device_upload(dp, p.ctypes.data, p.nbytes))
+            self.sample_classes_device(len(p), dp.value, dc.value, dc.value + out[0].nbytes)
+            self.synchronize()
+            check(lib.tsdf_device_download(out.ctypes.data, dc, out.nbytes))
+        finally:
+            lib.tsdf_device_free(dp)
+            if dc.value:
+                lib.tsdf_device_free(dc)
+        return out[0], out[1]
+
+    def class_counts(self, n_classes, min_votes=1):
+        """(n_classes,) uint64: the resident voxels whose class is k and whose votes are at least max(min_votes, 1)."""
+        n = int(n_classes)
+        if not 1 <= n <= 65535:
+            raise ValueError("class_counts: n_classes %d is not in 1..65535" % n)
+        out = np.empty(n, np.uint64)
+        check(lib.tsdf_volume_class_counts(self._h, n, int(min_votes), out.ctypes.data))
+        return out
+
+    def extract_classed_surface(self):
+        """extract_surface() and the class of every vertex (sample_classes): (vertices (3T, 3) float32, classes (3T,) uint16)."""
+        V = self.extract_surface()
+        return V, self.sample_classes(V)[0]
+
     # ---- field queries (include/tsdf_amd.h, "field queries"; not in the reference's class)
     def sample_field_device(self, n, points_ptr, distance_ptr=None, gradient_ptr=None, weight_ptr=None, unit_gradient=False,
                             stream=None):
@@ -779,6 +882,25 @@ class GPURaycaster:
         check(lib.tsdf_raycast_colour_device(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), C.c_void_p(int(vertices_ptr)),
                                              C.c_void_p(int(normals_ptr)) if normals_ptr else None, C.c_void_p(int(rgb_ptr))))
 
+    def raycast_classes(self, volume, camera):
+        """raycast() plus the class of the voxel every vertex lies in: (vertices, normals, classes (width*height,) uint16, votes
+        (width*height,) uint16); misses and unclassified voxels are (CLASS_VOID, 0).  The volume must have classes enabled."""
+        pose, _, _, kinv = _camera_matrices(camera)
+        n = self.m_width * self.m_height
+        V = np.empty((n, 3), np.float32)
+        N = np.empty((n, 3), np.float32)
+        classes = np.empty(n, np.uint16)
+        votes = np.empty(n, np.uint16)
+        check(lib.tsdf_raycast_classes(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), V.ctypes.data, N.ctypes.data,
+                                       classes.ctypes.data, votes.ctypes.data))
+        return V, N, classes, votes
+
+    def raycast_classes_device(self, volume, camera, vertices_ptr, normals_ptr, classes_ptr, votes_ptr=None):
+        pose, _, _, kinv = _camera_matrices(camera)
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_raycast_classes_device(volume._h, self.m_width, self.m_height, _fp(pose), _fp(kinv), ptr(vertices_ptr),
+                                              ptr(normals_ptr), ptr(classes_ptr), ptr(votes_ptr)))
+
     def raycast_gradient_normals(self, volume, camera):
         """raycast() with the unit gradient of the fused field at every vertex in place of the cross-product normals (NaN along
         every silhouette and beside every miss): -> (vertices, normals); the vertices are raycast()'s, a miss is a NaN row in both."""
@@ -1009,6 +1131,26 @@ class Mesh:
     def colours(self):
         """(n_vertices, 3) uint8; ValueError unless the mesh was extracted with colours."""
         return self._download(3, (self.n_vertices, 3), np.uint8)
+
+    def sample_classes(self, volume):
+        """(n_vertices,) uint16: the class volume.sample_classes gives at every vertex, sampled device to device on the mesh's vertex
+        buffer (CLASS_VOID where the voxel is unclassified).  The volume must have classes enabled."""
+        n = self.n_vertices
+        out = np.empty(n, np.uint16)
+        if not n:
+            if not volume.classes_enabled():
+                raise ValueError("sample_classes: classes are not enabled on this volume")
+            return out
+        vertices = self.device_buffers()[0]
+        dc = C.c_void_p()
+        check(lib.tsdf_device_alloc(out.nbytes, C.byref(dc)))
+        try:
+            volume.sample_classes_device(n, vertices, dc.value)
+            volume.synchronize()
+            check(lib.tsdf_device_download(out.ctypes.data, dc, out.nbytes))
+        finally:
+            lib.tsdf_device_free(dc)
+        return out
 
     def triangles(self):
         """(n_indices / 3, 3) uint32, wired as extract_surface wires its soup: triangle t = (I[3t], I[3t+2], I[3t+1])."""
@@ -1652,6 +1794,7 @@ def depth_to_points(depth, width, height, kinv, step=1, depth_cutoff=float("inf"
 
 #: tsdf_depth_weights flags (include/tsdf_amd.h, "weighted integration")
 WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE = _capi.TSDF_WEIGHTS_INVERSE_SQUARE, _capi.TSDF_WEIGHTS_COSINE
+CLASS_VOID = _capi.TSDF_CLASS_VOID   # a pixel, or a sample, without a class
 
 
 def depth_weights_device(width, height, depth_ptr, kinv, flags, z_ref, weights_ptr, stream=0):

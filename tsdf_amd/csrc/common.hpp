@@ -368,7 +368,14 @@ struct tsdf_volume {
     uint32_t *colour;
     uint8_t *rgb_buf;
     size_t rgb_cap;
-    int slab;                 // made by tsdf_volume_create_slab (colour is refused there)
+    int slab;                 // made by tsdf_volume_create_slab (colour and classes are refused there)
+    // class fusion (classes.hip): one dword {class, votes} per resident voxel while enabled (tsdf_volume_enable_classes), else null;
+    // class_buf / conf_buf cache the host variants' uploads of the class and confidence frames (class_buf also a cast's class map)
+    uint32_t *classes;
+    uint16_t *class_buf;
+    size_t class_cap;
+    uint8_t *conf_buf;
+    size_t conf_cap;
     // weighted integration (integrate_weighted.hip): the frame's depth with the pixels of invalid weight zeroed, and the host variant's
     // upload of the pixel weights; both empty until the first weighted frame
     uint16_t *wdepth_buf;

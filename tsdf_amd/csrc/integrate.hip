@@ -96,6 +96,10 @@ int launch_integrate_packed_kernel(tsdf_volume *v, dim3 grid, const BrickGrid &b
 // colour.hip
 int launch_colour_integrate(tsdf_volume *v, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, const Mat33 &mkinv, bool std_camera,
                             uint32_t width, uint32_t height, const uint16_t *d_depth, const uint8_t *d_rgb, const uint32_t *count);
+// classes.hip
+int launch_class_integrate(tsdf_volume *v, const BrickGrid &bg, const Mat44 &ip, const Mat33 &mk, const Mat33 &mkinv, bool std_camera,
+                           uint32_t width, uint32_t height, const uint16_t *d_depth, const uint16_t *d_classes, const uint8_t *d_confidence,
+                           const uint32_t *count);
 
 constexpr int kDepthTile = TSDF_DEPTH_TILE;  // pixels per side of a depth tile (16)
 constexpr int kCullTilesLds = 4096;  // tile maxima brick_cull_kernel keeps in LDS (1200 at 640x480)
@@ -345,7 +349,8 @@ enum IntegratePhase { kIntBoth = 0, kIntPrepare = 1 };
 static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t width, uint32_t height,
                             const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *caller_tile_max = nullptr,
                             IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr, const uint8_t *d_rgb = nullptr,
-                            bool remove = false, const float *d_pweight = nullptr) {
+                            bool remove = false, const float *d_pweight = nullptr, const uint16_t *d_classes = nullptr,
+                            const uint8_t *d_confidence = nullptr) {
     // d_pweight: tsdf_integrate_weighted* -- d_depth is then the masked image and the weights are fp32 already (integrate_weighted below)
     Mat44 ip;
     Mat33 mk, mkinv;
@@ -533,6 +538,10 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
         const int rcc = launch_colour_integrate(v, bg, ip, mk, mkinv, std_camera, width, height, d_depth, d_rgb, count);
         if (rcc != TSDF_OK) return rcc;
     }
+    if (d_classes) {   // tsdf_integrate_classes: the class vote over the same brick list, behind the integrate kernel and the colour update
+        const int rcl = launch_class_integrate(v, bg, ip, mk, mkinv, std_camera, width, height, d_depth, d_classes, d_confidence, count);
+        if (rcl != TSDF_OK) return rcl;
+    }
 #ifdef TSDF_DIAGNOSTICS
     diag_brick_report(v, bg, n_bricks, count, boxes, brick_log);   // TSDF_DEBUG_BRICKS: survivors, list order, per-brick clocks
 #endif
@@ -557,6 +566,15 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
 int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
                           const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max) {
     return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, tile_max, kIntBoth, nullptr, d_rgb);
+}
+
+// tsdf_integrate_classes_device (classes.hip): integrate, the colour update of tsdf_integrate_colour when d_rgb is given, then the class
+// pass behind them over the frame's brick list
+int integrate_with_classes(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, const uint16_t *d_classes,
+                           const uint8_t *d_confidence, uint32_t width, uint32_t height, const float inv_pose[16], const float k[9],
+                           const float kinv[9]) {
+    return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, d_rgb, false, nullptr, d_classes,
+                            d_confidence);
 }
 
 // tsdf_integrate_weighted_device (integrate_weighted.hip): d_masked is the depth image with the pixels of invalid weight zeroed; the

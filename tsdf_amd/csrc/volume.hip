@@ -933,6 +933,7 @@ int tsdf_volume_destroy(tsdf_volume *v) {
         }
     device_free_all(v->brick_list, v->brick_boxes, v->tile_max, v->colour, v->rgb_buf, v->fuse_scratch, v->rays_scratch, v->rays_colour_scratch);
     device_free_all(v->wdepth_buf, v->pweight_buf);
+    device_free_all(v->classes, v->class_buf, v->conf_buf);
     delete v;
     return TSDF_OK;
 }
@@ -969,6 +970,7 @@ int tsdf_volume_clear(tsdf_volume *v) {
     hipLaunchKernelGGL(fill_kernel, dim3(2048), dim3(256), 0, v->stream, v->dist, n, v->g.trunc);
     TSDF_HIP(hipGetLastError(), "Couldn't clear TSDF data");
     if (v->colour) TSDF_HIP(hipMemsetAsync(v->colour, 0, n * sizeof(uint32_t), v->stream), "Couldn't clear colour data");
+    if (v->classes) TSDF_HIP(hipMemsetAsync(v->classes, 0, n * sizeof(uint32_t), v->stream), "Couldn't clear class data");
     // every distance is +trunc again: only the permanent boundary marks remain
     int rc0 = occupancy_reset(v);
     if (rc0 != TSDF_OK) return rc0;

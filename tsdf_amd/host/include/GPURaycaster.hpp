@@ -23,6 +23,12 @@ public:
     void raycast(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
                  Eigen::Matrix<float, 3, Eigen::Dynamic> &normals, std::vector<uchar3> &colours) const;
 
+    // raycast() plus the class of the voxel each vertex lies in and (votes may be null) its votes; (TSDF_CLASS_VOID, 0) for misses and
+    // unclassified voxels; the volume must have classes enabled (not in the reference's class)
+    void raycast_classes(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
+                         Eigen::Matrix<float, 3, Eigen::Dynamic> &normals, std::vector<uint16_t> &classes,
+                         std::vector<uint16_t> *votes = nullptr) const;
+
     // raycast() with the unit gradient of the fused field at every vertex in place of the cross-product normals (which are NaN along
     // every silhouette and beside every miss): tsdf_raycast_gradient_normals_device.  Same vertices; a miss is the NaN triple (not
     // in the reference's class)

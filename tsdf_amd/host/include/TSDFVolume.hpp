@@ -106,6 +106,21 @@ public:
     // integrate() plus the colour of `rgb` (8-bit interleaved RGB, width * height * 3, registered to the depth map); needs colour on
     void integrate(const uint16_t *depth_map, const uint8_t *rgb, uint32_t width, uint32_t height, const Camera &camera);
 
+    // Class fusion (include/tsdf_amd.h, "class fusion"; not in the reference's class): one {class, votes} dword per voxel while enabled.
+    // enable_classes(true) allocates it zeroed (throws std::invalid_argument on a Z-slab), false frees it.
+    void enable_classes(bool enabled);
+    bool classes_enabled() const;
+    // integrate() plus the vote of `classes` (width * height class ids registered to the depth map, TSDF_CLASS_VOID = none) with the
+    // strength `confidence` (width * height bytes; nullptr: 1 everywhere); `rgb` (or nullptr) as in the coloured integrate().  Throws
+    // std::invalid_argument while classes are off, on null classes and on rgb without colour.
+    void integrate_classes(const uint16_t *depth_map, const uint16_t *classes, uint32_t width, uint32_t height, const Camera &camera,
+                           const uint8_t *confidence = nullptr, const uint8_t *rgb = nullptr);
+    // classes[i] / votes[i] (votes may be null): the class of the voxel points[i] (world, mm) lies in and its votes; (TSDF_CLASS_VOID, 0)
+    // for NaN, off-grid and unclassified voxels
+    void sample_classes(const std::vector<float3> &points, std::vector<uint16_t> &classes, std::vector<uint16_t> *votes = nullptr) const;
+    // counts[k], k < n_classes (1..65535): the voxels whose class is k with at least max(min_votes, 1) votes
+    std::vector<uint64_t> class_counts(uint32_t n_classes, uint32_t min_votes = 1) const;
+
     // De-integration (include/tsdf_amd.h, "de-integration"; not in the reference's class): takes the frame of an earlier integrate() --
     // the same depth map at the same camera -- back out.  Throws std::invalid_argument on a volume with a weight cap.
     void deintegrate(const uint16_t *depth_map, uint32_t width, uint32_t height, const Camera &camera);

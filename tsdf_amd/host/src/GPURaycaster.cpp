@@ -33,6 +33,19 @@ void GPURaycaster::raycast(const TSDFVolume &volume, const Camera &camera, Eigen
           "process_ray failed ");
 }
 
+void GPURaycaster::raycast_classes(const TSDFVolume &volume, const Camera &camera, Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
+                                   Eigen::Matrix<float, 3, Eigen::Dynamic> &normals, std::vector<uint16_t> &classes,
+                                   std::vector<uint16_t> *votes) const {
+    vertices.resize(3, m_width * m_height);
+    normals.resize(3, m_width * m_height);
+    classes.resize((size_t)m_width * m_height);
+    if (votes) votes->resize((size_t)m_width * m_height);
+    const Eigen::Matrix3f kinv = camera.kinv();
+    check(tsdf_raycast_classes(volume.handle(), m_width, m_height, camera.pose().data(), kinv.data(), vertices.data(), normals.data(),
+                               classes.data(), votes ? votes->data() : nullptr),
+          "process_ray failed ");
+}
+
 void GPURaycaster::raycast_gradient_normals(const TSDFVolume &volume, const Camera &camera,
                                             Eigen::Matrix<float, 3, Eigen::Dynamic> &vertices,
                                             Eigen::Matrix<float, 3, Eigen::Dynamic> &normals) const {

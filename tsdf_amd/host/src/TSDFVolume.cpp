@@ -382,6 +382,52 @@ void TSDFVolume::integrate(const uint16_t *depth_map, const uint8_t *rgb, uint32
           "Integrate kernel failed");
 }
 
+// ---- class fusion (no reference counterpart)
+void TSDFVolume::enable_classes(bool enabled) {
+    check(tsdf_volume_enable_classes(m_handle, enabled ? 1 : 0), "Couldn't enable classes");
+    check(tsdf_volume_synchronize(m_handle), "Couldn't enable classes");
+}
+
+bool TSDFVolume::classes_enabled() const {
+    int enabled = 0;
+    check(tsdf_volume_classes_enabled(m_handle, &enabled), "Couldn't query classes");
+    return enabled != 0;
+}
+
+void TSDFVolume::integrate_classes(const uint16_t *depth_map, const uint16_t *classes, uint32_t width, uint32_t height, const Camera &camera,
+                                   const uint8_t *confidence, const uint8_t *rgb) {
+    const Eigen::Matrix3f k = camera.k(), kinv = camera.kinv();
+    check(tsdf_integrate_classes(m_handle, depth_map, rgb, classes, confidence, width, height, camera.pose().data(),
+                                 camera.inverse_pose().data(), k.data(), kinv.data()),
+          "Class integrate failed");
+}
+
+void TSDFVolume::sample_classes(const std::vector<float3> &points, std::vector<uint16_t> &classes, std::vector<uint16_t> *votes) const {
+    const size_t n = points.size(), in_bytes = n * 3 * sizeof(float), out_bytes = n * sizeof(uint16_t);
+    classes.assign(n, (uint16_t)TSDF_CLASS_VOID);
+    if (votes) votes->assign(n, 0);
+    void *d_buf = nullptr, *stream = nullptr;
+    check(tsdf_volume_stream(m_handle, &stream), "Class sample failed");
+    // (n == 0 still goes through the entry point: it refuses a volume without classes)
+    check(tsdf_device_alloc(in_bytes + 2 * out_bytes + 4, &d_buf), "Class sample alloc failed");
+    float *d_points = static_cast<float *>(d_buf);
+    uint16_t *d_classes = reinterpret_cast<uint16_t *>(d_points + 3 * n), *d_votes = d_classes + n;
+    int rc = n ? tsdf_device_upload(d_points, points.data(), in_bytes) : TSDF_OK;
+    if (rc == TSDF_OK) rc = tsdf_volume_sample_classes_device(m_handle, n, d_points, d_classes, d_votes, stream);
+    const int rs = tsdf_stream_synchronize(stream);   // (before the buffer goes, whatever happened)
+    if (rc == TSDF_OK) rc = rs;
+    if (rc == TSDF_OK && n) rc = tsdf_device_download(classes.data(), d_classes, out_bytes);
+    if (rc == TSDF_OK && n && votes) rc = tsdf_device_download(votes->data(), d_votes, out_bytes);
+    (void)tsdf_device_free(d_buf);
+    check(rc, "Class sample failed");
+}
+
+std::vector<uint64_t> TSDFVolume::class_counts(uint32_t n_classes, uint32_t min_votes) const {
+    std::vector<uint64_t> counts(n_classes ? n_classes : 1);
+    check(tsdf_volume_class_counts(m_handle, n_classes, min_votes, counts.data()), "Class counts failed");
+    return counts;
+}
+
 void TSDFVolume::integrate_weighted(const uint16_t *depth_map, const float *weights, uint32_t width, uint32_t height, const Camera &camera,
                                     const uint8_t *rgb) {
     assert(depth_map);

@@ -134,6 +134,27 @@ def colour_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, inside=Fal
     return trace_colour(cam, width, height), cam
 
 
+# per-object class id of the class image (trace_classes); CLASS_VOID = nothing hit (TSDF_CLASS_VOID of include/tsdf_amd.h)
+WALL_CLASS, SPHERE_CLASS, BOX_CLASS, CLASS_VOID = 1, 2, 3, 0xFFFF
+
+
+def trace_classes(camera, width=WIDTH, height=HEIGHT):
+    """Per-pixel class (uint16 (H*W,)) of the analytic scene, from _trace's object map: WALL_CLASS / SPHERE_CLASS / BOX_CLASS,
+    CLASS_VOID where nothing is hit (exactly where trace_depth is infinite)."""
+    obj = _trace(camera, width, height)[1]
+    lut = np.full(256, CLASS_VOID, np.uint16)
+    lut[WALL_B], lut[SPHERE_B], lut[BOX_B] = WALL_CLASS, SPHERE_CLASS, BOX_CLASS
+    return lut[obj].reshape(-1)
+
+
+def class_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, inside=False):
+    """-> (classes uint16 (H*W,), camera): the class frame registered to depth_frame(i, n, seed, ...) -- same camera, same pixels (a
+    depth dropout keeps its class).  Noise-free: `seed` is accepted for symmetry with depth_frame."""
+    del seed
+    cam = camera_for_frame(i, n, camera, inside)
+    return trace_classes(cam, width, height), cam
+
+
 def depth_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, noise=True, inside=False):
     """-> (depth uint16 (H*W,), camera) for frame i of an n-frame stream (inside: the config-4 trajectory within the volume)."""
     cam = camera_for_frame(i, n, camera, inside)
