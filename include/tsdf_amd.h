@@ -1006,7 +1006,7 @@ int tsdf_mesh_scratch_bytes(const tsdf_mesh *mesh, uint64_t *bytes);
  *   Refused (TSDF_ERR_INVALID, with a message): NULL device_labels, NULL device_indices with n_indices > 0, a NULL handle;
  *     n_indices % 3 != 0; n_vertices or n_indices above 2^32 - 1; an index >= n_vertices; dst == src; unknown flags; handles made on
  *     different devices.
- *   Out of scope: slab volumes, components of the volume's voxels, hole filling, labelling inside tsdf_volume_extract_mesh, labels
+ *   Out of scope: slab volumes, components of the volume's voxels (those of its frontier voxels: group "exploration"), hole filling, labelling inside tsdf_volume_extract_mesh, labels
  *     that stay stable across re-meshes.  Welding by position and simplification are the group "mesh simplification" below. */
 typedef struct tsdf_components_info {
     uint64_t n_components, n_triangles, largest_triangles;
@@ -1280,6 +1280,116 @@ int tsdf_esdf_sample(const tsdf_esdf *esdf, uint64_t n, const float *host_points
                      float *host_gradient, int flags);
 /* Device bytes the handle holds besides the output array. */
 int tsdf_esdf_scratch_bytes(const tsdf_esdf *esdf, uint64_t *bytes);
+
+/* ---- exploration (no reference counterpart: the reference's volume is asked about its surface only) -------------------------------- */
+/* What has not been seen yet, and from where could it be seen?  The free voxels that border unseen space (frontiers), their connected
+ * clusters, and the number of unseen voxels a set of rays would pass through (view gain) -- what a robot's next-best-view planner, a
+ * "scan here next" hint or a coverage report asks.  Opt-in by being called: no other entry point, launch or result changes; distances,
+ * weights, colours, classes, occupancy flags and counters are never written.  Results are integers and sets only (unique values,
+ * whatever computes them); two runs give the same bytes.
+ *   1. Voxel states.  X x Y x Z voxels, voxel (x, y, z) has id (z * Y + y) * X + x (uint32: more than 2^32 - 1 voxels are refused);
+ *      distances d and weights w as every accessor reports them (the same in 8-bit, 16-bit and fp32 storage).
+ *        UNKNOWN(v):  not w(v) > 0 (a NaN weight is unknown).
+ *        OCCUPIED(v): w(v) > 0 and d(v) < 0 -- the mesh's and the distance field's sign test: NaN and both zeros are not negative.
+ *        FREE(v):     otherwise.
+ *        FRONTIER(v): FREE(v) and at least one of the six face neighbours INSIDE the grid is UNKNOWN.  The grid border is not unknown
+ *                     space: a neighbour outside the grid counts for nothing.
+ *   2. tsdf_volume_find_frontiers fills the handle with the list of the ids of all frontier voxels in ascending order, and with the
+ *      whole-grid counts n_unknown, n_free, n_occupied (they sum to X * Y * Z) and n_frontiers (the length of the list).  It also
+ *      keeps, per 64 consecutive voxel ids, the 64-bit mask of the frontier voxels among them (bit l: id 64 c + l) and the list index of
+ *      the chunk's first frontier (the base): a listed voxel's list index is base[id / 64] + popcount(mask[id / 64] & ((1 << id % 64) - 1)),
+ *      and a voxel is listed iff its mask bit is set.  It runs on the volume's stream and waits for it once, to size the list.
+ *   3. tsdf_explorer_cluster_frontiers labels the listed voxels.  Two listed voxels are adjacent when their coordinates differ by at
+ *      most 1 on every axis and, at connectivity 6, on exactly one axis (face neighbours); at 26 on one, two or three axes (face, edge
+ *      and corner neighbours).  A cluster is a connected set of that graph.
+ *        L[i] (uint32, one per listed voxel): the smallest LIST INDEX in the cluster of list entry i.
+ *        Per cluster: label = that smallest index, size = its number of voxels, lo[k] / hi[k] = the smallest / largest coordinate on
+ *          axis k (the inclusive box; k = 0, 1, 2 for x, y, z), sum[k] = the integer sum of the coordinates on axis k -- the centroid
+ *          in voxel units is sum[k] / size, exact for whoever divides; its world position is offset[k] + (sum[k] / size + 0.5) * voxel_size[k].
+ *        The table holds one tsdf_frontier_cluster row per cluster with size >= min_size, in ascending label.  info.n_clusters counts
+ *          all clusters, info.n_listed_clusters the rows; info.connectivity is the connectivity last used (0: not clustered).
+ *      It runs on hip_stream behind the handle's pending work and waits for it once, to size the table.  How: the lock-free union-find
+ *      of "mesh components" over the list indices (hooks towards the smaller index), a lane per listed voxel uniting
+ *      with its 3 or 13 forward neighbours found through mask and base; sizes, sums and boxes by integer atomics.
+ *   4. View gain: n rays of the caller's own, in the ray frame of "ray queries": origins and directions are 3 n floats in world
+ *      millimetres, the volume's CURRENT offset is the grid's lower corner, the direction is used AS GIVEN and t is in units of it.
+ *      Every fp32 operation below is rounded on its own.  With o, d the origin and direction of ray i, offset and vs the volume's
+ *      offset and voxel size, N = (X, Y, Z):
+ *        a. The ray is SKIPPED (stop = 0, both counts 0) if a component of o or d is not finite; if d is all zeros (-0.0 included);
+ *           if t_max[i] is NaN or <= 0 (t_max NULL: +inf for every ray); or if any a_k or s_k of b. is not finite.
+ *        b. a_k = (o_k - offset_k) / vs_k, s_k = d_k / vs_k: the ray in voxel units, position a + t s.
+ *        c. Clip: t0 = 0, t1 = t_max[i].  Per axis k = x, y, z in turn: if s_k == 0, the ray is skipped unless 0 <= a_k < (float)N_k;
+ *           otherwise ta = (0 - a_k) / s_k, tb = ((float)N_k - a_k) / s_k, t0 = fmaxf(t0, fminf(ta, tb)), t1 = fminf(t1, fmaxf(ta, tb)).
+ *           Then the ray is skipped unless t0 < t1.
+ *        d. Start voxel: i_k = clamp((int)floorf(a_k + t0 * s_k), 0, N_k - 1) (the conversion saturates, NaN gives 0).  Per axis
+ *           step_k = +1 if s_k > 0 else -1, ahead_k = 1 if s_k > 0 else 0.
+ *        e. Walk, at most X + Y + Z voxels.  Visit the current voxel (f.).  Then the next boundary per axis with s_k != 0 is
+ *           tn_k = ((float)(i_k + ahead_k) - a_k) / s_k; the smallest wins, x before y before z on ties (y replaces x, and z the
+ *           winner so far, only if strictly smaller).  The walk ends if no axis has s_k != 0, if the winner's tn > t1, or if
+ *           i_k + step_k of the winning axis leaves [0, N_k); otherwise i_k += step_k and the next voxel is visited.
+ *        f. A visited voxel that is UNKNOWN: unknown[i] += 1, and the voxel's bit is set in a mask of one bit per voxel id that the
+ *           handle keeps.  OCCUPIED: the walk stops, stop[i] = 2, the voxel is counted nowhere.  FREE: free[i] += 1.  A walk that
+ *           ends in any other way (e., or the visit limit) has stop[i] = 1.
+ *        g. *host_gain = the number of set bits of the mask after the call: a voxel seen by many rays counts once.  The mask is
+ *           zeroed before the rays are walked unless TSDF_GAIN_KEEP_MASK is given; with it successive calls accumulate (the union), so
+ *           a greedy planner asks what a view adds to the views already chosen.  (A handle's first call, and the first after a
+ *           tsdf_volume_find_frontiers of another grid size, start from an empty mask either way.)
+ *      Any of unknown, free, stop and host_gain may be NULL, not all four.  The call enqueues on the volume's stream; with host_gain it
+ *      waits for it once, like tsdf_volume_fuse with fused_voxels.  n == 0 is TSDF_OK: no ray is walked (the mask is still zeroed or
+ *      kept, and counted when host_gain is given).
+ *   The handle (tsdf_explorer_create, on the current device) owns the list, the masks and bases, the labels, the table and the gain
+ *     mask, keeps them between calls and only grows them: a warm second call allocates nothing.  It remembers the geometry (sizes,
+ *     voxel sizes, offset) of the last tsdf_volume_find_frontiers, or of its first view gain, so nothing downstream needs the volume.
+ *     Scratch: 12 bytes per 64 voxels for masks and bases (3/16 byte a voxel) and 1 bit a voxel for the gain mask; clustering adds
+ *     56 bytes per listed voxel and 12 per 64 of them (tsdf_explorer_scratch_bytes: everything but the list, the labels and the table).
+ *     A handle is used by one thread at a time.  tsdf_explorer_destroy(NULL) is ignored.
+ *   tsdf_explorer_frontier_buffers: the device arrays (any pointer may be NULL; the list is NULL when it is empty);
+ *     tsdf_explorer_frontier_download copies the list (n_frontiers words).  tsdf_explorer_cluster_buffers gives the labels (n_frontiers
+ *     words) and the table (n_listed_clusters rows), NULL where empty; tsdf_explorer_cluster_download copies them (either pointer may be
+ *     NULL).  All four wait for the handle's pending work.  The frontier pair refuses a handle without a tsdf_volume_find_frontiers, the
+ *     cluster pair one not clustered since its last tsdf_volume_find_frontiers.
+ *   Refused (TSDF_ERR_INVALID, with a message naming the entry point): NULL handles or volumes; a Z-slab volume; a materialised
+ *     deformation-node array; unknown flags; a connectivity other than 6 or 26; clustering before any tsdf_volume_find_frontiers; NULL
+ *     origins or directions with n > 0; all four outputs NULL; more rays than a launch holds (n > (2^31 - 1) * 256); a view gain with
+ *     a handle whose geometry (sizes, voxel sizes, offset) is not the volume's, unless the handle is fresh -- it then adopts the volume's.
+ *   Out of scope: frontiers inside the pipeline step or the tracker, Z-slabs, incremental updates, and planning itself. */
+typedef struct tsdf_explorer tsdf_explorer;
+#define TSDF_GAIN_KEEP_MASK 1u
+typedef struct tsdf_explorer_info {
+    uint32_t size[3];
+    uint32_t connectivity;   /* of the last clustering; 0: not clustered since the last tsdf_volume_find_frontiers */
+    float voxel_size[3];
+    float offset[3];         /* the volume's current offset when the geometry was taken */
+    uint64_t n_unknown, n_free, n_occupied, n_frontiers;
+    uint64_t n_clusters, n_listed_clusters;
+} tsdf_explorer_info;
+typedef struct tsdf_frontier_cluster {
+    uint32_t label, size;
+    uint32_t lo[3], hi[3];
+    uint64_t sum[3];
+} tsdf_frontier_cluster;
+int tsdf_explorer_create(tsdf_explorer **out);   /* on the current device */
+void tsdf_explorer_destroy(tsdf_explorer *explorer);
+int tsdf_volume_find_frontiers(const tsdf_volume *volume, uint32_t flags /* none defined: 0 */, tsdf_explorer *explorer);
+int tsdf_explorer_get_info(const tsdf_explorer *explorer, tsdf_explorer_info *info);
+int tsdf_explorer_frontier_buffers(const tsdf_explorer *explorer, const uint32_t **device_voxels, const uint64_t **device_masks,
+                                   const uint32_t **device_bases);
+int tsdf_explorer_frontier_download(const tsdf_explorer *explorer, uint32_t *host_voxels);
+/* Device bytes the handle holds besides the list, the labels and the table. */
+int tsdf_explorer_scratch_bytes(const tsdf_explorer *explorer, uint64_t *bytes);
+int tsdf_explorer_cluster_frontiers(tsdf_explorer *explorer, uint32_t connectivity, uint32_t min_size, void *hip_stream);
+int tsdf_explorer_cluster_buffers(const tsdf_explorer *explorer, const uint32_t **device_labels,
+                                  const tsdf_frontier_cluster **device_clusters);
+int tsdf_explorer_cluster_download(const tsdf_explorer *explorer, uint32_t *host_labels, tsdf_frontier_cluster *host_clusters);
+/* Device arrays for the rays and the per-ray outputs; host_gain is a host pointer. */
+int tsdf_volume_view_gain_device(const tsdf_volume *volume, tsdf_explorer *explorer, uint64_t n, const float *device_origins,
+                                 const float *device_directions, const float *device_t_max /* n floats, or NULL = no limit */,
+                                 uint32_t flags, uint32_t *device_unknown, uint32_t *device_free, uint8_t *device_stop,
+                                 uint64_t *host_gain);
+/* The same on host arrays, on the volume's stream; blocking. */
+int tsdf_volume_view_gain(const tsdf_volume *volume, tsdf_explorer *explorer, uint64_t n, const float *host_origins,
+                          const float *host_directions, const float *host_t_max, uint32_t flags, uint32_t *host_unknown,
+                          uint32_t *host_free, uint8_t *host_stop, uint64_t *host_gain);
 
 /* ---- sparse snapshot (no reference counterpart: the reference saves a volume densely, and cannot load one) ------------------------ */
 /* The state of a whole volume as the bricks that hold anything but what clear() leaves: taken out of the dense arrays on the device,

@@ -18,6 +18,7 @@ TSDF_MESH_KEEP_LARGEST = 1
 TSDF_CLASS_VOID = 0xFFFF
 TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
+TSDF_GAIN_KEEP_MASK = 1
 TSDF_SCENE_FLOW_DEFORMED = 1
 TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
 TSDF_WEIGHTS_INVERSE_SQUARE, TSDF_WEIGHTS_COSINE = 1, 2
@@ -58,6 +59,18 @@ class EsdfInfo(C.Structure):
     """struct tsdf_esdf_info (include/tsdf_amd.h)."""
     _fields_ = [("size", C.c_uint32 * 3), ("flags", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
                 ("max_distance", C.c_float), ("n_sites", C.c_uint64)]
+
+
+class ExplorerInfo(C.Structure):
+    """struct tsdf_explorer_info (include/tsdf_amd.h)."""
+    _fields_ = [("size", C.c_uint32 * 3), ("connectivity", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
+                ("n_unknown", C.c_uint64), ("n_free", C.c_uint64), ("n_occupied", C.c_uint64), ("n_frontiers", C.c_uint64),
+                ("n_clusters", C.c_uint64), ("n_listed_clusters", C.c_uint64)]
+
+
+class FrontierCluster(C.Structure):
+    """struct tsdf_frontier_cluster (include/tsdf_amd.h): 56 bytes, sum at offset 32."""
+    _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("sum", C.c_uint64 * 3)]
 
 
 class SnapshotInfo(C.Structure):
@@ -262,6 +275,18 @@ _SIGS = {
     "tsdf_esdf_sample_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _i, _vp]),
     "tsdf_esdf_sample": (_i, [_vp, C.c_uint64, _vp, _vp, _vp, _i]),
     "tsdf_esdf_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_explorer_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_explorer_destroy": (None, [_vp]),
+    "tsdf_volume_find_frontiers": (_i, [_vp, _u32, _vp]),
+    "tsdf_explorer_get_info": (_i, [_vp, C.POINTER(ExplorerInfo)]),
+    "tsdf_explorer_frontier_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_explorer_frontier_download": (_i, [_vp, _vp]),
+    "tsdf_explorer_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_explorer_cluster_frontiers": (_i, [_vp, _u32, _u32, _vp]),
+    "tsdf_explorer_cluster_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_explorer_cluster_download": (_i, [_vp, _vp, _vp]),
+    "tsdf_volume_view_gain_device": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "tsdf_volume_view_gain": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "tsdf_snapshot_create": (_i, [C.POINTER(_vp)]),
     "tsdf_snapshot_destroy": (None, [_vp]),
     "tsdf_volume_snapshot": (_i, [_vp, _u32, _vp]),

@@ -595,6 +595,58 @@ class TSDFVolume:
         check(lib.tsdf_volume_compute_esdf(self._h, float(max_distance), _capi.TSDF_ESDF_FILL_UNKNOWN if fill_unknown else 0, esdf._h))
         return esdf
 
+    # ---- exploration (include/tsdf_amd.h, "exploration"; not in the reference's class)
+    def find_frontiers(self, into=None):
+        """The free voxels with an unobserved face neighbour inside the grid (tsdf_volume_find_frontiers), as an ascending list of voxel
+        ids that stays on the device, with the whole-grid counts of unknown, free and occupied voxels.  `into`: an Explorer to reuse
+        -- its arrays are kept and only grow.  Returns the Explorer."""
+        explorer = Explorer() if into is None else into
+        check(lib.tsdf_volume_find_frontiers(self._h, 0, explorer._h))
+        return explorer
+
+    def view_gain_device(self, explorer, n, origins_ptr, directions_ptr, t_max_ptr=None, unknown_ptr=None, free_ptr=None, stop_ptr=None,
+                         keep=False, gain=True):
+        """n rays (origins and directions 3 float32 each, t_max n float32 or None; device) -> unknown (n uint32), free (n uint32), stop
+        (n uint8): device pointers, any may be None.  gain: wait for the volume's stream and return the number of distinct unknown
+        voxels marked in `explorer` (None otherwise: asynchronous); keep: add to the marks of earlier calls."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        g = C.c_uint64(0)
+        check(lib.tsdf_volume_view_gain_device(self._h, explorer._h, int(n), ptr(origins_ptr), ptr(directions_ptr), ptr(t_max_ptr),
+                                               _capi.TSDF_GAIN_KEEP_MASK if keep else 0, ptr(unknown_ptr), ptr(free_ptr), ptr(stop_ptr),
+                                               C.byref(g) if gain else None))
+        return int(g.value) if gain else None
+
+    def view_gain(self, origins, directions, t_max=None, explorer=None, keep=False):
+        """(n, 3) float32 origins and directions (world mm; the direction is used as given, t_max (n,) is in units of it) -> (gain,
+        unknown (n,) uint32, free (n,) uint32, stop (n,) uint8): each ray is walked voxel by voxel until it leaves the grid, passes
+        t_max (stop 1) or meets an occupied voxel (stop 2); unknown / free count the voxels it passed in either state, gain the
+        distinct unknown voxels all rays passed (stop 0: the ray was skipped).  explorer: the Explorer whose mask takes the marks (None:
+        a private one); keep: add to the marks of earlier calls with that explorer, so gain is that of the union."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        if len(d) != n:
+            raise ValueError("view_gain: %d origins, %d directions" % (n, len(d)))
+        m = None
+        if t_max is not None:
+            m = np.ascontiguousarray(t_max, dtype=np.float32).reshape(-1)
+            if len(m) != n:
+                raise ValueError("view_gain: %d rays, %d range limits" % (n, len(m)))
+        own = explorer is None
+        if own:
+            explorer = Explorer()
+        # (one element more than asked for: the pointer of an empty array may be null, which the C ABI reads as "not asked for")
+        u, f, s = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint8)
+        g = C.c_uint64(0)
+        try:
+            check(lib.tsdf_volume_view_gain(self._h, explorer._h, n, o.ctypes.data if n else None, d.ctypes.data if n else None,
+                                            m.ctypes.data if (m is not None and n) else None, _capi.TSDF_GAIN_KEEP_MASK if keep else 0,
+                                            u.ctypes.data, f.ctypes.data, s.ctypes.data, C.byref(g)))
+        finally:
+            if own:
+                explorer.close()
+        return int(g.value), u[:n], f[:n], s[:n]
+
     # ---- sparse snapshots (include/tsdf_amd.h, "sparse snapshot"; not in the reference's class)
     def _file_header(self):
         """The fields of the .tsdf header as the volume reports them now."""
@@ -1305,6 +1357,121 @@ class ESDF:
         n = C.c_uint64(0)
         check(lib.tsdf_esdf_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
+
+
+#: one row of Explorer.clusters: struct tsdf_frontier_cluster (56 bytes)
+CLUSTER_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.uint32, 3), ("hi", np.uint32, 3), ("sum", np.uint64, 3)])
+
+
+class Explorer:
+    """tsdf_explorer (include/tsdf_amd.h, "exploration"): the frontier voxels of a volume (TSDFVolume.find_frontiers(into=explorer)),
+    their clusters (cluster()) and the mask of unknown voxels that view-gain rays have passed (TSDFVolume.view_gain(explorer=...)), on
+    the device, with the geometry they belong to.  Nothing here needs the volume."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        check(lib.tsdf_explorer_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            lib.tsdf_explorer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def info(self):
+        """tsdf_explorer_info: size, connectivity, voxel_size, offset, n_unknown, n_free, n_occupied, n_frontiers, n_clusters,
+        n_listed_clusters."""
+        i = _capi.ExplorerInfo()
+        check(lib.tsdf_explorer_get_info(self._h, C.byref(i)))
+        return i
+
+    @property
+    def voxels(self):
+        """(n_frontiers,) uint32: the ids (z * Y + y) * X + x of the frontier voxels, ascending; a blocking download."""
+        n = int(self.info.n_frontiers)
+        out = np.empty(n + 1, np.uint32)   # (one element more: the pointer of an empty array may be null)
+        check(lib.tsdf_explorer_frontier_download(self._h, out.ctypes.data))
+        return out[:n]
+
+    @property
+    def coordinates(self):
+        """(n_frontiers, 3) uint32: (x, y, z) of the frontier voxels."""
+        sx, sy, _ = (int(v) for v in self.info.size)
+        ids = self.voxels.astype(np.uint64)
+        return np.stack([ids % sx, (ids // sx) % sy, ids // (sx * sy)], axis=1).astype(np.uint32)
+
+    @property
+    def points(self):
+        """(n_frontiers, 3) float32: the world centres (mm) of the frontier voxels, offset + (coordinate + 0.5) * voxel_size."""
+        i = self.info
+        vs, off = np.array(i.voxel_size, np.float32), np.array(i.offset, np.float32)
+        return ((self.coordinates.astype(np.float32) + np.float32(0.5)) * vs + off).astype(np.float32)
+
+    def cluster(self, connectivity=26, min_size=1, stream=0):
+        """Label the connected sets of frontier voxels (tsdf_explorer_cluster_frontiers): connectivity 6 (faces) or 26 (faces, edges,
+        corners); the table lists the clusters of at least min_size voxels.  Returns the explorer."""
+        check(lib.tsdf_explorer_cluster_frontiers(self._h, int(connectivity), int(min_size), C.c_void_p(int(stream) if stream else 0)))
+        return self
+
+    def _download_clusters(self):
+        i = self.info
+        labels = np.empty(int(i.n_frontiers) + 1, np.uint32)
+        rows = np.zeros(int(i.n_listed_clusters) + 1, CLUSTER_DTYPE)
+        check(lib.tsdf_explorer_cluster_download(self._h, labels.ctypes.data, rows.ctypes.data))
+        return labels[:-1], rows[:-1]
+
+    @property
+    def labels(self):
+        """(n_frontiers,) uint32: per listed voxel the smallest list index of its cluster."""
+        return self._download_clusters()[0]
+
+    @property
+    def clusters(self):
+        """(n_listed_clusters,) CLUSTER_DTYPE rows in ascending label: label, size, lo / hi (the inclusive voxel box), sum (the integer
+        coordinate sums)."""
+        return self._download_clusters()[1]
+
+    @property
+    def centroids(self):
+        """(n_listed_clusters, 3) float64: the world centroid (mm) of every listed cluster, offset + (sum / size + 0.5) * voxel_size."""
+        i, rows = self.info, self.clusters
+        vs, off = np.array(i.voxel_size, np.float64), np.array(i.offset, np.float64)
+        return (rows["sum"].astype(np.float64) / np.maximum(rows["size"], 1)[:, None] + 0.5) * vs + off
+
+    def device_buffers(self):
+        """Raw device pointers {voxels, masks, bases, labels, clusters} (0 where empty or not clustered); valid until the next call
+        that fills them."""
+        v, m, b = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib.tsdf_explorer_frontier_buffers(self._h, C.byref(v), C.byref(m), C.byref(b)))
+        out = {"voxels": int(v.value or 0), "masks": int(m.value or 0), "bases": int(b.value or 0), "labels": 0, "clusters": 0}
+        if self.info.connectivity:
+            l, r = C.c_void_p(), C.c_void_p()
+            check(lib.tsdf_explorer_cluster_buffers(self._h, C.byref(l), C.byref(r)))
+            out["labels"], out["clusters"] = int(l.value or 0), int(r.value or 0)
+        return out
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides the list, the labels and the table."""
+        n = C.c_uint64(0)
+        check(lib.tsdf_explorer_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+
+def pixel_rays(camera, width, height, step=1):
+    """The rays of every step-th pixel of a width x height pinhole view, for TSDFVolume.view_gain and cast_rays: (origins, directions),
+    (n, 3) float32 each, rows first.  The origin is the camera's position; the direction of pixel (u, v) is R (K^-1 (u, v, 1)) in float32,
+    not normalised -- t is the camera depth, as in the image cast."""
+    pose, _, _, kinv = _camera_matrices(camera)
+    P, Ki = pose.reshape(4, 4).T, kinv.reshape(3, 3).T
+    step = max(int(step), 1)
+    v, u = np.meshgrid(np.arange(0, int(height), step, dtype=np.float32), np.arange(0, int(width), step, dtype=np.float32), indexing="ij")
+    pix = np.stack([u.reshape(-1), v.reshape(-1), np.ones(u.size, np.float32)], axis=1)
+    d = ((pix @ Ki.T).astype(np.float32) @ P[:3, :3].T).astype(np.float32)
+    o = np.broadcast_to(P[:3, 3].astype(np.float32), d.shape)
+    return np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)
 
 
 SPARSE_MAGIC = b"TSDFSPR1"

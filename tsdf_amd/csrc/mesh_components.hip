@@ -26,43 +26,13 @@
 #include "common.hpp"
 #include "mesh_device.hpp"
 #include "mesh_handle.hpp"
+#include "union_find.hpp"
 
 namespace tsdf {
 
 enum { kWordError = 0, kWordRoots = 1, kWordLargest = 2 };   // tsdf_mesh::component_words
 
-__device__ inline uint32_t parent_load(const uint32_t *parent, uint32_t v) {
-    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The root the chain from x ends in.  SHORTEN: every node passed whose parent has a parent is pointed at that grandparent, with
-// atomicMin (the word can only get smaller, and a grandparent -- fresh or stale -- is a smaller member of the same tree).
-// Bounded: x strictly decreases.
-template <bool SHORTEN>
-__device__ inline uint32_t components_find(uint32_t *parent, uint32_t x) {
-    uint32_t p = parent_load(parent, x);
-    while (p != x) {
-        const uint32_t g = parent_load(parent, p);
-        if (SHORTEN && g != p) atomicMin(parent + x, g);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-// Bounded: a + b strictly decreases with every trip (find never goes up, and a failed CAS returns a word below hi).
-__device__ inline void components_unite(uint32_t *parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = components_find<true>(parent, a);
-        b = components_find<true>(parent, b);
-        if (a == b) return;
-        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const uint32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = old;   // someone else hooked hi, below itself: go on from there
-        b = lo;
-    }
-}
+// (parent_load, components_find and components_unite: union_find.hpp, shared with explore.hip)
 
 __global__ __launch_bounds__(256) void components_init_kernel(uint32_t n_vertices, uint32_t *__restrict__ parent, uint32_t *__restrict__ sizes) {
     const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;

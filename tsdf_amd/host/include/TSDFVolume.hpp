@@ -21,6 +21,8 @@ struct tsdf_volume;  // C-ABI handle (include/tsdf_amd.h)
 struct tsdf_esdf;    // distance-field handle (include/tsdf_amd.h)
 struct tsdf_mesh;    // indexed-mesh handle (include/tsdf_amd.h)
 struct tsdf_snapshot;  // sparse-snapshot handle (include/tsdf_amd.h)
+struct tsdf_explorer;  // exploration handle (include/tsdf_amd.h)
+struct tsdf_frontier_cluster;  // a row of its cluster table (include/tsdf_amd.h)
 
 class TSDFVolume {
 public:
@@ -215,6 +217,46 @@ public:
     std::vector<float> compute_esdf(float max_distance, bool fill_unknown = false) const;
     // the same into a caller's handle (tsdf_esdf_create), where it stays on the device: tsdf_esdf_buffer, tsdf_esdf_sample_device
     void compute_esdf(float max_distance, bool fill_unknown, tsdf_esdf *esdf) const;
+
+    // Exploration (include/tsdf_amd.h, "exploration"; not in the reference's class): the free voxels with an unobserved face neighbour
+    // (frontiers), their clusters, and the mask of unobserved voxels that view-gain rays have passed, in a handle that keeps its device
+    // arrays between calls.
+    class Explorer {
+    public:
+        Explorer();    // throws std::invalid_argument / exits like every device failure when the handle cannot be made
+        ~Explorer();
+        Explorer(const Explorer &) = delete;
+        Explorer &operator=(const Explorer &) = delete;
+        inline tsdf_explorer *handle() const { return m_handle; }
+        // the whole-grid counts of the last find_frontiers
+        uint64_t n_unknown() const;
+        uint64_t n_free() const;
+        uint64_t n_occupied() const;
+        uint64_t n_frontiers() const;
+        // the ids (z * Y + y) * X + x of the frontier voxels, ascending; a blocking download
+        std::vector<uint32_t> voxels() const;
+        // Label the connected sets of frontier voxels, connectivity 6 or 26; the table lists those of at least min_size voxels.
+        // Returns the number of clusters (of any size).  Throws std::invalid_argument on another connectivity or before find_frontiers.
+        uint64_t cluster(uint32_t connectivity = 26, uint32_t min_size = 1);
+        // per listed voxel the smallest list index of its cluster / the table's rows in ascending label (tsdf_frontier_cluster,
+        // include/tsdf_amd.h); blocking downloads
+        std::vector<uint32_t> labels() const;
+        std::vector<tsdf_frontier_cluster> clusters() const;
+
+    private:
+        tsdf_explorer *m_handle;
+    };
+    // The frontiers of this volume into `into` (nothing of the volume is written).  Throws std::invalid_argument on the refusals (a
+    // Z-slab, materialised deformation nodes).
+    void find_frontiers(Explorer &into) const;
+    // View gain: every ray (world mm, the direction used as given, t_max in units of it or null for no limit) is walked voxel by voxel
+    // until it leaves the grid or passes t_max (stop 1) or meets an occupied voxel (stop 2; 0: the ray was skipped); unknown / free count
+    // the voxels it passed in either state.  Returns the number of distinct unobserved voxels marked in `explorer` after the call; `keep`
+    // adds to the marks of earlier calls.  The three outputs may be null.  Throws std::invalid_argument on the refusals (arrays of
+    // different lengths, an explorer that holds another volume's geometry).
+    uint64_t view_gain(Explorer &explorer, const std::vector<float3> &origins, const std::vector<float3> &directions,
+                       const std::vector<float> *t_max = nullptr, bool keep = false, std::vector<uint32_t> *unknown = nullptr,
+                       std::vector<uint32_t> *free_voxels = nullptr, std::vector<uint8_t> *stop = nullptr) const;
 
     // Scene flow (include/tsdf_amd.h, "scene flow"; the device part of the reference's process_frames, SceneFusion_krnl.hpp): the
     // vertices of `mesh` -- a handle holding tsdf_volume_extract_mesh of this volume's whole grid -- that the depth frame sees take the

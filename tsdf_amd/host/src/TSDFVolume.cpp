@@ -189,6 +189,77 @@ std::vector<float> TSDFVolume::compute_esdf(float max_distance, bool fill_unknow
     return distances;
 }
 
+TSDFVolume::Explorer::Explorer() : m_handle{nullptr} { check(tsdf_explorer_create(&m_handle), "Couldn't create the explorer handle"); }
+
+TSDFVolume::Explorer::~Explorer() { tsdf_explorer_destroy(m_handle); }
+
+namespace {
+
+tsdf_explorer_info explorer_info(const tsdf_explorer *e) {
+    tsdf_explorer_info info;
+    check(tsdf_explorer_get_info(e, &info), "Couldn't query the explorer");
+    return info;
+}
+
+}  // namespace
+
+uint64_t TSDFVolume::Explorer::n_unknown() const { return explorer_info(m_handle).n_unknown; }
+uint64_t TSDFVolume::Explorer::n_free() const { return explorer_info(m_handle).n_free; }
+uint64_t TSDFVolume::Explorer::n_occupied() const { return explorer_info(m_handle).n_occupied; }
+uint64_t TSDFVolume::Explorer::n_frontiers() const { return explorer_info(m_handle).n_frontiers; }
+
+std::vector<uint32_t> TSDFVolume::Explorer::voxels() const {
+    // (one element more than needed: data() of an empty vector may be null)
+    std::vector<uint32_t> ids((size_t)explorer_info(m_handle).n_frontiers + 1, 0u);
+    check(tsdf_explorer_frontier_download(m_handle, ids.data()), "Couldn't download the frontiers");
+    ids.pop_back();
+    return ids;
+}
+
+uint64_t TSDFVolume::Explorer::cluster(uint32_t connectivity, uint32_t min_size) {
+    check(tsdf_explorer_cluster_frontiers(m_handle, connectivity, min_size, nullptr), "Couldn't cluster the frontiers");
+    return explorer_info(m_handle).n_clusters;
+}
+
+std::vector<uint32_t> TSDFVolume::Explorer::labels() const {
+    std::vector<uint32_t> labels((size_t)explorer_info(m_handle).n_frontiers + 1, 0u);
+    check(tsdf_explorer_cluster_download(m_handle, labels.data(), nullptr), "Couldn't download the frontier labels");
+    labels.pop_back();
+    return labels;
+}
+
+std::vector<tsdf_frontier_cluster> TSDFVolume::Explorer::clusters() const {
+    std::vector<tsdf_frontier_cluster> rows((size_t)explorer_info(m_handle).n_listed_clusters + 1, tsdf_frontier_cluster());
+    check(tsdf_explorer_cluster_download(m_handle, nullptr, rows.data()), "Couldn't download the frontier clusters");
+    rows.pop_back();
+    return rows;
+}
+
+void TSDFVolume::find_frontiers(Explorer &into) const { check(tsdf_volume_find_frontiers(m_handle, 0u, into.handle()), "Couldn't find the frontiers"); }
+
+uint64_t TSDFVolume::view_gain(Explorer &explorer, const std::vector<float3> &origins, const std::vector<float3> &directions,
+                               const std::vector<float> *t_max, bool keep, std::vector<uint32_t> *unknown, std::vector<uint32_t> *free_voxels,
+                               std::vector<uint8_t> *stop) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    const size_t n = origins.size();
+    if (directions.size() != n) throw std::invalid_argument("view_gain: origins and directions differ in length");
+    if (t_max && t_max->size() != n) throw std::invalid_argument("view_gain: t_max and the rays differ in length");
+    // (one element more than needed: data() of an empty vector may be null, which the C ABI reads as "not asked for")
+    if (unknown) unknown->assign(n + 1, 0u);
+    if (free_voxels) free_voxels->assign(n + 1, 0u);
+    if (stop) stop->assign(n + 1, (uint8_t)0);
+    uint64_t gain = 0;
+    check(tsdf_volume_view_gain(m_handle, explorer.handle(), n, reinterpret_cast<const float *>(origins.data()),
+                                reinterpret_cast<const float *>(directions.data()), (t_max && n) ? t_max->data() : nullptr,
+                                keep ? TSDF_GAIN_KEEP_MASK : 0u, unknown ? unknown->data() : nullptr, free_voxels ? free_voxels->data() : nullptr,
+                                stop ? stop->data() : nullptr, &gain),
+          "Couldn't compute the view gain");
+    if (unknown) unknown->resize(n);
+    if (free_voxels) free_voxels->resize(n);
+    if (stop) stop->resize(n);
+    return gain;
+}
+
 void TSDFVolume::cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
                            std::vector<float> *t, std::vector<float3> *normals, const std::vector<float> *t_max) const {
     static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
