@@ -465,7 +465,8 @@ int tsdf_raycast_colour_device(const tsdf_volume *volume, uint32_t width, uint32
  *     tsdf_integrate_rays*, tsdf_volume_fuse, snapshots and restore, the .tsdf and .tsdfs files, tsdf_pipeline_step* and
  *     tsdf_tracker_* neither read nor write class words.
  *   Out of scope: classes in the pipeline step, the tracker and kinfu_stream; classes from ray sets; classes through fuse, snapshots
- *     and files; a per-vertex class array inside the mesh handle and a filter by class; the class at tsdf_volume_cast_rays* hits. */
+ *     and files; a per-vertex class array inside the mesh handle and a filter by class; the class at tsdf_volume_cast_rays* hits.  (The connected pieces of each
+ *     class, and which of them a point lies in: group "class objects".) */
 #define TSDF_CLASS_VOID 0xFFFFu
 int tsdf_volume_enable_classes(tsdf_volume *volume, int enabled);   /* 1: allocate zeroed (kept if already enabled), 0: free */
 int tsdf_volume_classes_enabled(const tsdf_volume *volume, int *enabled);
@@ -1390,6 +1391,93 @@ int tsdf_volume_view_gain_device(const tsdf_volume *volume, tsdf_explorer *explo
 int tsdf_volume_view_gain(const tsdf_volume *volume, tsdf_explorer *explorer, uint64_t n, const float *host_origins,
                           const float *host_directions, const float *host_t_max, uint32_t flags, uint32_t *host_unknown,
                           uint32_t *host_free, uint8_t *host_stop, uint64_t *host_gain);
+
+/* ---- class objects (no reference counterpart; the per-object maps of Voxblox++, Kimera and SemanticFusion) -------------------------- */
+/* Which objects are in the scene, where is each, how big is it, and which object did this ray or pixel hit?  The connected pieces of
+ * each fused class (group "class fusion"), on the device.  Opt-in by being called: no other entry point, launch or result changes.
+ * Only the class words are read; distances, weights and colours are never read, and nothing of the volume is written.
+ *   1. Labelled voxels.  Grid and voxel ids as in "exploration": X x Y x Z voxels, voxel (x, y, z) has id (z * Y + y) * X + x (uint32:
+ *      more than 2^32 - 1 voxels are refused).  The word (c, n) of a voxel -- class c in bits 0-15, votes n in bits 16-31 -- is what
+ *      tsdf_volume_get_class_data reports.  A voxel is LABELLED iff
+ *        n >= max(min_votes, 1), and
+ *        the selection admits c: host_select == NULL admits every class; otherwise host_select is n_select bytes and admits c iff
+ *          c < n_select && host_select[c] != 0.
+ *      A word with n == 0 is unlabelled whatever its class bits are.
+ *   2. List.  The handle holds the ids of all labelled voxels in ascending order; n_labelled is the list's length.  Per 64 consecutive
+ *      voxel ids it keeps the 64-bit mask of the labelled voxels among them (bit l: id 64 c + l) and the list index of the chunk's
+ *      first labelled voxel (the base), exactly as the explorer keeps them: a listed voxel's list index is
+ *      base[id / 64] + popcount(mask[id / 64] & ((1 << id % 64) - 1)), and a voxel is listed iff its mask bit is set.
+ *   3. Objects.  Two listed voxels are adjacent iff they are neighbours at the chosen connectivity -- 6 or 26, as in "exploration"
+ *      rule 3: their coordinates differ by at most 1 on every axis and, at 6, on exactly one axis -- AND their class ids are equal.
+ *      An object is a connected set of that graph.
+ *        L[i] (uint32, one per listed voxel): the smallest LIST INDEX in the object of list entry i.
+ *        Per object a tsdf_class_object row (72 bytes): label = that smallest index, size = its number of voxels, lo[k] / hi[k] =
+ *          the smallest / largest coordinate on axis k (the inclusive box; k = 0, 1, 2 for x, y, z), sum[k] = the integer sum of the
+ *          coordinates on axis k, votes = the sum of the members' vote counts, class_id = the class all members share, reserved = 0.
+ *          The centroid's world position is offset[k] + (sum[k] / size + 0.5) * voxel_size[k], as for a frontier cluster.
+ *        The table holds the rows with size >= min_size, in ascending label.  info.n_objects counts all objects,
+ *          info.n_listed_objects the rows.
+ *   4. Lookup.  tsdf_objects_lookup_device resolves n world points (3 floats each) to table rows.  For each point it takes the voxel
+ *      tsdf_volume_sample_classes_device reads for that point -- the same frame (offset_at_clear subtracted), the same index
+ *      expression -- with the geometry (sizes, voxel sizes, offset, offset_at_clear) the handle remembers from the last
+ *      tsdf_volume_find_objects.  rows[i] is the 0-based index in the table of the object that holds the voxel, or TSDF_OBJECT_NONE
+ *      for a NaN coordinate, an off-grid index, an unlisted voxel, or an object below min_size.  The row is found through a second
+ *      mask and base pair over list indices (bit l of row_mask[j]: list index 64 j + l is the label of a listed row): the row of list
+ *      entry i is row_base[L[i] / 64] + popcount(row_mask[L[i] / 64] & ((1 << L[i] % 64) - 1)).  n == 0 is TSDF_OK and launches nothing.
+ *      An instance-segmentation image is this lookup on a ray cast's vertices (misses are NaN: TSDF_OBJECT_NONE).
+ *      tsdf_objects_lookup_device enqueues on hip_stream behind the handle's pending work; tsdf_objects_lookup is the same on host
+ *      arrays, on the null stream, blocking.
+ *   5. Uniqueness.  Everything is a set, an integer sum, a minimum or a maximum: two runs give the same bytes, whatever order the
+ *      waves run in.  No float atomics.  No lane ever waits for another: no spin loops, locks or flags.  Every loop has a stated
+ *      bound: a lane's hook makes 13 trips, a wave's root loop 64, and the union-find's walks are bounded as DESIGN.md 20 argues.
+ *   tsdf_volume_find_objects runs list, labels and table on the volume's stream and waits for it twice, once to size the list and once
+ *     to size the table (once when the list is empty).  flags: none defined, 0.
+ *   The handle (tsdf_objects_create, on the current device) owns the list, the masks and bases, the labels and the table, keeps them
+ *     between calls and only grows them: a warm second call allocates nothing and leaves tsdf_objects_scratch_bytes unchanged.
+ *     Scratch (tsdf_objects_scratch_bytes: everything but the list, the labels and the table): 12 bytes per 64 voxels for masks and
+ *     bases (3/16 byte a voxel), the chunk scan's sums, the device copy of the selection (n_select bytes), 72 bytes per listed voxel
+ *     for the accumulator rows and 12 per 64 of them for the row masks and bases.  A handle is used by one thread at a time.
+ *     tsdf_objects_destroy(NULL) is ignored.
+ *   tsdf_objects_buffers: the device arrays -- the list and the labels (n_labelled words each), the masks and bases (one per 64 voxel
+ *     ids), the table (n_listed_objects rows); any pointer may be NULL, a buffer is NULL where it is empty.  tsdf_objects_download
+ *     copies list, labels and table (any pointer may be NULL).  Both wait for the handle's pending work.
+ *   Refused (TSDF_ERR_INVALID, with a message naming the entry point, nothing written): NULL handles or volumes; a volume without
+ *     classes enabled; more than 2^32 - 1 voxels; a connectivity other than 6 or 26; unknown flags; host_select == NULL with
+ *     n_select > 0, or n_select > 65535; buffers, download or lookup before any tsdf_volume_find_objects; NULL points or rows with n > 0.
+ *   Out of scope: objects in the pipeline step or the tracker; labels that stay stable across calls; per-object meshes (a row's box
+ *     feeds tsdf_volume_extract_mesh); merging objects across classes; classes through fuse, snapshots and files. */
+typedef struct tsdf_objects tsdf_objects;
+#define TSDF_OBJECT_NONE 0xFFFFFFFFu
+typedef struct tsdf_objects_info {
+    uint32_t size[3];
+    uint32_t connectivity;
+    float voxel_size[3];
+    float offset[3];         /* the volume's current offset at the last tsdf_volume_find_objects */
+    uint32_t min_votes, min_size;   /* as given */
+    uint64_t n_labelled, n_objects, n_listed_objects;
+} tsdf_objects_info;         /* 72 bytes, n_labelled at 48 */
+typedef struct tsdf_class_object {
+    uint32_t label, size;
+    uint32_t lo[3], hi[3];
+    uint64_t sum[3];
+    uint64_t votes;
+    uint32_t class_id, reserved;
+} tsdf_class_object;         /* 72 bytes, sum at 32, votes at 56, class_id at 64 */
+int tsdf_objects_create(tsdf_objects **out);   /* on the current device */
+void tsdf_objects_destroy(tsdf_objects *objects);
+int tsdf_volume_find_objects(const tsdf_volume *volume, uint32_t min_votes, const uint8_t *host_select /* or NULL: every class */,
+                             uint32_t n_select, uint32_t connectivity, uint32_t min_size, uint32_t flags /* none defined: 0 */,
+                             tsdf_objects *objects);
+int tsdf_objects_get_info(const tsdf_objects *objects, tsdf_objects_info *info);
+int tsdf_objects_buffers(const tsdf_objects *objects, const uint32_t **device_voxels, const uint64_t **device_masks,
+                         const uint32_t **device_bases, const uint32_t **device_labels, const tsdf_class_object **device_rows);
+int tsdf_objects_download(const tsdf_objects *objects, uint32_t *host_voxels, uint32_t *host_labels, tsdf_class_object *host_rows);
+/* n points (3 floats each) -> the table row of the object each lies in, or TSDF_OBJECT_NONE. */
+int tsdf_objects_lookup_device(const tsdf_objects *objects, uint64_t n, const float *device_points, uint32_t *device_rows,
+                               void *hip_stream);
+int tsdf_objects_lookup(const tsdf_objects *objects, uint64_t n, const float *host_points, uint32_t *host_rows);
+/* Device bytes the handle holds besides the list, the labels and the table. */
+int tsdf_objects_scratch_bytes(const tsdf_objects *objects, uint64_t *bytes);
 
 /* ---- sparse snapshot (no reference counterpart: the reference saves a volume densely, and cannot load one) ------------------------ */
 /* The state of a whole volume as the bricks that hold anything but what clear() leaves: taken out of the dense arrays on the device,

@@ -5,4 +5,5 @@ from .api import (TSDFVolume, GPURaycaster, BilateralFilter, Camera, ICPOdometry
                   merge_hits_device, merge_hits_normals_device, HIT_RECORD_BYTES, vertices_to_depth_device, marching_cubes, marching_cubes_table, load_block_tsdf, load_tum_directory,
                   FieldAligner, depth_to_points, depth_to_points_device, Mesh, ESDF, Explorer, pixel_rays, Snapshot, label_components, label_components_device, simplify_mesh,
                   simplify_mesh_device, smooth_mesh, smooth_mesh_device, vertex_normals, rgb_to_intensity, rgb_to_intensity_device,
-                  depth_weights, depth_weights_device, WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE, CLASS_VOID)
+                  depth_weights, depth_weights_device, WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE, CLASS_VOID, Objects, OBJECT_DTYPE,
+                  OBJECT_NONE)

@@ -19,6 +19,7 @@ TSDF_CLASS_VOID = 0xFFFF
 TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
 TSDF_GAIN_KEEP_MASK = 1
+TSDF_OBJECT_NONE = 0xFFFFFFFF
 TSDF_SCENE_FLOW_DEFORMED = 1
 TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
 TSDF_WEIGHTS_INVERSE_SQUARE, TSDF_WEIGHTS_COSINE = 1, 2
@@ -71,6 +72,19 @@ class ExplorerInfo(C.Structure):
 class FrontierCluster(C.Structure):
     """struct tsdf_frontier_cluster (include/tsdf_amd.h): 56 bytes, sum at offset 32."""
     _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("sum", C.c_uint64 * 3)]
+
+
+class ObjectsInfo(C.Structure):
+    """struct tsdf_objects_info (include/tsdf_amd.h): 72 bytes, n_labelled at offset 48."""
+    _fields_ = [("size", C.c_uint32 * 3), ("connectivity", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
+                ("min_votes", C.c_uint32), ("min_size", C.c_uint32), ("n_labelled", C.c_uint64), ("n_objects", C.c_uint64),
+                ("n_listed_objects", C.c_uint64)]
+
+
+class ClassObject(C.Structure):
+    """struct tsdf_class_object (include/tsdf_amd.h): 72 bytes, sum at offset 32, votes at 56, class_id at 64."""
+    _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("sum", C.c_uint64 * 3),
+                ("votes", C.c_uint64), ("class_id", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class SnapshotInfo(C.Structure):
@@ -287,6 +301,15 @@ _SIGS = {
     "tsdf_explorer_cluster_download": (_i, [_vp, _vp, _vp]),
     "tsdf_volume_view_gain_device": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_view_gain": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "tsdf_objects_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_objects_destroy": (None, [_vp]),
+    "tsdf_volume_find_objects": (_i, [_vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp]),
+    "tsdf_objects_get_info": (_i, [_vp, C.POINTER(ObjectsInfo)]),
+    "tsdf_objects_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_objects_download": (_i, [_vp, _vp, _vp, _vp]),
+    "tsdf_objects_lookup_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    "tsdf_objects_lookup": (_i, [_vp, C.c_uint64, _vp, _vp]),
+    "tsdf_objects_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "tsdf_snapshot_create": (_i, [C.POINTER(_vp)]),
     "tsdf_snapshot_destroy": (None, [_vp]),
     "tsdf_volume_snapshot": (_i, [_vp, _u32, _vp]),

@@ -647,6 +647,25 @@ class TSDFVolume:
                 explorer.close()
         return int(g.value), u[:n], f[:n], s[:n]
 
+    # ---- class objects (include/tsdf_amd.h, "class objects"; not in the reference's class)
+    def find_objects(self, min_votes=1, classes=None, connectivity=26, min_size=1, into=None):
+        """The connected pieces of each fused class (tsdf_volume_find_objects): the voxels whose word has at least max(min_votes, 1)
+        votes and a class in `classes` (an iterable of admitted ids; None: every class) are listed, neighbours at `connectivity` (6 or
+        26) of the SAME class are joined, and the table lists the objects of at least min_size voxels.  Everything stays on the
+        device.  `into`: an Objects to reuse -- its arrays are kept and only grow.  Returns the Objects."""
+        select, n_select = None, 0
+        if classes is not None:
+            ids = sorted({int(c) for c in classes})
+            if ids and not 0 <= ids[0] <= ids[-1] <= 65534:
+                raise ValueError("find_objects: class ids are 0..65534, got %d .. %d" % (ids[0], ids[-1]))
+            select = np.zeros(ids[-1] + 1 if ids else 1, np.uint8)   # (an empty selection admits nothing: one zero byte)
+            select[ids] = 1
+            n_select = len(select)
+        objects = Objects() if into is None else into
+        check(lib.tsdf_volume_find_objects(self._h, int(min_votes), select.ctypes.data if select is not None else None, n_select,
+                                           int(connectivity), int(min_size), 0, objects._h))
+        return objects
+
     # ---- sparse snapshots (include/tsdf_amd.h, "sparse snapshot"; not in the reference's class)
     def _file_header(self):
         """The fields of the .tsdf header as the volume reports them now."""
@@ -1457,6 +1476,111 @@ class Explorer:
         """Device bytes the handle holds besides the list, the labels and the table."""
         n = C.c_uint64(0)
         check(lib.tsdf_explorer_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+
+#: one row of Objects.objects: struct tsdf_class_object (72 bytes)
+OBJECT_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.uint32, 3), ("hi", np.uint32, 3), ("sum", np.uint64, 3),
+                         ("votes", np.uint64), ("class_id", np.uint32), ("reserved", np.uint32)])
+#: what Objects.lookup gives for a point in no listed object
+OBJECT_NONE = _capi.TSDF_OBJECT_NONE
+
+
+class Objects:
+    """tsdf_objects (include/tsdf_amd.h, "class objects"): the labelled voxels of a volume, the connected pieces of each class among
+    them and their table (TSDFVolume.find_objects(into=objects)), on the device, with the geometry they belong to; lookup() resolves
+    world points to table rows.  Nothing here needs the volume."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        check(lib.tsdf_objects_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            lib.tsdf_objects_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def info(self):
+        """tsdf_objects_info: size, connectivity, voxel_size, offset, min_votes, min_size, n_labelled, n_objects, n_listed_objects."""
+        i = _capi.ObjectsInfo()
+        check(lib.tsdf_objects_get_info(self._h, C.byref(i)))
+        return i
+
+    def _download(self, voxels=False, labels=False, rows=False):
+        # (one element more than asked for: the pointer of an empty array may be null, which the C ABI reads as "not asked for")
+        i = self.info
+        v = np.empty(int(i.n_labelled) + 1, np.uint32) if voxels else None
+        l = np.empty(int(i.n_labelled) + 1, np.uint32) if labels else None
+        r = np.zeros(int(i.n_listed_objects) + 1, OBJECT_DTYPE) if rows else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        check(lib.tsdf_objects_download(self._h, ptr(v), ptr(l), ptr(r)))
+        return tuple(a[:-1] if a is not None else None for a in (v, l, r))
+
+    @property
+    def voxels(self):
+        """(n_labelled,) uint32: the ids (z * Y + y) * X + x of the labelled voxels, ascending; a blocking download."""
+        return self._download(voxels=True)[0]
+
+    @property
+    def coordinates(self):
+        """(n_labelled, 3) uint32: (x, y, z) of the labelled voxels."""
+        sx, sy, _ = (int(v) for v in self.info.size)
+        ids = self.voxels.astype(np.uint64)
+        return np.stack([ids % sx, (ids // sx) % sy, ids // (sx * sy)], axis=1).astype(np.uint32)
+
+    @property
+    def labels(self):
+        """(n_labelled,) uint32: per listed voxel the smallest list index of its object."""
+        return self._download(labels=True)[1]
+
+    @property
+    def objects(self):
+        """(n_listed_objects,) OBJECT_DTYPE rows in ascending label: label, size, lo / hi (the inclusive voxel box), sum (the integer
+        coordinate sums), votes (the sum of the members' votes), class_id."""
+        return self._download(rows=True)[2]
+
+    @property
+    def centroids(self):
+        """(n_listed_objects, 3) float64: the world centroid (mm) of every listed object, offset + (sum / size + 0.5) * voxel_size."""
+        i, rows = self.info, self.objects
+        vs, off = np.array(i.voxel_size, np.float64), np.array(i.offset, np.float64)
+        return (rows["sum"].astype(np.float64) / np.maximum(rows["size"], 1)[:, None] + 0.5) * vs + off
+
+    @property
+    def boxes(self):
+        """(n_listed_objects, 6) uint32: (x0, y0, z0, x1, y1, z1) per listed object, lower corner inclusive and upper exclusive -- the
+        box argument of TSDFVolume.extract_mesh."""
+        rows = self.objects
+        return np.concatenate([rows["lo"], rows["hi"] + np.uint32(1)], axis=1).astype(np.uint32)
+
+    def lookup_device(self, n, points_ptr, rows_ptr, stream=0):
+        """n points (3 float32 each, device) -> n uint32 table rows (device), OBJECT_NONE where the point lies in no listed object;
+        asynchronous on `stream`, behind the handle's pending work."""
+        check(lib.tsdf_objects_lookup_device(self._h, int(n), C.c_void_p(int(points_ptr)) if points_ptr else None,
+                                             C.c_void_p(int(rows_ptr)) if rows_ptr else None, C.c_void_p(int(stream) if stream else 0)))
+
+    def lookup(self, points):
+        """(n, 3) float32 world points (mm, the frame of TSDFVolume.sample_classes) -> (n,) uint32: the row in `objects` of the object
+        whose voxel each point lies in, OBJECT_NONE for NaN, off-grid and unlisted voxels and objects below min_size.  Blocking."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.empty(len(p) + 1, np.uint32)
+        check(lib.tsdf_objects_lookup(self._h, len(p), p.ctypes.data if len(p) else None, out.ctypes.data))
+        return out[:-1]
+
+    def device_buffers(self):
+        """Raw device pointers {voxels, masks, bases, labels, objects} (0 where empty); valid until the next call that fills them."""
+        p = [C.c_void_p() for _ in range(5)]
+        check(lib.tsdf_objects_buffers(self._h, *[C.byref(q) for q in p]))
+        return {k: int(q.value or 0) for k, q in zip(("voxels", "masks", "bases", "labels", "objects"), p)}
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides the list, the labels and the table."""
+        n = C.c_uint64(0)
+        check(lib.tsdf_objects_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
 
 

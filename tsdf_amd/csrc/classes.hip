@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "class_voxel.hpp"
 #include "common.hpp"
 #include "integrate_grid.hpp"
 
@@ -100,19 +101,15 @@ __global__ __launch_bounds__(256) void class_integrate_kernel(uint32_t *__restri
 }
 
 // One thread per point: the voxel colour_sample_kernel reads -- i = (int)floorf(((p - offset) - offset_at_clear) / voxel_size) per
-// axis; (VOID, 0) for NaN, off-grid or unclassified (votes = 0) voxels.  votes may be null.
+// axis (class_voxel.hpp, shared with objects.hip's lookup); (VOID, 0) for NaN, off-grid or unclassified (votes = 0) voxels.  votes
+// may be null.
 __global__ __launch_bounds__(256) void class_sample_kernel(const uint32_t *__restrict__ cls, const Geom g, const uint64_t n_points,
                                                            const float *__restrict__ points, uint16_t *__restrict__ classes,
                                                            uint16_t *__restrict__ votes) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n_points) return;
-    const float fx = floorf(((points[3 * i + 0] - g.offset.x) - g.offset_clear.x) / g.vs.x);
-    const float fy = floorf(((points[3 * i + 1] - g.offset.y) - g.offset_clear.y) / g.vs.y);
-    const float fz = floorf(((points[3 * i + 2] - g.offset.z) - g.offset_clear.z) / g.vs.z);
-    uint32_t w = 0;
-    // (false for NaN; the grid's sides are below 2^16, so the bounds are exact floats)
-    if (fx >= 0.0f && fx < (float)g.X && fy >= 0.0f && fy < (float)g.Y && fz >= (float)g.z_store_begin && fz < (float)g.z_store_end)
-        w = cls[((size_t)((uint32_t)fz - g.z_store_begin) * g.Y + (uint32_t)fy) * g.X + (uint32_t)fx];
+    size_t at;
+    const uint32_t w = class_voxel_at(g, points + 3 * i, at) ? cls[at] : 0u;
     const uint32_t n = w >> 16;
     classes[i] = (uint16_t)(n ? (w & 0xFFFFu) : kClassVoid);
     if (votes) votes[i] = (uint16_t)n;

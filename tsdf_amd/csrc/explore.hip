@@ -27,25 +27,13 @@
 #include "mesh_device.hpp"
 #include "mesh_handle.hpp"
 #include "union_find.hpp"
+#include "voxel_grid.hpp"
 
 namespace tsdf {
 
 enum { kWordUnknown = 0, kWordFree = 1, kWordOccupied = 2, kWordFrontiers = 3, kWordClusters = 4, kWordGain = 5, kWordTotal = 6, kExploreWords = 8 };
 
 constexpr uint64_t kGainMaxRays = (uint64_t)0x7fffffff * 256;   // what a launch of 256-lane workgroups holds
-
-struct VoxelGrid {
-    uint32_t X, Y, Z, n;   // n = X * Y * Z <= 2^32 - 1
-    __device__ void split(uint32_t id, uint32_t &x, uint32_t &y, uint32_t &z) const {
-        const uint32_t xy = X * Y;
-        z = id / xy;
-        const uint32_t ip = id - z * xy;
-        y = ip / X;
-        x = ip - y * X;
-    }
-};
-
-__device__ inline bool mask_bit(const uint64_t *__restrict__ mask, uint32_t id) { return (mask[id >> 6] >> (id & 63u)) & 1u; }
 
 // A wave walks kFlagChunks consecutive chunks and adds its counts up in registers, the four waves of a workgroup add theirs up in LDS
 // (integer atomics), and the four counters see one atomic per workgroup and 16 384 voxels.  With one per chunk, two million waves queue
@@ -349,8 +337,6 @@ int clusters_ready(const char *who, const tsdf_explorer *s) {
     TSDF_REQUIRE(s->found && s->clustered, "%s: the handle has not been clustered since its last tsdf_volume_find_frontiers (tsdf_explorer_cluster_frontiers)", who);
     return explorer_wait(s);
 }
-
-VoxelGrid voxel_grid(const Geom &g) { return {g.X, g.Y, g.Z, (uint32_t)((uint64_t)g.X * g.Y * g.Z)}; }
 
 int gain_checked(const char *who, const tsdf_volume *v, const tsdf_explorer *s, uint64_t n, const float *origins, const float *directions,
                  uint32_t flags, const void *unknown, const void *free_out, const void *stop, const void *gain) {

@@ -23,6 +23,8 @@ struct tsdf_mesh;    // indexed-mesh handle (include/tsdf_amd.h)
 struct tsdf_snapshot;  // sparse-snapshot handle (include/tsdf_amd.h)
 struct tsdf_explorer;  // exploration handle (include/tsdf_amd.h)
 struct tsdf_frontier_cluster;  // a row of its cluster table (include/tsdf_amd.h)
+struct tsdf_objects;       // class-objects handle (include/tsdf_amd.h)
+struct tsdf_class_object;  // a row of its table (include/tsdf_amd.h)
 
 class TSDFVolume {
 public:
@@ -257,6 +259,37 @@ public:
     uint64_t view_gain(Explorer &explorer, const std::vector<float3> &origins, const std::vector<float3> &directions,
                        const std::vector<float> *t_max = nullptr, bool keep = false, std::vector<uint32_t> *unknown = nullptr,
                        std::vector<uint32_t> *free_voxels = nullptr, std::vector<uint8_t> *stop = nullptr) const;
+
+    // Class objects (include/tsdf_amd.h, "class objects"; not in the reference's class): the connected pieces of each fused class and
+    // their table, in a handle that keeps its device arrays between calls.
+    class Objects {
+    public:
+        Objects();    // throws std::invalid_argument / exits like every device failure when the handle cannot be made
+        ~Objects();
+        Objects(const Objects &) = delete;
+        Objects &operator=(const Objects &) = delete;
+        inline tsdf_objects *handle() const { return m_handle; }
+        // the labelled voxels and the objects (of any size) of the last find_objects
+        uint64_t n_labelled() const;
+        uint64_t n_objects() const;
+        // the ids (z * Y + y) * X + x of the labelled voxels, ascending / per listed voxel the smallest list index of its object / the
+        // table's rows in ascending label (tsdf_class_object, include/tsdf_amd.h); blocking downloads
+        std::vector<uint32_t> voxels() const;
+        std::vector<uint32_t> labels() const;
+        std::vector<tsdf_class_object> objects() const;
+        // per point (world mm, the frame of sample_classes) the row in objects() of the object whose voxel it lies in, or
+        // TSDF_OBJECT_NONE; blocking.  Throws std::invalid_argument before any find_objects.
+        std::vector<uint32_t> lookup(const std::vector<float3> &points) const;
+
+    private:
+        tsdf_objects *m_handle;
+    };
+    // The objects of this volume into `into` (nothing of the volume is written): voxels with at least max(min_votes, 1) votes and, when
+    // `select` is given, select[class] != 0 (classes beyond its end are left out); neighbours at `connectivity` (6 or 26) of the same
+    // class are joined; the table lists the objects of at least min_size voxels.  Throws std::invalid_argument on the refusals
+    // (classes not enabled, another connectivity, more than 65535 selection bytes).
+    void find_objects(Objects &into, uint32_t min_votes = 1, const std::vector<uint8_t> *select = nullptr, uint32_t connectivity = 26,
+                      uint32_t min_size = 1) const;
 
     // Scene flow (include/tsdf_amd.h, "scene flow"; the device part of the reference's process_frames, SceneFusion_krnl.hpp): the
     // vertices of `mesh` -- a handle holding tsdf_volume_extract_mesh of this volume's whole grid -- that the depth frame sees take the

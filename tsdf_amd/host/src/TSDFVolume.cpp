@@ -260,6 +260,63 @@ uint64_t TSDFVolume::view_gain(Explorer &explorer, const std::vector<float3> &or
     return gain;
 }
 
+TSDFVolume::Objects::Objects() : m_handle{nullptr} { check(tsdf_objects_create(&m_handle), "Couldn't create the objects handle"); }
+
+TSDFVolume::Objects::~Objects() { tsdf_objects_destroy(m_handle); }
+
+namespace {
+
+tsdf_objects_info objects_info(const tsdf_objects *o) {
+    tsdf_objects_info info;
+    check(tsdf_objects_get_info(o, &info), "Couldn't query the objects");
+    return info;
+}
+
+}  // namespace
+
+uint64_t TSDFVolume::Objects::n_labelled() const { return objects_info(m_handle).n_labelled; }
+uint64_t TSDFVolume::Objects::n_objects() const { return objects_info(m_handle).n_objects; }
+
+std::vector<uint32_t> TSDFVolume::Objects::voxels() const {
+    // (one element more than needed: data() of an empty vector may be null, which the C ABI reads as "not asked for")
+    std::vector<uint32_t> ids((size_t)objects_info(m_handle).n_labelled + 1, 0u);
+    check(tsdf_objects_download(m_handle, ids.data(), nullptr, nullptr), "Couldn't download the labelled voxels");
+    ids.pop_back();
+    return ids;
+}
+
+std::vector<uint32_t> TSDFVolume::Objects::labels() const {
+    std::vector<uint32_t> labels((size_t)objects_info(m_handle).n_labelled + 1, 0u);
+    check(tsdf_objects_download(m_handle, nullptr, labels.data(), nullptr), "Couldn't download the object labels");
+    labels.pop_back();
+    return labels;
+}
+
+std::vector<tsdf_class_object> TSDFVolume::Objects::objects() const {
+    std::vector<tsdf_class_object> rows((size_t)objects_info(m_handle).n_listed_objects + 1, tsdf_class_object());
+    check(tsdf_objects_download(m_handle, nullptr, nullptr, rows.data()), "Couldn't download the objects");
+    rows.pop_back();
+    return rows;
+}
+
+std::vector<uint32_t> TSDFVolume::Objects::lookup(const std::vector<float3> &points) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    const size_t n = points.size();
+    std::vector<uint32_t> rows(n + 1, TSDF_OBJECT_NONE);
+    check(tsdf_objects_lookup(m_handle, n, n ? reinterpret_cast<const float *>(points.data()) : nullptr, rows.data()), "Couldn't look the points up");
+    rows.pop_back();
+    return rows;
+}
+
+void TSDFVolume::find_objects(Objects &into, uint32_t min_votes, const std::vector<uint8_t> *select, uint32_t connectivity, uint32_t min_size) const {
+    // (an empty selection admits nothing: one zero byte, so that the pointer is not null)
+    static const uint8_t none = 0;
+    const uint8_t *bytes = !select ? nullptr : select->empty() ? &none : select->data();
+    const size_t n_select = !select ? 0 : select->empty() ? 1 : select->size();
+    if (n_select > 65535) throw std::invalid_argument("find_objects: more than 65535 selection bytes");
+    check(tsdf_volume_find_objects(m_handle, min_votes, bytes, (uint32_t)n_select, connectivity, min_size, 0u, into.handle()), "Couldn't find the objects");
+}
+
 void TSDFVolume::cast_rays(const std::vector<float3> &origins, const std::vector<float3> &directions, std::vector<float3> &points,
                            std::vector<float> *t, std::vector<float3> *normals, const std::vector<float> *t_max) const {
     static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
