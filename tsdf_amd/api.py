@@ -1382,6 +1382,19 @@ class ESDF:
 CLUSTER_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.uint32, 3), ("hi", np.uint32, 3), ("sum", np.uint64, 3)])
 
 
+def _voxel_coordinates(ids, size):
+    """(n,) voxel ids (z * Y + y) * X + x of a grid of `size` -> (n, 3) uint32 (x, y, z)."""
+    sx, sy, _ = (int(v) for v in size)
+    ids = ids.astype(np.uint64)
+    return np.stack([ids % sx, (ids // sx) % sy, ids // (sx * sy)], axis=1).astype(np.uint32)
+
+
+def _row_centroids(rows, info):
+    """Table rows with `sum` and `size`, and the info with their geometry -> (n, 3) float64 world centroids (mm)."""
+    vs, off = np.array(info.voxel_size, np.float64), np.array(info.offset, np.float64)
+    return (rows["sum"].astype(np.float64) / np.maximum(rows["size"], 1)[:, None] + 0.5) * vs + off
+
+
 class Explorer:
     """tsdf_explorer (include/tsdf_amd.h, "exploration"): the frontier voxels of a volume (TSDFVolume.find_frontiers(into=explorer)),
     their clusters (cluster()) and the mask of unknown voxels that view-gain rays have passed (TSDFVolume.view_gain(explorer=...)), on
@@ -1417,9 +1430,7 @@ class Explorer:
     @property
     def coordinates(self):
         """(n_frontiers, 3) uint32: (x, y, z) of the frontier voxels."""
-        sx, sy, _ = (int(v) for v in self.info.size)
-        ids = self.voxels.astype(np.uint64)
-        return np.stack([ids % sx, (ids // sx) % sy, ids // (sx * sy)], axis=1).astype(np.uint32)
+        return _voxel_coordinates(self.voxels, self.info.size)
 
     @property
     def points(self):
@@ -1455,9 +1466,7 @@ class Explorer:
     @property
     def centroids(self):
         """(n_listed_clusters, 3) float64: the world centroid (mm) of every listed cluster, offset + (sum / size + 0.5) * voxel_size."""
-        i, rows = self.info, self.clusters
-        vs, off = np.array(i.voxel_size, np.float64), np.array(i.offset, np.float64)
-        return (rows["sum"].astype(np.float64) / np.maximum(rows["size"], 1)[:, None] + 0.5) * vs + off
+        return _row_centroids(self.clusters, self.info)
 
     def device_buffers(self):
         """Raw device pointers {voxels, masks, bases, labels, clusters} (0 where empty or not clustered); valid until the next call
@@ -1527,9 +1536,7 @@ class Objects:
     @property
     def coordinates(self):
         """(n_labelled, 3) uint32: (x, y, z) of the labelled voxels."""
-        sx, sy, _ = (int(v) for v in self.info.size)
-        ids = self.voxels.astype(np.uint64)
-        return np.stack([ids % sx, (ids // sx) % sy, ids // (sx * sy)], axis=1).astype(np.uint32)
+        return _voxel_coordinates(self.voxels, self.info.size)
 
     @property
     def labels(self):
@@ -1545,9 +1552,7 @@ class Objects:
     @property
     def centroids(self):
         """(n_listed_objects, 3) float64: the world centroid (mm) of every listed object, offset + (sum / size + 0.5) * voxel_size."""
-        i, rows = self.info, self.objects
-        vs, off = np.array(i.voxel_size, np.float64), np.array(i.offset, np.float64)
-        return (rows["sum"].astype(np.float64) / np.maximum(rows["size"], 1)[:, None] + 0.5) * vs + off
+        return _row_centroids(self.objects, self.info)
 
     @property
     def boxes(self):

@@ -5,15 +5,7 @@
 //   frontier_flag_kernel     the state of every voxel (unknown / free / occupied) and the frontier test; per chunk the ballot mask and
 //                            its popcount; the four counts by ballot and popcount over the 64 chunks a wave walks, one integer atomic
 //                            per workgroup that has any
-//   (the chunk scan of mesh_scan.hip turns the popcounts into bases)
-//   frontier_list_kernel     list[compact_index(mask, base, id)] = id: ascending, no atomics, one writer per word
-// Clusters: the union-find of union_find.hpp over the list indices, a lane per listed voxel.
-//   frontier_init_kernel     parent[i] = i, the accumulator rows emptied
-//   frontier_hook_kernel     the 3 or 13 forward neighbours, looked up through mask + base, united with the lane's own index
-//   frontier_flatten_kernel  L[i] = root(i) (a launch of its own: the kernel boundary makes every hook visible); roots counted
-//   frontier_stats_kernel    size, coordinate sums and the box, to the root's row with integer atomics; one set per wave and root
-//   frontier_keep_kernel     per 64 list indices: the mask of roots with size >= min_size and its popcount (then the chunk scan)
-//   frontier_rows_kernel     the kept rows, in ascending label, to where compact_index says
+// The list and the clusters are voxel_set.hpp's, with the policy "any listed neighbour is adjacent".
 // View gain: a lane per ray.
 //   view_gain_kernel         gain_walk (explore_walk.hpp); an unknown voxel sets its bit in the handle's mask with atomicOr
 //   mask_count_kernel        the set bits, by popcount and a wave sum, one integer atomic per wave that has any
@@ -24,14 +16,13 @@
 #include "common.hpp"
 #include "explore_walk.hpp"
 #include "field_sample.hpp"
-#include "mesh_device.hpp"
-#include "mesh_handle.hpp"
-#include "union_find.hpp"
-#include "voxel_grid.hpp"
+#include "voxel_set.hpp"
 
 namespace tsdf {
 
-enum { kWordUnknown = 0, kWordFree = 1, kWordOccupied = 2, kWordFrontiers = 3, kWordClusters = 4, kWordGain = 5, kWordTotal = 6, kExploreWords = 8 };
+// the handle's counter words: the flag kernel's four, then the set's two (roots, scan total: voxel_set.hpp), then the gain
+enum { kWordUnknown = 0, kWordFree = 1, kWordOccupied = 2, kWordFrontiers = 3, kWordGain = 6 };
+using FrontierSet = VoxelSet<tsdf_frontier_cluster, 4, 8>;
 
 constexpr uint64_t kGainMaxRays = (uint64_t)0x7fffffff * 256;   // what a launch of 256-lane workgroups holds
 
@@ -85,128 +76,6 @@ __global__ __launch_bounds__(256) void frontier_flag_kernel(const float *__restr
     if (threadIdx.x < 4 && totals[threadIdx.x]) atomicAdd(words + threadIdx.x, (unsigned long long)totals[threadIdx.x]);
 }
 
-__global__ __launch_bounds__(256) void frontier_list_kernel(const uint32_t n_chunks, const uint64_t *__restrict__ mask,
-                                                            const uint32_t *__restrict__ base, uint32_t *__restrict__ list) {
-    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (chunk >= n_chunks) return;
-    if (!((mask[chunk] >> lane) & 1u)) return;   // (no bit beyond the grid is ever set)
-    const uint32_t id = chunk * 64 + lane;
-    list[compact_index(mask, base, id)] = id;
-}
-
-// what a root's row holds before the first voxel reaches it
-__device__ inline void empty_row(tsdf_frontier_cluster &r, uint32_t label) {
-    r.label = label;
-    r.size = 0;
-    for (int k = 0; k < 3; k++) {
-        r.lo[k] = 0xffffffffu;
-        r.hi[k] = 0;
-        r.sum[k] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void frontier_init_kernel(const uint32_t n_list, uint32_t *__restrict__ parent, tsdf_frontier_cluster *__restrict__ acc) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_list) return;
-    parent[i] = (uint32_t)i;
-    empty_row(acc[i], (uint32_t)i);
-}
-
-// A lane per listed voxel: its forward neighbours -- the offsets (dx, dy, dz) that come after (0, 0, 0) in the order z, then y, then x,
-// 3 of them at connectivity 6 and 13 at 26 -- that lie inside the grid and are listed are united with it.  Every pair of neighbours is
-// forward from one of its two ends, so all of them are seen.  Bounded: 13 trips, and the bounds of components_unite.
-__global__ __launch_bounds__(256) void frontier_hook_kernel(const uint32_t n_list, const uint32_t *__restrict__ list, const uint64_t *__restrict__ mask,
-                                                            const uint32_t *__restrict__ base, const VoxelGrid grid, const uint32_t connectivity,
-                                                            uint32_t *parent) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_list) return;
-    const uint32_t id = list[i];
-    uint32_t x, y, z;
-    grid.split(id, x, y, z);
-    for (int k = 14; k < 27; k++) {   // k = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); 13 is the voxel itself
-        const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
-        if (connectivity == 6u && abs(dx) + abs(dy) + abs(dz) != 1) continue;
-        const int64_t nx = (int64_t)x + dx, ny = (int64_t)y + dy, nz = (int64_t)z + dz;
-        if (nx < 0 || nx >= (int64_t)grid.X || ny < 0 || ny >= (int64_t)grid.Y || nz >= (int64_t)grid.Z) continue;   // (nz >= 0: dz >= 0)
-        const uint32_t id2 = (uint32_t)((nz * grid.Y + ny) * grid.X + nx);
-        if (mask_bit(mask, id2)) components_unite(parent, (uint32_t)i, compact_index(mask, base, id2));
-    }
-}
-
-__global__ __launch_bounds__(256) void frontier_flatten_kernel(const uint32_t n_list, uint32_t *labels, unsigned long long *__restrict__ words) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    bool is_root = false;
-    if (i < n_list) {
-        const uint32_t root = components_find<false>(labels, (uint32_t)i);
-        is_root = root == (uint32_t)i;
-        // (another lane may be walking through i: it reads the old ancestor or the root, both on its way)
-        if (!is_root) __hip_atomic_store(labels + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const uint64_t roots = __ballot(is_root);
-    if (roots && (threadIdx.x & 63u) == 0) atomicAdd(words + kWordClusters, (unsigned long long)__popcll(roots));
-}
-
-__device__ inline void row_add(tsdf_frontier_cluster *row, uint32_t count, const uint32_t lo[3], const uint32_t hi[3], const uint32_t sum[3]) {
-    atomicAdd(&row->size, count);
-    for (int k = 0; k < 3; k++) {
-        atomicMin(&row->lo[k], lo[k]);
-        atomicMax(&row->hi[k], hi[k]);
-        atomicAdd((unsigned long long *)&row->sum[k], (unsigned long long)sum[k]);
-    }
-}
-
-// One set of atomics per wave and root: the wave takes its distinct roots in turn, the lanes of a root reduce among themselves (the
-// others hold the neutral values) and the root's first lane adds the result.  Neighbours in the list are neighbours in the grid, so
-// most waves have one root or two; adding lane by lane wherever a wave is mixed queued thousands of atomics on the rows of the large
-// clusters (5 ms at half a million frontiers).  Bounded: at most 64 trips, every trip retires its leading lane.  (A wave's coordinate
-// sum is at most 64 * 65535: it fits 32 bits.)
-__global__ __launch_bounds__(256) void frontier_stats_kernel(const uint32_t n_list, const uint32_t *__restrict__ list, const uint32_t *__restrict__ labels,
-                                                             const VoxelGrid grid, tsdf_frontier_cluster *__restrict__ acc) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n_list;
-    const uint32_t label = valid ? labels[i] : 0xffffffffu;
-    uint32_t c[3] = {0, 0, 0};
-    if (valid) grid.split(list[i], c[0], c[1], c[2]);
-    uint64_t remaining = __ballot(valid);
-    for (int trip = 0; trip < 64 && remaining; trip++) {
-        const int first = __ffsll((unsigned long long)remaining) - 1;
-        const uint32_t lead = __shfl(label, first);
-        const bool mine = valid && label == lead;
-        const uint64_t same = __ballot(mine);
-        uint32_t lo[3], hi[3], sum[3];
-        for (int k = 0; k < 3; k++) {
-            lo[k] = mine ? c[k] : 0xffffffffu;
-            hi[k] = mine ? c[k] : 0u;
-            sum[k] = mine ? c[k] : 0u;
-            for (int o = 32; o > 0; o >>= 1) {
-                lo[k] = min(lo[k], (uint32_t)__shfl_xor(lo[k], o));
-                hi[k] = max(hi[k], (uint32_t)__shfl_xor(hi[k], o));
-                sum[k] += (uint32_t)__shfl_xor(sum[k], o);
-            }
-        }
-        if ((int)(threadIdx.x & 63u) == first) row_add(acc + lead, (uint32_t)__popcll(same), lo, hi, sum);
-        remaining &= ~same;
-    }
-}
-
-__global__ __launch_bounds__(256) void frontier_keep_kernel(const uint32_t n_list, const uint32_t *__restrict__ labels,
-                                                            const tsdf_frontier_cluster *__restrict__ acc, const uint32_t min_size, const uint32_t n_chunks,
-                                                            uint64_t *__restrict__ row_mask, uint32_t *__restrict__ row_base) {
-    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (chunk >= n_chunks) return;
-    const uint64_t i = (uint64_t)chunk * 64 + lane;
-    store_keep_mask(i < n_list && labels[i] == (uint32_t)i && acc[i].size >= min_size, lane, chunk, row_mask, row_base);
-}
-
-__global__ __launch_bounds__(256) void frontier_rows_kernel(const uint32_t n_chunks, const uint64_t *__restrict__ row_mask, const uint32_t *__restrict__ row_base,
-                                                            const tsdf_frontier_cluster *__restrict__ acc, tsdf_frontier_cluster *__restrict__ rows) {
-    const uint32_t lane = threadIdx.x & 63u, chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (chunk >= n_chunks) return;
-    if (!((row_mask[chunk] >> lane) & 1u)) return;
-    const uint32_t i = chunk * 64 + lane;
-    rows[compact_index(row_mask, row_base, i)] = acc[i];
-}
-
 struct GainView {
     const float *dist;
     WeightView wv;
@@ -248,60 +117,27 @@ __global__ __launch_bounds__(256) void mask_count_kernel(const uint32_t n_words,
 
 using namespace tsdf;
 
-struct tsdf_explorer {
-    int device;
-    hipEvent_t done;        // recorded behind the last call's launches
-    int pending;            // ... and not waited for yet
-    int has_geometry;       // a find_frontiers or a view gain has given the handle a geometry
+struct tsdf_explorer : FrontierSet {
+    int has_geometry;       // a find_frontiers or a view gain has given the handle a geometry (g)
     int found;              // the list, masks and bases are a find_frontiers' of that geometry
     int clustered;          // labels and rows are of that list
     int mask_ready;         // the gain mask is allocated for that geometry and holds only bits that view-gain calls have set
-    Geom g;
-    uint64_t *masks;        // one frontier mask per 64 voxel ids
-    uint32_t *bases;        // ... and the list index of the chunk's first frontier
-    uint64_t *parts;        // the chunk scan's sums
-    uint32_t *list;         // the frontier voxel ids, ascending
-    uint32_t *labels;       // L, one per listed voxel
-    tsdf_frontier_cluster *acc;    // one accumulator row per listed voxel; the roots' are filled
-    uint64_t *row_masks;    // one keep mask per 64 list indices
-    uint32_t *row_bases;
-    tsdf_frontier_cluster *rows;   // the table
     uint32_t *gain_mask;    // one bit per voxel
-    size_t masks_cap, bases_cap, parts_cap, list_cap, labels_cap, acc_cap, row_masks_cap, row_bases_cap, rows_cap, gain_mask_cap;
-    unsigned long long *words;        // kExploreWords device words
-    unsigned long long *host_words;   // pinned: where they land
+    size_t gain_mask_cap;
     tsdf_explorer_info info;
 };
 
 namespace {
 
+constexpr VoxelSetText kExplorerText = {
+    "explorer stream order", "explorer event", "explorer wait",
+    "frontier scratch alloc failed", "frontier counts reset", "frontier count kernels failed", "frontier counts download", "frontier count", "frontier list alloc failed",
+    "frontier cluster alloc failed", "frontier cluster kernels failed", "frontier cluster counts download", "frontier cluster count", "frontier cluster table alloc failed", "frontier rows kernel failed"};
+
 void explorer_free(tsdf_explorer *s) {
-    if (s->done) (void)hipEventSynchronize(s->done);
-    device_free_all(s->masks, s->bases, s->parts, s->list, s->labels, s->acc, s->row_masks, s->row_bases, s->rows, s->gain_mask, s->words);
-    (void)hipHostFree(s->host_words);
-    if (s->done) (void)hipEventDestroy(s->done);
+    s->release();
+    (void)hipFree(s->gain_mask);
     delete s;
-}
-
-// the stream waits for what is in flight on the handle / what has just been enqueued is in flight on it / the host waits for it
-int explorer_join(tsdf_explorer *s, hipStream_t stream) {
-    if (s->pending) TSDF_HIP(hipStreamWaitEvent(stream, s->done, 0), "explorer stream order");
-    return TSDF_OK;
-}
-
-int explorer_leave(tsdf_explorer *s, hipStream_t stream) {
-    TSDF_HIP(hipEventRecord(s->done, stream), "explorer event");
-    s->pending = 1;
-    return TSDF_OK;
-}
-
-int explorer_wait(const tsdf_explorer *cs) {
-    tsdf_explorer *s = const_cast<tsdf_explorer *>(cs);
-    if (s->pending) {
-        TSDF_HIP(hipEventSynchronize(s->done), "explorer wait");
-        s->pending = 0;
-    }
-    return TSDF_OK;
 }
 
 bool same_geometry(const Geom &a, const Geom &b) {
@@ -313,9 +149,7 @@ void adopt_geometry(tsdf_explorer *s, const Geom &g) {
     if (!s->has_geometry || s->g.X != g.X || s->g.Y != g.Y || s->g.Z != g.Z) s->mask_ready = 0;   // the bits are voxel ids of another grid
     s->g = g;
     s->has_geometry = 1;
-    s->info.size[0] = g.X; s->info.size[1] = g.Y; s->info.size[2] = g.Z;
-    s->info.voxel_size[0] = g.vs.x; s->info.voxel_size[1] = g.vs.y; s->info.voxel_size[2] = g.vs.z;
-    s->info.offset[0] = g.offset.x; s->info.offset[1] = g.offset.y; s->info.offset[2] = g.offset.z;
+    geometry_into(s->info, g);
 }
 
 // what every entry point that reads a volume refuses, under its own name
@@ -335,7 +169,7 @@ int volume_checked(const char *who, const tsdf_volume *v, const tsdf_explorer *s
 int clusters_ready(const char *who, const tsdf_explorer *s) {
     TSDF_REQUIRE(s, "%s: null handle", who);
     TSDF_REQUIRE(s->found && s->clustered, "%s: the handle has not been clustered since its last tsdf_volume_find_frontiers (tsdf_explorer_cluster_frontiers)", who);
-    return explorer_wait(s);
+    return s->wait();
 }
 
 int gain_checked(const char *who, const tsdf_volume *v, const tsdf_explorer *s, uint64_t n, const float *origins, const float *directions,
@@ -356,7 +190,7 @@ int gain_checked(const char *who, const tsdf_volume *v, const tsdf_explorer *s, 
 int gain_on(tsdf_volume *v, tsdf_explorer *s, uint64_t n, const float *origins, const float *directions, const float *t_max, uint32_t flags,
             uint32_t *unknown, uint32_t *free_out, uint8_t *stop, uint64_t *host_gain) {
     hipStream_t stream = v->stream;
-    int rc = explorer_join(s, stream);
+    int rc = s->join(stream);
     if (rc != TSDF_OK) return rc;
     adopt_geometry(s, v->g);
     const VoxelGrid grid = voxel_grid(v->g);
@@ -379,7 +213,7 @@ int gain_on(tsdf_volume *v, tsdf_explorer *s, uint64_t n, const float *origins, 
         TSDF_HIP(hipMemcpyAsync(s->host_words + kWordGain, s->words + kWordGain, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "view gain count download");
     }
     TSDF_HIP(hipGetLastError(), "view gain kernels failed");
-    rc = explorer_leave(s, stream);
+    rc = s->leave(stream);
     if (rc != TSDF_OK) return rc;
     if (host_gain) {
         TSDF_HIP(hipStreamSynchronize(stream), "view gain count");
@@ -401,16 +235,11 @@ int tsdf_explorer_create(tsdf_explorer **out) {
         set_error("out of host memory");
         return TSDF_ERR_NOMEM;
     }
-    std::memset(s, 0, sizeof(*s));
-    hipError_t e = hipGetDevice(&s->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->words, kExploreWords * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->host_words, kExploreWords * sizeof(unsigned long long), hipHostMallocDefault);
+    const hipError_t e = s->create(&kExplorerText);
     if (e != hipSuccess) {
         explorer_free(s);
         return hip_fail(e, "explorer alloc failed");
     }
-    std::memset(s->host_words, 0, kExploreWords * sizeof(unsigned long long));
     *out = s;
     return TSDF_OK;
 }
@@ -425,45 +254,28 @@ int tsdf_volume_find_frontiers(const tsdf_volume *cv, uint32_t flags, tsdf_explo
     TSDF_REQUIRE(flags == 0, "tsdf_volume_find_frontiers: unknown flags %#x", flags);
     tsdf_volume *v = const_cast<tsdf_volume *>(cv);
     hipStream_t stream = v->stream;
-    int rc = explorer_join(s, stream);
+    int rc = s->join(stream);
     if (rc != TSDF_OK) return rc;
     s->found = s->clustered = 0;
     const VoxelGrid grid = voxel_grid(v->g);
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)grid.n + 63) / 64), n_parts = mesh_scan_parts(n_chunks);
-    hipError_t e = device_reserve(s->masks, s->masks_cap, (size_t)n_chunks);
-    if (e == hipSuccess) e = device_reserve(s->bases, s->bases_cap, (size_t)n_chunks);
-    if (e == hipSuccess) e = device_reserve(s->parts, s->parts_cap, 2 * ((size_t)n_parts + 1));
-    if (e != hipSuccess) return hip_fail(e, "frontier scratch alloc failed");
-    adopt_geometry(s, v->g);
-    s->info.connectivity = 0;
-    s->info.n_unknown = s->info.n_free = s->info.n_occupied = s->info.n_frontiers = s->info.n_clusters = s->info.n_listed_clusters = 0;
-
-    const WeightView wv = {v->weight, v->wpacked, v->wmode};
-    const dim3 chunk_grid((n_chunks + 3) / 4), flag_grid((n_chunks + 4 * kFlagChunks - 1) / (4 * kFlagChunks));
-    TSDF_HIP(hipMemsetAsync(s->words, 0, kExploreWords * sizeof(unsigned long long), stream), "frontier counts reset");
-    hipLaunchKernelGGL(frontier_flag_kernel, flag_grid, dim3(256), 0, stream, v->dist, wv, grid, n_chunks, s->masks, s->bases, s->words);
-    mesh_scan(ArrayCounts{s->bases, n_chunks, nullptr, 0}, n_parts, s->parts, stream);
-    TSDF_HIP(hipGetLastError(), "frontier count kernels failed");
-    TSDF_HIP(hipMemcpyAsync(s->host_words, s->words, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "frontier counts download");
-    TSDF_HIP(hipMemcpyAsync(s->host_words + kWordTotal, s->parts + 2 * (size_t)n_parts, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "frontier counts download");
-    TSDF_HIP(hipStreamSynchronize(stream), "frontier count");   // the list is sized from the count
-    s->pending = 0;
-    const uint64_t n_list = s->host_words[kWordTotal];
+    uint64_t n_list = 0;
+    rc = voxel_set_list(s, "tsdf_volume_find_frontiers", "frontiers", grid, stream, [&](uint32_t n_chunks) -> int {
+        adopt_geometry(s, v->g);
+        s->info.connectivity = 0;
+        s->info.n_unknown = s->info.n_free = s->info.n_occupied = s->info.n_frontiers = s->info.n_clusters = s->info.n_listed_clusters = 0;
+        const WeightView wv = {v->weight, v->wpacked, v->wmode};
+        const dim3 flag_grid((n_chunks + 4 * kFlagChunks - 1) / (4 * kFlagChunks));
+        hipLaunchKernelGGL(frontier_flag_kernel, flag_grid, dim3(256), 0, stream, v->dist, wv, grid, n_chunks, s->masks, s->bases, s->words);
+        return TSDF_OK;
+    }, &n_list);
+    if (rc != TSDF_OK) return rc;
     s->info.n_unknown = s->host_words[kWordUnknown];
     s->info.n_free = s->host_words[kWordFree];
     s->info.n_occupied = s->host_words[kWordOccupied];
-    s->info.n_frontiers = s->host_words[kWordFrontiers];
-    if (n_list != s->info.n_frontiers) {
-        set_error("tsdf_volume_find_frontiers: the scan's total (%llu) is not the counted frontiers (%llu)", (unsigned long long)n_list,
-                  (unsigned long long)s->info.n_frontiers);
-        return TSDF_ERR_DEVICE;
-    }
+    s->info.n_frontiers = n_list;
     if (n_list) {
-        e = device_reserve(s->list, s->list_cap, (size_t)n_list);
-        if (e != hipSuccess) return hip_fail(e, "frontier list alloc failed");
-        hipLaunchKernelGGL(frontier_list_kernel, chunk_grid, dim3(256), 0, stream, n_chunks, s->masks, s->bases, s->list);
         TSDF_HIP(hipGetLastError(), "frontier list kernel failed");
-        rc = explorer_leave(s, stream);
+        rc = s->leave(stream);
         if (rc != TSDF_OK) return rc;
     }
     s->found = 1;
@@ -479,7 +291,7 @@ int tsdf_explorer_get_info(const tsdf_explorer *s, tsdf_explorer_info *info) {
 int tsdf_explorer_frontier_buffers(const tsdf_explorer *s, const uint32_t **device_voxels, const uint64_t **device_masks, const uint32_t **device_bases) {
     TSDF_REQUIRE(s, "tsdf_explorer_frontier_buffers: null handle");
     TSDF_REQUIRE(s->found, "tsdf_explorer_frontier_buffers: the handle holds no frontiers (tsdf_volume_find_frontiers)");
-    const int rc = explorer_wait(s);
+    const int rc = s->wait();
     if (rc != TSDF_OK) return rc;
     if (device_voxels) *device_voxels = s->info.n_frontiers ? s->list : nullptr;
     if (device_masks) *device_masks = s->masks;
@@ -490,7 +302,7 @@ int tsdf_explorer_frontier_buffers(const tsdf_explorer *s, const uint32_t **devi
 int tsdf_explorer_frontier_download(const tsdf_explorer *s, uint32_t *host_voxels) {
     TSDF_REQUIRE(s && host_voxels, "tsdf_explorer_frontier_download: null argument");
     TSDF_REQUIRE(s->found, "tsdf_explorer_frontier_download: the handle holds no frontiers (tsdf_volume_find_frontiers)");
-    const int rc = explorer_wait(s);
+    const int rc = s->wait();
     if (rc != TSDF_OK) return rc;
     if (s->info.n_frontiers) TSDF_HIP(hipMemcpy(host_voxels, s->list, (size_t)s->info.n_frontiers * sizeof(uint32_t), hipMemcpyDeviceToHost), "frontier download");
     return TSDF_OK;
@@ -498,9 +310,7 @@ int tsdf_explorer_frontier_download(const tsdf_explorer *s, uint32_t *host_voxel
 
 int tsdf_explorer_scratch_bytes(const tsdf_explorer *s, uint64_t *bytes) {
     TSDF_REQUIRE(s && bytes, "tsdf_explorer_scratch_bytes: null argument");
-    *bytes = (uint64_t)s->masks_cap * sizeof(uint64_t) + (uint64_t)s->bases_cap * sizeof(uint32_t) + (uint64_t)s->parts_cap * sizeof(uint64_t) +
-             (uint64_t)s->acc_cap * sizeof(tsdf_frontier_cluster) + (uint64_t)s->row_masks_cap * sizeof(uint64_t) +
-             (uint64_t)s->row_bases_cap * sizeof(uint32_t) + (uint64_t)s->gain_mask_cap * sizeof(uint32_t) + kExploreWords * sizeof(unsigned long long);
+    *bytes = s->scratch_bytes() + (uint64_t)s->gain_mask_cap * sizeof(uint32_t);
     return TSDF_OK;
 }
 
@@ -509,7 +319,7 @@ int tsdf_explorer_cluster_frontiers(tsdf_explorer *s, uint32_t connectivity, uin
     TSDF_REQUIRE(connectivity == 6u || connectivity == 26u, "tsdf_explorer_cluster_frontiers: connectivity must be 6 or 26, got %u", connectivity);
     TSDF_REQUIRE(s->found, "tsdf_explorer_cluster_frontiers: the handle holds no frontiers (tsdf_volume_find_frontiers)");
     hipStream_t stream = (hipStream_t)hip_stream;
-    int rc = explorer_join(s, stream);
+    int rc = s->join(stream);
     if (rc != TSDF_OK) return rc;
     s->clustered = 0;
     s->info.connectivity = connectivity;
@@ -519,37 +329,12 @@ int tsdf_explorer_cluster_frontiers(tsdf_explorer *s, uint32_t connectivity, uin
         s->clustered = 1;
         return TSDF_OK;
     }
-    const uint32_t n_list = (uint32_t)n64, n_chunks = (uint32_t)((n64 + 63) / 64), n_parts = mesh_scan_parts(n_chunks);
-    hipError_t e = device_reserve(s->labels, s->labels_cap, (size_t)n_list);
-    if (e == hipSuccess) e = device_reserve(s->acc, s->acc_cap, (size_t)n_list);
-    if (e == hipSuccess) e = device_reserve(s->row_masks, s->row_masks_cap, (size_t)n_chunks);
-    if (e == hipSuccess) e = device_reserve(s->row_bases, s->row_bases_cap, (size_t)n_chunks);
-    if (e == hipSuccess) e = device_reserve(s->parts, s->parts_cap, 2 * ((size_t)n_parts + 1));
-    if (e != hipSuccess) return hip_fail(e, "frontier cluster alloc failed");
-    const VoxelGrid grid = voxel_grid(s->g);
-    const dim3 lanes = grid_for(n_list, 256), chunk_grid((n_chunks + 3) / 4);
-    TSDF_HIP(hipMemsetAsync(s->words + kWordClusters, 0, sizeof(unsigned long long), stream), "frontier cluster count reset");
-    hipLaunchKernelGGL(frontier_init_kernel, lanes, dim3(256), 0, stream, n_list, s->labels, s->acc);
-    hipLaunchKernelGGL(frontier_hook_kernel, lanes, dim3(256), 0, stream, n_list, s->list, s->masks, s->bases, grid, connectivity, s->labels);
-    hipLaunchKernelGGL(frontier_flatten_kernel, lanes, dim3(256), 0, stream, n_list, s->labels, s->words);
-    hipLaunchKernelGGL(frontier_stats_kernel, lanes, dim3(256), 0, stream, n_list, s->list, s->labels, grid, s->acc);
-    hipLaunchKernelGGL(frontier_keep_kernel, chunk_grid, dim3(256), 0, stream, n_list, s->labels, s->acc, min_size, n_chunks, s->row_masks, s->row_bases);
-    mesh_scan(ArrayCounts{s->row_bases, n_chunks, nullptr, 0}, n_parts, s->parts, stream);
-    TSDF_HIP(hipGetLastError(), "frontier cluster kernels failed");
-    TSDF_HIP(hipMemcpyAsync(s->host_words + kWordClusters, s->words + kWordClusters, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "frontier cluster counts download");
-    TSDF_HIP(hipMemcpyAsync(s->host_words + kWordTotal, s->parts + 2 * (size_t)n_parts, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "frontier cluster counts download");
-    TSDF_HIP(hipStreamSynchronize(stream), "frontier cluster count");   // the table is sized from the count
-    s->pending = 0;
-    const uint64_t n_rows = s->host_words[kWordTotal];
-    if (n_rows) {
-        e = device_reserve(s->rows, s->rows_cap, (size_t)n_rows);
-        if (e != hipSuccess) return hip_fail(e, "frontier cluster table alloc failed");
-        hipLaunchKernelGGL(frontier_rows_kernel, chunk_grid, dim3(256), 0, stream, n_chunks, s->row_masks, s->row_bases, s->acc, s->rows);
-        TSDF_HIP(hipGetLastError(), "frontier rows kernel failed");
-        rc = explorer_leave(s, stream);
-        if (rc != TSDF_OK) return rc;
-    }
-    s->info.n_clusters = s->host_words[kWordClusters];
+    // (a find_frontiers zeroes every word; a second clustering of its list counts the roots again)
+    TSDF_HIP(hipMemsetAsync(s->words + FrontierSet::kWordRoots, 0, sizeof(unsigned long long), stream), "frontier cluster count reset");
+    uint64_t n_roots = 0, n_rows = 0;
+    rc = voxel_set_cluster(s, AnyListedNeighbour{}, (uint32_t)n64, connectivity, min_size, stream, &n_roots, &n_rows);
+    if (rc != TSDF_OK) return rc;
+    s->info.n_clusters = n_roots;
     s->info.n_listed_clusters = n_rows;
     s->clustered = 1;
     return TSDF_OK;

@@ -32,7 +32,7 @@ namespace tsdf {
 
 enum { kWordError = 0, kWordRoots = 1, kWordLargest = 2 };   // tsdf_mesh::component_words
 
-// (parent_load, components_find and components_unite: union_find.hpp, shared with explore.hip)
+// (parent_load, components_find and components_unite: union_find.hpp, shared with voxel_set.hpp)
 
 __global__ __launch_bounds__(256) void components_init_kernel(uint32_t n_vertices, uint32_t *__restrict__ parent, uint32_t *__restrict__ sizes) {
     const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;

@@ -1,5 +1,6 @@
-// The lock-free union-find the labellings share: mesh_components.hip (a lane per index triple, over the vertices) and explore.hip (a lane
-// per listed frontier voxel, over the list).  Hooks go towards the smaller index; DESIGN.md 20 argues the three invariants:
+// The lock-free union-find the labellings share: mesh_components.hip (a lane per index triple, over the vertices) and voxel_set.hpp (a
+// lane per listed voxel, over the list: the frontier clusters of explore.hip and the class objects of objects.hip).  Hooks go towards
+// the smaller index; DESIGN.md 20 argues the three invariants:
 //   1. parent[v] <= v always; a word changes only from v to something smaller in the same component (the CAS of unite) or from one
 //      ancestor to a smaller one (the atomicMin of find).  So every chain strictly decreases: find terminates, there are no cycles,
 //      and the final root is the component's minimum.

@@ -1,4 +1,5 @@
-// Voxel ids and the per-chunk masks over them, shared by explore.hip (frontier voxels) and objects.hip (labelled voxels): voxel
+// Voxel ids and the per-chunk masks over them, shared by voxel_set.hpp (the list and the clusters of a voxel set), explore.hip (its
+// flag kernel marks the frontier voxels) and objects.hip (its flag kernel marks the labelled voxels, its lookup reads the masks): voxel
 // (x, y, z) of an X x Y x Z grid has id (z * Y + y) * X + x, 64 consecutive ids are a chunk, and a chunk's 64-bit mask says which of its
 // voxels are listed (store_keep_mask and compact_index, mesh_device.hpp, write the masks and turn an id into a list index).
 #pragma once
