@@ -2,8 +2,9 @@
 tsdf_amd.TSDFVolume (and the source volume of its fuses) side by side with the composed CPU model (tests/volume_model.py), and
 everything is compared bit for bit, without a tolerance:
 
-  * after every writer and every switch: distances, weights, the colour words when enabled, colour_enabled(), weight_cap(), and the
-    updated-voxel count where the call returns one;
+  * after every writer and every switch: distances, weights, the colour words when enabled, colour_enabled(), the class words when
+    enabled, classes_enabled(), weight_cap(), and the updated-voxel count where the call returns one (the counters, behind a class
+    frame);
   * at every observer: ray-cast vertices and normals against the oracle on the model's arrays, extract_surface against the oracle's
     marching cubes, the lazy brick flags at least their definition and the rebuilt ones (reach included) equal to it, a snapshot
     against tests/snapshot_ref.py at the storage the volume has at that moment;
@@ -36,7 +37,9 @@ F32, U32 = np.float32, np.uint32
 DEPTH_TILE = 16          # TSDF_DEPTH_TILE (include/tsdf_amd.h)
 REFUSALS = {"remove": "tsdf_deintegrate: the volume has a weight cap", "rays_colour": "tsdf_integrate_rays_colour: colour is not enabled",
             "restore_other": "tsdf_volume_restore: the snapshot is of a 8 x 8 x 8 grid",
-            "depth_weighted_colour": "tsdf_integrate_weighted: colour is not enabled"}
+            "depth_weighted_colour": "tsdf_integrate_weighted: colour is not enabled",
+            "depth_classes_rgb": "tsdf_integrate_classes: rgb given but colour is not enabled",
+            "depth_classes_nodes": "tsdf_integrate_classes: not supported once the deformation nodes are explicit"}
 _SEEN = {"seeds": set(), "modes": {}, "casts": {True: 0, False: 0}}
 
 
@@ -68,6 +71,7 @@ class Sequenced:
         self.src.set_distance_data(self.info["source"]["dist"])
         self.src.set_weight_data(self.info["source"]["weight"])
         self.snaps = []
+        self.counting = False
         self.dims = tuple(self.info["dims"])
         assert F32(self.gv.truncation_distance()) == self.model.trunc() and np.array_equal(self.gv.voxel_size(), self.model.ov.voxel_size())
 
@@ -78,7 +82,8 @@ class Sequenced:
     # ---- comparisons
     def library_state(self, v=None):
         v = self.gv if v is None else v
-        return (v.get_distance_data(), v.get_weight_data(), v.get_colour_data() if v.colour_enabled() else None, v.weight_cap(), v.weight_storage())
+        return (v.get_distance_data(), v.get_weight_data(), v.get_colour_data() if v.colour_enabled() else None, v.weight_cap(), v.weight_storage(),
+                v.get_class_data() if v.classes_enabled() else None)
 
     def same_as_model(self, what, v=None):
         v = self.gv if v is None else v
@@ -90,6 +95,11 @@ class Sequenced:
             got = v.get_colour_data()
             bad = np.flatnonzero(got != m.colour)
             assert not bad.size, "%s: %d colour words differ, first at %d: %#x vs %#x" % (what, bad.size, bad[0], got[bad[0]], m.colour[bad[0]])
+        assert v.classes_enabled() == (m.classes is not None), what + ": classes enabled"
+        if m.classes is not None:
+            got = v.get_class_data()
+            bad = np.flatnonzero(got != m.classes)
+            assert not bad.size, "%s: %d class words differ, first at %d: %#x vs %#x" % (what, bad.size, bad[0], got[bad[0]], m.classes[bad[0]])
         assert v.weight_cap() == m.cap, what + ": weight cap"
         bits = v.weight_storage()[0]
         _SEEN["modes"][bits] = _SEEN["modes"].get(bits, 0) + 1
@@ -99,6 +109,8 @@ class Sequenced:
         kind, gv, w, h = op[0], self.gv, self.width, self.height
         if kind == "depth_prepared":
             return self.prepared(op, what)
+        if kind == "classes_prepared":
+            return self.classes_prepared(op, what)
         if kind == "refused":
             return self.refused(op[1], what)
         want = self.run.apply(op)
@@ -106,6 +118,23 @@ class Sequenced:
             gv.integrate(op[1], w, h, Cam(*op[2]))
         elif kind == "depth_colour":
             gv.integrate_colour(op[1], op[2], w, h, Cam(*op[3]))
+        elif kind == "depth_classes":
+            gv.integrate_classes(op[1], op[2], w, h, Cam(*op[5]), confidence=op[3], rgb=op[4])
+            if self.counting:
+                assert gv.last_updated_voxels() == want, what + ": updated voxels"
+        elif kind == "classes":
+            gv.enable_classes(op[1])
+        elif kind == "upload_classes":
+            gv.set_class_data(op[1])
+        elif kind == "nodes":
+            assert gv.deformation()
+        elif kind == "pin":
+            assert gv.weight_data() and gv.weight_storage() == (32, True), what
+        elif kind == "counting":
+            gv.set_counting(op[1])
+            self.counting = bool(op[1])
+        elif kind == "image":
+            self.width, self.height = op[1]
         elif kind == "depth_weighted":
             gv.integrate_weighted(op[1], op[2], w, h, Cam(*op[3]))
         elif kind == "depth_weighted_colour":
@@ -194,13 +223,55 @@ class Sequenced:
         gv.synchronize()
         self.same_as_model(what)
 
+    def classes_prepared(self, op, what):
+        """integrate_prepare_device for a frame (on the default stream, waited for), then integrate_classes_device with that frame's
+        depth pointer and camera -- it holds no tile maxima, so the list is not its own and it culls for itself -- then the
+        integrate_device the list was prepared for, which finds it used up and culls too: the frame is fused twice, the vote cast once.
+        The images live in allocations of the library's own (tsdf_device_alloc)."""
+        import ctypes as C
+        gv, w, h, lib = self.gv, self.width, self.height, _capi.lib
+        _, d, k, s, cam4 = op
+        cam = Cam(*cam4)
+        held = []
+
+        def dev(a, dtype):
+            a = np.ascontiguousarray(a, dtype).reshape(-1)
+            p = C.c_void_p()
+            _capi.check(lib.tsdf_device_alloc(max(a.nbytes, 4), C.byref(p)))
+            held.append(p)
+            _capi.check(lib.tsdf_device_upload(p, a.ctypes.data, a.nbytes))
+            return p.value
+
+        try:
+            depth, classes, tiles = dev(d, np.uint16), dev(k, np.uint16), dev(tile_maxima(d, w, h), np.uint16)
+            conf = dev(s, np.uint8) if s is not None else None
+            gv.synchronize()
+            gv.integrate_prepare_device(depth, w, h, cam, tiles, 0)
+            _capi.check(lib.tsdf_stream_synchronize(None))
+            self.run.apply(("depth_classes", d, k, s, None, cam4))
+            gv.integrate_classes_device(depth, classes, w, h, cam, confidence_ptr=conf)
+            gv.synchronize()
+            self.same_as_model(what + ", the class call")
+            self.model.integrate(d, w, h, cam)
+            gv.integrate_device(depth, w, h, cam, tile_max_ptr=tiles)
+            gv.synchronize()
+            self.same_as_model(what)
+        finally:
+            for p in held:
+                lib.tsdf_device_free(p)
+
     def refused(self, op, what):
         gv = self.gv
         before = self.library_state()
         self.run.apply(("refused", op))          # (the model refuses it too, and stays as it was)
         other = snap = None
-        with pytest.raises(ValueError, match=REFUSALS[op[0]]):
-            if op[0] == "remove":
+        reason = op[0]
+        if reason == "depth_classes":
+            reason = "depth_classes_rgb" if op[4] is not None and not gv.colour_enabled() else "depth_classes_nodes"
+        with pytest.raises(ValueError, match=REFUSALS[reason]):
+            if op[0] == "depth_classes":
+                gv.integrate_classes(op[1], op[2], self.width, self.height, Cam(*op[5]), confidence=op[3], rgb=op[4])
+            elif op[0] == "remove":
                 gv.deintegrate(op[1], self.width, self.height, Cam(*op[2]))
             elif op[0] == "rays_colour":
                 gv.integrate_rays(op[1], op[2], band_only=op[4], min_range=op[5], max_range=op[6], rgb=op[3])
@@ -211,12 +282,12 @@ class Sequenced:
                 other.set_weight_data(np.ones(other.resident_voxels(), F32))
                 snap = other.snapshot()
                 gv.restore(snap)
-        assert REFUSALS[op[0]] in _capi.last_error(), what
+        assert REFUSALS[reason] in _capi.last_error(), what
         for o in (snap, other):
             if o is not None:
                 o.close()
         after = self.library_state()
-        for a, b, name in zip(before, after, ("distances", "weights", "colours", "cap", "storage")):
+        for a, b, name in zip(before, after, ("distances", "weights", "colours", "cap", "storage", "class words")):
             assert (a is None and b is None) or np.array_equal(np.asarray(a).view(U32) if isinstance(a, np.ndarray) else a,
                                                                np.asarray(b).view(U32) if isinstance(b, np.ndarray) else b), what + ": " + name
         self.same_as_model(what)
@@ -232,6 +303,9 @@ class Sequenced:
         if m.colour is not None:
             t.enable_colour()
             t.set_colour_data(m.colour)
+        if m.classes is not None:
+            t.enable_classes()
+            t.set_class_data(m.classes)
         t.set_weight_cap(m.cap)
         t.set_distance_data(m.dist)
         t.set_weight_data(m.weight)

@@ -15,6 +15,13 @@ drives through the library.
 3. Sensitivity: the model with one plausible defect at a time ends at least three sequences in another state than the true model.
    Achieved: counts that wrap modulo 256 in rays and fuse: seeds 2, 3, 4, 24; a restore that leaves the colour words: 18, 19, 20, 21; rays
    that ignore the cap: 10, 14, 16; a removal that keeps the distance where the weight reaches 0: 8, 10, 26, 30, 31.
+4. Class words (tests/class_sequences.py, run on the GPU by tests/test_class_fuzz.py): the twelve sequences run to their end on the model;
+   every class frame but the refused ones changes 16 words or more; a class frame takes the largest weight past 255 and one past 65535;
+   class frames stand on both sides of a storage switch, a pin, a cap switched on and off, a removal, rays, a fuse, a weighted frame, a
+   restore, a clear and a change of the image size; only a class frame, a clear, an upload of words and the switch itself change a
+   word -- a restore leaves the words voted since its snapshot in place; both refusals occur and leave the state alone; each of three
+   defects (a restore that zeroes the words, a removal that takes the votes of the voxels it empties, a vote in free space) ends at
+   least two sequences in another state.
 """
 import functools
 
@@ -24,21 +31,22 @@ import pytest
 from tests import colour_ref, deintegrate_ref, fuse_ref, rays_colour_ref, rays_integrate_ref, snapshot_ref
 from tests import op_sequences as S
 from tests.helpers import Cam, assert_same_floats
-from tests.volume_model import ModelRun, Refused, VolumeModel, WEIGHTED_MUTANTS
+from tests import class_sequences as CS
+from tests.volume_model import CLASS_MUTANTS, ModelRun, Refused, VolumeModel, WEIGHTED_MUTANTS
 from tests.volume_model import MUTANTS as ALL_MUTANTS
 from tests.weight_cap_ref import oracle_step
 
 F32, U32 = np.float32, np.uint32
 # the defects of integrate_weighted have sequences of their own (tests/weighted_sequences.py, tests/test_weighted_fuzz_host.py): the 32
 # pinned sequences hold no weighted frame
-MUTANTS = tuple(m for m in ALL_MUTANTS if m not in WEIGHTED_MUTANTS)
+MUTANTS = tuple(m for m in ALL_MUTANTS if m not in WEIGHTED_MUTANTS and m not in CLASS_MUTANTS)
 
 
 def _same_state(a, b):
     if a is None or b is None:
         return False
     return all((x is None and y is None) or (x is not None and y is not None and np.array_equal(np.asarray(x).view(U32), np.asarray(y).view(U32)))
-               for x, y in zip(a[:3], b[:3])) and a[3] == b[3]
+               for x, y in zip(a[:3] + a[4:], b[:3] + b[4:])) and a[3] == b[3]
 
 
 def _changed(before, after):
@@ -208,7 +216,7 @@ def test_restore_is_the_snapshot_references_round_trip_and_the_headers_colour_ru
     m, rng = busy
     if not with_colour:
         m.enable_colour(False)
-    D, Wt, Cl, _ = m.state()
+    D, Wt, Cl, _ = m.state()[:4]
     assert Wt.max() <= 255
     snap = m.snapshot()
     # the reference as tests/test_snapshot.py calls it, at the storage a volume with these counts has
@@ -419,6 +427,93 @@ def test_a_defect_of_this_kind_changes_the_end_of_three_sequences(caught, mutant
 
 def test_the_model_without_a_defect_repeats_itself(oracle):
     assert _same_state(final_state(9, None), survey(9)[1])
+
+
+# ---- 4. class words among the writers ---------------------------------------------------------------------------------------------------
+def _flat_class_ops(ops):
+    """The ops in the order they act: a "classes_prepared" is its class frame and then the plain frame the list was prepared for."""
+    out = []
+    for op in ops:
+        if op[0] == CS.KP:
+            out += [(CS.K, op[1], op[2], op[3], None, op[4]), ("depth", op[1], op[4])]
+        else:
+            out.append(op)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def class_survey(i, mutant=None):
+    """One run of the model over a class sequence: a record per acting op (observers left out) and the final state, or None where a
+    defect made the model refuse a call."""
+    import oracle as O
+    O.build()
+    base, ops = CS.sequence(i)
+    info, image, _ = S.sequence(base)
+    run = ModelRun(O, info, image, mutant)
+    m = run.model
+    records = []
+    for op in _flat_class_ops(ops):
+        if op[0] in ("raycast", "surface", "flags"):
+            continue
+        before = m.state()
+        try:
+            run.apply(op)
+        except Refused:
+            return records, None
+        after = m.state()
+        words = 0 if before[4] is None or after[4] is None else int((before[4] != after[4]).sum())
+        records.append({"kind": op[0], "op": op, "words": words, "had_words": before[4] is not None and bool(before[4].any()),
+                        "top_before": float(np.nanmax(before[1])), "top_after": float(np.nanmax(after[1])),
+                        "state_changed": _changed(before, after), "image": (run.width, run.height)})
+    return records, m.state()
+
+
+def test_the_class_sequences_hold_what_they_were_built_for(oracle):
+    assert 10 <= CS.N <= 14
+    runs = [class_survey(i) for i in range(CS.N)]
+    assert all(end is not None for _, end in runs)
+    frames = [r for recs, _ in runs for r in recs if r["kind"] == CS.K]
+    assert len(frames) >= 40 and sum(r["words"] >= 16 for r in frames) >= 0.9 * len(frames), [r["words"] for r in frames]
+    assert any(r["top_before"] <= 255 < r["top_after"] for r in frames) and any(r["top_before"] <= 65535 < r["top_after"] for r in frames)
+    # only the class writers change a word; the other writers do their own work beside words that are there
+    others = [r for recs, _ in runs for r in recs if r["kind"] not in (CS.K, "clear", "upload_classes", "classes", "refused")]
+    assert all(r["words"] == 0 for r in others)
+    beside = {r["kind"] for r in others if r["had_words"] and (r["state_changed"] or r["kind"] in ("storage", "pin", "cap", "image", "snapshot"))}
+    assert {"depth", "depth_colour", "depth_weighted", "remove", "rays", "fuse", "restore", "storage", "pin", "cap", "image", "snapshot"} <= beside, beside
+    # a class frame straight or one op behind each of them, and in front of each
+    for recs, _ in runs:
+        kinds = [r["kind"] for r in recs]
+        for a, b in zip(kinds, kinds[1:]):
+            if a in beside and b == CS.K:
+                beside = beside - {a}
+    assert not beside - {"snapshot", "cap"}, beside
+    # a restore leaves the words voted since its snapshot in place
+    for i in (0, 7):
+        recs = class_survey(i)[0]
+        at = [k for k, r in enumerate(recs) if r["kind"] == "restore"][0]
+        assert recs[at]["had_words"] and recs[at]["words"] == 0 and recs[at]["state_changed"] > 0
+    clears = [r for recs, _ in runs for r in recs if r["kind"] == "clear"]
+    assert len(clears) >= 3 and all(r["words"] > 0 for r in clears if r["had_words"]) and any(r["had_words"] for r in clears)
+    # the image size changes between class frames and returns
+    sizes = [r["image"] for r in class_survey(8)[0] if r["kind"] == CS.K]
+    assert len(set(sizes)) == 3 and sizes[0] == sizes[-1]
+    # both refusals, with words to lose
+    refused = [r for recs, _ in runs for r in recs if r["kind"] == "refused"]
+    assert sorted((r["op"][1][4] is not None) for r in refused) == [False, True, True] and all(r["had_words"] and not r["state_changed"] for r in refused)
+    assert sum(op[0] == CS.KP for i in range(CS.N) for op in CS.sequence(i)[1]) >= 2
+    assert sum(op == ("counting", True) for i in range(CS.N) for op in CS.sequence(i)[1]) >= 2
+
+
+def test_class_sequences_are_deterministic_data():
+    a = S.describe(CS.sequence(3)[1])
+    CS.sequence.cache_clear()
+    assert S.describe(CS.sequence(3)[1]) == a
+
+
+@pytest.mark.parametrize("mutant", CLASS_MUTANTS)
+def test_a_defect_round_the_class_words_changes_the_end_of_two_class_sequences(oracle, mutant):
+    caught = [i for i in range(CS.N) if not _same_state(class_survey(i, mutant)[1], class_survey(i)[1])]
+    assert len(caught) >= 2, (mutant, caught)
 
 
 if __name__ == "__main__":

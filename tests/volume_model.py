@@ -1,22 +1,27 @@
-"""One CPU model of a whole volume: every writer, switch and observer of tsdf_amd.TSDFVolume on plain (dist, weight, colour) arrays, each
+"""One CPU model of a whole volume: every writer, switch and observer of tsdf_amd.TSDFVolume on plain (dist, weight, colour, class) arrays, each
 delegated to the reference that already pins that operation on its own -- oracle/ for integrate, ray cast and marching cubes,
-weight_cap_ref, colour_ref, deintegrate_ref, weighted_ref, rays_integrate_ref, rays_colour_ref, fuse_ref, snapshot_ref, and the flag
-definition of tests/test_occupancy.py.  No arithmetic of its own: what is new is only that the references act on ONE state, in any
-order (tests/op_sequences.py, tests/test_op_sequences.py; tests/weighted_sequences.py, tests/test_weighted_fuzz.py).  How the weights
+weight_cap_ref, colour_ref, deintegrate_ref, weighted_ref, rays_integrate_ref, rays_colour_ref, fuse_ref, snapshot_ref, classes_ref, and
+the flag definition of tests/test_occupancy.py.  No arithmetic of its own: what is new is only that the references act on ONE state, in any
+order (tests/op_sequences.py, tests/test_op_sequences.py; tests/weighted_sequences.py, tests/test_weighted_fuzz.py;
+tests/class_sequences.py, tests/test_class_fuzz.py).  The class words belong to the class writers alone: a class integrate votes, clear
+zeroes, an upload sets them, and every other writer -- restore included -- leaves them as they are.  How the weights
 are stored must not show in a single bit, so the model has no storage.  `mutant=` switches in one plausible defect at a time
 (tests/test_op_sequences_host.py and tests/test_weighted_fuzz_host.py show that the sequences see each).
 Test infrastructure only."""
 import numpy as np
 
-from tests import colour_ref, deintegrate_ref, fuse_ref, rays_colour_ref, rays_integrate_ref, snapshot_ref, weighted_ref
+from tests import classes_ref, colour_ref, deintegrate_ref, fuse_ref, rays_colour_ref, rays_integrate_ref, snapshot_ref, weighted_ref
 from tests.field_ref import geometry as field_geometry
 from tests.weight_cap_ref import oracle_step
 
 F32, U32 = np.float32, np.uint32
 MUTANTS = ("counts_wrap_at_256", "restore_keeps_colour", "rays_ignore_cap", "remove_keeps_distance",
            # switched in only inside integrate_weighted (tests/test_weighted_fuzz_host.py shows that its sequences and cases see each)
-           "weighted_cap_clamps_divisor", "weighted_invalid_pixel_colours", "weighted_next_pixel")
-WEIGHTED_MUTANTS = MUTANTS[4:]
+           "weighted_cap_clamps_divisor", "weighted_invalid_pixel_colours", "weighted_next_pixel",
+           # switched in only where class words are enabled (tests/test_op_sequences_host.py shows that the class sequences see each)
+           "restore_zeroes_classes", "remove_takes_votes_back", "classes_vote_in_free_space")
+WEIGHTED_MUTANTS = MUTANTS[4:7]
+CLASS_MUTANTS = MUTANTS[7:]
 
 
 class Refused(Exception):
@@ -31,6 +36,8 @@ class VolumeModel:
         if offset is not None:
             self.ov.offset(*offset)          # (set without a clear, as the ray and fuse tests do: offset_at_clear stays zero)
         self.colour = None                   # uint32 words, or None while colour is not enabled
+        self.classes = None                  # uint32 {class, votes} words, or None while classes are not enabled
+        self.explicit_nodes = False          # deformation() was called: the nodes are materialised (a class integrate is refused)
         self.cap = 0
         self.last_stores = None              # distance stores of the last integrate_weighted
 
@@ -50,8 +57,9 @@ class VolumeModel:
         return F32(self.ov.truncation_distance())
 
     def state(self):
-        """Copies of (dist, weight, colour or None, cap)."""
-        return self.dist.copy(), self.weight.copy(), None if self.colour is None else self.colour.copy(), self.cap
+        """Copies of (dist, weight, colour or None, cap, class words or None)."""
+        return (self.dist.copy(), self.weight.copy(), None if self.colour is None else self.colour.copy(), self.cap,
+                None if self.classes is None else self.classes.copy())
 
     def _colour_geometry(self):
         g = self.ov.g
@@ -68,6 +76,25 @@ class VolumeModel:
             raise Refused("colour integrate on a volume without colour enabled")
         self.colour = colour_ref.integrate_colour(self.O, self.colour, self._colour_geometry(), depth, rgb, width, height, cam)[0]
         return self.integrate(depth, width, height, cam)
+
+    def integrate_classes(self, depth, classes, confidence, rgb, width, height, cam):
+        """tsdf_integrate_classes: the plain (or, with rgb, the colour) integrate plus tests/classes_ref.py's vote.  The vote reads the
+        geometry, the images and the old words only: which of the two comes first makes no difference."""
+        if self.classes is None:
+            raise Refused("tsdf_integrate_classes: classes are not enabled on this volume")
+        if self.explicit_nodes:
+            raise Refused("tsdf_integrate_classes: not supported once the deformation nodes are explicit")
+        if rgb is not None and self.colour is None:
+            raise Refused("tsdf_integrate_classes: rgb given but colour is not enabled on this volume")
+        geom = self._colour_geometry()
+        if self.mutant == "classes_vote_in_free_space":
+            geom = geom[:4] + (F32(np.inf),)
+        self.classes, updated, _ = classes_ref.integrate_classes(self.O, self.classes, geom, depth, classes, confidence, width, height, cam)
+        if rgb is None:
+            self.integrate(depth, width, height, cam)
+        else:
+            self.integrate_colour(depth, rgb, width, height, cam)
+        return int(updated.sum())            # (the distance update's set: what the counter counts, whether or not a cap holds the weight)
 
     def integrate_weighted(self, depth, weights, width, height, cam, rgb=None):
         """tsdf_integrate_weighted: tests/weighted_ref.py's frame and blend, tests/colour_ref.py on the masked image."""
@@ -100,6 +127,8 @@ class VolumeModel:
         if self.mutant == "remove_keeps_distance":
             gone = in_set & (self.weight == 0)
             self.dist[gone] = keep[gone]
+        if self.mutant == "remove_takes_votes_back" and self.classes is not None:
+            self.classes = np.where(in_set & (self.weight == 0), U32(0), self.classes)
         return updated
 
     def integrate_rays(self, origins, points, rgb=None, band_only=False, min_range=0.0, max_range=np.inf):
@@ -142,6 +171,8 @@ class VolumeModel:
         d, w, c = snapshot_ref.put(s["ids"], s["dist"], s["weight"], s["colour"], s["size"], s["fill"])
         self.ov.set_distance_data(d)
         self.ov.set_weight_data(w)
+        if self.mutant == "restore_zeroes_classes" and self.classes is not None:
+            self.classes = np.zeros_like(self.classes)
         if self.mutant == "restore_keeps_colour":
             return
         if c is not None:
@@ -153,6 +184,8 @@ class VolumeModel:
         self.ov.clear()
         if self.colour is not None:
             self.colour = np.zeros_like(self.colour)
+        if self.classes is not None:
+            self.classes = np.zeros_like(self.classes)
 
     def set_distance_data(self, d):
         self.ov.set_distance_data(d)
@@ -166,7 +199,23 @@ class VolumeModel:
         self.colour = np.array(c, U32).reshape(-1)
         assert self.colour.size == self.dist.size
 
+    def set_class_data(self, c):
+        if self.classes is None:
+            raise Refused("class data access on a volume without classes enabled")
+        self.classes = np.array(c, U32).reshape(-1)
+        assert self.classes.size == self.dist.size
+
     # ---- switches
+    def enable_classes(self, on=True):
+        if not on:
+            self.classes = None
+        elif self.classes is None:
+            self.classes = np.zeros(self.dist.size, U32)
+
+    def materialise_nodes(self):
+        """deformation(): the regular grid as explicit nodes -- the same centres, so every writer that takes nodes writes the same bits."""
+        self.explicit_nodes = True
+
     def enable_colour(self, on=True):
         if not on:
             self.colour = None
@@ -220,6 +269,19 @@ class ModelRun:
             return m.integrate(op[1], w, h, self.Cam(*op[2]))
         if kind == "depth_colour":
             return m.integrate_colour(op[1], op[2], w, h, self.Cam(*op[3]))
+        if kind == "depth_classes":
+            return m.integrate_classes(op[1], op[2], op[3], op[4], w, h, self.Cam(*op[5]))
+        if kind == "classes":
+            return m.enable_classes(op[1])
+        if kind == "upload_classes":
+            return m.set_class_data(op[1])
+        if kind == "nodes":
+            return m.materialise_nodes()
+        if kind in ("counting", "pin"):
+            return None                      # (the counters and the storage are the library's: the model counts every writer and has no storage)
+        if kind == "image":
+            self.width, self.height = op[1]  # the size of every image from here on
+            return None
         if kind == "depth_weighted":
             return m.integrate_weighted(op[1], op[2], w, h, self.Cam(*op[3]))
         if kind == "depth_weighted_colour":
@@ -267,7 +329,8 @@ class ModelRun:
                 self.apply(op[1])
             except Refused:
                 after = m.state()
-                assert all((a is None and b is None) or np.array_equal(a, b) for a, b in zip(before[:3], after[:3])) and before[3] == after[3]
+                assert all((a is None and b is None) or np.array_equal(a, b) for a, b in zip(before[:3] + before[4:], after[:3] + after[4:]))
+                assert before[3] == after[3]
                 return None
             raise AssertionError("the model does not refuse %r" % (op[1][0],))
         raise ValueError(kind)
