@@ -446,7 +446,7 @@ int tsdf_raycast_colour_device(const tsdf_volume *volume, uint32_t width, uint32
  *         c != k, n == s  -> 0x00000000
  *         c != k, n <  s  -> (k, s - n)
  *     the weighted Boyer-Moore majority vote.  One writer per word and no atomics: a call's result is a unique set of bits.  The
- *     update is a pass of its own (class_integrate_kernel) behind the integrate kernel -- and behind the colour update, when rgb is
+ *     update is a pass of its own (band_pass_kernel with the policy ClassVote) behind the integrate kernel -- and behind the colour update, when rgb is
  *     given -- on the volume's stream over the frame's brick list, for standard and general cameras and all three weight storages.
  *   Sampling: tsdf_volume_sample_classes_device reads the voxel tsdf_volume_sample_colours_device reads -- the same frame
  *     (offset_at_clear subtracted), the same index expression -- and gives (TSDF_CLASS_VOID, 0) for a NaN coordinate, an off-grid

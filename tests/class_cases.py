@@ -3,7 +3,7 @@ tests/test_class_fuzz_host.py surveys on the CPU reference (tests/classes_ref.py
 
     python -m tests.class_cases SEED...     prints the cases
 
-The first len(AIMED) seeds are aimed, not drawn: each row of AIMED reaches one path of class_integrate_kernel (tsdf_amd/csrc/classes.hip)
+The first len(AIMED) seeds are aimed, not drawn: each row of AIMED reaches one path of band_pass_kernel<STD, ClassVote> (tsdf_amd/csrc/band_pass.hpp)
 nobody would draw -- a 1 x 1 image, widths round one wave, planes appended to the last brick layer, a camera inside the grid and one
 exactly on a voxel centre, voxels with sdf == +-trunc, start votes and strengths over the saturation edge.  The N_DRAWN seeds behind them
 draw grid, voxel sizes and image as tests/test_colour_parity.py::random_case does, cameras and depths as tests/test_fuzz_parity.py, and
@@ -350,7 +350,7 @@ MUTANTS = ("open_band", "no_z_extra", "wrapping_add")      # the defects tests/t
 
 class Reference:
     """The oracle's volume and the reference class words of a case; apply(frame) -> what the frame did.  `mutant=` switches in one
-    plausible defect of class_integrate_kernel: sdf < trunc in place of <=, the appended planes left out of the z bound, n + s that
+    plausible defect of band_pass_kernel or ClassVote: sdf < trunc in place of <=, the appended planes left out of the z bound, n + s that
     wraps at 16 bits."""
 
     @staticmethod

@@ -1,7 +1,8 @@
 """GPU: class fusion against its CPU reference where kernels go wrong (include/tsdf_amd.h, "class fusion"; tsdf_amd/csrc/classes.hip).
 
-class_integrate_kernel is a copy of colour_integrate_kernel, not a call into it: brick walk, camera split, rounding guard band, frustum
-test, depth read, band test and appended-z-chunk bound of its own.  tests/test_class_fusion.py holds it to the reference at 640 x 480 on
+The class update is band_pass_kernel<STD, ClassVote> (tsdf_amd/csrc/band_pass.hpp), an instantiation of its own of the walk colour
+takes: brick walk, camera split, rounding guard band, frustum test, depth read, band test and appended-z-chunk bound, then the vote
+of ClassVote.  tests/test_class_fusion.py holds it to the reference at 640 x 480 on
 two 3000 mm cubes seen from outside; here it meets what colour (tests/test_colour_parity.py) and weighted integration
 (tests/test_weighted_fuzz.py) are held to.
 

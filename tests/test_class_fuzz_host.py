@@ -10,7 +10,7 @@
      camera; silent 35, first 36, same 27, saturate 17, lead 23, tie 21, take-over 23.  The whole survey takes under a second.)
   3. the drawn seeds are what the issue describes: the planes of every fifth seed, the moved offsets, the start words, rgb and the device
      variant by seed, growing images within a device case;
-  4. three plausible defects of class_integrate_kernel, switched into the reference (class_cases.MUTANTS), change the final words of
+  4. three plausible defects of band_pass_kernel and ClassVote, switched into the reference (class_cases.MUTANTS), change the final words of
      the cases aimed at them and of at least one drawn seed: sdf < trunc for <=, the appended planes left out of the z bound, a
      vote count that wraps at 16 bits;
   5. classify() agrees with the vote rule of tests/classes_ref.py on every (n, s) of a grid round the edges.

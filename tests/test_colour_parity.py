@@ -1,6 +1,6 @@
 """Colour fusion against its CPU reference where kernels go wrong (include/tsdf_amd.h, "colour fusion"; tsdf_amd/csrc/colour.hip).
 
-test_colour_fusion.py checks colour on cubic 3000 mm grids seen from outside at 640x480.  colour_integrate_kernel has a brick walk,
+test_colour_fusion.py checks colour on cubic 3000 mm grids seen from outside at 640x480.  band_pass_kernel (tsdf_amd/csrc/band_pass.hpp) has a brick walk,
 camera split, rounding, frustum test, depth read and band test of its own, so here it meets the corners the distance path is held to
 (test_fuzz_parity.py, test_parity_integrate.py): random grids, images and cameras, appended planes, odd widths and unaligned
 pointers, cameras inside the grid, voxels with sdf exactly +-trunc, every observation count, the weight storage transitions and the

@@ -112,6 +112,29 @@ int weights_require_f32(struct ::tsdf_volume *v);
 int weights_make_room(struct ::tsdf_volume *v);
 int weights_upload(struct ::tsdf_volume *v, const float *host);
 int weights_download(const struct ::tsdf_volume *v, float *host);
+// integrate.hip: one frame into the volume.  The first six fields are every frame's (device depth image, its size, inv_pose[16],
+// k[9], kinv[9]); the rest are off unless set, by name:
+//   tile_max       the caller's maxima per 16 x 16 depth tile (the bilateral filter's), else computed here
+//   rgb            tsdf_integrate_colour: the colour update, in the packed kernel or as the colour pass behind the integrate kernel
+//   pweight        tsdf_integrate_weighted: a weight per pixel; depth is then the masked image and the weights are fp32 already
+//   classes, confidence   tsdf_integrate_classes: the class pass behind the integrate kernel and the colour update
+//   remove         tsdf_deintegrate
+//   phase, prepare_stream   kIntPrepare: the culling only, on prepare_stream (tsdf_integrate_prepare_device_tiles)
+enum IntegratePhase { kIntBoth = 0, kIntPrepare = 1 };
+struct IntegrateFrame {
+    const uint16_t *depth;
+    uint32_t width, height;
+    const float *inv_pose, *k, *kinv;
+    const uint16_t *tile_max = nullptr;
+    const uint8_t *rgb = nullptr;
+    const float *pweight = nullptr;
+    const uint16_t *classes = nullptr;
+    const uint8_t *confidence = nullptr;
+    bool remove = false;
+    IntegratePhase phase = kIntBoth;
+    hipStream_t prepare_stream = nullptr;
+};
+int launch_integrate(struct ::tsdf_volume *v, const IntegrateFrame &f);
 
 #define TSDF_HIP(call, what)                                  \
     do {                                                      \

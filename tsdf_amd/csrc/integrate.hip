@@ -345,13 +345,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // then finds the list prepared (same image, pose, intrinsics, tile maxima) and launches integrate_kernel alone.
 // remove: tsdf_deintegrate* -- the same culling, list and counters, then the removal kernel of the volume's storage; the weights are
 // neither given room nor counted (weight_bound stays an upper bound), and the frame does not count as an integration.
-enum IntegratePhase { kIntBoth = 0, kIntPrepare = 1 };
-static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t width, uint32_t height,
-                            const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *caller_tile_max = nullptr,
-                            IntegratePhase phase = kIntBoth, hipStream_t prepare_stream = nullptr, const uint8_t *d_rgb = nullptr,
-                            bool remove = false, const float *d_pweight = nullptr, const uint16_t *d_classes = nullptr,
-                            const uint8_t *d_confidence = nullptr) {
-    // d_pweight: tsdf_integrate_weighted* -- d_depth is then the masked image and the weights are fp32 already (integrate_weighted below)
+int launch_integrate(tsdf_volume *v, const IntegrateFrame &f) {
+    const uint16_t *const d_depth = f.depth, *const caller_tile_max = f.tile_max, *const d_classes = f.classes;
+    const uint32_t width = f.width, height = f.height;
+    const float *const inv_pose = f.inv_pose, *const k = f.k, *const kinv = f.kinv, *const d_pweight = f.pweight;
+    const uint8_t *const d_rgb = f.rgb, *const d_confidence = f.confidence;
+    const bool remove = f.remove;
+    const IntegratePhase phase = f.phase;
+    const hipStream_t prepare_stream = f.prepare_stream;
     Mat44 ip;
     Mat33 mk, mkinv;
     memcpy(&ip, inv_pose, sizeof(ip));
@@ -561,32 +562,6 @@ static int launch_integrate(tsdf_volume *v, const uint16_t *d_depth, uint32_t wi
     return TSDF_OK;
 }
 
-// tsdf_integrate_colour_device (colour.hip) and the pipeline's / tracker's coloured steps (pipeline.hip, with the filter's tile
-// maxima): integrate and the colour update, in the packed kernel or as the colour pass behind the integrate kernel
-int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
-                          const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max) {
-    return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, tile_max, kIntBoth, nullptr, d_rgb);
-}
-
-// tsdf_integrate_classes_device (classes.hip): integrate, the colour update of tsdf_integrate_colour when d_rgb is given, then the class
-// pass behind them over the frame's brick list
-int integrate_with_classes(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, const uint16_t *d_classes,
-                           const uint8_t *d_confidence, uint32_t width, uint32_t height, const float inv_pose[16], const float k[9],
-                           const float kinv[9]) {
-    return launch_integrate(v, d_depth, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, d_rgb, false, nullptr, d_classes,
-                            d_confidence);
-}
-
-// tsdf_integrate_weighted_device (integrate_weighted.hip): d_masked is the depth image with the pixels of invalid weight zeroed; the
-// volume goes to fp32 weights first (it stays there until clear(), as after any widening), then the usual culling, integrate_weighted_kernel
-// and -- with d_rgb -- the colour pass over the masked image
-int integrate_weighted(tsdf_volume *v, const uint16_t *d_masked, const float *d_pweight, const uint8_t *d_rgb, uint32_t width, uint32_t height,
-                       const float inv_pose[16], const float k[9], const float kinv[9]) {
-    const int rc = weights_require_f32(v);
-    if (rc != TSDF_OK) return rc;
-    return launch_integrate(v, d_masked, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, d_rgb, false, d_pweight);
-}
-
 }  // namespace tsdf
 
 using namespace tsdf;
@@ -598,7 +573,7 @@ int tsdf_integrate_device(tsdf_volume *v, const uint16_t *device_depth, uint32_t
     TSDF_REQUIRE(v && device_depth && inv_pose && k && kinv, "tsdf_integrate: null argument");
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate: empty depth map");
     (void)pose;  // the reference passes pose to its kernel but never reads it (src/TSDF/TSDFVolume.cu:316)
-    return launch_integrate(v, device_depth, width, height, inv_pose, k, kinv);
+    return launch_integrate(v, {device_depth, width, height, inv_pose, k, kinv});
 }
 
 // de-integration (include/tsdf_amd.h): the frame's voxels are the ones tsdf_integrate_device visits; the blend is inverted
@@ -608,7 +583,9 @@ int tsdf_deintegrate_device(tsdf_volume *v, const uint16_t *device_depth, uint32
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_deintegrate: empty depth map");
     TSDF_REQUIRE(v->weight_cap == 0, "tsdf_deintegrate: the volume has a weight cap (a saturated count is not a frame count: tsdf_volume_set_weight_cap(volume, 0) first)");
     (void)pose;
-    return launch_integrate(v, device_depth, width, height, inv_pose, k, kinv, nullptr, kIntBoth, nullptr, nullptr, true);
+    IntegrateFrame f{device_depth, width, height, inv_pose, k, kinv};
+    f.remove = true;
+    return launch_integrate(v, f);
 }
 
 int tsdf_integrate_device_tiles(tsdf_volume *v, const uint16_t *device_depth, uint32_t width, uint32_t height,
@@ -617,7 +594,9 @@ int tsdf_integrate_device_tiles(tsdf_volume *v, const uint16_t *device_depth, ui
     TSDF_REQUIRE(v && device_depth && inv_pose && k && kinv && device_tile_max, "tsdf_integrate: null argument");
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate: empty depth map");
     (void)pose;
-    return launch_integrate(v, device_depth, width, height, inv_pose, k, kinv, device_tile_max);
+    IntegrateFrame f{device_depth, width, height, inv_pose, k, kinv};
+    f.tile_max = device_tile_max;
+    return launch_integrate(v, f);
 }
 
 int tsdf_integrate_prepare_device_tiles(tsdf_volume *v, const uint16_t *device_depth, uint32_t width, uint32_t height,
@@ -626,7 +605,11 @@ int tsdf_integrate_prepare_device_tiles(tsdf_volume *v, const uint16_t *device_d
     TSDF_REQUIRE(v && device_depth && inv_pose && k && kinv && device_tile_max, "tsdf_integrate: null argument");
     TSDF_REQUIRE(width > 0 && height > 0, "tsdf_integrate: empty depth map");
     (void)pose;
-    return launch_integrate(v, device_depth, width, height, inv_pose, k, kinv, device_tile_max, kIntPrepare, (hipStream_t)hip_stream);
+    IntegrateFrame f{device_depth, width, height, inv_pose, k, kinv};
+    f.tile_max = device_tile_max;
+    f.phase = kIntPrepare;
+    f.prepare_stream = (hipStream_t)hip_stream;
+    return launch_integrate(v, f);
 }
 
 int tsdf_integrate_discard_prepared(tsdf_volume *v) {

@@ -18,8 +18,7 @@
 //     brick_cull_kernel leaves in memory); distance rows addressed as wave-uniform base + one 32-bit lane offset.
 #include <type_traits>
 
-#include "common.hpp"
-#include "integrate_grid.hpp"
+#include "band_pass.hpp"
 
 namespace tsdf {
 
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TSDF_PACKED
 #include "integrate_packed_body.hpp"
 }
 
-// The same walk plus the colour update of colour_integrate_kernel (colour.hip), made on the voxels the walk updates from the pixel and
+// The same walk plus the colour update of the band pass (band_pass.hpp, ColourBlend), made on the voxels the walk updates from the pixel and
 // the sdf it has formed: the same words as the separate pass, without a second projection of every listed voxel.  A kernel of its own
 // name, so that the plain kernels and their rocprof rows stay as they are.  rgb: the frame's 3 * width * height bytes, registered to
 // the depth image (any alignment).  (The COUNT instances spill two scalar registers -- the counter's address, kept in a vector lane

@@ -215,7 +215,7 @@
                 upd_[j] = update;
                 asm("v_min_f32 %0, %1, %2" : "=v"(tsdf_[j]) : "s"(g.trunc), "v"(sdf));   // (the plain instruction: fminf would first canonicalise both operands)
                 if constexpr (COLOUR) {
-                    // colour_integrate_kernel's set: the voxels updated, without free space -- on the sdf itself, not the blend's min(sdf, trunc).
+                    // band_pass_kernel's set: the voxels updated, without free space -- on the sdf itself, not the blend's min(sdf, trunc).
                     // Its pixel is the look-up's: d != 0 means the look-up was not clamped onto the ring, so (rx, ry) lies in the image.
                     // pix_ = kNoPixel outside the set (a vector register, not one more lane mask: the scalar file is full).
                     pix_[j] = kNoPixel;
@@ -324,13 +324,7 @@
             if constexpr (COLOUR) {
 #pragma unroll
                 for (int j = 0; j < kBatchZ; j++) {
-                    if (pix_[j] != kNoPixel) {   // colour.hip's blend: (old n + c + (n + 1) / 2) / (n + 1) per channel, n saturating at 255
-                        const uint32_t old = cw_[j], n = old >> 24, n1 = n + 1u, half = n1 >> 1;
-                        const uint32_t r = ((old & 0xFFu) * n + c0_[j] + half) / n1;
-                        const uint32_t gg = (((old >> 8) & 0xFFu) * n + c1_[j] + half) / n1;
-                        const uint32_t bb = (((old >> 16) & 0xFFu) * n + c2_[j] + half) / n1;
-                        *cword(o + j) = r | (gg << 8) | (bb << 16) | (min(n1, 255u) << 24);
-                    }
+                    if (pix_[j] != kNoPixel) *cword(o + j) = colour_blend(cw_[j], c0_[j], c1_[j], c2_[j]);
                 }
             }
         };

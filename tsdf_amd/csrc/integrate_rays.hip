@@ -24,7 +24,7 @@
 //     into both scratch words.
 #include <algorithm>
 
-#include "common.hpp"
+#include "band_pass.hpp"
 #include "field_sample.hpp"
 #include "rays_walk.hpp"
 
@@ -118,13 +118,7 @@ __global__ __launch_bounds__(256) void rays_colour_apply_kernel(uint32_t *__rest
         const uint32_t count = (uint32_t)(ab.x >> kRaysCountShift);
         const uint32_t mr = rays_colour_mean((uint32_t)ab.x, count);   // (the sum of R is below 2^31: the low dword holds it)
         const uint32_t mg = rays_colour_mean((uint32_t)(ab.y >> 32), count), mb = rays_colour_mean((uint32_t)ab.y, count);
-        // rule 12: the blend of colour_integrate_kernel (colour.hip)
-        const uint32_t old = colour[at];
-        const uint32_t n = old >> 24, n1 = n + 1u, half = n1 >> 1;
-        const uint32_t r = ((old & 0xFFu) * n + mr + half) / n1;
-        const uint32_t gg = (((old >> 8) & 0xFFu) * n + mg + half) / n1;
-        const uint32_t bb = (((old >> 16) & 0xFFu) * n + mb + half) / n1;
-        colour[at] = r | (gg << 8) | (bb << 16) | (min(n1, 255u) << 24);
+        colour[at] = colour_blend(colour[at], mr, mg, mb);   // rule 12: the blend of tsdf_integrate_colour (band_pass.hpp)
     }
 }
 

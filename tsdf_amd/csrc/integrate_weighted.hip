@@ -12,10 +12,6 @@
 
 namespace tsdf {
 
-// integrate.hip
-int integrate_weighted(tsdf_volume *v, const uint16_t *d_masked, const float *d_pweight, const uint8_t *d_rgb, uint32_t width, uint32_t height,
-                       const float inv_pose[16], const float k[9], const float kinv[9]);
-
 __global__ __launch_bounds__(256) void weight_mask_kernel(const uint16_t *__restrict__ depth, const float *__restrict__ pweight, const uint32_t n,
                                                           uint16_t *__restrict__ masked) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -136,7 +132,14 @@ int tsdf_integrate_weighted_device(tsdf_volume *v, const uint16_t *device_depth,
     TSDF_HIP(device_reserve(v->wdepth_buf, v->wdepth_cap, (size_t)n), "Couldn't allocate storage for the masked depth map");
     hipLaunchKernelGGL(weight_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, v->stream, device_depth, device_pixel_weight, n, v->wdepth_buf);
     TSDF_HIP(hipGetLastError(), "weight mask kernel failed");
-    return integrate_weighted(v, v->wdepth_buf, device_pixel_weight, device_rgb, width, height, inv_pose, k, kinv);
+    // the volume goes to fp32 weights first (it stays there until clear(), as after any widening), then the usual culling,
+    // integrate_weighted_kernel and -- with rgb -- the colour pass, all over the masked image
+    const int rc = weights_require_f32(v);
+    if (rc != TSDF_OK) return rc;
+    IntegrateFrame f{v->wdepth_buf, width, height, inv_pose, k, kinv};
+    f.pweight = device_pixel_weight;
+    f.rgb = device_rgb;
+    return launch_integrate(v, f);
 }
 
 int tsdf_integrate_weighted(tsdf_volume *v, const uint16_t *host_depth, const float *host_pixel_weight, const uint8_t *host_rgb, uint32_t width,

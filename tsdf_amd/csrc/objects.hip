@@ -6,13 +6,12 @@
 //                           count by popcount over the 64 chunks a wave walks, one integer atomic per workgroup that has any
 // The list and the objects are voxel_set.hpp's, with the policy "a listed neighbour of the same class is adjacent".
 // Lookup: a lane per point.
-//   objects_lookup_kernel   the sampler's voxel (class_voxel.hpp) -> its list index -> its label -> the label's row, or NONE
+//   objects_lookup_kernel   the sampler's voxel (point_voxel_at, voxel_grid.hpp) -> its list index -> its label -> the label's row, or NONE
 // Every result is a set, an integer sum, a minimum or a maximum: two runs give the same bytes whatever order the waves run in.  No float
 // atomics, no lane waits for another, and every loop has a stated bound.
 #include <algorithm>
 #include <new>
 
-#include "class_voxel.hpp"
 #include "common.hpp"
 #include "voxel_set.hpp"
 
@@ -63,7 +62,7 @@ __global__ __launch_bounds__(256) void objects_flag_kernel(const uint32_t *__res
 
 // what a lookup reads of the handle; labels, row_mask and row_base are touched only behind a set mask bit, that is with a list
 struct ObjectsView {
-    Geom g;   // of the last tsdf_volume_find_objects: every plane resident, so class_voxel_at's place is the voxel id
+    Geom g;   // of the last tsdf_volume_find_objects: every plane resident, so point_voxel_at's place is the voxel id
     const uint64_t *mask;
     const uint32_t *base, *labels;
     const uint64_t *row_mask;
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(256) void objects_lookup_kernel(const ObjectsView o
     if (i >= n) return;
     uint32_t row = TSDF_OBJECT_NONE;
     size_t at;
-    if (class_voxel_at(o.g, points + 3 * i, at) && mask_bit(o.mask, (uint32_t)at)) {
+    if (point_voxel_at(o.g, points + 3 * i, at) && mask_bit(o.mask, (uint32_t)at)) {
         const uint32_t label = o.labels[compact_index(o.mask, o.base, (uint32_t)at)];
         if (mask_bit(o.row_mask, label)) row = compact_index(o.row_mask, o.row_base, label);
     }

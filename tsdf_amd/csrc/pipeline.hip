@@ -158,9 +158,13 @@ struct tsdf_tracker {
 
 using namespace tsdf;
 
-namespace tsdf {
-int integrate_with_colour(tsdf_volume *v, const uint16_t *d_depth, const uint8_t *d_rgb, uint32_t width, uint32_t height,
-                          const float inv_pose[16], const float k[9], const float kinv[9], const uint16_t *tile_max);   // integrate.hip
+// a coloured step's integrate: tsdf_integrate_device_tiles (the filter's tile maxima) with the colour update of tsdf_integrate_colour
+static int integrate_colour_tiles(tsdf_volume *v, const uint16_t *filtered, const uint8_t *rgb, uint32_t width, uint32_t height,
+                                  const tsdf_camera_matrices *cam, const uint16_t *tile_max) {
+    IntegrateFrame f{filtered, width, height, cam->inv_pose, cam->k, cam->kinv};
+    f.tile_max = tile_max;
+    f.rgb = rgb;
+    return launch_integrate(v, f);
 }
 
 static int run_filter(tsdf_pipeline *p, const uint16_t *depth, int b, hipStream_t s) {
@@ -560,7 +564,7 @@ static int pipeline_step(tsdf_pipeline *p, const uint16_t *device_depth, const u
     p->ahead_depth = nullptr;
     if (rgb)   // (the colour update reads the brick list the next frame's culling rewrites: when it is a pass of its own it is
                // enqueued in there too, so the `done` event below comes after it)
-        rc = integrate_with_colour(p->volume, p->filtered[b], rgb, W, H, cam->inv_pose, cam->k, cam->kinv, p->tile_max[b]);
+        rc = integrate_colour_tiles(p->volume, p->filtered[b], rgb, W, H, cam, p->tile_max[b]);
     else
         rc = tsdf_integrate_device_tiles(p->volume, p->filtered[b], W, H, cam->pose, cam->inv_pose, cam->k, cam->kinv, p->tile_max[b]);
     if (rc != TSDF_OK) return rc;
@@ -862,7 +866,7 @@ static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera
             rc = tsdf_integrate_weighted_device(t->volume, t->filtered[b], t->pixel_weights, rgb, t->width, t->height, camera->pose, camera->inv_pose,
                                                 camera->k, camera->kinv);
     } else if (rgb)
-        rc = integrate_with_colour(t->volume, t->filtered[b], rgb, t->width, t->height, camera->inv_pose, camera->k, camera->kinv, t->tile_max[b]);
+        rc = integrate_colour_tiles(t->volume, t->filtered[b], rgb, t->width, t->height, camera, t->tile_max[b]);
     else
         rc = tsdf_integrate_device_tiles(t->volume, t->filtered[b], t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
                                          t->tile_max[b]);
