@@ -1392,6 +1392,116 @@ int tsdf_volume_view_gain(const tsdf_volume *volume, tsdf_explorer *explorer, ui
                           const float *host_directions, const float *host_t_max, uint32_t flags, uint32_t *host_unknown,
                           uint32_t *host_free, uint8_t *host_stop, uint64_t *host_gain);
 
+/* ---- reachability (no reference counterpart: the reference's volume is asked about its surface only) ------------------------------- */
+/* Can I get there, how far is it, and along which voxels?  The travel cost from seed points through free space to every voxel, the
+ * voxel path from any goal back to a seed, and the nearest voxel of every frontier cluster -- what a robot asks between "which frontier?"
+ * (group "exploration") and "go".  Opt-in by being called: no other entry point, launch or result changes; nothing of a volume, an ESDF
+ * or an explorer is written.  Results are integers and sets only (unique values, whatever computes them); two runs give the same bytes.
+ *   1. Grid, ids and voxel states are those of "exploration" rule 1: voxel (x, y, z) has id (z * Y + y) * X + x (uint32: more than
+ *      2^32 - 1 voxels are refused), and UNKNOWN / OCCUPIED / FREE are as defined there.
+ *   2. TRAVERSABLE(v): FREE(v) -- with TSDF_REACH_THROUGH_UNKNOWN also UNKNOWN(v) -- and, if an ESDF handle is given, its value at v
+ *      satisfies e(v) >= clearance (an fp32 compare: NaN fails, so a planner that is optimistic about unseen space passes an ESDF
+ *      computed with TSDF_ESDF_FILL_UNKNOWN).  Without an ESDF handle clearance must be 0.
+ *   3. Steps.  Two voxels u != v are neighbours when their coordinates differ by at most 1 on every axis; the step is a face, edge or
+ *      corner step for a difference on 1, 2 or 3 axes.  At connectivity 6 only face steps exist, at 26 all three.  A step u <-> v is
+ *      ADMISSIBLE iff every voxel w with w_k in {u_k, v_k} on each axis k is TRAVERSABLE -- 2, 4 or 8 voxels, all inside the grid by
+ *      construction: no corner cutting, a diagonal never squeezes between two blocked voxels.  The graph is undirected.  A step costs
+ *      TSDF_REACH_COST_FACE 10, TSDF_REACH_COST_EDGE 14 or TSDF_REACH_COST_CORNER 17: tenths of a voxel step in the 10-14-17 chamfer
+ *      metric.  For isotropic voxels cost * voxel_size / 10 is a length in mm.  Its error, derived: a path's cost is its own polyline's
+ *      length with 14 for 10 sqrt 2 and 17 for 10 sqrt 3, so cost / 10 lies in [17 / (10 sqrt 3), 1] = [0.9815, 1] times that length in
+ *      voxels; and a straight run in free space along a direction with sorted components a >= b >= c >= 0 costs 10 a + 4 b + 3 c against
+ *      10 sqrt(a^2 + b^2 + c^2), a ratio between 0.9815 (at (1, 1, 1); the minimum over the cone is on an extreme ray: 1, 0.98995, 0.9815)
+ *      and sqrt(1 + 0.16 + 0.09) = 1.1180 (Cauchy-Schwarz, at (1, 0.4, 0.3)): -1.9 % .. +11.8 % of the Euclidean distance.  For
+ *      anisotropic voxels the cost is a step count only.
+ *   4. Seeds: n world points (3 n floats) in the frame of view-gain rays ("exploration" rule 4b).  Seed voxel i_k =
+ *      floorf((p_k - offset_k) / vs_k) with the volume's CURRENT offset, every fp32 operation rounded on its own.  A seed is ignored if a
+ *      coordinate is not finite, an index is off the grid, or its voxel is not TRAVERSABLE.  n == 0, or all seeds ignored, is TSDF_OK:
+ *      nothing is then reached.
+ *   5. Cost field.  D(v) = the minimum over all paths of admissible steps from any seed voxel to v of the sum of the step costs; D = 0 at
+ *      seed voxels.  cap = max_cost if nonzero, else 0xFFFFFFFE.  The output, one uint32 per voxel id, is D(v) if v is reachable and
+ *      D(v) <= cap, otherwise TSDF_REACH_UNREACHED (0xFFFFFFFF).  The cap never changes a value at or below it.
+ *   6. tsdf_reach_info: sizes, voxel sizes and offset as tsdf_explorer_info has them; connectivity, flags, clearance and max_cost as
+ *      given; n_traversable; n_reached (voxels with an output other than UNREACHED); n_seed_voxels (voxels with output 0);
+ *      max_cost_reached (the largest output other than UNREACHED, 0 if none); rounds.  All are unique integers except rounds: a
+ *      diagnostic of the implementation that may differ from run to run and is excluded from every byte comparison.
+ *   7. Lookup: n world points, each resolved to a voxel by rule 4's expression with the handle's remembered geometry; the output is
+ *      that voxel's value, UNREACHED for a coordinate that is not finite or an index off the grid.  n == 0 launches nothing.
+ *   8. Paths: n goal points, each mapped to a voxel as in rule 7, and a row capacity max_len.  For goal i: if its voxel is off the
+ *      grid or UNREACHED, length[i] = 0.  Otherwise, starting at v = the goal voxel, while out(v) != 0, move to the FIRST neighbour u such
+ *      that the step is admissible and out(u) + cost(u, v) == out(v), in the fixed neighbour order dz = -1, 0, 1 outermost, then dy,
+ *      then dx innermost, (0, 0, 0) skipped, at connectivity 6 only the face offsets.  length[i] is the number of voxels of the whole
+ *      path, goal and seed voxel included; the first min(length[i], max_len) ids, goal first, are written to row i (max_len words a
+ *      row) and the rest of the row is left as it was.  Such a neighbour always exists for a reached voxel that is no seed, and the
+ *      walk takes at most out(goal) / 10 steps.  The connectivity is that of the computation.
+ *   9. Ranking frontier clusters: an explorer handle that has been clustered (tsdf_explorer_cluster_frontiers) and whose geometry
+ *      equals the reach handle's.  For each row of its cluster table, in table order, one 16-byte tsdf_reach_cluster {label, cost,
+ *      voxel, reserved = 0}: (cost, voxel) is the lexicographic minimum over the cluster's member voxels of (out(id), id), and
+ *      (UNREACHED, 0xFFFFFFFF) when no member was reached.  What a next-best-view loop sorts by; one paths call on the centres of the
+ *      `voxel`s then gives the routes.
+ *  10. The handle (tsdf_reach_create, on the current device) owns the cost array (4 bytes a voxel) and its scratch, keeps them between
+ *      calls and only grows them: a warm second computation allocates nothing and leaves tsdf_reach_scratch_bytes unchanged.  Scratch:
+ *      1 bit a voxel (the traversable mask), 8 bytes per brick of 8^3 voxels, 8 bytes per ranked cluster row, 160 bytes of counters.
+ *      It snapshots the geometry, so lookup, paths and ranking need no volume.  A handle is used by one thread at a time.
+ *      tsdf_reach_destroy(NULL) is ignored.
+ *  11. Stream order: tsdf_volume_compute_reach[_device] runs on the volume's stream -- a tsdf_volume_compute_esdf enqueued before it is
+ *      therefore ordered -- and returns when the field is final (it reads a convergence word anyway).  The _device lookup / paths / rank
+ *      calls order their stream behind the handle's event; ranking waits for the explorer's pending work first.  Host variants block.
+ *  12. Refused (TSDF_ERR_INVALID, with a message naming the entry point, before any device work where possible): NULL handle or volume;
+ *      NULL seeds with n > 0; a Z-slab volume; a materialised deformation-node array; connectivity other than 6 or 26; unknown flags;
+ *      a clearance that is negative, not finite, or nonzero without an ESDF; an ESDF never computed, or one whose sizes, voxel sizes or
+ *      offset are not the volume's; lookup / paths / rank / download on a handle never computed; max_len == 0 with n > 0; NULL outputs;
+ *      an explorer that is not clustered or has another geometry.  A computation that has not converged after n_traversable + 1 rounds
+ *      -- it cannot -- fails with TSDF_ERR_DEVICE rather than loop.
+ *   Out of scope: Z-slabs, incremental updates, costs other than the chamfer metric (a clearance-weighted cost), and planning itself:
+ *     this is the cost field and the read-out of voxel paths, not a trajectory planner. */
+typedef struct tsdf_reach tsdf_reach;
+#define TSDF_REACH_THROUGH_UNKNOWN 1u
+#define TSDF_REACH_UNREACHED 0xFFFFFFFFu
+#define TSDF_REACH_COST_FACE 10u
+#define TSDF_REACH_COST_EDGE 14u
+#define TSDF_REACH_COST_CORNER 17u
+typedef struct tsdf_reach_info {
+    uint32_t size[3];
+    uint32_t connectivity;
+    float voxel_size[3];
+    float offset[3];         /* the volume's current offset when computed */
+    uint32_t flags;
+    float clearance;
+    uint32_t max_cost;
+    uint32_t max_cost_reached;
+    uint64_t n_traversable, n_reached, n_seed_voxels;
+    uint64_t rounds;         /* a diagnostic: not a unique value */
+} tsdf_reach_info;
+typedef struct tsdf_reach_cluster {
+    uint32_t label, cost, voxel, reserved;
+} tsdf_reach_cluster;
+int tsdf_reach_create(tsdf_reach **out);   /* on the current device */
+void tsdf_reach_destroy(tsdf_reach *reach);
+/* n seeds (3 floats each) on the host; esdf may be NULL (clearance then 0); max_cost 0: no cap.  Blocking. */
+int tsdf_volume_compute_reach(const tsdf_volume *volume, uint64_t n, const float *host_seeds, uint32_t connectivity,
+                              const tsdf_esdf *esdf, float clearance, uint32_t max_cost, uint32_t flags, tsdf_reach *reach);
+/* The same with the seeds in device memory. */
+int tsdf_volume_compute_reach_device(const tsdf_volume *volume, uint64_t n, const float *device_seeds, uint32_t connectivity,
+                                     const tsdf_esdf *esdf, float clearance, uint32_t max_cost, uint32_t flags, tsdf_reach *reach);
+int tsdf_reach_get_info(const tsdf_reach *reach, tsdf_reach_info *info);
+/* The device array of the last computation (NULL before the first); valid until the next computation into the handle. */
+int tsdf_reach_buffer(const tsdf_reach *reach, const uint32_t **device_costs);
+/* Blocking copy to size[0] * size[1] * size[2] words. */
+int tsdf_reach_download(const tsdf_reach *reach, uint32_t *host_costs);
+/* Device bytes the handle holds besides the cost array. */
+int tsdf_reach_scratch_bytes(const tsdf_reach *reach, uint64_t *bytes);
+/* n points (3 floats each) -> n costs. */
+int tsdf_reach_lookup_device(const tsdf_reach *reach, uint64_t n, const float *device_points, uint32_t *device_costs, void *hip_stream);
+int tsdf_reach_lookup(const tsdf_reach *reach, uint64_t n, const float *host_points, uint32_t *host_costs);
+/* n goals (3 floats each) -> n lengths and n rows of max_len voxel ids. */
+int tsdf_reach_paths_device(const tsdf_reach *reach, uint64_t n, const float *device_goals, uint32_t max_len, uint32_t *device_lengths,
+                            uint32_t *device_rows, void *hip_stream);
+int tsdf_reach_paths(const tsdf_reach *reach, uint64_t n, const float *host_goals, uint32_t max_len, uint32_t *host_lengths,
+                     uint32_t *host_rows);
+/* One row per row of the explorer's cluster table (tsdf_explorer_info.n_listed_clusters). */
+int tsdf_reach_rank_frontiers_device(tsdf_reach *reach, const tsdf_explorer *explorer, tsdf_reach_cluster *device_rows, void *hip_stream);
+int tsdf_reach_rank_frontiers(tsdf_reach *reach, const tsdf_explorer *explorer, tsdf_reach_cluster *host_rows);
+
 /* ---- class objects (no reference counterpart; the per-object maps of Voxblox++, Kimera and SemanticFusion) -------------------------- */
 /* Which objects are in the scene, where is each, how big is it, and which object did this ray or pixel hit?  The connected pieces of
  * each fused class (group "class fusion"), on the device.  Opt-in by being called: no other entry point, launch or result changes.

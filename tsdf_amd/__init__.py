@@ -6,4 +6,5 @@ from .api import (TSDFVolume, GPURaycaster, BilateralFilter, Camera, ICPOdometry
                   FieldAligner, depth_to_points, depth_to_points_device, Mesh, ESDF, Explorer, pixel_rays, Snapshot, label_components, label_components_device, simplify_mesh,
                   simplify_mesh_device, smooth_mesh, smooth_mesh_device, vertex_normals, rgb_to_intensity, rgb_to_intensity_device,
                   depth_weights, depth_weights_device, WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE, CLASS_VOID, Objects, OBJECT_DTYPE,
-                  OBJECT_NONE)
+                  OBJECT_NONE, Reach, REACH_CLUSTER_DTYPE, REACH_UNREACHED, REACH_COST_FACE, REACH_COST_EDGE, REACH_COST_CORNER,
+                  TSDF_REACH_THROUGH_UNKNOWN)

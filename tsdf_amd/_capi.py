@@ -19,6 +19,9 @@ TSDF_CLASS_VOID = 0xFFFF
 TSDF_SMOOTH_PIN_BOUNDARY, TSDF_SMOOTH_NORMALS = 1, 2
 TSDF_ESDF_FILL_UNKNOWN = 1
 TSDF_GAIN_KEEP_MASK = 1
+TSDF_REACH_THROUGH_UNKNOWN = 1
+TSDF_REACH_UNREACHED = 0xFFFFFFFF
+TSDF_REACH_COST_FACE, TSDF_REACH_COST_EDGE, TSDF_REACH_COST_CORNER = 10, 14, 17
 TSDF_OBJECT_NONE = 0xFFFFFFFF
 TSDF_SCENE_FLOW_DEFORMED = 1
 TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
@@ -72,6 +75,18 @@ class ExplorerInfo(C.Structure):
 class FrontierCluster(C.Structure):
     """struct tsdf_frontier_cluster (include/tsdf_amd.h): 56 bytes, sum at offset 32."""
     _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("sum", C.c_uint64 * 3)]
+
+
+class ReachInfo(C.Structure):
+    """struct tsdf_reach_info (include/tsdf_amd.h): 88 bytes, n_traversable at offset 56, rounds at 80."""
+    _fields_ = [("size", C.c_uint32 * 3), ("connectivity", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
+                ("flags", C.c_uint32), ("clearance", C.c_float), ("max_cost", C.c_uint32), ("max_cost_reached", C.c_uint32),
+                ("n_traversable", C.c_uint64), ("n_reached", C.c_uint64), ("n_seed_voxels", C.c_uint64), ("rounds", C.c_uint64)]
+
+
+class ReachCluster(C.Structure):
+    """struct tsdf_reach_cluster (include/tsdf_amd.h): 16 bytes."""
+    _fields_ = [("label", C.c_uint32), ("cost", C.c_uint32), ("voxel", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ObjectsInfo(C.Structure):
@@ -301,6 +316,20 @@ _SIGS = {
     "tsdf_explorer_cluster_download": (_i, [_vp, _vp, _vp]),
     "tsdf_volume_view_gain_device": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "tsdf_volume_view_gain": (_i, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "tsdf_reach_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_reach_destroy": (None, [_vp]),
+    "tsdf_volume_compute_reach": (_i, [_vp, C.c_uint64, _vp, _u32, _vp, _f, _u32, _u32, _vp]),
+    "tsdf_volume_compute_reach_device": (_i, [_vp, C.c_uint64, _vp, _u32, _vp, _f, _u32, _u32, _vp]),
+    "tsdf_reach_get_info": (_i, [_vp, C.POINTER(ReachInfo)]),
+    "tsdf_reach_buffer": (_i, [_vp, C.POINTER(_vp)]),
+    "tsdf_reach_download": (_i, [_vp, _vp]),
+    "tsdf_reach_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_reach_lookup_device": (_i, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    "tsdf_reach_lookup": (_i, [_vp, C.c_uint64, _vp, _vp]),
+    "tsdf_reach_paths_device": (_i, [_vp, C.c_uint64, _vp, _u32, _vp, _vp, _vp]),
+    "tsdf_reach_paths": (_i, [_vp, C.c_uint64, _vp, _u32, _vp, _vp]),
+    "tsdf_reach_rank_frontiers_device": (_i, [_vp, _vp, _vp, _vp]),
+    "tsdf_reach_rank_frontiers": (_i, [_vp, _vp, _vp]),
     "tsdf_objects_create": (_i, [C.POINTER(_vp)]),
     "tsdf_objects_destroy": (None, [_vp]),
     "tsdf_volume_find_objects": (_i, [_vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp]),

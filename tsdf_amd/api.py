@@ -647,6 +647,20 @@ class TSDFVolume:
                 explorer.close()
         return int(g.value), u[:n], f[:n], s[:n]
 
+    # ---- reachability (include/tsdf_amd.h, "reachability"; not in the reference's class)
+    def reach(self, seeds, connectivity=26, esdf=None, clearance=0.0, max_cost=0, through_unknown=False, into=None):
+        """The travel cost from `seeds` ((n, 3) float32 world points, mm) to every voxel through free voxels (through_unknown: unobserved
+        ones too) whose ESDF value is at least `clearance` (esdf: an ESDF of this volume; None: no clearance), in steps of 10 / 14 / 17
+        for face / edge / corner neighbours (connectivity 6: faces only) that never cut a corner; max_cost: values above it are
+        REACH_UNREACHED (0: no cap).  It stays on the device; the call returns when the field is final.  `into`: a Reach to reuse -- its
+        arrays are kept and only grow.  Returns the Reach."""
+        p = np.ascontiguousarray(seeds, dtype=np.float32).reshape(-1, 3)
+        reach = Reach() if into is None else into
+        check(lib.tsdf_volume_compute_reach(self._h, len(p), p.ctypes.data if len(p) else None, int(connectivity),
+                                            esdf._h if esdf is not None else None, float(clearance), int(max_cost),
+                                            _capi.TSDF_REACH_THROUGH_UNKNOWN if through_unknown else 0, reach._h))
+        return reach
+
     # ---- class objects (include/tsdf_amd.h, "class objects"; not in the reference's class)
     def find_objects(self, min_votes=1, classes=None, connectivity=26, min_size=1, into=None):
         """The connected pieces of each fused class (tsdf_volume_find_objects): the voxels whose word has at least max(min_votes, 1)
@@ -1485,6 +1499,115 @@ class Explorer:
         """Device bytes the handle holds besides the list, the labels and the table."""
         n = C.c_uint64(0)
         check(lib.tsdf_explorer_scratch_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+
+#: one row of Reach.rank: struct tsdf_reach_cluster (16 bytes)
+REACH_CLUSTER_DTYPE = np.dtype([("label", np.uint32), ("cost", np.uint32), ("voxel", np.uint32), ("reserved", np.uint32)])
+#: the cost of a voxel that no admissible path reaches, or none within max_cost
+REACH_UNREACHED = _capi.TSDF_REACH_UNREACHED
+REACH_COST_FACE, REACH_COST_EDGE, REACH_COST_CORNER = _capi.TSDF_REACH_COST_FACE, _capi.TSDF_REACH_COST_EDGE, _capi.TSDF_REACH_COST_CORNER
+TSDF_REACH_THROUGH_UNKNOWN = _capi.TSDF_REACH_THROUGH_UNKNOWN
+
+
+class Reach:
+    """tsdf_reach (include/tsdf_amd.h, "reachability"): the travel cost from a set of seeds to every voxel of a volume
+    (TSDFVolume.reach(into=reach)), on the device, with the geometry it belongs to.  Lookup, paths and ranking need no volume."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        check(lib.tsdf_reach_create(C.byref(self._h)))
+
+    def close(self):
+        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
+            lib.tsdf_reach_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def info(self):
+        """tsdf_reach_info: size, connectivity, voxel_size, offset, flags, clearance, max_cost, max_cost_reached, n_traversable,
+        n_reached, n_seed_voxels, rounds (a diagnostic: it may differ from run to run)."""
+        i = _capi.ReachInfo()
+        check(lib.tsdf_reach_get_info(self._h, C.byref(i)))
+        return i
+
+    @property
+    def costs(self):
+        """(X * Y * Z,) uint32 by voxel id (z * Y + y) * X + x: the cost, REACH_UNREACHED where there is none; a blocking download."""
+        sx, sy, sz = (int(v) for v in self.info.size)
+        out = np.empty(sx * sy * sz + 1, np.uint32)   # (one element more: the pointer of an empty array may be null)
+        check(lib.tsdf_reach_download(self._h, out.ctypes.data))
+        return out[:-1]
+
+    def device_buffer(self):
+        """The raw device pointer of the cost array (0 before the first computation); valid until the next computation into this handle."""
+        p = C.c_void_p()
+        check(lib.tsdf_reach_buffer(self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def lookup_device(self, n, points_ptr, costs_ptr, stream=None):
+        """n points (3 float32 each, device) -> n uint32 costs (device), on `stream` (default: the null stream)."""
+        ptr = lambda p: C.c_void_p(int(p)) if p else None
+        check(lib.tsdf_reach_lookup_device(self._h, int(n), ptr(points_ptr), ptr(costs_ptr), C.c_void_p(int(stream) if stream else 0)))
+
+    def lookup(self, points):
+        """(n, 3) float32 world points (mm) -> (n,) uint32: the cost of the voxel each lies in, REACH_UNREACHED off the grid."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        out = np.empty(n + 1, np.uint32)
+        check(lib.tsdf_reach_lookup(self._h, n, p.ctypes.data if n else None, out.ctypes.data))
+        return out[:n]
+
+    def paths(self, goals, max_len=None, rows=None):
+        """(n, 3) float32 goal points -> the voxel path of each back to a seed, goal first.  max_len None: a list of n uint32 id arrays,
+        each as long as its path (empty for a goal off the grid or not reached).  With max_len: (lengths (n,) uint32, rows (n, max_len)
+        uint32) -- a length is that of the whole path even where the row holds only its first max_len ids; `rows`: the array to write
+        into (what a path does not fill is left as it was; default: filled with REACH_UNREACHED)."""
+        p = np.ascontiguousarray(goals, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        want = 1 if max_len is None else int(max_len)
+        while True:
+            lengths = np.zeros(n + 1, np.uint32)
+            if rows is not None and max_len is not None:
+                table = np.ascontiguousarray(rows, dtype=np.uint32).reshape(n, want)
+            else:
+                table = np.full((n, want), REACH_UNREACHED, np.uint32)
+            buf = table if table.size else np.zeros(1, np.uint32)
+            check(lib.tsdf_reach_paths(self._h, n, p.ctypes.data if n else None, want, lengths.ctypes.data, buf.ctypes.data))
+            lengths = lengths[:n]
+            if max_len is not None:
+                return lengths, table
+            longest = int(lengths.max()) if n else 0
+            if longest <= want:
+                return [table[i, :int(lengths[i])].copy() for i in range(n)]
+            want = longest   # (a second call with rows as long as the longest path)
+
+    def rank(self, explorer):
+        """(n_listed_clusters,) REACH_CLUSTER_DTYPE rows in the order of explorer.clusters: label, cost and voxel -- the smallest (cost,
+        voxel id) among the cluster's voxels; (REACH_UNREACHED, 0xFFFFFFFF) where none was reached."""
+        out = np.zeros(int(explorer.info.n_listed_clusters) + 1, REACH_CLUSTER_DTYPE)
+        check(lib.tsdf_reach_rank_frontiers(self._h, explorer._h, out.ctypes.data))
+        return out[:-1]
+
+    def rank_device(self, explorer, rows_ptr, stream=None):
+        """The same into n_listed_clusters 16-byte rows on the device, on `stream`."""
+        check(lib.tsdf_reach_rank_frontiers_device(self._h, explorer._h, C.c_void_p(int(rows_ptr)) if rows_ptr else None,
+                                                   C.c_void_p(int(stream) if stream else 0)))
+
+    def voxel_centres(self, ids):
+        """(n,) voxel ids -> (n, 3) float32 world centres (mm), offset + (coordinate + 0.5) * voxel_size: what paths() takes as goals."""
+        i = self.info
+        vs, off = np.array(i.voxel_size, np.float32), np.array(i.offset, np.float32)
+        c = _voxel_coordinates(np.asarray(ids, np.uint32).reshape(-1), i.size)
+        return ((c.astype(np.float32) + np.float32(0.5)) * vs + off).astype(np.float32)
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides the cost array."""
+        n = C.c_uint64(0)
+        check(lib.tsdf_reach_scratch_bytes(self._h, C.byref(n)))
         return int(n.value)
 
 

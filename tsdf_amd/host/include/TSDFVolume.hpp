@@ -23,6 +23,9 @@ struct tsdf_mesh;    // indexed-mesh handle (include/tsdf_amd.h)
 struct tsdf_snapshot;  // sparse-snapshot handle (include/tsdf_amd.h)
 struct tsdf_explorer;  // exploration handle (include/tsdf_amd.h)
 struct tsdf_frontier_cluster;  // a row of its cluster table (include/tsdf_amd.h)
+struct tsdf_reach;          // reachability handle (include/tsdf_amd.h)
+struct tsdf_reach_info;     // what it reports of its last computation (include/tsdf_amd.h)
+struct tsdf_reach_cluster;  // a row of its ranking of frontier clusters (include/tsdf_amd.h)
 struct tsdf_objects;       // class-objects handle (include/tsdf_amd.h)
 struct tsdf_class_object;  // a row of its table (include/tsdf_amd.h)
 
@@ -259,6 +262,38 @@ public:
     uint64_t view_gain(Explorer &explorer, const std::vector<float3> &origins, const std::vector<float3> &directions,
                        const std::vector<float> *t_max = nullptr, bool keep = false, std::vector<uint32_t> *unknown = nullptr,
                        std::vector<uint32_t> *free_voxels = nullptr, std::vector<uint8_t> *stop = nullptr) const;
+
+    // Reachability (include/tsdf_amd.h, "reachability"; not in the reference's class): the travel cost from seed points through free
+    // voxels to every voxel, the voxel paths back to the seeds and the nearest voxel of every frontier cluster, in a handle that keeps
+    // its device arrays between calls and needs no volume once computed.
+    class Reach {
+    public:
+        Reach();    // throws std::invalid_argument / exits like every device failure when the handle cannot be made
+        ~Reach();
+        Reach(const Reach &) = delete;
+        Reach &operator=(const Reach &) = delete;
+        inline tsdf_reach *handle() const { return m_handle; }
+        // tsdf_reach_info of the last computation (rounds is a diagnostic, not a unique value)
+        tsdf_reach_info info() const;
+        // the cost per voxel id (z * Y + y) * X + x, TSDF_REACH_UNREACHED where there is none; a blocking download
+        std::vector<uint32_t> costs() const;
+        // the cost of the voxel each world point lies in, TSDF_REACH_UNREACHED off the grid
+        std::vector<uint32_t> lookup(const std::vector<float3> &points) const;
+        // The voxel path of each goal back to a seed, goal first, at most max_len ids a path (0: every path whole); `lengths` (may be
+        // null) takes the lengths of the whole paths.  A goal off the grid or not reached has an empty path.
+        std::vector<std::vector<uint32_t>> paths(const std::vector<float3> &goals, uint32_t max_len = 0, std::vector<uint32_t> *lengths = nullptr) const;
+        // one row per row of explorer.clusters(): the smallest (cost, voxel id) among the cluster's voxels.  Throws std::invalid_argument
+        // for an explorer that is not clustered or holds another geometry.
+        std::vector<tsdf_reach_cluster> rank(const Explorer &explorer);
+
+    private:
+        tsdf_reach *m_handle;
+    };
+    // The cost field of this volume from `seeds` (world mm) into `into` (nothing of the volume is written): connectivity 6 or 26, esdf
+    // (may be null) and clearance as TRAVERSABLE takes them, max_cost 0 for no cap, flags TSDF_REACH_THROUGH_UNKNOWN or 0.  Returns when
+    // the field is final.  Throws std::invalid_argument on the refusals.
+    void reach(const std::vector<float3> &seeds, uint32_t connectivity, const tsdf_esdf *esdf, float clearance, uint32_t max_cost,
+               uint32_t flags, Reach &into) const;
 
     // Class objects (include/tsdf_amd.h, "class objects"; not in the reference's class): the connected pieces of each fused class and
     // their table, in a handle that keeps its device arrays between calls.

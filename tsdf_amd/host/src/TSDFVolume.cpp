@@ -260,6 +260,68 @@ uint64_t TSDFVolume::view_gain(Explorer &explorer, const std::vector<float3> &or
     return gain;
 }
 
+TSDFVolume::Reach::Reach() : m_handle{nullptr} { check(tsdf_reach_create(&m_handle), "Couldn't create the reach handle"); }
+
+TSDFVolume::Reach::~Reach() { tsdf_reach_destroy(m_handle); }
+
+tsdf_reach_info TSDFVolume::Reach::info() const {
+    tsdf_reach_info info;
+    check(tsdf_reach_get_info(m_handle, &info), "Couldn't query the reach handle");
+    return info;
+}
+
+std::vector<uint32_t> TSDFVolume::Reach::costs() const {
+    const tsdf_reach_info i = info();
+    // (one element more than needed: data() of an empty vector may be null)
+    std::vector<uint32_t> out((size_t)i.size[0] * i.size[1] * i.size[2] + 1, 0u);
+    check(tsdf_reach_download(m_handle, out.data()), "Couldn't download the costs");
+    out.pop_back();
+    return out;
+}
+
+std::vector<uint32_t> TSDFVolume::Reach::lookup(const std::vector<float3> &points) const {
+    static_assert(sizeof(float3) == 3 * sizeof(float), "float3 must be 3 packed floats");
+    const size_t n = points.size();
+    std::vector<uint32_t> out(n + 1, 0u);
+    check(tsdf_reach_lookup(m_handle, n, reinterpret_cast<const float *>(points.data()), out.data()), "Couldn't look the costs up");
+    out.resize(n);
+    return out;
+}
+
+std::vector<std::vector<uint32_t>> TSDFVolume::Reach::paths(const std::vector<float3> &goals, uint32_t max_len, std::vector<uint32_t> *lengths) const {
+    const size_t n = goals.size();
+    std::vector<uint32_t> len(n + 1, 0u), rows;
+    uint32_t row = max_len ? max_len : 1u;
+    for (;;) {   // at most twice: rows of one first when every path is wanted whole, then rows as long as the longest
+        rows.assign(n * row + 1, TSDF_REACH_UNREACHED);
+        check(tsdf_reach_paths(m_handle, n, reinterpret_cast<const float *>(goals.data()), row, len.data(), rows.data()), "Couldn't walk the paths");
+        uint32_t longest = 0;
+        for (size_t i = 0; i < n; i++) longest = std::max(longest, len[i]);
+        if (max_len || longest <= row) break;
+        row = longest;
+    }
+    std::vector<std::vector<uint32_t>> out(n);
+    for (size_t i = 0; i < n; i++) out[i].assign(rows.begin() + i * row, rows.begin() + i * row + std::min(len[i], row));
+    if (lengths) lengths->assign(len.begin(), len.begin() + n);
+    return out;
+}
+
+std::vector<tsdf_reach_cluster> TSDFVolume::Reach::rank(const Explorer &explorer) {
+    tsdf_explorer_info ei;
+    check(tsdf_explorer_get_info(explorer.handle(), &ei), "Couldn't query the explorer");
+    std::vector<tsdf_reach_cluster> rows((size_t)ei.n_listed_clusters + 1, tsdf_reach_cluster());
+    check(tsdf_reach_rank_frontiers(m_handle, explorer.handle(), rows.data()), "Couldn't rank the frontier clusters");
+    rows.pop_back();
+    return rows;
+}
+
+void TSDFVolume::reach(const std::vector<float3> &seeds, uint32_t connectivity, const tsdf_esdf *esdf, float clearance, uint32_t max_cost,
+                       uint32_t flags, Reach &into) const {
+    check(tsdf_volume_compute_reach(m_handle, seeds.size(), reinterpret_cast<const float *>(seeds.data()), connectivity, esdf, clearance, max_cost,
+                                    flags, into.handle()),
+          "Couldn't compute the reach");
+}
+
 TSDFVolume::Objects::Objects() : m_handle{nullptr} { check(tsdf_objects_create(&m_handle), "Couldn't create the objects handle"); }
 
 TSDFVolume::Objects::~Objects() { tsdf_objects_destroy(m_handle); }
