@@ -80,8 +80,9 @@ sanitize-scene-flow: tests/cpp/scene_flow_refusals.cpp $(CSRC)/scene_flow.hip $(
 	build/scene_flow_refusals
 
 # The same for device_buffer.hpp (the grow-only array, release, free-all and the frame of a host variant): where there is no device every
-# allocation fails, the one branch the GPU suite never takes.  Header only: nothing of the library is linked.
-sanitize-device-buffer: tests/cpp/device_buffer_host.cpp $(CSRC)/device_buffer.hpp include/tsdf_amd.h
+# allocation fails, the one branch the GPU suite never takes; and for handle_order.hpp (a handle's event: create without a device, destroy
+# of what was never created, join and wait with nothing pending).  Headers only: nothing of the library is linked.
+sanitize-device-buffer: tests/cpp/device_buffer_host.cpp $(CSRC)/device_buffer.hpp $(CSRC)/handle_order.hpp include/tsdf_amd.h
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -Iinclude -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/device_buffer_host.cpp -o build/device_buffer_host
 	build/device_buffer_host

@@ -1,12 +1,14 @@
-// Stand-alone host program for a sanitizer build (make sanitize-device-buffer): the branches of tsdf_amd/csrc/device_buffer.hpp that a
-// machine WITH a device never takes.  Run where there is no device, every hipMalloc fails; the program checks what a failed growth
-// leaves behind, that releasing an empty handle does nothing, and the order in which the frame of a host variant reports errors.
-// With a device the allocations succeed and the same invariants are checked on that side.  Nothing is launched.
+// Stand-alone host program for a sanitizer build (make sanitize-device-buffer): the branches of tsdf_amd/csrc/device_buffer.hpp and
+// handle_order.hpp that a machine WITH a device never takes.  Run where there is no device, every hipMalloc fails; the program checks
+// what a failed growth leaves behind, that releasing an empty handle does nothing, the order in which the frame of a host variant
+// reports errors, and what a handle's stream order does without an event.  With a device the allocations succeed and the same
+// invariants are checked on that side.  Nothing is launched.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "device_buffer.hpp"
+#include "handle_order.hpp"
 
 static char g_message[512];
 static hipError_t g_failed_with = hipSuccess;   // what hip_fail was last given
@@ -134,6 +136,40 @@ int main() {
     }
     (void)st.finish(TSDF_OK, "what");
     (void)hipGetLastError();
+
+    // the stream order of a handle (handle_order.hpp)
+    HandleOrder none;
+    std::memset(&none, 0, sizeof(none));
+    auto untouched = [](const HandleOrder &o) { return o.device == 0 && !o.done && !o.pending; };
+    {   // destroy of a handle that was never created: nothing happens
+        HandleOrder o = none;
+        o.destroy();
+        EXPECT(untouched(o), "destroy of a zeroed handle order changes it");
+    }
+    {   // nothing in flight: join and wait return at once and touch neither the event (there is none) nor the error plumbing
+        HandleOrder o = none;
+        g_failed_what = nullptr;
+        EXPECT(o.join(nullptr, "order") == TSDF_OK && o.wait("wait") == TSDF_OK && g_failed_what == nullptr, "join / wait with nothing pending");
+        EXPECT(untouched(o), "join / wait with nothing pending change the handle order");
+    }
+    {   // create: without a device it fails and leaves no event, and destroy after it is clean; with one, the whole cycle
+        HandleOrder o = none;
+        const hipError_t e = o.create();
+        (void)hipGetLastError();
+        if (e != hipSuccess) {
+            EXPECT(!o.done && !o.pending, "a failed create leaves an event or pending work");
+            o.destroy();
+            EXPECT(!o.done && !o.pending, "destroy after a failed create");
+        } else {
+            EXPECT(o.done && !o.pending, "a successful create");
+            EXPECT(o.leave(nullptr, "event") == TSDF_OK && o.pending == 1, "leave");
+            EXPECT(o.join(nullptr, "order") == TSDF_OK && o.pending == 1, "join keeps the work pending");
+            EXPECT(o.wait("wait") == TSDF_OK && o.pending == 0, "wait");
+            o.destroy();
+            EXPECT(!o.done && !o.pending, "destroy");
+        }
+        std::printf("hipGetDevice / event here: %s\n", hipGetErrorString(e));
+    }
 
     std::printf(failures ? "device buffer host checks: %d FAILED\n" : "device buffer host checks ok\n", failures);
     return failures ? 1 : 0;

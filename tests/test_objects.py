@@ -21,8 +21,9 @@ NONE = tsdf_amd.OBJECT_NONE
 SEED = 0x5EED0003
 # one voxel; 64-voxel chunks that straddle rows with a partial last chunk; exactly two chunks of one row each plane; a row one longer than a
 # chunk; rows of two chunks and two voxels (several chunks a plane); and, because a wave of the flag kernel walks 64 chunks, 104 chunks:
-# a full wave and part of a second (the fused 48^3 below: 27 waves, six workgroups and three quarters of one)
-GRIDS = [(1, 1, 1), (13, 7, 5), (64, 3, 2), (65, 4, 3), (130, 3, 3), (67, 9, 11)]
+# a full wave and part of a second (the fused 48^3 below: 27 waves, six workgroups and three quarters of one); and 17 391 voxels in 272
+# chunks: a second workgroup whose first wave walks 16 chunks while its other three walk none, and a last chunk of 47 voxels
+GRIDS = [(1, 1, 1), (13, 7, 5), (64, 3, 2), (65, 4, 3), (130, 3, 3), (67, 9, 11), (33, 31, 17)]
 DENSITIES = [0.0, 0.1, 0.5, 0.9, 1.0]
 CLASS_COUNTS = [1, 3, 300]
 OFFSET = (100.0, -50.0, 25.0)

@@ -1156,25 +1156,45 @@ def marching_cubes_table():
     return t
 
 
-class Mesh:
-    """tsdf_mesh (include/tsdf_amd.h, "indexed mesh"): the device arrays of an indexed mesh and the scratch of its extraction, kept
-    between extractions (TSDFVolume.extract_mesh(into=mesh)).  The array properties are blocking downloads."""
+class _Handle:
+    """What the handles that live beside a volume share: creation, destruction, the info struct and the scratch size.  A subclass
+    names its C functions by their stem (`_c`: tsdf_<_c>_create, _destroy, _get_info, _scratch_bytes) and its info struct (`_Info`)."""
+
+    _c = None
+    _Info = None
 
     def __init__(self):
         self._h = C.c_void_p()
-        check(lib.tsdf_mesh_create(C.byref(self._h)))
+        check(getattr(lib, "tsdf_%s_create" % self._c)(C.byref(self._h)))
 
     def close(self):
         if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
-            lib.tsdf_mesh_destroy(self._h)
+            getattr(lib, "tsdf_%s_destroy" % self._c)(self._h)
             self._h = C.c_void_p()
 
     __del__ = close
 
-    def info(self):
-        i = _capi.MeshInfo()
-        check(lib.tsdf_mesh_get_info(self._h, C.byref(i)))
+    def _get_info(self):
+        i = self._Info()
+        check(getattr(lib, "tsdf_%s_get_info" % self._c)(self._h, C.byref(i)))
         return i
+
+    @property
+    def scratch_bytes(self):
+        """Device bytes the handle holds besides the arrays it hands out (include/tsdf_amd.h, tsdf_*_scratch_bytes, says which)."""
+        n = C.c_uint64(0)
+        check(getattr(lib, "tsdf_%s_scratch_bytes" % self._c)(self._h, C.byref(n)))
+        return int(n.value)
+
+
+class Mesh(_Handle):
+    """tsdf_mesh (include/tsdf_amd.h, "indexed mesh"): the device arrays of an indexed mesh and the scratch of its extraction, kept
+    between extractions (TSDFVolume.extract_mesh(into=mesh)).  The array properties are blocking downloads."""
+
+    _c, _Info = "mesh", _capi.MeshInfo
+
+    def info(self):
+        return self._get_info()
 
     @property
     def n_vertices(self):
@@ -1248,13 +1268,6 @@ class Mesh:
         check(lib.tsdf_mesh_buffers(self._h, *[C.byref(q) for q in p]))
         return tuple(int(q.value or 0) for q in p)
 
-    @property
-    def scratch_bytes(self):
-        """Device bytes the handle holds besides its four output arrays."""
-        n = C.c_uint64(0)
-        check(lib.tsdf_mesh_scratch_bytes(self._h, C.byref(n)))
-        return int(n.value)
-
     # ---- mesh components (include/tsdf_amd.h, "mesh components")
     def label_components(self, stream=0):
         """Label the connected pieces of the mesh on the device (tsdf_mesh_label_components): returns {n_components, n_triangles,
@@ -1326,27 +1339,16 @@ class Mesh:
         return self
 
 
-class ESDF:
+class ESDF(_Handle):
     """tsdf_esdf (include/tsdf_amd.h, "distance field"): the device array of a distance field, its scratch and the geometry it was
     computed for, kept between computations (TSDFVolume.compute_esdf(into=esdf)).  Sampling needs no volume."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
-        check(lib.tsdf_esdf_create(C.byref(self._h)))
-
-    def close(self):
-        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
-            lib.tsdf_esdf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+    _c, _Info = "esdf", _capi.EsdfInfo
 
     @property
     def info(self):
         """tsdf_esdf_info: size, flags, voxel_size, offset, max_distance, n_sites.  Waits for the computation."""
-        i = _capi.EsdfInfo()
-        check(lib.tsdf_esdf_get_info(self._h, C.byref(i)))
-        return i
+        return self._get_info()
 
     @property
     def n_sites(self):
@@ -1384,13 +1386,6 @@ class ESDF:
                                    _capi.TSDF_FIELD_UNIT_GRADIENT if unit else 0))
         return (d[:n], g[:n]) if gradient else d[:n]
 
-    @property
-    def scratch_bytes(self):
-        """Device bytes the handle holds besides the output array."""
-        n = C.c_uint64(0)
-        check(lib.tsdf_esdf_scratch_bytes(self._h, C.byref(n)))
-        return int(n.value)
-
 
 #: one row of Explorer.clusters: struct tsdf_frontier_cluster (56 bytes)
 CLUSTER_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.uint32, 3), ("hi", np.uint32, 3), ("sum", np.uint64, 3)])
@@ -1409,29 +1404,18 @@ def _row_centroids(rows, info):
     return (rows["sum"].astype(np.float64) / np.maximum(rows["size"], 1)[:, None] + 0.5) * vs + off
 
 
-class Explorer:
+class Explorer(_Handle):
     """tsdf_explorer (include/tsdf_amd.h, "exploration"): the frontier voxels of a volume (TSDFVolume.find_frontiers(into=explorer)),
     their clusters (cluster()) and the mask of unknown voxels that view-gain rays have passed (TSDFVolume.view_gain(explorer=...)), on
     the device, with the geometry they belong to.  Nothing here needs the volume."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
-        check(lib.tsdf_explorer_create(C.byref(self._h)))
-
-    def close(self):
-        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
-            lib.tsdf_explorer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+    _c, _Info = "explorer", _capi.ExplorerInfo
 
     @property
     def info(self):
         """tsdf_explorer_info: size, connectivity, voxel_size, offset, n_unknown, n_free, n_occupied, n_frontiers, n_clusters,
         n_listed_clusters."""
-        i = _capi.ExplorerInfo()
-        check(lib.tsdf_explorer_get_info(self._h, C.byref(i)))
-        return i
+        return self._get_info()
 
     @property
     def voxels(self):
@@ -1494,13 +1478,6 @@ class Explorer:
             out["labels"], out["clusters"] = int(l.value or 0), int(r.value or 0)
         return out
 
-    @property
-    def scratch_bytes(self):
-        """Device bytes the handle holds besides the list, the labels and the table."""
-        n = C.c_uint64(0)
-        check(lib.tsdf_explorer_scratch_bytes(self._h, C.byref(n)))
-        return int(n.value)
-
 
 #: one row of Reach.rank: struct tsdf_reach_cluster (16 bytes)
 REACH_CLUSTER_DTYPE = np.dtype([("label", np.uint32), ("cost", np.uint32), ("voxel", np.uint32), ("reserved", np.uint32)])
@@ -1510,28 +1487,17 @@ REACH_COST_FACE, REACH_COST_EDGE, REACH_COST_CORNER = _capi.TSDF_REACH_COST_FACE
 TSDF_REACH_THROUGH_UNKNOWN = _capi.TSDF_REACH_THROUGH_UNKNOWN
 
 
-class Reach:
+class Reach(_Handle):
     """tsdf_reach (include/tsdf_amd.h, "reachability"): the travel cost from a set of seeds to every voxel of a volume
     (TSDFVolume.reach(into=reach)), on the device, with the geometry it belongs to.  Lookup, paths and ranking need no volume."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
-        check(lib.tsdf_reach_create(C.byref(self._h)))
-
-    def close(self):
-        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
-            lib.tsdf_reach_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+    _c, _Info = "reach", _capi.ReachInfo
 
     @property
     def info(self):
         """tsdf_reach_info: size, connectivity, voxel_size, offset, flags, clearance, max_cost, max_cost_reached, n_traversable,
         n_reached, n_seed_voxels, rounds (a diagnostic: it may differ from run to run)."""
-        i = _capi.ReachInfo()
-        check(lib.tsdf_reach_get_info(self._h, C.byref(i)))
-        return i
+        return self._get_info()
 
     @property
     def costs(self):
@@ -1603,13 +1569,6 @@ class Reach:
         c = _voxel_coordinates(np.asarray(ids, np.uint32).reshape(-1), i.size)
         return ((c.astype(np.float32) + np.float32(0.5)) * vs + off).astype(np.float32)
 
-    @property
-    def scratch_bytes(self):
-        """Device bytes the handle holds besides the cost array."""
-        n = C.c_uint64(0)
-        check(lib.tsdf_reach_scratch_bytes(self._h, C.byref(n)))
-        return int(n.value)
-
 
 #: one row of Objects.objects: struct tsdf_class_object (72 bytes)
 OBJECT_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.uint32, 3), ("hi", np.uint32, 3), ("sum", np.uint64, 3),
@@ -1618,28 +1577,17 @@ OBJECT_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.ui
 OBJECT_NONE = _capi.TSDF_OBJECT_NONE
 
 
-class Objects:
+class Objects(_Handle):
     """tsdf_objects (include/tsdf_amd.h, "class objects"): the labelled voxels of a volume, the connected pieces of each class among
     them and their table (TSDFVolume.find_objects(into=objects)), on the device, with the geometry they belong to; lookup() resolves
     world points to table rows.  Nothing here needs the volume."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
-        check(lib.tsdf_objects_create(C.byref(self._h)))
-
-    def close(self):
-        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
-            lib.tsdf_objects_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+    _c, _Info = "objects", _capi.ObjectsInfo
 
     @property
     def info(self):
         """tsdf_objects_info: size, connectivity, voxel_size, offset, min_votes, min_size, n_labelled, n_objects, n_listed_objects."""
-        i = _capi.ObjectsInfo()
-        check(lib.tsdf_objects_get_info(self._h, C.byref(i)))
-        return i
+        return self._get_info()
 
     def _download(self, voxels=False, labels=False, rows=False):
         # (one element more than asked for: the pointer of an empty array may be null, which the C ABI reads as "not asked for")
@@ -1703,13 +1651,6 @@ class Objects:
         p = [C.c_void_p() for _ in range(5)]
         check(lib.tsdf_objects_buffers(self._h, *[C.byref(q) for q in p]))
         return {k: int(q.value or 0) for k, q in zip(("voxels", "masks", "bases", "labels", "objects"), p)}
-
-    @property
-    def scratch_bytes(self):
-        """Device bytes the handle holds besides the list, the labels and the table."""
-        n = C.c_uint64(0)
-        check(lib.tsdf_objects_scratch_bytes(self._h, C.byref(n)))
-        return int(n.value)
 
 
 def pixel_rays(camera, width, height, step=1):
@@ -1802,29 +1743,21 @@ def read_sparse_file(path):
     return header, info, ids, dist, weights, colours
 
 
-class Snapshot:
+class Snapshot(_Handle):
     """tsdf_snapshot (include/tsdf_amd.h, "sparse snapshot"): the live bricks of a volume as compact device arrays -- ids, distances,
     weights in the volume's own element type, colour words -- with the scratch that fills them, kept between snapshots
     (TSDFVolume.snapshot(into=snap)).  `header`: the .tsdf header fields that go into a file (set by TSDFVolume.snapshot and load)."""
 
+    _c, _Info = "snapshot", _capi.SnapshotInfo
+
     def __init__(self):
-        self._h = C.c_void_p()
         self.header = None
-        check(lib.tsdf_snapshot_create(C.byref(self._h)))
-
-    def close(self):
-        if lib is not None and getattr(self, "_h", None) is not None and self._h.value:
-            lib.tsdf_snapshot_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
+        super().__init__()
 
     @property
     def info(self):
         """tsdf_snapshot_info: size, bricks, flags, weight_bits, weight_bound, fill_distance, voxel_size, offset, n_bricks, bytes."""
-        i = _capi.SnapshotInfo()
-        check(lib.tsdf_snapshot_get_info(self._h, C.byref(i)))
-        return i
+        return self._get_info()
 
     @property
     def n_bricks(self):
@@ -1863,13 +1796,6 @@ class Snapshot:
         p = [C.c_void_p() for _ in range(4)]
         check(lib.tsdf_snapshot_buffers(self._h, *(C.byref(q) for q in p)))
         return tuple(int(q.value or 0) for q in p)
-
-    @property
-    def scratch_bytes(self):
-        """Device bytes the handle holds besides the four arrays."""
-        n = C.c_uint64(0)
-        check(lib.tsdf_snapshot_scratch_bytes(self._h, C.byref(n)))
-        return int(n.value)
 
     @classmethod
     def from_arrays(cls, size, bricks, distances, weights, colours=None, fill_distance=0.0, voxel_size=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0),

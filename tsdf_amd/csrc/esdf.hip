@@ -15,6 +15,8 @@
 // One writer per word, no float atomics: the array is the same on every run.  Nothing of the volume is written.
 #include "common.hpp"
 #include "field_sample.hpp"
+#include "handle_order.hpp"
+#include "voxel_grid.hpp"
 
 namespace tsdf {
 
@@ -34,10 +36,10 @@ __global__ __launch_bounds__(256) void esdf_sites_kernel(const float *__restrict
     bool site = false;
     if (x < X && y < Y) {
         const size_t xy = (size_t)X * Y, ip = (size_t)X * y + x;
-        if (weight_at(wv, xy, ip, z) > 0.0f) {   // (false for a NaN weight)
-            const bool neg = dist[xy * z + ip] < 0.0f;   // the mesh's sign test: NaN and both zeros are not negative
+        if (voxel_observed(wv, xy, ip, z)) {
+            const bool neg = voxel_occupied(dist, xy * z + ip);
             // an observed neighbour inside the grid of the other sign
-            auto other = [&](size_t ip2, uint32_t z2) { return weight_at(wv, xy, ip2, z2) > 0.0f && (dist[xy * z2 + ip2] < 0.0f) != neg; };
+            auto other = [&](size_t ip2, uint32_t z2) { return voxel_observed(wv, xy, ip2, z2) && voxel_occupied(dist, xy * z2 + ip2) != neg; };
             site = (x > 0 && other(ip - 1, z)) || (x + 1 < X && other(ip + 1, z)) || (y > 0 && other(ip - X, z)) ||
                    (y + 1 < Y && other(ip + X, z)) || (z > 0 && other(ip, z - 1)) || (z + 1 < Z && other(ip, z + 1));
         }
@@ -128,8 +130,8 @@ __global__ __launch_bounds__(256) void esdf_pass_z_kernel(const float *__restric
     float e = sqrtf(best);
     if (!(e < max_distance)) e = max_distance;
     float r;
-    if (weight_at(wv, xy, ip, z) > 0.0f)
-        r = dist[xy * z + ip] < 0.0f ? -e : e;
+    if (voxel_observed(wv, xy, ip, z))
+        r = voxel_occupied(dist, xy * z + ip) ? -e : e;
     else
         r = fill_unknown ? e : NAN;
     out[xy * z + ip] = r;
@@ -139,10 +141,7 @@ __global__ __launch_bounds__(256) void esdf_pass_z_kernel(const float *__restric
 
 using namespace tsdf;
 
-struct tsdf_esdf {
-    int device;
-    hipEvent_t done;        // recorded behind the last computation's launches
-    int pending;            // ... and not waited for yet
+struct tsdf_esdf : HandleOrder {
     int computed;           // a computation has been enqueued into this handle
     float *out;             // the distance array
     float *work;            // the other side of the ping-pong
@@ -157,21 +156,18 @@ struct tsdf_esdf {
 namespace {
 
 void esdf_free(tsdf_esdf *s) {
-    if (s->done) (void)hipEventSynchronize(s->done);
+    s->destroy();
     device_free_all(s->out, s->work, s->aux);
     (void)hipHostFree(s->n_sites_host);
-    if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
 
-int esdf_wait(const tsdf_esdf *cs, const char *what) {
-    tsdf_esdf *s = const_cast<tsdf_esdf *>(cs);
-    if (s->pending) {
-        TSDF_HIP(hipEventSynchronize(s->done), what);
-        s->pending = 0;
-        s->info.n_sites = *s->n_sites_host;
-    }
-    return TSDF_OK;
+// the host waits for the computation in flight; its count of sites has then landed
+int esdf_wait(const tsdf_esdf *cs) {
+    if (!cs->pending) return TSDF_OK;
+    const int rc = cs->wait("esdf wait");
+    if (rc == TSDF_OK) const_cast<tsdf_esdf *>(cs)->info.n_sites = *cs->n_sites_host;
+    return rc;
 }
 
 // the last scan index that can matter under the cap: ceil(max_distance / voxel_size) + 1, the whole axis where that is longer
@@ -206,8 +202,7 @@ int tsdf_esdf_create(tsdf_esdf **out) {
         return TSDF_ERR_NOMEM;
     }
     std::memset(s, 0, sizeof(*s));
-    hipError_t e = hipGetDevice(&s->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+    hipError_t e = s->create();
     if (e == hipSuccess) e = hipMalloc((void **)&s->aux, sizeof(EsdfAux));
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->n_sites_host, sizeof(unsigned long long), hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -227,15 +222,15 @@ int tsdf_volume_compute_esdf(const tsdf_volume *cv, float max_distance, uint32_t
     TSDF_REQUIRE(cv && s, "tsdf_volume_compute_esdf: null argument");
     tsdf_volume *v = const_cast<tsdf_volume *>(cv);
     const Geom &g = v->g;
-    TSDF_REQUIRE(!v->slab && g.z_store_begin == 0 && g.z_store_end == g.Z,
-                 "tsdf_volume_compute_esdf: a Z-slab volume (tsdf_volume_create_slab) is not supported: the nearest site may lie in another slab");
-    TSDF_REQUIRE(!v->nodes, "%s has a materialised deformation-node array: voxel centres must be the implicit grid", "tsdf_volume_compute_esdf: the volume");
+    // (no 32-bit voxel ids here: the kernels index with size_t, and the axes are bounded below)
+    int rc = whole_volume_checked("tsdf_volume_compute_esdf", v, s->device, "the nearest site may lie in another slab", kAcceptsWideIds);
+    if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(max_distance > 0.0f, "tsdf_volume_compute_esdf: max_distance must be > 0 (INFINITY: no cap), got %g", (double)max_distance);
     TSDF_REQUIRE((flags & ~(uint32_t)TSDF_ESDF_FILL_UNKNOWN) == 0, "tsdf_volume_compute_esdf: unknown flags %#x", flags);
     TSDF_REQUIRE(g.X <= kEsdfMaxAxis && g.Y <= kEsdfMaxAxis && g.Z <= kEsdfMaxAxis,
                  "tsdf_volume_compute_esdf: an axis of %u x %u x %u is longer than %u voxels", g.X, g.Y, g.Z, kEsdfMaxAxis);
-    TSDF_REQUIRE(v->device == s->device, "tsdf_volume_compute_esdf: the handle was created on device %d, the volume on device %d", s->device, v->device);
-    if (s->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, s->done, 0), "esdf stream order");   // what a previous computation into this handle left in flight
+    rc = s->join(v->stream, "esdf stream order");   // what a previous computation into this handle left in flight
+    if (rc != TSDF_OK) return rc;
     const size_t n = (size_t)g.X * g.Y * g.Z;
     hipError_t e = device_reserve(s->out, s->out_cap, n);
     if (e == hipSuccess) e = device_reserve(s->work, s->work_cap, n);
@@ -245,10 +240,8 @@ int tsdf_volume_compute_esdf(const tsdf_volume *cv, float max_distance, uint32_t
     }
     s->g = g;
     s->fast_div = v->fast_div;
-    s->info.size[0] = g.X; s->info.size[1] = g.Y; s->info.size[2] = g.Z;
+    geometry_into(s->info, g);
     s->info.flags = flags;
-    s->info.voxel_size[0] = g.vs.x; s->info.voxel_size[1] = g.vs.y; s->info.voxel_size[2] = g.vs.z;
-    s->info.offset[0] = g.offset.x; s->info.offset[1] = g.offset.y; s->info.offset[2] = g.offset.z;
     s->info.max_distance = max_distance;
     s->info.n_sites = 0;
     s->computed = 1;
@@ -270,14 +263,12 @@ int tsdf_volume_compute_esdf(const tsdf_volume *cv, float max_distance, uint32_t
                        max_distance, (flags & TSDF_ESDF_FILL_UNKNOWN) ? 1 : 0);
     TSDF_HIP(hipGetLastError(), "esdf kernels failed");
     TSDF_HIP(hipMemcpyAsync(s->n_sites_host, &s->aux->n_sites, sizeof(unsigned long long), hipMemcpyDeviceToHost, v->stream), "esdf count download");
-    TSDF_HIP(hipEventRecord(s->done, v->stream), "esdf event");
-    s->pending = 1;
-    return TSDF_OK;
+    return s->leave(v->stream, "esdf event");
 }
 
 int tsdf_esdf_get_info(const tsdf_esdf *s, tsdf_esdf_info *info) {
     TSDF_REQUIRE(s && info, "tsdf_esdf_get_info: null argument");
-    const int rc = esdf_wait(s, "esdf wait");
+    const int rc = esdf_wait(s);
     if (rc != TSDF_OK) return rc;
     *info = s->info;
     return TSDF_OK;
@@ -285,7 +276,7 @@ int tsdf_esdf_get_info(const tsdf_esdf *s, tsdf_esdf_info *info) {
 
 int tsdf_esdf_buffer(const tsdf_esdf *s, const float **device_distance) {
     TSDF_REQUIRE(s && device_distance, "tsdf_esdf_buffer: null argument");
-    const int rc = esdf_wait(s, "esdf wait");
+    const int rc = esdf_wait(s);
     if (rc != TSDF_OK) return rc;
     *device_distance = s->computed ? s->out : nullptr;
     return TSDF_OK;
@@ -294,7 +285,7 @@ int tsdf_esdf_buffer(const tsdf_esdf *s, const float **device_distance) {
 int tsdf_esdf_download(const tsdf_esdf *s, float *host_distance) {
     TSDF_REQUIRE(s && host_distance, "tsdf_esdf_download: null argument");
     TSDF_REQUIRE(s->computed, "tsdf_esdf_download: the handle has never been computed (tsdf_volume_compute_esdf)");
-    const int rc = esdf_wait(s, "esdf wait");
+    const int rc = esdf_wait(s);
     if (rc != TSDF_OK) return rc;
     const size_t n = (size_t)s->g.X * s->g.Y * s->g.Z;
     if (n) TSDF_HIP(hipMemcpy(host_distance, s->out, n * sizeof(float), hipMemcpyDeviceToHost), "esdf download");
@@ -307,7 +298,8 @@ int tsdf_esdf_sample_device(const tsdf_esdf *s, uint64_t n, const float *device_
     if (rc0 != TSDF_OK) return rc0;
     if (n == 0) return TSDF_OK;
     // the caller's stream behind the computation
-    if (s->pending) TSDF_HIP(hipStreamWaitEvent((hipStream_t)hip_stream, s->done, 0), "esdf stream order");
+    const int rc = s->join((hipStream_t)hip_stream, "esdf stream order");
+    if (rc != TSDF_OK) return rc;
     return sample_field_view(esdf_view(s), s->fast_div != 0, n, device_points, device_distance, device_gradient, nullptr, flags,
                              (hipStream_t)hip_stream);
 }
@@ -317,7 +309,7 @@ int tsdf_esdf_sample(const tsdf_esdf *s, uint64_t n, const float *host_points, f
     if (rc0 != TSDF_OK) return rc0;
     if (n == 0) return TSDF_OK;
     TSDF_REQUIRE(n <= ((uint64_t)1 << 40), "tsdf_esdf_sample: too many points");
-    const int rcw = esdf_wait(s, "esdf wait");
+    const int rcw = esdf_wait(s);
     if (rcw != TSDF_OK) return rcw;
     // one allocation: points (3n), then distance (n) and gradient (3n) as far as asked for; on the null stream, blocking
     const size_t fn = (size_t)n;

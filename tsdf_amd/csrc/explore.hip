@@ -1,11 +1,8 @@
 // Exploration queries for gfx950 (include/tsdf_amd.h, "exploration"): which free voxels border unseen space, how they
 // hang together, and how much unseen space a set of rays would see.  No reference counterpart.  Nothing of the volume is written.
 //
-// Frontiers: chunks of 64 consecutive voxel ids, a wave at a time.
-//   frontier_flag_kernel     the state of every voxel (unknown / free / occupied) and the frontier test; per chunk the ballot mask and
-//                            its popcount; the four counts by ballot and popcount over the 64 chunks a wave walks, one integer atomic
-//                            per workgroup that has any
-// The list and the clusters are voxel_set.hpp's, with the policy "any listed neighbour is adjacent".
+// Frontiers: FrontierFlag, the state of a voxel (unknown / free / occupied) and the frontier test, four counters.  The flag walk, the
+// list and the clusters are voxel_set.hpp's, with the policy "any listed neighbour is adjacent".
 // View gain: a lane per ray.
 //   view_gain_kernel         gain_walk (explore_walk.hpp); an unknown voxel sets its bit in the handle's mask with atomicOr
 //   mask_count_kernel        the set bits, by popcount and a wave sum, one integer atomic per wave that has any
@@ -26,55 +23,28 @@ using FrontierSet = VoxelSet<tsdf_frontier_cluster, 4, 8>;
 
 constexpr uint64_t kGainMaxRays = (uint64_t)0x7fffffff * 256;   // what a launch of 256-lane workgroups holds
 
-// A wave walks kFlagChunks consecutive chunks and adds its counts up in registers, the four waves of a workgroup add theirs up in LDS
-// (integer atomics), and the four counters see one atomic per workgroup and 16 384 voxels.  With one per chunk, two million waves queue
-// on the same four words at 512^3 and the kernel takes 31 ms; with one per wave and 32 chunks, 1.5 ms, still twice esdf_sites_kernel.
-constexpr uint32_t kFlagChunks = 64;
-
-__global__ __launch_bounds__(256) void frontier_flag_kernel(const float *__restrict__ dist, const WeightView wv, const VoxelGrid grid,
-                                                            const uint32_t n_chunks, uint64_t *__restrict__ mask, uint32_t *__restrict__ base,
-                                                            unsigned long long *__restrict__ words) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t first = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kFlagChunks;
-    const size_t xy = (size_t)grid.X * grid.Y;
-    __shared__ uint32_t totals[4];   // in the order of kWordUnknown .. kWordFrontiers
-    if (threadIdx.x < 4) totals[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t n_unknown = 0, n_free = 0, n_occupied = 0, n_frontiers = 0;   // (at most 64 * kFlagChunks each)
-    for (uint32_t k = 0; k < kFlagChunks; k++) {   // bounded: kFlagChunks trips
-        if (first + k >= n_chunks) break;   // (the whole wave)
-        const uint32_t chunk = (uint32_t)(first + k);
-        const uint64_t id = (uint64_t)chunk * 64 + lane;
-        bool unknown = false, occupied = false, is_free = false, frontier = false;
-        if (id < grid.n) {
-            uint32_t x, y, z;
-            grid.split((uint32_t)id, x, y, z);
-            const size_t ip = (size_t)grid.X * y + x;
-            unknown = !(weight_at(wv, xy, ip, z) > 0.0f);   // (true for a NaN weight)
-            // the distance is read only where the voxel is observed: the mesh's sign test, NaN and both zeros are not negative
-            occupied = !unknown && dist[id] < 0.0f;
-            is_free = !unknown && !occupied;
-            if (is_free) {
-                auto unseen = [&](size_t ip2, uint32_t z2) { return !(weight_at(wv, xy, ip2, z2) > 0.0f); };
-                frontier = (x > 0 && unseen(ip - 1, z)) || (x + 1 < grid.X && unseen(ip + 1, z)) || (y > 0 && unseen(ip - grid.X, z)) ||
-                           (y + 1 < grid.Y && unseen(ip + grid.X, z)) || (z > 0 && unseen(ip, z - 1)) || (z + 1 < grid.Z && unseen(ip, z + 1));
-            }
+// The state of every voxel (unknown / free / occupied: voxel_state, field_sample.hpp) and the frontier test: free, with a 6-neighbour
+// inside the grid that is unknown.  The counters in the order of kWordUnknown .. kWordFrontiers; the frontiers are listed.
+struct FrontierFlag {
+    static constexpr uint32_t kCounts = 4, kListed = kWordFrontiers;
+    const float *dist;
+    WeightView wv;
+    __device__ uint32_t operator()(uint32_t id, const VoxelGrid &grid) const {
+        uint32_t x, y, z;
+        grid.split(id, x, y, z);
+        const size_t xy = (size_t)grid.X * grid.Y, ip = (size_t)grid.X * y + x;
+        const int state = voxel_state(dist, wv, xy, ip, z);
+        bool frontier = false;
+        if (state == kVoxelFree) {
+            auto unseen = [&](size_t ip2, uint32_t z2) { return !voxel_observed(wv, xy, ip2, z2); };
+            frontier = (x > 0 && unseen(ip - 1, z)) || (x + 1 < grid.X && unseen(ip + 1, z)) || (y > 0 && unseen(ip - grid.X, z)) ||
+                       (y + 1 < grid.Y && unseen(ip + grid.X, z)) || (z > 0 && unseen(ip, z - 1)) || (z + 1 < grid.Z && unseen(ip, z + 1));
         }
-        store_keep_mask(frontier, lane, chunk, mask, base);
-        n_unknown += (uint32_t)__popcll(__ballot(unknown));
-        n_free += (uint32_t)__popcll(__ballot(is_free));
-        n_occupied += (uint32_t)__popcll(__ballot(occupied));
-        n_frontiers += (uint32_t)__popcll(__ballot(frontier));
+        // (a bit per test, each selected on its own: the walk's ballots then read the tests themselves)
+        return (state == kVoxelUnknown ? 1u << kWordUnknown : 0u) | (state == kVoxelFree ? 1u << kWordFree : 0u) |
+               (state == kVoxelOccupied ? 1u << kWordOccupied : 0u) | (frontier ? 1u << kWordFrontiers : 0u);
     }
-    if (lane == 0) {
-        if (n_unknown) atomicAdd(&totals[kWordUnknown], n_unknown);
-        if (n_free) atomicAdd(&totals[kWordFree], n_free);
-        if (n_occupied) atomicAdd(&totals[kWordOccupied], n_occupied);
-        if (n_frontiers) atomicAdd(&totals[kWordFrontiers], n_frontiers);
-    }
-    __syncthreads();   // (every lane gets here: the loop is left by break, never by return)
-    if (threadIdx.x < 4 && totals[threadIdx.x]) atomicAdd(words + threadIdx.x, (unsigned long long)totals[threadIdx.x]);
-}
+};
 
 struct GainView {
     const float *dist;
@@ -93,12 +63,12 @@ __global__ __launch_bounds__(256) void view_gain_kernel(const GainView f, const 
     const uint8_t code = gain_walk(f.g, origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], directions[3 * i], directions[3 * i + 1],
                                    directions[3 * i + 2], t_max ? t_max[i] : INFINITY, n_unknown, n_free, [&](int ix, int iy, int iz) {
                                        const size_t ip = (size_t)f.g.X * (uint32_t)iy + (uint32_t)ix;
-                                       if (!(weight_at(f.wv, xy, ip, (uint32_t)iz) > 0.0f)) {
+                                       if (!voxel_observed(f.wv, xy, ip, (uint32_t)iz)) {
                                            const uint32_t id = (uint32_t)(xy * (uint32_t)iz + ip);
                                            atomicOr(gain_mask + (id >> 5), 1u << (id & 31u));   // (a set: order-free)
                                            return (int)kVoxelUnknown;
                                        }
-                                       return f.dist[xy * (uint32_t)iz + ip] < 0.0f ? (int)kVoxelOccupied : (int)kVoxelFree;
+                                       return voxel_occupied(f.dist, xy * (uint32_t)iz + ip) ? (int)kVoxelOccupied : (int)kVoxelFree;
                                    });
     if (unknown) unknown[i] = n_unknown;
     if (free_out) free_out[i] = n_free;
@@ -140,11 +110,6 @@ void explorer_free(tsdf_explorer *s) {
     delete s;
 }
 
-bool same_geometry(const Geom &a, const Geom &b) {
-    return a.X == b.X && a.Y == b.Y && a.Z == b.Z && a.vs.x == b.vs.x && a.vs.y == b.vs.y && a.vs.z == b.vs.z && a.offset.x == b.offset.x &&
-           a.offset.y == b.offset.y && a.offset.z == b.offset.z;
-}
-
 void adopt_geometry(tsdf_explorer *s, const Geom &g) {
     if (!s->has_geometry || s->g.X != g.X || s->g.Y != g.Y || s->g.Z != g.Z) s->mask_ready = 0;   // the bits are voxel ids of another grid
     s->g = g;
@@ -156,13 +121,7 @@ void adopt_geometry(tsdf_explorer *s, const Geom &g) {
 int volume_checked(const char *who, const tsdf_volume *v, const tsdf_explorer *s) {
     TSDF_REQUIRE(v, "%s: null volume", who);
     TSDF_REQUIRE(s, "%s: null explorer handle", who);
-    const Geom &g = v->g;
-    TSDF_REQUIRE(!v->slab && g.z_store_begin == 0 && g.z_store_end == g.Z,
-                 "%s: a Z-slab volume (tsdf_volume_create_slab) is not supported: a voxel's neighbours and a ray's voxels lie in other slabs", who);
-    TSDF_REQUIRE(!v->nodes, "%s: the volume has a materialised deformation-node array: voxel centres must be the implicit grid", who);
-    TSDF_REQUIRE((uint64_t)g.X * g.Y * g.Z <= 0xffffffffull, "%s: %u x %u x %u voxels do not fit 32-bit voxel ids", who, g.X, g.Y, g.Z);
-    TSDF_REQUIRE(v->device == s->device, "%s: the handle was created on device %d, the volume on device %d", who, s->device, v->device);
-    return TSDF_OK;
+    return whole_volume_checked(who, v, s->device, "a voxel's neighbours and a ray's voxels lie in other slabs");
 }
 
 // the labels and the table are the list's, and nothing is in flight on them
@@ -263,9 +222,7 @@ int tsdf_volume_find_frontiers(const tsdf_volume *cv, uint32_t flags, tsdf_explo
         adopt_geometry(s, v->g);
         s->info.connectivity = 0;
         s->info.n_unknown = s->info.n_free = s->info.n_occupied = s->info.n_frontiers = s->info.n_clusters = s->info.n_listed_clusters = 0;
-        const WeightView wv = {v->weight, v->wpacked, v->wmode};
-        const dim3 flag_grid((n_chunks + 4 * kFlagChunks - 1) / (4 * kFlagChunks));
-        hipLaunchKernelGGL(frontier_flag_kernel, flag_grid, dim3(256), 0, stream, v->dist, wv, grid, n_chunks, s->masks, s->bases, s->words);
+        voxel_flag(FrontierFlag{v->dist, {v->weight, v->wpacked, v->wmode}}, grid, n_chunks, s->masks, s->bases, s->words, stream);
         return TSDF_OK;
     }, &n_list);
     if (rc != TSDF_OK) return rc;

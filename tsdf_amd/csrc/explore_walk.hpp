@@ -4,11 +4,11 @@
 // same arithmetic, every fp32 operation rounded on its own (-ffp-contract=off).
 #pragma once
 
+#include "field_sample.hpp"   // kVoxelUnknown / kVoxelFree / kVoxelOccupied
 #include "rays_walk.hpp"
 
 namespace tsdf {
 
-enum : int { kVoxelUnknown = 0, kVoxelFree = 1, kVoxelOccupied = 2 };
 enum : uint8_t { kGainSkipped = 0, kGainEnded = 1, kGainBlocked = 2 };
 
 // The stop code of the ray; n_unknown / n_free count the voxels visited in either state.  t_max: +inf for "no limit".

@@ -24,6 +24,24 @@ __device__ inline float weight_at(const WeightView &wv, size_t xy, size_t in_pla
     return (float)((wv.packed[xy * (z >> 1) + in_plane] >> (16u * (z & 1u))) & 0xffffu);
 }
 
+// The state of a voxel, for everything that asks what has been seen (explore.hip, reach.hip, esdf.hip).  Observed: weight > 0, false
+// for a NaN weight, so such a voxel is unknown.  The distance is read only where the voxel is observed; occupied is the mesh's sign
+// test, dist < 0: NaN and both zeros are not negative, so they are free.  voxel_state is the whole rule; a caller that does something
+// between its two halves (marks an unknown voxel, compares two observed ones) asks voxel_observed, then voxel_occupied.
+enum : int { kVoxelUnknown = 0, kVoxelFree = 1, kVoxelOccupied = 2 };
+
+__device__ inline bool voxel_observed(const WeightView &wv, size_t xy, size_t in_plane, uint32_t z) {
+    return weight_at(wv, xy, in_plane, z) > 0.0f;
+}
+
+// of an OBSERVED voxel, `at` its place in the distance array
+__device__ inline bool voxel_occupied(const float *__restrict__ dist, size_t at) { return dist[at] < 0.0f; }
+
+__device__ inline int voxel_state(const float *__restrict__ dist, const WeightView &wv, size_t xy, size_t in_plane, uint32_t z) {
+    if (!voxel_observed(wv, xy, in_plane, z)) return kVoxelUnknown;
+    return voxel_occupied(dist, xy * z + in_plane) ? kVoxelOccupied : kVoxelFree;
+}
+
 // What a read-only kernel needs of a whole (not Z-slab) volume; travels as one kernel argument.
 struct FieldView {
     const float *dist;

@@ -183,13 +183,12 @@ using namespace tsdf;
 namespace {
 
 void mesh_free(tsdf_mesh *m) {
-    if (m->done) (void)hipEventSynchronize(m->done);
+    m->destroy();
     device_free_all(m->vertices, m->indices, m->normals, m->rgb, m->chunks, m->parts, m->table, m->labels, m->sizes, m->component_words,
                     m->keep_masks, m->keep_bases, m->cell_keys, m->cell_reps, m->cluster_of, m->cluster_sums, m->row_begin, m->row_end, m->rows,
                     m->smooth_positions, m->pinned, m->normal_sums, m->flow_vertex, m->flow_points, m->flow_counts, m->flow_depth, m->flow_image);
     (void)hipHostFree(m->flow_totals);
     (void)hipHostFree(m->totals);
-    if (m->done) (void)hipEventDestroy(m->done);
     delete m;
 }
 
@@ -206,8 +205,7 @@ int tsdf_mesh_create(tsdf_mesh **out) {
         return TSDF_ERR_NOMEM;
     }
     std::memset(m, 0, sizeof(*m));
-    hipError_t e = hipGetDevice(&m->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->done, hipEventDisableTiming);
+    hipError_t e = m->create();
     if (e == hipSuccess) e = hipMalloc((void **)&m->table, sizeof(MeshTable));
     if (e == hipSuccess) e = hipHostMalloc((void **)&m->totals, 2 * sizeof(uint64_t), hipHostMallocDefault);
     if (e != hipSuccess) {

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "handle_order.hpp"
 
 namespace tsdf {
 
@@ -71,10 +72,7 @@ inline uint32_t mesh_table_bits(uint64_t n) {
 
 }  // namespace tsdf
 
-struct tsdf_mesh {
-    int device;
-    hipEvent_t done;        // recorded behind the last extraction's (labelling's, filter's) launches
-    int pending;            // ... and not waited for yet
+struct tsdf_mesh : tsdf::HandleOrder {   // (the event: behind the last extraction's, labelling's or filter's launches)
     float *vertices;
     uint32_t *indices;
     float *normals;
@@ -134,29 +132,10 @@ struct tsdf_mesh {
 
 namespace tsdf {
 
-// ---- the stream order of a handle --------------------------------------------------------------------------------------------------
-// the stream waits for what is in flight on the handle
-inline int mesh_join(tsdf_mesh *m, hipStream_t stream) {
-    if (m->pending) TSDF_HIP(hipStreamWaitEvent(stream, m->done, 0), "mesh stream order");
-    return TSDF_OK;
-}
-
-// what has just been enqueued on the stream is in flight on the handle
-inline int mesh_leave(tsdf_mesh *m, hipStream_t stream) {
-    TSDF_HIP(hipEventRecord(m->done, stream), "mesh event");
-    m->pending = 1;
-    return TSDF_OK;
-}
-
-// the host waits for it
-inline int mesh_wait(const tsdf_mesh *cm) {
-    tsdf_mesh *m = const_cast<tsdf_mesh *>(cm);
-    if (m->pending) {
-        TSDF_HIP(hipEventSynchronize(m->done), "mesh wait");
-        m->pending = 0;
-    }
-    return TSDF_OK;
-}
+// ---- the stream order of a handle (handle_order.hpp), under the mesh's texts ---------------------------------------------------------
+inline int mesh_join(const tsdf_mesh *m, hipStream_t stream) { return m->join(stream, "mesh stream order"); }
+inline int mesh_leave(const tsdf_mesh *m, hipStream_t stream) { return m->leave(stream, "mesh event"); }
+inline int mesh_wait(const tsdf_mesh *m) { return m->wait("mesh wait"); }
 
 // ---- argument checks ---------------------------------------------------------------------------------------------------------------
 // (labelling, which takes no vertex array, starts here)

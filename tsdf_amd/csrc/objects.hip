@@ -1,10 +1,8 @@
 // Class objects for gfx950 (include/tsdf_amd.h, "class objects"): the connected pieces of each fused class, their table,
 // and the object a world point lies in.  No reference counterpart.  Only the class words are read; nothing of the volume is written.
 //
-// List: chunks of 64 consecutive voxel ids, a wave at a time.
-//   objects_flag_kernel     one coalesced dword per lane, the vote and selection test; per chunk the ballot mask and its popcount; the
-//                           count by popcount over the 64 chunks a wave walks, one integer atomic per workgroup that has any
-// The list and the objects are voxel_set.hpp's, with the policy "a listed neighbour of the same class is adjacent".
+// List: LabelledFlag, the vote and selection test on one coalesced dword per voxel, one counter.  The flag walk, the list and the
+// objects are voxel_set.hpp's, with the policy "a listed neighbour of the same class is adjacent".
 // Lookup: a lane per point.
 //   objects_lookup_kernel   the sampler's voxel (point_voxel_at, voxel_grid.hpp) -> its list index -> its label -> the label's row, or NONE
 // Every result is a set, an integer sum, a minimum or a maximum: two runs give the same bytes whatever order the waves run in.  No float
@@ -25,40 +23,23 @@ using LabelledSet = VoxelSet<tsdf_class_object, 1, 4>;
 
 constexpr uint64_t kLookupMaxPoints = (uint64_t)0x7fffffff * 256;   // what a launch of 256-lane workgroups holds
 
-// As frontier_flag_kernel (explore.hip): a wave walks kObjFlagChunks consecutive chunks and adds its count up in a register, the four
-// waves of a workgroup add theirs up in LDS, and the counter sees one atomic per workgroup and 16 384 voxels.
-constexpr uint32_t kObjFlagChunks = 64;
-
-// select: the device copy of the caller's selection (n_select bytes), or null = every class.  min_votes >= 1.
-__global__ __launch_bounds__(256) void objects_flag_kernel(const uint32_t *__restrict__ cls, const uint32_t n_voxels, const uint32_t n_chunks,
-                                                           const uint32_t min_votes, const uint8_t *__restrict__ select, const uint32_t n_select,
-                                                           uint64_t *__restrict__ mask, uint32_t *__restrict__ base,
-                                                           unsigned long long *__restrict__ words) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t first = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kObjFlagChunks;
-    __shared__ uint32_t total;
-    if (threadIdx.x == 0) total = 0;
-    __syncthreads();
-    uint32_t n_labelled = 0;   // (at most 64 * kObjFlagChunks)
-    for (uint32_t k = 0; k < kObjFlagChunks; k++) {   // bounded: kObjFlagChunks trips
-        if (first + k >= n_chunks) break;   // (the whole wave)
-        const uint32_t chunk = (uint32_t)(first + k);
-        const uint64_t id = (uint64_t)chunk * 64 + lane;
-        bool labelled = false;
-        if (id < n_voxels) {
-            const uint32_t w = cls[id];
-            const uint32_t c = w & 0xFFFFu;
-            labelled = (w >> 16) >= min_votes;
-            // the selection byte is read only for a voxel with the votes (c < n_select before c is an address)
-            if (labelled && select) labelled = c < n_select && select[c] != 0;
-        }
-        store_keep_mask(labelled, lane, chunk, mask, base);
-        n_labelled += (uint32_t)__popcll(__ballot(labelled));
+// One coalesced dword per voxel: labelled = enough votes, and of a selected class.  select: the device copy of the caller's selection
+// (n_select bytes), or null = every class.  min_votes >= 1.  One counter; the labelled voxels are listed.
+struct LabelledFlag {
+    static constexpr uint32_t kCounts = 1, kListed = kObjWordLabelled;
+    const uint32_t *cls;
+    uint32_t min_votes;
+    const uint8_t *select;
+    uint32_t n_select;
+    __device__ uint32_t operator()(uint32_t id, const VoxelGrid &) const {
+        const uint32_t w = cls[id];
+        const uint32_t c = w & 0xFFFFu;
+        bool labelled = (w >> 16) >= min_votes;
+        // the selection byte is read only for a voxel with the votes (c < n_select before c is an address)
+        if (labelled && select) labelled = c < n_select && select[c] != 0;
+        return labelled ? 1u : 0u;
     }
-    if (lane == 0 && n_labelled) atomicAdd(&total, n_labelled);
-    __syncthreads();   // (every lane gets here: the loop is left by break, never by return)
-    if (threadIdx.x == 0 && total) atomicAdd(words + kObjWordLabelled, (unsigned long long)total);
-}
+};
 
 // what a lookup reads of the handle; labels, row_mask and row_base are touched only behind a set mask bit, that is with a list
 struct ObjectsView {
@@ -170,14 +151,13 @@ int tsdf_volume_find_objects(const tsdf_volume *cv, uint32_t min_votes, const ui
     TSDF_REQUIRE(s, "%s: null objects handle", who);
     TSDF_REQUIRE(cv->classes, "%s: classes are not enabled on this volume (tsdf_volume_enable_classes)", who);
     const Geom &g = cv->g;
-    // (classes are refused on a Z-slab volume: every plane is resident)
-    TSDF_REQUIRE(!cv->slab && g.z_store_begin == 0 && g.z_store_end == g.Z, "%s: a Z-slab volume (tsdf_volume_create_slab) is not supported", who);
-    TSDF_REQUIRE((uint64_t)g.X * g.Y * g.Z <= 0xffffffffull, "%s: %u x %u x %u voxels do not fit 32-bit voxel ids", who, g.X, g.Y, g.Z);
+    // (classes are refused on a Z-slab volume: every plane is resident; only the class words are read, so the nodes do not matter)
+    const int rcv = whole_volume_checked(who, cv, s->device, nullptr, kAcceptsNodes);
+    if (rcv != TSDF_OK) return rcv;
     TSDF_REQUIRE(connectivity == 6u || connectivity == 26u, "%s: connectivity must be 6 or 26, got %u", who, connectivity);
     TSDF_REQUIRE(flags == 0, "%s: unknown flags %#x", who, flags);
     TSDF_REQUIRE(host_select || n_select == 0, "%s: null host_select with n_select = %u", who, n_select);
     TSDF_REQUIRE(n_select <= kMaxSelect, "%s: n_select %u is above 65535", who, n_select);
-    TSDF_REQUIRE(cv->device == s->device, "%s: the handle was created on device %d, the volume on device %d", who, s->device, cv->device);
     tsdf_volume *v = const_cast<tsdf_volume *>(cv);
     hipStream_t stream = v->stream;
     int rc = s->join(stream);
@@ -202,9 +182,8 @@ int tsdf_volume_find_objects(const tsdf_volume *cv, uint32_t min_votes, const ui
             std::memcpy(s->host_select, host_select, n_select);
             TSDF_HIP(hipMemcpyAsync(s->select, s->host_select, n_select, hipMemcpyHostToDevice, stream), "objects selection upload");
         }
-        const dim3 flag_grid((n_chunks + 4 * kObjFlagChunks - 1) / (4 * kObjFlagChunks));
-        hipLaunchKernelGGL(objects_flag_kernel, flag_grid, dim3(256), 0, stream, v->classes, grid.n, n_chunks, std::max(min_votes, 1u),
-                           host_select ? s->select : nullptr, n_select, s->masks, s->bases, s->words);
+        voxel_flag(LabelledFlag{v->classes, std::max(min_votes, 1u), host_select ? s->select : nullptr, n_select}, grid, n_chunks, s->masks, s->bases,
+                   s->words, stream);
         return TSDF_OK;
     }, &n64);
     if (rc != TSDF_OK) return rc;

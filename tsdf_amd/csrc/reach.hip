@@ -2,8 +2,7 @@
 // voxels in the 10-14-17 chamfer metric without corner cutting, the voxel paths back to the seeds, and the nearest voxel of every
 // frontier cluster.  No reference counterpart.  Nothing of a volume, an ESDF or an explorer is written.
 //
-//   reach_flag_kernel     TRAVERSABLE per voxel (rule 2), the ballot mask per 64 voxel ids; counted over the 64 chunks a wave walks, then
-//                         in LDS, then with one 64-bit integer atomic per workgroup (explore.hip's flag kernel)
+//   TraversableFlag       TRAVERSABLE per voxel (rule 2), the ballot mask per 64 voxel ids and the count: voxel_set.hpp's flag walk
 //   reach_init_kernel     costs to UNREACHED, the per-brick dirty words of both parities to 0
 //   reach_seed_kernel     a lane per seed: a plain store of 0 (idempotent); its brick and the bricks that see it dirty for round 0
 //   reach_relax_kernel    one round: a workgroup per brick of 8^3 voxels; a dirty brick stages its 10^3 tile (its own voxels and a halo of
@@ -95,39 +94,23 @@ __host__ __device__ constexpr uint32_t nb_needs(int k) {
 }
 constexpr uint32_t kFaceSteps = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);
 
-__global__ __launch_bounds__(256) void reach_flag_kernel(const float *__restrict__ dist, const WeightView wv, const VoxelGrid grid,
-                                                         const uint32_t n_chunks, const float *__restrict__ esdf, const float clearance,
-                                                         const int through_unknown, uint64_t *__restrict__ mask,
-                                                         unsigned long long *__restrict__ n_traversable) {
-    constexpr uint32_t kChunks = 64;   // chunks a wave walks: one atomic per workgroup and 16 384 voxels (explore.hip)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t first = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kChunks;
-    const size_t xy = (size_t)grid.X * grid.Y;
-    __shared__ uint32_t total;
-    if (threadIdx.x == 0) total = 0;
-    __syncthreads();
-    uint32_t count = 0;   // (at most 64 * kChunks)
-    for (uint32_t k = 0; k < kChunks; k++) {   // bounded: kChunks trips
-        if (first + k >= n_chunks) break;   // (the whole wave)
-        const uint32_t chunk = (uint32_t)(first + k);
-        const uint64_t id = (uint64_t)chunk * 64 + lane;
-        bool ok = false;
-        if (id < grid.n) {
-            uint32_t x, y, z;
-            grid.split((uint32_t)id, x, y, z);
-            const bool unknown = !(weight_at(wv, xy, (size_t)grid.X * y + x, z) > 0.0f);   // (true for a NaN weight)
-            // the distance is read only where the voxel is observed: NaN and both zeros are not negative
-            ok = unknown ? through_unknown != 0 : !(dist[id] < 0.0f);
-            if (ok && esdf) ok = esdf[id] >= clearance;   // (false for NaN)
-        }
-        const uint64_t m = __ballot(ok);
-        if (lane == 0) mask[chunk] = m;
-        count += (uint32_t)__popcll(m);
+// TRAVERSABLE (rule 2): not occupied -- an unknown voxel only with THROUGH_UNKNOWN -- and, with an ESDF, at least the clearance away from
+// the nearest surface.  One counter, into ReachWords::n_traversable; the mask is read by id, never listed.
+struct TraversableFlag {
+    static constexpr uint32_t kCounts = 1, kListed = 0;
+    const float *dist;
+    WeightView wv;
+    const float *esdf;
+    float clearance;
+    int through_unknown;
+    __device__ uint32_t operator()(uint32_t id, const VoxelGrid &grid) const {
+        uint32_t x, y, z;
+        grid.split(id, x, y, z);
+        bool ok = voxel_observed(wv, (size_t)grid.X * grid.Y, (size_t)grid.X * y + x, z) ? !voxel_occupied(dist, id) : through_unknown != 0;
+        if (ok && esdf) ok = esdf[id] >= clearance;   // (false for NaN)
+        return ok ? 1u : 0u;
     }
-    if (lane == 0 && count) atomicAdd(&total, count);
-    __syncthreads();   // (every lane gets here: the loop is left by break, never by return)
-    if (threadIdx.x == 0 && total) atomicAdd(n_traversable, (unsigned long long)total);
-}
+};
 
 __global__ __launch_bounds__(256) void reach_init_kernel(uint32_t *__restrict__ cost, const uint32_t n, uint32_t *__restrict__ dirty,
                                                          const uint32_t n_dirty) {
@@ -418,10 +401,7 @@ __global__ __launch_bounds__(256) void reach_unpack_kernel(const uint32_t n_rows
 
 using namespace tsdf;
 
-struct tsdf_reach {
-    int device;
-    hipEvent_t done;        // recorded behind the last call's launches
-    int pending;            // ... and not waited for yet
+struct tsdf_reach : HandleOrder {
     int computed;           // the cost array and the mask are a finished computation's of the geometry g
     Geom g;
     uint32_t *cost;         // one word per voxel id
@@ -437,33 +417,14 @@ struct tsdf_reach {
 namespace {
 
 void reach_free(tsdf_reach *s) {
-    if (s->done) (void)hipEventSynchronize(s->done);
+    s->destroy();
     device_free_all(s->cost, s->mask, s->dirty, s->keys, s->words);
     (void)hipHostFree(s->host_words);
-    if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
 
-int reach_wait(const tsdf_reach *cs) {
-    tsdf_reach *s = const_cast<tsdf_reach *>(cs);
-    if (s->pending) {
-        TSDF_HIP(hipEventSynchronize(s->done), "reach wait");
-        s->pending = 0;
-    }
-    return TSDF_OK;
-}
-
-// the caller's stream behind what is in flight on the handle / what it has just enqueued in flight on it
-int reach_join(const tsdf_reach *s, hipStream_t stream) {
-    if (s->pending) TSDF_HIP(hipStreamWaitEvent(stream, s->done, 0), "reach stream order");
-    return TSDF_OK;
-}
-int reach_leave(const tsdf_reach *cs, hipStream_t stream) {
-    tsdf_reach *s = const_cast<tsdf_reach *>(cs);
-    TSDF_HIP(hipEventRecord(s->done, stream), "reach event");
-    s->pending = 1;
-    return TSDF_OK;
-}
+// the texts of the handle's stream order (handle_order.hpp)
+constexpr const char *kReachOrder = "reach stream order", *kReachEvent = "reach event", *kReachWait = "reach wait";
 
 int reach_computed(const char *who, const tsdf_reach *s) {
     TSDF_REQUIRE(s, "%s: null handle", who);
@@ -478,16 +439,12 @@ int compute_checked(const char *who, const tsdf_volume *v, const tsdf_reach *s, 
     TSDF_REQUIRE(s, "%s: null reach handle", who);
     TSDF_REQUIRE(n == 0 || seeds, "%s: null seeds with n = %llu", who, (unsigned long long)n);
     TSDF_REQUIRE(n <= kReachMaxPoints, "%s: %llu seeds are more than a launch holds (%llu)", who, (unsigned long long)n, (unsigned long long)kReachMaxPoints);
-    const Geom &g = v->g;
-    TSDF_REQUIRE(!v->slab && g.z_store_begin == 0 && g.z_store_end == g.Z,
-                 "%s: a Z-slab volume (tsdf_volume_create_slab) is not supported: a path's voxels lie in other slabs", who);
-    TSDF_REQUIRE(!v->nodes, "%s: the volume has a materialised deformation-node array: voxel centres must be the implicit grid", who);
-    TSDF_REQUIRE((uint64_t)g.X * g.Y * g.Z <= 0xffffffffull, "%s: %u x %u x %u voxels do not fit 32-bit voxel ids", who, g.X, g.Y, g.Z);
+    const int rcv = whole_volume_checked(who, v, s->device, "a path's voxels lie in other slabs");
+    if (rcv != TSDF_OK) return rcv;
     TSDF_REQUIRE(connectivity == 6u || connectivity == 26u, "%s: connectivity must be 6 or 26, got %u", who, connectivity);
     TSDF_REQUIRE((flags & ~(uint32_t)TSDF_REACH_THROUGH_UNKNOWN) == 0, "%s: unknown flags %#x", who, flags);
     TSDF_REQUIRE(clearance >= 0.0f && clearance < INFINITY, "%s: clearance must be finite and >= 0, got %g", who, (double)clearance);
     TSDF_REQUIRE(esdf || clearance == 0.0f, "%s: a clearance (%g) needs an ESDF handle", who, (double)clearance);
-    TSDF_REQUIRE(v->device == s->device, "%s: the handle was created on device %d, the volume on device %d", who, s->device, v->device);
     *esdf_array = nullptr;
     if (esdf) {
         tsdf_esdf_info ei;
@@ -495,9 +452,7 @@ int compute_checked(const char *who, const tsdf_volume *v, const tsdf_reach *s, 
         if (rc == TSDF_OK) rc = tsdf_esdf_buffer(esdf, esdf_array);
         if (rc != TSDF_OK) return rc;
         TSDF_REQUIRE(*esdf_array, "%s: the ESDF handle has never been computed (tsdf_volume_compute_esdf)", who);
-        TSDF_REQUIRE(ei.size[0] == g.X && ei.size[1] == g.Y && ei.size[2] == g.Z && ei.voxel_size[0] == g.vs.x && ei.voxel_size[1] == g.vs.y &&
-                         ei.voxel_size[2] == g.vs.z && ei.offset[0] == g.offset.x && ei.offset[1] == g.offset.y && ei.offset[2] == g.offset.z,
-                     "%s: the ESDF was computed for another geometry (%u x %u x %u, or other voxel sizes or offset) than the volume's", who,
+        TSDF_REQUIRE(same_geometry(geometry_of(ei), v->g), "%s: the ESDF was computed for another geometry (%u x %u x %u, or other voxel sizes or offset) than the volume's", who,
                      ei.size[0], ei.size[1], ei.size[2]);
     }
     return TSDF_OK;
@@ -507,7 +462,7 @@ int compute_checked(const char *who, const tsdf_volume *v, const tsdf_reach *s, 
 int reach_on(const char *who, tsdf_volume *v, tsdf_reach *s, uint64_t n, const float *seeds, uint32_t connectivity, const float *esdf_array,
              float clearance, uint32_t max_cost, uint32_t flags) {
     hipStream_t stream = v->stream;
-    int rc = reach_join(s, stream);
+    int rc = s->join(stream, kReachOrder);
     if (rc != TSDF_OK) return rc;
     s->computed = 0;
     const VoxelGrid grid = voxel_grid(v->g);
@@ -528,9 +483,8 @@ int reach_on(const char *who, tsdf_volume *v, tsdf_reach *s, uint64_t n, const f
     const uint32_t faces_only = connectivity == 6u ? 1u : 0u;
 
     TSDF_HIP(hipMemsetAsync(s->words, 0, sizeof(ReachWords), stream), "reach counts reset");
-    const WeightView wv = {v->weight, v->wpacked, v->wmode};
-    hipLaunchKernelGGL(reach_flag_kernel, dim3((n_chunks + 4 * 64 - 1) / (4 * 64)), dim3(256), 0, stream, v->dist, wv, grid, n_chunks, esdf_array,
-                       clearance, (flags & TSDF_REACH_THROUGH_UNKNOWN) ? 1 : 0, s->mask, &s->words->n_traversable);
+    voxel_flag(TraversableFlag{v->dist, {v->weight, v->wpacked, v->wmode}, esdf_array, clearance, (flags & TSDF_REACH_THROUGH_UNKNOWN) ? 1 : 0}, grid,
+               n_chunks, s->mask, nullptr, &s->words->n_traversable, stream);
     hipLaunchKernelGGL(reach_init_kernel, grid_for(((uint64_t)max(grid.n, n_dirty) + 3) / 4, 256), dim3(256), 0, stream, s->cost, grid.n, s->dirty, n_dirty);
     if (n) hipLaunchKernelGGL(reach_seed_kernel, grid_for(n, 256), dim3(256), 0, stream, v->g, nb, n, seeds, s->mask, s->cost, s->dirty);
     TSDF_HIP(hipGetLastError(), "reach setup kernels failed");
@@ -612,10 +566,7 @@ int rank_checked(const char *who, const tsdf_reach *s, const tsdf_explorer *ex, 
     rc = tsdf_explorer_get_info(ex, &ei);
     if (rc != TSDF_OK) return rc;
     TSDF_REQUIRE(ei.connectivity != 0u, "%s: the explorer has not been clustered since its last tsdf_volume_find_frontiers (tsdf_explorer_cluster_frontiers)", who);
-    const Geom &g = s->g;
-    TSDF_REQUIRE(ei.size[0] == g.X && ei.size[1] == g.Y && ei.size[2] == g.Z && ei.voxel_size[0] == g.vs.x && ei.voxel_size[1] == g.vs.y &&
-                     ei.voxel_size[2] == g.vs.z && ei.offset[0] == g.offset.x && ei.offset[1] == g.offset.y && ei.offset[2] == g.offset.z,
-                 "%s: the explorer holds another geometry (%u x %u x %u, or other voxel sizes or offset) than the reach handle's", who, ei.size[0],
+    TSDF_REQUIRE(same_geometry(geometry_of(ei), s->g), "%s: the explorer holds another geometry (%u x %u x %u, or other voxel sizes or offset) than the reach handle's", who, ei.size[0],
                  ei.size[1], ei.size[2]);
     TSDF_REQUIRE(ei.n_listed_clusters == 0 || out, "%s: null output for %llu clusters", who, (unsigned long long)ei.n_listed_clusters);
     in->n_list = (uint32_t)ei.n_frontiers;
@@ -627,7 +578,7 @@ int rank_checked(const char *who, const tsdf_reach *s, const tsdf_explorer *ex, 
 
 int rank_on(tsdf_reach *s, const RankInput &in, tsdf_reach_cluster *out, hipStream_t stream) {
     if (in.n_rows == 0) return TSDF_OK;
-    int rc = reach_join(s, stream);
+    int rc = s->join(stream, kReachOrder);
     if (rc != TSDF_OK) return rc;
     const hipError_t e = device_reserve(s->keys, s->keys_cap, (size_t)in.n_rows);
     if (e != hipSuccess) return hip_fail(e, "reach rank alloc failed");
@@ -635,7 +586,7 @@ int rank_on(tsdf_reach *s, const RankInput &in, tsdf_reach_cluster *out, hipStre
     hipLaunchKernelGGL(reach_rank_kernel, grid_for(in.n_list, 256), dim3(256), 0, stream, in.n_list, in.list, in.labels, in.table, in.n_rows, s->cost, s->keys);
     hipLaunchKernelGGL(reach_unpack_kernel, grid_for(in.n_rows, 256), dim3(256), 0, stream, in.n_rows, in.table, s->keys, out);
     TSDF_HIP(hipGetLastError(), "reach rank kernels failed");
-    return reach_leave(s, stream);
+    return s->leave(stream, kReachEvent);
 }
 
 }  // namespace
@@ -651,8 +602,7 @@ int tsdf_reach_create(tsdf_reach **out) {
         return TSDF_ERR_NOMEM;
     }
     std::memset(s, 0, sizeof(*s));
-    hipError_t e = hipGetDevice(&s->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+    hipError_t e = s->create();
     if (e == hipSuccess) e = hipMalloc((void **)&s->words, sizeof(ReachWords));
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->host_words, sizeof(ReachWords), hipHostMallocDefault);
     if (e != hipSuccess) {
@@ -701,7 +651,7 @@ int tsdf_reach_get_info(const tsdf_reach *s, tsdf_reach_info *info) {
 
 int tsdf_reach_buffer(const tsdf_reach *s, const uint32_t **device_costs) {
     TSDF_REQUIRE(s && device_costs, "tsdf_reach_buffer: null argument");
-    const int rc = reach_wait(s);
+    const int rc = s->wait(kReachWait);
     if (rc != TSDF_OK) return rc;
     *device_costs = s->computed ? s->cost : nullptr;
     return TSDF_OK;
@@ -710,7 +660,7 @@ int tsdf_reach_buffer(const tsdf_reach *s, const uint32_t **device_costs) {
 int tsdf_reach_download(const tsdf_reach *s, uint32_t *host_costs) {
     TSDF_REQUIRE(s && host_costs, "tsdf_reach_download: null argument");
     TSDF_REQUIRE(s->computed, "tsdf_reach_download: the handle has never been computed (tsdf_volume_compute_reach)");
-    const int rc = reach_wait(s);
+    const int rc = s->wait(kReachWait);
     if (rc != TSDF_OK) return rc;
     const size_t n = (size_t)s->g.X * s->g.Y * s->g.Z;
     if (n) TSDF_HIP(hipMemcpy(host_costs, s->cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "reach download");
@@ -729,11 +679,11 @@ int tsdf_reach_lookup_device(const tsdf_reach *s, uint64_t n, const float *devic
     if (rc != TSDF_OK) return rc;
     if (n == 0) return TSDF_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = reach_join(s, stream);
+    rc = s->join(stream, kReachOrder);
     if (rc != TSDF_OK) return rc;
     hipLaunchKernelGGL(reach_lookup_kernel, grid_for(n, 256), dim3(256), 0, stream, s->g, n, device_points, s->cost, device_costs);
     TSDF_HIP(hipGetLastError(), "reach lookup kernel failed");
-    return reach_leave(s, stream);
+    return s->leave(stream, kReachEvent);
 }
 
 int tsdf_reach_lookup(const tsdf_reach *s, uint64_t n, const float *host_points, uint32_t *host_costs) {
@@ -758,12 +708,12 @@ int tsdf_reach_paths_device(const tsdf_reach *s, uint64_t n, const float *device
     if (rc != TSDF_OK) return rc;
     if (n == 0) return TSDF_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = reach_join(s, stream);
+    rc = s->join(stream, kReachOrder);
     if (rc != TSDF_OK) return rc;
     hipLaunchKernelGGL(reach_paths_kernel, grid_for(n, 256), dim3(256), 0, stream, s->g, n, device_goals, s->cost, s->mask,
                        s->info.connectivity == 6u ? 1u : 0u, max_len, device_lengths, device_rows);
     TSDF_HIP(hipGetLastError(), "reach paths kernel failed");
-    return reach_leave(s, stream);
+    return s->leave(stream, kReachEvent);
 }
 
 int tsdf_reach_paths(const tsdf_reach *s, uint64_t n, const float *host_goals, uint32_t max_len, uint32_t *host_lengths, uint32_t *host_rows) {

@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "field_sample.hpp"
+#include "handle_order.hpp"
 #include "mesh_handle.hpp"
 
 namespace tsdf {
@@ -237,10 +238,7 @@ __global__ __launch_bounds__(512) void snapshot_scatter_kernel(float *__restrict
 
 using namespace tsdf;
 
-struct tsdf_snapshot {
-    int device;
-    hipEvent_t done;        // recorded behind whatever was enqueued last on the handle
-    int pending;            // ... and not waited for yet
+struct tsdf_snapshot : HandleOrder {
     int filled;             // a snapshot or an upload has gone into the handle
     uint32_t *ids;
     float *dist;
@@ -259,28 +257,14 @@ struct tsdf_snapshot {
 namespace {
 
 void snapshot_free(tsdf_snapshot *s) {
-    if (s->done) (void)hipEventSynchronize(s->done);
+    s->destroy();
     device_free_all(s->ids, s->dist, s->weights, s->colours, s->flags, s->map, s->parts);
     (void)hipHostFree(s->total_host);
-    if (s->done) (void)hipEventDestroy(s->done);
     delete s;
 }
 
-int snapshot_wait(const tsdf_snapshot *cs) {
-    tsdf_snapshot *s = const_cast<tsdf_snapshot *>(cs);
-    if (s->pending) {
-        TSDF_HIP(hipEventSynchronize(s->done), "snapshot wait");
-        s->pending = 0;
-    }
-    return TSDF_OK;
-}
-
-int snapshot_leave(const tsdf_snapshot *cs, hipStream_t stream) {
-    tsdf_snapshot *s = const_cast<tsdf_snapshot *>(cs);
-    TSDF_HIP(hipEventRecord(s->done, stream), "snapshot event");
-    s->pending = 1;
-    return TSDF_OK;
-}
+// the texts of the handle's stream order (handle_order.hpp)
+constexpr const char *kSnapOrder = "snapshot stream order", *kSnapEvent = "snapshot event", *kSnapWait = "snapshot wait";
 
 uint64_t brick_count(const uint32_t size[3], uint32_t nb[3]) {
     for (int a = 0; a < 3; a++) nb[a] = (size[a] + kSnapBrick - 1) / kSnapBrick;
@@ -322,8 +306,7 @@ int tsdf_snapshot_create(tsdf_snapshot **out) {
         return TSDF_ERR_NOMEM;
     }
     std::memset(s, 0, sizeof(*s));
-    hipError_t e = hipGetDevice(&s->device);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+    hipError_t e = s->create();
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->total_host, sizeof(uint64_t), hipHostMallocDefault);
     if (e != hipSuccess) {
         snapshot_free(s);
@@ -357,7 +340,8 @@ int tsdf_volume_snapshot(const tsdf_volume *cv, uint32_t flags, tsdf_snapshot *s
     info.fill_distance = g.trunc;
     info.voxel_size[0] = g.vs.x; info.voxel_size[1] = g.vs.y; info.voxel_size[2] = g.vs.z;
     info.offset[0] = g.offset.x; info.offset[1] = g.offset.y; info.offset[2] = g.offset.z;
-    if (s->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, s->done, 0), "snapshot stream order");   // what is in flight on the handle
+    const int rcj = s->join(v->stream, kSnapOrder);   // what is in flight on the handle
+    if (rcj != TSDF_OK) return rcj;
     s->filled = 0;
     const uint32_t n_parts = mesh_scan_parts((uint32_t)total);
     hipError_t e = device_reserve(s->flags, s->flags_cap, (size_t)total);
@@ -386,7 +370,7 @@ int tsdf_volume_snapshot(const tsdf_volume *cv, uint32_t flags, tsdf_snapshot *s
                            s->dist, s->weights, s->colours);
     TSDF_HIP(hipGetLastError(), "snapshot gather kernels failed");
     s->filled = 1;
-    return snapshot_leave(s, v->stream);
+    return s->leave(v->stream, kSnapEvent);
 }
 
 int tsdf_volume_restore(tsdf_volume *v, const tsdf_snapshot *s) {
@@ -413,7 +397,8 @@ int tsdf_volume_restore(tsdf_volume *v, const tsdf_snapshot *s) {
         rc = tsdf_volume_enable_colour(v, 1);
         if (rc != TSDF_OK) return rc;
     }
-    if (s->pending) TSDF_HIP(hipStreamWaitEvent(v->stream, s->done, 0), "snapshot stream order");
+    rc = s->join(v->stream, kSnapOrder);
+    if (rc != TSDF_OK) return rc;
     v->occ_dirty = 1;
     v->occ_scan_all = 1;
     v->prepared_valid = 0;
@@ -424,12 +409,12 @@ int tsdf_volume_restore(tsdf_volume *v, const tsdf_snapshot *s) {
     hipLaunchKernelGGL(snapshot_scatter_kernel, dim3((sg.nbx + kScatterBricks - 1) / kScatterBricks, sg.nby, sg.nbz), dim3(64 * 2 * kScatterBricks), 0, v->stream, v->dist, v->weight, v->wpacked, v->wmode, v->colour, sg, fill_bits,
                        s->map, s->dist, s->weights, (int)info.weight_bits, (info.flags & TSDF_SNAPSHOT_COLOUR) ? s->colours : nullptr);
     TSDF_HIP(hipGetLastError(), "snapshot scatter kernel failed");
-    return snapshot_leave(s, v->stream);   // the handle's arrays are read by what has just been enqueued
+    return s->leave(v->stream, kSnapEvent);   // the handle's arrays are read by what has just been enqueued
 }
 
 int tsdf_snapshot_get_info(const tsdf_snapshot *s, tsdf_snapshot_info *info) {
     TSDF_REQUIRE(s && info, "tsdf_snapshot_get_info: null argument");
-    const int rc = snapshot_wait(s);
+    const int rc = s->wait(kSnapWait);
     if (rc != TSDF_OK) return rc;
     *info = s->info;
     return TSDF_OK;
@@ -439,7 +424,7 @@ int tsdf_snapshot_buffers(const tsdf_snapshot *s, const uint32_t **device_bricks
                           const uint32_t **device_colours) {
     TSDF_REQUIRE(s && device_bricks && device_distances && device_weights && device_colours, "tsdf_snapshot_buffers: null argument");
     TSDF_REQUIRE(s->filled, "tsdf_snapshot_buffers: the handle has never been filled (tsdf_volume_snapshot, tsdf_snapshot_upload)");
-    const int rc = snapshot_wait(s);
+    const int rc = s->wait(kSnapWait);
     if (rc != TSDF_OK) return rc;
     const bool any = s->info.n_bricks != 0;
     *device_bricks = any ? s->ids : nullptr;
@@ -454,7 +439,7 @@ int tsdf_snapshot_download(const tsdf_snapshot *s, uint32_t *host_bricks, float 
     TSDF_REQUIRE(s->filled, "tsdf_snapshot_download: the handle has never been filled (tsdf_volume_snapshot, tsdf_snapshot_upload)");
     const bool colour = (s->info.flags & TSDF_SNAPSHOT_COLOUR) != 0;
     TSDF_REQUIRE(host_bricks && host_distances && host_weights && (host_colours || !colour), "tsdf_snapshot_download: null argument");
-    const int rc = snapshot_wait(s);
+    const int rc = s->wait(kSnapWait);
     if (rc != TSDF_OK) return rc;
     const size_t n = (size_t)s->info.n_bricks, nv = n * kSnapVoxels;
     if (n == 0) return TSDF_OK;
@@ -503,7 +488,7 @@ int tsdf_snapshot_upload(tsdf_snapshot *s, const tsdf_snapshot_info *in, const u
     info.weight_bound = top;
     info.bytes = snapshot_bytes(info);
 
-    int rc = snapshot_wait(s);
+    int rc = s->wait(kSnapWait);
     if (rc != TSDF_OK) return rc;
     s->filled = 0;
     s->info = info;

@@ -1,7 +1,9 @@
-// Voxel ids and the per-chunk masks over them, shared by voxel_set.hpp (the list and the clusters of a voxel set), explore.hip (its
-// flag kernel marks the frontier voxels) and objects.hip (its flag kernel marks the labelled voxels, its lookup reads the masks): voxel
-// (x, y, z) of an X x Y x Z grid has id (z * Y + y) * X + x, 64 consecutive ids are a chunk, and a chunk's 64-bit mask says which of its
-// voxels are listed (store_keep_mask and compact_index, mesh_device.hpp, write the masks and turn an id into a list index).
+// Voxel ids and the per-chunk masks over them, shared by voxel_set.hpp (the flag walk, the list and the clusters of a voxel set) and
+// its users explore.hip (frontier voxels), objects.hip (labelled voxels; its lookup reads the masks) and reach.hip (traversable voxels;
+// its seeds, tiles and paths read the mask): voxel (x, y, z) of an X x Y x Z grid has id (z * Y + y) * X + x, 64 consecutive ids are a
+// chunk, and a chunk's 64-bit mask says which of its voxels are listed (compact_index, mesh_device.hpp, turns an id into a list index).
+// The host side of the handles that walk a volume by voxel id, esdf.hip included: which volumes they refuse (whole_volume_checked) and
+// the geometry they hold and report (geometry_into, geometry_of, same_geometry).
 // And the voxel a world point lies in, which the samplers of the per-voxel words (colour.hip, classes.hip) and objects.hip's lookup share.
 #pragma once
 
@@ -23,6 +25,46 @@ struct VoxelGrid {
 __device__ inline bool mask_bit(const uint64_t *__restrict__ mask, uint32_t id) { return (mask[id >> 6] >> (id & 63u)) & 1u; }
 
 inline VoxelGrid voxel_grid(const Geom &g) { return {g.X, g.Y, g.Z, (uint32_t)((uint64_t)g.X * g.Y * g.Z)}; }
+
+// ---- the host side: which volumes a handle takes, and whose geometry it holds ------------------------------------------------------
+// What an entry point that walks a volume's voxels by id refuses, under its own name `who`: a Z-slab (why_not_slab, if given, says
+// what of the caller's lies in other slabs), a materialised deformation-node array, more voxels than 32-bit ids hold, and a handle
+// of another device.  v is not null.  `accepts`: what this caller has always taken -- objects.hip reads only the class words, so the
+// nodes do not matter to it; esdf.hip indexes with size_t.
+enum : unsigned { kAcceptsNodes = 1u, kAcceptsWideIds = 2u };
+inline int whole_volume_checked(const char *who, const tsdf_volume *v, int handle_device, const char *why_not_slab, unsigned accepts = 0u) {
+    const Geom &g = v->g;
+    TSDF_REQUIRE(!v->slab && g.z_store_begin == 0 && g.z_store_end == g.Z, "%s: a Z-slab volume (tsdf_volume_create_slab) is not supported%s%s", who,
+                 why_not_slab ? ": " : "", why_not_slab ? why_not_slab : "");
+    TSDF_REQUIRE((accepts & kAcceptsNodes) || !v->nodes,
+                 "%s: the volume has a materialised deformation-node array: voxel centres must be the implicit grid", who);
+    TSDF_REQUIRE((accepts & kAcceptsWideIds) || (uint64_t)g.X * g.Y * g.Z <= 0xffffffffull, "%s: %u x %u x %u voxels do not fit 32-bit voxel ids", who,
+                 g.X, g.Y, g.Z);
+    TSDF_REQUIRE(v->device == handle_device, "%s: the handle was created on device %d, the volume on device %d", who, handle_device, v->device);
+    return TSDF_OK;
+}
+
+// the geometry as every info struct reports it, and back (the fields no info carries stay zero)
+template <class Info>
+void geometry_into(Info &info, const Geom &g) {
+    info.size[0] = g.X; info.size[1] = g.Y; info.size[2] = g.Z;
+    info.voxel_size[0] = g.vs.x; info.voxel_size[1] = g.vs.y; info.voxel_size[2] = g.vs.z;
+    info.offset[0] = g.offset.x; info.offset[1] = g.offset.y; info.offset[2] = g.offset.z;
+}
+template <class Info>
+Geom geometry_of(const Info &info) {
+    Geom g = {};
+    g.X = info.size[0]; g.Y = info.size[1]; g.Z = info.size[2];
+    g.vs = {info.voxel_size[0], info.voxel_size[1], info.voxel_size[2]};
+    g.offset = {info.offset[0], info.offset[1], info.offset[2]};
+    return g;
+}
+
+// the same grid, voxel sizes and offset: what a handle's arrays and another's can be read together for
+inline bool same_geometry(const Geom &a, const Geom &b) {
+    return a.X == b.X && a.Y == b.Y && a.Z == b.Z && a.vs.x == b.vs.x && a.vs.y == b.vs.y && a.vs.z == b.vs.z && a.offset.x == b.offset.x &&
+           a.offset.y == b.offset.y && a.offset.z == b.offset.z;
+}
 
 // The voxel a world point lies in, in the frame colour and class words are sampled in (include/tsdf_amd.h, "class fusion", Sampling):
 // i = (int)floorf(((p - offset) - offset_at_clear) / voxel_size) per axis, the cell whose centre, as integrate forms it, is nearest.

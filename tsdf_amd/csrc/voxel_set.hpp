@@ -1,6 +1,8 @@
-// A set of voxels, listed and clustered: what explore.hip (frontier voxels, any two listed neighbours adjacent) and
-// objects.hip (voxels with class votes, adjacent when their classes are equal) share.  The user's own flag kernel writes a ballot mask
-// and a popcount per chunk of 64 voxel ids and counts the set; from there on the chain is the same:
+// A set of voxels, flagged, listed and clustered: what explore.hip (frontier voxels, any two listed neighbours
+// adjacent), objects.hip (voxels with class votes, adjacent when their classes are equal) and reach.hip (traversable voxels: the flag
+// walk and its masks only) share.  The user gives the test of one voxel; the chain is the same:
+//   voxel_flag_kernel     the user's Flag per voxel id; per chunk of 64 ids the ballot mask and, for a set that is listed, its popcount;
+//                         the counts over the 64 chunks a wave walks, one integer atomic per counter and workgroup that has any
 //   (the chunk scan of mesh_scan.hip turns the popcounts into bases)
 //   voxel_list_kernel     list[compact_index(mask, base, id)] = id: ascending, no atomics, one writer per word
 // Clusters: the union-find of union_find.hpp over the list indices, a lane per listed voxel.
@@ -48,6 +50,57 @@ struct SameClass {
     __device__ uint32_t word(uint32_t id) const { return cls[id]; }
     __device__ bool adjacent(uint32_t own_word, uint32_t id2) const { return (cls[id2] & 0xFFFFu) == (own_word & 0xFFFFu); }
 };
+
+// ---- the flag walk -----------------------------------------------------------------------------------------------------------------
+// A wave walks kFlagChunks consecutive chunks and adds its counts up in registers, the four waves of a workgroup add theirs up in LDS
+// (integer atomics), and every counter sees one atomic per workgroup and 16 384 voxels.  With one per chunk, two million waves queue
+// on the same four words at 512^3 and the frontier walk takes 31 ms; with one per wave and 32 chunks, 1.5 ms, still twice
+// esdf_sites_kernel.
+constexpr uint32_t kFlagChunks = 64;
+
+// Flag: a small struct passed by value.  flag(id, grid), for a voxel id below grid.n, returns one bit per counter: bit k counts into
+// words[k], k < Flag::kCounts, and bit Flag::kListed is the voxel's bit in mask[chunk].  base: the popcount per chunk for the chunk
+// scan, or null for a set that is never listed.  No bit beyond the grid is ever set.
+template <class Flag>
+__global__ __launch_bounds__(256) void voxel_flag_kernel(const Flag flag, const VoxelGrid grid, const uint32_t n_chunks, uint64_t *__restrict__ mask,
+                                                         uint32_t *__restrict__ base, unsigned long long *__restrict__ words) {
+    constexpr uint32_t kCounts = Flag::kCounts;
+    static_assert(Flag::kListed < kCounts && kCounts <= 32, "a bit per counter, the listed one among them");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t first = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kFlagChunks;
+    __shared__ uint32_t totals[kCounts];
+    if (threadIdx.x < kCounts) totals[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t counts[kCounts] = {};   // (at most 64 * kFlagChunks each)
+    for (uint32_t k = 0; k < kFlagChunks; k++) {   // bounded: kFlagChunks trips
+        if (first + k >= n_chunks) break;   // (the whole wave)
+        const uint32_t chunk = (uint32_t)(first + k);
+        const uint64_t id = (uint64_t)chunk * 64 + lane;
+        const uint32_t bits = id < grid.n ? flag((uint32_t)id, grid) : 0u;
+        const uint64_t listed = __ballot((bits >> Flag::kListed) & 1u);
+        if (lane == 0) {
+            mask[chunk] = listed;
+            if (base) base[chunk] = (uint32_t)__popcll(listed);
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < kCounts; c++) counts[c] += (uint32_t)__popcll(c == Flag::kListed ? listed : __ballot((bits >> c) & 1u));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t c = 0; c < kCounts; c++)
+            if (counts[c]) atomicAdd(&totals[c], counts[c]);
+    }
+    __syncthreads();   // (every lane gets here: the loop is left by break, never by return)
+    if (threadIdx.x < kCounts && totals[threadIdx.x]) atomicAdd(words + threadIdx.x, (unsigned long long)totals[threadIdx.x]);
+}
+
+// its launch: a workgroup per 4 * kFlagChunks chunks
+template <class Flag>
+void voxel_flag(const Flag &flag, const VoxelGrid &grid, uint32_t n_chunks, uint64_t *mask, uint32_t *base, unsigned long long *words,
+                hipStream_t stream) {
+    hipLaunchKernelGGL(voxel_flag_kernel<Flag>, dim3((n_chunks + 4 * kFlagChunks - 1) / (4 * kFlagChunks)), dim3(256), 0, stream, flag, grid, n_chunks,
+                       mask, base, words);
+}
 
 static __global__ __launch_bounds__(256) void voxel_list_kernel(const uint32_t n_chunks, const uint64_t *__restrict__ mask,
                                                                 const uint32_t *__restrict__ base, uint32_t *__restrict__ list) {
@@ -195,16 +248,13 @@ struct VoxelSetText {
     const char *cluster_alloc, *cluster_kernels, *cluster_download, *cluster_count, *table_alloc, *rows_kernel;   // voxel_set_cluster
 };
 
-// What the two handles have in common.  The flag kernel fills the first kFlagWords of the kWords counter words, the set's size last;
+// What the two listed sets' handles have in common.  The flag kernel fills the first kFlagWords of the kWords counter words, the set's size last;
 // then come the roots and the total of the last chunk scan.  Plain data: a handle is value-initialised to zero, then create()d.
 template <class RowType, uint32_t kFlagWords, uint32_t kWords>
-struct VoxelSet {
+struct VoxelSet : HandleOrder {
     using Row = RowType;
     static constexpr uint32_t kCounterWords = kWords, kWordCounted = kFlagWords - 1, kWordRoots = kFlagWords, kWordTotal = kFlagWords + 1;
     static_assert(kWordTotal < kWords, "the counter words hold the flag kernel's, the roots and the scan's total");
-    int device;
-    hipEvent_t done;        // recorded behind the last call's launches
-    int pending;            // ... and not waited for yet
     const VoxelSetText *text;
     Geom g;                 // the geometry the arrays belong to
     uint64_t *masks;        // one mask of listed voxels per 64 voxel ids
@@ -222,8 +272,7 @@ struct VoxelSet {
 
     hipError_t create(const VoxelSetText *names) {
         text = names;
-        hipError_t e = hipGetDevice(&device);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+        hipError_t e = HandleOrder::create();
         if (e == hipSuccess) e = hipMalloc((void **)&words, kWords * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipHostMalloc((void **)&host_words, kWords * sizeof(unsigned long long), hipHostMallocDefault);
         if (e == hipSuccess) std::memset(host_words, 0, kWords * sizeof(unsigned long long));
@@ -232,30 +281,15 @@ struct VoxelSet {
 
     // waits for what is in flight, then frees everything above (a half-created handle too)
     void release() {
-        if (done) (void)hipEventSynchronize(done);
+        destroy();
         device_free_all(masks, bases, parts, list, labels, acc, row_masks, row_bases, rows, words);
         (void)hipHostFree(host_words);
-        if (done) (void)hipEventDestroy(done);
     }
 
-    // the stream waits for what is in flight on the handle / what has just been enqueued is in flight on it / the host waits for it
-    int join(hipStream_t stream) {
-        if (pending) TSDF_HIP(hipStreamWaitEvent(stream, done, 0), text->order);
-        return TSDF_OK;
-    }
-    int leave(hipStream_t stream) {
-        TSDF_HIP(hipEventRecord(done, stream), text->event);
-        pending = 1;
-        return TSDF_OK;
-    }
-    int wait() const {
-        VoxelSet *s = const_cast<VoxelSet *>(this);
-        if (s->pending) {
-            TSDF_HIP(hipEventSynchronize(s->done), text->wait);
-            s->pending = 0;
-        }
-        return TSDF_OK;
-    }
+    // the handle's stream order (handle_order.hpp), under the user's texts
+    int join(hipStream_t stream) const { return HandleOrder::join(stream, text->order); }
+    int leave(hipStream_t stream) const { return HandleOrder::leave(stream, text->event); }
+    int wait() const { return HandleOrder::wait(text->wait); }
 
     // the device bytes besides the list, the labels and the table
     uint64_t scratch_bytes() const {
@@ -265,17 +299,9 @@ struct VoxelSet {
     }
 };
 
-// the geometry as both info structs report it
-template <class Info>
-void geometry_into(Info &info, const Geom &g) {
-    info.size[0] = g.X; info.size[1] = g.Y; info.size[2] = g.Z;
-    info.voxel_size[0] = g.vs.x; info.voxel_size[1] = g.vs.y; info.voxel_size[2] = g.vs.z;
-    info.offset[0] = g.offset.x; info.offset[1] = g.offset.y; info.offset[2] = g.offset.z;
-}
-
-// The list of a grid's voxels that flag(n_chunks) -- the user's launch, behind whatever it has to do once the scratch is there -- marks
-// in s->masks and counts in s->bases and s->words: the chunk scan, the one synchronisation (the list is sized from the count), the
-// list.  *n_list is also s->host_words[kWordTotal], and the flag kernel's words are in s->host_words.  Joining and leaving are the
+// The list of a grid's voxels that flag(n_chunks) -- the user's voxel_flag launch, behind whatever it has to do once the scratch is
+// there -- marks in s->masks and counts in s->bases and s->words: the chunk scan, the one synchronisation (the list is sized from the
+// count), the list.  *n_list is also s->host_words[kWordTotal], and the flag kernel's words are in s->host_words.  Joining and leaving are the
 // caller's.
 template <class Set, class Flag>
 int voxel_set_list(Set *s, const char *who, const char *noun, const VoxelGrid &grid, hipStream_t stream, Flag flag, uint64_t *n_list) {
