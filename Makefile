@@ -58,7 +58,7 @@ $(LIBDIR)/libtsdf_hip.so: $(HIP_OBJS)
 oracle:
 	$(MAKE) -C oracle -s all
 
-CPPTESTS  = surface colour classes weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf explore reach objects components simplify smooth scene_flow snapshot weighted
+CPPTESTS  = surface colour classes weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf explore reach objects components simplify smooth scene_flow snapshot weighted rolling
 cpptest: $(CPPTESTS:%=build/test_%) build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
@@ -87,8 +87,15 @@ sanitize-device-buffer: tests/cpp/device_buffer_host.cpp $(CSRC)/device_buffer.h
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -Iinclude -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/device_buffer_host.cpp -o build/device_buffer_host
 	build/device_buffer_host
 
+# The same for brick_shift.hpp (the rolling volume's brick arithmetic: shifts at the ends of the int32 range, formed in 64 bits).  The
+# argument checks of tsdf_snapshot_select / tsdf_volume_shift live in snapshot.hip, which does not link without the rest of the library.
+sanitize-rolling: tests/cpp/rolling_host.cpp $(CSRC)/brick_shift.hpp
+	@mkdir -p build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/rolling_host.cpp -o build/rolling_host
+	build/rolling_host
+
 clean:
 	rm -f $(HIP_OBJS) $(HOST_OBJS) $(LIBDIR)/*.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all hip host oracle cpptest clean sanitize-scene-flow sanitize-device-buffer
+.PHONY: all hip host oracle cpptest clean sanitize-scene-flow sanitize-device-buffer sanitize-rolling

@@ -1626,8 +1626,8 @@ int tsdf_objects_scratch_bytes(const tsdf_objects *objects, uint64_t *bytes);
  *   Refused (TSDF_ERR_INVALID, with a message naming the function): NULL arguments (host_colours / device_colours results aside when
  *     there is no colour); flags other than 0; a Z-slab volume; a materialised deformation-node array; restore into a grid of another
  *     size; restore, download or buffers from a handle that was never filled.  tsdf_snapshot_destroy(NULL) is ignored.
- *   Out of scope: shifting bricks on restore, a box of the grid, merging into live data (tsdf_volume_fuse), Z-slabs, deformation
- *     nodes, compression, incremental snapshots. */
+ *   Out of scope: merging into live data (tsdf_volume_fuse), Z-slabs, deformation nodes, compression, incremental snapshots.
+ *     (Shifting bricks on restore and a box of the list are the next group, "rolling volume".) */
 typedef struct tsdf_snapshot tsdf_snapshot;
 #define TSDF_SNAPSHOT_BRICK 8
 #define TSDF_SNAPSHOT_COLOUR 1u            /* info.flags: colour words are carried */
@@ -1658,6 +1658,49 @@ int tsdf_snapshot_upload(tsdf_snapshot *snapshot, const tsdf_snapshot_info *info
                          const float *host_distances, const void *host_weights, const uint32_t *host_colours);
 /* Device bytes the handle holds besides the four arrays. */
 int tsdf_snapshot_scratch_bytes(const tsdf_snapshot *snapshot, uint64_t *bytes);
+
+/* ---- rolling volume (no reference counterpart: the reference's volume stays where it was made) ------------------------------------ */
+/* A volume that follows the camera: a shift by whole bricks is a snapshot put back at other brick coordinates, the bricks that fall out
+ * are themselves a snapshot (to keep on the host, write to a .tsdfs file, mesh later, or page back in when the camera returns).  No
+ * voxel is resampled: whole words move, there are no atomics, every output word has one writer, every run gives the same bytes.
+ *   tsdf_volume_restore_shifted: nbS is the snapshot's brick grid, nbD the volume's.  Destination brick bD takes source brick
+ *     bS = bD - brick_shift per axis (formed in 64 bits: every int32 shift is served).  The copy happens iff bS lies in [0, nbS) on every
+ *     axis and is stored in the snapshot; then every voxel of bD inside the destination grid takes the snapshot's word at the same local
+ *     position lx + 8 ly + 64 lz -- positions of a partial source brick beyond the source grid hold fill, 0 and 0 and are written as
+ *     such -- and voxels of bD beyond the destination grid are not written.  Without flags every other voxel of the volume gets the
+ *     cleared state (the snapshot's fill_distance, weight 0, colour 0), as after tsdf_volume_restore; with TSDF_RESTORE_KEEP_OTHERS every
+ *     other voxel keeps its bits (paging in), and the launch is over the snapshot's list, not over the grid.  The two grid sizes need
+ *     not be equal: a shifted restore into a smaller or larger grid crops or grows a volume.  Voxel sizes and offsets are neither
+ *     compared nor touched.  Storage, colour and flags follow tsdf_volume_restore: weight storage widens and never narrows, a snapshot
+ *     with colour enables colour, the occupancy flags are rebuilt from everything and a prepared brick list is discarded.  Under
+ *     KEEP_OTHERS widening carries the data already in the volume, weight_bound becomes the larger of the two, and a snapshot without
+ *     colour writes colour 0 on the bricks it writes only.  A zero shift into a grid of the snapshot's size without flags leaves the
+ *     state tsdf_volume_restore leaves.
+ *   tsdf_snapshot_select: dst becomes the snapshot of those bricks of src whose brick coordinates lie inside the box [lo, hi) -- with
+ *     TSDF_SELECT_OUTSIDE, outside it.  Ids are unchanged and still ascending, each brick's 512-word rows are copied; geometry, flags,
+ *     weight_bits, fill_distance and weight_bound are src's, n_bricks and bytes are new; an empty result is a filled handle with
+ *     n_bricks == 0.  Runs on the null stream, ordered against both handles by their events, and synchronises once, to size dst; a warm
+ *     dst that is large enough allocates nothing.
+ *   tsdf_volume_shift: the box moves by box_shift bricks in the world, the content stays where it is in the world.  In order: the
+ *     volume is snapshotted into work; leaving (if not NULL) gets the bricks b of work for which b - box_shift is outside [0, nb) on some
+ *     axis, its info.offset the old offset, so that brick b sits at offset + 8 b voxel_size; tsdf_volume_restore_shifted(volume, work,
+ *     -box_shift, 0); offset[k] = offset[k] + (float)(8 * box_shift[k]) * voxel_size[k] in fp32, with the effects of
+ *     tsdf_volume_set_offset.  offset_at_clear is not touched: integrate forms a centre as (((i + 0.5f) vs) + offset_at_clear) + offset,
+ *     the ray cast and the queries use offset, so moving offset alone moves every frame together.  An all-zero shift writes nothing of
+ *     the volume (leaving, if given, is filled empty).
+ *   Refused (TSDF_ERR_INVALID, with a message naming the function): NULL arguments (leaving aside); unknown flags; a Z-slab volume; a
+ *     materialised deformation-node array; handles on other devices; a handle that was never filled; dst == src; leaving == work;
+ *     tsdf_volume_shift of a grid whose size is not a multiple of 8 on every axis (voxels cut off at a partial border would be lost
+ *     without appearing in leaving; tsdf_volume_restore_shifted still serves such grids) or of a volume with classes enabled
+ *     (snapshots do not carry class words: they would stay behind while the geometry moves).
+ *   Out of scope: the tracker and tsdf_pipeline_*, kinfu_stream, class words, Z-slabs, shifts by less than a brick, a shift in place
+ *     without the snapshot round trip. */
+#define TSDF_RESTORE_KEEP_OTHERS 1u        /* tsdf_volume_restore_shifted: voxels of bricks that are not written keep their bits */
+#define TSDF_SELECT_OUTSIDE 1u             /* tsdf_snapshot_select: the bricks outside the box */
+int tsdf_volume_restore_shifted(tsdf_volume *volume, const tsdf_snapshot *snapshot, const int32_t brick_shift[3], uint32_t flags);
+int tsdf_snapshot_select(const tsdf_snapshot *src, const int32_t lo[3], const int32_t hi[3], uint32_t flags, tsdf_snapshot *dst);
+/* leaving may be NULL */
+int tsdf_volume_shift(tsdf_volume *volume, const int32_t box_shift[3], tsdf_snapshot *work, tsdf_snapshot *leaving);
 
 /* Multi-GPU raycast: a slab evaluates only the samples whose lower trilinear tap plane it owns and writes
  * one 8-byte record per pixel: k = index of the first owned sample with tsdf <= 0 (TSDF_NO_HIT if none), t = that sample's

@@ -8,3 +8,4 @@ from .api import (TSDFVolume, GPURaycaster, BilateralFilter, Camera, ICPOdometry
                   depth_weights, depth_weights_device, WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE, CLASS_VOID, Objects, OBJECT_DTYPE,
                   OBJECT_NONE, Reach, REACH_CLUSTER_DTYPE, REACH_UNREACHED, REACH_COST_FACE, REACH_COST_EDGE, REACH_COST_CORNER,
                   TSDF_REACH_THROUGH_UNKNOWN)
+from .rolling import BrickStore, RollingVolume  # noqa: F401

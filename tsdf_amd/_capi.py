@@ -25,6 +25,7 @@ TSDF_REACH_COST_FACE, TSDF_REACH_COST_EDGE, TSDF_REACH_COST_CORNER = 10, 14, 17
 TSDF_OBJECT_NONE = 0xFFFFFFFF
 TSDF_SCENE_FLOW_DEFORMED = 1
 TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
+TSDF_RESTORE_KEEP_OTHERS, TSDF_SELECT_OUTSIDE = 1, 1
 TSDF_WEIGHTS_INVERSE_SQUARE, TSDF_WEIGHTS_COSINE = 1, 2
 
 
@@ -348,6 +349,9 @@ _SIGS = {
     "tsdf_snapshot_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "tsdf_snapshot_upload": (_i, [_vp, C.POINTER(SnapshotInfo), _vp, _vp, _vp, _vp]),
     "tsdf_snapshot_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_volume_restore_shifted": (_i, [_vp, _vp, C.POINTER(C.c_int32), _u32]),
+    "tsdf_snapshot_select": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _vp]),
+    "tsdf_volume_shift": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp]),
     "tsdf_merge_hits_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_merge_hits_normals_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_slab_exchange_unique_id": (_i, [_vp, C.c_char_p]),

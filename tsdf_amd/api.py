@@ -697,10 +697,33 @@ class TSDFVolume:
         snap.header = self._file_header()
         return snap
 
-    def restore(self, snapshot):
+    def restore(self, snapshot, shift=(0, 0, 0), keep_others=False):
         """Put a Snapshot of a grid of this size back (tsdf_volume_restore): every accessor then reports the state the snapshot was
-        taken from, bit for bit.  The offset and the other header fields, the weight cap and the stream are not touched."""
-        check(lib.tsdf_volume_restore(self._h, snapshot._h))
+        taken from, bit for bit.  The offset and the other header fields, the weight cap and the stream are not touched.
+        With a `shift` in bricks or `keep_others` (tsdf_volume_restore_shifted; include/tsdf_amd.h, "rolling volume"): brick b of the
+        volume takes brick b - shift of the snapshot, whose grid may be of another size; with `keep_others` the voxels of bricks that are
+        not written keep their bits instead of being cleared."""
+        shift = tuple(int(s) for s in shift)
+        if shift == (0, 0, 0) and not keep_others:
+            check(lib.tsdf_volume_restore(self._h, snapshot._h))
+        else:
+            check(lib.tsdf_volume_restore_shifted(self._h, snapshot._h, (C.c_int32 * 3)(*shift),
+                                                  _capi.TSDF_RESTORE_KEEP_OTHERS if keep_others else 0))
+
+    def shift(self, box_shift, work=None, leaving=None):
+        """Move the volume's box by `box_shift` bricks of 8^3 voxels in the world; the content stays where it is in the world
+        (tsdf_volume_shift).  `work`: a Snapshot to use for the round trip (its arrays are kept and only grow); `leaving`: a Snapshot to
+        fill with the bricks that fall out, at the old offset -- one is made if None.  Returns `leaving`."""
+        own = work is None
+        work = Snapshot() if own else work
+        leaving = Snapshot() if leaving is None else leaving
+        try:
+            check(lib.tsdf_volume_shift(self._h, (C.c_int32 * 3)(*(int(s) for s in box_shift)), work._h, leaving._h))
+        finally:
+            if own:
+                work.close()
+        leaving.header = None
+        return leaving
 
     def save_sparse(self, path):
         """Write the volume's live bricks and header to a .tsdfs file.  Deformation nodes are not stored."""
@@ -1796,6 +1819,15 @@ class Snapshot(_Handle):
         p = [C.c_void_p() for _ in range(4)]
         check(lib.tsdf_snapshot_buffers(self._h, *(C.byref(q) for q in p)))
         return tuple(int(q.value or 0) for q in p)
+
+    def select(self, lo, hi, outside=False, into=None):
+        """The Snapshot of those bricks whose brick coordinates lie inside the box [lo, hi) -- with `outside`, outside it
+        (tsdf_snapshot_select).  Ids, geometry and storage are this snapshot's.  `into`: a Snapshot to reuse (not this one)."""
+        dst = Snapshot() if into is None else into
+        i3 = lambda v: (C.c_int32 * 3)(*(int(x) for x in v))
+        check(lib.tsdf_snapshot_select(self._h, i3(lo), i3(hi), _capi.TSDF_SELECT_OUTSIDE if outside else 0, dst._h))
+        dst.header = self.header
+        return dst
 
     @classmethod
     def from_arrays(cls, size, bricks, distances, weights, colours=None, fill_distance=0.0, voxel_size=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0),

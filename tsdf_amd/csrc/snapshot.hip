@@ -11,9 +11,14 @@
 //                            packed weights taken out of their z-groups (weights.hip)
 //   snapshot_scatter_kernel  one workgroup per four bricks of the grid along x: every dense word written once, the stored brick or the
 //                            fill, eight threads to 128 contiguous bytes of a row
+// and the rolling volume built on them ("rolling volume"; brick_shift.hpp has its arithmetic, DESIGN.md 32 the reasons):
+//   snapshot_scatter_shifted_kernel  the scatter over a grid that need not be the snapshot's, each brick from the brick a shift away
+//   snapshot_page_in_kernel  the same rows and z-groups over the snapshot's list: only the stored bricks are written
+//   select_flag_kernel, mesh_scan, select_gather_kernel   the entries of a list inside (outside) a box of bricks -> a list of their own
 // Every output word has one writer and there are no atomics: the same bytes on every run.
 #include <algorithm>
 
+#include "brick_shift.hpp"
 #include "common.hpp"
 #include "field_sample.hpp"
 #include "handle_order.hpp"
@@ -188,19 +193,15 @@ __device__ inline void scatter_packed(uint32_t *__restrict__ wp, const SnapGrid 
     store4(wp, (size_t)g.X * g.Y * (z0 / kPer) + (size_t)g.X * y + x, x, g.X, (g.X & 3u) == 0u, w);
 }
 
-// A workgroup takes kScatterBricks bricks next to each other along x: thread t the half t & 1 of row t >> 3 (ly = row & 7, lz = row >> 3)
-// of brick (t >> 1) & 3, so that eight consecutive threads write 128 contiguous bytes of a dense row.
+// One thread's share of brick (bx, by, bz) of the volume -- the half `half` of row `row` (ly = row & 7, lz = row >> 3) and, in the packed
+// modes, one dword column of four -- from list position p of the snapshot, or the cleared state for kSnapNone.
 // dmode: the volume's weight storage (0 / 8 / 16), sbits: the snapshot's element type (8 / 16 / 32); the host has made dmode hold sbits
-constexpr uint32_t kScatterBricks = 4;
-__global__ __launch_bounds__(512) void snapshot_scatter_kernel(float *__restrict__ dist, float *__restrict__ wf32, uint32_t *__restrict__ wpacked,
-                                                               const int dmode, uint32_t *__restrict__ colour, const SnapGrid g,
-                                                               const uint32_t fill_bits, const uint32_t *__restrict__ map,
-                                                               const float *__restrict__ sdist, const void *__restrict__ sweights, const int sbits,
-                                                               const uint32_t *__restrict__ scolour) {
-    const uint32_t half = threadIdx.x & 1u, row = threadIdx.x >> 3;
-    const uint32_t bx = blockIdx.x * kScatterBricks + ((threadIdx.x >> 1) & (kScatterBricks - 1u)), by = blockIdx.y, bz = blockIdx.z;
-    if (bx >= g.nbx) return;
-    const uint32_t p = map[bx + g.nbx * (by + (size_t)g.nby * bz)];
+// (the pointers are the calling kernel's own __restrict__ arguments; inlined before anything is optimised, so that
+// snapshot_scatter_kernel compiles to what it was when this was its body)
+__device__ __forceinline__ void scatter_brick(float *dist, float *wf32, uint32_t *wpacked, const int dmode, uint32_t *colour, const SnapGrid &g,
+                                     const uint32_t fill_bits, const uint32_t bx, const uint32_t by, const uint32_t bz, const uint32_t p,
+                                     const uint32_t half, const uint32_t row, const float *sdist, const void *sweights, const int sbits,
+                                     const uint32_t *scolour) {
     const uint32_t x = bx * kSnapBrick + 4u * half, y = by * kSnapBrick + (row & 7u), z = bz * kSnapBrick + (row >> 3);
     const bool vec = (g.X & 3u) == 0u, stored = p != kSnapNone;
     if (y < g.Y && z < g.Z) {
@@ -232,6 +233,81 @@ __global__ __launch_bounds__(512) void snapshot_scatter_kernel(float *__restrict
     // packed counts: the threads of the first 8 y x 2 (8-bit) or 4 (16-bit) z-groups, one dword column of four each
     if (dmode == 8 && row < 16u) scatter_packed<8>(wpacked, g, bx, by, bz, p, sweights, sbits, half, row & 7u, row >> 3);
     else if (dmode == 16 && row < 32u) scatter_packed<16>(wpacked, g, bx, by, bz, p, sweights, sbits, half, row & 7u, row >> 3);
+}
+
+// A workgroup takes kScatterBricks bricks next to each other along x: thread t the half t & 1 of row t >> 3 (ly = row & 7, lz = row >> 3)
+// of brick (t >> 1) & 3, so that eight consecutive threads write 128 contiguous bytes of a dense row.
+constexpr uint32_t kScatterBricks = 4;
+__global__ __launch_bounds__(512) void snapshot_scatter_kernel(float *__restrict__ dist, float *__restrict__ wf32, uint32_t *__restrict__ wpacked,
+                                                               const int dmode, uint32_t *__restrict__ colour, const SnapGrid g,
+                                                               const uint32_t fill_bits, const uint32_t *__restrict__ map,
+                                                               const float *__restrict__ sdist, const void *__restrict__ sweights, const int sbits,
+                                                               const uint32_t *__restrict__ scolour) {
+    const uint32_t half = threadIdx.x & 1u, row = threadIdx.x >> 3;
+    const uint32_t bx = blockIdx.x * kScatterBricks + ((threadIdx.x >> 1) & (kScatterBricks - 1u)), by = blockIdx.y, bz = blockIdx.z;
+    if (bx >= g.nbx) return;
+    const uint32_t p = map[bx + g.nbx * (by + (size_t)g.nby * bz)];
+    scatter_brick(dist, wf32, wpacked, dmode, colour, g, fill_bits, bx, by, bz, p, half, row, sdist, sweights, sbits, scolour);
+}
+
+// The same over the grid g of a volume that need not be the snapshot's: brick bD takes the source brick bD + from (from = -brick_shift,
+// from.nb* the snapshot's brick grid, which `map` is indexed by); a brick whose source is outside that grid or not stored is cleared.
+// A kernel of its own, so that the launch of tsdf_volume_restore is what it was.
+__global__ __launch_bounds__(512) void snapshot_scatter_shifted_kernel(float *__restrict__ dist, float *__restrict__ wf32, uint32_t *__restrict__ wpacked,
+                                                                       const int dmode, uint32_t *__restrict__ colour, const SnapGrid g,
+                                                                       const uint32_t fill_bits, const uint32_t *__restrict__ map, const BrickShift from,
+                                                                       const float *__restrict__ sdist, const void *__restrict__ sweights,
+                                                                       const int sbits, const uint32_t *__restrict__ scolour) {
+    const uint32_t half = threadIdx.x & 1u, row = threadIdx.x >> 3;
+    const uint32_t bx = blockIdx.x * kScatterBricks + ((threadIdx.x >> 1) & (kScatterBricks - 1u)), by = blockIdx.y, bz = blockIdx.z;
+    if (bx >= g.nbx) return;
+    uint32_t s[3], p = kSnapNone;
+    if (brick_moved(from, bx, by, bz, s)) p = map[s[0] + from.nbx * (s[1] + (size_t)from.nby * s[2])];
+    scatter_brick(dist, wf32, wpacked, dmode, colour, g, fill_bits, bx, by, bz, p, half, row, sdist, sweights, sbits, scolour);
+}
+
+// Paging in (TSDF_RESTORE_KEEP_OTHERS): over the snapshot's list, not over the grid.  A workgroup takes kScatterBricks consecutive list
+// positions -- neighbours along x where the list has them -- with the thread layout of the kernels above; brick bS of the snapshot's
+// grid (nbx, nby) lands at bS + to (to = brick_shift, to.nb* the volume's brick grid) or, outside it, nowhere.
+__global__ __launch_bounds__(512) void snapshot_page_in_kernel(float *__restrict__ dist, float *__restrict__ wf32, uint32_t *__restrict__ wpacked,
+                                                               const int dmode, uint32_t *__restrict__ colour, const SnapGrid g,
+                                                               const uint32_t *__restrict__ ids, const uint32_t n, const uint32_t nbx, const uint32_t nby,
+                                                               const BrickShift to, const float *__restrict__ sdist, const void *__restrict__ sweights,
+                                                               const int sbits, const uint32_t *__restrict__ scolour) {
+    const uint32_t half = threadIdx.x & 1u, row = threadIdx.x >> 3;
+    const uint32_t p = blockIdx.x * kScatterBricks + ((threadIdx.x >> 1) & (kScatterBricks - 1u));
+    if (p >= n) return;
+    const uint32_t b = ids[p];
+    uint32_t d[3];
+    if (!brick_moved(to, b % nbx, (b / nbx) % nby, b / (nbx * nby), d)) return;
+    scatter_brick(dist, wf32, wpacked, dmode, colour, g, 0u, d[0], d[1], d[2], p, half, row, sdist, sweights, sbits, scolour);
+}
+
+// tsdf_snapshot_select: one flag per list entry -- its brick is inside the box, or with `outside` is not
+__global__ __launch_bounds__(256) void select_flag_kernel(const uint32_t *__restrict__ ids, const uint32_t n, const uint32_t nbx, const uint32_t nby,
+                                                          const BrickBox box, const uint32_t outside, uint32_t *__restrict__ flags) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t b = ids[i];
+    const bool inside = brick_in_box(box, b % nbx, (b / nbx) % nby, b / (nbx * nby));
+    flags[i] = inside != (outside != 0u) ? 1u : 0u;
+}
+
+// ... and, the flags scanned into bases (total: the scan's first total), a workgroup per entry of the source list: the id and the
+// brick's rows, one uint4 per lane and array; wq: the uint4 words of a brick's weights (32, 64 or 128)
+__global__ __launch_bounds__(128) void select_gather_kernel(const uint32_t *__restrict__ bases, const uint64_t *__restrict__ total, const uint32_t n,
+                                                            const uint32_t *__restrict__ ids, const uint4 *__restrict__ sdist,
+                                                            const uint4 *__restrict__ sweights, const uint4 *__restrict__ scolour, const uint32_t wq,
+                                                            uint32_t *__restrict__ oids, uint4 *__restrict__ odist, uint4 *__restrict__ oweights,
+                                                            uint4 *__restrict__ ocolour) {
+    const uint32_t i = blockIdx.x, t = threadIdx.x;
+    const uint32_t base = bases[i], next = i + 1u < n ? bases[i + 1u] : (uint32_t)*total;
+    if (next == base) return;
+    constexpr uint32_t kQ = kSnapVoxels / 4u;   // the uint4 words of 512 dwords
+    if (t == 0) oids[base] = ids[i];
+    odist[(size_t)base * kQ + t] = sdist[(size_t)i * kQ + t];
+    if (scolour) ocolour[(size_t)base * kQ + t] = scolour[(size_t)i * kQ + t];
+    if (t < wq) oweights[(size_t)base * wq + t] = sweights[(size_t)i * wq + t];
 }
 
 }  // namespace tsdf
@@ -291,6 +367,121 @@ int refuse_volume(const tsdf_volume *v, const char *who) {
                  "%s: a Z-slab volume (tsdf_volume_create_slab) is not supported", who);
     TSDF_REQUIRE(!v->nodes, "%s: the volume has a materialised deformation-node array, which a snapshot does not carry", who);
     return TSDF_OK;
+}
+
+// What every restore does before its launch: the volume's storage made to hold the snapshot's, the stream behind the handle, the marks
+// of a writer of distances and weights.  keep: the data in the volume stays (TSDF_RESTORE_KEEP_OTHERS), so its bound does too.
+int restore_prepare(tsdf_volume *v, const tsdf_snapshot *s, bool keep) {
+    const tsdf_snapshot_info &info = s->info;
+    // what a writer of distances and weights owes the volume (common.hpp, "THE INVARIANT"): the tightening in flight first, then
+    // every flag is rebuilt from everything
+    int rc = occupancy_join(v);
+    if (rc != TSDF_OK) return rc;
+    // the storage: the wider of what the volume has and what the snapshot carries (a pinned volume is fp32 already); widening converts
+    // the counts the volume holds
+    const uint32_t now = v->wmode == 0 ? 32u : (uint32_t)v->wmode;
+    if (info.weight_bits > now) {
+        rc = tsdf_volume_set_weight_storage(v, (int)info.weight_bits);
+        if (rc != TSDF_OK) return rc;
+    }
+    if (info.flags & TSDF_SNAPSHOT_COLOUR) {
+        rc = tsdf_volume_enable_colour(v, 1);
+        if (rc != TSDF_OK) return rc;
+    }
+    rc = s->join(v->stream, kSnapOrder);
+    if (rc != TSDF_OK) return rc;
+    v->occ_dirty = 1;
+    v->occ_scan_all = 1;
+    v->prepared_valid = 0;
+    v->weight_bound = keep ? std::max(v->weight_bound, info.weight_bound) : info.weight_bound;
+    return TSDF_OK;
+}
+
+// tsdf_volume_restore_shifted with a shift of 64 bits (tsdf_volume_shift negates an int32)
+int restore_shifted(tsdf_volume *v, const tsdf_snapshot *s, const long long shift[3], uint32_t flags) {
+    TSDF_REQUIRE(s->filled, "tsdf_volume_restore_shifted: the handle has never been filled (tsdf_volume_snapshot, tsdf_snapshot_upload)");
+    TSDF_REQUIRE((flags & ~(uint32_t)TSDF_RESTORE_KEEP_OTHERS) == 0, "tsdf_volume_restore_shifted: unknown flags %#x", flags);
+    int rc = refuse_volume(v, "tsdf_volume_restore_shifted");
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(v->device == s->device, "tsdf_volume_restore_shifted: the handle was created on device %d, the volume on device %d", s->device,
+                 v->device);
+    const bool keep = (flags & TSDF_RESTORE_KEEP_OTHERS) != 0;
+    rc = restore_prepare(v, s, keep);
+    if (rc != TSDF_OK) return rc;
+    const tsdf_snapshot_info &info = s->info;
+    const uint32_t size[3] = {v->g.X, v->g.Y, v->g.Z};
+    uint32_t nb[3];
+    brick_count(size, nb);
+    const SnapGrid dg = {size[0], size[1], size[2], nb[0], nb[1], nb[2]};
+    uint32_t fill_bits;
+    std::memcpy(&fill_bits, &info.fill_distance, sizeof(fill_bits));
+    const uint32_t *scolour = (info.flags & TSDF_SNAPSHOT_COLOUR) ? s->colours : nullptr;
+    if (keep) {
+        // over the list: source brick + shift, inside the volume's grid
+        const BrickShift to = {shift[0], shift[1], shift[2], nb[0], nb[1], nb[2]};
+        const uint32_t n = (uint32_t)info.n_bricks;
+        if (n)
+            hipLaunchKernelGGL(snapshot_page_in_kernel, grid_for(n, kScatterBricks), dim3(64 * 2 * kScatterBricks), 0, v->stream, v->dist, v->weight,
+                               v->wpacked, v->wmode, v->colour, dg, s->ids, n, info.bricks[0], info.bricks[1], to, s->dist, s->weights,
+                               (int)info.weight_bits, scolour);
+    } else {
+        // over the grid: destination brick - shift, inside the snapshot's grid
+        const BrickShift from = {-shift[0], -shift[1], -shift[2], info.bricks[0], info.bricks[1], info.bricks[2]};
+        hipLaunchKernelGGL(snapshot_scatter_shifted_kernel, dim3((dg.nbx + kScatterBricks - 1) / kScatterBricks, dg.nby, dg.nbz),
+                           dim3(64 * 2 * kScatterBricks), 0, v->stream, v->dist, v->weight, v->wpacked, v->wmode, v->colour, dg, fill_bits, s->map, from,
+                           s->dist, s->weights, (int)info.weight_bits, scolour);
+    }
+    TSDF_HIP(hipGetLastError(), "snapshot shifted scatter kernel failed");
+    return s->leave(v->stream, kSnapEvent);
+}
+
+// tsdf_snapshot_select on a stream of the caller's choice
+int snapshot_select(const tsdf_snapshot *src, const BrickBox &box, uint32_t flags, tsdf_snapshot *dst, hipStream_t stream) {
+    TSDF_REQUIRE(dst != src, "tsdf_snapshot_select: dst is src");
+    TSDF_REQUIRE(src->filled, "tsdf_snapshot_select: src has never been filled (tsdf_volume_snapshot, tsdf_snapshot_upload)");
+    TSDF_REQUIRE((flags & ~(uint32_t)TSDF_SELECT_OUTSIDE) == 0, "tsdf_snapshot_select: unknown flags %#x", flags);
+    TSDF_REQUIRE(src->device == dst->device, "tsdf_snapshot_select: src was created on device %d, dst on device %d", src->device, dst->device);
+    int rc = src->join(stream, kSnapOrder);
+    if (rc == TSDF_OK) rc = dst->join(stream, kSnapOrder);   // (what still reads dst's arrays)
+    if (rc != TSDF_OK) return rc;
+    dst->filled = 0;
+    tsdf_snapshot_info info = src->info;
+    const uint32_t n = (uint32_t)info.n_bricks;
+    const uint64_t total = (uint64_t)info.bricks[0] * info.bricks[1] * info.bricks[2];
+    const uint32_t n_parts = mesh_scan_parts(n);
+    hipError_t e = device_reserve(dst->flags, dst->flags_cap, (size_t)n);
+    if (e == hipSuccess) e = device_reserve(dst->map, dst->map_cap, (size_t)total);
+    if (e == hipSuccess) e = device_reserve(dst->parts, dst->parts_cap, 2 * ((size_t)n_parts + 1));
+    if (e != hipSuccess) return hip_fail(e, "snapshot select scratch alloc failed");
+    uint64_t *count = dst->parts + 2 * (size_t)n_parts;
+    *dst->total_host = 0;
+    if (n) {
+        hipLaunchKernelGGL(select_flag_kernel, grid_for(n, 256), dim3(256), 0, stream, src->ids, n, info.bricks[0], info.bricks[1], box,
+                           flags & TSDF_SELECT_OUTSIDE, dst->flags);
+        mesh_scan(ArrayCounts{dst->flags, n, nullptr, 0u}, n_parts, dst->parts, stream);
+        TSDF_HIP(hipGetLastError(), "snapshot select flag kernels failed");
+        TSDF_HIP(hipMemcpyAsync(dst->total_host, count, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "snapshot select count download");
+        TSDF_HIP(hipStreamSynchronize(stream), "snapshot select count");   // the one synchronisation: dst is sized by the count
+    }
+    info.n_bricks = *dst->total_host;
+    info.bytes = snapshot_bytes(info);
+    dst->info = info;
+    e = snapshot_reserve(dst);
+    if (e != hipSuccess) return hip_fail(e, "snapshot select array alloc failed");
+    TSDF_HIP(hipMemsetAsync(dst->map, 0xff, (size_t)total * sizeof(uint32_t), stream), "snapshot select map");
+    if (info.n_bricks) {
+        const bool colour = (info.flags & TSDF_SNAPSHOT_COLOUR) != 0;
+        hipLaunchKernelGGL(select_gather_kernel, dim3(n), dim3(128), 0, stream, dst->flags, count, n, src->ids,
+                           reinterpret_cast<const uint4 *>(src->dist), static_cast<const uint4 *>(src->weights),
+                           colour ? reinterpret_cast<const uint4 *>(src->colours) : nullptr, 4u * info.weight_bits,
+                           dst->ids, reinterpret_cast<uint4 *>(dst->dist), static_cast<uint4 *>(dst->weights),
+                           colour ? reinterpret_cast<uint4 *>(dst->colours) : nullptr);
+        hipLaunchKernelGGL(snapshot_map_kernel, grid_for(info.n_bricks, 256), dim3(256), 0, stream, dst->ids, (uint32_t)info.n_bricks, dst->map);
+    }
+    TSDF_HIP(hipGetLastError(), "snapshot select gather kernels failed");
+    dst->filled = 1;
+    rc = src->leave(stream, kSnapEvent);
+    return rc == TSDF_OK ? dst->leave(stream, kSnapEvent) : rc;
 }
 
 }  // namespace
@@ -383,26 +574,8 @@ int tsdf_volume_restore(tsdf_volume *v, const tsdf_snapshot *s) {
                  "tsdf_volume_restore: the snapshot is of a %u x %u x %u grid, the volume is %u x %u x %u", info.size[0], info.size[1], info.size[2],
                  v->g.X, v->g.Y, v->g.Z);
     TSDF_REQUIRE(v->device == s->device, "tsdf_volume_restore: the handle was created on device %d, the volume on device %d", s->device, v->device);
-    // what a writer of distances and weights owes the volume (common.hpp, "THE INVARIANT"): the tightening in flight first, then
-    // every flag is rebuilt from everything
-    int rc = occupancy_join(v);
+    const int rc = restore_prepare(v, s, false);
     if (rc != TSDF_OK) return rc;
-    // the storage: the wider of what the volume has and what the snapshot carries (a pinned volume is fp32 already)
-    const uint32_t now = v->wmode == 0 ? 32u : (uint32_t)v->wmode;
-    if (info.weight_bits > now) {
-        rc = tsdf_volume_set_weight_storage(v, (int)info.weight_bits);
-        if (rc != TSDF_OK) return rc;
-    }
-    if (info.flags & TSDF_SNAPSHOT_COLOUR) {
-        rc = tsdf_volume_enable_colour(v, 1);
-        if (rc != TSDF_OK) return rc;
-    }
-    rc = s->join(v->stream, kSnapOrder);
-    if (rc != TSDF_OK) return rc;
-    v->occ_dirty = 1;
-    v->occ_scan_all = 1;
-    v->prepared_valid = 0;
-    v->weight_bound = info.weight_bound;
     const SnapGrid sg = {info.size[0], info.size[1], info.size[2], info.bricks[0], info.bricks[1], info.bricks[2]};
     uint32_t fill_bits;
     std::memcpy(&fill_bits, &info.fill_distance, sizeof(fill_bits));
@@ -410,6 +583,50 @@ int tsdf_volume_restore(tsdf_volume *v, const tsdf_snapshot *s) {
                        s->map, s->dist, s->weights, (int)info.weight_bits, (info.flags & TSDF_SNAPSHOT_COLOUR) ? s->colours : nullptr);
     TSDF_HIP(hipGetLastError(), "snapshot scatter kernel failed");
     return s->leave(v->stream, kSnapEvent);   // the handle's arrays are read by what has just been enqueued
+}
+
+// ---- rolling volume (include/tsdf_amd.h) ---------------------------------------------------------------------------------------------
+int tsdf_volume_restore_shifted(tsdf_volume *v, const tsdf_snapshot *s, const int32_t brick_shift[3], uint32_t flags) {
+    TSDF_REQUIRE(v && s && brick_shift, "tsdf_volume_restore_shifted: null argument");
+    const long long shift[3] = {brick_shift[0], brick_shift[1], brick_shift[2]};
+    return restore_shifted(v, s, shift, flags);
+}
+
+int tsdf_snapshot_select(const tsdf_snapshot *src, const int32_t lo[3], const int32_t hi[3], uint32_t flags, tsdf_snapshot *dst) {
+    TSDF_REQUIRE(src && lo && hi && dst, "tsdf_snapshot_select: null argument");
+    const BrickBox box = {{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+    return snapshot_select(src, box, flags, dst, nullptr);
+}
+
+int tsdf_volume_shift(tsdf_volume *v, const int32_t box_shift[3], tsdf_snapshot *work, tsdf_snapshot *leaving) {
+    TSDF_REQUIRE(v && box_shift && work, "tsdf_volume_shift: null argument");
+    TSDF_REQUIRE(leaving != work, "tsdf_volume_shift: leaving is work");
+    int rc = refuse_volume(v, "tsdf_volume_shift");
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(v->g.X % kSnapBrick == 0 && v->g.Y % kSnapBrick == 0 && v->g.Z % kSnapBrick == 0,
+                 "tsdf_volume_shift: the grid is %u x %u x %u, not a multiple of 8 on every axis: the voxels of a partial brick cut off at the border "
+                 "would be lost without appearing in leaving",
+                 v->g.X, v->g.Y, v->g.Z);
+    TSDF_REQUIRE(!v->classes, "tsdf_volume_shift: classes are enabled on this volume; snapshots do not carry class words, which would stay behind "
+                              "while the geometry moves");
+    TSDF_REQUIRE(v->device == work->device && (!leaving || v->device == leaving->device),
+                 "tsdf_volume_shift: a handle was created on another device than the volume's %d", v->device);
+    const bool zero = box_shift[0] == 0 && box_shift[1] == 0 && box_shift[2] == 0;
+    if (zero && !leaving) return TSDF_OK;
+    rc = tsdf_volume_snapshot(v, 0, work);
+    if (rc != TSDF_OK) return rc;
+    if (leaving) {
+        // (work's offset is the volume's, still the old one; with no shift every brick stays)
+        rc = snapshot_select(work, staying_box(box_shift, work->info.bricks), TSDF_SELECT_OUTSIDE, leaving, v->stream);
+        if (rc != TSDF_OK) return rc;
+    }
+    if (zero) return TSDF_OK;
+    const long long back[3] = {-(long long)box_shift[0], -(long long)box_shift[1], -(long long)box_shift[2]};
+    rc = restore_shifted(v, work, back, 0);
+    if (rc != TSDF_OK) return rc;
+    const Geom &g = v->g;
+    return tsdf_volume_set_offset(v, shifted_offset(g.offset.x, box_shift[0], g.vs.x), shifted_offset(g.offset.y, box_shift[1], g.vs.y),
+                                  shifted_offset(g.offset.z, box_shift[2], g.vs.z));
 }
 
 int tsdf_snapshot_get_info(const tsdf_snapshot *s, tsdf_snapshot_info *info) {

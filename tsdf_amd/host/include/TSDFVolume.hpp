@@ -355,6 +355,9 @@ public:
         // blocking download: n_bricks ids, 512 n_bricks distances, weights (weight_bits / 8 bytes each) and, with colour, colour words
         void download(std::vector<uint32_t> &bricks, std::vector<float> &distances, std::vector<unsigned char> &weights,
                       std::vector<uint32_t> &colours) const;
+        // `into` becomes the snapshot of the bricks with coordinates inside the box [lo, hi), or with TSDF_SELECT_OUTSIDE outside it
+        // (tsdf_snapshot_select); throws std::invalid_argument when into is this snapshot or this one was never filled
+        void select(const int32_t lo[3], const int32_t hi[3], uint32_t flags, Snapshot &into) const;
 
     private:
         tsdf_snapshot *m_handle;
@@ -364,6 +367,13 @@ public:
     // materialised deformation nodes, a snapshot of a grid of another size, a handle that was never filled).
     void snapshot(Snapshot &into) const;
     void restore(const Snapshot &from);
+    // Rolling volume (include/tsdf_amd.h, "rolling volume"): brick b takes brick b - shift of `from`, whose grid may be of another size;
+    // flags: 0 or TSDF_RESTORE_KEEP_OTHERS (tsdf_volume_restore_shifted) ...
+    void restore(const Snapshot &from, const int32_t shift[3], uint32_t flags);
+    // ... and the box moved by box_shift bricks in the world, the content staying where it is: through `work`, the bricks that fall out
+    // into `leaving` if given (tsdf_volume_shift).  Both throw std::invalid_argument on the refusals (those above; for shift also
+    // leaving == &work, a grid that is no multiple of 8 on every axis, classes enabled).
+    void shift(const int32_t box_shift[3], Snapshot &work, Snapshot *leaving);
     // The volume's live bricks and header as a .tsdfs file; false with a message when the volume cannot be saved so
     // (materialised deformation nodes are not stored) or the file cannot be written.
     bool save_sparse(const std::string &file_name) const;

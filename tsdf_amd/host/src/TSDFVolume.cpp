@@ -885,6 +885,20 @@ void TSDFVolume::snapshot(Snapshot &into) const { check(tsdf_volume_snapshot(m_h
 
 void TSDFVolume::restore(const Snapshot &from) { check(tsdf_volume_restore(m_handle, from.handle()), "Couldn't restore the snapshot"); }
 
+// ---- rolling volume (include/tsdf_amd.h, "rolling volume")
+void TSDFVolume::Snapshot::select(const int32_t lo[3], const int32_t hi[3], uint32_t flags, Snapshot &into) const {
+    check(tsdf_snapshot_select(m_handle, lo, hi, flags, into.handle()), "Couldn't select from the snapshot");
+}
+
+void TSDFVolume::restore(const Snapshot &from, const int32_t shift[3], uint32_t flags) {
+    check(tsdf_volume_restore_shifted(m_handle, from.handle(), shift, flags), "Couldn't restore the shifted snapshot");
+}
+
+void TSDFVolume::shift(const int32_t box_shift[3], Snapshot &work, Snapshot *leaving) {
+    check(tsdf_volume_shift(m_handle, box_shift, work.handle(), leaving ? leaving->handle() : nullptr), "Couldn't shift the volume");
+    refresh_from_handle();   // (the offset has moved)
+}
+
 bool TSDFVolume::save_sparse(const std::string &file_name) const { return save_sparse(m_handle, file_name); }
 
 bool TSDFVolume::save_sparse(const tsdf_volume *handle, const std::string &file_name) {
