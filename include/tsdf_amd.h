@@ -170,6 +170,15 @@ int tsdf_selftest_bilateral_chain_image(float sigma_colour, float sigma_space, c
 int tsdf_selftest_cell_boxes(const float *r, const float *k, const float *voxel_size, const float *offset, const uint32_t *grid,
                              uint32_t width, uint32_t height, float z_clip, float z_near, size_t n, const uint32_t *cells, int corners_only,
                              int32_t *boxes, uint8_t *seen);
+/* Self-test of the rule by which the cell-parallel ray cast gives every sample to ONE dual cell (cell_owner.hpp: cell_owns, two exact
+ * comparisons per axis).  Runs on the host, with the very expression the kernel compiles, and needs no GPU.  grid = voxels per axis
+ * (2 .. 65535), voxel_size per axis.  For each of n points (grid millimetres, 3 per point) and cells (the lower voxel's coordinates, 3 per
+ * cell, each + 1 below the grid's size): owns = bit a set when the cell owns the point along axis a, + 8 when it owns it on all three;
+ * lower = per axis the lower tap the reference's trilinearly_interpolate chooses for the point (restated: voxel_for_point,
+ * centre_of_voxel_at, the clamps; -1 where it leaves through its off-grid return), its quotient formed by IEEE division, or with
+ * fast_division != 0 by the three-instruction sequence of the kernels (without the check a volume makes before it uses that). */
+int tsdf_selftest_cell_owner(const uint32_t *grid, const float *voxel_size, int fast_division, size_t n, const float *points,
+                             const uint32_t *cells, uint8_t *owns, int32_t *lower);
 /* Self-test of the Gauss-Newton back end that ICP and the field aligners share (gn_solve.hpp: icp_finish_step -- the second stage of the
  * 29-entry reduction, the unpivoted and the pivoted 6 x 6 LDL^T, the SE3 exponential, T <- exp(x) * T).  One launch of the very kernel
  * ICP and the plain aligner finish a step with, on sums the caller makes up: partial = n_blocks x 32 floats (a workgroup's 29 sums in

@@ -186,6 +186,7 @@ _SIGS = {
     "tsdf_selftest_bilateral_chain_taps": (_i, [C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tsdf_selftest_bilateral_chain_image": (_i, [_f, _f, _vp, _i, _i, _i, _vp, C.POINTER(C.c_uint64)]),
     "tsdf_selftest_cell_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _f, _f, C.c_size_t, _vp, _i, _vp, _vp]),
+    "tsdf_selftest_cell_owner": (_i, [_vp, _vp, _i, C.c_size_t, _vp, _vp, _vp, _vp]),
     "tsdf_selftest_gn_finish": (_i, [_vp, _i, _vp, _i, _vp]),
     "tsdf_volume_deformation": (_i, [_vp, C.POINTER(_vp)]),
     "tsdf_volume_set_distance_data": (_i, [_vp, _vp]),

@@ -13,6 +13,7 @@
 #include "raycast_sample.hpp"
 #include "field_sample.hpp"
 #include "cell_boxes.hpp"
+#include "cell_owner.hpp"
 
 namespace tsdf {
 
@@ -1430,6 +1431,30 @@ int tsdf_selftest_cell_boxes(const float *r, const float *k, const float *voxel_
         if (!any) pb = {0, 0, 0, 0};
         boxes[4 * i] = pb.u0; boxes[4 * i + 1] = pb.v0; boxes[4 * i + 2] = pb.w; boxes[4 * i + 3] = pb.h;
         seen[i] = (uint8_t)((any ? 1 : 0) | (near ? 2 : 0));
+    }
+    return TSDF_OK;
+}
+
+// ---- a sample's owning cell on the host (include/tsdf_amd.h, "self-tests") -----------------------------------------------------------
+int tsdf_selftest_cell_owner(const uint32_t *grid, const float *voxel_size, int fast_division, size_t n, const float *points,
+                             const uint32_t *cells, uint8_t *owns, int32_t *lower) {
+    TSDF_REQUIRE(grid && voxel_size && points && cells && owns && lower, "tsdf_selftest_cell_owner: null pointer");
+    TSDF_REQUIRE(grid[0] >= 2 && grid[1] >= 2 && grid[2] >= 2 && grid[0] <= 65535u && grid[1] <= 65535u && grid[2] <= 65535u,
+                 "tsdf_selftest_cell_owner: 2 .. 65535 voxels per axis");
+    TSDF_REQUIRE(voxel_size[0] > 0.0f && voxel_size[1] > 0.0f && voxel_size[2] > 0.0f, "tsdf_selftest_cell_owner: voxel sizes must be positive");
+    for (size_t i = 0; i < n; i++) {
+        uint8_t bits = 0;
+        for (int a = 0; a < 3; a++) {
+            const uint32_t l = cells[3 * i + a];
+            TSDF_REQUIRE(l + 1u < grid[a], "tsdf_selftest_cell_owner: cell %zu is not a cell of the grid", i);
+            const float p = points[3 * i + a];
+            if (cell_owns(p, (float)l, voxel_size[a])) bits |= (uint8_t)(1u << a);
+            lower[3 * i + a] = reference_lower(p, voxel_size[a], grid[a], fast_division != 0, kFastDivMin);
+        }
+        if (bits == 7u && cell_owns(points[3 * i], points[3 * i + 1], points[3 * i + 2], (float)cells[3 * i], (float)cells[3 * i + 1], (float)cells[3 * i + 2],
+                                    voxel_size[0], voxel_size[1], voxel_size[2]))
+            bits |= 8u;
+        owns[i] = bits;
     }
     return TSDF_OK;
 }

@@ -18,11 +18,14 @@
 // (grown by the guard band eps) into the image -- the view's projection is only used to bound the PIXELS worth looking at -- and for
 // every such pixel intersects that pixel's ray (the same start point and direction as ever: cell_cast_prepare_kernel runs setup_ray) with
 // the cell, walks the few samples inside -- the reference's expressions for the value, the look-ahead of process_sample to pass the
-// ones proven positive -- and lowers the pixel's word to the first one <= 0.  A sample within eps of a cell face, where the cheap
-// arithmetic and the reference's may disagree about the cell, takes the reference's full trilinearly_interpolate, which picks its own
-// cell: it is evaluated by the task of every mixed cell it could belong to, and two tasks that evaluate the same sample compute the
-// same value.  The minimum over all tasks (atomicMin on {k, value}) is the sample the reference's loop stops at: every sample <= 0 is
-// found by some task, and every sample evaluated is one the reference would evaluate with the same result.  resolve_*_kernel is unchanged.
+// ones proven positive -- and lowers the pixel's word to the first one <= 0.  The cheap arithmetic only says that a sample is near the
+// cell (within eps of it); whose sample it is, is decided exactly: the reference's choice of cell comes down to two comparisons per
+// axis against products it forms itself (cell_owns, cell_owner.hpp, with the argument), so every sample has ONE owning cell, the
+// owner's task evaluates it with the reference's expressions on the reference's 8 taps -- the brick's voxels, already in LDS -- and
+// every other task passes it by.  (Up to round 7 a sample within eps of a face took the reference's full trilinearly_interpolate, eight
+// loads from memory inside the walk, in the task of every mixed cell it could belong to: a tenth of the kernel's instructions, a
+// seventh of its time.)  The minimum over all tasks (atomicMin on {k, value}) is the sample the reference's loop stops at: every sample <= 0 is
+// found by its owner's task, and every sample evaluated is one the reference would evaluate with the same result.  resolve_*_kernel is unchanged.
 // No ray is marched through free space, no wave waits for a long ray: the cast is the number of (mixed cell, pixel) pairs, a few per ray.
 // Needs a view whose projection exists (camera depth == ray parameter: view_projection); a mixed cell that reaches across the camera
 // plane is bounded from the side it lies on, one that holds the camera is offered to every pixel (project_box).  Volumes whose flagged
@@ -712,9 +715,11 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
                     continue;
                 }
                 entered = true;
-                if (far_ < 0.5f - e) {
+                // near the cell; whose sample it is, is decided exactly (cell_owner.hpp: the reference's own two products per axis,
+                // the upper ones formed here and dead again at once -- nothing more is carried through the loop)
+                if (cell_owns(ppx, ppy, ppz, lfx, lfy, lfz, g.vs.x, g.vs.y, g.vs.z)) {
                     RAY_MIX(38);
-                    // the sample's dual cell is this one, to the reference's arithmetic too: its value from the cell's 8 voxels
+                    // the sample's dual cell is this one in the reference's arithmetic: its value from the cell's 8 voxels
                     const float u = div_by<FASTDIV>(ppx - lcx, tc.dx);
                     const float v = div_by<FASTDIV>(ppy - lcy, tc.dy);
                     const float w = div_by<FASTDIV>(ppz - lcz, tc.dz);
@@ -731,6 +736,10 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
                         lower_best(&best[idx], k, val);
                         break;
                     }
+                    // (an owned sample may lie in the band between the shrunk cell [e, 1 - e] and the face.  Beyond the face the ray
+                    // leaves through, samples_until's argument is negative and it answers its minimum, 1: limit 0, no skip, never a
+                    // negative one.  Behind the face it came in through, the samples skipped are further along the ray: fp32 products
+                    // and sums are monotone, so they stay on this cell's side of that face exactly as this one does.)
                     int ahead = 0;
                     if (rs.skip_ok && val > 0) {
                         const float cell_lo = e, cell_hi = 1.0f - e;
@@ -740,14 +749,8 @@ __global__ __launch_bounds__(256) void cast_cells_kernel(const float *__restrict
                     }
                     k += 1 + ahead;
                 } else {
-                    // within eps of a face of the cell: the reference's own choice of cell and taps
+                    // beyond a face, if only just: the sample of the cell on the other side, whose task is offered it too
                     RAY_MIX(39);
-                    bool owned;
-                    const float tsdf = trilinear<SLAB, false, FASTDIV>(ppx, ppy, ppz, dist, g, tc, rp.own_lo, rp.own_hi, owned, nullptr);
-                    if (tsdf <= 0) {
-                        lower_best(&best[idx], k, tsdf);
-                        break;
-                    }
                     k++;
                 }
             }
