@@ -11,7 +11,7 @@ CSRC      = tsdf_amd/csrc
 ifeq ($(DIAG),1)
 HIPFLAGS += -DTSDF_DIAGNOSTICS
 endif
-HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_weighted.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/classes.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_scan.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/esdf.hip $(CSRC)/explore.hip $(CSRC)/reach.hip $(CSRC)/objects.hip $(CSRC)/scene_flow.hip $(CSRC)/snapshot.hip
+HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_weighted.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/classes.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_scan.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/esdf.hip $(CSRC)/explore.hip $(CSRC)/reach.hip $(CSRC)/objects.hip $(CSRC)/scene_flow.hip $(CSRC)/snapshot.hip $(CSRC)/columns.hip
 HIP_OBJS  = $(HIP_SRCS:.hip=.o)
 LIBDIR    = tsdf_amd/lib
 
@@ -58,7 +58,7 @@ $(LIBDIR)/libtsdf_hip.so: $(HIP_OBJS)
 oracle:
 	$(MAKE) -C oracle -s all
 
-CPPTESTS  = surface colour classes weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf explore reach objects components simplify smooth scene_flow snapshot weighted rolling
+CPPTESTS  = surface colour classes weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf explore reach objects components simplify smooth scene_flow snapshot weighted rolling columns
 cpptest: $(CPPTESTS:%=build/test_%) build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
@@ -94,8 +94,15 @@ sanitize-rolling: tests/cpp/rolling_host.cpp $(CSRC)/brick_shift.hpp
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/rolling_host.cpp -o build/rolling_host
 	build/rolling_host
 
+# The same for columns_index.hpp (the column maps' cell and band arithmetic: map axes, strides, the reversed index, U * V * L in 64 bits)
+# against brute force on small grids and at the longest axis a map takes.
+sanitize-columns: tests/cpp/columns_host.cpp $(CSRC)/columns_index.hpp
+	@mkdir -p build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/columns_host.cpp -o build/columns_host
+	build/columns_host
+
 clean:
 	rm -f $(HIP_OBJS) $(HOST_OBJS) $(LIBDIR)/*.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all hip host oracle cpptest clean sanitize-scene-flow sanitize-device-buffer sanitize-rolling
+.PHONY: all hip host oracle cpptest clean sanitize-scene-flow sanitize-device-buffer sanitize-rolling sanitize-columns

@@ -1711,6 +1711,109 @@ int tsdf_snapshot_select(const tsdf_snapshot *src, const int32_t lo[3], const in
 /* leaving may be NULL */
 int tsdf_volume_shift(tsdf_volume *volume, const int32_t box_shift[3], tsdf_snapshot *work, tsdf_snapshot *leaving);
 
+/* ---- column maps (no reference counterpart: the reference's volume is asked about its surface only) -------------------------------- */
+/* Where is the floor and how high is it, is this cell of the floor plan free, occupied or unseen, how much headroom is above the
+ * ground, how close is the nearest obstacle in my height range?  Every column of voxels along one axis of the grid is reduced to one
+ * small row of a 2-D map -- what a ground robot's planner, a drone's altitude hold or a map viewer asks before anything in 3-D.  Opt-in
+ * by being called: no other entry point, launch or result changes; nothing of a volume or an ESDF is written.  Every result is an
+ * integer, a set, a minimum or the outcome of a fixed fp32 expression: two runs give the same bytes.
+ *   1. Grid, ids and voxel states are those of "exploration" rule 1: voxel (x, y, z) has id (z * Y + y) * X + x (uint32: more than
+ *      2^32 - 1 voxels are refused), and UNKNOWN / FREE / OCCUPIED are as defined there.  Weights are read in place from all three
+ *      storages; a distance d(v) is read only where the voxel is observed.
+ *   2. Axis and map.  axis in {0, 1, 2} (x, y, z) is the axis reduced.  The map's axes (a_u, a_v) are the two others in ascending
+ *      order: axis 0 -> (y, z); axis 1 -> (x, z); axis 2 -> (x, y).  The map has U x V cells, U = N[a_u], V = N[a_v]; cell (u, v) has
+ *      index v * U + u.
+ *   3. Band and walk.  lo, hi are voxel indices on `axis` with 0 <= lo < hi <= N_axis; hi == 0 means N_axis.  L = hi - lo.  The
+ *      column of a cell is the sequence c_0 .. c_{L-1}; c_p is the voxel with axis index lo + p -- with TSDF_COLUMNS_REVERSED, with
+ *      axis index hi - 1 - p.  "Up" is increasing p: a volume whose gravity axis points down the index is served by the flag, not by
+ *      a second definition.
+ *   4. Row.  One 32-byte tsdf_column per cell:
+ *        n_unknown, n_free, n_occupied: the counts over the column; they sum to L.
+ *        top: the largest p with OCCUPIED(c_p), or -1 if there is none.  bottom: the smallest such p, or -1.
+ *        headroom: 0 if top == -1; otherwise the number of consecutive FREE voxels at p = top + 1, top + 2, ...: the count ends at
+ *          the first voxel that is not FREE, or at L.
+ *        height, in voxels of the walk, measured from the band's start: NaN if top == -1.  The fallback is (float)top + 1.0f, the
+ *          voxel's upper face.  If top + 1 < L and c_{top+1} is FREE, let d0 = d(c_top), d1 = d(c_{top+1}) and f = d0 / (d0 - d1),
+ *          every fp32 operation rounded on its own.  If f >= 0.0f and f <= 1.0f (NaN fails both), height = ((float)top + 0.5f) + f:
+ *          the zero crossing between the two voxel centres.  Otherwise it is the fallback.  In the world the surface is at
+ *          offset[axis] + ((float)lo + height) * voxel_size[axis] forward, offset[axis] + ((float)hi - height) * voxel_size[axis]
+ *          reversed.
+ *        min_distance: with an ESDF handle, the minimum over the column of the ESDF values that are not NaN; NaN if all of them are
+ *          NaN.  A minimum that compares equal to zero is stored as +0.0f, so the order of the reduction never shows.  Without an
+ *          ESDF handle it is NaN.
+ *      Every NaN of height and min_distance is the canonical quiet NaN 0x7FC00000.
+ *   5. tsdf_columns_info: the volume's sizes, voxel sizes and offset as tsdf_explorer_info has them; axis, lo, hi (resolved), flags,
+ *      map_size = {U, V}, map_axes = {a_u, a_v}, has_esdf; the totals n_unknown, n_free, n_occupied over all rows (they sum to
+ *      U * V * L) and n_ground, the cells with top >= 0.  After a classification n_no_ground, n_traversable, n_blocked and the
+ *      max_step and min_headroom given; zero before one, and again after the next projection.  All are unique integers: integer
+ *      atomics, one per counter and workgroup.
+ *   6. Classification: tsdf_columns_classify[_device](map, max_step, min_headroom, flags = 0, uint8 out[U * V], stream), 2.5-D
+ *      traversability from the rows alone, one byte per cell in cell order:
+ *        TSDF_CELL_NO_GROUND 0:   top == -1.
+ *        TSDF_CELL_BLOCKED 2:     top >= 0 and headroom < min_headroom, or some 4-neighbour cell (u -+ 1, v), (u, v -+ 1) inside the
+ *                                 map with top_nb >= 0 has |top - top_nb| > max_step (an integer compare).  A neighbour without ground
+ *                                 blocks nothing.
+ *        TSDF_CELL_TRAVERSABLE 1: every other cell with top >= 0.
+ *   7. The handle (tsdf_columns_create, on the current device) owns the rows and eight counter words, keeps them between calls and
+ *      only grows them: a warm second call allocates nothing.  It snapshots the geometry, so classification and downloads need no
+ *      volume.  tsdf_volume_project_columns runs on the volume's stream and does not synchronise (an ESDF handle's own pending work is
+ *      waited for first, as "reachability" does); tsdf_columns_classify_device runs on hip_stream behind the handle's pending work;
+ *      tsdf_columns_classify blocks.  tsdf_columns_get_info, tsdf_columns_buffer and tsdf_columns_download wait for the handle's
+ *      pending work.  tsdf_columns_scratch_bytes: the device bytes the handle holds, rows (32 a cell of the largest map so far) and
+ *      counters (64).  A handle is used by one thread at a time.  tsdf_columns_destroy(NULL) is ignored.
+ *   8. Refused (TSDF_ERR_INVALID, with a message naming the entry point, before any device work): NULL handle or volume; a Z-slab
+ *      volume; a materialised deformation-node array; axis > 2; lo >= hi after resolving hi == 0; hi > N_axis; an axis of more than
+ *      2^31 - 1 voxels (top is an int32); unknown flags; an ESDF that was never computed, or whose sizes, voxel sizes or offset are not
+ *      the volume's; classification, buffer or download on a handle that was never projected; a NULL output.
+ *   How: a lane per cell, consecutive lanes along the map's u axis, walking its column in strides (columns_walk_kernel).  For axes 1
+ *     and 2 u is x, so every step of the walk reads 64 consecutive words of a row; for axis 0 the lanes lie X words apart.  A second
+ *     kernel for axis 0 -- a wave per column, 64 voxels a step, ballots and popcounts -- was measured against the walk and was slower;
+ *     it is not in the library.
+ *   Out of scope: several surfaces per column (multi-level maps), a 2-D reachability over the classified map, maps inside the pipeline
+ *     step or the tracker, Z-slabs, incremental updates. */
+typedef struct tsdf_columns tsdf_columns;
+#define TSDF_COLUMNS_REVERSED 1u
+#define TSDF_CELL_NO_GROUND 0u
+#define TSDF_CELL_TRAVERSABLE 1u
+#define TSDF_CELL_BLOCKED 2u
+typedef struct tsdf_column {
+    uint32_t n_unknown, n_free, n_occupied;
+    int32_t top, bottom;
+    uint32_t headroom;
+    float height;
+    float min_distance;
+} tsdf_column;
+typedef struct tsdf_columns_info {
+    uint32_t size[3];
+    uint32_t axis;
+    float voxel_size[3];
+    float offset[3];         /* the volume's current offset when projected */
+    uint32_t lo, hi;         /* the band, hi resolved */
+    uint32_t flags;
+    uint32_t has_esdf;
+    uint32_t map_size[2];    /* U, V */
+    uint32_t map_axes[2];    /* a_u, a_v */
+    uint64_t n_unknown, n_free, n_occupied, n_ground;
+    uint64_t n_no_ground, n_traversable, n_blocked;
+    uint32_t max_step, min_headroom;
+} tsdf_columns_info;
+int tsdf_columns_create(tsdf_columns **out);   /* on the current device */
+void tsdf_columns_destroy(tsdf_columns *columns);
+/* esdf may be NULL (min_distance is then NaN); hi == 0: the whole axis from lo. */
+int tsdf_volume_project_columns(const tsdf_volume *volume, uint32_t axis, uint32_t lo, uint32_t hi, const tsdf_esdf *esdf, uint32_t flags,
+                                tsdf_columns *columns);
+int tsdf_columns_get_info(const tsdf_columns *columns, tsdf_columns_info *info);
+/* The device rows of the last projection, map_size[0] * map_size[1] of them; valid until the next projection into the handle. */
+int tsdf_columns_buffer(const tsdf_columns *columns, const tsdf_column **device_rows);
+/* Blocking copy of the rows. */
+int tsdf_columns_download(const tsdf_columns *columns, tsdf_column *host_rows);
+int tsdf_columns_scratch_bytes(const tsdf_columns *columns, uint64_t *bytes);
+/* One byte per cell into a device array, on hip_stream. */
+int tsdf_columns_classify_device(tsdf_columns *columns, uint32_t max_step, uint32_t min_headroom, uint32_t flags /* none defined: 0 */,
+                                 uint8_t *device_cells, void *hip_stream);
+/* The same into a host array; blocking. */
+int tsdf_columns_classify(tsdf_columns *columns, uint32_t max_step, uint32_t min_headroom, uint32_t flags, uint8_t *host_cells);
+
 /* Multi-GPU raycast: a slab evaluates only the samples whose lower trilinear tap plane it owns and writes
  * one 8-byte record per pixel: k = index of the first owned sample with tsdf <= 0 (TSDF_NO_HIT if none), t = that sample's
  * refined ray parameter (src/RayCaster/GPURaycaster.cu:338-341).  After an all-gather of the records (layout

@@ -27,6 +27,8 @@ TSDF_SCENE_FLOW_DEFORMED = 1
 TSDF_SNAPSHOT_BRICK, TSDF_SNAPSHOT_COLOUR = 8, 1
 TSDF_RESTORE_KEEP_OTHERS, TSDF_SELECT_OUTSIDE = 1, 1
 TSDF_WEIGHTS_INVERSE_SQUARE, TSDF_WEIGHTS_COSINE = 1, 2
+TSDF_COLUMNS_REVERSED = 1
+TSDF_CELL_NO_GROUND, TSDF_CELL_TRAVERSABLE, TSDF_CELL_BLOCKED = 0, 1, 2
 
 
 class TsdfError(RuntimeError):
@@ -88,6 +90,21 @@ class ReachInfo(C.Structure):
 class ReachCluster(C.Structure):
     """struct tsdf_reach_cluster (include/tsdf_amd.h): 16 bytes."""
     _fields_ = [("label", C.c_uint32), ("cost", C.c_uint32), ("voxel", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Column(C.Structure):
+    """struct tsdf_column (include/tsdf_amd.h): 32 bytes, top at offset 12, height at 24."""
+    _fields_ = [("n_unknown", C.c_uint32), ("n_free", C.c_uint32), ("n_occupied", C.c_uint32), ("top", C.c_int32), ("bottom", C.c_int32),
+                ("headroom", C.c_uint32), ("height", C.c_float), ("min_distance", C.c_float)]
+
+
+class ColumnsInfo(C.Structure):
+    """struct tsdf_columns_info (include/tsdf_amd.h): 136 bytes, lo at offset 40, n_unknown at 72, max_step at 128."""
+    _fields_ = [("size", C.c_uint32 * 3), ("axis", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
+                ("lo", C.c_uint32), ("hi", C.c_uint32), ("flags", C.c_uint32), ("has_esdf", C.c_uint32), ("map_size", C.c_uint32 * 2),
+                ("map_axes", C.c_uint32 * 2), ("n_unknown", C.c_uint64), ("n_free", C.c_uint64), ("n_occupied", C.c_uint64),
+                ("n_ground", C.c_uint64), ("n_no_ground", C.c_uint64), ("n_traversable", C.c_uint64), ("n_blocked", C.c_uint64),
+                ("max_step", C.c_uint32), ("min_headroom", C.c_uint32)]
 
 
 class ObjectsInfo(C.Structure):
@@ -353,6 +370,15 @@ _SIGS = {
     "tsdf_volume_restore_shifted": (_i, [_vp, _vp, C.POINTER(C.c_int32), _u32]),
     "tsdf_snapshot_select": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _vp]),
     "tsdf_volume_shift": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp]),
+    "tsdf_columns_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_columns_destroy": (None, [_vp]),
+    "tsdf_volume_project_columns": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "tsdf_columns_get_info": (_i, [_vp, C.POINTER(ColumnsInfo)]),
+    "tsdf_columns_buffer": (_i, [_vp, C.POINTER(_vp)]),
+    "tsdf_columns_download": (_i, [_vp, _vp]),
+    "tsdf_columns_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_columns_classify_device": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "tsdf_columns_classify": (_i, [_vp, _u32, _u32, _u32, _vp]),
     "tsdf_merge_hits_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp]),
     "tsdf_merge_hits_normals_device": (_i, [_vp, _vp, _u32, _u32, _u32, _fp, _fp, _vp, _vp, _vp]),
     "tsdf_slab_exchange_unique_id": (_i, [_vp, C.c_char_p]),

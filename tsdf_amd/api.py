@@ -661,6 +661,22 @@ class TSDFVolume:
                                             _capi.TSDF_REACH_THROUGH_UNKNOWN if through_unknown else 0, reach._h))
         return reach
 
+    # ---- column maps (include/tsdf_amd.h, "column maps"; not in the reference's class)
+    def column_map(self, axis=2, band=None, reversed=False, esdf=None, into=None):
+        """Every column of voxels along `axis` (0, 1, 2 for x, y, z) reduced to one row of a 2-D map over the two other axes
+        (tsdf_volume_project_columns): counts of unknown / free / occupied voxels, the highest and lowest occupied voxel (top, bottom),
+        the free run above the top (headroom), the sub-voxel height of the surface there and, with `esdf` (an ESDF of this volume), the
+        smallest distance to a surface anywhere in the column.  band: (lo, hi) voxel indices on the axis, None for all of it;
+        reversed: "up" is towards smaller indices.  It stays on the device and the call does not wait.  `into`: a ColumnMap to reuse
+        -- its arrays are kept and only grow.  Returns the ColumnMap."""
+        lo, hi = (0, 0) if band is None else (int(band[0]), int(band[1]))
+        if band is not None and hi == 0:
+            raise ValueError("column_map: the band (%d, %d) is empty" % (lo, hi))   # (hi == 0 is the C ABI's "to the axis' end")
+        cmap = ColumnMap() if into is None else into
+        flags = _capi.TSDF_COLUMNS_REVERSED if reversed else 0
+        check(lib.tsdf_volume_project_columns(self._h, int(axis), lo, hi, esdf._h if esdf is not None else None, flags, cmap._h))
+        return cmap
+
     # ---- class objects (include/tsdf_amd.h, "class objects"; not in the reference's class)
     def find_objects(self, min_votes=1, classes=None, connectivity=26, min_size=1, into=None):
         """The connected pieces of each fused class (tsdf_volume_find_objects): the voxels whose word has at least max(min_votes, 1)
@@ -1591,6 +1607,65 @@ class Reach(_Handle):
         vs, off = np.array(i.voxel_size, np.float32), np.array(i.offset, np.float32)
         c = _voxel_coordinates(np.asarray(ids, np.uint32).reshape(-1), i.size)
         return ((c.astype(np.float32) + np.float32(0.5)) * vs + off).astype(np.float32)
+
+
+#: one row of ColumnMap.columns: struct tsdf_column (32 bytes)
+COLUMN_DTYPE = np.dtype([("n_unknown", np.uint32), ("n_free", np.uint32), ("n_occupied", np.uint32), ("top", np.int32), ("bottom", np.int32),
+                         ("headroom", np.uint32), ("height", np.float32), ("min_distance", np.float32)])
+CELL_NO_GROUND, CELL_TRAVERSABLE, CELL_BLOCKED = _capi.TSDF_CELL_NO_GROUND, _capi.TSDF_CELL_TRAVERSABLE, _capi.TSDF_CELL_BLOCKED
+
+
+class ColumnMap(_Handle):
+    """tsdf_columns (include/tsdf_amd.h, "column maps"): the rows of a 2-D map of a volume's columns along one axis
+    (TSDFVolume.column_map(into=cmap)), on the device, with the geometry they belong to.  Classification and downloads need no volume."""
+
+    _c, _Info = "columns", _capi.ColumnsInfo
+
+    @property
+    def info(self):
+        """tsdf_columns_info: size, axis, voxel_size, offset, lo, hi, flags, has_esdf, map_size (U, V), map_axes, the totals n_unknown,
+        n_free, n_occupied, n_ground and, after classify, n_no_ground, n_traversable, n_blocked, max_step, min_headroom.  Waits for
+        the handle's pending work."""
+        return self._get_info()
+
+    @property
+    def columns(self):
+        """(V, U) COLUMN_DTYPE: the row of cell (u, v) at [v, u]; a blocking download."""
+        u, v = (int(n) for n in self.info.map_size)
+        out = np.zeros(u * v + 1, COLUMN_DTYPE)   # (one element more: the pointer of an empty array may be null)
+        check(lib.tsdf_columns_download(self._h, out.ctypes.data))
+        return out[:-1].reshape(v, u)
+
+    def device_buffer(self):
+        """The raw device pointer of the rows (cell order, 32 bytes each); valid until the next projection into this handle."""
+        p = C.c_void_p()
+        check(lib.tsdf_columns_buffer(self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def classify_device(self, max_step, min_headroom, cells_ptr, stream=None):
+        """One uint8 per cell (CELL_NO_GROUND / CELL_TRAVERSABLE / CELL_BLOCKED) into U * V device bytes, on `stream` (default: the
+        null stream), ordered behind the projection."""
+        check(lib.tsdf_columns_classify_device(self._h, int(max_step), int(min_headroom), 0, C.c_void_p(int(cells_ptr)) if cells_ptr else None,
+                                               C.c_void_p(int(stream) if stream else 0)))
+
+    def classify(self, max_step, min_headroom):
+        """(V, U) uint8: CELL_NO_GROUND where the column holds no occupied voxel; CELL_BLOCKED where the headroom is below
+        min_headroom or a 4-neighbour with ground has a top more than max_step voxels away; CELL_TRAVERSABLE otherwise."""
+        u, v = (int(n) for n in self.info.map_size)
+        out = np.zeros(u * v + 1, np.uint8)
+        check(lib.tsdf_columns_classify(self._h, int(max_step), int(min_headroom), 0, out.ctypes.data))
+        return out[:-1].reshape(v, u)
+
+    def height_world(self, columns=None):
+        """(V, U) float32: the world coordinate (mm) of the surface on the map's axis, offset + (lo + height) * voxel_size forward,
+        offset + (hi - height) * voxel_size reversed, in fp32; NaN where a cell has no ground.  columns: rows already downloaded."""
+        i = self.info
+        rows = self.columns if columns is None else columns
+        f32 = np.float32
+        off, vs = f32(i.offset[i.axis]), f32(i.voxel_size[i.axis])
+        if i.flags & _capi.TSDF_COLUMNS_REVERSED:
+            return (off + (f32(i.hi) - rows["height"]) * vs).astype(f32)
+        return (off + (f32(i.lo) + rows["height"]) * vs).astype(f32)
 
 
 #: one row of Objects.objects: struct tsdf_class_object (72 bytes)

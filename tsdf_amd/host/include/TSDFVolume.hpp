@@ -26,6 +26,9 @@ struct tsdf_frontier_cluster;  // a row of its cluster table (include/tsdf_amd.h
 struct tsdf_reach;          // reachability handle (include/tsdf_amd.h)
 struct tsdf_reach_info;     // what it reports of its last computation (include/tsdf_amd.h)
 struct tsdf_reach_cluster;  // a row of its ranking of frontier clusters (include/tsdf_amd.h)
+struct tsdf_columns;        // column map handle (include/tsdf_amd.h)
+struct tsdf_columns_info;   // what it reports of its last projection and classification (include/tsdf_amd.h)
+struct tsdf_column;         // a row of the map (include/tsdf_amd.h)
 struct tsdf_objects;       // class-objects handle (include/tsdf_amd.h)
 struct tsdf_class_object;  // a row of its table (include/tsdf_amd.h)
 
@@ -294,6 +297,35 @@ public:
     // the field is final.  Throws std::invalid_argument on the refusals.
     void reach(const std::vector<float3> &seeds, uint32_t connectivity, const tsdf_esdf *esdf, float clearance, uint32_t max_cost,
                uint32_t flags, Reach &into) const;
+
+    // Column maps (include/tsdf_amd.h, "column maps"; not in the reference's class): every column of voxels along one axis reduced to one
+    // row of a 2-D map over the two other axes, and a 2.5-D traversability class per cell, in a handle that keeps its device arrays
+    // between calls and needs no volume once projected.
+    class ColumnMap {
+    public:
+        ColumnMap();    // throws std::invalid_argument / exits like every device failure when the handle cannot be made
+        ~ColumnMap();
+        ColumnMap(const ColumnMap &) = delete;
+        ColumnMap &operator=(const ColumnMap &) = delete;
+        inline tsdf_columns *handle() const { return m_handle; }
+        // tsdf_columns_info of the last projection and classification; waits for the handle's pending work
+        tsdf_columns_info info() const;
+        // the rows in cell order, cell (u, v) at v * map_size[0] + u (tsdf_column, include/tsdf_amd.h); a blocking download
+        std::vector<tsdf_column> columns() const;
+        // one class per cell (TSDF_CELL_NO_GROUND / _TRAVERSABLE / _BLOCKED) in cell order.  Throws std::invalid_argument before any
+        // projection.
+        std::vector<uint8_t> classify(uint32_t max_step, uint32_t min_headroom);
+        // rule 4's world coordinate of a row's height on the map's axis, in fp32 (NaN where the cell has no ground)
+        float height_world(const tsdf_column &row) const;
+
+    private:
+        tsdf_columns *m_handle;
+    };
+    // The map of this volume's columns along `axis` over the band [lo, hi) (hi 0: the axis' end) into `into` (nothing of the volume is
+    // written); reversed: "up" is towards smaller indices; esdf (may be null): the handle whose values min_distance is the minimum of.
+    // Does not wait.  Throws std::invalid_argument on the refusals (an axis above 2, an empty band or one that leaves the axis, a
+    // Z-slab, materialised deformation nodes, an ESDF never computed or of another geometry).
+    void column_map(ColumnMap &into, uint32_t axis = 2, uint32_t lo = 0, uint32_t hi = 0, bool reversed = false, const tsdf_esdf *esdf = nullptr) const;
 
     // Class objects (include/tsdf_amd.h, "class objects"; not in the reference's class): the connected pieces of each fused class and
     // their table, in a handle that keeps its device arrays between calls.

@@ -322,6 +322,45 @@ void TSDFVolume::reach(const std::vector<float3> &seeds, uint32_t connectivity, 
           "Couldn't compute the reach");
 }
 
+TSDFVolume::ColumnMap::ColumnMap() : m_handle{nullptr} { check(tsdf_columns_create(&m_handle), "Couldn't create the columns handle"); }
+
+TSDFVolume::ColumnMap::~ColumnMap() { tsdf_columns_destroy(m_handle); }
+
+tsdf_columns_info TSDFVolume::ColumnMap::info() const {
+    tsdf_columns_info info;
+    check(tsdf_columns_get_info(m_handle, &info), "Couldn't query the columns handle");
+    return info;
+}
+
+std::vector<tsdf_column> TSDFVolume::ColumnMap::columns() const {
+    const tsdf_columns_info i = info();
+    // (one element more than needed: data() of an empty vector may be null)
+    std::vector<tsdf_column> rows((size_t)i.map_size[0] * i.map_size[1] + 1, tsdf_column());
+    check(tsdf_columns_download(m_handle, rows.data()), "Couldn't download the columns");
+    rows.pop_back();
+    return rows;
+}
+
+std::vector<uint8_t> TSDFVolume::ColumnMap::classify(uint32_t max_step, uint32_t min_headroom) {
+    const tsdf_columns_info i = info();
+    std::vector<uint8_t> cells((size_t)i.map_size[0] * i.map_size[1] + 1, (uint8_t)0);
+    check(tsdf_columns_classify(m_handle, max_step, min_headroom, 0u, cells.data()), "Couldn't classify the columns");
+    cells.pop_back();
+    return cells;
+}
+
+float TSDFVolume::ColumnMap::height_world(const tsdf_column &row) const {
+    const tsdf_columns_info i = info();
+    const float along = (i.flags & TSDF_COLUMNS_REVERSED) ? (float)i.hi - row.height : (float)i.lo + row.height;
+    const float scaled = along * i.voxel_size[i.axis];
+    return i.offset[i.axis] + scaled;
+}
+
+void TSDFVolume::column_map(ColumnMap &into, uint32_t axis, uint32_t lo, uint32_t hi, bool reversed, const tsdf_esdf *esdf) const {
+    check(tsdf_volume_project_columns(m_handle, axis, lo, hi, esdf, reversed ? TSDF_COLUMNS_REVERSED : 0u, into.handle()),
+          "Couldn't project the columns");
+}
+
 TSDFVolume::Objects::Objects() : m_handle{nullptr} { check(tsdf_objects_create(&m_handle), "Couldn't create the objects handle"); }
 
 TSDFVolume::Objects::~Objects() { tsdf_objects_destroy(m_handle); }
