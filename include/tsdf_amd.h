@@ -1169,6 +1169,101 @@ int tsdf_vertex_normals_device(uint64_t n_vertices, uint64_t n_indices, const fl
                                float *device_normals_out, void *hip_stream);
 int tsdf_mesh_compute_normals(tsdf_mesh *mesh, void *hip_stream);
 
+/* ---- mesh rendering (no reference counterpart: the reference renders its volume, never a mesh) ------------------------------------- */
+/* An indexed mesh rasterised from a pinhole camera into depth, vertex, normal, colour and triangle-id maps, on the device: the view of
+ * a mesh that no longer matches a resident volume (simplified, smoothed, filtered, deformed, loaded, or paged out).  Opt-in by being
+ * called: no other entry point, launch or result changes.  A volume is not an argument.
+ *   The result (unique bytes, whatever computes them), for V (n_vertices float triples), I (n_indices uint32, a multiple of 3),
+ *   optionally a normal (float triple) and a colour (3 bytes) per vertex, width, height, inv_pose[16] and k[9] (column-major), z_near,
+ *   z_far and flags.  Triangle t has the corners (I[3t], I[3t+2], I[3t+1]), the wiring extract_surface uses; corner 0, 1, 2 below are
+ *   those, in that order.  Every fp32 operation is rounded on its own (no contraction), in exactly the order written.
+ *   1. Camera point, per shared vertex: c = world_to_camera(V[e], inv_pose) (cuda_coordinate_transforms.cu:108-121): each row
+ *     ((m_i1 x + m_i2 y) + m_i3 z) + m_i4, then x, y, z each divided by w.  r = 1.0f / c.z.
+ *   2. Screen point: sx = fx * (c.x / c.z) + cx, sy = fy * (c.y / c.z) + cy with fx = k[0], fy = k[4], cx = k[6], cy = k[7].  Pixel
+ *     (i, j) has its centre at the screen point (i, j) (world_to_pixel's roundf).  X = (int32)rintf(sx * 256.0f), Y likewise.  A vertex
+ *     is USABLE iff c is finite, z_near <= c.z <= z_far and |sx|, |sy| <= 2^20 (so |X|, |Y| <= 2^28).
+ *   3. A triangle is LIVE iff its three indices are < n_vertices, its three corners are usable and
+ *     A2 = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0), formed in 64 bits, is not 0.  With TSDF_RENDER_CULL_BACK also A2 < 0: that is the
+ *     FRONT-FACING sign -- x to the right, y down, the camera looking along +z -- and the one extract_surface's wiring of a fused surface
+ *     has when seen from outside through a rigid pose.  There is no near-plane clipping: a triangle with a corner that is not usable is
+ *     dropped and counted (n_dropped).
+ *   4. Coverage of pixel (i, j), at P = (256 i, 256 j): with s = sign(A2), for k = 0, 1, 2 and (A, B) = (P1, P2), (P2, P0), (P0, P1),
+ *     E_k(P) = a_k P.x + b_k P.y + c_k, a_k = -s (B.y - A.y), b_k = s (B.x - A.x), c_k = s ((B.y - A.y) A.x - (B.x - A.x) A.y), all in
+ *     64 bits; E_0 + E_1 + E_2 == |A2|.  The pixel is covered iff for every k: E_k > 0, or E_k == 0 and edge k is TOP-LEFT: a_k > 0, or
+ *     a_k == 0 and b_k > 0.  Only pixels of the image inside the corners' bounding box are asked, so |P| <= 2^28 and every product stays
+ *     below 2^58.  Two triangles that share an edge with opposite directions cover each centre on it exactly once.
+ *   5. Depth: b1 = (float)E_1 / (float)|A2|, b2 = (float)E_2 / (float)|A2| (int64 to fp32, round to nearest even);
+ *     rr = r0 + (b1 * (r1 - r0) + b2 * (r2 - r0)); z = 1.0f / rr.  A covered pixel yields a fragment iff z is finite and
+ *     z_near <= z <= z_far.
+ *   6. Visibility: a fragment's key is ((uint64)bits(z) << 32) | t; the pixel's winner is the smallest key over all its fragments
+ *     (z > 0: the bits order like the values), so equal depths go to the smaller triangle index.  No fragment: a miss.
+ *   7. Targets, each an optional device pointer of tsdf_render_targets, in pixel order y * width + x, of the winner:
+ *     triangle (uint32) t, 0xFFFFFFFF on a miss.  z (fp32) the key's z, NaN on a miss.  depth (uint16) tsdf_vertices_to_depth_device's
+ *     conversion of z: (uint16)roundf(z), 0 on a miss or outside 1..65535.
+ *     With q1 = (b1 * r1) * z, q2 = (b2 * r2) * z and mix(a0, a1, a2) = a0 + (q1 * (a1 - a0) + q2 * (a2 - a0)) (perspective-correct):
+ *     vertices (float triple) mix per component of the corners' world positions, a NaN triple on a miss: the layout of
+ *     tsdf_raycast_device's vertex map, so it feeds tsdf_normals_device, ICP, the reach and object lookups.
+ *     normals (float triple), with vertex normals: n = mix per component of the corners' normals, then n / L per component with
+ *     L = sqrtf((n.x n.x + n.y n.y) + n.z n.z); a NaN triple if a component of n is not finite or L == 0.  Without vertex normals: the
+ *     same normalisation of the face normal u x w = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x), u = V1 - V0, w = V2 - V0
+ *     in fp32: it points out of a fused surface, as the field queries' unit gradient does.  NaN triple on a miss.
+ *     rgb (3 bytes): per channel f = mix of the corners' bytes as floats, + 0.5f, then 0 unless f > 0, 255 where f > 255, truncated;
+ *     (0, 0, 0) on a miss.
+ *   8. tsdf_render_info: n_triangles = n_indices / 3; n_live (3); n_dropped: triangles with valid indices and a corner that is not
+ *     usable; n_large: live triangles whose clipped pixel box held more than TSDF_RENDER_LARGE_BOX pixels (tsdf_render_set_large_box; they take
+ *     render_large_kernel; scheduling only); n_pixels_hit.  Integer atomics, one per counter and workgroup, read through a pinned
+ *     mirror.  A render synchronises only when `info` is not NULL; tsdf_render_get_info waits for the last render and gives the same.
+ *   An index >= n_vertices is found on the device before it is used as an address (its triangle is dead) and reported as
+ *     TSDF_ERR_INVALID by the next call that waits: the render itself when info is given, tsdf_render_get_info, tsdf_mesh_render.  The
+ *     targets then hold the render of the other triangles.  With n_vertices == 0 any index is refused on the host.  An empty mesh is a
+ *     successful render of all misses.
+ *   tsdf_render_mesh_device: any arrays on the device, device targets, enqueued on hip_stream (NULL: the default stream).
+ *     tsdf_mesh_render_device: a mesh handle's arrays (normals and colours where it has them), ordered behind its pending work; the
+ *     mesh is not written.  tsdf_mesh_render: the same into host arrays, blocking.
+ *   The handle begins with the stream order every handle has; it owns its scratch, which only grows: 8 bytes per pixel (the keys), 16
+ *     bytes per shared vertex ({X, Y, r, usable}), 4 bytes per triangle + 4 (the large list), 40 bytes of counters
+ *     (tsdf_render_scratch_bytes).  A warm repeat allocates nothing.  A handle is used by one thread at a time, on its device.
+ *   How: render_project_kernel, a lane per shared vertex; the keys set to all ones by a memset; render_raster_kernel, a lane per
+ *     triangle walking its box; render_large_kernel, a wave per listed triangle in 8 x 8 tiles; render_resolve_kernel, a lane per
+ *     pixel.  Visibility is one 64-bit atomicMin without return per fragment, behind a plain load and a skip when the fragment's key
+ *     is not smaller (words only fall).  No float atomics, no compare-and-swap loop, no lane waits for another.
+ *   Refused (TSDF_ERR_INVALID, with a message, before any device work): NULL handle, mesh, targets, arrays with non-zero counts or
+ *     matrices; n_indices % 3 != 0; counts above 2^32 - 1; an image of no pixels or of 2^32 - 1 or more; a matrix entry that is not
+ *     finite; a k whose other entries differ from (0, 0, 0, 0, 1); z_near or z_far not finite, z_near <= 0, z_near > z_far; unknown
+ *     flags; an rgb target for a mesh without colours; handles made on different devices.
+ *   Out of scope: near-plane clipping, several meshes in one key buffer, anti-aliasing, general cameras, textures, use inside the
+ *     tracker or the pipeline, visibility for the scene-flow correspondence. */
+typedef struct tsdf_render tsdf_render;
+#define TSDF_RENDER_CULL_BACK 1u
+#define TSDF_RENDER_LARGE_BOX 256u
+typedef struct tsdf_render_targets {
+    uint32_t *triangle;
+    float *z;
+    uint16_t *depth;
+    float *vertices;
+    float *normals;
+    uint8_t *rgb;
+} tsdf_render_targets;
+typedef struct tsdf_render_info {
+    uint64_t n_triangles, n_live, n_dropped, n_large, n_pixels_hit;
+} tsdf_render_info;
+int tsdf_render_create(tsdf_render **out);   /* on the current device */
+void tsdf_render_destroy(tsdf_render *render);
+int tsdf_render_scratch_bytes(const tsdf_render *render, uint64_t *bytes);
+int tsdf_render_get_info(const tsdf_render *render, tsdf_render_info *info);
+/* Scheduling only: from how many pixels of its clipped box on a live triangle goes to render_large_kernel (TSDF_RENDER_LARGE_BOX when the
+ * handle is made; 0xFFFFFFFF: every triangle stays on the lane path).  No target changes by a byte; n_large counts by this value. */
+int tsdf_render_set_large_box(tsdf_render *render, uint32_t pixels);
+int tsdf_render_mesh_device(tsdf_render *render, uint64_t n_vertices, uint64_t n_indices, const float *device_vertices,
+                            const uint32_t *device_indices, const float *device_normals, const uint8_t *device_rgb, uint32_t width,
+                            uint32_t height, const float inv_pose[16], const float k[9], float z_near, float z_far, uint32_t flags,
+                            const tsdf_render_targets *device_targets, tsdf_render_info *info, void *hip_stream);
+int tsdf_mesh_render_device(tsdf_render *render, tsdf_mesh *mesh, uint32_t width, uint32_t height, const float inv_pose[16],
+                            const float k[9], float z_near, float z_far, uint32_t flags, const tsdf_render_targets *device_targets,
+                            tsdf_render_info *info, void *hip_stream);
+int tsdf_mesh_render(tsdf_render *render, tsdf_mesh *mesh, uint32_t width, uint32_t height, const float inv_pose[16], const float k[9],
+                     float z_near, float z_far, uint32_t flags, const tsdf_render_targets *host_targets, tsdf_render_info *info);
+
 /* ---- scene flow (replaces the device part of process_frames, src/SceneFusion/SceneFusion_krnl.cu:235-401) ------------------------- */
 /* One frame of the reference's non-rigid step: the mesh vertices a depth frame sees take the scene flow at their pixel, and the flow
  * is pushed into the deformation nodes of the two voxels that bracket each vertex -- the reference's update made deterministic.  Opt-in

@@ -29,6 +29,9 @@ TSDF_RESTORE_KEEP_OTHERS, TSDF_SELECT_OUTSIDE = 1, 1
 TSDF_WEIGHTS_INVERSE_SQUARE, TSDF_WEIGHTS_COSINE = 1, 2
 TSDF_COLUMNS_REVERSED = 1
 TSDF_CELL_NO_GROUND, TSDF_CELL_TRAVERSABLE, TSDF_CELL_BLOCKED = 0, 1, 2
+TSDF_RENDER_CULL_BACK = 1
+TSDF_RENDER_LARGE_BOX = 256
+TSDF_RENDER_MISS = 0xFFFFFFFF
 
 
 class TsdfError(RuntimeError):
@@ -105,6 +108,18 @@ class ColumnsInfo(C.Structure):
                 ("map_axes", C.c_uint32 * 2), ("n_unknown", C.c_uint64), ("n_free", C.c_uint64), ("n_occupied", C.c_uint64),
                 ("n_ground", C.c_uint64), ("n_no_ground", C.c_uint64), ("n_traversable", C.c_uint64), ("n_blocked", C.c_uint64),
                 ("max_step", C.c_uint32), ("min_headroom", C.c_uint32)]
+
+
+class RenderTargets(C.Structure):
+    """struct tsdf_render_targets (include/tsdf_amd.h): 48 bytes, six optional pointers."""
+    _fields_ = [("triangle", C.c_void_p), ("z", C.c_void_p), ("depth", C.c_void_p), ("vertices", C.c_void_p), ("normals", C.c_void_p),
+                ("rgb", C.c_void_p)]
+
+
+class RenderInfo(C.Structure):
+    """struct tsdf_render_info (include/tsdf_amd.h): 40 bytes."""
+    _fields_ = [("n_triangles", C.c_uint64), ("n_live", C.c_uint64), ("n_dropped", C.c_uint64), ("n_large", C.c_uint64),
+                ("n_pixels_hit", C.c_uint64)]
 
 
 class ObjectsInfo(C.Structure):
@@ -312,6 +327,15 @@ _SIGS = {
     "tsdf_mesh_smooth": (_i, [_vp, _u32, C.c_float, C.c_float, _u32, _vp, _vp]),
     "tsdf_vertex_normals_device": (_i, [C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]),
     "tsdf_mesh_compute_normals": (_i, [_vp, _vp]),
+    "tsdf_render_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_render_destroy": (None, [_vp]),
+    "tsdf_render_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_render_get_info": (_i, [_vp, C.POINTER(RenderInfo)]),
+    "tsdf_render_set_large_box": (_i, [_vp, _u32]),
+    "tsdf_render_mesh_device": (_i, [_vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _f, _f, _u32, C.POINTER(RenderTargets),
+                                     C.POINTER(RenderInfo), _vp]),
+    "tsdf_mesh_render_device": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _f, _f, _u32, C.POINTER(RenderTargets), C.POINTER(RenderInfo), _vp]),
+    "tsdf_mesh_render": (_i, [_vp, _vp, _u32, _u32, _fp, _fp, _f, _f, _u32, C.POINTER(RenderTargets), C.POINTER(RenderInfo)]),
     "tsdf_volume_apply_scene_flow": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _f, _u32, C.POINTER(SceneFlowInfo)]),
     "tsdf_volume_apply_scene_flow_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _fp, _fp, _fp, _fp, _f, _u32, C.POINTER(SceneFlowInfo), _vp]),
     "tsdf_esdf_create": (_i, [C.POINTER(_vp)]),

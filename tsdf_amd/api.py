@@ -1377,6 +1377,136 @@ class Mesh(_Handle):
         check(lib.tsdf_mesh_compute_normals(self._h, C.c_void_p(int(stream) if stream else 0)))
         return self
 
+    # ---- mesh rendering (include/tsdf_amd.h, "mesh rendering")
+    def render(self, inv_pose, k, size, near=1.0, far=65535.0, cull_back=False, targets=("depth",), into=None):
+        """The mesh seen from a pinhole camera (tsdf_mesh_render): `inv_pose` (16) and `k` (9) column-major, `size` = (width, height),
+        only triangles with all corners in [near, far] are drawn.  `targets`: any of RENDER_TARGETS.  Returns a dict of host arrays in
+        pixel order -- triangle (n,) uint32, z (n,) float32, depth (n,) uint16, vertices / normals (n, 3) float32, rgb (n, 3) uint8 --
+        and "info".  `into`: a Renderer to reuse.  Blocking."""
+        renderer = Renderer() if into is None else into
+        try:
+            return renderer.render(self, inv_pose, k, size, near, far, cull_back, targets)
+        finally:
+            if into is None:
+                renderer.close()
+
+
+#: the maps a render can fill: name -> (dtype, values per pixel)
+RENDER_TARGETS = {"triangle": (np.uint32, 1), "z": (np.float32, 1), "depth": (np.uint16, 1), "vertices": (np.float32, 3),
+                  "normals": (np.float32, 3), "rgb": (np.uint8, 3)}
+RENDER_CULL_BACK = _capi.TSDF_RENDER_CULL_BACK
+RENDER_MISS = _capi.TSDF_RENDER_MISS
+
+
+def _render_info(i):
+    return {"n_triangles": int(i.n_triangles), "n_live": int(i.n_live), "n_dropped": int(i.n_dropped), "n_large": int(i.n_large),
+            "n_pixels_hit": int(i.n_pixels_hit)}
+
+
+def _render_targets(pointers):
+    unknown = set(pointers) - set(RENDER_TARGETS)
+    if unknown:
+        raise ValueError("unknown render targets %s (known: %s)" % (sorted(unknown), ", ".join(RENDER_TARGETS)))
+    return _capi.RenderTargets(**{name: C.c_void_p(int(p) if p else 0) for name, p in pointers.items()})
+
+
+class Renderer(_Handle):
+    """tsdf_render (include/tsdf_amd.h, "mesh rendering"): the scratch of the mesh renderer -- 8 bytes per pixel, 16 per shared vertex, 4
+    per triangle -- kept between renders, so a warm one allocates nothing."""
+
+    _c, _Info = "render", _capi.RenderInfo
+
+    def info(self):
+        """The counts of the last render (waits for it): n_triangles, n_live, n_dropped, n_large, n_pixels_hit.  ValueError if the
+        render met an index that is not below n_vertices."""
+        return _render_info(self._get_info())
+
+    def set_large_box(self, pixels=_capi.TSDF_RENDER_LARGE_BOX):
+        """Scheduling only (tsdf_render_set_large_box): a live triangle whose clipped box holds more pixels than this is rasterised by a
+        whole wave; None: never."""
+        check(lib.tsdf_render_set_large_box(self._h, 0xFFFFFFFF if pixels is None else int(pixels)))
+
+    def _view(self, inv_pose, k, size, cull_back):
+        width, height = (int(v) for v in size)
+        return width, height, _mat(inv_pose, 16), _mat(k, 9), (_capi.TSDF_RENDER_CULL_BACK if cull_back else 0)
+
+    def render_device(self, mesh, inv_pose, k, size, near, far, cull_back=False, targets=None, info=False, stream=0):
+        """tsdf_mesh_render_device: the Mesh `mesh` into device pointers (`targets`: name -> pointer), enqueued on `stream` behind the
+        mesh's pending work.  With `info` the call waits and returns the counts, otherwise None."""
+        width, height, ip, km, flags = self._view(inv_pose, k, size, cull_back)
+        t, i = _render_targets(targets or {}), _capi.RenderInfo()
+        check(lib.tsdf_mesh_render_device(self._h, mesh._h, width, height, _fp(ip), _fp(km), float(near), float(far), flags, C.byref(t),
+                                          C.byref(i) if info else None, C.c_void_p(int(stream) if stream else 0)))
+        return _render_info(i) if info else None
+
+    def render_arrays_device(self, n_vertices, n_indices, vertices_ptr, indices_ptr, inv_pose, k, size, near, far, cull_back=False, targets=None,
+                             normals_ptr=0, colours_ptr=0, info=False, stream=0):
+        """tsdf_render_mesh_device: plain device arrays (float32 x 3 vertices, uint32 indices, float32 x 3 normals or 0, uint8 x 3
+        colours or 0) into device pointers."""
+        width, height, ip, km, flags = self._view(inv_pose, k, size, cull_back)
+        vp = lambda p: C.c_void_p(int(p) if p else 0)
+        t, i = _render_targets(targets or {}), _capi.RenderInfo()
+        check(lib.tsdf_render_mesh_device(self._h, int(n_vertices), int(n_indices), vp(vertices_ptr), vp(indices_ptr), vp(normals_ptr), vp(colours_ptr),
+                                          width, height, _fp(ip), _fp(km), float(near), float(far), flags, C.byref(t), C.byref(i) if info else None,
+                                          vp(stream)))
+        return _render_info(i) if info else None
+
+    def render(self, mesh, inv_pose, k, size, near=1.0, far=65535.0, cull_back=False, targets=("depth",)):
+        """tsdf_mesh_render: the Mesh `mesh` into host arrays, blocking; see Mesh.render."""
+        width, height, ip, km, flags = self._view(inv_pose, k, size, cull_back)
+        n = max(width * height, 0)
+        out = {name: np.empty((n, RENDER_TARGETS[name][1]) if RENDER_TARGETS[name][1] > 1 else (n,), RENDER_TARGETS[name][0])
+               for name in targets if name in RENDER_TARGETS}
+        t, i = _render_targets({name: (out[name].ctypes.data if name in out else 1) for name in targets}), _capi.RenderInfo()
+        check(lib.tsdf_mesh_render(self._h, mesh._h, width, height, _fp(ip), _fp(km), float(near), float(far), flags, C.byref(t), C.byref(i)))
+        out["info"] = _render_info(i)
+        return out
+
+
+def render_mesh_device(renderer, n_vertices, n_indices, vertices_ptr, indices_ptr, inv_pose, k, size, near, far, cull_back=False, targets=None,
+                       normals_ptr=0, colours_ptr=0, info=False, stream=0):
+    """tsdf_render_mesh_device on device pointers with the Renderer `renderer` (Renderer.render_arrays_device)."""
+    return renderer.render_arrays_device(n_vertices, n_indices, vertices_ptr, indices_ptr, inv_pose, k, size, near, far, cull_back, targets, normals_ptr,
+                                         colours_ptr, info, stream)
+
+
+def render_mesh(vertices, indices, inv_pose, k, size, near=1.0, far=65535.0, cull_back=False, targets=("depth",), normals=None, colours=None,
+                into=None):
+    """Host arrays rendered on the device (upload, tsdf_render_mesh_device, download): (n, 3) float32 vertices, 3 m indices, optionally
+    (n, 3) float32 normals and (n, 3) uint8 colours -> the dict Mesh.render returns.  `into`: a Renderer to reuse."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    I = np.ascontiguousarray(np.asarray(indices).reshape(-1), np.uint32)
+    N = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    RGB = None if colours is None else np.ascontiguousarray(colours, np.uint8).reshape(-1, 3)
+    for a, what in ((N, "normals"), (RGB, "colours")):
+        if a is not None and len(a) != len(V):
+            raise ValueError("%d %s for %d vertices" % (len(a), what, len(V)))
+    _render_targets({name: 0 for name in targets})
+    width, height = (int(v) for v in size)
+    n = max(width * height, 0)
+    out = {name: np.empty((n, RENDER_TARGETS[name][1]) if RENDER_TARGETS[name][1] > 1 else (n,), RENDER_TARGETS[name][0]) for name in targets}
+    renderer = Renderer() if into is None else into
+    try:
+        with _DeviceArray(V) as dv, _DeviceArray(I) as di, _DeviceArray(nbytes=4) as none:
+            with _DeviceArray(N if N is not None and len(V) else None, 0) as dn, _DeviceArray(RGB if RGB is not None and len(V) else None, 0) as dc:
+                given = lambda a, d: 0 if a is None else (d.ptr.value or none.ptr.value)      # (see simplify_mesh)
+                buffers = {name: _DeviceArray(nbytes=max(a.nbytes, 4)) for name, a in out.items()}
+                try:
+                    for b in buffers.values():
+                        b.__enter__()
+                    out["info"] = renderer.render_arrays_device(len(V), I.size, dv.ptr.value, di.ptr.value, inv_pose, k, (width, height), near, far, cull_back,
+                                                                {name: b.ptr.value for name, b in buffers.items()}, given(N, dn), given(RGB, dc), info=True)
+                    for name, b in buffers.items():
+                        if out[name].nbytes:
+                            check(lib.tsdf_device_download(out[name].ctypes.data, b.ptr, out[name].nbytes))
+                finally:
+                    for b in buffers.values():
+                        b.__exit__()
+        return out
+    finally:
+        if into is None:
+            renderer.close()
+
 
 class ESDF(_Handle):
     """tsdf_esdf (include/tsdf_amd.h, "distance field"): the device array of a distance field, its scratch and the geometry it was
