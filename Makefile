@@ -11,7 +11,7 @@ CSRC      = tsdf_amd/csrc
 ifeq ($(DIAG),1)
 HIPFLAGS += -DTSDF_DIAGNOSTICS
 endif
-HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_weighted.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/classes.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_scan.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/mesh_render.hip $(CSRC)/esdf.hip $(CSRC)/explore.hip $(CSRC)/reach.hip $(CSRC)/objects.hip $(CSRC)/scene_flow.hip $(CSRC)/snapshot.hip $(CSRC)/columns.hip
+HIP_SRCS  = $(CSRC)/diagnostics.hip $(CSRC)/volume.hip $(CSRC)/integrate.hip $(CSRC)/integrate_weighted.hip $(CSRC)/integrate_packed.hip $(CSRC)/weights.hip $(CSRC)/raycast.hip $(CSRC)/bilateral.hip $(CSRC)/icp.hip $(CSRC)/mcubes.hip $(CSRC)/pipeline.hip $(CSRC)/colour.hip $(CSRC)/classes.hip $(CSRC)/field.hip $(CSRC)/fuse.hip $(CSRC)/align.hip $(CSRC)/integrate_rays.hip $(CSRC)/mesh.hip $(CSRC)/mesh_scan.hip $(CSRC)/mesh_components.hip $(CSRC)/mesh_simplify.hip $(CSRC)/mesh_smooth.hip $(CSRC)/mesh_render.hip $(CSRC)/esdf.hip $(CSRC)/explore.hip $(CSRC)/reach.hip $(CSRC)/objects.hip $(CSRC)/scene_flow.hip $(CSRC)/snapshot.hip $(CSRC)/columns.hip $(CSRC)/frame_diff.hip
 HIP_OBJS  = $(HIP_SRCS:.hip=.o)
 LIBDIR    = tsdf_amd/lib
 
@@ -58,7 +58,7 @@ $(LIBDIR)/libtsdf_hip.so: $(HIP_OBJS)
 oracle:
 	$(MAKE) -C oracle -s all
 
-CPPTESTS  = surface colour classes weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf explore reach objects components simplify smooth scene_flow snapshot weighted rolling columns render
+CPPTESTS  = surface colour classes weight_cap field rays fuse align align_colour integrate_rays rays_colour mesh esdf explore reach objects components simplify smooth scene_flow snapshot weighted rolling columns render frame_diff
 cpptest: $(CPPTESTS:%=build/test_%) build/kinfu_stream
 
 # C++ driver of BASELINE configs[2] (TUM directory -> tsdf_pipeline_step, no Python): tools/kinfu_stream.cpp
@@ -108,8 +108,15 @@ sanitize-render: tests/cpp/render_host.cpp $(CSRC)/raster_index.hpp
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/render_host.cpp -o build/render_host
 	build/render_host
 
+# The same for frame_diff_index.hpp (the frame differences' integer arithmetic: the tolerance and its saturation, the states, the image
+# neighbours, the clipped dilation window, the any-bit range test, W * H in 64 bits) at the ends of the ranges and against brute force.
+sanitize-frame-diff: tests/cpp/frame_diff_host.cpp $(CSRC)/frame_diff_index.hpp
+	@mkdir -p build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/frame_diff_host.cpp -o build/frame_diff_host
+	build/frame_diff_host
+
 clean:
 	rm -f $(HIP_OBJS) $(HOST_OBJS) $(LIBDIR)/*.so
 	$(MAKE) -C oracle clean
 
-.PHONY: all hip host oracle cpptest clean sanitize-scene-flow sanitize-device-buffer sanitize-rolling sanitize-columns sanitize-render
+.PHONY: all hip host oracle cpptest clean sanitize-scene-flow sanitize-device-buffer sanitize-rolling sanitize-columns sanitize-render sanitize-frame-diff

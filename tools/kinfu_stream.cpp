@@ -8,7 +8,7 @@
 // the same entry points from Python: same checksum, same ms per step (tools/compare_drivers.sh).
 //
 //   kinfu_stream -d <tum dir> [-n grid=512] [-p physical_mm=3000] [-k steps=20] [-w warmup=5] [--no-overlap]
-//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE] [--weights inverse-square[,cosine]] [--weight-ref MM]
+//                [--no-cull-ahead] [--dump <dir>] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE] [--weights inverse-square[,cosine]] [--weight-ref MM] [--reject-dynamic TOL[,QUAD,STEP,MIN,DILATE]] [-v]
 //   --weights LIST (with --track): tsdf_tracker_set_weighting -- every tracked frame is fused with the weights of the standard models in
 //           LIST (inverse-square, cosine, comma separated: tsdf_depth_weights_device on the filtered frame, tsdf_integrate_weighted_device);
 //           --weight-ref MM is the inverse-square model's z_ref in millimetres (required with it, > 0); refused without --track, with
@@ -21,6 +21,10 @@
 //   --field (with --track): every tracked frame is aligned to the volume's distance field (tsdf_tracker_align_field: the filtered frame's
 //           pixels as points, no model ray cast, no ICP) from the previous pose; refused without --track and with --ranks; the line
 //           gains "align": "field" and reports the last step's inliers and sum of squared distances in the ICP fields.
+//   --reject-dynamic TOL[,QUAD,STEP,MIN,DILATE] (with --track): tsdf_tracker_set_dynamic_rejection -- every frame is compared with the model's depth
+//           at its camera and fused without the blobs that lie in front of it (tolerance mm, quadratic, depth step mm, least pixels, dilation;
+//           defaults 50,0,50,64,4; connectivity 8).  The line gains "reject_dynamic": [..], "rejected_blobs" and "masked_share" of the last frame;
+//           -v prints the blob count and the masked share of every frame to stderr.
 //   --window N (with --track): tsdf_tracker_set_window(N) -- the volume holds the last N tracked frames, each integrate past the N-th takes
 //           the oldest back out (tsdf_deintegrate); 0 (the default) = off; refused without --track, with --weight-cap and with --ranks; the
 //           line gains "window": N.
@@ -150,6 +154,8 @@ int main(int argc, char **argv) {
     std::string weights_list;
     double weight_ref = 0.0;
     unsigned weight_flags = 0;
+    std::string reject_list;
+    bool verbose = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto value = [&]() -> const char * {
@@ -179,12 +185,14 @@ int main(int argc, char **argv) {
         else if (a == "--save-sparse") sparse_file = value();
         else if (a == "--weights") weights_list = value();
         else if (a == "--weight-ref") weight_ref = std::atof(value());
+        else if (a == "--reject-dynamic") reject_list = value();
+        else if (a == "-v") verbose = true;
         else if (a == "--colour-weight") {
             colour_weight = std::atof(value());
             colour_weight_given = true;
         }
         else {
-            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE] [--weights inverse-square[,cosine]] [--weight-ref MM]\n");
+            std::fprintf(stderr, "usage: kinfu_stream -d <tum dir> [-n grid] [-p physical_mm] [-k steps] [-w warmup] [--no-overlap] [--no-cull-ahead] [--dump dir] [--track] [--ranks P] [--share-gpu] [--planes Z] [--validate-merge] [--colour] [--weight-cap N] [--window N] [--field] [--colour-weight W] [--save-sparse FILE] [--weights inverse-square[,cosine]] [--weight-ref MM] [--reject-dynamic TOL[,QUAD,STEP,MIN,DILATE]] [-v]\n");
             return 2;
         }
     }
@@ -196,6 +204,28 @@ int main(int argc, char **argv) {
     if (weight_cap < 0 || weight_cap > 65535) {
         std::fprintf(stderr, "kinfu_stream: --weight-cap is 0 (off) or 1 .. 65535\n");
         return 2;
+    }
+    tsdf_diff_rejection rejection = {50, 0, 8, 50, 64, 4};
+    if (!reject_list.empty()) {
+        unsigned long v[5] = {50, 0, 50, 64, 4};
+        int got = 0;
+        const char *c = reject_list.c_str();
+        bool bad = !track;
+        while (!bad && *c && got < 5) {
+            char *end = nullptr;
+            v[got++] = std::strtoul(c, &end, 10);
+            bad = end == c || (*end && *end != ',') || (*end == ',' && !end[1]) || v[got - 1] > 0xfffffffful;   // (no empty field, no trailing comma)
+            c = *end ? end + 1 : end;
+        }
+        if (bad || got == 0 || *c || v[4] > 32) {
+            std::fprintf(stderr, "kinfu_stream: --reject-dynamic takes TOL[,QUAD,STEP,MIN,DILATE] (unsigned, DILATE <= 32) and needs --track\n");
+            return 2;
+        }
+        rejection.tolerance = (uint32_t)v[0];
+        rejection.quadratic = (uint32_t)v[1];
+        rejection.depth_step = (uint32_t)v[2];
+        rejection.min_pixels = (uint32_t)v[3];
+        rejection.dilate = (uint32_t)v[4];
     }
     if (window < 0 || window > 65535 || (window && (!track || weight_cap || ranks > 1))) {
         std::fprintf(stderr, "kinfu_stream: --window is 0 (off) or 1 .. 65535 frames; it needs --track and goes with neither --weight-cap nor --ranks\n");
@@ -381,6 +411,9 @@ int main(int argc, char **argv) {
         ok(tsdf_tracker_create(vol, bil, icp, W, H, 20.0f, overlap ? TSDF_PIPELINE_OVERLAP : 0, &trk), "tracker");
         if (window) ok(tsdf_tracker_set_window(trk, (uint32_t)window), "window");
         if (weight_flags) ok(tsdf_tracker_set_weighting(trk, weight_flags, (float)weight_ref), "weighting");
+        if (!reject_list.empty()) ok(tsdf_tracker_set_dynamic_rejection(trk, &rejection), "dynamic rejection");
+        uint64_t reject_counts[5] = {0, 0, 0, 0, 0}, reject_blobs = 0;
+        double masked_share = 0.0;
         const size_t n_track = std::min(F, (size_t)K);
         std::vector<float> tracked;
         float error = 0.f, inliers = 0.f, colour_inliers = 0.f;
@@ -429,6 +462,19 @@ int main(int argc, char **argv) {
             const tsdf_camera_matrices now = matrices_of(*camera);
             if (colour) ok(tsdf_tracker_integrate_colour(trk, &now, rgb_dev + i * n_pix * 3), "integrate");
             else ok(tsdf_tracker_integrate(trk, &now), "integrate");
+            if (!reject_list.empty() && (verbose || i + 1 == n_track)) {
+                // the masked share: the mask's set bytes over the pixels (a blocking download; only under -v and for the last frame)
+                const uint8_t *mask_dev = nullptr;
+                ok(tsdf_tracker_last_rejection(trk, reject_counts, &reject_blobs, &mask_dev), "last rejection");
+                std::vector<uint8_t> mask(n_pix);
+                ok(tsdf_device_download(mask.data(), mask_dev, n_pix), "mask download");
+                size_t set = 0;
+                for (uint8_t m : mask) set += m;
+                masked_share = (double)set / (double)n_pix;
+                if (verbose)
+                    std::fprintf(stderr, "frame %zu: %llu blobs rejected, %.4f of the pixels masked, %llu nearer\n", i, (unsigned long long)reject_blobs,
+                                 masked_share, (unsigned long long)reject_counts[TSDF_DIFF_NEARER]);
+            }
             tracked.insert(tracked.end(), now.pose, now.pose + 16);
         }
         ok(tsdf_tracker_synchronize(trk), "synchronize");
@@ -443,6 +489,9 @@ int main(int argc, char **argv) {
         if (weight_cap) std::printf(", \"weight_cap\": %ld", weight_cap);
         if (window) std::printf(", \"window\": %ld", window);
         if (weight_flags) std::printf(", \"weights\": \"%s\", \"weight_ref\": %g", weights_list.c_str(), weight_ref);
+        if (!reject_list.empty())
+            std::printf(", \"reject_dynamic\": [%u, %u, %u, %u, %u], \"rejected_blobs\": %llu, \"masked_share\": %.6f", rejection.tolerance, rejection.quadratic,
+                        rejection.depth_step, rejection.min_pixels, rejection.dilate, (unsigned long long)reject_blobs, masked_share);
         if (field) std::printf(", \"align\": \"field\"");
         if (colour_weight_given) std::printf(", \"colour_weight\": %g, \"last_colour_inliers\": %.0f", colour_weight, colour_inliers);
         if (!sparse_file.empty()) std::printf(", \"sparse_file_bytes\": %lld", save_sparse_file(vol, sparse_file));

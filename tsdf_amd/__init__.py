@@ -8,5 +8,6 @@ from .api import (TSDFVolume, GPURaycaster, BilateralFilter, Camera, ICPOdometry
                   depth_weights, depth_weights_device, WEIGHTS_INVERSE_SQUARE, WEIGHTS_COSINE, CLASS_VOID, Objects, OBJECT_DTYPE,
                   OBJECT_NONE, Reach, REACH_CLUSTER_DTYPE, REACH_UNREACHED, REACH_COST_FACE, REACH_COST_EDGE, REACH_COST_CORNER,
                   TSDF_REACH_THROUGH_UNKNOWN, ColumnMap, COLUMN_DTYPE, CELL_NO_GROUND, CELL_TRAVERSABLE, CELL_BLOCKED, Renderer, render_mesh,
-                  render_mesh_device, RENDER_TARGETS, RENDER_CULL_BACK, RENDER_MISS)
+                  render_mesh_device, RENDER_TARGETS, RENDER_CULL_BACK, RENDER_MISS, FrameDiff, DIFF_BLOB_DTYPE, DIFF_NO_FRAME, DIFF_NO_MODEL, DIFF_SAME,
+                  DIFF_FARTHER, DIFF_NEARER, DIFF_NO_BLOB, DIFF_DEFAULTS)
 from .rolling import BrickStore, RollingVolume  # noqa: F401

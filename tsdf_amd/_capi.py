@@ -83,6 +83,30 @@ class FrontierCluster(C.Structure):
     _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("sum", C.c_uint64 * 3)]
 
 
+class DiffParams(C.Structure):
+    """struct tsdf_diff_params (include/tsdf_amd.h)."""
+    _fields_ = [("tolerance", C.c_uint32), ("quadratic", C.c_uint32)]
+
+
+class FrameDiffInfo(C.Structure):
+    """struct tsdf_frame_diff_info (include/tsdf_amd.h): 88 bytes, counts at offset 32."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("tolerance", C.c_uint32), ("quadratic", C.c_uint32),
+                ("connectivity", C.c_uint32), ("depth_step", C.c_uint32), ("min_pixels", C.c_uint32), ("reserved", C.c_uint32),
+                ("counts", C.c_uint64 * 5), ("n_blobs", C.c_uint64), ("n_kept_blobs", C.c_uint64)]
+
+
+class DiffBlob(C.Structure):
+    """struct tsdf_diff_blob (include/tsdf_amd.h): 56 bytes, sum_x at offset 32."""
+    _fields_ = [("label", C.c_uint32), ("size", C.c_uint32), ("lo", C.c_uint32 * 2), ("hi", C.c_uint32 * 2), ("min_depth", C.c_uint32),
+                ("max_depth", C.c_uint32), ("sum_x", C.c_uint64), ("sum_y", C.c_uint64), ("sum_depth", C.c_uint64)]
+
+
+class DiffRejection(C.Structure):
+    """struct tsdf_diff_rejection (include/tsdf_amd.h)."""
+    _fields_ = [("tolerance", C.c_uint32), ("quadratic", C.c_uint32), ("connectivity", C.c_uint32), ("depth_step", C.c_uint32),
+                ("min_pixels", C.c_uint32), ("dilate", C.c_uint32)]
+
+
 class ReachInfo(C.Structure):
     """struct tsdf_reach_info (include/tsdf_amd.h): 88 bytes, n_traversable at offset 56, rounds at 80."""
     _fields_ = [("size", C.c_uint32 * 3), ("connectivity", C.c_uint32), ("voxel_size", C.c_float * 3), ("offset", C.c_float * 3),
@@ -432,6 +456,18 @@ _SIGS = {
     "tsdf_tracker_window": (_i, [_vp, C.POINTER(C.c_uint32)]),
     "tsdf_tracker_set_weighting": (_i, [_vp, _u32, _f]),
     "tsdf_tracker_weighting": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "tsdf_tracker_set_dynamic_rejection": (_i, [_vp, C.POINTER(DiffRejection)]),
+    "tsdf_tracker_dynamic_rejection": (_i, [_vp, C.POINTER(_i), C.POINTER(DiffRejection)]),
+    "tsdf_tracker_last_rejection": (_i, [_vp, C.POINTER(C.c_uint64 * 5), C.POINTER(C.c_uint64), C.POINTER(_vp)]),
+    "tsdf_frame_diff_create": (_i, [C.POINTER(_vp)]),
+    "tsdf_frame_diff_destroy": (None, [_vp]),
+    "tsdf_frame_diff_get_info": (_i, [_vp, C.POINTER(FrameDiffInfo)]),
+    "tsdf_frame_diff_scratch_bytes": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "tsdf_frame_diff_compare_device": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(DiffParams), _vp, _vp]),
+    "tsdf_frame_diff_cluster": (_i, [_vp, _u32, _u32, _u32, _vp]),
+    "tsdf_frame_diff_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "tsdf_frame_diff_download": (_i, [_vp, _vp, _vp, _vp]),
+    "tsdf_frame_diff_mask_device": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "tsdf_tracker_synchronize": (_i, [_vp]),
     "tsdf_tracker_streams": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "tsdf_tracker_buffers": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

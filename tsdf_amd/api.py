@@ -1648,6 +1648,129 @@ class Explorer(_Handle):
         return out
 
 
+#: one row of FrameDiff.blobs: struct tsdf_diff_blob (56 bytes)
+DIFF_BLOB_DTYPE = np.dtype([("label", np.uint32), ("size", np.uint32), ("lo", np.uint32, 2), ("hi", np.uint32, 2), ("min_depth", np.uint32),
+                            ("max_depth", np.uint32), ("sum_x", np.uint64), ("sum_y", np.uint64), ("sum_depth", np.uint64)])
+DIFF_NO_FRAME, DIFF_NO_MODEL, DIFF_SAME, DIFF_FARTHER, DIFF_NEARER = 0, 1, 2, 3, 4
+DIFF_NO_BLOB = 0xFFFFFFFF
+#: starting values of dynamic rejection, unvalidated on real data
+DIFF_DEFAULTS = dict(tolerance=50, quadratic=0, connectivity=8, depth_step=50, min_pixels=64, dilate=4)
+
+
+class FrameDiff(_Handle):
+    """tsdf_frame_diff (include/tsdf_amd.h, "frame differences"): a depth frame compared with the model's depth image (compare), the
+    pixels in front of the model clustered into blobs (cluster), and the dilated mask of the blobs kept (mask), on the device."""
+
+    _c, _Info = "frame_diff", _capi.FrameDiffInfo
+    #: the state image of the last compare(states=True), else None
+    states = None
+
+    @property
+    def info(self):
+        """tsdf_frame_diff_info: width, height, tolerance, quadratic, connectivity, depth_step, min_pixels, counts[5], n_blobs,
+        n_kept_blobs."""
+        return self._get_info()
+
+    def compare_device(self, frame_ptr, model_ptr, width, height, tolerance=50, quadratic=0, states_ptr=0, stream=0):
+        """tsdf_frame_diff_compare_device on device pointers (uint16 mm images; states: uint8 per pixel, or 0).  Returns self."""
+        vp = lambda p: C.c_void_p(int(p) if p else 0)
+        params = _capi.DiffParams(int(tolerance), int(quadratic))
+        check(lib.tsdf_frame_diff_compare_device(self._h, vp(frame_ptr), vp(model_ptr), int(width), int(height), C.byref(params), vp(states_ptr),
+                                                 vp(stream)))
+        return self
+
+    def compare(self, frame, model, tolerance=50, quadratic=0, states=False):
+        """Host images (H, W) uint16; with states=True the (H, W) uint8 state image is kept in self.states.  Returns self."""
+        f = np.ascontiguousarray(frame, np.uint16)
+        m = np.ascontiguousarray(model, np.uint16)
+        if f.ndim != 2 or f.shape != m.shape:
+            raise ValueError("compare: frame and model are (height, width) images of one shape, got %r and %r" % (f.shape, m.shape))
+        h, w = f.shape
+        self.states = None
+        if not states:
+            with _DeviceArray(f) as df, _DeviceArray(m) as dm:
+                return self.compare_device(df.ptr.value, dm.ptr.value, w, h, tolerance, quadratic)
+        out = np.empty((h, w), np.uint8)
+        with _DeviceArray(f) as df, _DeviceArray(m) as dm, _DeviceArray(nbytes=max(out.nbytes, 1)) as ds:
+            self.compare_device(df.ptr.value, dm.ptr.value, w, h, tolerance, quadratic, ds.ptr.value)
+            if out.nbytes:
+                check(lib.tsdf_device_download(out.ctypes.data, ds.ptr, out.nbytes))
+        self.states = out
+        return self
+
+    @property
+    def counts(self):
+        """(5,) uint64: the pixels in each state, indexed by DIFF_NO_FRAME .. DIFF_NEARER."""
+        return np.array(list(self.info.counts), np.uint64)
+
+    def cluster(self, connectivity=8, depth_step=50, min_pixels=64, stream=0):
+        """tsdf_frame_diff_cluster: connectivity 4 or 8; listed neighbours whose frame depths differ by at most depth_step are joined; the
+        table lists the blobs of at least max(min_pixels, 1) pixels.  Returns self."""
+        check(lib.tsdf_frame_diff_cluster(self._h, int(connectivity), int(depth_step), int(min_pixels), C.c_void_p(int(stream) if stream else 0)))
+        return self
+
+    def _download(self):
+        i = self.info
+        n = int(i.counts[DIFF_NEARER])
+        pixels, labels = np.empty(n + 1, np.uint32), np.empty(n + 1, np.uint32)
+        rows = np.zeros(int(i.n_kept_blobs) + 1, DIFF_BLOB_DTYPE)
+        check(lib.tsdf_frame_diff_download(self._h, pixels.ctypes.data, labels.ctypes.data, rows.ctypes.data))
+        return pixels[:n], labels[:n], rows[:-1]
+
+    @property
+    def pixels(self):
+        """(n_nearer,) uint32: the ids y * width + x of the listed pixels, ascending."""
+        return self._download()[0]
+
+    @property
+    def labels(self):
+        """(n_nearer,) uint32: per listed pixel the smallest list index of its blob."""
+        return self._download()[1]
+
+    @property
+    def blobs(self):
+        """(n_kept_blobs,) DIFF_BLOB_DTYPE rows in ascending label."""
+        return self._download()[2]
+
+    def device_buffers(self):
+        """Raw device pointers {pixels, masks, bases, labels, blobs} (0 where empty); valid until the next call that fills them."""
+        p = [C.c_void_p() for _ in range(5)]
+        check(lib.tsdf_frame_diff_buffers(self._h, *[C.byref(x) for x in p]))
+        return dict(zip(("pixels", "masks", "bases", "labels", "blobs"), (int(x.value or 0) for x in p)))
+
+    def mask_device(self, dilate=4, mask_ptr=0, blob_index_ptr=0, frame_in_ptr=0, frame_out_ptr=0, stream=0):
+        """tsdf_frame_diff_mask_device on device pointers (any may be 0; frame_in and frame_out together).  Asynchronous on `stream`."""
+        vp = lambda p: C.c_void_p(int(p) if p else 0)
+        check(lib.tsdf_frame_diff_mask_device(self._h, int(dilate), vp(mask_ptr), vp(blob_index_ptr), vp(frame_in_ptr), vp(frame_out_ptr), vp(stream)))
+        return self
+
+    def mask(self, dilate=4, frame=None, blob_index=False):
+        """The (H, W) uint8 mask of the kept blobs dilated by `dilate` pixels; with `frame` ((H, W) uint16) also the frame with the masked
+        pixels set to 0; with blob_index=True also the (H, W) uint32 instance image.  Returns the mask, or a tuple in that order."""
+        i = self.info
+        h, w = int(i.height), int(i.width)
+        m = np.empty((h, w), np.uint8)
+        b = np.empty((h, w), np.uint32) if blob_index else None
+        f = None
+        if frame is not None:
+            f = np.ascontiguousarray(frame, np.uint16)
+            if f.shape != (h, w):
+                raise ValueError("mask: the frame is (%d, %d), the comparison was of (%d, %d)" % (f.shape + (h, w)))
+            f = f.copy()
+        with _DeviceArray(nbytes=max(m.nbytes, 1)) as dm, _DeviceArray(nbytes=4 * max(m.size, 1) if blob_index else 0) as db, \
+                _DeviceArray(f if f is not None else None, nbytes=0) as df:
+            self.mask_device(dilate, dm.ptr.value, db.ptr.value, df.ptr.value, df.ptr.value)
+            self.device_buffers()   # (waits for the handle's pending work)
+            if m.nbytes:
+                check(lib.tsdf_device_download(m.ctypes.data, dm.ptr, m.nbytes))
+                if b is not None:
+                    check(lib.tsdf_device_download(b.ctypes.data, db.ptr, b.nbytes))
+                if f is not None:
+                    check(lib.tsdf_device_download(f.ctypes.data, df.ptr, f.nbytes))
+        out = (m,) + ((f,) if f is not None else ()) + ((b,) if b is not None else ())
+        return out[0] if len(out) == 1 else out
+
+
 #: one row of Reach.rank: struct tsdf_reach_cluster (16 bytes)
 REACH_CLUSTER_DTYPE = np.dtype([("label", np.uint32), ("cost", np.uint32), ("voxel", np.uint32), ("reserved", np.uint32)])
 #: the cost of a voxel that no admissible path reaches, or none within max_cost

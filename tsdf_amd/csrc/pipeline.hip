@@ -154,6 +154,13 @@ struct tsdf_tracker {
     uint32_t weighting_flags;
     float weighting_z_ref;
     float *pixel_weights;       // width * height, made by the first weighted integrate
+    // tsdf_tracker_set_dynamic_rejection: rejection_on = 0: nothing of this is allocated or used
+    int rejection_on, rejection_have_last;
+    tsdf_diff_rejection rejection;
+    tsdf_frame_diff *diff;
+    uint16_t *reject_model, *masked;   // the model's depth at the frame's camera; the frame as it is fused
+    uint8_t *reject_mask;
+    uint64_t reject_counts[5], reject_blobs;
 };
 
 using namespace tsdf;
@@ -675,7 +682,8 @@ int tsdf_tracker_destroy(tsdf_tracker *t) {
         if (t->integrated[b]) (void)hipEventDestroy(t->integrated[b]);
     }
     if (t->ready) (void)hipEventDestroy(t->ready);
-    device_free_all(t->model, t->ring, t->pixel_weights);
+    device_free_all(t->model, t->ring, t->pixel_weights, t->reject_model, t->masked, t->reject_mask);
+    tsdf_frame_diff_destroy(t->diff);
     delete[] t->ring_cam;
     if (t->aligner) tsdf_aligner_destroy(t->aligner);
     device_free_all(t->align_points[0], t->align_points[1], t->align_points[2]);
@@ -852,23 +860,49 @@ int tsdf_tracker_align_field_colour(tsdf_tracker *t, const float kinv[9], const 
     return tsdf_aligner_run_colour(t->aligner, t->volume, 3, stages, t->volume->g.trunc, colour_gate, colour_weight, T_world_cam, residual, inliers);
 }
 
+// Dynamic rejection in front of a frame's integrate, on the main stream: the model's depth at the frame's camera, the compare, the
+// clustering (a host synchronisation each) and the mask, into t->reject_mask and t->masked.
+static int tracker_reject(tsdf_tracker *t, const tsdf_camera_matrices *camera, const uint16_t *frame) {
+    const tsdf_diff_rejection &r = t->rejection;
+    int rc = tsdf_raycast_depth_device(t->volume, t->width, t->height, camera->pose, camera->inv_pose, camera->kinv, t->reject_model, nullptr);
+    if (rc != TSDF_OK) return rc;
+    const tsdf_diff_params params = {r.tolerance, r.quadratic};
+    rc = tsdf_frame_diff_compare_device(t->diff, frame, t->reject_model, t->width, t->height, &params, nullptr, t->main);
+    if (rc == TSDF_OK) rc = tsdf_frame_diff_cluster(t->diff, r.connectivity, r.depth_step, r.min_pixels, t->main);
+    if (rc == TSDF_OK) rc = tsdf_frame_diff_mask_device(t->diff, r.dilate, t->reject_mask, nullptr, frame, t->masked, t->main);
+    if (rc != TSDF_OK) return rc;
+    tsdf_frame_diff_info info;
+    rc = tsdf_frame_diff_get_info(t->diff, &info);
+    if (rc != TSDF_OK) return rc;
+    for (int k = 0; k < 5; k++) t->reject_counts[k] = info.counts[k];
+    t->reject_blobs = info.n_kept_blobs;
+    t->rejection_have_last = 1;
+    return TSDF_OK;
+}
+
 // tsdf_tracker_integrate (rgb == nullptr) and tsdf_tracker_integrate_colour
 static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera, const uint8_t *rgb) {
     TSDF_REQUIRE(t->have_frame, "tsdf_tracker_integrate: no frame filtered");
     int rc = tracker_join(t);
     if (rc != TSDF_OK) return rc;
     const int b = t->cur;
+    const uint16_t *frame = t->filtered[b];   // what is fused, kept in the ring and weighted
+    if (t->rejection_on) {
+        rc = tracker_reject(t, camera, frame);
+        if (rc != TSDF_OK) return rc;
+        frame = t->masked;   // (the filter's tile maxima stay upper bounds of a frame with pixels zeroed)
+    }
     if (t->weighting_on) {
         // the model's weights of the filtered frame, then the weighted integrate, both on the step's stream
         if (!t->pixel_weights) TSDF_HIP(hipMalloc((void **)&t->pixel_weights, (size_t)t->width * t->height * sizeof(float)), "tracker: pixel weights");
-        rc = tsdf_depth_weights_device(t->width, t->height, t->filtered[b], camera->kinv, t->weighting_flags, t->weighting_z_ref, t->pixel_weights, t->main);
+        rc = tsdf_depth_weights_device(t->width, t->height, frame, camera->kinv, t->weighting_flags, t->weighting_z_ref, t->pixel_weights, t->main);
         if (rc == TSDF_OK)
-            rc = tsdf_integrate_weighted_device(t->volume, t->filtered[b], t->pixel_weights, rgb, t->width, t->height, camera->pose, camera->inv_pose,
+            rc = tsdf_integrate_weighted_device(t->volume, frame, t->pixel_weights, rgb, t->width, t->height, camera->pose, camera->inv_pose,
                                                 camera->k, camera->kinv);
     } else if (rgb)
-        rc = integrate_colour_tiles(t->volume, t->filtered[b], rgb, t->width, t->height, camera, t->tile_max[b]);
+        rc = integrate_colour_tiles(t->volume, frame, rgb, t->width, t->height, camera, t->tile_max[b]);
     else
-        rc = tsdf_integrate_device_tiles(t->volume, t->filtered[b], t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
+        rc = tsdf_integrate_device_tiles(t->volume, frame, t->width, t->height, camera->pose, camera->inv_pose, camera->k, camera->kinv,
                                          t->tile_max[b]);
     if (rc != TSDF_OK) return rc;
     if (t->window) {
@@ -883,7 +917,7 @@ static int tracker_integrate(tsdf_tracker *t, const tsdf_camera_matrices *camera
             t->ring_head = (t->ring_head + 1u) % t->window;
         } else
             t->ring_count++;
-        TSDF_HIP(hipMemcpyAsync(t->ring + n * slot, t->filtered[b], n * sizeof(uint16_t), hipMemcpyDeviceToDevice, t->main), "tracker: keep the frame");
+        TSDF_HIP(hipMemcpyAsync(t->ring + n * slot, frame, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, t->main), "tracker: keep the frame");
         t->ring_cam[slot] = *camera;
     }
     if (t->side) TSDF_HIP(hipEventRecord(t->integrated[b], t->main), "tracker: integrate done");
@@ -934,6 +968,63 @@ int tsdf_tracker_set_weighting(tsdf_tracker *t, uint32_t flags, float z_ref) {
     t->weighting_on = 1;
     t->weighting_flags = flags;
     t->weighting_z_ref = z_ref;
+    return TSDF_OK;
+}
+
+int tsdf_tracker_set_dynamic_rejection(tsdf_tracker *t, const tsdf_diff_rejection *params) {
+    const char *who = "tsdf_tracker_set_dynamic_rejection";
+    if (params) {
+        TSDF_REQUIRE(params->connectivity == 4u || params->connectivity == 8u, "%s: connectivity must be 4 or 8, got %u", who, params->connectivity);
+        TSDF_REQUIRE(params->dilate <= 32u, "%s: dilate %u is above 32", who, params->dilate);
+    }
+    TSDF_REQUIRE(t, "%s: null tracker", who);
+    TSDF_REQUIRE(!t->have_frame, "%s: a frame has been filtered and not yet integrated (call it between frames)", who);
+    t->rejection_have_last = 0;
+    if (!params) {
+        if (!t->rejection_on) return TSDF_OK;
+        TSDF_HIP(hipStreamSynchronize(t->main), who);   // (the last frame's mask may still be in flight)
+        t->rejection_on = 0;
+        tsdf_frame_diff_destroy(t->diff);
+        t->diff = nullptr;
+        device_free_all(t->reject_model, t->masked, t->reject_mask);
+        return TSDF_OK;
+    }
+    if (!t->rejection_on) {
+        const size_t n = (size_t)t->width * t->height;
+        int rc = tsdf_frame_diff_create(&t->diff);
+        if (rc != TSDF_OK) return rc;
+        hipError_t e = hipMalloc((void **)&t->reject_model, n * sizeof(uint16_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&t->masked, n * sizeof(uint16_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&t->reject_mask, n);
+        if (e != hipSuccess) {
+            tsdf_frame_diff_destroy(t->diff);
+            t->diff = nullptr;
+            device_free_all(t->reject_model, t->masked, t->reject_mask);
+            return hip_fail(e, "tsdf_tracker_set_dynamic_rejection: buffers");
+        }
+    }
+    t->rejection = *params;
+    t->rejection_on = 1;
+    return TSDF_OK;
+}
+
+int tsdf_tracker_dynamic_rejection(const tsdf_tracker *t, int *on, tsdf_diff_rejection *params) {
+    TSDF_REQUIRE(t && on, "tsdf_tracker_dynamic_rejection: null argument");
+    *on = t->rejection_on;
+    if (params) *params = t->rejection_on ? t->rejection : tsdf_diff_rejection{};
+    return TSDF_OK;
+}
+
+int tsdf_tracker_last_rejection(const tsdf_tracker *t, uint64_t counts[5], uint64_t *n_blobs, const uint8_t **device_mask) {
+    const char *who = "tsdf_tracker_last_rejection";
+    TSDF_REQUIRE(t, "%s: null tracker", who);
+    TSDF_REQUIRE(t->rejection_on, "%s: dynamic rejection is off (tsdf_tracker_set_dynamic_rejection)", who);
+    TSDF_REQUIRE(t->rejection_have_last, "%s: no frame has been integrated since rejection was set", who);
+    TSDF_HIP(hipStreamSynchronize(t->main), who);
+    if (counts)
+        for (int k = 0; k < 5; k++) counts[k] = t->reject_counts[k];
+    if (n_blobs) *n_blobs = t->reject_blobs;
+    if (device_mask) *device_mask = t->reject_mask;
     return TSDF_OK;
 }
 

@@ -337,9 +337,11 @@ int voxel_set_list(Set *s, const char *who, const char *noun, const VoxelGrid &g
 // The list's n_list > 0 voxels, of the grid of s->g, into connected sets: labels, the roots counted behind whatever s->words holds at
 // kWordRoots, one synchronisation (the table is sized from the count), and the rows of at least min_size voxels.  Leaves the handle
 // with the rows in flight where there are any; joining is the caller's.
-template <class Policy, class Set>
-int voxel_set_cluster(Set *s, const Policy policy, uint32_t n_list, uint32_t connectivity, uint32_t min_size, hipStream_t stream, uint64_t *n_roots,
-                      uint64_t *n_rows) {
+// init(lanes, n_list, labels, acc) and stats(lanes, n_list, list, labels, grid, acc) launch the two kernels that know the row's fields:
+// voxel_set_cluster below gives voxel_init_kernel and voxel_stats_kernel; a user whose row has other fields (frame_diff.hip) gives its own.
+template <class Policy, class Set, class Init, class Stats>
+int voxel_set_cluster_with(Set *s, const Policy policy, uint32_t n_list, uint32_t connectivity, uint32_t min_size, hipStream_t stream, uint64_t *n_roots,
+                           uint64_t *n_rows, Init init, Stats stats) {
     using Row = typename Set::Row;
     static_assert(std::is_same<Row, typename Policy::Row>::value, "the policy's rows are the handle's");
     const VoxelSetText &t = *s->text;
@@ -351,10 +353,10 @@ int voxel_set_cluster(Set *s, const Policy policy, uint32_t n_list, uint32_t con
     if (e != hipSuccess) return hip_fail(e, t.cluster_alloc);
     const VoxelGrid grid = voxel_grid(s->g);
     const dim3 lanes = grid_for(n_list, 256), chunk_grid((n_chunks + 3) / 4);
-    hipLaunchKernelGGL(voxel_init_kernel<Policy>, lanes, dim3(256), 0, stream, n_list, s->labels, s->acc);
+    init(lanes, n_list, s->labels, s->acc);
     hipLaunchKernelGGL(voxel_hook_kernel<Policy>, lanes, dim3(256), 0, stream, n_list, s->list, s->masks, s->bases, policy, grid, connectivity, s->labels);
     hipLaunchKernelGGL(voxel_flatten_kernel, lanes, dim3(256), 0, stream, n_list, s->labels, s->words + Set::kWordRoots);
-    hipLaunchKernelGGL(voxel_stats_kernel<Policy>, lanes, dim3(256), 0, stream, n_list, s->list, s->labels, policy, grid, s->acc);
+    stats(lanes, n_list, s->list, s->labels, grid, s->acc);
     hipLaunchKernelGGL(voxel_keep_kernel<Row>, chunk_grid, dim3(256), 0, stream, n_list, s->labels, s->acc, min_size, n_chunks, s->row_masks, s->row_bases);
     mesh_scan(ArrayCounts{s->row_bases, n_chunks, nullptr, 0}, n_parts, s->parts, stream);
     TSDF_HIP(hipGetLastError(), t.cluster_kernels);
@@ -372,6 +374,18 @@ int voxel_set_cluster(Set *s, const Policy policy, uint32_t n_list, uint32_t con
         return s->leave(stream);
     }
     return TSDF_OK;
+}
+
+template <class Policy, class Set>
+int voxel_set_cluster(Set *s, const Policy policy, uint32_t n_list, uint32_t connectivity, uint32_t min_size, hipStream_t stream, uint64_t *n_roots,
+                      uint64_t *n_rows) {
+    using Row = typename Set::Row;
+    return voxel_set_cluster_with(
+        s, policy, n_list, connectivity, min_size, stream, n_roots, n_rows,
+        [&](dim3 lanes, uint32_t n, uint32_t *labels, Row *acc) { hipLaunchKernelGGL(voxel_init_kernel<Policy>, lanes, dim3(256), 0, stream, n, labels, acc); },
+        [&](dim3 lanes, uint32_t n, const uint32_t *list, const uint32_t *labels, const VoxelGrid &grid, Row *acc) {
+            hipLaunchKernelGGL(voxel_stats_kernel<Policy>, lanes, dim3(256), 0, stream, n, list, labels, policy, grid, acc);
+        });
 }
 
 }  // namespace tsdf

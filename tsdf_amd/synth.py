@@ -172,6 +172,20 @@ def depth_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, noise=True,
     return depth, cam
 
 
+def moving_disc_frame(i, n, seed, width=WIDTH, height=HEIGHT, camera=None, noise=True, inside=False, disc_depth=900, radius=None):
+    """depth_frame with something that moves: a disc of constant depth `disc_depth` (mm, nearer than the scene) pasted over the frame,
+    its centre moving with i from the left third to the right third of the image on the middle row; radius: pixels (default
+    height / 6).  -> (depth uint16 (H*W,), camera, disc (H*W,) bool: the pasted pixels)."""
+    depth, cam = depth_frame(i, n, seed, width, height, camera, noise, inside)
+    r = max(int(radius if radius is not None else height // 6), 1)
+    cx = width // 3 + ((width // 3) * int(i)) // max(int(n) - 1, 1)
+    cy = height // 2
+    y, x = np.mgrid[0:height, 0:width]
+    disc = ((x - cx) ** 2 + (y - cy) ** 2 <= r * r).reshape(-1)
+    depth = np.where(disc, np.uint16(disc_depth), depth).astype(np.uint16)
+    return depth, cam, disc
+
+
 def wall_depth(mm=2500, width=WIDTH, height=HEIGHT):
     """The survey probe's frame: a wall at constant depth everywhere."""
     return np.full(width * height, mm, np.uint16)

@@ -27,7 +27,7 @@ from .pipeline import OVERLAP, _matrices
 
 class FrameToModelTracker:
     def __init__(self, volume, width=640, height=480, camera=None, sigma_colour=30.0, sigma_space=4.5, depth_cutoff=20.0, overlap=True, window=0,
-                 method="icp", colour_weight=0.0, colour_gate=None, weighting=None):
+                 method="icp", colour_weight=0.0, colour_gate=None, weighting=None, reject_dynamic=None):
         import torch
         if method not in ("icp", "field"):
             raise ValueError("method is 'icp' or 'field', got %r" % (method,))
@@ -63,6 +63,8 @@ class FrameToModelTracker:
             self.set_window(window)
         if weighting is not None:
             self.set_weighting(*weighting)
+        if reject_dynamic is not None:
+            self.set_dynamic_rejection(**dict(reject_dynamic))
         self.frames = 0
         self.last_error, self.last_inliers = 0.0, 0.0
         self.last_T = None          # the last incremental transformation (4x4, metres) as ICPOdometry returned it
@@ -97,6 +99,40 @@ class FrameToModelTracker:
         f, z = C.c_uint32(), C.c_float()
         check(lib.tsdf_tracker_weighting(self._h, C.byref(f), C.byref(z)))
         return int(f.value), float(z.value)
+
+    def set_dynamic_rejection(self, on=True, **params):
+        """Keep what moves out of the fusion (include/tsdf_amd.h, "the tracked loop", tsdf_tracker_set_dynamic_rejection): every integrate
+        renders the model's depth at its camera, compares the filtered frame with it, clusters the pixels in front of the model and
+        fuses the frame with the kept blobs' dilated mask set to 0.  params: tolerance, quadratic, connectivity, depth_step, min_pixels,
+        dilate (defaults: api.DIFF_DEFAULTS, starting values).  on=False (or set_dynamic_rejection(None)): off, the default."""
+        if not on:
+            if params:
+                raise ValueError("set_dynamic_rejection: parameters given while turning it off")
+            check(lib.tsdf_tracker_set_dynamic_rejection(self._h, None))
+            return
+        unknown = set(params) - set(api.DIFF_DEFAULTS)
+        if unknown:
+            raise ValueError("set_dynamic_rejection: unknown parameters %s" % sorted(unknown))
+        p = dict(api.DIFF_DEFAULTS, **params)
+        r = api._capi.DiffRejection(int(p["tolerance"]), int(p["quadratic"]), int(p["connectivity"]), int(p["depth_step"]), int(p["min_pixels"]),
+                                    int(p["dilate"]))
+        check(lib.tsdf_tracker_set_dynamic_rejection(self._h, C.byref(r)))
+
+    def dynamic_rejection(self):
+        """The parameters of set_dynamic_rejection as a dict, or None when off."""
+        on, r = C.c_int(), api._capi.DiffRejection()
+        check(lib.tsdf_tracker_dynamic_rejection(self._h, C.byref(on), C.byref(r)))
+        return {k: int(getattr(r, k)) for k in api.DIFF_DEFAULTS} if on.value else None
+
+    def last_rejection(self, mask=True):
+        """(counts (5,) uint64 by state, kept blobs, mask (height, width) uint8 or None) of the last integrated frame."""
+        counts, blobs, ptr = (C.c_uint64 * 5)(), C.c_uint64(), C.c_void_p()
+        check(lib.tsdf_tracker_last_rejection(self._h, C.byref(counts), C.byref(blobs), C.byref(ptr)))
+        m = None
+        if mask:
+            m = np.empty((self.height, self.width), np.uint8)
+            check(lib.tsdf_device_download(m.ctypes.data, ptr, m.nbytes))
+        return np.array(list(counts), np.uint64), int(blobs.value), m
 
     def pose(self):
         """Current camera pose, 4x4 float64 (camera -> world, millimetres)."""
