@@ -81,39 +81,36 @@ sanitize-scene-flow: tests/cpp/scene_flow_refusals.cpp $(CSRC)/scene_flow.hip $(
 
 # The same for device_buffer.hpp (the grow-only array, release, free-all and the frame of a host variant): where there is no device every
 # allocation fails, the one branch the GPU suite never takes; and for handle_order.hpp (a handle's event: create without a device, destroy
-# of what was never created, join and wait with nothing pending).  Headers only: nothing of the library is linked.
-sanitize-device-buffer: tests/cpp/device_buffer_host.cpp $(CSRC)/device_buffer.hpp $(CSRC)/handle_order.hpp include/tsdf_amd.h
+# of what was never created, join and wait with nothing pending) and handle_counters.hpp (a handle's counter block: create without a
+# device, release of what was never or half created).  Headers only: nothing of the library is linked.
+sanitize-device-buffer: tests/cpp/device_buffer_host.cpp $(CSRC)/device_buffer.hpp $(CSRC)/handle_order.hpp $(CSRC)/handle_counters.hpp include/tsdf_amd.h
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -Iinclude -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/device_buffer_host.cpp -o build/device_buffer_host
 	build/device_buffer_host
 
-# The same for brick_shift.hpp (the rolling volume's brick arithmetic: shifts at the ends of the int32 range, formed in 64 bits).  The
-# argument checks of tsdf_snapshot_select / tsdf_volume_shift live in snapshot.hip, which does not link without the rest of the library.
-sanitize-rolling: tests/cpp/rolling_host.cpp $(CSRC)/brick_shift.hpp
+# The same for the headers of pure integer arithmetic, each with its stand-alone program tests/cpp/NAME_host.cpp:
+#   sanitize-rolling     brick_shift.hpp: the rolling volume's brick arithmetic, shifts at the ends of the int32 range, formed in 64 bits.
+#                        (The argument checks of tsdf_snapshot_select / tsdf_volume_shift live in snapshot.hip, which does not link
+#                        without the rest of the library.)
+#   sanitize-columns     columns_index.hpp: the column maps' cell and band arithmetic (map axes, strides, the reversed index, U * V * L in
+#                        64 bits) against brute force on small grids and at the longest axis a map takes.
+#   sanitize-render      raster_index.hpp: the mesh renderer's integer arithmetic (the snap, the twice-area, the edge functions, the
+#                        top-left rule and the box clamp) at the ends of the coordinate range, on boxes wholly outside the image and
+#                        against brute force over small images.
+#   sanitize-frame-diff  frame_diff_index.hpp: the frame differences' integer arithmetic (the tolerance and its saturation, the states, the
+#                        image neighbours, the clipped dilation window, the any-bit range test, W * H in 64 bits) at the ends of the
+#                        ranges and against brute force.
+# $(1): the target's suffix, $(2): the program's stem, $(3): the header
+define SANITIZE_HEADER
+sanitize-$(1): tests/cpp/$(2)_host.cpp $$(CSRC)/$(3)
 	@mkdir -p build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/rolling_host.cpp -o build/rolling_host
-	build/rolling_host
-
-# The same for columns_index.hpp (the column maps' cell and band arithmetic: map axes, strides, the reversed index, U * V * L in 64 bits)
-# against brute force on small grids and at the longest axis a map takes.
-sanitize-columns: tests/cpp/columns_host.cpp $(CSRC)/columns_index.hpp
-	@mkdir -p build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/columns_host.cpp -o build/columns_host
-	build/columns_host
-
-# The same for raster_index.hpp (the mesh renderer's integer arithmetic: the snap, the twice-area, the edge functions, the top-left rule
-# and the box clamp) at the ends of the coordinate range, on boxes wholly outside the image and against brute force over small images.
-sanitize-render: tests/cpp/render_host.cpp $(CSRC)/raster_index.hpp
-	@mkdir -p build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/render_host.cpp -o build/render_host
-	build/render_host
-
-# The same for frame_diff_index.hpp (the frame differences' integer arithmetic: the tolerance and its saturation, the states, the image
-# neighbours, the clipped dilation window, the any-bit range test, W * H in 64 bits) at the ends of the ranges and against brute force.
-sanitize-frame-diff: tests/cpp/frame_diff_host.cpp $(CSRC)/frame_diff_index.hpp
-	@mkdir -p build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/frame_diff_host.cpp -o build/frame_diff_host
-	build/frame_diff_host
+	$$(HIPCC) --offload-arch=$$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -I$$(CSRC) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip tests/cpp/$(2)_host.cpp -o build/$(2)_host
+	build/$(2)_host
+endef
+$(eval $(call SANITIZE_HEADER,rolling,rolling,brick_shift.hpp))
+$(eval $(call SANITIZE_HEADER,columns,columns,columns_index.hpp))
+$(eval $(call SANITIZE_HEADER,render,render,raster_index.hpp))
+$(eval $(call SANITIZE_HEADER,frame-diff,frame_diff,frame_diff_index.hpp))
 
 clean:
 	rm -f $(HIP_OBJS) $(HOST_OBJS) $(LIBDIR)/*.so

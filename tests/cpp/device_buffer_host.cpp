@@ -1,13 +1,15 @@
-// Stand-alone host program for a sanitizer build (make sanitize-device-buffer): the branches of tsdf_amd/csrc/device_buffer.hpp and
-// handle_order.hpp that a machine WITH a device never takes.  Run where there is no device, every hipMalloc fails; the program checks
-// what a failed growth leaves behind, that releasing an empty handle does nothing, the order in which the frame of a host variant
-// reports errors, and what a handle's stream order does without an event.  With a device the allocations succeed and the same
-// invariants are checked on that side.  Nothing is launched.
+// Stand-alone host program for a sanitizer build (make sanitize-device-buffer): the branches of tsdf_amd/csrc/device_buffer.hpp,
+// handle_order.hpp and handle_counters.hpp (the counter block) that a machine WITH a device never takes.  Run where there is no device,
+// every hipMalloc fails; the program checks what a failed growth leaves behind, that releasing an empty handle does nothing, the order in
+// which the frame of a host variant reports errors, what a handle's stream order does without an event, and what a counter block's
+// failed create and its releases leave.  With a device the allocations succeed and the same invariants are checked on that side.
+// Nothing is launched.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "device_buffer.hpp"
+#include "handle_counters.hpp"
 #include "handle_order.hpp"
 
 static char g_message[512];
@@ -169,6 +171,55 @@ int main() {
             EXPECT(!o.done && !o.pending, "destroy");
         }
         std::printf("hipGetDevice / event here: %s\n", hipGetErrorString(e));
+    }
+
+    // the counter block of a handle (handle_counters.hpp), over a word array and over a struct of named words
+    struct Named {
+        unsigned long long a, b;
+        unsigned rounds[4];
+    };
+    auto empty = [](const auto &b) { return !b.dev && !b.host; };
+    {   // release of a block that was never created, and a second release: nothing happens
+        CounterBlock<unsigned long long, 8> w;
+        std::memset(&w, 0, sizeof(w));
+        w.release();
+        w.release();
+        EXPECT(empty(w), "release of a zeroed counter block changes it");
+        static_assert(CounterBlock<unsigned long long, 8>::device_bytes() == 64 && CounterBlock<Named>::device_bytes() == sizeof(Named), "the bytes a block holds");
+    }
+    {   // a half-created block: the mirror alone (hipHostFree of a null pointer and hipFree of a null pointer are both fine)
+        CounterBlock<Named> w;
+        std::memset(&w, 0, sizeof(w));
+        if (hipHostMalloc((void **)&w.host, sizeof(Named), hipHostMallocDefault) != hipSuccess) w.host = nullptr;
+        (void)hipGetLastError();
+        w.release();
+        EXPECT(empty(w), "release of a half-created counter block");
+        w.release();
+        EXPECT(empty(w), "a second release of a counter block");
+    }
+    {   // create: without a device it fails and leaves an empty block; with one, a zeroed mirror and the ranges
+        CounterBlock<Named> w;
+        std::memset(&w, 0xff, sizeof(w));   // (create does not read what the block held)
+        const hipError_t e = w.create();
+        (void)hipGetLastError();
+        if (e != hipSuccess) {
+            EXPECT(empty(w), "a failed create does not leave the counter block empty");
+        } else {
+            Named zero_words;
+            std::memset(&zero_words, 0, sizeof(zero_words));
+            EXPECT(w.dev && w.host && std::memcmp(w.host, &zero_words, sizeof(Named)) == 0, "a successful create: both sides, the mirror zeroed");
+            w.host->b = 7;
+            w.host->rounds[3] = 9;
+            EXPECT(w.reset(nullptr) == hipSuccess && w.download(w.dev->rounds, 4, nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+                       w.host->b == 7 && w.host->rounds[3] == 0,
+                   "a range lands at its own place in the mirror and nowhere else");
+            EXPECT(w.download(nullptr) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess && w.host->b == 0, "the whole block lands");
+        }
+        w.release();
+        EXPECT(empty(w), "release after create");
+        w.release();
+        EXPECT(empty(w), "a second release after create");
+        std::printf("counter block create here: %s\n", hipGetErrorString(e));
     }
 
     std::printf(failures ? "device buffer host checks: %d FAILED\n" : "device buffer host checks ok\n", failures);

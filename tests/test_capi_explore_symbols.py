@@ -5,6 +5,8 @@ import ctypes as C
 import os
 import re
 
+from tests.capi_header import declarations
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAIN_ARGS = ["const tsdf_volume *", "tsdf_explorer *", "uint64_t", "const float *", "const float *", "const float *", "uint32_t", "uint32_t *",
              "uint32_t *", "uint8_t *", "uint64_t *"]
@@ -24,25 +26,8 @@ EXPECTED = {
 }
 
 
-def declarations():
-    """name -> (return type, argument types with the parameter names taken out) of every declaration in EXPECTED."""
-    text = open(os.path.join(ROOT, "include", "tsdf_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|void)\s+(tsdf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        if name not in EXPECTED:
-            continue
-        types = []
-        for a in args.split(","):
-            a = " ".join(a.split())
-            m = re.match(r"^(.*?)([A-Za-z_][A-Za-z0-9_]*)(\[\d+\])?$", a)
-            types.append((m.group(1).strip() + (" " + m.group(3) if m.group(3) else "")).strip())
-        out[name] = (ret, types)
-    return text, out
-
-
 def test_the_header_declares_the_signatures():
-    text, decl = declarations()
+    text, decl = declarations(EXPECTED)
     for name, sig in EXPECTED.items():
         assert name in decl, name
         assert decl[name] == sig, (name, decl[name])

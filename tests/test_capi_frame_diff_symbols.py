@@ -6,6 +6,8 @@ import ctypes as C
 import os
 import re
 
+from tests.capi_header import declarations
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPECTED = {
     "tsdf_frame_diff_create": ("int", ["tsdf_frame_diff **"]),
@@ -25,30 +27,13 @@ EXPECTED = {
 }
 
 
-def declarations():
-    """name -> (return type, argument types with the parameter names taken out) of every declaration in EXPECTED."""
-    text = open(os.path.join(ROOT, "include", "tsdf_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int|void)\s+(tsdf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        if name not in EXPECTED:
-            continue
-        types = []
-        for a in args.split(","):
-            a = " ".join(a.split())
-            m = re.match(r"^(.*?)([A-Za-z_][A-Za-z0-9_]*)(\[\d+\])?$", a)
-            types.append((m.group(1).strip() + (" " + m.group(3) if m.group(3) else "")).strip())
-        out[name] = (ret, types)
-    return text, out
-
-
 def struct_body(text, name):
     m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), text, flags=re.S)
     return " ".join(m.group(1).split()) if m else None
 
 
 def test_the_header_declares_the_signatures():
-    text, decl = declarations()
+    text, decl = declarations(EXPECTED)
     for name, sig in EXPECTED.items():
         assert name in decl, name
         assert decl[name] == sig, (name, decl[name])

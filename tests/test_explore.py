@@ -91,6 +91,23 @@ def test_random_state_fields_equal_the_reference(size):
     ex.close()
 
 
+def test_sixty_four_roots_in_a_wave_and_a_one_lane_wave():
+    """130 x 1 x 1, free at even x and unknown at odd x: 65 frontiers, none adjacent to another, so the first wave of the stats kernel
+    reduces 64 distinct roots and the second has one lane."""
+    size = (130, 1, 1)
+    D = np.full(130, 0.5, F32)
+    Wt = (np.arange(130) % 2 == 0).astype(F32)
+    gv = volume_of(size, D, Wt)
+    ex = gv.find_frontiers()
+    ids = assert_frontiers(ex, D, Wt, size, "every other voxel")
+    assert ids.tolist() == list(range(0, 130, 2))
+    for connectivity in (6, 26):
+        rows = assert_clusters(ex, ids, size, connectivity, 1, "every other voxel at %d" % connectivity)
+        assert len(rows) == 65 and (rows["size"] == 1).all() and rows["sum"][:, 0].tolist() == list(range(0, 130, 2))
+    gv.close()
+    ex.close()
+
+
 def test_a_snake_and_a_half_observed_cube_give_deep_chains():
     # one row of 200 free voxels under a row of unknown ones: a single cluster, 200 long, whatever the order the hooks land in
     size = (200, 2, 1)

@@ -216,6 +216,29 @@ def test_three_hundred_blobs_and_two_runs():
         assert again[k].tobytes() == got[k].tobytes(), k
 
 
+def test_sixty_four_roots_in_a_wave_and_one_row_for_three_waves():
+    """129 x 2, NEARER at even x on row 0 and odd x on row 1: 129 listed pixels in waves of 64, 64 and 1.  At connectivity 4 every pixel is
+    its own blob (a wave reduces 64 distinct roots); at 8 the three waves all add to one row.  One compare, then both clusterings in
+    either order on the same handle: the root counter is reset before the second."""
+    import tsdf_amd
+    from tsdf_amd import api
+    w, h = 129, 2
+    frame, model = planted(w, h, [(x, 0, 700 + x) for x in range(0, w, 2)] + [(x, 1, 900 + x) for x in range(1, w, 2)])
+    p = dict(DEFAULT, depth_step=65535, min_pixels=1)
+    want = {c: R.run(frame, model, **dict(p, connectivity=c)) for c in (4, 8)}
+    assert len(want[4]["pixels"]) == 129 and len(want[4]["blobs"]) == 129 and len(want[8]["blobs"]) == 1
+    for order in ((4, 8), (8, 4)):
+        fd = tsdf_amd.FrameDiff()
+        with api._DeviceArray(frame) as df, api._DeviceArray(model) as dm:
+            fd.compare_device(df.ptr.value, dm.ptr.value, w, h, p["tolerance_mm"], p["quadratic"], 0)
+            for c in order:
+                fd.cluster(c, p["depth_step"], p["min_pixels"])
+                got = dict(counts=fd.counts, pixels=fd.pixels, labels=fd.labels, blobs=fd.blobs, info=fd.info)
+                assert_same(got, want[c], (order, c))
+                assert int(got["info"].connectivity) == c and got["blobs"]["size"].sum() == 129
+        fd.close()
+
+
 def scratch_formula(calls):
     """The handle's scratch after `calls` [(pixels, listed)]: every array at the largest size it was asked for."""
     chunks = lambda n: (n + 63) // 64

@@ -115,6 +115,22 @@ def test_a_two_class_checkerboard():
     ob.close()
 
 
+def test_sixty_four_roots_in_a_wave_and_a_one_lane_wave():
+    """130 x 1 x 1 with a labelled voxel at every other x: 65 listed voxels, none adjacent to another, so the first wave of the stats
+    kernel reduces 64 distinct roots and the second has one lane."""
+    size = (130, 1, 1)
+    x = np.arange(130)
+    words = R.words_of(x % 7, np.where(x % 2 == 0, 1 + x % 5, 0))
+    gv = volume_of(size, words)
+    ob = tsdf_amd.Objects()
+    for connectivity in (6, 26):
+        ids, L, rows = assert_objects(gv, ob, words, size, 1, None, connectivity, (1,), "every other voxel at %d" % connectivity)
+        assert np.array_equal(ids, x[::2]) and np.array_equal(L, np.arange(65)) and len(rows) == 65 and (rows["size"] == 1).all()
+        assert rows["votes"].tolist() == (1 + x[::2] % 5).tolist() and rows["class_id"].tolist() == (x[::2] % 7).tolist()
+    gv.close()
+    ob.close()
+
+
 def test_snakes_a_serpentine_and_a_half_filled_cube_give_deep_chains():
     ob = tsdf_amd.Objects()
     # two 200-voxel snakes of different classes next to each other: rows y = 0 and y = 1 of a 200 x 2 grid; then two wound ones

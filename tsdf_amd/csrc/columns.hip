@@ -9,12 +9,12 @@
 // Every result is an integer, a minimum or one fixed fp32 expression evaluated by one lane: two runs give the same bytes whatever order the
 // waves run in.  No float atomics, no lane waits for another, and every loop has a stated bound.
 #include <cstring>
-#include <new>
 
 #include "common.hpp"
 #include "columns_index.hpp"
 #include "device_buffer.hpp"
 #include "field_sample.hpp"
+#include "handle_counters.hpp"
 #include "handle_order.hpp"
 #include "voxel_grid.hpp"
 
@@ -51,23 +51,6 @@ __device__ inline float columns_height(int32_t top, bool free_above, float d0, f
 
 // +0.0f for a minimum that compares equal to zero, the canonical NaN for none
 __device__ inline float columns_min_out(float m) { return m != m ? columns_nan() : m == 0.0f ? 0.0f : m; }
-
-// K per-lane counts of a workgroup of 256 into words[first .. first + K): wave sums by shuffles, the four waves through LDS, one integer
-// atomic per counter and workgroup.  Every lane of the workgroup calls it.  (All the voxels of a grid fit 32 bits: so does every sum.)
-template <int K>
-__device__ inline void columns_block_add(const uint32_t (&counts)[K], unsigned long long *__restrict__ words, uint32_t first) {
-    __shared__ uint32_t totals[K];
-    if (threadIdx.x < K) totals[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < K; c++) {
-        uint32_t v = counts[c];
-        for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor(v, o);
-        if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&totals[c], v);
-    }
-    __syncthreads();
-    if (threadIdx.x < K && totals[threadIdx.x]) atomicAdd(words + first + threadIdx.x, (unsigned long long)totals[threadIdx.x]);
-}
 
 // A lane per cell.  The walk goes in groups of four steps (columns_index.hpp): the weights of a group, then the distances of its observed
 // voxels, and its ESDF values, are loaded before the first of them is used -- no load depends on the running state, so a group has up
@@ -159,7 +142,7 @@ __global__ __launch_bounds__(256) void columns_walk_kernel(const ColumnsView f, 
         r.min_distance = columns_min_out(m);
         rows[cell] = r;
     }
-    columns_block_add(counts, words, kWordUnknown);
+    block_counts_add(counts, words, kWordUnknown);
 }
 
 // Rule 6, a lane per cell: the cell's own top and headroom, and the tops of the four neighbours inside the map.
@@ -186,7 +169,7 @@ __global__ __launch_bounds__(256) void columns_classify_kernel(const tsdf_column
         counts[1] = cls == TSDF_CELL_TRAVERSABLE;
         counts[2] = cls == TSDF_CELL_BLOCKED;
     }
-    columns_block_add(counts, words, kWordNoGround);
+    block_counts_add(counts, words, kWordNoGround);
 }
 
 }  // namespace tsdf
@@ -197,10 +180,9 @@ struct tsdf_columns : HandleOrder {
     int projected;          // the rows are a projection's of the shape s
     ColumnsShape s;
     tsdf_column *rows;      // one per cell
-    unsigned long long *words;        // kColumnWords counters on the device
-    size_t rows_cap, words_cap;
-    unsigned long long *host_words;   // pinned: where they land
-    tsdf_columns_info info;           // (the totals are filled from host_words by whoever has waited)
+    size_t rows_cap;
+    CounterBlock<unsigned long long, kColumnWords> words;   // (handle_counters.hpp)
+    tsdf_columns_info info;           // (the totals are filled from words.host by whoever has waited)
 };
 
 namespace {
@@ -209,8 +191,8 @@ constexpr const char *kColumnsOrder = "columns stream order", *kColumnsEvent = "
 
 void columns_free(tsdf_columns *s) {
     s->destroy();
-    device_free_all(s->rows, s->words);
-    (void)hipHostFree(s->host_words);
+    device_free_all(s->rows);
+    s->words.release();
     delete s;
 }
 
@@ -244,12 +226,11 @@ int classify_on(tsdf_columns *s, uint32_t max_step, uint32_t min_headroom, uint8
     if (rc != TSDF_OK) return rc;
     s->info.max_step = max_step;
     s->info.min_headroom = min_headroom;
-    TSDF_HIP(hipMemsetAsync(s->words + kWordNoGround, 0, 3 * sizeof(unsigned long long), stream), "columns classify counts reset");
+    TSDF_HIP(s->words.reset(s->words.dev + kWordNoGround, 3, stream), "columns classify counts reset");
     hipLaunchKernelGGL(columns_classify_kernel, dim3((unsigned)((columns_cells(s->s) + 255) / 256)), dim3(256), 0, stream, s->rows, s->s.U, s->s.V, max_step,
-                       min_headroom, device_cells, s->words);
+                       min_headroom, device_cells, s->words.dev);
     TSDF_HIP(hipGetLastError(), "columns classify kernel failed");
-    TSDF_HIP(hipMemcpyAsync(s->host_words + kWordNoGround, s->words + kWordNoGround, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream),
-             "columns classify counts download");
+    TSDF_HIP(s->words.download(s->words.dev + kWordNoGround, 3, stream), "columns classify counts download");
     return s->leave(stream, kColumnsEvent);
 }
 
@@ -258,23 +239,10 @@ int classify_on(tsdf_columns *s, uint32_t max_step, uint32_t min_headroom, uint8
 extern "C" {
 
 int tsdf_columns_create(tsdf_columns **out) {
-    TSDF_REQUIRE(out, "tsdf_columns_create: null argument");
-    *out = nullptr;
-    tsdf_columns *s = new (std::nothrow) tsdf_columns();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    hipError_t e = s->create();
-    if (e == hipSuccess) e = device_reserve(s->words, s->words_cap, (size_t)kColumnWords);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->host_words, kColumnWords * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        columns_free(s);
-        return hip_fail(e, "columns alloc failed");
-    }
-    for (int k = 0; k < kColumnWords; k++) s->host_words[k] = 0;
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_columns_create", "columns alloc failed", [](tsdf_columns *s) {
+        const hipError_t e = s->create();
+        return e == hipSuccess ? s->words.create() : e;
+    }, columns_free);
 }
 
 void tsdf_columns_destroy(tsdf_columns *s) {
@@ -297,15 +265,8 @@ int tsdf_volume_project_columns(const tsdf_volume *cv, uint32_t axis, uint32_t l
                  "%s: the band [%u, %u) is empty or leaves axis %u of %u x %u x %u (hi == 0: the axis' end), or the axis is longer than %u voxels", who, lo, hi,
                  axis, g.X, g.Y, g.Z, kColumnsMaxAxis);
     const float *esdf_array = nullptr;
-    if (esdf) {   // (the check of reach.hip)
-        tsdf_esdf_info ei;
-        rc = tsdf_esdf_get_info(esdf, &ei);   // (waits for a computation in flight; it is on the volume's stream anyway)
-        if (rc == TSDF_OK) rc = tsdf_esdf_buffer(esdf, &esdf_array);
-        if (rc != TSDF_OK) return rc;
-        TSDF_REQUIRE(esdf_array, "%s: the ESDF handle has never been computed (tsdf_volume_compute_esdf)", who);
-        TSDF_REQUIRE(same_geometry(geometry_of(ei), g), "%s: the ESDF was computed for another geometry (%u x %u x %u, or other voxel sizes or offset) than the volume's",
-                     who, ei.size[0], ei.size[1], ei.size[2]);
-    }
+    rc = esdf_array_checked(who, esdf, g, &esdf_array);
+    if (rc != TSDF_OK) return rc;
     hipStream_t stream = v->stream;
     rc = s->join(stream, kColumnsOrder);
     if (rc != TSDF_OK) return rc;
@@ -326,11 +287,11 @@ int tsdf_volume_project_columns(const tsdf_volume *cv, uint32_t axis, uint32_t l
     s->info.map_axes[0] = shape.au;
     s->info.map_axes[1] = shape.av;
 
-    TSDF_HIP(hipMemsetAsync(s->words, 0, kColumnWords * sizeof(unsigned long long), stream), "columns counts reset");
+    TSDF_HIP(s->words.reset(stream), "columns counts reset");
     const ColumnsView f = {v->dist, {v->weight, v->wpacked, v->wmode}, esdf_array, shape};
-    launch_walk(f, n_cells, s->rows, s->words, stream);
+    launch_walk(f, n_cells, s->rows, s->words.dev, stream);
     TSDF_HIP(hipGetLastError(), "columns kernel failed");
-    TSDF_HIP(hipMemcpyAsync(s->host_words, s->words, kColumnWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "columns counts download");
+    TSDF_HIP(s->words.download(stream), "columns counts download");
     rc = s->leave(stream, kColumnsEvent);
     if (rc != TSDF_OK) return rc;
     s->projected = 1;
@@ -343,13 +304,13 @@ int tsdf_columns_get_info(const tsdf_columns *s, tsdf_columns_info *info) {
     if (rc != TSDF_OK) return rc;
     *info = s->info;
     if (s->projected) {
-        info->n_unknown = s->host_words[kWordUnknown];
-        info->n_free = s->host_words[kWordFree];
-        info->n_occupied = s->host_words[kWordOccupied];
-        info->n_ground = s->host_words[kWordGround];
-        info->n_no_ground = s->host_words[kWordNoGround];
-        info->n_traversable = s->host_words[kWordTraversable];
-        info->n_blocked = s->host_words[kWordBlocked];
+        info->n_unknown = s->words.host[kWordUnknown];
+        info->n_free = s->words.host[kWordFree];
+        info->n_occupied = s->words.host[kWordOccupied];
+        info->n_ground = s->words.host[kWordGround];
+        info->n_no_ground = s->words.host[kWordNoGround];
+        info->n_traversable = s->words.host[kWordTraversable];
+        info->n_blocked = s->words.host[kWordBlocked];
     }
     return TSDF_OK;
 }
@@ -374,7 +335,7 @@ int tsdf_columns_download(const tsdf_columns *s, tsdf_column *host_rows) {
 
 int tsdf_columns_scratch_bytes(const tsdf_columns *s, uint64_t *bytes) {
     TSDF_REQUIRE(s && bytes, "tsdf_columns_scratch_bytes: null argument");
-    *bytes = (uint64_t)s->rows_cap * sizeof(tsdf_column) + (uint64_t)s->words_cap * sizeof(unsigned long long);
+    *bytes = (uint64_t)s->rows_cap * sizeof(tsdf_column) + s->words.device_bytes();
     return TSDF_OK;
 }
 

@@ -15,6 +15,7 @@
 // One writer per word, no float atomics: the array is the same on every run.  Nothing of the volume is written.
 #include "common.hpp"
 #include "field_sample.hpp"
+#include "handle_counters.hpp"
 #include "handle_order.hpp"
 #include "voxel_grid.hpp"
 
@@ -194,24 +195,14 @@ int esdf_sample_check(const tsdf_esdf *s, uint64_t n, const float *points, const
 extern "C" {
 
 int tsdf_esdf_create(tsdf_esdf **out) {
-    TSDF_REQUIRE(out, "tsdf_esdf_create: null argument");
-    *out = nullptr;
-    tsdf_esdf *s = new (std::nothrow) tsdf_esdf();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    std::memset(s, 0, sizeof(*s));
-    hipError_t e = s->create();
-    if (e == hipSuccess) e = hipMalloc((void **)&s->aux, sizeof(EsdfAux));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->n_sites_host, sizeof(unsigned long long), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        esdf_free(s);
-        return hip_fail(e, "esdf alloc failed");
-    }
-    *s->n_sites_host = 0;
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_esdf_create", "esdf alloc failed", [](tsdf_esdf *s) {
+        std::memset(s, 0, sizeof(*s));
+        hipError_t e = s->create();
+        if (e == hipSuccess) e = hipMalloc((void **)&s->aux, sizeof(EsdfAux));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s->n_sites_host, sizeof(unsigned long long), hipHostMallocDefault);
+        if (e == hipSuccess) *s->n_sites_host = 0;
+        return e;
+    }, esdf_free);
 }
 
 void tsdf_esdf_destroy(tsdf_esdf *s) {

@@ -8,8 +8,6 @@
 //   mask_count_kernel        the set bits, by popcount and a wave sum, one integer atomic per wave that has any
 // Every result is a set, an integer sum, a minimum or a maximum: two runs give the same bytes whatever order the waves run in.  No float
 // atomics, no lane waits for another, and every loop has a stated bound.
-#include <new>
-
 #include "common.hpp"
 #include "explore_walk.hpp"
 #include "field_sample.hpp"
@@ -167,9 +165,9 @@ int gain_on(tsdf_volume *v, tsdf_explorer *s, uint64_t n, const float *origins, 
         hipLaunchKernelGGL(view_gain_kernel, grid_for(n, 256), dim3(256), 0, stream, f, n, origins, directions, t_max, unknown, free_out, stop, s->gain_mask);
     }
     if (host_gain) {
-        TSDF_HIP(hipMemsetAsync(s->words + kWordGain, 0, sizeof(unsigned long long), stream), "view gain count reset");
-        hipLaunchKernelGGL(mask_count_kernel, grid_for(n_words, 256), dim3(256), 0, stream, (uint32_t)n_words, s->gain_mask, s->words);
-        TSDF_HIP(hipMemcpyAsync(s->host_words + kWordGain, s->words + kWordGain, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "view gain count download");
+        TSDF_HIP(s->words.reset(s->words.dev + kWordGain, 1, stream), "view gain count reset");
+        hipLaunchKernelGGL(mask_count_kernel, grid_for(n_words, 256), dim3(256), 0, stream, (uint32_t)n_words, s->gain_mask, s->words.dev);
+        TSDF_HIP(s->words.download(s->words.dev + kWordGain, 1, stream), "view gain count download");
     }
     TSDF_HIP(hipGetLastError(), "view gain kernels failed");
     rc = s->leave(stream);
@@ -177,7 +175,7 @@ int gain_on(tsdf_volume *v, tsdf_explorer *s, uint64_t n, const float *origins, 
     if (host_gain) {
         TSDF_HIP(hipStreamSynchronize(stream), "view gain count");
         s->pending = 0;
-        *host_gain = s->host_words[kWordGain];
+        *host_gain = s->words.host[kWordGain];
     }
     return TSDF_OK;
 }
@@ -187,20 +185,7 @@ int gain_on(tsdf_volume *v, tsdf_explorer *s, uint64_t n, const float *origins, 
 extern "C" {
 
 int tsdf_explorer_create(tsdf_explorer **out) {
-    TSDF_REQUIRE(out, "tsdf_explorer_create: null argument");
-    *out = nullptr;
-    tsdf_explorer *s = new (std::nothrow) tsdf_explorer();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    const hipError_t e = s->create(&kExplorerText);
-    if (e != hipSuccess) {
-        explorer_free(s);
-        return hip_fail(e, "explorer alloc failed");
-    }
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_explorer_create", "explorer alloc failed", [](tsdf_explorer *s) { return s->create(&kExplorerText); }, explorer_free);
 }
 
 void tsdf_explorer_destroy(tsdf_explorer *s) {
@@ -222,13 +207,13 @@ int tsdf_volume_find_frontiers(const tsdf_volume *cv, uint32_t flags, tsdf_explo
         adopt_geometry(s, v->g);
         s->info.connectivity = 0;
         s->info.n_unknown = s->info.n_free = s->info.n_occupied = s->info.n_frontiers = s->info.n_clusters = s->info.n_listed_clusters = 0;
-        voxel_flag(FrontierFlag{v->dist, {v->weight, v->wpacked, v->wmode}}, grid, n_chunks, s->masks, s->bases, s->words, stream);
+        voxel_flag(FrontierFlag{v->dist, {v->weight, v->wpacked, v->wmode}}, grid, n_chunks, s->masks, s->bases, s->words.dev, stream);
         return TSDF_OK;
     }, &n_list);
     if (rc != TSDF_OK) return rc;
-    s->info.n_unknown = s->host_words[kWordUnknown];
-    s->info.n_free = s->host_words[kWordFree];
-    s->info.n_occupied = s->host_words[kWordOccupied];
+    s->info.n_unknown = s->words.host[kWordUnknown];
+    s->info.n_free = s->words.host[kWordFree];
+    s->info.n_occupied = s->words.host[kWordOccupied];
     s->info.n_frontiers = n_list;
     if (n_list) {
         TSDF_HIP(hipGetLastError(), "frontier list kernel failed");
@@ -287,7 +272,7 @@ int tsdf_explorer_cluster_frontiers(tsdf_explorer *s, uint32_t connectivity, uin
         return TSDF_OK;
     }
     // (a find_frontiers zeroes every word; a second clustering of its list counts the roots again)
-    TSDF_HIP(hipMemsetAsync(s->words + FrontierSet::kWordRoots, 0, sizeof(unsigned long long), stream), "frontier cluster count reset");
+    TSDF_HIP(s->words.reset(s->words.dev + FrontierSet::kWordRoots, 1, stream), "frontier cluster count reset");
     uint64_t n_roots = 0, n_rows = 0;
     rc = voxel_set_cluster(s, AnyListedNeighbour{}, (uint32_t)n64, connectivity, min_size, stream, &n_roots, &n_rows);
     if (rc != TSDF_OK) return rc;

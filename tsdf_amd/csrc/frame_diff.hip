@@ -4,10 +4,8 @@
 //
 // Compare: DiffFlag, the state of a pixel (frame_diff_index.hpp) on two coalesced uint16 loads, five counters, the frame copied and the
 // state stored on the way.  The flag walk, the chunk scan and the list are voxel_set.hpp's over a W x H x 1 grid.
-// Cluster: voxel_set.hpp's clustering (voxel_set_cluster_with: hook, flatten, keep, scan, rows) with the policy NearInDepth; the blob row
-// has a 2-D box and depth extremes, so the init and the stats kernel it is given are this file's:
-//   diff_init_kernel      parent[i] = i, the accumulator rows emptied
-//   diff_stats_kernel     size, box, depth extremes and the three sums to the root's row, integer atomics, one set per wave and root
+// Cluster: voxel_set.hpp's clustering (voxel_set_cluster) with the policy NearInDepth: the blob row has a 2-D box and depth extremes, so
+// the policy's three values are x, y and the depth.
 // Mask:
 //   diff_paint_kernel     a wave per 64 pixel ids: pixel -> list index -> label -> kept row; the row to blob_index, the kept bit by ballot
 //   diff_dilate_kernel    a 64 x 16 tile: the row window of every tile row and the `dilate` rows above and below as an any-bit test on a
@@ -15,7 +13,6 @@
 // Every result is a set, an integer sum, a minimum or a maximum: two runs give the same bytes whatever order the waves run in.  No float
 // atomics, no lane waits for another, and every loop has a stated bound.
 #include <algorithm>
-#include <new>
 
 #include "common.hpp"
 #include "frame_diff_index.hpp"
@@ -48,81 +45,43 @@ struct DiffFlag {
     }
 };
 
-// listed neighbours are adjacent when their frame depths differ by at most `step`
+// listed neighbours are adjacent when their frame depths differ by at most `step`; the row's values are x, y and the depth (each at
+// most 65535)
 struct NearInDepth {
     using Row = tsdf_diff_blob;
+    static constexpr int kSummed = 0;
     const uint16_t *depth;   // the handle's copy of the frame
     uint32_t step;
+    __device__ static void clear(Row &r) {
+        r.lo[0] = r.lo[1] = 0xffffffffu;
+        r.hi[0] = r.hi[1] = 0;
+        r.min_depth = 0xffffffffu;
+        r.max_depth = 0;
+        r.sum_x = r.sum_y = r.sum_depth = 0;
+    }
     __device__ uint32_t word(uint32_t id) const { return depth[id]; }
     __device__ bool adjacent(uint32_t own, uint32_t id2) const {
         const uint32_t d = depth[id2];
         return (d > own ? d - own : own - d) <= step;
     }
-};
-
-__global__ __launch_bounds__(256) void diff_init_kernel(const uint32_t n_list, uint32_t *__restrict__ parent, tsdf_diff_blob *__restrict__ acc) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_list) return;
-    parent[i] = (uint32_t)i;
-    tsdf_diff_blob &r = acc[i];
-    r.label = (uint32_t)i;
-    r.size = 0;
-    r.lo[0] = r.lo[1] = 0xffffffffu;
-    r.hi[0] = r.hi[1] = 0;
-    r.min_depth = 0xffffffffu;
-    r.max_depth = 0;
-    r.sum_x = r.sum_y = r.sum_depth = 0;
-}
-
-// voxel_stats_kernel's scheme on the blob row: the wave takes its distinct roots in turn, the lanes of a root reduce among themselves
-// and the root's first lane adds the result.  Bounded: at most 64 trips, every trip retires its leading lane.  (x, y and the depth are
-// at most 65535: a wave's sums fit 32 bits.)  v[0], v[1], v[2]: x, y, depth.
-__global__ __launch_bounds__(256) void diff_stats_kernel(const uint32_t n_list, const uint32_t *__restrict__ list, const uint32_t *__restrict__ labels,
-                                                         const uint16_t *__restrict__ depth, const uint32_t width, tsdf_diff_blob *__restrict__ acc) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n_list;
-    const uint32_t label = valid ? labels[i] : 0xffffffffu;
-    uint32_t v[3] = {0, 0, 0};
-    if (valid) {
-        const uint32_t id = list[i];
-        v[1] = id / width;
-        v[0] = id - v[1] * width;
+    __device__ void values(uint32_t id, const VoxelGrid &grid, bool, Row &, uint32_t (&v)[3], uint32_t *) const {
+        v[1] = id / grid.X;
+        v[0] = id - v[1] * grid.X;
         v[2] = depth[id];
     }
-    uint64_t remaining = __ballot(valid);
-    for (int trip = 0; trip < 64 && remaining; trip++) {
-        const int first = __ffsll((unsigned long long)remaining) - 1;
-        const uint32_t lead = __shfl(label, first);
-        const bool mine = valid && label == lead;
-        const uint64_t same = __ballot(mine);
-        uint32_t lo[3], hi[3], sum[3];
-        for (int k = 0; k < 3; k++) {
-            lo[k] = mine ? v[k] : 0xffffffffu;
-            hi[k] = mine ? v[k] : 0u;
-            sum[k] = mine ? v[k] : 0u;
+    __device__ static void add(Row *row, uint32_t n, const uint32_t *lo, const uint32_t *hi, const uint32_t *sum, const uint32_t *) {
+        atomicAdd(&row->size, n);
+        for (int k = 0; k < 2; k++) {
+            atomicMin(&row->lo[k], lo[k]);
+            atomicMax(&row->hi[k], hi[k]);
         }
-        for (int o = 32; o > 0; o >>= 1)
-            for (int k = 0; k < 3; k++) {
-                lo[k] = min(lo[k], (uint32_t)__shfl_xor(lo[k], o));
-                hi[k] = max(hi[k], (uint32_t)__shfl_xor(hi[k], o));
-                sum[k] += (uint32_t)__shfl_xor(sum[k], o);
-            }
-        if ((int)(threadIdx.x & 63u) == first) {
-            tsdf_diff_blob *row = acc + lead;
-            atomicAdd(&row->size, (uint32_t)__popcll(same));
-            for (int k = 0; k < 2; k++) {
-                atomicMin(&row->lo[k], lo[k]);
-                atomicMax(&row->hi[k], hi[k]);
-            }
-            atomicMin(&row->min_depth, lo[2]);
-            atomicMax(&row->max_depth, hi[2]);
-            atomicAdd((unsigned long long *)&row->sum_x, (unsigned long long)sum[0]);
-            atomicAdd((unsigned long long *)&row->sum_y, (unsigned long long)sum[1]);
-            atomicAdd((unsigned long long *)&row->sum_depth, (unsigned long long)sum[2]);
-        }
-        remaining &= ~same;
+        atomicMin(&row->min_depth, lo[2]);
+        atomicMax(&row->max_depth, hi[2]);
+        atomicAdd((unsigned long long *)&row->sum_x, (unsigned long long)sum[0]);
+        atomicAdd((unsigned long long *)&row->sum_y, (unsigned long long)sum[1]);
+        atomicAdd((unsigned long long *)&row->sum_depth, (unsigned long long)sum[2]);
     }
-}
+};
 
 // what a paint reads of the handle; labels, row_mask and row_base are touched only behind a set mask bit (have_rows: there is a table)
 struct DiffView {
@@ -231,20 +190,7 @@ int blobs_ready(const char *who, const tsdf_frame_diff *s) {
 extern "C" {
 
 int tsdf_frame_diff_create(tsdf_frame_diff **out) {
-    TSDF_REQUIRE(out, "tsdf_frame_diff_create: null argument");
-    *out = nullptr;
-    tsdf_frame_diff *s = new (std::nothrow) tsdf_frame_diff();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    const hipError_t e = s->create(&kDiffText);
-    if (e != hipSuccess) {
-        diff_free(s);
-        return hip_fail(e, "frame diff alloc failed");
-    }
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_frame_diff_create", "frame diff alloc failed", [](tsdf_frame_diff *s) { return s->create(&kDiffText); }, diff_free);
 }
 
 void tsdf_frame_diff_destroy(tsdf_frame_diff *s) {
@@ -293,11 +239,11 @@ int tsdf_frame_diff_compare_device(tsdf_frame_diff *s, const uint16_t *device_fr
         s->g.Y = height;
         s->g.Z = 1;
         voxel_flag(DiffFlag{device_frame, device_model, s->depth, device_states, params->tolerance, params->quadratic}, grid, n_chunks, s->masks,
-                   s->bases, s->words, stream);
+                   s->bases, s->words.dev, stream);
         return TSDF_OK;
     }, &n_list);
     if (rc != TSDF_OK) return rc;
-    for (uint32_t k = 0; k < kDiffStates; k++) info.counts[k] = s->host_words[k];
+    for (uint32_t k = 0; k < kDiffStates; k++) info.counts[k] = s->words.host[k];
     if (n_list) {
         TSDF_HIP(hipGetLastError(), "frame diff list kernel failed");
         rc = s->leave(stream);
@@ -327,17 +273,11 @@ int tsdf_frame_diff_cluster(tsdf_frame_diff *s, uint32_t connectivity, uint32_t 
         return TSDF_OK;
     }
     // (a compare zeroes every word; a second clustering of its list counts the roots again)
-    TSDF_HIP(hipMemsetAsync(s->words + DiffSet::kWordRoots, 0, sizeof(unsigned long long), stream), "frame diff cluster count reset");
+    TSDF_HIP(s->words.reset(s->words.dev + DiffSet::kWordRoots, 1, stream), "frame diff cluster count reset");
     uint64_t n_roots = 0, n_rows = 0;
     // (on a grid one plane deep the hook's forward neighbours at 6 / 26 are the image's at 4 / 8)
-    // voxel_set.hpp's clustering with this file's init and stats kernels (the blob row's fields are not the voxel rows')
-    const uint16_t *depth = s->depth;
-    rc = voxel_set_cluster_with(
-        s, NearInDepth{depth, depth_step}, (uint32_t)n64, connectivity == 4u ? 6u : 26u, std::max(min_pixels, 1u), stream, &n_roots, &n_rows,
-        [&](dim3 lanes, uint32_t n, uint32_t *labels, tsdf_diff_blob *acc) { hipLaunchKernelGGL(diff_init_kernel, lanes, dim3(256), 0, stream, n, labels, acc); },
-        [&](dim3 lanes, uint32_t n, const uint32_t *list, const uint32_t *labels, const VoxelGrid &grid, tsdf_diff_blob *acc) {
-            hipLaunchKernelGGL(diff_stats_kernel, lanes, dim3(256), 0, stream, n, list, labels, depth, grid.X, acc);
-        });
+    rc = voxel_set_cluster(s, NearInDepth{s->depth, depth_step}, (uint32_t)n64, connectivity == 4u ? 6u : 26u, std::max(min_pixels, 1u), stream, &n_roots,
+                           &n_rows);
     if (rc != TSDF_OK) return rc;
     info.n_blobs = n_roots;
     info.n_kept_blobs = n_rows;

@@ -1,7 +1,7 @@
 // The stream order of a handle ("scratch arrays"): the device it was created on, the event recorded behind what was last
 // enqueued on it, and whether anybody has waited for that yet.  Every handle that lives beside a volume begins with one: tsdf_mesh
-// (mesh_handle.hpp), VoxelSet (voxel_set.hpp: tsdf_explorer, tsdf_objects), tsdf_reach, tsdf_esdf and tsdf_snapshot.  A plain struct:
-// all zero is "not created", like every handle here.  The texts of the failures are the caller's, so each handle reports under its own
+// (mesh_handle.hpp), VoxelSet (voxel_set.hpp: tsdf_explorer, tsdf_objects, tsdf_frame_diff), tsdf_reach, tsdf_esdf, tsdf_snapshot,
+// tsdf_columns and tsdf_render.  A plain struct: all zero is "not created", like every handle here.  The texts of the failures are the caller's, so each handle reports under its own
 // name.  Like device_buffer.hpp this includes only the HIP runtime and the public header.
 #pragma once
 

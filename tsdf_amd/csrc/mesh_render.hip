@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "handle_counters.hpp"
 #include "handle_order.hpp"
 #include "mesh_device.hpp"
 #include "mesh_handle.hpp"
@@ -114,18 +115,14 @@ __device__ inline void render_fragment(const RenderTriangle &tri, const RenderVi
     if (key < *word) __hip_atomic_fetch_min(word, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// per workgroup: the lanes' flags counted into LDS by wave, one global atomic per counter that is not zero
-__device__ inline void render_count(uint32_t *lds, int slot, bool flag) {
-    const uint64_t m = __ballot(flag);
-    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(lds + slot, (uint32_t)__popcll(m));
-}
+// the lanes' flags counted by wave into the workgroup's LDS totals (block_counts_*, handle_counters.hpp)
+__device__ inline void render_count(uint32_t *lds, uint32_t slot, bool flag) { block_counts_wave(lds, slot, (uint32_t)__popcll(__ballot(flag))); }
 
 __global__ __launch_bounds__(256) void render_raster_kernel(uint32_t n_vertices, uint32_t n_triangles, const uint32_t *__restrict__ indices,
                                                             const int4 *__restrict__ records, const RenderView view, uint32_t large_box,
                                                             unsigned long long *keys, uint32_t *__restrict__ large_list, unsigned long long *words) {
     __shared__ uint32_t counts[kRenderWords];
-    if (threadIdx.x < kRenderWords) counts[threadIdx.x] = 0;
-    __syncthreads();
+    block_counts_clear(counts);
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     RenderTriangle tri;
@@ -156,11 +153,10 @@ __global__ __launch_bounds__(256) void render_raster_kernel(uint32_t n_vertices,
             }
         }
     }
-    __syncthreads();
-    if (threadIdx.x < kRenderWords && counts[threadIdx.x]) {
-        if (threadIdx.x == kWordError) raise_error((uint64_t *)words + kWordError, kErrorIndex);
-        else atomicAdd(words + threadIdx.x, (unsigned long long)counts[threadIdx.x]);
-    }
+    block_counts_flush(counts, [&](uint32_t k, uint32_t total) {
+        if (k == kWordError) raise_error((uint64_t *)words + kWordError, kErrorIndex);
+        else atomicAdd(words + k, (unsigned long long)total);
+    });
 }
 
 // One wave per listed triangle.  Every index was checked by render_raster_kernel, which listed live triangles only.
@@ -202,8 +198,7 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(uint32_t n_pixels, 
                                                              const float *__restrict__ normals, const uint8_t *__restrict__ rgb, const RenderView view,
                                                              const RenderTargets out, unsigned long long *words) {
     __shared__ uint32_t counts[kRenderWords];
-    if (threadIdx.x < kRenderWords) counts[threadIdx.x] = 0;
-    __syncthreads();
+    block_counts_clear(counts);
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const bool mine = p < n_pixels;
     const unsigned long long key = mine ? keys[p] : ~0ull;
@@ -258,6 +253,7 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(uint32_t n_pixels, 
             }
         }
     }
+    // (its own closing: block_counts_flush over the one counter costs two more SGPRs here, profiles/handle_counters_refactor.txt)
     __syncthreads();
     if (threadIdx.x == kWordHit && counts[kWordHit]) atomicAdd(words + kWordHit, (unsigned long long)counts[kWordHit]);
 }
@@ -270,9 +266,8 @@ struct tsdf_render : tsdf::HandleOrder {
     unsigned long long *keys;    // 8 bytes per pixel
     int4 *records;               // 16 bytes per shared vertex
     uint32_t *large_list;        // the list's length, then 4 bytes per triangle
-    unsigned long long *words;   // kRenderWords: the error word and the counters
-    size_t keys_cap, records_cap, large_list_cap, words_cap;
-    unsigned long long *host_words;   // pinned: where they land
+    size_t keys_cap, records_cap, large_list_cap;
+    CounterBlock<unsigned long long, kRenderWords> words;   // the error word and the counters (handle_counters.hpp)
     uint64_t n_triangles, n_vertices;   // of the last render
     uint32_t large_box;                 // tsdf_render_set_large_box
     int rendered;
@@ -284,8 +279,8 @@ constexpr const char *kRenderOrder = "render stream order", *kRenderEvent = "ren
 
 void render_free(tsdf_render *r) {
     r->destroy();
-    device_free_all(r->keys, r->records, r->large_list, r->words);
-    (void)hipHostFree(r->host_words);
+    device_free_all(r->keys, r->records, r->large_list);
+    r->words.release();
     delete r;
 }
 
@@ -313,13 +308,13 @@ int render_checked(const char *who, const tsdf_render *r, uint64_t n_vertices, u
 
 // the counters of the last render, once somebody has waited; the error word first
 int render_verdict(const char *who, const tsdf_render *r, tsdf_render_info *info) {
-    if (r->rendered && r->host_words[kWordError]) return index_refused(who, r->n_vertices);
+    if (r->rendered && r->words.host[kWordError]) return index_refused(who, r->n_vertices);
     if (info) {
         info->n_triangles = r->n_triangles;
-        info->n_live = r->rendered ? r->host_words[kWordLive] : 0;
-        info->n_dropped = r->rendered ? r->host_words[kWordDropped] : 0;
-        info->n_large = r->rendered ? r->host_words[kWordLarge] : 0;
-        info->n_pixels_hit = r->rendered ? r->host_words[kWordHit] : 0;
+        info->n_live = r->rendered ? r->words.host[kWordLive] : 0;
+        info->n_dropped = r->rendered ? r->words.host[kWordDropped] : 0;
+        info->n_large = r->rendered ? r->words.host[kWordLarge] : 0;
+        info->n_pixels_hit = r->rendered ? r->words.host[kWordHit] : 0;
     }
     return TSDF_OK;
 }
@@ -352,20 +347,20 @@ int render_on(const char *who, tsdf_render *r, uint64_t n_vertices, uint64_t n_i
     r->n_triangles = n_triangles;
     r->n_vertices = n_vertices;
 
-    TSDF_HIP(hipMemsetAsync(r->words, 0, kRenderWords * sizeof(unsigned long long), stream), "render counts reset");
+    TSDF_HIP(r->words.reset(stream), "render counts reset");
     TSDF_HIP(hipMemsetAsync(r->large_list, 0, sizeof(uint32_t), stream), "render list reset");
     TSDF_HIP(hipMemsetAsync(r->keys, 0xff, (size_t)n_pixels * sizeof(unsigned long long), stream), "render keys fill");
     if (n_triangles) {
         hipLaunchKernelGGL(render_project_kernel, grid_for(nv, 256), dim3(256), 0, stream, nv, vertices, view, r->records);
         hipLaunchKernelGGL(render_raster_kernel, grid_for(n_triangles, 256), dim3(256), 0, stream, nv, n_triangles, indices, r->records, view, r->large_box,
-                           r->keys, r->large_list, r->words);
+                           r->keys, r->large_list, r->words.dev);
         const uint32_t large_grid = (n_triangles + 3) / 4 < kLargeGrid ? (n_triangles + 3) / 4 : kLargeGrid;
         hipLaunchKernelGGL(render_large_kernel, dim3(large_grid), dim3(256), 0, stream, nv, indices, r->records, view, r->keys, r->large_list);
     }
     hipLaunchKernelGGL(render_resolve_kernel, grid_for(n_pixels, 256), dim3(256), 0, stream, n_pixels, r->keys, indices, r->records, vertices, normals, rgb, view,
-                       out, r->words);
+                       out, r->words.dev);
     TSDF_HIP(hipGetLastError(), "render kernels failed");
-    TSDF_HIP(hipMemcpyAsync(r->host_words, r->words, kRenderWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), "render counts download");
+    TSDF_HIP(r->words.download(stream), "render counts download");
     rc = r->leave(stream, kRenderEvent);
     if (rc != TSDF_OK) return rc;
     r->rendered = 1;
@@ -408,24 +403,11 @@ int handle_checked(const char *who, const tsdf_render *r, const tsdf_mesh *mesh,
 extern "C" {
 
 int tsdf_render_create(tsdf_render **out) {
-    TSDF_REQUIRE(out, "tsdf_render_create: null argument");
-    *out = nullptr;
-    tsdf_render *r = new (std::nothrow) tsdf_render();
-    if (!r) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    hipError_t e = r->create();
-    if (e == hipSuccess) e = device_reserve(r->words, r->words_cap, (size_t)kRenderWords);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&r->host_words, kRenderWords * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        render_free(r);
-        return hip_fail(e, "render alloc failed");
-    }
-    for (int i = 0; i < kRenderWords; i++) r->host_words[i] = 0;
-    r->large_box = TSDF_RENDER_LARGE_BOX;
-    *out = r;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_render_create", "render alloc failed", [](tsdf_render *r) {
+        r->large_box = TSDF_RENDER_LARGE_BOX;
+        const hipError_t e = r->create();
+        return e == hipSuccess ? r->words.create() : e;
+    }, render_free);
 }
 
 void tsdf_render_destroy(tsdf_render *r) {
@@ -435,7 +417,7 @@ void tsdf_render_destroy(tsdf_render *r) {
 int tsdf_render_scratch_bytes(const tsdf_render *r, uint64_t *bytes) {
     TSDF_REQUIRE(r && bytes, "tsdf_render_scratch_bytes: null argument");
     *bytes = (uint64_t)r->keys_cap * sizeof(unsigned long long) + (uint64_t)r->records_cap * sizeof(int4) + (uint64_t)r->large_list_cap * sizeof(uint32_t) +
-             (uint64_t)r->words_cap * sizeof(unsigned long long);
+             r->words.device_bytes();
     return TSDF_OK;
 }
 

@@ -8,7 +8,6 @@
 // Every result is a set, an integer sum, a minimum or a maximum: two runs give the same bytes whatever order the waves run in.  No float
 // atomics, no lane waits for another, and every loop has a stated bound.
 #include <algorithm>
-#include <new>
 
 #include "common.hpp"
 #include "voxel_set.hpp"
@@ -123,21 +122,10 @@ int lookup_on(const tsdf_objects *cs, uint64_t n, const float *points, uint32_t 
 extern "C" {
 
 int tsdf_objects_create(tsdf_objects **out) {
-    TSDF_REQUIRE(out, "tsdf_objects_create: null argument");
-    *out = nullptr;
-    tsdf_objects *s = new (std::nothrow) tsdf_objects();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    hipError_t e = s->create(&kObjectsText);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->host_select, kMaxSelect, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        objects_free(s);
-        return hip_fail(e, "objects alloc failed");
-    }
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_objects_create", "objects alloc failed", [](tsdf_objects *s) {
+        const hipError_t e = s->create(&kObjectsText);
+        return e == hipSuccess ? hipHostMalloc((void **)&s->host_select, kMaxSelect, hipHostMallocDefault) : e;
+    }, objects_free);
 }
 
 void tsdf_objects_destroy(tsdf_objects *s) {
@@ -183,7 +171,7 @@ int tsdf_volume_find_objects(const tsdf_volume *cv, uint32_t min_votes, const ui
             TSDF_HIP(hipMemcpyAsync(s->select, s->host_select, n_select, hipMemcpyHostToDevice, stream), "objects selection upload");
         }
         voxel_flag(LabelledFlag{v->classes, std::max(min_votes, 1u), host_select ? s->select : nullptr, n_select}, grid, n_chunks, s->masks, s->bases,
-                   s->words, stream);
+                   s->words.dev, stream);
         return TSDF_OK;
     }, &n64);
     if (rc != TSDF_OK) return rc;

@@ -22,8 +22,6 @@
 // and when a round marks nothing every brick is at its local fixed point over final halo values: the global one.  The owner of a voxel
 // is the only writer of its word in a round: no atomics on the cost array, no float atomics anywhere, no grid-wide barrier, no lane or
 // workgroup waits for another, and every loop has a stated bound.
-#include <new>
-
 #include "common.hpp"
 #include "field_sample.hpp"
 #include "voxel_set.hpp"
@@ -409,8 +407,7 @@ struct tsdf_reach : HandleOrder {
     uint32_t *dirty;        // per brick, two parities
     unsigned long long *keys;   // ranking: one packed minimum per table row
     size_t cost_cap, mask_cap, dirty_cap, keys_cap;
-    ReachWords *words;      // on the device
-    ReachWords *host_words; // pinned: where they land
+    CounterBlock<ReachWords> words;   // (handle_counters.hpp)
     tsdf_reach_info info;
 };
 
@@ -418,8 +415,8 @@ namespace {
 
 void reach_free(tsdf_reach *s) {
     s->destroy();
-    device_free_all(s->cost, s->mask, s->dirty, s->keys, s->words);
-    (void)hipHostFree(s->host_words);
+    device_free_all(s->cost, s->mask, s->dirty, s->keys);
+    s->words.release();
     delete s;
 }
 
@@ -445,17 +442,7 @@ int compute_checked(const char *who, const tsdf_volume *v, const tsdf_reach *s, 
     TSDF_REQUIRE((flags & ~(uint32_t)TSDF_REACH_THROUGH_UNKNOWN) == 0, "%s: unknown flags %#x", who, flags);
     TSDF_REQUIRE(clearance >= 0.0f && clearance < INFINITY, "%s: clearance must be finite and >= 0, got %g", who, (double)clearance);
     TSDF_REQUIRE(esdf || clearance == 0.0f, "%s: a clearance (%g) needs an ESDF handle", who, (double)clearance);
-    *esdf_array = nullptr;
-    if (esdf) {
-        tsdf_esdf_info ei;
-        int rc = tsdf_esdf_get_info(esdf, &ei);   // (waits for a computation in flight; it is on the volume's stream anyway)
-        if (rc == TSDF_OK) rc = tsdf_esdf_buffer(esdf, esdf_array);
-        if (rc != TSDF_OK) return rc;
-        TSDF_REQUIRE(*esdf_array, "%s: the ESDF handle has never been computed (tsdf_volume_compute_esdf)", who);
-        TSDF_REQUIRE(same_geometry(geometry_of(ei), v->g), "%s: the ESDF was computed for another geometry (%u x %u x %u, or other voxel sizes or offset) than the volume's", who,
-                     ei.size[0], ei.size[1], ei.size[2]);
-    }
-    return TSDF_OK;
+    return esdf_array_checked(who, esdf, v->g, esdf_array);
 }
 
 // The whole computation on the volume's stream, seeds on the device; returns when the field is final.
@@ -482,9 +469,10 @@ int reach_on(const char *who, tsdf_volume *v, tsdf_reach *s, uint64_t n, const f
     const uint32_t cap = max_cost ? max_cost : 0xFFFFFFFEu;
     const uint32_t faces_only = connectivity == 6u ? 1u : 0u;
 
-    TSDF_HIP(hipMemsetAsync(s->words, 0, sizeof(ReachWords), stream), "reach counts reset");
+    ReachWords *const words = s->words.dev, *const host_words = s->words.host;
+    TSDF_HIP(s->words.reset(stream), "reach counts reset");
     voxel_flag(TraversableFlag{v->dist, {v->weight, v->wpacked, v->wmode}, esdf_array, clearance, (flags & TSDF_REACH_THROUGH_UNKNOWN) ? 1 : 0}, grid,
-               n_chunks, s->mask, nullptr, &s->words->n_traversable, stream);
+               n_chunks, s->mask, nullptr, &words->n_traversable, stream);
     hipLaunchKernelGGL(reach_init_kernel, grid_for(((uint64_t)max(grid.n, n_dirty) + 3) / 4, 256), dim3(256), 0, stream, s->cost, grid.n, s->dirty, n_dirty);
     if (n) hipLaunchKernelGGL(reach_seed_kernel, grid_for(n, 256), dim3(256), 0, stream, v->g, nb, n, seeds, s->mask, s->cost, s->dirty);
     TSDF_HIP(hipGetLastError(), "reach setup kernels failed");
@@ -495,38 +483,38 @@ int reach_on(const char *who, tsdf_volume *v, tsdf_reach *s, uint64_t n, const f
     // steps, and one more round sees nothing change: rounds <= n_traversable + 1, or the call fails rather than loop.
     uint64_t rounds = 0;
     for (bool final = false; !final;) {
-        TSDF_HIP(hipMemsetAsync(s->words->round, 0, sizeof(s->words->round), stream), "reach round words reset");
+        TSDF_HIP(s->words.reset(words->round, kReachMaxBatch, stream), "reach round words reset");
         for (uint32_t r = 0; r < kReachBatch; r++) {
             const uint64_t k = rounds + r;
             hipLaunchKernelGGL(reach_relax_kernel, dim3(nb.n), dim3(256), 0, stream, s->cost, s->mask, grid, nb, faces_only, cap,
-                               s->dirty + (k & 1u) * nb.n, s->dirty + ((k + 1) & 1u) * nb.n, s->words->round + r);
+                               s->dirty + (k & 1u) * nb.n, s->dirty + ((k + 1) & 1u) * nb.n, words->round + r);
         }
         TSDF_HIP(hipGetLastError(), "reach relax kernel failed");
-        TSDF_HIP(hipMemcpyAsync(s->host_words, s->words, sizeof(ReachWords), hipMemcpyDeviceToHost, stream), "reach round words download");
+        TSDF_HIP(s->words.download(stream), "reach round words download");
         TSDF_HIP(hipStreamSynchronize(stream), "reach rounds");
         s->pending = 0;
         uint32_t used = kReachBatch;
         for (uint32_t r = 0; r < kReachBatch; r++)
-            if (s->host_words->round[r] == 0u) {
+            if (host_words->round[r] == 0u) {
                 used = r + 1;
                 final = true;
                 break;
             }
         rounds += used;
-        if (!final && rounds > s->host_words->n_traversable) {
+        if (!final && rounds > host_words->n_traversable) {
             set_error("%s: %llu rounds have not converged on %llu traversable voxels", who, (unsigned long long)rounds,
-                      (unsigned long long)s->host_words->n_traversable);
+                      (unsigned long long)host_words->n_traversable);
             return TSDF_ERR_DEVICE;
         }
     }
-    hipLaunchKernelGGL(reach_stats_kernel, grid_for(grid.n, 256 * 16), dim3(256), 0, stream, s->cost, grid.n, s->words);
+    hipLaunchKernelGGL(reach_stats_kernel, grid_for(grid.n, 256 * 16), dim3(256), 0, stream, s->cost, grid.n, words);
     TSDF_HIP(hipGetLastError(), "reach stats kernel failed");
-    TSDF_HIP(hipMemcpyAsync(s->host_words, s->words, sizeof(ReachWords), hipMemcpyDeviceToHost, stream), "reach counts download");
+    TSDF_HIP(s->words.download(stream), "reach counts download");
     TSDF_HIP(hipStreamSynchronize(stream), "reach counts");
-    s->info.n_traversable = s->host_words->n_traversable;
-    s->info.n_reached = s->host_words->n_reached;
-    s->info.n_seed_voxels = s->host_words->n_seed_voxels;
-    s->info.max_cost_reached = (uint32_t)s->host_words->max_cost_reached;
+    s->info.n_traversable = host_words->n_traversable;
+    s->info.n_reached = host_words->n_reached;
+    s->info.n_seed_voxels = host_words->n_seed_voxels;
+    s->info.max_cost_reached = (uint32_t)host_words->max_cost_reached;
     s->info.rounds = rounds;
     s->computed = 1;
     return TSDF_OK;
@@ -594,24 +582,11 @@ int rank_on(tsdf_reach *s, const RankInput &in, tsdf_reach_cluster *out, hipStre
 extern "C" {
 
 int tsdf_reach_create(tsdf_reach **out) {
-    TSDF_REQUIRE(out, "tsdf_reach_create: null argument");
-    *out = nullptr;
-    tsdf_reach *s = new (std::nothrow) tsdf_reach();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    std::memset(s, 0, sizeof(*s));
-    hipError_t e = s->create();
-    if (e == hipSuccess) e = hipMalloc((void **)&s->words, sizeof(ReachWords));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->host_words, sizeof(ReachWords), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        reach_free(s);
-        return hip_fail(e, "reach alloc failed");
-    }
-    std::memset(s->host_words, 0, sizeof(ReachWords));
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_reach_create", "reach alloc failed", [](tsdf_reach *s) {
+        std::memset(s, 0, sizeof(*s));
+        const hipError_t e = s->create();
+        return e == hipSuccess ? s->words.create() : e;
+    }, reach_free);
 }
 
 void tsdf_reach_destroy(tsdf_reach *s) {
@@ -670,7 +645,7 @@ int tsdf_reach_download(const tsdf_reach *s, uint32_t *host_costs) {
 int tsdf_reach_scratch_bytes(const tsdf_reach *s, uint64_t *bytes) {
     TSDF_REQUIRE(s && bytes, "tsdf_reach_scratch_bytes: null argument");
     *bytes = (uint64_t)s->mask_cap * sizeof(uint64_t) + (uint64_t)s->dirty_cap * sizeof(uint32_t) + (uint64_t)s->keys_cap * sizeof(unsigned long long) +
-             sizeof(ReachWords);
+             s->words.device_bytes();
     return TSDF_OK;
 }
 

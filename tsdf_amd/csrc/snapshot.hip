@@ -21,6 +21,7 @@
 #include "brick_shift.hpp"
 #include "common.hpp"
 #include "field_sample.hpp"
+#include "handle_counters.hpp"
 #include "handle_order.hpp"
 #include "mesh_handle.hpp"
 
@@ -489,23 +490,13 @@ int snapshot_select(const tsdf_snapshot *src, const BrickBox &box, uint32_t flag
 extern "C" {
 
 int tsdf_snapshot_create(tsdf_snapshot **out) {
-    TSDF_REQUIRE(out, "tsdf_snapshot_create: null argument");
-    *out = nullptr;
-    tsdf_snapshot *s = new (std::nothrow) tsdf_snapshot();
-    if (!s) {
-        set_error("out of host memory");
-        return TSDF_ERR_NOMEM;
-    }
-    std::memset(s, 0, sizeof(*s));
-    hipError_t e = s->create();
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->total_host, sizeof(uint64_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        snapshot_free(s);
-        return hip_fail(e, "snapshot alloc failed");
-    }
-    *s->total_host = 0;
-    *out = s;
-    return TSDF_OK;
+    return handle_create(out, "tsdf_snapshot_create", "snapshot alloc failed", [](tsdf_snapshot *s) {
+        std::memset(s, 0, sizeof(*s));
+        hipError_t e = s->create();
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s->total_host, sizeof(uint64_t), hipHostMallocDefault);
+        if (e == hipSuccess) *s->total_host = 0;
+        return e;
+    }, snapshot_free);
 }
 
 void tsdf_snapshot_destroy(tsdf_snapshot *s) {

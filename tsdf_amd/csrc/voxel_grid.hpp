@@ -2,7 +2,7 @@
 // its users explore.hip (frontier voxels), objects.hip (labelled voxels; its lookup reads the masks) and reach.hip (traversable voxels;
 // its seeds, tiles and paths read the mask): voxel (x, y, z) of an X x Y x Z grid has id (z * Y + y) * X + x, 64 consecutive ids are a
 // chunk, and a chunk's 64-bit mask says which of its voxels are listed (compact_index, mesh_device.hpp, turns an id into a list index).
-// The host side of the handles that walk a volume by voxel id, esdf.hip included: which volumes they refuse (whole_volume_checked) and
+// The host side of the handles that walk a volume by voxel id, esdf.hip included: which volumes and ESDFs they refuse (whole_volume_checked, esdf_array_checked) and
 // the geometry they hold and report (geometry_into, geometry_of, same_geometry).
 // And the voxel a world point lies in, which the samplers of the per-voxel words (colour.hip, classes.hip) and objects.hip's lookup share.
 #pragma once
@@ -64,6 +64,21 @@ Geom geometry_of(const Info &info) {
 inline bool same_geometry(const Geom &a, const Geom &b) {
     return a.X == b.X && a.Y == b.Y && a.Z == b.Z && a.vs.x == b.vs.x && a.vs.y == b.vs.y && a.vs.z == b.vs.z && a.offset.x == b.offset.x &&
            a.offset.y == b.offset.y && a.offset.z == b.offset.z;
+}
+
+// What an entry point that reads an optional ESDF beside the volume (reach.hip, columns.hip) refuses, under its own name: a handle that
+// has never been computed, or one computed for another geometry than `g`.  *array: the ESDF's device array, null without a handle.
+inline int esdf_array_checked(const char *who, const tsdf_esdf *esdf, const Geom &g, const float **array) {
+    *array = nullptr;
+    if (!esdf) return TSDF_OK;
+    tsdf_esdf_info ei;
+    int rc = tsdf_esdf_get_info(esdf, &ei);   // (waits for a computation in flight; it is on the volume's stream anyway)
+    if (rc == TSDF_OK) rc = tsdf_esdf_buffer(esdf, array);
+    if (rc != TSDF_OK) return rc;
+    TSDF_REQUIRE(*array, "%s: the ESDF handle has never been computed (tsdf_volume_compute_esdf)", who);
+    TSDF_REQUIRE(same_geometry(geometry_of(ei), g), "%s: the ESDF was computed for another geometry (%u x %u x %u, or other voxel sizes or offset) than the volume's",
+                 who, ei.size[0], ei.size[1], ei.size[2]);
+    return TSDF_OK;
 }
 
 // The voxel a world point lies in, in the frame colour and class words are sampled in (include/tsdf_amd.h, "class fusion", Sampling):

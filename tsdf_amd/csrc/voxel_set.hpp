@@ -1,6 +1,7 @@
 // A set of voxels, flagged, listed and clustered: what explore.hip (frontier voxels, any two listed neighbours
-// adjacent), objects.hip (voxels with class votes, adjacent when their classes are equal) and reach.hip (traversable voxels: the flag
-// walk and its masks only) share.  The user gives the test of one voxel; the chain is the same:
+// adjacent), objects.hip (voxels with class votes, adjacent when their classes are equal), frame_diff.hip (the NEARER pixels of a
+// W x H x 1 grid, adjacent when their depths are close) and reach.hip (traversable voxels: the flag walk and its masks only) share.
+// The user gives the test of one voxel and, for a clustered set, a policy; the chain is the same:
 //   voxel_flag_kernel     the user's Flag per voxel id; per chunk of 64 ids the ballot mask and, for a set that is listed, its popcount;
 //                         the counts over the 64 chunks a wave walks, one integer atomic per counter and workgroup that has any
 //   (the chunk scan of mesh_scan.hip turns the popcounts into bases)
@@ -9,8 +10,8 @@
 //   voxel_init_kernel     parent[i] = i, the accumulator rows emptied
 //   voxel_hook_kernel     the 3 or 13 forward neighbours that are listed and adjacent by the policy, united with the lane's own index
 //   voxel_flatten_kernel  L[i] = root(i) (a launch of its own: the kernel boundary makes every hook visible); roots counted
-//   voxel_stats_kernel    size, coordinate sums and the box (with votes: their sum too), to the root's row with integer atomics, one
-//                         set per wave and root; with votes, the class id stored once, by the root's own lane
+//   voxel_stats_kernel    size and the policy's three values as minimum, maximum and sum (with votes: their sum too), to the root's row
+//                         with integer atomics, one set per wave and root; with votes, the class id stored once, by the root's own lane
 //   voxel_keep_kernel     per 64 list indices: the mask of roots with size >= min_size and its popcount (then the chunk scan)
 //   voxel_rows_kernel     the kept rows, in ascending label, to where compact_index says
 // Every result is a set, an integer sum, a minimum or a maximum: two runs give the same bytes whatever order the waves run in.  No float
@@ -21,6 +22,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "handle_counters.hpp"
 #include "mesh_device.hpp"
 #include "mesh_handle.hpp"
 #include "union_find.hpp"
@@ -28,27 +30,64 @@
 
 namespace tsdf {
 
-// ---- the two policies: the row type, what an empty row clears besides the common fields, the word read once per listed voxel, when a
-// listed neighbour is adjacent (asked only behind its set mask bit), and whether votes and the class id are accumulated ---------------
+// ---- the policies of the clustered sets: the row type; what an empty row holds besides its label and a size of 0; the word read once per
+// listed voxel and when a listed neighbour is adjacent (asked only behind its set mask bit); the three values of a listed id that are
+// reduced to a minimum, a maximum and a sum, and kSummed more that are summed only (the votes); how a wave's result for one root is added
+// to the root's row.  values() is also told whether the lane is its root's own: the one writer of a row's class id.  The third policy,
+// NearInDepth with the blob row, is frame_diff.hip's. ------------------------------------------------------------------------------------
+template <class Row>
+__device__ inline void voxel_row_clear(Row &r) {
+    for (int k = 0; k < 3; k++) {
+        r.lo[k] = 0xffffffffu;
+        r.hi[k] = 0;
+        r.sum[k] = 0;
+    }
+}
+
+template <class Row>
+__device__ inline void voxel_row_add(Row *row, uint32_t n, const uint32_t *lo, const uint32_t *hi, const uint32_t *sum) {
+    atomicAdd(&row->size, n);
+    for (int k = 0; k < 3; k++) {
+        atomicMin(&row->lo[k], lo[k]);
+        atomicMax(&row->hi[k], hi[k]);
+        atomicAdd((unsigned long long *)&row->sum[k], (unsigned long long)sum[k]);
+    }
+}
+
 struct AnyListedNeighbour {
     using Row = tsdf_frontier_cluster;
-    static constexpr bool kVotes = false;
-    __device__ static void clear_more(Row &) {}
+    static constexpr int kSummed = 0;
+    __device__ static void clear(Row &r) { voxel_row_clear(r); }
     __device__ uint32_t word(uint32_t) const { return 0u; }
     __device__ bool adjacent(uint32_t, uint32_t) const { return true; }
+    __device__ void values(uint32_t id, const VoxelGrid &grid, bool, Row &, uint32_t (&v)[3], uint32_t *) const { grid.split(id, v[0], v[1], v[2]); }
+    __device__ static void add(Row *row, uint32_t n, const uint32_t *lo, const uint32_t *hi, const uint32_t *sum, const uint32_t *) {
+        voxel_row_add(row, n, lo, hi, sum);
+    }
 };
 
 struct SameClass {
     using Row = tsdf_class_object;
-    static constexpr bool kVotes = true;
+    static constexpr int kSummed = 1;
     const uint32_t *cls;   // the volume's class words, {votes, class}
-    __device__ static void clear_more(Row &r) {
+    __device__ static void clear(Row &r) {
+        voxel_row_clear(r);
         r.votes = 0;
         r.class_id = 0;
         r.reserved = 0;
     }
     __device__ uint32_t word(uint32_t id) const { return cls[id]; }
     __device__ bool adjacent(uint32_t own_word, uint32_t id2) const { return (cls[id2] & 0xFFFFu) == (own_word & 0xFFFFu); }
+    __device__ void values(uint32_t id, const VoxelGrid &grid, bool own_root, Row &own, uint32_t (&v)[3], uint32_t *votes) const {
+        grid.split(id, v[0], v[1], v[2]);
+        const uint32_t w = cls[id];
+        if (own_root) own.class_id = w & 0xFFFFu;
+        votes[0] = w >> 16;
+    }
+    __device__ static void add(Row *row, uint32_t n, const uint32_t *lo, const uint32_t *hi, const uint32_t *sum, const uint32_t *votes) {
+        voxel_row_add(row, n, lo, hi, sum);
+        atomicAdd((unsigned long long *)&row->votes, (unsigned long long)votes[0]);
+    }
 };
 
 // ---- the flag walk -----------------------------------------------------------------------------------------------------------------
@@ -69,8 +108,7 @@ __global__ __launch_bounds__(256) void voxel_flag_kernel(const Flag flag, const 
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t first = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kFlagChunks;
     __shared__ uint32_t totals[kCounts];
-    if (threadIdx.x < kCounts) totals[threadIdx.x] = 0;
-    __syncthreads();
+    block_counts_clear(totals);
     uint32_t counts[kCounts] = {};   // (at most 64 * kFlagChunks each)
     for (uint32_t k = 0; k < kFlagChunks; k++) {   // bounded: kFlagChunks trips
         if (first + k >= n_chunks) break;   // (the whole wave)
@@ -85,13 +123,8 @@ __global__ __launch_bounds__(256) void voxel_flag_kernel(const Flag flag, const 
 #pragma unroll
         for (uint32_t c = 0; c < kCounts; c++) counts[c] += (uint32_t)__popcll(c == Flag::kListed ? listed : __ballot((bits >> c) & 1u));
     }
-    if (lane == 0) {
-#pragma unroll
-        for (uint32_t c = 0; c < kCounts; c++)
-            if (counts[c]) atomicAdd(&totals[c], counts[c]);
-    }
-    __syncthreads();   // (every lane gets here: the loop is left by break, never by return)
-    if (threadIdx.x < kCounts && totals[threadIdx.x]) atomicAdd(words + threadIdx.x, (unsigned long long)totals[threadIdx.x]);
+    block_counts_wave(totals, counts);
+    block_counts_flush(totals, words, 0);   // (every lane gets here: the loop is left by break, never by return)
 }
 
 // its launch: a workgroup per 4 * kFlagChunks chunks
@@ -120,12 +153,7 @@ __global__ __launch_bounds__(256) void voxel_init_kernel(const uint32_t n_list, 
     typename Policy::Row &r = acc[i];
     r.label = (uint32_t)i;
     r.size = 0;
-    for (int k = 0; k < 3; k++) {
-        r.lo[k] = 0xffffffffu;
-        r.hi[k] = 0;
-        r.sum[k] = 0;
-    }
-    Policy::clear_more(r);
+    Policy::clear(r);
 }
 
 // A lane per listed voxel: its forward neighbours -- the offsets (dx, dy, dz) that come after (0, 0, 0) in the order z, then y, then x,
@@ -165,59 +193,23 @@ static __global__ __launch_bounds__(256) void voxel_flatten_kernel(const uint32_
     if (roots && (threadIdx.x & 63u) == 0) atomicAdd(n_roots, (unsigned long long)__popcll(roots));
 }
 
-// One set of atomics per wave and root: the wave takes its distinct roots in turn, the lanes of a root reduce among themselves (the
-// others hold the neutral values) and the root's first lane adds the result.  Neighbours in the list are neighbours in the grid, so
+// One set of atomics per wave and root (wave_reduce_roots, handle_counters.hpp): the wave takes its distinct roots in turn, the lanes of
+// a root reduce among themselves and the root's first lane adds the result.  Neighbours in the list are neighbours in the grid, so
 // most waves have one root or two; adding lane by lane wherever a wave is mixed queued thousands of atomics on the rows of the large
-// clusters (5 ms at half a million frontiers).  Bounded: at most 64 trips, every trip retires its leading lane.  (A wave's coordinate
-// sum is at most 64 * 65535 and so is its vote sum: both fit 32 bits.)  The class id has one writer, the lane whose list index is the
-// root.
+// clusters (5 ms at half a million frontiers).  (A value is at most 65535 -- a coordinate, a vote count, a depth -- so a wave's sum
+// fits 32 bits.)  The class id has one writer, the lane whose list index is the root.
 template <class Policy>
 __global__ __launch_bounds__(256) void voxel_stats_kernel(const uint32_t n_list, const uint32_t *__restrict__ list, const uint32_t *__restrict__ labels,
                                                           const Policy policy, const VoxelGrid grid, typename Policy::Row *__restrict__ acc) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = i < n_list;
     const uint32_t label = valid ? labels[i] : 0xffffffffu;
-    uint32_t c[3] = {0, 0, 0}, word = 0;
-    if (valid) {
-        const uint32_t id = list[i];
-        grid.split(id, c[0], c[1], c[2]);
-        if constexpr (Policy::kVotes) {
-            word = policy.word(id);
-            if (label == (uint32_t)i) acc[i].class_id = word & 0xFFFFu;
-        }
-    }
-    uint64_t remaining = __ballot(valid);
-    for (int trip = 0; trip < 64 && remaining; trip++) {
-        const int first = __ffsll((unsigned long long)remaining) - 1;
-        const uint32_t lead = __shfl(label, first);
-        const bool mine = valid && label == lead;
-        const uint64_t same = __ballot(mine);
-        uint32_t lo[3], hi[3], sum[3], votes = mine ? word >> 16 : 0u;
-        for (int k = 0; k < 3; k++) {
-            lo[k] = mine ? c[k] : 0xffffffffu;
-            hi[k] = mine ? c[k] : 0u;
-            sum[k] = mine ? c[k] : 0u;
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            for (int k = 0; k < 3; k++) {
-                lo[k] = min(lo[k], (uint32_t)__shfl_xor(lo[k], o));
-                hi[k] = max(hi[k], (uint32_t)__shfl_xor(hi[k], o));
-                sum[k] += (uint32_t)__shfl_xor(sum[k], o);
-            }
-            if constexpr (Policy::kVotes) votes += (uint32_t)__shfl_xor(votes, o);
-        }
-        if ((int)(threadIdx.x & 63u) == first) {
-            typename Policy::Row *row = acc + lead;
-            atomicAdd(&row->size, (uint32_t)__popcll(same));
-            for (int k = 0; k < 3; k++) {
-                atomicMin(&row->lo[k], lo[k]);
-                atomicMax(&row->hi[k], hi[k]);
-                atomicAdd((unsigned long long *)&row->sum[k], (unsigned long long)sum[k]);
-            }
-            if constexpr (Policy::kVotes) atomicAdd((unsigned long long *)&row->votes, (unsigned long long)votes);
-        }
-        remaining &= ~same;
-    }
+    uint32_t v[3] = {0, 0, 0}, more[Policy::kSummed ? Policy::kSummed : 1] = {};
+    if (valid) policy.values(list[i], grid, label == (uint32_t)i, acc[i], v, more);
+    wave_reduce_roots<3, Policy::kSummed>(valid, label, v, more,
+                                          [&](uint32_t lead, uint32_t n, const uint32_t *lo, const uint32_t *hi, const uint32_t *sum, const uint32_t *summed) {
+                                              Policy::add(acc + lead, n, lo, hi, sum, summed);
+                                          });
 }
 
 template <class Row>
@@ -248,7 +240,7 @@ struct VoxelSetText {
     const char *cluster_alloc, *cluster_kernels, *cluster_download, *cluster_count, *table_alloc, *rows_kernel;   // voxel_set_cluster
 };
 
-// What the two listed sets' handles have in common.  The flag kernel fills the first kFlagWords of the kWords counter words, the set's size last;
+// What the listed sets' handles (tsdf_explorer, tsdf_objects, tsdf_frame_diff) have in common.  The flag kernel fills the first kFlagWords of the kWords counter words, the set's size last;
 // then come the roots and the total of the last chunk scan.  Plain data: a handle is value-initialised to zero, then create()d.
 template <class RowType, uint32_t kFlagWords, uint32_t kWords>
 struct VoxelSet : HandleOrder {
@@ -267,23 +259,19 @@ struct VoxelSet : HandleOrder {
     uint32_t *row_bases;
     Row *rows;              // the table
     size_t masks_cap, bases_cap, parts_cap, list_cap, labels_cap, acc_cap, row_masks_cap, row_bases_cap, rows_cap;
-    unsigned long long *words;        // kWords device words
-    unsigned long long *host_words;   // pinned: where they land
+    CounterBlock<unsigned long long, kWords> words;   // (handle_counters.hpp)
 
     hipError_t create(const VoxelSetText *names) {
         text = names;
-        hipError_t e = HandleOrder::create();
-        if (e == hipSuccess) e = hipMalloc((void **)&words, kWords * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&host_words, kWords * sizeof(unsigned long long), hipHostMallocDefault);
-        if (e == hipSuccess) std::memset(host_words, 0, kWords * sizeof(unsigned long long));
-        return e;
+        const hipError_t e = HandleOrder::create();
+        return e == hipSuccess ? words.create() : e;
     }
 
     // waits for what is in flight, then frees everything above (a half-created handle too)
     void release() {
         destroy();
-        device_free_all(masks, bases, parts, list, labels, acc, row_masks, row_bases, rows, words);
-        (void)hipHostFree(host_words);
+        device_free_all(masks, bases, parts, list, labels, acc, row_masks, row_bases, rows);
+        words.release();
     }
 
     // the handle's stream order (handle_order.hpp), under the user's texts
@@ -295,14 +283,14 @@ struct VoxelSet : HandleOrder {
     uint64_t scratch_bytes() const {
         return (uint64_t)masks_cap * sizeof(uint64_t) + (uint64_t)bases_cap * sizeof(uint32_t) + (uint64_t)parts_cap * sizeof(uint64_t) +
                (uint64_t)acc_cap * sizeof(Row) + (uint64_t)row_masks_cap * sizeof(uint64_t) + (uint64_t)row_bases_cap * sizeof(uint32_t) +
-               kWords * sizeof(unsigned long long);
+               words.device_bytes();
     }
 };
 
 // The list of a grid's voxels that flag(n_chunks) -- the user's voxel_flag launch, behind whatever it has to do once the scratch is
 // there -- marks in s->masks and counts in s->bases and s->words: the chunk scan, the one synchronisation (the list is sized from the
-// count), the list.  *n_list is also s->host_words[kWordTotal], and the flag kernel's words are in s->host_words.  Joining and leaving are the
-// caller's.
+// count), the list.  *n_list is also s->words.host[kWordTotal], and the flag kernel's words are in s->words.host.  Joining and leaving are
+// the caller's.
 template <class Set, class Flag>
 int voxel_set_list(Set *s, const char *who, const char *noun, const VoxelGrid &grid, hipStream_t stream, Flag flag, uint64_t *n_list) {
     const VoxelSetText &t = *s->text;
@@ -311,17 +299,17 @@ int voxel_set_list(Set *s, const char *who, const char *noun, const VoxelGrid &g
     if (e == hipSuccess) e = device_reserve(s->bases, s->bases_cap, (size_t)n_chunks);
     if (e == hipSuccess) e = device_reserve(s->parts, s->parts_cap, 2 * ((size_t)n_parts + 1));   // (a list has no more chunks than its grid)
     if (e != hipSuccess) return hip_fail(e, t.scratch_alloc);
-    TSDF_HIP(hipMemsetAsync(s->words, 0, Set::kCounterWords * sizeof(unsigned long long), stream), t.counts_reset);
+    TSDF_HIP(s->words.reset(stream), t.counts_reset);
     const int rc = flag(n_chunks);
     if (rc != TSDF_OK) return rc;
     mesh_scan(ArrayCounts{s->bases, n_chunks, nullptr, 0}, n_parts, s->parts, stream);
     TSDF_HIP(hipGetLastError(), t.count_kernels);
-    TSDF_HIP(hipMemcpyAsync(s->host_words, s->words, (Set::kWordCounted + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), t.counts_download);
-    TSDF_HIP(hipMemcpyAsync(s->host_words + Set::kWordTotal, s->parts + 2 * (size_t)n_parts, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), t.counts_download);
+    TSDF_HIP(s->words.download(s->words.dev, Set::kWordCounted + 1, stream), t.counts_download);
+    TSDF_HIP(hipMemcpyAsync(s->words.host + Set::kWordTotal, s->parts + 2 * (size_t)n_parts, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), t.counts_download);
     TSDF_HIP(hipStreamSynchronize(stream), t.count);
     s->pending = 0;
-    *n_list = s->host_words[Set::kWordTotal];
-    const uint64_t counted = s->host_words[Set::kWordCounted];
+    *n_list = s->words.host[Set::kWordTotal];
+    const uint64_t counted = s->words.host[Set::kWordCounted];
     if (*n_list != counted) {
         set_error("%s: the scan's total (%llu) is not the counted %s (%llu)", who, (unsigned long long)*n_list, noun, (unsigned long long)counted);
         return TSDF_ERR_DEVICE;
@@ -337,11 +325,9 @@ int voxel_set_list(Set *s, const char *who, const char *noun, const VoxelGrid &g
 // The list's n_list > 0 voxels, of the grid of s->g, into connected sets: labels, the roots counted behind whatever s->words holds at
 // kWordRoots, one synchronisation (the table is sized from the count), and the rows of at least min_size voxels.  Leaves the handle
 // with the rows in flight where there are any; joining is the caller's.
-// init(lanes, n_list, labels, acc) and stats(lanes, n_list, list, labels, grid, acc) launch the two kernels that know the row's fields:
-// voxel_set_cluster below gives voxel_init_kernel and voxel_stats_kernel; a user whose row has other fields (frame_diff.hip) gives its own.
-template <class Policy, class Set, class Init, class Stats>
-int voxel_set_cluster_with(Set *s, const Policy policy, uint32_t n_list, uint32_t connectivity, uint32_t min_size, hipStream_t stream, uint64_t *n_roots,
-                           uint64_t *n_rows, Init init, Stats stats) {
+template <class Policy, class Set>
+int voxel_set_cluster(Set *s, const Policy policy, uint32_t n_list, uint32_t connectivity, uint32_t min_size, hipStream_t stream, uint64_t *n_roots,
+                      uint64_t *n_rows) {
     using Row = typename Set::Row;
     static_assert(std::is_same<Row, typename Policy::Row>::value, "the policy's rows are the handle's");
     const VoxelSetText &t = *s->text;
@@ -353,19 +339,20 @@ int voxel_set_cluster_with(Set *s, const Policy policy, uint32_t n_list, uint32_
     if (e != hipSuccess) return hip_fail(e, t.cluster_alloc);
     const VoxelGrid grid = voxel_grid(s->g);
     const dim3 lanes = grid_for(n_list, 256), chunk_grid((n_chunks + 3) / 4);
-    init(lanes, n_list, s->labels, s->acc);
+    unsigned long long *const roots = s->words.dev + Set::kWordRoots;
+    hipLaunchKernelGGL(voxel_init_kernel<Policy>, lanes, dim3(256), 0, stream, n_list, s->labels, s->acc);
     hipLaunchKernelGGL(voxel_hook_kernel<Policy>, lanes, dim3(256), 0, stream, n_list, s->list, s->masks, s->bases, policy, grid, connectivity, s->labels);
-    hipLaunchKernelGGL(voxel_flatten_kernel, lanes, dim3(256), 0, stream, n_list, s->labels, s->words + Set::kWordRoots);
-    stats(lanes, n_list, s->list, s->labels, grid, s->acc);
+    hipLaunchKernelGGL(voxel_flatten_kernel, lanes, dim3(256), 0, stream, n_list, s->labels, roots);
+    hipLaunchKernelGGL(voxel_stats_kernel<Policy>, lanes, dim3(256), 0, stream, n_list, s->list, s->labels, policy, grid, s->acc);
     hipLaunchKernelGGL(voxel_keep_kernel<Row>, chunk_grid, dim3(256), 0, stream, n_list, s->labels, s->acc, min_size, n_chunks, s->row_masks, s->row_bases);
     mesh_scan(ArrayCounts{s->row_bases, n_chunks, nullptr, 0}, n_parts, s->parts, stream);
     TSDF_HIP(hipGetLastError(), t.cluster_kernels);
-    TSDF_HIP(hipMemcpyAsync(s->host_words + Set::kWordRoots, s->words + Set::kWordRoots, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream), t.cluster_download);
-    TSDF_HIP(hipMemcpyAsync(s->host_words + Set::kWordTotal, s->parts + 2 * (size_t)n_parts, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), t.cluster_download);
+    TSDF_HIP(s->words.download(roots, 1, stream), t.cluster_download);
+    TSDF_HIP(hipMemcpyAsync(s->words.host + Set::kWordTotal, s->parts + 2 * (size_t)n_parts, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), t.cluster_download);
     TSDF_HIP(hipStreamSynchronize(stream), t.cluster_count);
     s->pending = 0;
-    *n_roots = s->host_words[Set::kWordRoots];
-    *n_rows = s->host_words[Set::kWordTotal];
+    *n_roots = s->words.host[Set::kWordRoots];
+    *n_rows = s->words.host[Set::kWordTotal];
     if (*n_rows) {
         e = device_reserve(s->rows, s->rows_cap, (size_t)*n_rows);
         if (e != hipSuccess) return hip_fail(e, t.table_alloc);
@@ -374,18 +361,6 @@ int voxel_set_cluster_with(Set *s, const Policy policy, uint32_t n_list, uint32_
         return s->leave(stream);
     }
     return TSDF_OK;
-}
-
-template <class Policy, class Set>
-int voxel_set_cluster(Set *s, const Policy policy, uint32_t n_list, uint32_t connectivity, uint32_t min_size, hipStream_t stream, uint64_t *n_roots,
-                      uint64_t *n_rows) {
-    using Row = typename Set::Row;
-    return voxel_set_cluster_with(
-        s, policy, n_list, connectivity, min_size, stream, n_roots, n_rows,
-        [&](dim3 lanes, uint32_t n, uint32_t *labels, Row *acc) { hipLaunchKernelGGL(voxel_init_kernel<Policy>, lanes, dim3(256), 0, stream, n, labels, acc); },
-        [&](dim3 lanes, uint32_t n, const uint32_t *list, const uint32_t *labels, const VoxelGrid &grid, Row *acc) {
-            hipLaunchKernelGGL(voxel_stats_kernel<Policy>, lanes, dim3(256), 0, stream, n, list, labels, policy, grid, acc);
-        });
 }
 
 }  // namespace tsdf
